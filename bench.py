@@ -1,6 +1,6 @@
 """bench.py - correspondences/second of the GMF multimodal-fusion hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--sweep]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--sweep] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -25,6 +25,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
   cpu_baseline - the CPU oracle (a port of the reference's PyTorch CPU path) timed on this host's cores, all cores and 1 thread
   ranks        - per-rank step time and the all-gather's own time (multi-GPU diagnostics)
   sweep        - with --sweep: N = 1000 / 10000, the KITTI shape and the B = 1 latency points (headline unchanged)
+
+--dump-outputs DIR writes the last timed step's results (logits, final_trans, final_labels; the gathered all_logits /
+all_trans too with N > 1 ranks) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -116,6 +119,43 @@ def time_steps(driver, data, steps, warmup):
     return time.perf_counter() - t0, out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def host_outputs(out) -> dict:
+    """The arrays one driver step returns to its caller, on the host: float64 stays float64, everything else becomes float32
+    (labels are 0 / 1).  The gathered arrays of a multi-rank run only when there is more than one rank (else they ARE the
+    local ones)."""
+    import numpy as np
+    names = ["logits", "final_trans", "final_labels"]
+    if out["all_logits"] is not out["logits"]:
+        names += ["all_logits", "all_trans"]
+    res = {}
+    for k in names:
+        v = out.get(k)
+        if v is None:
+            continue
+        v = v.detach().cpu().numpy()
+        res[k] = v if v.dtype == np.float64 else v.astype(np.float32)
+    return res
+
+
+def write_outputs(path: str, arrays: dict) -> None:
+    """DIR/<name>.npy for every array.  Past DUMP_BYTES in all, every array is cut to its share of the budget: a fixed sample of
+    its elements (flat indices from a seeded generator, ascending), the same for the same shapes in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_BYTES - 1024 * len(arrays)          # (room for the .npy headers)
+    for k, a in arrays.items():
+        if total > budget:
+            keep = max(1, int(a.size * budget // total))
+            if keep < a.size:
+                idx = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def launch_ranks(n_ranks: int, argv, rehearsal: bool) -> int:
     """`python bench.py --gpus N` without a launcher: one child process per rank, started BEFORE this process makes any GPU call
     (it never makes one: children are new interpreters, nothing is re-executed in a process that initialised HIP).  Rendezvous on
@@ -167,6 +207,9 @@ def main():
     ap.add_argument("--sweep", action="store_true", help="full sweep: the default size points (N = 1000 / 10000, KITTI shape, B = 1, ragged) plus the "
                                                        "throughput numerics modes and the DGR rows (rank 0, N = 1 GPU)")
     ap.add_argument("--no-sweep", action="store_true", help="headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / "
+                         "float64, at most 64 MB in all (a fixed, seeded sample of every array when more)")
     ap.add_argument("--rehearsal", action="store_true",
                     help="N > 1 ranks on a box with fewer GPUs: ranks share the devices (local_rank %% device_count) and exchange "
                          "through gloo staged over the host.  Exercises the launch line, the sharded step and the JSON line; the "
@@ -227,6 +270,8 @@ def main():
     handle.call("gmf_profile_read", C.byref(ms_total), C.byref(launches))
     handle.call("gmf_profile_enable", 0)
     dt = driver.max_over_ranks(dt)
+    # the last timed step's results on the host, before the diagnostic step below can reuse any device buffer
+    dump = host_outputs(out) if (args.dump_outputs and rank == 0) else None
     # diagnostics outside the timed region: per-rank step time, and one more step with the model / gather split timed by events
     per_rank_ms = driver.gather_floats(t_local / args.steps * 1e3)
     driver.time_steps = True
@@ -315,6 +360,8 @@ def main():
         line["cpu_baseline"], line["parity"] = cpu_baseline(sd, batch, out, N, T, tau)
         if args.kind == "3dmatch":
             line["parity"]["kitti_shape"] = kitti_parity(dev)
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump)
     print(json.dumps(line))
     driver.close()
 

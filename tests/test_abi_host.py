@@ -342,3 +342,29 @@ def test_bench_launches_its_own_ranks_and_refuses_without_devices():
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearsal", "--no-sweep", "--no-cpu-baseline"],
                            capture_output=True, text=True, timeout=300)
         assert r.returncode != 0 and r.stderr.count("needs a HIP device") == 2 and not r.stdout.strip()
+
+
+def test_bench_dump_outputs_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's arrays as float32 / float64 .npy files, whole under the budget; past it every
+    array is cut to a seeded sample of its elements - the same sample in every run, the files together inside the budget."""
+    # (bench sets HSA_ENABLE_IPC_MODE_LEGACY when first imported; the variable is left as it was for the rest of the session)
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    import bench
+    lg, tr = torch.randn(4, 3000), torch.randn(4, 4, 4, dtype=torch.float64)
+    out = {"logits": lg, "final_trans": tr, "final_labels": (lg > 0).float(), "all_logits": lg, "all_trans": tr}
+    arrays = bench.host_outputs(out)
+    assert sorted(arrays) == ["final_labels", "final_trans", "logits"]
+    assert arrays["logits"].dtype == np.float32 and arrays["final_trans"].dtype == np.float64
+    bench.write_outputs(str(tmp_path / "whole"), arrays)
+    assert np.array_equal(np.load(tmp_path / "whole" / "logits.npy"), lg.numpy())
+    assert np.array_equal(np.load(tmp_path / "whole" / "final_trans.npy"), tr.numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40000)
+    for d in ("a", "b"):
+        bench.write_outputs(str(tmp_path / d), arrays)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["final_labels.npy", "final_trans.npy", "logits.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 40000
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert np.array_equal(a, b)
+    assert set(np.load(tmp_path / "a" / "logits.npy").tolist()) <= set(lg.numpy().reshape(-1).tolist())

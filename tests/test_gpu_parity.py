@@ -2270,7 +2270,11 @@ def test_pose_parity_beyond_golden_sizes(sd_full, N):
     """Whole forward at N beyond the golden fixtures, on weights whose classifier bias is raised so that more than S local
     maxima have a positive score.  (With fewer, the reference's seed list runs into the zero-key tie group, whose order
     torch's unstable argsort leaves to its sorting algorithm - DESIGN.md section 2 - and no two implementations need agree.)
-    Seeds identical, final transform within 1e-4 of the oracle."""
+    Seeds identical as a set, final transform within 1e-4 of the oracle.  Their ORDER is the order of the logits, which agree
+    to 1e-4 only, and positive maxima lie closer than that (N = 3000: ranks 140 / 141 carry the same fp32 logit in the oracle,
+    ranks 124 / 125 are 9.3e-6 apart): the seeds are the stable sort of the NMS keys of the HIP path's own logits (exact,
+    section 2's contract, as in test_f16_pose_in_tie_scenes), and at every rank the oracle's key of the HIP seed is the
+    oracle's own key there to within the two logit tolerances, 2e-4 - only seeds that near-tie may trade places."""
     sd = dict(sd_full)
     sd["classification.4.bias"] = sd_full["classification.4.bias"] + 4.0
     m = gmf_amd.PointDSC(in_dim=6, num_layers=12, num_channels=128, num_iterations=10, ratio=0.1,
@@ -2288,7 +2292,16 @@ def test_pose_parity_beyond_golden_sizes(sd_full, N):
     res = m(data)
     assert _maxerr(m.last_logits.cpu(), ref["logits"]) < 1e-4
     _, _, aux = m.pose_head(m.last_features, data["src_keypts"], data["tgt_keypts"], m.last_logits, True, return_aux=True)
-    assert np.array_equal(aux["seeds"][0].cpu().numpy(), ref["seeds"][0].numpy())
+    seeds = aux["seeds"][0].cpu().long()
+    lg = m.last_logits.cpu()
+    hip_is_max = torch.all((lg[:, :, None] >= lg[:, None, :]) | (sdist >= 0.10), dim=-1)
+    expect = torch.sort((lg * hip_is_max)[0], descending=True, stable=True)[1][: int(N * 0.1)]
+    diff = (seeds != expect).nonzero().flatten()[:8].tolist()
+    assert torch.equal(seeds, expect), (diff, seeds[diff].tolist(), expect[diff].tolist())
+    ref_seeds = ref["seeds"][0]
+    assert set(seeds.tolist()) == set(ref_seeds.tolist())
+    ref_keys = (ref["logits"] * is_max)[0]
+    assert _maxerr(ref_keys[seeds], ref_keys[ref_seeds]) < 2e-4
     assert _maxerr(res["final_trans"].cpu(), ref["final_trans"]) < 1e-4
 
 
