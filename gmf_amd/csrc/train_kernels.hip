@@ -698,7 +698,9 @@ k_relu_bwd(const float* __restrict__ dy, const float* __restrict__ y, float* __r
 // =========================================================================================
 // Loss backward halves (libs/loss.py) for an upstream gradient of 1.
 //   k_bce_bwd: d/dpred of mean BCE-with-logits with pos_weight pw (pw = 1: the unbalanced form; weight: optional per-element):
-//              (sigmoid(x) (1 - gt + pw gt) - pw gt) * w / count                                        loss.py:85-93
+//              ((1 - gt) sigmoid(x) - pw gt sigmoid(-x)) * w / count                                    loss.py:85-93
+//              (= (sigmoid(x) (1 - gt + pw gt) - pw gt), but without the cancellation of pw sigmoid(x) - pw that loses
+//              a confident positive's gradient when pw is large: one inlier in the batch makes pw ~ the number of rows)
 //   k_sm_dense_bwd: dL/dM of SpectralMatchingLoss(M, gt) with the per-pair constants cP, cN of k_sm_bwd_prep (consts[b] = {cP, cN, ..}):
 //              gtM (M - 1) cP + (1 - gtM) M cN, zero on the diagonal                                     loss.py:116-140
 //   k_sim_bwd_G: from S = Fn Fn^T and an upstream dM: G = dM [0 <= u <= 1] / sigma^2 off the diagonal (clamp's gradient mask,
@@ -728,8 +730,8 @@ k_bce_bwd(const float* __restrict__ pred, const float* __restrict__ gt, const fl
   if (idx >= total) return;
   const float pos_weight = pw_dev ? pw_dev[0] : 1.0f;
   const float x = pred[idx], g = gt[idx];
-  const float sg = 1.0f / (1.0f + expf(-x));
-  float d = sg * (1.0f - g + pos_weight * g) - pos_weight * g;
+  const float sp = 1.0f / (1.0f + expf(-x)), sn = 1.0f / (1.0f + expf(x));      // sigmoid(x), sigmoid(-x)
+  float d = (1.0f - g) * sp - pos_weight * g * sn;
   if (weight) d *= weight[idx];
   dpred[idx] = d * inv_count;
 }

@@ -452,8 +452,10 @@ k_transformation_final(const float* __restrict__ trans, const float* __restrict_
 //     dL/dFn   = (G + G^T) Fn = 2 G Fn                             (G is symmetric)
 //     dL/dsigma = sum_ij dL/dM_ij [0 <= u_ij <= 1] 2 (1 - s_ij) / sigma^3
 // i.e. the structure of the attention kernel with K = V = Fn and P = G: per 32 x 32 tile S^T = F_J F_I^T and
-// dF_I^T += F_J^T G^T on the f16 MFMA with split-fp16 operands; G is scaled by a power of two per pair so that its fp16
-// planes stay in the normal range.  One launch: 1 024 N^2 MFMA flops per pair, the size of one attention launch.
+// dF_I^T += F_J^T G^T on the f16 MFMA with split-fp16 operands; each row of G is scaled by a power of two of its own so
+// that its fp16 planes stay in the normal range.  A per-pair scale is not enough: under the balanced loss a pair with few
+// inliers has cN / cP ~ n^2 / N^2, and the rows that only ever see cN (a negative row, or every row when the pair has fewer
+// than two inliers) would fall into fp16 subnormals and lose their low plane (1e-3 of the row at N = 2000).  One launch: 1 024 N^2 MFMA flops per pair, the size of one attention launch.
 // =========================================================================================
 // T image of the features for the second product: unit ((plane * 8 + slot) * 64 + lane), slot = 2 db + s2, lane (h, d): the 8
 // halves are Fn[32 t + 16 s2 + 4 h + e][32 db + d] (e < 4) followed by Fn[32 t + 16 s2 + 8 + 4 h + e][32 db + d] - the key order
@@ -479,7 +481,9 @@ __global__ void k_pack_rows_t_h2(const float* __restrict__ feat, float* __restri
   o[(1 * 8 + slot) * 64 + lane] = lo;
 }
 
-// per pair: cP, cN (see above), and the power-of-two scale of G; consts[b] = {cP, cN, scale, 1 / scale}
+// per pair: cP, cN (see above), and the power-of-two scales of G's rows; consts[b] = {cP, cN, scale of a positive row, scale of
+// a negative row}.  A negative row (gt_i = 0) only holds M cN; a positive row also holds (M - 1) cP when the pair has another
+// inlier (gt_M is zero on the diagonal, so the lone inlier of a pair is a cN-only row too).
 __global__ void __launch_bounds__(256)
 k_sm_bwd_prep(const float* __restrict__ gt, float* __restrict__ consts, int B, int N, int balanced, float inv_sig2,
               const float* __restrict__ sigma_dev) {
@@ -494,11 +498,14 @@ k_sm_bwd_prep(const float* __restrict__ gt, float* __restrict__ consts, int B, i
     double cP, cN;
     if (balanced) { cP = 1.0 / ((double)B * (fmax(np - 1.0, 0.0) + 1.0)); cN = 1.0 / ((double)B * (fmax(nn - 1.0, 0.0) + 1.0)); }
     else cP = cN = 2.0 / ((double)B * (double)N * (double)N);
-    const double gmax = fmax(cP, cN) * inv_sig2;                   // |G| <= gmax
-    int e;
-    frexp(gmax, &e);                                               // gmax = m 2^e, m in [0.5, 1)
-    const float scale = ldexpf(1.0f, 8 - e);                       // scaled |G| <= 256
-    consts[4 * b + 0] = (float)cP; consts[4 * b + 1] = (float)cN; consts[4 * b + 2] = scale; consts[4 * b + 3] = 1.0f / scale;
+    auto pow2_scale = [&](double gmax) {                           // |G| <= gmax on the row
+      int e;
+      frexp(gmax * inv_sig2, &e);                                  // gmax / sigma^2 = m 2^e, m in [0.5, 1)
+      return ldexpf(1.0f, 8 - e);                                  // scaled |G| <= 256
+    };
+    consts[4 * b + 0] = (float)cP; consts[4 * b + 1] = (float)cN;
+    consts[4 * b + 2] = pow2_scale(n1 >= 2.0 ? fmax(cP, cN) : cN);
+    consts[4 * b + 3] = pow2_scale(cN);
   }
 }
 
@@ -521,10 +528,11 @@ k_sm_backward(const float* __restrict__ img, const float* __restrict__ timg, con
   const bool active = tile_raw < tiles;
   const int tile = active ? tile_raw : tiles - 1;
   const size_t pbase = (size_t)pair * tiles;
-  const float cP = consts[4 * pair + 0], cN = consts[4 * pair + 1], scale = consts[4 * pair + 2], inv_scale = consts[4 * pair + 3];
+  const float cP = consts[4 * pair + 0], cN = consts[4 * pair + 1];
   const int row_i = 32 * tile + i;
   const float* gtp = gt + (size_t)pair * N;
   const float gt_i = row_i < N ? gtp[row_i] : 0.f;
+  const float scale = consts[4 * pair + (gt_i == 1.0f ? 2 : 3)];           // this lane's row of G (powers of two: 1 / scale is exact)
 
   f16x8 qh[8], ql[8];
   {
@@ -591,7 +599,7 @@ k_sm_backward(const float* __restrict__ img, const float* __restrict__ timg, con
   // dF_i = 2 G F: lane (h, i) register r of block db is feature 32 db + 8 (r >> 2) + 4 h + (r & 3) of row i
   if (active && row_i < N) {
     float4* o = reinterpret_cast<float4*>(dF + ((size_t)pair * N + row_i) * kFeat);
-    const float c2 = 2.0f * inv_scale;
+    const float c2 = 2.0f / scale;
 #pragma unroll
     for (int db = 0; db < 4; ++db)
 #pragma unroll
