@@ -186,6 +186,10 @@ SIGNATURES = {
     "gmf_transformation_loss_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     "gmf_pose_head_backward": (C.c_int, [_vp, C.POINTER(PoseParams), _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
     "gmf_weighted_procrustes_backward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_float, _vp, _vp, _vp, _vp]),
+    "gmf_ransac_correspondence": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _ll, C.c_int, C.c_int, C.c_int, C.c_float,
+                                            C.c_ulonglong, C.c_int] + [_vp] * 7),
+    "gmf_icp_point_to_point": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _ll, C.c_int, C.c_int, _vp, C.c_float, C.c_int,
+                                         C.c_double, C.c_double] + [_vp] * 6),
 }
 
 _lib = None

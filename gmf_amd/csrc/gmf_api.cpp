@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <algorithm>
@@ -15,6 +16,7 @@
 
 #include "api_common.hpp"
 #include "launchers_pose.hpp"
+#include "launchers_solvers.hpp"
 
 extern "C" {
 
@@ -1119,6 +1121,51 @@ int gmf_global_registration(gmf_handle* h, const float* X, const float* Y, const
   SetDevice sd(h, stream);
   GMF_HIP(gmf::launch_global_registration(X, Y, w, offsets, B, eps, quantization_size, max_iter, max_break_count,
                                           break_threshold_ratio, R, t, stats, max_points > 0 ? max_points : (1 << 30), S(stream)));
+  return GMF_OK;
+}
+
+int gmf_ransac_correspondence(gmf_handle* h, const float* src, const float* tgt, const int* offsets, const unsigned char* mask,
+                              int B, long long total_rows, int max_rows, int ransac_n, int num_hypotheses, float tau,
+                              unsigned long long seed, int first_pair, float* T_out, unsigned char* inliers, float* fitness,
+                              float* inlier_rmse, long long* hypothesis, long long* sample, gmf_stream_t stream) {
+  GMF_REQUIRE(h && src && tgt && offsets && T_out && inliers && fitness && inlier_rmse && hypothesis && sample, GMF_ERR_BAD_ARG,
+              "ransac_correspondence: null pointer");
+  GMF_REQUIRE(B > 0 && total_rows > 0 && total_rows < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "ransac_correspondence: empty batch or more than 2^31 rows");
+  GMF_REQUIRE(ransac_n >= 3 && ransac_n <= 8, GMF_ERR_BAD_ARG, "ransac_correspondence: ransac_n must be in 3..8");
+  GMF_REQUIRE(num_hypotheses >= 1 && num_hypotheses <= (1 << 24), GMF_ERR_BAD_ARG,
+              "ransac_correspondence: num_hypotheses must be in 1..2^24");
+  GMF_REQUIRE(tau > 0.f && std::isfinite(tau), GMF_ERR_BAD_ARG, "ransac_correspondence: max_correspondence_distance must be > 0");
+  GMF_REQUIRE(first_pair >= 0, GMF_ERR_BAD_ARG, "ransac_correspondence: first_pair must be >= 0");
+  SetDevice sd(h, stream);
+  const size_t need = gmf::ransac_scratch_bytes(total_rows, B, num_hypotheses);
+  if (int rc = arena_reserve(h, need)) return rc;
+  gmf::RansacScratch ws;
+  gmf::ransac_scratch_carve(arena_take<char>(h, need), total_rows, B, num_hypotheses, ws);
+  GMF_HIP(gmf::launch_ransac(src, tgt, offsets, mask, B, total_rows, max_rows > 0 ? max_rows : (int)total_rows, ransac_n,
+                             num_hypotheses, tau, seed, first_pair, ws, T_out, inliers, fitness, inlier_rmse, hypothesis, sample,
+                             S(stream)));
+  return GMF_OK;
+}
+
+int gmf_icp_point_to_point(gmf_handle* h, const float* src, const int* src_offsets, const float* tgt, const int* tgt_offsets,
+                           int B, long long total_src, int max_src, int max_tgt, const float* init, float tau, int max_iter,
+                           double rel_fitness, double rel_rmse, float* T_out, float* fitness, float* inlier_rmse,
+                           int* iterations, long long* nn, gmf_stream_t stream) {
+  GMF_REQUIRE(h && src && src_offsets && tgt && tgt_offsets && init && T_out && fitness && inlier_rmse && iterations && nn,
+              GMF_ERR_BAD_ARG, "icp_point_to_point: null pointer");
+  GMF_REQUIRE(B > 0 && total_src > 0 && total_src < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "icp_point_to_point: empty batch or more than 2^31 source rows");
+  GMF_REQUIRE(tau > 0.f && std::isfinite(tau), GMF_ERR_BAD_ARG, "icp_point_to_point: max_correspondence_distance must be > 0");
+  GMF_REQUIRE(max_iter >= 0 && max_iter <= 100000, GMF_ERR_BAD_ARG, "icp_point_to_point: max_iteration must be in 0..100000");
+  SetDevice sd(h, stream);
+  const size_t need = gmf::icp_scratch_bytes(total_src, B);
+  if (int rc = arena_reserve(h, need)) return rc;
+  gmf::IcpScratch ws;
+  gmf::icp_scratch_carve(arena_take<char>(h, need), total_src, B, ws);
+  GMF_HIP(gmf::launch_icp(src, src_offsets, tgt, tgt_offsets, B, total_src, max_src > 0 ? max_src : (int)total_src,
+                          max_tgt > 0 ? max_tgt : (int)total_src, init, tau, max_iter, rel_fitness, rel_rmse, ws, T_out, fitness,
+                          inlier_rmse, iterations, nn, S(stream)));
   return GMF_OK;
 }
 

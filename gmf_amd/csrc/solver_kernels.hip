@@ -1,0 +1,518 @@
+// Correspondence RANSAC and point-to-point ICP, batched over ragged pairs: the solvers the reference's evaluation scripts run on
+// the CPU through open3d after the network (GMF_PointDSC/evaluation/test_3DMatch.py:76-96, benchmark_utils.py:40-56;
+// GMF_DeepGlobalRegistration/*/core/deep_global_registration.py:57-85, 256-272, 385-405).  Contract: gmf_amd/solvers.py.
+//
+// RANSAC, three launches after one memset:
+//   k_ransac_compact   one workgroup per pair: the participating rows (mask) packed to the front of the pair's slot.
+//   k_ransac_score     one lane per hypothesis: draw (ransac_sampler.hpp), fp64 Kabsch in registers, then the pair's rows
+//                      stream through an LDS tile that every lane reads at the same address (a broadcast).  The rows of a pair
+//                      are split over gridDim.y; the partial counts and d^2 sums are integers (d^2 in units of tau^2 / 2^24),
+//                      so the atomics that combine them give the same bits in any order and for any split.
+//   k_ransac_finish    one workgroup per pair: argmax over (valid, count, -sum, -h), a total order, then the winner's inlier
+//                      mask, fitness and rmse (fp64 sums in a fixed tree).
+// ICP, 2 + 2 (max_iteration + 1) launches, none of which the host waits for:
+//   k_icp_init         T = init in fp64, done = 0.
+//   k_icp_nn           exact nearest target of every transformed source row by direct fp32 differences; the targets are split
+//                      over gridDim.y and folded with a 64-bit atomicMin of (d^2 bits | target row): smallest d^2, then row.
+//   k_icp_step         one workgroup per pair: C, fitness, rmse, the convergence test, then Umeyama over C and T <- dT T.
+//   A finished pair's workgroups return at once.
+#include <algorithm>
+#include <math.h>
+
+#include "kabsch.hpp"
+#include "launchers_solvers.hpp"
+#include "ransac_sampler.hpp"
+
+namespace gmf {
+
+constexpr int kThreads = 256;
+
+// |R s + t - q|^2 in fp32 with every rounding pinned by explicit fmas (the scoring and the finishing kernels must agree bitwise)
+GMF_DEVINL float resid2(const float* T, float sx, float sy, float sz, float qx, float qy, float qz) {
+  const float dx = fmaf(T[0], sx, fmaf(T[1], sy, fmaf(T[2], sz, T[3]))) - qx;
+  const float dy = fmaf(T[4], sx, fmaf(T[5], sy, fmaf(T[6], sz, T[7]))) - qy;
+  const float dz = fmaf(T[8], sx, fmaf(T[9], sy, fmaf(T[10], sz, T[11]))) - qz;
+  return fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+}
+
+// fixed-shape tree sum over the workgroup: the same bits whatever the timing.  sh: kThreads * D doubles.  Result in sh[0 .. D).
+template <int D>
+GMF_DEVINL void tree_sum(double* v, double* sh) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+#pragma unroll
+  for (int d = 0; d < D; ++d) sh[d * kThreads + tid] = v[d];
+  __syncthreads();
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+#pragma unroll
+      for (int d = 0; d < D; ++d) sh[d * kThreads + tid] += sh[d * kThreads + tid + s];
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int d = 0; d < D; ++d) v[d] = sh[d * kThreads];
+  __syncthreads();
+}
+
+// unweighted Umeyama / Kabsch without scaling of NS rows in fp64: [R | t] row-major 3 x 4.  false: the SVD failed (H == 0, NaN).
+template <int NS>
+GMF_DEVINL bool fit_sample(const float4* __restrict__ cs, const float4* __restrict__ cq, const int* rows, double* Tout) {
+  double ca[3] = {0, 0, 0}, cb[3] = {0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    const float4 a = cs[rows[k]], b = cq[rows[k]];
+    ca[0] += a.x; ca[1] += a.y; ca[2] += a.z;
+    cb[0] += b.x; cb[1] += b.y; cb[2] += b.z;
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { ca[c] /= NS; cb[c] /= NS; }
+  double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    const float4 a = cs[rows[k]], b = cq[rows[k]];
+    const double am[3] = {a.x - ca[0], a.y - ca[1], a.z - ca[2]};
+    const double bm[3] = {b.x - cb[0], b.y - cb[1], b.z - cb[2]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) H[3 * r + c] = fma(am[r], bm[c], H[3 * r + c]);
+  }
+  KabschFrames f;
+  kabsch_frames(H, f);
+  if (!f.ok) return false;
+  bool fin = true;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    double t = cb[r];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double R = f.v[0][r] * f.u[0][c] + f.v[1][r] * f.u[1][c] + f.v[2][r] * f.u[2][c];
+      Tout[4 * r + c] = R;
+      t -= R * ca[c];
+      fin = fin && isfinite(R);
+    }
+    Tout[4 * r + 3] = t;
+    fin = fin && isfinite(t);
+  }
+  return fin;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// RANSAC
+// ---------------------------------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(kThreads)
+k_ransac_compact(const float* __restrict__ src, const float* __restrict__ tgt, const int* __restrict__ off,
+                 const unsigned char* __restrict__ mask, float4* __restrict__ cs, float4* __restrict__ cq, int* __restrict__ cidx,
+                 int* __restrict__ m_out) {
+  __shared__ int wsum[kThreads / 64];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r0 = off[b], n = off[b + 1] - r0;
+  int base = 0;
+  for (int i0 = 0; i0 < n; i0 += kThreads) {
+    const int i = i0 + tid;
+    const bool keep = i < n && (!mask || mask[r0 + i]);
+    const unsigned long long bal = __ballot(keep);
+    const int pre = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wsum[wave] = __popcll(bal);
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) {
+      before += (w < wave) ? wsum[w] : 0;
+      total += wsum[w];
+    }
+    if (keep) {
+      const int pos = r0 + base + before + pre;
+      const float* a = src + 3 * (size_t)(r0 + i);
+      const float* q = tgt + 3 * (size_t)(r0 + i);
+      cs[pos] = make_float4(a[0], a[1], a[2], 0.f);
+      cq[pos] = make_float4(q[0], q[1], q[2], 0.f);
+      cidx[pos] = i;
+    }
+    base += total;
+    __syncthreads();
+  }
+  if (tid == 0) m_out[b] = base;
+}
+
+// grid (hb * B, Y): workgroup x scores hypotheses [256 (x % hb), +256) of pair x / hb over the y-th share of the pair's row tiles
+template <int NS>
+__global__ void __launch_bounds__(kThreads)
+k_ransac_score(const float4* __restrict__ cs, const float4* __restrict__ cq, const int* __restrict__ off, const int* __restrict__ m_in,
+               int H, int hb, unsigned long long seed, int first_pair, float tau2, float qscale, unsigned* __restrict__ cnt,
+               unsigned long long* __restrict__ sq, unsigned char* __restrict__ valid, float* __restrict__ thyp) {
+  __shared__ float4 tile[2 * kThreads];
+  const int b = blockIdx.x / hb, tid = threadIdx.x;
+  const int h = (blockIdx.x % hb) * kThreads + tid;
+  const int r0 = off[b], M = m_in[b];
+  if (M < NS) return;                                    // (uniform) no hypothesis: the pair reports identity
+  const float4* ps = cs + r0;
+  const float4* pq = cq + r0;
+  const bool active = h < H;
+  float T[12];
+  bool ok = false;
+  {
+    double Td[12];
+    if (active) {
+      int rows[NS];
+      ransac_draw<NS>(seed, (uint32_t)(first_pair + b), (uint32_t)h, (uint32_t)M, rows);
+      ok = fit_sample<NS>(ps, pq, rows, Td);
+    }
+#pragma unroll
+    for (int e = 0; e < 12; ++e) T[e] = ok ? (float)Td[e] : 0.f;
+  }
+  const size_t slot = (size_t)b * H + h;
+  if (blockIdx.y == 0 && active) {
+    valid[slot] = ok ? 1 : 0;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) thyp[slot * 12 + e] = T[e];
+  }
+  const int ntile = (M + kThreads - 1) / kThreads;
+  const int t0 = (int)((long long)ntile * blockIdx.y / gridDim.y), t1 = (int)((long long)ntile * (blockIdx.y + 1) / gridDim.y);
+  unsigned n_in = 0;
+  unsigned long long sum = 0;
+  for (int t = t0; t < t1; ++t) {
+    const int rb = t * kThreads, nrow = min(kThreads, M - rb);
+    __syncthreads();
+    if (tid < nrow) {
+      tile[tid] = ps[rb + tid];
+      tile[kThreads + tid] = pq[rb + tid];
+    }
+    __syncthreads();
+    unsigned part = 0;                                   // <= 256 rows of < 2^24 each: no overflow
+    for (int j = 0; j < nrow; ++j) {
+      const float4 a = tile[j], q = tile[kThreads + j];
+      const float d2 = resid2(T, a.x, a.y, a.z, q.x, q.y, q.z);
+      const bool in = d2 < tau2;
+      n_in += in ? 1u : 0u;
+      part += in ? min(__float2uint_rz(d2 * qscale), 0xFFFFFFu) : 0u;
+    }
+    sum += part;
+  }
+  if (active && ok && t1 > t0) {
+    atomicAdd(cnt + slot, n_in);
+    atomicAdd(sq + slot, sum);
+  }
+}
+
+struct HypKey {
+  unsigned valid, cnt;
+  unsigned long long sq;
+  int h;
+};
+
+GMF_DEVINL bool better(const HypKey& a, const HypKey& b) {
+  if (a.valid != b.valid) return a.valid > b.valid;
+  if (a.cnt != b.cnt) return a.cnt > b.cnt;
+  if (a.sq != b.sq) return a.sq < b.sq;
+  return a.h < b.h;
+}
+
+template <int NS>
+__global__ void __launch_bounds__(kThreads)
+k_ransac_finish(const float* __restrict__ src, const float* __restrict__ tgt, const int* __restrict__ off,
+                const unsigned char* __restrict__ mask, const int* __restrict__ cidx, const int* __restrict__ m_in, int H,
+                unsigned long long seed, int first_pair, float tau2, const unsigned* __restrict__ cnt,
+                const unsigned long long* __restrict__ sq, const unsigned char* __restrict__ valid, const float* __restrict__ thyp,
+                float* __restrict__ T_out, unsigned char* __restrict__ inliers, float* __restrict__ fitness, float* __restrict__ rmse,
+                long long* __restrict__ hyp_out, long long* __restrict__ sample_out) {
+  __shared__ double sh[kThreads * 2];
+  __shared__ HypKey kk[kThreads];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int r0 = off[b], n = off[b + 1] - r0, M = m_in[b];
+  HypKey best = {0u, 0u, ~0ull, 0x7fffffff};
+  if (M >= NS) {
+    for (int h = tid; h < H; h += kThreads) {
+      const size_t slot = (size_t)b * H + h;
+      const HypKey c = {(unsigned)valid[slot], cnt[slot], sq[slot], h};
+      if (better(c, best)) best = c;
+    }
+  }
+  kk[tid] = best;
+  __syncthreads();
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if (tid < s && better(kk[tid + s], kk[tid])) kk[tid] = kk[tid + s];
+    __syncthreads();
+  }
+  const HypKey w = kk[0];
+  const bool have = w.valid != 0;
+  float T[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[e] = have ? thyp[((size_t)b * H + w.h) * 12 + e] : ((e % 5 == 0) ? 1.f : 0.f);
+  double v[2] = {0.0, 0.0};                              // inliers, sum d^2
+  for (int i = tid; i < n; i += kThreads) {
+    bool in = false;
+    if (have && (!mask || mask[r0 + i])) {
+      const float* a = src + 3 * (size_t)(r0 + i);
+      const float* q = tgt + 3 * (size_t)(r0 + i);
+      const float d2 = resid2(T, a[0], a[1], a[2], q[0], q[1], q[2]);
+      in = d2 < tau2;
+      if (in) { v[0] += 1.0; v[1] += (double)d2; }
+    }
+    inliers[r0 + i] = in ? 1 : 0;
+  }
+  tree_sum<2>(v, sh);
+  if (tid == 0) {
+    float* To = T_out + 16 * (size_t)b;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) To[e] = T[e];
+    To[12] = 0.f; To[13] = 0.f; To[14] = 0.f; To[15] = 1.f;
+    fitness[b] = (have && M > 0) ? (float)(v[0] / M) : 0.f;
+    rmse[b] = (have && v[0] > 0) ? (float)sqrt(v[1] / v[0]) : 0.f;
+    hyp_out[b] = have ? w.h : -1;
+    int rows[NS];
+    if (have) ransac_draw<NS>(seed, (uint32_t)(first_pair + b), (uint32_t)w.h, (uint32_t)M, rows);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) sample_out[(size_t)b * NS + k] = have ? cidx[r0 + rows[k]] : -1;
+  }
+}
+
+size_t ransac_scratch_bytes(long long total_rows, int B, int H) {
+  const size_t BH = (size_t)B * H;
+  auto a = [](size_t v) { return (v + 255) / 256 * 256; };
+  return a(total_rows * 16) * 2 + a(total_rows * 4) + a((size_t)B * 4) + a(BH * 4) + a(BH * 8) + a(BH) + a(BH * 48) + 256;
+}
+
+void ransac_scratch_carve(void* base, long long total_rows, int B, int H, RansacScratch& s) {
+  const size_t BH = (size_t)B * H;
+  auto a = [](size_t v) { return (v + 255) / 256 * 256; };
+  char* p = static_cast<char*>(base);
+  s.cs = reinterpret_cast<float4*>(p); p += a(total_rows * 16);
+  s.cq = reinterpret_cast<float4*>(p); p += a(total_rows * 16);
+  s.cidx = reinterpret_cast<int*>(p); p += a(total_rows * 4);
+  s.m = reinterpret_cast<int*>(p); p += a((size_t)B * 4);
+  s.sq = reinterpret_cast<unsigned long long*>(p); p += a(BH * 8);       // cnt, sq, valid adjacent: one memset
+  s.cnt = reinterpret_cast<unsigned*>(p); p += a(BH * 4);
+  s.valid = reinterpret_cast<unsigned char*>(p); p += a(BH);
+  s.thyp = reinterpret_cast<float*>(p);
+}
+
+template <int NS>
+static void launch_ransac_n(const float* src, const float* tgt, const int* off, const unsigned char* mask, int B, int max_rows,
+                            int H, float tau, uint64_t seed, int first_pair, const RansacScratch& ws, float* T_out,
+                            unsigned char* inliers, float* fitness, float* rmse, long long* hyp, long long* sample, hipStream_t s) {
+  const int hb = (H + kThreads - 1) / kThreads;
+  // split the rows when B * hb workgroups alone would leave CUs idle: about 2048 workgroups in all, every split >= 1 tile
+  const long long wg = (long long)hb * B;
+  const int tiles = std::max(1, (max_rows + kThreads - 1) / kThreads);
+  const int Y = (int)std::max(1LL, std::min<long long>({(2048 + wg - 1) / wg, (long long)tiles, 64LL}));
+  const float tau2 = tau * tau;
+  const float qscale = 16777216.0f / tau2;
+  hipLaunchKernelGGL(k_ransac_compact, dim3(B), dim3(kThreads), 0, s, src, tgt, off, mask, ws.cs, ws.cq, ws.cidx, ws.m);
+  hipLaunchKernelGGL(k_ransac_score<NS>, dim3((unsigned)wg, Y), dim3(kThreads), 0, s, ws.cs, ws.cq, off, ws.m, H, hb,
+                     (unsigned long long)seed, first_pair, tau2, qscale, ws.cnt, ws.sq, ws.valid, ws.thyp);
+  hipLaunchKernelGGL(k_ransac_finish<NS>, dim3(B), dim3(kThreads), 0, s, src, tgt, off, mask, ws.cidx, ws.m, H,
+                     (unsigned long long)seed, first_pair, tau2, ws.cnt, ws.sq, ws.valid, ws.thyp, T_out, inliers, fitness, rmse,
+                     hyp, sample);
+}
+
+hipError_t launch_ransac(const float* src, const float* tgt, const int* offsets, const unsigned char* mask, int B,
+                         long long total_rows, int max_rows, int ransac_n, int H, float tau, uint64_t seed, int first_pair,
+                         const RansacScratch& ws, float* T_out, unsigned char* inliers, float* fitness, float* rmse,
+                         long long* hypothesis, long long* sample, hipStream_t s) {
+  const size_t BH = (size_t)B * H;
+  // sq, cnt and valid are adjacent in the scratch (ransac_scratch_carve)
+  hipError_t e = hipMemsetAsync(ws.sq, 0, reinterpret_cast<char*>(ws.valid + BH) - reinterpret_cast<char*>(ws.sq), s);
+  if (e != hipSuccess) return e;
+  (void)total_rows;
+#define GMF_RANSAC_CASE(n) \
+  case n: launch_ransac_n<n>(src, tgt, offsets, mask, B, max_rows, H, tau, seed, first_pair, ws, T_out, inliers, fitness, rmse, \
+                             hypothesis, sample, s); break;
+  switch (ransac_n) {
+    GMF_RANSAC_CASE(3) GMF_RANSAC_CASE(4) GMF_RANSAC_CASE(5) GMF_RANSAC_CASE(6) GMF_RANSAC_CASE(7) GMF_RANSAC_CASE(8)
+    default: return hipErrorInvalidValue;
+  }
+#undef GMF_RANSAC_CASE
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// ICP
+// ---------------------------------------------------------------------------------------------------------------------------
+
+// the source row transformed by the pair's fp64 [R | t], rounded once to fp32 (explicit fmas: k_icp_nn and k_icp_step agree)
+GMF_DEVINL void transform_row(const double* T, const float* a, float* p) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+    p[r] = (float)fma(T[4 * r], (double)a[0], fma(T[4 * r + 1], (double)a[1], fma(T[4 * r + 2], (double)a[2], T[4 * r + 3])));
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_icp_init(const float* __restrict__ init, int B, double* __restrict__ T, double* __restrict__ prev, int* __restrict__ done) {
+  const int b = blockIdx.x * kThreads + threadIdx.x;
+  if (b >= B) return;
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[12 * (size_t)b + e] = (double)init[16 * (size_t)b + e];
+  prev[2 * b] = 0.0;
+  prev[2 * b + 1] = 0.0;
+  done[b] = 0;
+}
+
+// grid (B * stiles, Y): workgroup x takes the source tiles x % stiles, + stiles, ... of pair x / stiles (every tile of any pair
+// is covered whatever max_src said), and the y-th share of the pair's target tiles
+__global__ void __launch_bounds__(kThreads)
+k_icp_nn(const float* __restrict__ src, const int* __restrict__ soff, const float* __restrict__ tgt, const int* __restrict__ toff,
+         int stiles, const double* __restrict__ Tst, const int* __restrict__ done, unsigned long long* __restrict__ key) {
+  __shared__ float4 tile[kThreads];
+  const int b = blockIdx.x / stiles, tid = threadIdx.x;
+  if (done[b]) return;
+  const int s0 = soff[b], ns = soff[b + 1] - s0, q0 = toff[b], nt = toff[b + 1] - q0;
+  double T[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[e] = Tst[12 * (size_t)b + e];
+  const int ntile = (nt + kThreads - 1) / kThreads;
+  const int t0 = (int)((long long)ntile * blockIdx.y / gridDim.y), t1 = (int)((long long)ntile * (blockIdx.y + 1) / gridDim.y);
+  if (t1 <= t0) return;
+  for (int st = blockIdx.x % stiles; st * kThreads < ns; st += stiles) {
+    const int i = st * kThreads + tid;
+    float p[3] = {0.f, 0.f, 0.f};
+    if (i < ns) transform_row(T, src + 3 * (size_t)(s0 + i), p);
+    float best = INFINITY;
+    int bj = -1;
+    for (int t = t0; t < t1; ++t) {
+      const int jb = t * kThreads, nrow = min(kThreads, nt - jb);
+      __syncthreads();
+      if (tid < nrow) {
+        const float* q = tgt + 3 * (size_t)(q0 + jb + tid);
+        tile[tid] = make_float4(q[0], q[1], q[2], 0.f);
+      }
+      __syncthreads();
+      for (int j = 0; j < nrow; ++j) {
+        const float4 q = tile[j];
+        const float dx = p[0] - q.x, dy = p[1] - q.y, dz = p[2] - q.z;
+        const float d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+        if (d2 < best) { best = d2; bj = jb + j; }         // strict: the first (smallest) row among equal distances
+      }
+    }
+    if (i < ns && bj >= 0)                               // d2 >= 0: its bits order as unsigned integers
+      atomicMin(key + s0 + i, ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)bj);
+  }
+}
+
+// pass k of the loop (k = 0: the evaluation at init): C, fitness, rmse; stop on convergence or at k == max_iter, else T <- dT T.
+// Every key is read and reset to the atomicMin identity for the next k_icp_nn.
+__global__ void __launch_bounds__(kThreads)
+k_icp_step(const float* __restrict__ src, const int* __restrict__ soff, const float* __restrict__ tgt, const int* __restrict__ toff,
+           int k, int max_iter, float tau2, double rel_f, double rel_r, double* __restrict__ Tst, double* __restrict__ prev,
+           int* __restrict__ done, unsigned long long* __restrict__ key, float* __restrict__ T_out, float* __restrict__ fit_out,
+           float* __restrict__ rmse_out, int* __restrict__ it_out, long long* __restrict__ nn) {
+  __shared__ double sh[kThreads * 9];
+  __shared__ int stop_sh;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (done[b]) return;
+  const int s0 = soff[b], ns = soff[b + 1] - s0, q0 = toff[b];
+  double T[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[e] = Tst[12 * (size_t)b + e];
+  double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};               // |C|, sum d^2, sum p, sum q
+  for (int i = tid; i < ns; i += kThreads) {
+    const unsigned long long kv = key[s0 + i];
+    key[s0 + i] = ~0ull;
+    const float d2 = __uint_as_float((unsigned)(kv >> 32));
+    const int j = (int)(kv & 0xffffffffull);
+    const bool in = kv != ~0ull && d2 < tau2;
+    nn[s0 + i] = in ? j : -1;
+    if (in) {
+      float p[3];
+      transform_row(T, src + 3 * (size_t)(s0 + i), p);
+      const float* q = tgt + 3 * (size_t)(q0 + j);
+      v[0] += 1.0; v[1] += (double)d2;
+      v[2] += p[0]; v[3] += p[1]; v[4] += p[2];
+      v[5] += q[0]; v[6] += q[1]; v[7] += q[2];
+    }
+  }
+  tree_sum<8>(v, sh);
+  const double nc = v[0];
+  const double fit = nc / ns, rm = nc > 0 ? sqrt(v[1] / nc) : 0.0;
+  if (tid == 0) {
+    bool stop = k >= max_iter;
+    if (k >= 1 && fabs(prev[2 * b] - fit) < rel_f && fabs(prev[2 * b + 1] - rm) < rel_r) stop = true;
+    prev[2 * b] = fit;
+    prev[2 * b + 1] = rm;
+    if (stop) {
+      float* To = T_out + 16 * (size_t)b;
+#pragma unroll
+      for (int e = 0; e < 12; ++e) To[e] = (float)T[e];
+      To[12] = 0.f; To[13] = 0.f; To[14] = 0.f; To[15] = 1.f;
+      fit_out[b] = (float)fit;
+      rmse_out[b] = (float)rm;
+      it_out[b] = k;
+      done[b] = 1;
+    }
+    stop_sh = stop ? 1 : 0;
+  }
+  __syncthreads();
+  if (stop_sh || nc == 0.0) return;                      // empty C: dT = identity, T stays
+  const double ca[3] = {v[2] / nc, v[3] / nc, v[4] / nc}, cb[3] = {v[5] / nc, v[6] / nc, v[7] / nc};
+  double Hm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = tid; i < ns; i += kThreads) {
+    const long long j = nn[s0 + i];                       // written by this thread above
+    if (j < 0) continue;
+    float p[3];
+    transform_row(T, src + 3 * (size_t)(s0 + i), p);
+    const float* q = tgt + 3 * (size_t)(q0 + j);
+    const double am[3] = {p[0] - ca[0], p[1] - ca[1], p[2] - ca[2]};
+    const double bm[3] = {q[0] - cb[0], q[1] - cb[1], q[2] - cb[2]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) Hm[3 * r + c] = fma(am[r], bm[c], Hm[3 * r + c]);
+  }
+  tree_sum<9>(Hm, sh);
+  if (tid == 0) {
+    double R[9];
+    kabsch_rotation_from_H(Hm, R);
+    double dt[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) dt[r] = cb[r] - (R[3 * r] * ca[0] + R[3 * r + 1] * ca[1] + R[3 * r + 2] * ca[2]);
+    double Tn[12];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        Tn[4 * r + c] = R[3 * r] * T[c] + R[3 * r + 1] * T[4 + c] + R[3 * r + 2] * T[8 + c] + (c == 3 ? dt[r] : 0.0);
+    }
+#pragma unroll
+    for (int e = 0; e < 12; ++e) Tst[12 * (size_t)b + e] = Tn[e];
+  }
+}
+
+size_t icp_scratch_bytes(long long total_src, int B) {
+  auto a = [](size_t v) { return (v + 255) / 256 * 256; };
+  return a(total_src * 8) + a((size_t)B * 96) + a((size_t)B * 16) + a((size_t)B * 4) + 256;
+}
+
+void icp_scratch_carve(void* base, long long total_src, int B, IcpScratch& s) {
+  auto a = [](size_t v) { return (v + 255) / 256 * 256; };
+  char* p = static_cast<char*>(base);
+  s.key = reinterpret_cast<unsigned long long*>(p); p += a(total_src * 8);
+  s.T = reinterpret_cast<double*>(p); p += a((size_t)B * 96);
+  s.prev = reinterpret_cast<double*>(p); p += a((size_t)B * 16);
+  s.done = reinterpret_cast<int*>(p);
+}
+
+hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, const int* tgt_off, int B, long long total_src,
+                      int max_src, int max_tgt, const float* init, float tau, int max_iter, double rel_fitness, double rel_rmse,
+                      const IcpScratch& ws, float* T_out, float* fitness, float* rmse, int* iterations, long long* nn,
+                      hipStream_t s) {
+  hipError_t e = hipMemsetAsync(ws.key, 0xff, (size_t)total_src * 8, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_icp_init, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, s, init, B, ws.T, ws.prev, ws.done);
+  // about 2048 workgroups per nearest-neighbour pass: source tiles x target shares
+  const int stiles = std::max(1, (max_src + kThreads - 1) / kThreads);
+  const long long wg = (long long)stiles * B;
+  const int ttiles = std::max(1, (max_tgt + kThreads - 1) / kThreads);
+  const int Y = (int)std::max(1LL, std::min<long long>({(2048 + wg - 1) / wg, (long long)ttiles, 256LL}));
+  const float tau2 = tau * tau;
+  for (int k = 0; k <= max_iter; ++k) {
+    hipLaunchKernelGGL(k_icp_nn, dim3((unsigned)wg, Y), dim3(kThreads), 0, s, src, src_off, tgt, tgt_off, stiles, ws.T, ws.done,
+                       ws.key);
+    hipLaunchKernelGGL(k_icp_step, dim3(B), dim3(kThreads), 0, s, src, src_off, tgt, tgt_off, k, max_iter, tau2, rel_fitness,
+                       rel_rmse, ws.T, ws.prev, ws.done, ws.key, T_out, fitness, rmse, iterations, nn);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace gmf

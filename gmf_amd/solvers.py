@@ -1,0 +1,259 @@
+"""Correspondence RANSAC and point-to-point ICP on the device: the solvers the reference's evaluation scripts run after the network
+through open3d 0.9 / 0.10 on the CPU (GMF_PointDSC/evaluation/test_3DMatch.py:76-96, benchmark_utils.py:40-56;
+GMF_DeepGlobalRegistration/*/core/deep_global_registration.py:57-85, 256-272, 385-405).  Kernels: csrc/solver_kernels.hip.
+
+The batched forms take one stream, make no host synchronisation and can be captured into a graph.  The open3d-shaped wrappers
+read back once to size their correspondence set (and the RANSAC wrapper once more to check the indices of `corres`).
+Differences from open3d: INTEGRATION.md, "Evaluation solvers"."""
+from __future__ import annotations
+
+import collections
+
+import numpy as np
+import torch
+
+from ._util import handle_and_stream
+from .registration import _device_offsets
+
+RegistrationResult = collections.namedtuple("RegistrationResult", "transformation correspondence_set fitness inlier_rmse")
+
+_MAX_HYPOTHESES = 1 << 24
+
+
+def _fail(what, msg):
+    raise RuntimeError(f"gmf_amd.{what}: {msg}")
+
+
+def _check_points(x, name, what, dims):
+    if not isinstance(x, torch.Tensor):
+        _fail(what, f"`{name}` must be a torch tensor")
+    if x.dtype != torch.float32:
+        _fail(what, f"`{name}` must be float32 (got {x.dtype})")
+    if x.dim() != dims or x.shape[-1] != 3 or any(s == 0 for s in x.shape):
+        _fail(what, f"`{name}` must be a non-empty [{'B,N' if dims == 3 else 'sum N'},3] tensor (got {tuple(x.shape)})")
+
+
+def _check_offsets(offsets, n_rows, what):
+    """Host-side checks of an offset list (a device int32 tensor is checked by _device_offsets, as in registration.py)."""
+    if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
+        return offsets
+    off = offsets.tolist() if isinstance(offsets, (torch.Tensor, np.ndarray)) else list(offsets)
+    try:
+        off = [int(o) for o in off]
+    except (TypeError, ValueError):
+        _fail(what, "offsets must be B + 1 integers")
+    if len(off) < 2 or off[0] != 0 or off[-1] != n_rows or any(b <= a for a, b in zip(off, off[1:])):
+        _fail(what, "offsets must be increasing, start at 0 and end at N")
+    return off
+
+
+def _require_device(x, name, what):
+    if not x.is_cuda:
+        _fail(what, f"`{name}` must live on a HIP device (got {x.device}); the HIP path is mandatory, there is no CPU fallback")
+
+
+def _max_rows(off, n_rows):
+    return max(b - a for a, b in zip(off, off[1:])) if isinstance(off, list) else n_rows
+
+
+def ransac_correspondence_batched(src, tgt, max_correspondence_distance, offsets=None, mask=None, ransac_n=3,
+                                  num_hypotheses=1000, seed=0, first_pair=0):
+    """Correspondence RANSAC over B pairs: row i of `src` corresponds to row i of `tgt`.
+
+    src, tgt: [B,N,3] float32 (offsets None) or ragged [sum N,3] with `offsets` (B + 1 ints, or an int32 device tensor).
+    mask: optional bool tensor of src's leading shape; only its rows take part (PointDSC: pred_labels > 0).
+    Hypothesis h of pair b draws `ransac_n` distinct participating rows with the counter-based sampler of
+    csrc/ransac_sampler.hpp (pair index first_pair + b, so a batch split into calls gives the same results), fits them with the
+    fp64 Kabsch and counts the rows with |R s + t - q|^2 < tau^2.  The winner has the most inliers, then the smaller sum of their
+    d^2, then the smaller h; its T is returned without a final refit.
+
+    Returns T [B,4,4] f32, inliers (bool, src's leading shape), fitness [B] (inliers / participating rows), inlier_rmse [B],
+    hypothesis [B] int64 (-1 if the pair had fewer than ransac_n rows: T = identity) and sample [B, ransac_n] int64 (the winner's
+    rows, numbered within the pair)."""
+    what = "ransac_correspondence_batched"
+    dims = 3 if offsets is None else 2
+    _check_points(src, "src", what, dims)
+    _check_points(tgt, "tgt", what, dims)
+    if src.shape != tgt.shape:
+        _fail(what, f"src and tgt must have the same shape (got {tuple(src.shape)} / {tuple(tgt.shape)})")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != src.shape[:-1]:
+            _fail(what, f"mask must be a bool tensor of shape {tuple(src.shape[:-1])}")
+    n = int(ransac_n)
+    if n != ransac_n or not 3 <= n <= 8:
+        _fail(what, f"ransac_n must be an integer in 3..8 (got {ransac_n})")
+    H = int(num_hypotheses)
+    if H != num_hypotheses or not 1 <= H <= _MAX_HYPOTHESES:
+        _fail(what, f"num_hypotheses must be an integer in 1..2**24 (got {num_hypotheses})")
+    tau = float(max_correspondence_distance)
+    if not (tau > 0 and np.isfinite(tau)):
+        _fail(what, f"max_correspondence_distance must be > 0 (got {max_correspondence_distance})")
+    if int(first_pair) < 0:
+        _fail(what, "first_pair must be >= 0")
+    n_rows = src.shape[0] * src.shape[1] if dims == 3 else src.shape[0]
+    if dims == 3:
+        off = list(range(0, n_rows + 1, src.shape[1]))
+    else:
+        off = _check_offsets(offsets, n_rows, what)
+    _require_device(src, "src", what)
+    _require_device(tgt, "tgt", what)
+    if tgt.device != src.device or (mask is not None and mask.device != src.device):
+        _fail(what, "src, tgt and mask must live on the same device")
+    dev_off, _ = _device_offsets(off, n_rows, src.device, what)
+    B = dev_off.numel() - 1
+    S = src.reshape(-1, 3).contiguous()
+    Q = tgt.reshape(-1, 3).contiguous()
+    m = None if mask is None else mask.reshape(-1).contiguous()
+    dev = src.device
+    T = torch.empty((B, 4, 4), device=dev, dtype=torch.float32)
+    inliers = torch.empty(src.shape[:-1], device=dev, dtype=torch.bool)
+    stats = torch.empty((2, B), device=dev, dtype=torch.float32)
+    ids = torch.empty((B, 1 + n), device=dev, dtype=torch.int64)
+    h, st = handle_and_stream(S)
+    h.call("gmf_ransac_correspondence", S.data_ptr(), Q.data_ptr(), dev_off.data_ptr(), None if m is None else m.data_ptr(), B,
+           n_rows, _max_rows(off, n_rows), n, H, tau, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_pair), T.data_ptr(),
+           inliers.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), ids.data_ptr(), ids.data_ptr() + 8 * B, st)
+    # ids holds hypothesis [B] followed by sample [B, n] (one allocation)
+    flat = ids.view(-1)
+    return T, inliers, stats[0], stats[1], flat[:B], flat[B:].view(B, n)
+
+
+def icp_point_to_point_batched(source, target, init, max_correspondence_distance, source_offsets=None, target_offsets=None,
+                               max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6):
+    """Point-to-point ICP over B pairs (open3d's registration_icp loop).
+
+    source [B,Ns,3] / ragged [sum Ns,3] with `source_offsets`, target [B,Nt,3] / ragged with its own `target_offsets`,
+    init [B,4,4] float32.  C = the exact nearest target row of each transformed source row, kept when d^2 < tau^2.  The loop
+    evaluates C at init, then up to `max_iteration` times: dT = Umeyama over C, T <- dT T (fp64), the ORIGINAL source
+    transformed by T, C again; it stops when |d fitness| < relative_fitness and |d rmse| < relative_rmse.  Decided on the device.
+
+    Returns T [B,4,4] f32, fitness [B] (|C| / Ns), inlier_rmse [B], iterations [B] int32 (loop passes run) and nn (int64,
+    source's leading shape: the matched target row within the pair, -1 outside C)."""
+    what = "icp_point_to_point_batched"
+    if (source_offsets is None) != (target_offsets is None):
+        _fail(what, "give both source_offsets and target_offsets, or neither")
+    dims = 3 if source_offsets is None else 2
+    _check_points(source, "source", what, dims)
+    _check_points(target, "target", what, dims)
+    if dims == 3 and source.shape[0] != target.shape[0]:
+        _fail(what, f"source and target must hold the same number of pairs (got {source.shape[0]} / {target.shape[0]})")
+    if not isinstance(init, torch.Tensor) or init.dtype != torch.float32 or init.dim() != 3 or init.shape[1:] != (4, 4):
+        _fail(what, "init must be a float32 [B,4,4] tensor")
+    tau = float(max_correspondence_distance)
+    if not (tau > 0 and np.isfinite(tau)):
+        _fail(what, f"max_correspondence_distance must be > 0 (got {max_correspondence_distance})")
+    it = int(max_iteration)
+    if it != max_iteration or not 0 <= it <= 100000:
+        _fail(what, f"max_iteration must be an integer in 0..100000 (got {max_iteration})")
+    rf, rr = float(relative_fitness), float(relative_rmse)
+    if not (rf >= 0 and rr >= 0):
+        _fail(what, "relative_fitness and relative_rmse must be >= 0")
+    ns_rows = source.shape[0] * source.shape[1] if dims == 3 else source.shape[0]
+    nt_rows = target.shape[0] * target.shape[1] if dims == 3 else target.shape[0]
+    if dims == 3:
+        soff = list(range(0, ns_rows + 1, source.shape[1]))
+        toff = list(range(0, nt_rows + 1, target.shape[1]))
+    else:
+        soff = _check_offsets(source_offsets, ns_rows, what)
+        toff = _check_offsets(target_offsets, nt_rows, what)
+        if isinstance(soff, list) and isinstance(toff, list) and len(soff) != len(toff):
+            _fail(what, "source_offsets and target_offsets must describe the same number of pairs")
+    for x, name in ((source, "source"), (target, "target"), (init, "init")):
+        _require_device(x, name, what)
+    if target.device != source.device or init.device != source.device:
+        _fail(what, "source, target and init must live on the same device")
+    dev = source.device
+    dso, _ = _device_offsets(soff, ns_rows, dev, what)
+    dto, _ = _device_offsets(toff, nt_rows, dev, what)
+    B = dso.numel() - 1
+    if dto.numel() != B + 1:
+        _fail(what, "source_offsets and target_offsets must describe the same number of pairs")
+    if init.shape[0] != B:
+        _fail(what, f"init must hold one [4,4] transformation per pair ({B}; got {init.shape[0]})")
+    S = source.reshape(-1, 3).contiguous()
+    Q = target.reshape(-1, 3).contiguous()
+    T0 = init.contiguous()
+    T = torch.empty((B, 4, 4), device=dev, dtype=torch.float32)
+    stats = torch.empty((2, B), device=dev, dtype=torch.float32)
+    iters = torch.empty(B, device=dev, dtype=torch.int32)
+    nn = torch.empty(source.shape[:-1], device=dev, dtype=torch.int64)
+    h, st = handle_and_stream(S)
+    h.call("gmf_icp_point_to_point", S.data_ptr(), dso.data_ptr(), Q.data_ptr(), dto.data_ptr(), B, ns_rows,
+           _max_rows(soff, ns_rows), _max_rows(toff, nt_rows), T0.data_ptr(), tau, it, rf, rr, T.data_ptr(), stats[0].data_ptr(),
+           stats[1].data_ptr(), iters.data_ptr(), nn.data_ptr(), st)
+    return T, stats[0], stats[1], iters, nn
+
+
+def _on_device(x, dev, dtype):
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(x)
+    return x.to(device=dev, dtype=dtype)
+
+
+def _device_of(*xs):
+    for x in xs:
+        if isinstance(x, torch.Tensor):
+            return x.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def registration_ransac_based_on_correspondence(source, target, corres, max_correspondence_distance, ransac_n=3,
+                                                max_iteration=1000, max_validation=1000, seed=0):
+    """open3d.registration.registration_ransac_based_on_correspondence with TransformationEstimationPointToPoint(False) and no
+    checkers: source [Ns,3] and target [Nt,3] points (tensors or numpy), corres [M,2] (source row, target row).
+    min(max_iteration, max_validation) hypotheses.  -> RegistrationResult(transformation [4,4] f32 on the device,
+    correspondence_set [K,2] int64 on the device (the winner's inlier rows of corres), fitness, inlier_rmse)."""
+    what = "registration_ransac_based_on_correspondence"
+    dev = _device_of(source, target, corres)
+    if dev.type != "cuda":
+        _fail(what, f"the points must live on a HIP device (got {dev}); the HIP path is mandatory, there is no CPU fallback")
+    src_pts = _on_device(source, dev, torch.float32)
+    tgt_pts = _on_device(target, dev, torch.float32)
+    c = _on_device(corres, dev, torch.int64)
+    if c.dim() != 2 or c.shape[1] != 2:
+        _fail(what, f"corres must be [M,2] (got {tuple(c.shape)})")
+    H = min(int(max_iteration), int(max_validation))
+    if H < 1:
+        _fail(what, "max_iteration and max_validation must be >= 1")
+    if c.shape[0] == 0:
+        return RegistrationResult(torch.eye(4, device=dev), c.clone(), 0.0, 0.0)
+    lo, hi0, hi1 = torch.stack([c.min(), c[:, 0].max(), c[:, 1].max()]).tolist()      # (a host read: indices are checked)
+    if lo < 0 or hi0 >= src_pts.shape[0] or hi1 >= tgt_pts.shape[0]:
+        _fail(what, "corres holds a row outside source / target")
+    T, inl, fit, rmse, _, _ = ransac_correspondence_batched(src_pts[c[:, 0]][None], tgt_pts[c[:, 1]][None],
+                                                            max_correspondence_distance, ransac_n=ransac_n, num_hypotheses=H,
+                                                            seed=seed)
+    info = torch.stack([fit[0], rmse[0], inl[0].sum().float()]).cpu().tolist()     # the result's size
+    corr = torch.nonzero_static(inl[0], size=int(info[2])).view(-1)
+    return RegistrationResult(T[0], c[corr], info[0], info[1])
+
+
+def registration_icp(source, target, max_correspondence_distance, init=None, max_iteration=30, relative_fitness=1e-6,
+                     relative_rmse=1e-6):
+    """open3d.registration.registration_icp with TransformationEstimationPointToPoint(): source [Ns,3], target [Nt,3] (tensors
+    or numpy), init [4,4] (default identity).  -> RegistrationResult(transformation [4,4] f32 on the device,
+    correspondence_set [K,2] int64 on the device (source row, nearest target row) of the final C, fitness, inlier_rmse)."""
+    what = "registration_icp"
+    dev = _device_of(source, target, init)
+    if dev.type != "cuda":
+        _fail(what, f"the points must live on a HIP device (got {dev}); the HIP path is mandatory, there is no CPU fallback")
+    S = _on_device(source, dev, torch.float32)
+    Q = _on_device(target, dev, torch.float32)
+    T0 = torch.eye(4, device=dev) if init is None else _on_device(init, dev, torch.float32)
+    if T0.shape != (4, 4):
+        _fail(what, f"init must be [4,4] (got {tuple(T0.shape)})")
+    T, fit, rmse, _, nn = icp_point_to_point_batched(S[None], Q[None], T0[None], max_correspondence_distance,
+                                                     max_iteration=max_iteration, relative_fitness=relative_fitness,
+                                                     relative_rmse=relative_rmse)
+    nn = nn[0]
+    info = torch.stack([fit[0], rmse[0], (nn >= 0).sum().float()]).cpu().tolist()   # the one synchronisation
+    rows = torch.nonzero_static(nn >= 0, size=int(info[2])).view(-1)
+    return RegistrationResult(T[0], torch.stack([rows, nn[rows]], 1), info[0], info[1])
+
+
+def icp_refine(src_keypts, tgt_keypts, pred_trans):
+    """Drop-in for GMF_PointDSC/evaluation/benchmark_utils.py:40-56, batched: src_keypts, tgt_keypts [B,N,3], pred_trans
+    [B,4,4] -> the refined [B,4,4] float32 (point-to-point ICP, tau = 0.10, open3d's default criteria).  No host
+    synchronisation."""
+    T, _, _, _, _ = icp_point_to_point_batched(src_keypts, tgt_keypts, pred_trans.detach().float(), 0.10)
+    return T

@@ -430,6 +430,34 @@ int gmf_global_registration(gmf_handle* h, const float* X, const float* Y, const
                             double break_threshold_ratio, float* R, float* t, float* stats, int max_points,
                             gmf_stream_t stream);
 
+/* ---- evaluation solvers: correspondence RANSAC and point-to-point ICP (open3d's, as the reference's evaluation calls them) -- */
+
+/* registration_ransac_based_on_correspondence (GMF_PointDSC/evaluation/test_3DMatch.py:76-94; GMF_DeepGlobalRegistration/
+ * .../core/deep_global_registration.py:57-85) over B ragged pairs: row i of src [total_rows,3] corresponds to row i of
+ * tgt; offsets [B+1] (device int32) delimit the pairs; mask [total_rows] (uint8, NULL = every row) picks the rows that take part.
+ * H hypotheses per pair of ransac_n (3..8) distinct rows (the sampler of gmf_amd/csrc/ransac_sampler.hpp, pair index
+ * first_pair + b), each an unweighted fp64 Kabsch fit scored over all participating rows: inlier when |R s + t - q|^2 < tau^2.
+ * The winner has the most inliers, then the smaller sum of their d^2, then the smaller h.  max_rows: the largest pair if known
+ * (sizes the row split; any value is correct).  Out: T_out [B,16], inliers [total_rows] uint8 (the winner's), fitness [B],
+ * inlier_rmse [B], hypothesis [B] int64 (-1: no valid hypothesis, T = identity), sample [B, ransac_n] int64 (rows within
+ * the pair).  No host synchronisation; graph-capturable. */
+int gmf_ransac_correspondence(gmf_handle* h, const float* src, const float* tgt, const int* offsets, const unsigned char* mask,
+                              int B, long long total_rows, int max_rows, int ransac_n, int num_hypotheses, float tau,
+                              unsigned long long seed, int first_pair, float* T_out, unsigned char* inliers, float* fitness,
+                              float* inlier_rmse, long long* hypothesis, long long* sample, gmf_stream_t stream);
+
+/* registration_icp with TransformationEstimationPointToPoint (GMF_PointDSC/evaluation/benchmark_utils.py:40-56;
+ * GMF_DeepGlobalRegistration/.../core/deep_global_registration.py:385-405) over B ragged pairs: src [total_src,3] with
+ * src_offsets [B+1], tgt [sum Nt,3] with tgt_offsets [B+1] (device int32), init [B,16].  C = the exact nearest target row of
+ * each transformed source row with d^2 < tau^2; up to max_iter passes of T <- Umeyama(C) T, stopping when both
+ * |d fitness| < rel_fitness and |d rmse| < rel_rmse.  max_src / max_tgt: the largest pair sizes if known (size the grid; any
+ * value >= 1 is correct).  Out: T_out [B,16], fitness [B], inlier_rmse [B], iterations [B] int32, nn [total_src] int64
+ * (target row within the pair, -1 outside C).  2 max_iter + 4 launches; convergence is decided on the device. */
+int gmf_icp_point_to_point(gmf_handle* h, const float* src, const int* src_offsets, const float* tgt, const int* tgt_offsets,
+                           int B, long long total_src, int max_src, int max_tgt, const float* init, float tau, int max_iter,
+                           double rel_fitness, double rel_rmse, float* T_out, float* fitness, float* inlier_rmse,
+                           int* iterations, long long* nn, gmf_stream_t stream);
+
 /* ---- validation step: the non-test forward's similarity matrix and the metrics of libs/trainer.py:194-262 ---------- */
 
 /* M = clamp(1 - (1 - Fn Fn^T) / sigma^2, 0, 1) with a zero diagonal (GMF_PointDSC/models/PointDSC.py:231-234):

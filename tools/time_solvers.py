@@ -1,0 +1,110 @@
+"""Times the evaluation solvers (gmf_amd/solvers.py) at the sizes the reference's evaluation scripts run them:
+
+  PointDSC RANSAC   one pair, N = 5000 correspondences (~60 % masked in), 5000 hypotheses, ransac_n = 3, tau = 0.10
+  PointDSC ICP      keypoints, N = 5000 / 5000, tau = 0.10, open3d's default criteria (30 passes at most)
+  DGR RANSAC        80 000 hypotheses, ransac_n = 4, N = 8000 and 30 000 correspondences, tau = 0.06
+  DGR ICP           brute-force nearest neighbour, clouds of 10k / 10k and 50k / 50k points, tau = 0.05
+
+Device events around each call, after warm-up; median and spread over repeats.  For RANSAC the row tests per second and the share
+of the fp32 vector peak (15 vector ops per hypothesis-row test, the issue's count, at 157.3 TFLOP/s) are printed too.
+Usage: python tools/time_solvers.py [--repeats 20] [--out FILE]"""
+import argparse
+import os
+import statistics
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import gmf_amd                       # noqa: E402
+from gmf_amd import synthetic        # noqa: E402
+
+PEAK_F32_VECTOR = 157.3e12
+
+
+def timed(fn, repeats, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e3)        # us
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def cloud_pair(N, seed):
+    r = np.random.default_rng([seed, N])
+    X = r.uniform(0, 3, (N, 3))
+    R = synthetic.random_rotation(r)
+    t = r.uniform(-0.5, 0.5, 3)
+    tgt = (X @ R.T + t + r.normal(0, 0.005, X.shape)).astype(np.float32)
+    T0 = np.eye(4, dtype=np.float32)
+    T0[:3, :3], T0[:3, 3] = R, t + 0.02
+    return X.astype(np.float32), tgt, T0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "time_solvers.py measures on a HIP device"
+    dev = "cuda:0"
+    lines = []
+
+    def report(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    report(f"device: {torch.cuda.get_device_name(0)}; median [min, max] over {a.repeats} repeats, device events")
+
+    # PointDSC RANSAC
+    p = synthetic.synthetic_pair(1, 5000)
+    src, tgt = torch.as_tensor(p["src_keypts"]).to(dev)[None], torch.as_tensor(p["tgt_keypts"]).to(dev)[None]
+    r = np.random.default_rng(2)
+    mask = torch.as_tensor(np.where(p["gt_labels"] > 0, r.random(5000) < 0.9, r.random(5000) < 0.55)).to(dev)[None]
+    M = int(mask.sum())
+    med, lo, hi = timed(lambda: gmf_amd.ransac_correspondence_batched(src, tgt, 0.10, mask=mask, ransac_n=3,
+                                                                      num_hypotheses=5000), a.repeats)
+    report(f"PointDSC RANSAC  N=5000 M={M} H=5000 n=3: {med:8.1f} us [{lo:.1f}, {hi:.1f}]  "
+           f"{5000 * M / med * 1e-3:.1f} G row-tests/s")
+
+    # PointDSC ICP
+    T0 = torch.as_tensor(p["gt_trans"]).to(dev)[None]
+    med, lo, hi = timed(lambda: gmf_amd.icp_refine(src, tgt, T0), a.repeats)
+    it = int(gmf_amd.icp_point_to_point_batched(src, tgt, T0, 0.10)[3][0])
+    report(f"PointDSC ICP     N=5000/5000 tau=0.10: {med:8.1f} us [{lo:.1f}, {hi:.1f}]  ({it} passes)")
+
+    # DGR RANSAC
+    for N in (8000, 30000):
+        X, Y = synthetic.dgr_scene(N, 3)[:2]
+        X, Y = X.to(dev)[None], Y.to(dev)[None]
+        med, lo, hi = timed(lambda: gmf_amd.ransac_correspondence_batched(X, Y, 0.06, ransac_n=4, num_hypotheses=80000),
+                            a.repeats)
+        tests = 80000 * N
+        report(f"DGR RANSAC       N={N} H=80000 n=4: {med:8.1f} us [{lo:.1f}, {hi:.1f}]  {tests / med * 1e-3:.0f} G row-tests/s, "
+               f"{100 * tests * 15 / (med * 1e-6) / PEAK_F32_VECTOR:.0f} % of the fp32 vector peak at 15 ops per test")
+
+    # DGR ICP (brute force)
+    for N in (10000, 50000):
+        s, q, T0 = cloud_pair(N, 5)
+        s, q, T0 = torch.as_tensor(s).to(dev)[None], torch.as_tensor(q).to(dev)[None], torch.as_tensor(T0).to(dev)[None]
+        res = gmf_amd.icp_point_to_point_batched(s, q, T0, 0.05)
+        it = int(res[3][0])
+        med, lo, hi = timed(lambda: gmf_amd.icp_point_to_point_batched(s, q, T0, 0.05), max(3, a.repeats // 4), warmup=1)
+        per = med / (it + 1)
+        report(f"DGR ICP          N={N}/{N} tau=0.05: {med:8.1f} us [{lo:.1f}, {hi:.1f}]  ({it} passes, {per:.1f} us per "
+               f"nearest-neighbour pass, {N * N / per * 1e-3:.0f} G distance tests/s)")
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
