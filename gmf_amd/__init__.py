@@ -15,6 +15,9 @@ from . import se3 as SE3                         # noqa: F401
 from ._lib import check_status, set_handle_per_stream   # noqa: F401
 from .solvers import (ransac_correspondence_batched, icp_point_to_point_batched, RegistrationResult,  # noqa: F401
                       registration_ransac_based_on_correspondence, registration_icp, icp_refine)
+from .features import (radius_knn_batched, estimate_normals_batched, compute_fpfh_batched,  # noqa: F401
+                       voxel_down_sample_batched, voxel_select_batched, voxel_down_sample, voxel_select, estimate_normals,
+                       compute_fpfh_feature, fpfh_descriptors)
 from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss, similarity_matrix   # noqa: F401
 
 __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointDSC", "ImageEncoder",
@@ -22,4 +25,6 @@ __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointD
            "find_knn_gpu", "SE3", "ClassificationLoss", "SpectralMatchingLoss", "TransformationLoss",
            "similarity_matrix", "check_status", "set_handle_per_stream", "ransac_correspondence_batched",
            "icp_point_to_point_batched", "RegistrationResult", "registration_ransac_based_on_correspondence", "registration_icp",
-           "icp_refine"]
+           "icp_refine", "radius_knn_batched", "estimate_normals_batched", "compute_fpfh_batched", "voxel_down_sample_batched",
+           "voxel_select_batched", "voxel_down_sample", "voxel_select", "estimate_normals", "compute_fpfh_feature",
+           "fpfh_descriptors"]

@@ -17,6 +17,63 @@
 #include "api_common.hpp"
 #include "launchers_pose.hpp"
 #include "launchers_solvers.hpp"
+#include "launchers_pointcloud.hpp"
+
+namespace {
+
+// the checks every descriptor entry shares
+int check_cloud_args(gmf_handle* h, const char* what, const void* pts, const void* offsets, int B, long long total_rows, double r,
+                     int max_nn) {
+  GMF_REQUIRE(h && pts && offsets, GMF_ERR_BAD_ARG, std::string(what) + ": null pointer");
+  GMF_REQUIRE(B > 0 && total_rows > 0 && total_rows < (1LL << 30) && B <= total_rows, GMF_ERR_UNSUPPORTED_SHAPE,
+              std::string(what) + ": empty batch, more clouds than rows, or 2^30 rows or more");
+  GMF_REQUIRE(r > 0 && std::isfinite(r), GMF_ERR_BAD_ARG, std::string(what) + ": radius / voxel size must be > 0 and finite");
+  GMF_REQUIRE(max_nn >= 1 && max_nn <= gmf::kKnnMaxNN, GMF_ERR_BAD_ARG, std::string(what) + ": max_nn must be in 1..256");
+  return GMF_OK;
+}
+
+// neighbour lists of one descriptor call, in the workspace after the search grid
+struct KnnLists {
+  gmf::KnnScratch ws;
+  int* idx;
+  double* d2;
+  int* count;
+  double* spfh;
+};
+
+int take_knn(gmf_handle* h, long long N, int max_nn, bool spfh, KnnLists& k) {
+  const size_t NK = (size_t)N * max_nn;
+  const size_t grid = gmf::knn_scratch_bytes(N);
+  const size_t need = grid + arena_need(NK, 4) + arena_need(NK, 8) + arena_need(N, 4) + (spfh ? arena_need((size_t)N * 33, 8) : 0);
+  if (int rc = arena_reserve(h, need)) return rc;
+  gmf::knn_scratch_carve(arena_take<char>(h, grid), N, k.ws);
+  k.idx = arena_take<int>(h, NK);
+  k.d2 = arena_take<double>(h, NK);
+  k.count = arena_take<int>(h, N);
+  k.spfh = spfh ? arena_take<double>(h, (size_t)N * 33) : nullptr;
+  return GMF_OK;
+}
+
+int voxel_call(gmf_handle* h, const char* what, const float* pts, const int* offsets, int B, long long total_rows, double voxel,
+               float* out_pts, int* out_idx, int* out_offsets, long long* num_out, gmf_stream_t stream) {
+  if (int rc = check_cloud_args(h, what, pts, offsets, B, total_rows, voxel, 1)) return rc;
+  GMF_REQUIRE((out_pts || out_idx) && out_offsets && num_out, GMF_ERR_BAD_ARG, std::string(what) + ": null pointer");
+  SetDevice sd(h, stream);
+  const size_t need = gmf::voxel_scratch_bytes(total_rows, B);
+  if (int rc = arena_reserve(h, need)) return rc;
+  gmf::VoxelScratch ws;
+  gmf::voxel_scratch_carve(arena_take<char>(h, need), total_rows, B, ws);
+  int host2[2] = {0, 0};
+  GMF_HIP(gmf::launch_voxel(pts, offsets, B, total_rows, voxel, out_pts != nullptr, ws, out_pts, out_idx, out_offsets, host2,
+                            S(stream)));
+  GMF_REQUIRE(host2[1] == 0, GMF_ERR_UNSUPPORTED_SHAPE,
+              std::string(what) + ": a voxel index does not fit in int32 (voxel size too small for the extent) or a coordinate is "
+                                  "not finite");
+  *num_out = host2[0];
+  return GMF_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1167,6 +1224,55 @@ int gmf_icp_point_to_point(gmf_handle* h, const float* src, const int* src_offse
                           max_tgt > 0 ? max_tgt : (int)total_src, init, tau, max_iter, rel_fitness, rel_rmse, ws, T_out, fitness,
                           inlier_rmse, iterations, nn, S(stream)));
   return GMF_OK;
+}
+
+int gmf_radius_knn(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double radius, int max_nn,
+                   int* idx, double* d2, int* count, gmf_stream_t stream) {
+  if (int rc = check_cloud_args(h, "radius_knn", pts, offsets, B, total_rows, radius, max_nn)) return rc;
+  GMF_REQUIRE(idx && count, GMF_ERR_BAD_ARG, "radius_knn: null pointer");
+  SetDevice sd(h, stream);
+  const size_t need = gmf::knn_scratch_bytes(total_rows);
+  if (int rc = arena_reserve(h, need)) return rc;
+  gmf::KnnScratch ws;
+  gmf::knn_scratch_carve(arena_take<char>(h, need), total_rows, ws);
+  GMF_HIP(gmf::launch_radius_knn(pts, offsets, B, total_rows, radius, max_nn, ws, idx, d2, count, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_estimate_normals(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double radius,
+                         int max_nn, float* normals, gmf_stream_t stream) {
+  if (int rc = check_cloud_args(h, "estimate_normals", pts, offsets, B, total_rows, radius, max_nn)) return rc;
+  GMF_REQUIRE(normals, GMF_ERR_BAD_ARG, "estimate_normals: null pointer");
+  SetDevice sd(h, stream);
+  KnnLists k;
+  if (int rc = take_knn(h, total_rows, max_nn, false, k)) return rc;
+  GMF_HIP(gmf::launch_radius_knn(pts, offsets, B, total_rows, radius, max_nn, k.ws, k.idx, nullptr, k.count, S(stream)));
+  GMF_HIP(gmf::launch_normals(pts, offsets, B, total_rows, k.idx, k.count, max_nn, normals, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_compute_fpfh(gmf_handle* h, const float* pts, const float* normals, const int* offsets, int B, long long total_rows,
+                     double radius, int max_nn, float* features, gmf_stream_t stream) {
+  if (int rc = check_cloud_args(h, "compute_fpfh", pts, offsets, B, total_rows, radius, max_nn)) return rc;
+  GMF_REQUIRE(normals && features, GMF_ERR_BAD_ARG, "compute_fpfh: null pointer");
+  SetDevice sd(h, stream);
+  KnnLists k;
+  if (int rc = take_knn(h, total_rows, max_nn, true, k)) return rc;
+  GMF_HIP(gmf::launch_radius_knn(pts, offsets, B, total_rows, radius, max_nn, k.ws, k.idx, k.d2, k.count, S(stream)));
+  GMF_HIP(gmf::launch_fpfh(pts, normals, offsets, B, total_rows, k.idx, k.d2, k.count, max_nn, k.spfh, features, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_voxel_down_sample(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double voxel,
+                          float* out_pts, int* out_offsets, long long* num_out, gmf_stream_t stream) {
+  GMF_REQUIRE(out_pts, GMF_ERR_BAD_ARG, "voxel_down_sample: null pointer");
+  return voxel_call(h, "voxel_down_sample", pts, offsets, B, total_rows, voxel, out_pts, nullptr, out_offsets, num_out, stream);
+}
+
+int gmf_voxel_select(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double voxel,
+                     int* out_idx, int* out_offsets, long long* num_out, gmf_stream_t stream) {
+  GMF_REQUIRE(out_idx, GMF_ERR_BAD_ARG, "voxel_select: null pointer");
+  return voxel_call(h, "voxel_select", pts, offsets, B, total_rows, voxel, nullptr, out_idx, out_offsets, num_out, stream);
 }
 
 int gmf_similarity_matrix(gmf_handle* h, const float* feat_n, int B, int N, float sigma, float* M, int ldm,

@@ -458,6 +458,44 @@ int gmf_icp_point_to_point(gmf_handle* h, const float* src, const int* src_offse
                            double rel_fitness, double rel_rmse, float* T_out, float* fitness, float* inlier_rmse,
                            int* iterations, long long* nn, gmf_stream_t stream);
 
+/* ---- point-cloud descriptors: radius kNN, normals, FPFH, voxel grids (open3d's, as the reference's feature scripts call them) -- */
+
+/* Radius-bounded k nearest (open3d KDTreeFlann::SearchHybrid) over B ragged clouds: pts [total_rows,3] (float32), offsets
+ * [B+1] (device int32).  For every row, up to max_nn (1..256) rows of the same cloud with d^2 < radius^2, the row itself
+ * included, the smallest in the total order of (d^2, row).  d^2 = (dx dx + dy dy) + dz dz in fp64 from the fp32 coordinates,
+ * each operation rounded on its own.  Out, sorted by that key: idx [total_rows, max_nn] int32 (row within the cloud, -1
+ * padding), d2 [total_rows, max_nn] float64 (0 padding; may be NULL), count [total_rows] int32.  Hashed uniform grid sized
+ * from total_rows alone; no host synchronisation, graph-capturable. */
+int gmf_radius_knn(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double radius, int max_nn,
+                   int* idx, double* d2, int* count, gmf_stream_t stream);
+
+/* open3d estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) without prior normals: the neighbour set of gmf_radius_knn;
+ * with >= 3 neighbours the fp64 covariance E[x x^T] - mu mu^T and the eigenvector of its smallest eigenvalue by open3d's
+ * FastEigen3x3 (sign as that algorithm yields it), else (0, 0, 1).  normals [total_rows,3] float32.  No host synchronisation. */
+int gmf_estimate_normals(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double radius,
+                         int max_nn, float* normals, gmf_stream_t stream);
+
+/* open3d compute_fpfh_feature(KDTreeSearchParamHybrid(radius, max_nn)): the neighbour set of gmf_radius_knn, the query excluded
+ * by index; SPFH from the fp64 pair features (11 bins per angle), FPFH = the SPFH of the neighbours weighted by 1 / d^2, each
+ * 11-bin block renormalised to 100, plus the row's own SPFH.  features [total_rows,33] float32 (row-major; open3d's is
+ * [33,N]).  Fixed summation order: bitwise repeatable.  No host synchronisation. */
+int gmf_compute_fpfh(gmf_handle* h, const float* pts, const float* normals, const int* offsets, int B, long long total_rows,
+                     double radius, int max_nn, float* features, gmf_stream_t stream);
+
+/* open3d voxel_down_sample(voxel): per cloud the grid origin min(pts) - voxel/2, the voxel of a row floor((p - origin) /
+ * voxel), out_pts [<= total_rows,3] the fp64 mean of each voxel's rows (summed in ascending row order) stored as float32, the
+ * voxels of a cloud in first-occurrence order (by their smallest row).  out_offsets [B+1] (device int32), *num_out (host) the
+ * number of voxels.  Synchronises the stream once (the count); GMF_ERR_UNSUPPORTED_SHAPE when a voxel index leaves int32 or
+ * a coordinate is not finite. */
+int gmf_voxel_down_sample(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double voxel,
+                          float* out_pts, int* out_offsets, long long* num_out, gmf_stream_t stream);
+
+/* MinkowskiEngine sparse_quantize(pts / voxel, return_index=True) as DGR's preprocess calls it: the voxel floor(p / voxel),
+ * out_idx [<= total_rows] int32 the smallest row (within its cloud) of each voxel, ascending per cloud.  out_offsets, num_out
+ * and the errors as gmf_voxel_down_sample. */
+int gmf_voxel_select(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double voxel,
+                     int* out_idx, int* out_offsets, long long* num_out, gmf_stream_t stream);
+
 /* ---- validation step: the non-test forward's similarity matrix and the metrics of libs/trainer.py:194-262 ---------- */
 
 /* M = clamp(1 - (1 - Fn Fn^T) / sigma^2, 0, 1) with a zero diagonal (GMF_PointDSC/models/PointDSC.py:231-234):
