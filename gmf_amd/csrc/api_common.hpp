@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -107,6 +108,21 @@ T* arena_take(gmf_handle* h, size_t count) {
 }
 
 inline size_t arena_need(size_t count, size_t elem) { return align_up(count * elem, 256) + 256; }
+
+// One buffer of a call's workspace: `count` elements of T into `*slot` (count 0: no buffer, *slot = null).  A call lists its buffers
+// once, in arena_carve: the reservation is the sum of the list and the carving follows it, so the two cannot disagree.
+struct ArenaBuf { void* slot; size_t count, elem; void (*set)(void* slot, char* p); };
+template <typename T>
+ArenaBuf arena_buf(T*& slot, size_t count) {
+  return {&slot, count, sizeof(T), [](void* sl, char* p) { *static_cast<T**>(sl) = reinterpret_cast<T*>(p); }};
+}
+inline int arena_carve(gmf_handle* h, std::initializer_list<ArenaBuf> bufs) {
+  size_t need = 0;
+  for (const ArenaBuf& b : bufs) need += b.count ? arena_need(b.count, b.elem) : 0;
+  if (int rc = arena_reserve(h, need)) return rc;
+  for (const ArenaBuf& b : bufs) b.set(b.slot, b.count ? arena_take<char>(h, b.count * b.elem) : nullptr);
+  return GMF_OK;
+}
 
 inline hipStream_t S(gmf_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 inline int tiles_of(int n) { return (n + 31) / 32; }

@@ -1035,11 +1035,10 @@ k_ff_reduce(const float* __restrict__ part, const float* __restrict__ x1, const 
 // -----------------------------------------------------------------------------------------
 static inline dim3 tgrid(int tiles, int B, int sets = 1) { return dim3((tiles + kWavesPerWG - 1) / kWavesPerWG, B, sets); }
 
-hipError_t launch_front_h2(const Tuning& tune, int mode, const float* in, const float* wst, const float* vecs, float* f,
-                           float* q, float* k, float* v, int B, int N, int tiles, hipStream_t s, const PairTab* ptab, unsigned* v_scale,
-                           PvGuard guard) {
+hipError_t launch_front_h2(int mode, bool split, const float* in, const float* wst, const float* vecs, float* f, float* q, float* k,
+                           float* v, int B, int N, int tiles, hipStream_t s, const PairTab* ptab, unsigned* v_scale, PvGuard guard) {
   dim3 g = tgrid(tiles, B);
-  if (g.x * B < 128 && tune.front_split) g.z = 3;      // small grids: one workgroup per output (Q' + f | K | V)
+  if (split) g.z = 3;
   if (mode == 3) { g.z = 1; hipLaunchKernelGGL(k_front_h2<3>, g, dim3(256), 0, s, in, wst, vecs, f, q, k, v, N, tiles, ptab, v_scale, guard); }
   else if (mode == 1) hipLaunchKernelGGL(k_front_h2<1>, g, dim3(256), 0, s, in, wst, vecs, f, q, k, v, N, tiles, ptab, v_scale, guard);
   else if (mode == 2) hipLaunchKernelGGL(k_front_h2<2>, g, dim3(256), 0, s, in, wst, vecs, f, q, k, v, N, tiles, ptab, v_scale, guard);
@@ -1047,13 +1046,11 @@ hipError_t launch_front_h2(const Tuning& tune, int mode, const float* in, const 
   return hipGetLastError();
 }
 
-hipError_t launch_linear_h2(const Tuning& tune, const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
+hipError_t launch_linear_h2(bool roles, const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
                             const float* attn_wst, const float* attn_vec, const float* ff_wst, const float* ff_vec, float* q,
                             float* k, float* v, float* x2, int B, int N, int tiles, int T, int ttiles, hipStream_t s,
                             bool one_product, const PairTab* ptab, unsigned* v_scale, PvGuard guard) {
-  // grids that give a CU about one workgroup: two roles per row block (the Q'/K/V projections | Fusion-2) in one launch
-  const int W = ((tiles + 3) / 4) * B;
-  if (tune.mid_grid_roles > 0 && W < tune.mid_grid_roles && q)
+  if (roles)
     hipLaunchKernelGGL(k_linear_roles, tgrid(tiles, B, 2), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec,
                        ff_wst, ff_vec, q, k, v, x2, N, tiles, T, ttiles, v_scale, guard, ptab);
   else if (one_product)                            // throughput numerics mode: high planes only
@@ -1109,13 +1106,10 @@ hipError_t launch_pro_fattn_compat(const float* q_tokens, const float* f1ctx, co
   return hipGetLastError();
 }
 
-// returns through *hs_out the hidden splits of the feed-forward role (> 1: the caller runs launch_ff_reduce_h2 next)
-hipError_t launch_pro_ff_front(const Tuning& tune, const float* x1t, const float* wst, const float* vecs, float* imgfeat, int B,
-                               int ttiles, float* part, int max_parts, const float* corr_pos, const float* fwst, const float* fvecs,
-                               float* f, float* q, float* k, float* v, int N, int tiles, hipStream_t s, const PairTab* ptab,
-                               PvGuard guard, int* hs_out) {
+hipError_t launch_pro_ff_front(const float* x1t, const float* wst, const float* vecs, float* imgfeat, int B, int ttiles, float* part,
+                               int hs, const float* corr_pos, const float* fwst, const float* fvecs, float* f, float* q, float* k,
+                               float* v, int N, int tiles, hipStream_t s, const PairTab* ptab, PvGuard guard) {
   const dim3 ga = tgrid(ttiles, B), gf = tgrid(tiles, B);
-  const int hs = part ? plan_ff_split(tune, ga.x * B, max_parts) : 1;
   const int n_a = (int)(ga.x * B) * hs, n_b = (int)(gf.x * B);
 #define GMF_PRO_C(SPLIT, MINB, HS, PART)                                                                                              \
   hipLaunchKernelGGL((k_pro_ff_front<SPLIT, MINB>), dim3(n_a + n_b), dim3(256), 0, s, n_a, (int)ga.x, B, HS, x1t, wst, vecs, imgfeat, ttiles, \
@@ -1124,7 +1118,6 @@ hipError_t launch_pro_ff_front(const Tuning& tune, const float* x1t, const float
   if (hs > 1) { if (one_per_cu) GMF_PRO_C(true, 1, hs, part); else GMF_PRO_C(true, 2, hs, part); }
   else { if (one_per_cu) GMF_PRO_C(false, 1, 1, (float*)nullptr); else GMF_PRO_C(false, 2, 1, (float*)nullptr); }
 #undef GMF_PRO_C
-  *hs_out = hs;
   return hipGetLastError();
 }
 
@@ -1132,18 +1125,6 @@ hipError_t launch_ff_reduce_h2(const float* part, const float* x1, const float* 
   const dim3 g = tgrid(tiles, B);
   hipLaunchKernelGGL(k_ff_reduce, dim3(g.x, g.y, 4), dim3(256), 0, s, part, x1, vecs, x2, tiles, hs);
   return hipGetLastError();
-}
-
-// hidden splits of the feed-forward on a grid of `base` workgroups (tune.ff_split: 0 = automatic, 1 = off, 2 / 4 / 8 = forced)
-int plan_ff_split(const Tuning& tune, int base, int max_parts) {
-  int hs = 1;
-  if (max_parts >= 2) {
-    if (tune.ff_split > 0) hs = tune.ff_split;
-    else if (base < 256) hs = base <= 32 ? 8 : base <= 64 ? 4 : 2;   // (measured at B = 1 .. 4: the merge reads every partial)
-    hs = std::min(hs, max_parts);
-    if (hs != 2 && hs != 4 && hs != 8) hs = 1;
-  }
-  return hs;
 }
 
 hipError_t launch_small_front_fattn(const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
@@ -1158,11 +1139,10 @@ hipError_t launch_small_front_fattn(const float* f, const float* front_wst, cons
   return hipGetLastError();
 }
 
-hipError_t launch_fusion_ff_h2(const Tuning& tune, const float* x1, const float* wst, const float* vecs, float* x2, int B,
-                               int tiles, hipStream_t s, float* part, int max_parts) {
+hipError_t launch_fusion_ff_h2(const float* x1, const float* wst, const float* vecs, float* x2, int B, int tiles, hipStream_t s,
+                               float* part, int hs) {
   const dim3 g = tgrid(tiles, B);
   // small grids: divide the 16 hidden chunks over 2 / 4 / 8 workgroups (deterministic two-pass sum)
-  const int hs = part ? plan_ff_split(tune, g.x * B, max_parts) : 1;
   if (hs > 1) {
     hipLaunchKernelGGL(k_fusion_ff_h2p<true>, dim3(g.x, g.y, hs), dim3(256), 0, s, x1, wst, vecs, x2, tiles, part);
     hipLaunchKernelGGL(k_ff_reduce, dim3(g.x, g.y, 4), dim3(256), 0, s, part, x1, vecs, x2, tiles, hs);

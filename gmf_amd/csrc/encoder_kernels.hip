@@ -2292,18 +2292,6 @@ __global__ void k_pack_pts8(const float* __restrict__ src, const float* __restri
 
 namespace gmf {
 
-// compute units of the current device (256 on MI355X); queried once per process and device
-static int cu_count() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 256;
-  static int cached[16] = {0};
-  if (dev >= 0 && dev < 16 && cached[dev] > 0) return cached[dev];
-  int n = 0;
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  if (dev >= 0 && dev < 16) cached[dev] = n;
-  return n;
-}
-
 static inline dim3 tile_grid(int tiles, int B, int sets = 1) { return dim3((tiles + kWavesPerWG - 1) / kWavesPerWG, B, sets); }
 
 hipError_t launch_front(int mode, const float* in, const float* wst, const float* vecs, float* f, float* q, float* k,
@@ -2335,35 +2323,9 @@ hipError_t launch_scattn_fp32(const float* q, const float* k, const float* v, co
   return hipGetLastError();
 }
 
-// Work split of the attention grid (attn_item): W items on `slots` resident workgroups (2 per CU).  n_full = items per XCD
-// that run whole; the rest are split `ksplits` ways by key range (ksplits = 1: none).
-void plan_attn_split(const Tuning& tune, int W, int tiles, int max_splits, int* n_full_out, int* ksplits_out) {
-  const int slots = 2 * cu_count();
-  const int per_xcd = (W >> 3) + ((W & 7) ? 1 : 0);
-  int n_full = per_xcd, ksplits = 1;                                    // default: every item whole
-  if (max_splits > 1 && tiles >= 8) {
-    const int cap = std::min(max_splits, std::max(1, tiles / 4));
-    if (tune.key_splits > 1) { n_full = 0; ksplits = std::min(tune.key_splits, cap); }             // forced: every item split
-    else if (tune.key_splits == 0) {
-      // small grid: ONE workgroup per CU - a workgroup alone on its CU runs its tiles almost twice as fast as two
-      // co-resident ones (B = 1, N = 5000: 6 splits = 240 workgroups 1.64 ms per forward, 8 splits = 320 workgroups 1.75 ms)
-      if (W < slots / 2) { n_full = 0; ksplits = std::min(std::max(2, (slots / 2) / W), cap); }
-      else if (W < 3 * slots / 4 && tiles >= 64) { n_full = 0; ksplits = std::min(2, cap); }       // measured break-even
-      else if (W > slots && tune.tail_split) {
-        // large grid: whole rounds run whole; a last partial round of at most half the slots is split to fill them
-        const int full = (W / slots) * slots, rest = W - full;
-        if (rest > 0 && 2 * rest <= slots && tiles >= 16) { n_full = full / 8; ksplits = std::min(std::min(slots / rest, 4), cap); }
-      }
-    }
-    if (ksplits <= 1) { n_full = per_xcd; ksplits = 1; }
-  }
-  *n_full_out = n_full;
-  *ksplits_out = ksplits;
-}
-
 // Small grids, launches two and three of a layer (after k_small_front_fattn): key-split attention workgroups beside the
 // hidden-split feed-forward workgroups, then the merge kernel (partials of both -> block output / next layer's f).
-// Preconditions (checked by the caller with plan_attn_split / plan_ff_split): every attention item is split, ff_hs > 1.
+// Preconditions (the forward's plan, gmf_api.cpp): every attention item is split, ff_hs > 1.
 hipError_t launch_small_attn_ff_merge(const float* q, const float* k, const float* v, const float* x1, const float* ff_wst,
                                       const float* ff_vecs, float* ff_part, int ff_hs, const float* tail_vecs, float* out, int B,
                                       int N, int tiles, int ksplits, hipStream_t s, const CompatCache* cc, bool tile_merge) {
@@ -2393,55 +2355,49 @@ hipError_t launch_small_attn_ff_merge(const float* q, const float* k, const floa
   return hipGetLastError();
 }
 
-// Split-fp16 plane images of Q', K, V (k_front_h2 / k_linear_h2).  tune.scattn_variant:
-//   18 (default) = k_scattn_h2p: c streamed from the compat cache, tile loop software-pipelined inside each wave, split-fp16
-//                  fc_message epilogue; on small grids the keys of a query block are divided over several workgroups
-//                  (KSPLIT form) and k_scattn_merge finishes.  Needs cc->dense and cc->tail_wst_h2; otherwise:
-//   9            = k_scattn_h2: not pipelined, c from the cache when there is one, else recomputed per (i, j) from pts8
-//                  (the fallback when the cache would not fit); fp32-MFMA fc_message epilogue (wst = fp32 images).
-hipError_t launch_scattn_h2(const Tuning& tune, const float* q, const float* k, const float* v, const float* pts8,
-                            const float* fus, const float* wst, const float* vecs, float* out, int B, int N, int tiles,
-                            float sigma_d, hipStream_t s, const CompatCache* cc) {
+// Split-fp16 plane images of Q', K, V (k_front_h2 / k_linear_h2).
+// launch_scattn_h2p (scattn_variant 18, the default): k_scattn_h2p - c streamed from the compat cache, tile loop software-pipelined
+//   inside each wave, split-fp16 fc_message epilogue; the items beyond n_full per XCD are divided by keys over `ksplits` workgroups
+//   (KSPLIT form) and k_scattn_merge finishes.
+// launch_scattn_h2 (scattn_variant 9): k_scattn_h2 - not pipelined, c from the cache when there is one (c_dense), else recomputed per
+//   (i, j) from pts8 (also the fallback when the cache would not fit); fp32-MFMA fc_message epilogue (wst = fp32 images).
+hipError_t launch_scattn_h2p(const float* q, const float* k, const float* v, const float* fus, const float* vecs, float* out, int B,
+                             int N, int tiles, hipStream_t s, const CompatCache& cc, int n_full, int ksplits) {
+  const int wpp = (tiles + 3) / 4, W = wpp * B;
+  const int per_xcd = (W >> 3) + ((W & 7) ? 1 : 0);
+  const int max_tail = std::max(0, per_xcd - n_full);
+  const dim3 grid(8 * (std::min(n_full, per_xcd) + max_tail * ksplits));
+  if (cc.half && max_tail == 0)   // throughput numerics mode, whole items only: the three-tiles-in-flight form
+    hipLaunchKernelGGL(k_scattn_fast, dim3(8 * per_xcd), dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense, W,
+                       cc.next_wst_h2, cc.next_bias);
+  else if (cc.half)  // ... with a split tail: one fp16 product, c streamed as fp16 (the cache was built that way)
+    hipLaunchKernelGGL((k_scattn_h2p<1, 1>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense, W,
+                       n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, PvGuard{});
+  else if (cc.fmt == 2 && cc.v_scale)   // parity arithmetic, c streamed as 16-bit fixed point; fp8 cross products of P V
+    hipLaunchKernelGGL((k_scattn_h2p<3, 2, true>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
+                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, cc.v_scale, cc.qf_img, cc.qw_wst, cc.qw_bias, cc.guard);
+  else if (cc.fmt == 2)
+    hipLaunchKernelGGL((k_scattn_h2p<3, 2>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
+                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, cc.qf_img, cc.qw_wst, cc.qw_bias, PvGuard{});
+  else if (cc.v_scale)    // the default: V image with e4m3 cross planes (k_linear_h2 wrote it that way)
+    hipLaunchKernelGGL((k_scattn_h2p<3, 0, true>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
+                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, cc.v_scale, cc.qf_img, cc.qw_wst, cc.qw_bias, cc.guard);
+  else
+    hipLaunchKernelGGL((k_scattn_h2p<3, 0>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
+                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, cc.qf_img, cc.qw_wst, cc.qw_bias, PvGuard{});
+  if (max_tail > 0)
+    hipLaunchKernelGGL(k_scattn_merge, dim3(8 * max_tail), dim3(256), 0, s, cc.part_o, cc.part_ml, fus, cc.tail_wst_h2, vecs, out,
+                       tiles, wpp, W, n_full, ksplits, cc.next_wst_h2, cc.next_bias, (const float*)nullptr, 0,
+                       (const float*)nullptr, (const float*)nullptr, cc.guard.stat_next, N, cc.ptab);
+  return hipGetLastError();
+}
+
+hipError_t launch_scattn_h2(const float* q, const float* k, const float* v, const float* pts8, const float* fus, const float* wst,
+                            const float* vecs, float* out, int B, int N, int tiles, float sigma_d, hipStream_t s, const float* c_dense) {
   const float inv = 1.0f / (sigma_d * sigma_d);
   const int wpp = (tiles + 3) / 4;
-  const dim3 grid4(wpp * B);
-  const float* cd = (cc && tune.use_cache) ? cc->dense : nullptr;
-  if (tune.scattn_variant == 18 && cd && cc->tail_wst_h2) {
-    const int W = wpp * B;
-    const int per_xcd = (W >> 3) + ((W & 7) ? 1 : 0);
-    int n_full, ksplits;
-    // ragged batch: planned on the SMALLEST pair's tiles (every pair then has at least four key tiles per split); either every item is
-    // split - small grids: a handful of whole items walking all their keys alone left most of the chip idle (4 pairs x 1000: 1.50 ms
-    // against 0.74 for the uniform batch) - or none is (the split tail of large grids assumes items of one length)
-    plan_attn_split(tune, W, cc->ptab ? cc->min_tiles : tiles, cc->part_o ? cc->max_splits : 0, &n_full, &ksplits);
-    if (cc->ptab && n_full != 0) { n_full = per_xcd; ksplits = 1; }
-    const int max_tail = std::max(0, per_xcd - n_full);
-    const dim3 grid(8 * (std::min(n_full, per_xcd) + max_tail * ksplits));
-    if (cc->half && max_tail == 0)   // throughput numerics mode, whole items only: the three-tiles-in-flight form
-      hipLaunchKernelGGL(k_scattn_fast, dim3(8 * per_xcd), dim3(256), 0, s, q, k, v, fus, cc->tail_wst_h2, vecs, out, N, tiles, wpp, cd, W,
-                         cc->next_wst_h2, cc->next_bias);
-    else if (cc->half)  // ... with a split tail: one fp16 product, c streamed as fp16 (the cache was built that way)
-      hipLaunchKernelGGL((k_scattn_h2p<1, 1>), grid, dim3(256), 0, s, q, k, v, fus, cc->tail_wst_h2, vecs, out, N, tiles, wpp, cd, W,
-                         n_full, ksplits, cc->part_o, cc->part_ml, cc->next_wst_h2, cc->next_bias, cc->ptab, (const unsigned*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, PvGuard{});
-    else if (cc->fmt == 2 && cc->v_scale)   // parity arithmetic, c streamed as 16-bit fixed point; fp8 cross products of P V
-      hipLaunchKernelGGL((k_scattn_h2p<3, 2, true>), grid, dim3(256), 0, s, q, k, v, fus, cc->tail_wst_h2, vecs, out, N, tiles, wpp, cd,
-                         W, n_full, ksplits, cc->part_o, cc->part_ml, cc->next_wst_h2, cc->next_bias, cc->ptab, cc->v_scale, cc->qf_img, cc->qw_wst, cc->qw_bias, cc->guard);
-    else if (cc->fmt == 2)
-      hipLaunchKernelGGL((k_scattn_h2p<3, 2>), grid, dim3(256), 0, s, q, k, v, fus, cc->tail_wst_h2, vecs, out, N, tiles, wpp, cd,
-                         W, n_full, ksplits, cc->part_o, cc->part_ml, cc->next_wst_h2, cc->next_bias, cc->ptab, (const unsigned*)nullptr, cc->qf_img, cc->qw_wst, cc->qw_bias, PvGuard{});
-    else if (cc->v_scale)    // the default: V image with e4m3 cross planes (k_linear_h2 wrote it that way)
-      hipLaunchKernelGGL((k_scattn_h2p<3, 0, true>), grid, dim3(256), 0, s, q, k, v, fus, cc->tail_wst_h2, vecs, out, N, tiles, wpp, cd,
-                         W, n_full, ksplits, cc->part_o, cc->part_ml, cc->next_wst_h2, cc->next_bias, cc->ptab, cc->v_scale, cc->qf_img, cc->qw_wst, cc->qw_bias, cc->guard);
-    else
-      hipLaunchKernelGGL((k_scattn_h2p<3, 0>), grid, dim3(256), 0, s, q, k, v, fus, cc->tail_wst_h2, vecs, out, N, tiles, wpp, cd,
-                         W, n_full, ksplits, cc->part_o, cc->part_ml, cc->next_wst_h2, cc->next_bias, cc->ptab, (const unsigned*)nullptr, cc->qf_img, cc->qw_wst, cc->qw_bias, PvGuard{});
-    if (max_tail > 0)
-      hipLaunchKernelGGL(k_scattn_merge, dim3(8 * max_tail), dim3(256), 0, s, cc->part_o, cc->part_ml, fus, cc->tail_wst_h2, vecs, out,
-                         tiles, wpp, W, n_full, ksplits, cc->next_wst_h2, cc->next_bias, (const float*)nullptr, 0,
-                         (const float*)nullptr, (const float*)nullptr, cc->guard.stat_next, N, cc->ptab);
-  }
-  else if (cd) hipLaunchKernelGGL(k_scattn_h2<true>, grid4, dim3(256), 0, s, q, k, v, pts8, fus, wst, vecs, out, N, tiles, inv, wpp, cd);
-  else hipLaunchKernelGGL(k_scattn_h2<false>, grid4, dim3(256), 0, s, q, k, v, pts8, fus, wst, vecs, out, N, tiles, inv, wpp, cd);
+  if (c_dense) hipLaunchKernelGGL(k_scattn_h2<true>, dim3(wpp * B), dim3(256), 0, s, q, k, v, pts8, fus, wst, vecs, out, N, tiles, inv, wpp, c_dense);
+  else hipLaunchKernelGGL(k_scattn_h2<false>, dim3(wpp * B), dim3(256), 0, s, q, k, v, pts8, fus, wst, vecs, out, N, tiles, inv, wpp, c_dense);
   return hipGetLastError();
 }
 

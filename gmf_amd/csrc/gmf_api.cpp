@@ -421,35 +421,147 @@ static int check_weights(gmf_handle* h, const gmf_encoder_weights* w) {
   return GMF_OK;
 }
 
-// split-fp16 path: needs every split-fp16 weight image; the dense-`attention` drop-in and scattn_variant 0 run on fp32 images
-static bool use_h2(const gmf_handle* h, const gmf_encoder_weights* w, bool dense) {
-  return !dense && h->tune.scattn_variant >= 9 && w->front_wst_h2 && w->ctx_wst_h2 && w->attn_wst_h2 && w->ff_wst_h2 && w->tail_wst_h2;
+// compute units of the current device (256 on MI355X); queried once per process and device
+static int cu_count() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 256;
+  static int cached[16] = {0};
+  if (dev >= 0 && dev < 16 && cached[dev] > 0) return cached[dev];
+  int n = 0;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+  if (dev >= 0 && dev < 16) cached[dev] = n;
+  return n;
 }
 
-static int run_scattn(gmf_handle* h, const gmf_encoder_weights* w, int l, const float* q, const float* k, const float* v,
-                      const float* pts8, const float* x2, float* out, int B, int N, hipStream_t st, const float* dense_compat,
-                      const gmf::CompatCache* cc);
-
-// Runs Fusion-2 + the spatial-consistency block of layer `l` given f,q,k,v.
-static int run_block_tail(gmf_handle* h, const gmf_encoder_weights* w, int l, const float* f, const float* q,
-                          const float* k, const float* v, const float* pts8, const float* ctx_l, float* x1, float* x2,
-                          float* out, int B, int N, int T, hipStream_t st, const float* dense_compat = nullptr,
-                          const gmf::CompatCache* cc = nullptr) {
-  const int tiles = tiles_of(N), tt = tiles_of(T);
-  const bool h2 = use_h2(h, w, dense_compat != nullptr);
-  if (h2) {
-    GMF_HIP(gmf::launch_fusion_attn_h2(true, f, ctx_l, w->attn_wst_h2 + (size_t)l * w->attn_wst_stride,
-                                       w->attn_vec + (size_t)l * w->attn_vec_stride, x1, B, N, tiles, T, tt, st));
-    GMF_HIP(gmf::launch_fusion_ff_h2(h->tune, x1, w->ff_wst_h2 + (size_t)l * w->ff_wst_stride,
-                                     w->ff_vec + (size_t)l * w->ff_vec_stride, x2, B, tiles, st,
-                                     cc ? cc->part_o : nullptr, cc ? cc->max_splits : 0));   // the attention's partial buffer is free here
-  } else {
-    GMF_HIP(gmf::launch_fusion_attn(true, f, ctx_l, w->attn_wst + (size_t)l * w->attn_wst_stride,
-                                    w->attn_vec + (size_t)l * w->attn_vec_stride, x1, B, N, tiles, T, tt, st));
-    GMF_HIP(gmf::launch_fusion_ff(x1, w->ff_wst + (size_t)l * w->ff_wst_stride, w->ff_vec + (size_t)l * w->ff_vec_stride,
-                                  x2, B, tiles, st));
+// Work split of the attention grid (attn_item): W items on `slots` resident workgroups (2 per CU).  n_full = items per XCD
+// that run whole; the rest are split `ksplits` ways by key range (ksplits = 1: none).
+static void plan_attn_split(const gmf::Tuning& tune, int cus, int W, int tiles, int max_splits, bool ragged, int* n_full_out,
+                            int* ksplits_out) {
+  const int slots = 2 * cus;
+  const int per_xcd = (W >> 3) + ((W & 7) ? 1 : 0);
+  int n_full = per_xcd, ksplits = 1;                                    // default: every item whole
+  if (max_splits > 1 && tiles >= 8) {
+    const int cap = std::min(max_splits, std::max(1, tiles / 4));
+    if (tune.key_splits > 1) { n_full = 0; ksplits = std::min(tune.key_splits, cap); }             // forced: every item split
+    else if (tune.key_splits == 0) {
+      // small grid: ONE workgroup per CU - a workgroup alone on its CU runs its tiles almost twice as fast as two
+      // co-resident ones (B = 1, N = 5000: 6 splits = 240 workgroups 1.64 ms per forward, 8 splits = 320 workgroups 1.75 ms)
+      if (W < slots / 2) { n_full = 0; ksplits = std::min(std::max(2, (slots / 2) / W), cap); }
+      else if (W < 3 * slots / 4 && tiles >= 64) { n_full = 0; ksplits = std::min(2, cap); }       // measured break-even
+      else if (W > slots && tune.tail_split && !ragged) {
+        // large grid: whole rounds run whole; a last partial round of at most half the slots is split to fill them (the split
+        // tail assumes items of one length: not for ragged batches)
+        const int full = (W / slots) * slots, rest = W - full;
+        if (rest > 0 && 2 * rest <= slots && tiles >= 16) { n_full = full / 8; ksplits = std::min(std::min(slots / rest, 4), cap); }
+      }
+    }
+    if (ksplits <= 1) { n_full = per_xcd; ksplits = 1; }
   }
-  return run_scattn(h, w, l, q, k, v, pts8, x2, out, B, N, st, dense_compat, cc);
+  *n_full_out = n_full;
+  *ksplits_out = ksplits;
+}
+
+// hidden splits of the feed-forward on a grid of `base` workgroups (tune.ff_split: 0 = automatic, 1 = off, 2 / 4 / 8 = forced)
+static int plan_ff_split(const gmf::Tuning& tune, int base, int max_parts) {
+  int hs = 1;
+  if (max_parts >= 2) {
+    if (tune.ff_split > 0) hs = tune.ff_split;
+    else if (base < 256) hs = base <= 32 ? 8 : base <= 64 ? 4 : 2;   // (measured at B = 1 .. 4: the merge reads every partial)
+    hs = std::min(hs, max_parts);
+    if (hs != 2 && hs != 4 && hs != 8) hs = 1;
+  }
+  return hs;
+}
+
+// How one encoder forward runs: every launch decision, made once (plan_encoder) from the handle's knobs, the weight images
+// present and the shape, with the sizes of the buffers that depend on them.  The launchers are told; none reads the knobs.
+struct EncoderPlan {
+  enum Form {
+    kFp32,          // fp32 images and kernels for every stage (split-fp16 weight images missing, "scattn_variant" 0, dense attention)
+    kStages,        // split-fp16, one kernel per stage; the attention writes the block output
+    kFusedStages,   // the cached, pipelined attention applies the next layer's PointCN in its epilogue; one kernel per other stage
+    kLinear,        // ... and k_linear_h2 for Q'/K/V + Fusion-2: two launches per layer (the default)
+    kSmall3,        // ... small grids: three launches per layer with two workgroup roles each
+  };
+  Form form = kFp32;
+  bool fused() const { return form >= kFusedStages; }
+  bool f1_h2 = false;        // Fusion-1 on split-fp16 images
+  bool prologue = false;     // small grids: the prologue's two chains as roles of three shared launches (k_pro_*)
+  bool cache = false;        // compat cache, built once per batch
+  bool pipelined = false;    // attention: k_scattn_h2p streaming c from the cache (scattn_variant 18)
+  int fmt = 0;               // the cache's element format (CompatCache::fmt)
+  bool half = false;         // throughput numerics (CompatCache::half) ...
+  bool one_product = false;  // ... and the linear stages multiply one product as well ("precision" = 2)
+  bool front_split = false;  // k_front_h2 with one workgroup per output
+  int max_splits = 0;        // capacity of the key- and hidden-split partials (0: no workspace for them)
+  int attn_nf = 0, attn_ks = 1;   // attention items per XCD that run whole, key splits of the rest
+  int ff_hs = 1, f1_ff_hs = 1;    // hidden splits of the layers' feed-forward and of Fusion-1's
+  bool roles = false;        // k_linear_h2 as two workgroup roles per row block
+  bool q_in_attn = false;    // no Q' image: the attention projects its own (CompatCache::qf_img)
+  bool v_fp8 = false;        // V carries e4m3 cross planes (CompatCache::v_scale) ...
+  bool guard = false;        // ... chosen per pair and layer on the device (PvGuard)
+  bool clear_stats = false;  // the key-point packing clears the guard's statistics
+  size_t act = 0, tok = 0, cache_floats = 0;   // floats of an activation image, a token image, the cache
+};
+
+// min_tiles > 0: a ragged batch whose smallest pair has that many tiles.  dense: the caller passes the attention matrix.
+static EncoderPlan plan_encoder(const gmf::Tuning& t, const gmf_encoder_weights* w, int B, int N, int T, int L, int min_tiles, int cus,
+                                bool dense = false) {
+  EncoderPlan p;
+  const int tiles = tiles_of(N), tt = tiles_of(T);
+  const int W = ((tiles + 3) / 4) * B;     // workgroups of 128 query rows
+  const bool ragged = min_tiles > 0;
+  p.act = (size_t)B * tiles * kTileFloats;
+  p.tok = (size_t)B * tt * kTileFloats;
+  // split-fp16 path: needs every split-fp16 weight image; the dense-`attention` drop-in and scattn_variant 0 run on fp32 images
+  const bool h2 = !dense && t.scattn_variant >= 9 && w->front_wst_h2 && w->ctx_wst_h2 && w->attn_wst_h2 && w->ff_wst_h2 && w->tail_wst_h2;
+  const bool fusable = h2 && t.fused_linear && t.scattn_variant == 18;
+  // throughput numerics ("precision" = 1, 2): on the two-launch path of large grids the attention multiplies one fp16 product and
+  // streams the compat matrix as fp16 (level 2: the layer's linear stages multiply one product as well); every other path keeps the
+  // parity numerics
+  const bool half = t.precision >= 1 && fusable && W >= 256 && !ragged;
+  // the cache's element format: fp16 c in the throughput mode; else the handle's "compat_format" wherever the pipelined kernel
+  // (variant 18) is the cache's only reader.  4 KiB per pair of 32-row tiles as fp32, 2 KiB in the 16-bit formats
+  const int fmt = half ? 1 : t.scattn_variant == 18 ? t.compat_format : 0;
+  const size_t cache_floats = (size_t)B * tiles * tiles * (fmt ? 512 : 1024);
+  p.cache = h2 && L > 1 && t.use_cache && cache_floats * 4 <= ((size_t)96 << 30);
+  const bool fused = fusable && p.cache;
+  if (p.cache) { p.cache_floats = cache_floats; p.fmt = fmt; p.half = half; }
+  p.one_product = p.half && t.precision == 2;
+  p.pipelined = p.cache && t.scattn_variant == 18;
+  p.front_split = t.front_split && W < 128;
+  // partials of the key / hidden splits: small grids up to 8 splits of every query block, large grids 2..4 of the last partial round
+  p.max_splits = (p.cache && tiles >= 8) ? (W < 384 ? 8 : 4) : 0;
+  // ragged batch: planned on the SMALLEST pair's tiles (every pair then has at least four key tiles per split); either every item is
+  // split - small grids: a handful of whole items walking all their keys alone left most of the chip idle (4 pairs x 1000: 1.50 ms
+  // against 0.74 for the uniform batch) - or none is
+  plan_attn_split(t, cus, W, ragged ? min_tiles : tiles, p.max_splits, ragged, &p.attn_nf, &p.attn_ks);
+  p.ff_hs = plan_ff_split(t, W, p.max_splits);
+  p.f1_ff_hs = tt <= tiles ? plan_ff_split(t, ((tt + 3) / 4) * B, p.max_splits) : 1;   // (into the attention's partials)
+  if (!h2) p.form = EncoderPlan::kFp32;
+  else if (!fused) p.form = EncoderPlan::kStages;
+  // small grids: when both the attention and the feed-forward are split anyway, their workgroups share launches
+  else if (W < 256 && t.small_roles && p.attn_nf == 0 && p.attn_ks > 1 && p.ff_hs > 1 && p.max_splits == 8) p.form = EncoderPlan::kSmall3;
+  // below 256 row blocks key / hidden / output splits fill the chip better; a ragged batch takes either the three-launch form of
+  // small grids or the two-launch form (the one-kernel-per-stage form in between has no pair table)
+  else p.form = (W >= 256 || ragged) ? EncoderPlan::kLinear : EncoderPlan::kFusedStages;
+  // grids that give a CU about one workgroup: k_linear_h2 as two roles per row block (the Q'/K/V projections | Fusion-2) in one launch
+  p.roles = p.form == EncoderPlan::kLinear && t.mid_grid_roles > 0 && W < t.mid_grid_roles;
+  // [r4] Q' in the attention kernel's prologue (parity arithmetic of the pipelined kernel; not with the linear kernel as two roles,
+  // whose Q'/K/V role writes the image): k_linear_h2 then projects K and V only
+  p.q_in_attn = p.form == EncoderPlan::kLinear && t.q_in_attention && !p.half && !p.roles;
+  // parity arithmetic: V with e4m3 cross planes for the pv_fp8 form of every attention kernel of the fused forms (a weights block
+  // without thresholds, pv_guard = NULL, gets the three-product form under the guarded default, never the unguarded one).  [r5]
+  // "pv_fp8" = 1: guarded per pair and layer on the device; the key-point packing clears the statistics (a superset of the readers)
+  p.v_fp8 = fused && !p.half && (t.pv_fp8 == 2 || (t.pv_fp8 == 1 && w->pv_guard));
+  p.clear_stats = fused && t.pv_fp8 == 1 && w->pv_guard;
+  p.guard = p.clear_stats && !p.half;
+  p.f1_h2 = h2 && w->f1_ctx_wst_h2 && w->f1_attn_wst_h2 && w->f1_ff_wst_h2;
+  // [r5] small grids: the prologue is two independent chains of few-workgroup kernels - image side (Fusion-1 context, cross-attention,
+  // feed-forward) and point side (key points, compat cache, layer 0 + first PointCN).  Three launches carry one link of each
+  // (k_pro_*, encoder_h2.hip): the point side runs under the image side instead of behind it.  Same bodies: bit-identical.
+  p.prologue = t.small_prologue && fused && p.f1_h2 && p.fmt == 0 && W < 256;
+  return p;
 }
 
 // in-situ profiling: an event pair around the attention launch(es) of a layer, recorded on the caller's stream
@@ -469,25 +581,42 @@ static int prof_begin(gmf_handle* h, hipStream_t st, hipEvent_t* ev0, hipEvent_t
   return GMF_OK;
 }
 
-// The attention launch of layer `l` (bracketed by the in-situ profiling events when enabled).
-static int run_scattn(gmf_handle* h, const gmf_encoder_weights* w, int l, const float* q, const float* k, const float* v,
-                      const float* pts8, const float* x2, float* out, int B, int N, hipStream_t st, const float* dense_compat,
-                      const gmf::CompatCache* cc) {
+// The attention launch of layer `l` (bracketed by the in-situ profiling events when enabled): the dense-`attention` drop-in, the
+// pipelined kernel, the split-fp16 kernel of the kStages form (c from the cache when there is one, else recomputed), or fp32.
+static int run_scattn(gmf_handle* h, const gmf_encoder_weights* w, const EncoderPlan& p, int l, const float* q, const float* k,
+                      const float* v, const float* pts8, const float* x2, float* out, int B, int N, hipStream_t st,
+                      const float* dense_compat, const gmf::CompatCache& cc) {
   const int tiles = tiles_of(N);
-  const bool h2 = use_h2(h, w, dense_compat != nullptr);
+  const float* wst = w->tail_wst + (size_t)l * w->tail_wst_stride;
+  const float* vecs = w->tail_vec + (size_t)l * w->tail_vec_stride;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (int rc = prof_begin(h, st, &ev0, &ev1)) return rc;
-  if (dense_compat)
-    GMF_HIP(gmf::launch_scattn_dense(q, k, v, dense_compat, x2, w->tail_wst + (size_t)l * w->tail_wst_stride,
-                                     w->tail_vec + (size_t)l * w->tail_vec_stride, out, B, N, tiles, st));
-  else if (h2)
-    GMF_HIP(gmf::launch_scattn_h2(h->tune, q, k, v, pts8, x2, w->tail_wst + (size_t)l * w->tail_wst_stride,
-                                  w->tail_vec + (size_t)l * w->tail_vec_stride, out, B, N, tiles, w->sigma_d, st, cc));
-  else
-    GMF_HIP(gmf::launch_scattn_fp32(q, k, v, pts8, x2, w->tail_wst + (size_t)l * w->tail_wst_stride,
-                                    w->tail_vec + (size_t)l * w->tail_vec_stride, out, B, N, tiles, w->sigma_d, st));
+  if (dense_compat) GMF_HIP(gmf::launch_scattn_dense(q, k, v, dense_compat, x2, wst, vecs, out, B, N, tiles, st));
+  else if (p.pipelined) GMF_HIP(gmf::launch_scattn_h2p(q, k, v, x2, vecs, out, B, N, tiles, st, cc, p.attn_nf, p.attn_ks));
+  else if (p.form == EncoderPlan::kStages)
+    GMF_HIP(gmf::launch_scattn_h2(q, k, v, pts8, x2, wst, vecs, out, B, N, tiles, w->sigma_d, st, cc.dense));
+  else GMF_HIP(gmf::launch_scattn_fp32(q, k, v, pts8, x2, wst, vecs, out, B, N, tiles, w->sigma_d, st));
   if (ev1) GMF_HIP(hipEventRecord(ev1, st));
   return GMF_OK;
+}
+
+// Runs Fusion-2 + the spatial-consistency block of layer `l` given f,q,k,v (the kFp32 and kStages forms).
+static int run_block_tail(gmf_handle* h, const gmf_encoder_weights* w, const EncoderPlan& p, int l, const float* f, const float* q,
+                          const float* k, const float* v, const float* pts8, const float* ctx_l, float* x1, float* x2,
+                          float* out, int B, int N, int T, hipStream_t st, const float* dense_compat, const gmf::CompatCache& cc) {
+  const int tiles = tiles_of(N), tt = tiles_of(T);
+  if (p.form == EncoderPlan::kStages) {
+    GMF_HIP(gmf::launch_fusion_attn_h2(true, f, ctx_l, w->attn_wst_h2 + (size_t)l * w->attn_wst_stride,
+                                       w->attn_vec + (size_t)l * w->attn_vec_stride, x1, B, N, tiles, T, tt, st));
+    GMF_HIP(gmf::launch_fusion_ff_h2(x1, w->ff_wst_h2 + (size_t)l * w->ff_wst_stride, w->ff_vec + (size_t)l * w->ff_vec_stride, x2, B,
+                                     tiles, st, cc.part_o, p.ff_hs));   // the attention's partial buffer is free here
+  } else {
+    GMF_HIP(gmf::launch_fusion_attn(true, f, ctx_l, w->attn_wst + (size_t)l * w->attn_wst_stride,
+                                    w->attn_vec + (size_t)l * w->attn_vec_stride, x1, B, N, tiles, T, tt, st));
+    GMF_HIP(gmf::launch_fusion_ff(x1, w->ff_wst + (size_t)l * w->ff_wst_stride, w->ff_vec + (size_t)l * w->ff_vec_stride,
+                                  x2, B, tiles, st));
+  }
+  return run_scattn(h, w, p, l, q, k, v, pts8, x2, out, B, N, st, dense_compat, cc);
 }
 
 // Host table of a ragged batch -> the next slot of the handle's pinned ring; returns max n, sum n.
@@ -592,118 +721,65 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
   hipStream_t st = S(stream);
   // ragged batch: per-pair sizes from the host; every image keeps a slot of tiles(max n) tiles per pair
   const bool ragged = n_points != nullptr;
+  int min_tiles = 0;
   if (ragged) {
     long long n_sum = 0;
     if (int rc = build_pair_table(h, n_points, B, -1.0, 0, &N, &n_sum, nullptr)) return rc;
+    min_tiles = tiles_of(*std::min_element(n_points, n_points + B));
   }
   const int L = w->num_layers;
   const int tiles = tiles_of(N), tt = tiles_of(T);
-  const size_t act = (size_t)B * tiles * kTileFloats;
-  const size_t tok = (size_t)B * tt * kTileFloats;
-  // compat cache (built once per batch, streamed by all L attention launches): 4 KiB per pair of 32-row tiles
-  const size_t n_tt = (size_t)B * tiles * tiles;
-  const bool h2 = use_h2(h, w, false);
-  // (2 KiB per tile pair in the 16-bit formats of the pipelined kernel, 4 KiB as fp32)
-  const size_t c_tile_floats = (h->tune.scattn_variant == 18 && h->tune.compat_format != 0) ? 512 : 1024;
-  const bool want_cache = h2 && (L > 1) && h->tune.use_cache && n_tt * c_tile_floats * 4 <= ((size_t)96 << 30);
-  const size_t cache_need = want_cache ? arena_need(n_tt * c_tile_floats, 4) : 0;
-  // Two launches per layer (the default path): see below.  Checked BEFORE the workspace is reserved and anything is launched
-  const bool fuse = h2 && L > 0 && want_cache && h->tune.fused_linear && h->tune.scattn_variant == 18;
-  GMF_REQUIRE(fuse || !ragged, GMF_ERR_UNSUPPORTED_SHAPE,
+  const EncoderPlan p = plan_encoder(h->tune, w, B, N, T, L, min_tiles, cu_count());
+  // checked BEFORE the workspace is reserved and anything is launched
+  GMF_REQUIRE(p.fused() || !ragged, GMF_ERR_UNSUPPORTED_SHAPE,
               "encoder_forward_ragged: ragged batches run on the default path only (split-fp16 weight images, at least two layers, the "
               "compat cache, \"fused_linear\" = 1, \"scattn_variant\" = 18)");
-  // key-split attention for small grids (fewer than 256 workgroups of 128 queries): partial-result workspace
-  // (small grids: up to 8 splits of every query block; large grids: the last partial round of workgroups is split in 2..4)
-  const int kMaxSplits = ((tiles + 3) / 4) * B < 384 ? 8 : 4;
-  const bool want_split = want_cache && tiles >= 8;
-  const size_t split_need = want_split ? arena_need((size_t)kMaxSplits * act, 4) + arena_need((size_t)kMaxSplits * B * tiles * 64, 4) +
-                                             (kMaxSplits == 8 ? arena_need((size_t)8 * act, 4) : 0) : 0;
-  const size_t need = 8 * arena_need(act, 4) + arena_need((size_t)B * tiles * 32 * 8, 4) +
-                      5 * arena_need(tok, 4) + arena_need((size_t)(L > 0 ? L : 1) * tok, 4) + cache_need + split_need +
-                      arena_need((size_t)B, sizeof(gmf::PairTab)) + arena_need((size_t)B * tiles * 128, 4) +
-                      arena_need((size_t)(L + 1) * B * gmf::kPvStatStride, 4);
-  if (int rc = arena_reserve(h, need)) return rc;
-  const gmf::PairTab* ptab = nullptr;
-  if (ragged) {
-    gmf::PairTab* dtab = arena_take<gmf::PairTab>(h, (size_t)B);
-    if (int rc = upload_pair_table(h, dtab, B, st)) return rc;
-    ptab = dtab;
-  }
-  float* featA = arena_take<float>(h, act);
-  float* featB = arena_take<float>(h, act);
-  float* f = arena_take<float>(h, act);
-  float* q = arena_take<float>(h, act);
-  float* k = arena_take<float>(h, act);
-  float* v = arena_take<float>(h, act);
-  float* x1 = arena_take<float>(h, act);
-  float* x2 = arena_take<float>(h, act);
-  float* pts8 = arena_take<float>(h, (size_t)B * tiles * 32 * 8);
-  float* pimg = arena_take<float>(h, tok);
-  float* qimg = arena_take<float>(h, tok);
-  float* f1ctx = arena_take<float>(h, tok);
-  float* x1t = arena_take<float>(h, tok);
-  float* imgfeat = arena_take<float>(h, tok);
-  float* ctxall = arena_take<float>(h, (size_t)(L > 0 ? L : 1) * tok);
-  unsigned* v_scale = arena_take<unsigned>(h, (size_t)B * tiles * 128);    // scale words of the V and K images' e4m3 planes ("pv_fp8"): per tile [V: 64 | K: 64]
-  unsigned* fstat = arena_take<unsigned>(h, (size_t)(L + 1) * B * gmf::kPvStatStride);   // "pv_fp8" guard: [layer][pair] max row |f_l|^2 (float bits), one 128-byte line per pair
-  gmf::CompatCache cc{nullptr, nullptr, nullptr, nullptr, 0};
-  float* c_dense = nullptr;
-  if (want_cache) {
-    c_dense = arena_take<float>(h, n_tt * c_tile_floats);
-    cc.dense = c_dense;
-  }
-  float* ff_part = nullptr;
-  if (want_split && kMaxSplits == 8) ff_part = arena_take<float>(h, (size_t)8 * act);   // small grids: feed-forward partials beside the attention's
-  if (want_split) {
-    cc.part_o = arena_take<float>(h, (size_t)kMaxSplits * act);
-    cc.part_ml = arena_take<float>(h, (size_t)kMaxSplits * B * tiles * 64);
-    cc.max_splits = kMaxSplits;
-  }
-
-  // throughput numerics ("precision" = 1, 2): on the two-launch path of large grids the attention multiplies one fp16
-  // product and streams the compat matrix as fp16 (level 2: the layer's linear stages multiply one product as well); every
-  // other path keeps the parity numerics
-  cc.half = h->tune.precision >= 1 && h2 && L > 0 && want_cache && h->tune.fused_linear && h->tune.scattn_variant == 18 &&
-            ((tiles + 3) / 4) * B >= 256 && !ragged;
-  // the cache's element format: fp16 c in the throughput mode; else the handle's "compat_format" wherever the pipelined
-  // kernel (variant 18) is the cache's only reader
-  cc.fmt = cc.half ? 1 : (want_cache && h->tune.scattn_variant == 18) ? h->tune.compat_format : 0;
+  const size_t act = p.act, tok = p.tok;
+  gmf::PairTab* ptab;
+  float *featA, *featB, *f, *q, *k, *v, *x1, *x2, *pts8, *pimg, *qimg, *f1ctx, *x1t, *imgfeat, *ctxall, *c_dense, *ff_part, *part_o,
+      *part_ml;
+  unsigned *v_scale, *fstat;
+  if (int rc = arena_carve(h, {arena_buf(ptab, ragged ? (size_t)B : 0), arena_buf(featA, act), arena_buf(featB, act), arena_buf(f, act),
+                               arena_buf(q, act), arena_buf(k, act), arena_buf(v, act), arena_buf(x1, act), arena_buf(x2, act),
+                               arena_buf(pts8, (size_t)B * tiles * 32 * 8), arena_buf(pimg, tok), arena_buf(qimg, tok),
+                               arena_buf(f1ctx, tok), arena_buf(x1t, tok), arena_buf(imgfeat, tok),
+                               arena_buf(ctxall, (size_t)(L > 0 ? L : 1) * tok),
+                               // scale words of the V and K images' e4m3 planes ("pv_fp8"): per tile [V: 64 | K: 64]
+                               arena_buf(v_scale, (size_t)B * tiles * 128),
+                               // "pv_fp8" guard: [layer][pair] max row |f_l|^2 (float bits), one 128-byte line per pair
+                               arena_buf(fstat, (size_t)(L + 1) * B * gmf::kPvStatStride),
+                               arena_buf(c_dense, p.cache_floats),
+                               // small grids: feed-forward partials beside the attention's
+                               arena_buf(ff_part, p.max_splits == 8 ? 8 * act : 0),
+                               arena_buf(part_o, p.max_splits * act),
+                               arena_buf(part_ml, (size_t)p.max_splits * B * tiles * 64)}))
+    return rc;
+  if (int rc = ragged ? upload_pair_table(h, ptab, B, st) : GMF_OK) return rc;
+  gmf::CompatCache cc{c_dense, nullptr, part_o, part_ml};
+  cc.half = p.half;
+  cc.fmt = p.fmt;
   cc.ptab = ptab;
-  if (ragged) {
-    int nmin = n_points[0];
-    for (int b = 1; b < B; ++b) nmin = n_points[b] < nmin ? n_points[b] : nmin;
-    cc.min_tiles = tiles_of(nmin);
-  }
-  // (the key-point packing also clears the "pv_fp8" guard's statistics - a superset of the forwards that read them)
-  const bool may_guard = fuse && h->tune.pv_fp8 == 1 && w->pv_guard;
-  unsigned* const zero_words = may_guard ? fstat : nullptr;
-  const int n_zero = may_guard ? (L + 1) * B * gmf::kPvStatStride : 0;
-  // [r5] small grids: the prologue is two independent chains of few-workgroup kernels - image side (Fusion-1 context, cross-attention,
-  // feed-forward) and point side (key points, compat cache, layer 0 + first PointCN).  Three launches carry one link of each
-  // (k_pro_*, encoder_h2.hip): the point side runs under the image side instead of behind it.  Same bodies: bit-identical.
-  const bool pro = h->tune.small_prologue && fuse && w->f1_ctx_wst_h2 && w->f1_attn_wst_h2 && w->f1_ff_wst_h2 && cc.fmt == 0 &&
-                   ((tiles + 3) / 4) * B < 256;
-  if (pro) {
+  cc.v_scale = p.v_fp8 ? v_scale : nullptr;
+  unsigned* const zero_words = p.clear_stats ? fstat : nullptr;
+  const int n_zero = p.clear_stats ? (L + 1) * B * gmf::kPvStatStride : 0;
+  if (p.prologue) {
     GMF_HIP(gmf::launch_pro_ctx_pts(p_tokens, w->f1_ctx_wst_h2, w->f1_ctx_vec, f1ctx, B, T, tt, src_keypts, tgt_keypts, pts8, N, st, ptab,
                                     zero_words, n_zero));
     GMF_HIP(gmf::launch_pro_fattn_compat(q_tokens, f1ctx, w->f1_attn_wst_h2, w->f1_attn_vec, x1t, B, T, tt, pts8, c_dense, N, tiles,
                                          w->sigma_d, st, ptab));
     gmf::PvGuard g0;
-    if (may_guard) g0.stat_next = fstat;         // (small grids never run the throughput numerics: may_guard is `guarded` below)
-    int hs = 1;
-    GMF_HIP(gmf::launch_pro_ff_front(h->tune, x1t, w->f1_ff_wst_h2, w->f1_ff_vec, imgfeat, B, tt, tt <= tiles ? cc.part_o : nullptr,
-                                     tt <= tiles ? cc.max_splits : 0, corr_pos, w->front_wst_h2, w->front_vec, f, q, k, v, N, tiles, st,
-                                     ptab, g0, &hs));
-    if (hs > 1) GMF_HIP(gmf::launch_ff_reduce_h2(cc.part_o, x1t, w->f1_ff_vec, imgfeat, B, tt, hs, st));
+    if (p.guard) g0.stat_next = fstat;
+    GMF_HIP(gmf::launch_pro_ff_front(x1t, w->f1_ff_wst_h2, w->f1_ff_vec, imgfeat, B, tt, part_o, p.f1_ff_hs, corr_pos, w->front_wst_h2,
+                                     w->front_vec, f, q, k, v, N, tiles, st, ptab, g0));
+    if (p.f1_ff_hs > 1) GMF_HIP(gmf::launch_ff_reduce_h2(part_o, x1t, w->f1_ff_vec, imgfeat, B, tt, p.f1_ff_hs, st));
     GMF_HIP(gmf::launch_ctx_prep_h2(true, imgfeat, w->ctx_wst_h2, w->ctx_vec, ctxall, B, T, tt, L, w->ctx_wst_stride, w->ctx_vec_stride, st));
   } else {
     // Fusion-1: image_feat = FusionLayer(p_tok (context), queries = q_tok), pe = False (PointDSC.py:137)
-    if (h2 && w->f1_ctx_wst_h2 && w->f1_attn_wst_h2 && w->f1_ff_wst_h2) {
+    if (p.f1_h2) {
       // (the two token tensors are read row-major: no packing launches in front of these few-workgroup kernels)
       GMF_HIP(gmf::launch_ctx_prep_h2(false, p_tokens, w->f1_ctx_wst_h2, w->f1_ctx_vec, f1ctx, B, T, tt, 1, 0, 0, st, true));
       GMF_HIP(gmf::launch_fusion_attn_h2(false, q_tokens, f1ctx, w->f1_attn_wst_h2, w->f1_attn_vec, x1t, B, T, tt, T, tt, st, true));
-      GMF_HIP(gmf::launch_fusion_ff_h2(h->tune, x1t, w->f1_ff_wst_h2, w->f1_ff_vec, imgfeat, B, tt, st,
-                                       tt <= tiles ? cc.part_o : nullptr, tt <= tiles ? cc.max_splits : 0));
+      GMF_HIP(gmf::launch_fusion_ff_h2(x1t, w->f1_ff_wst_h2, w->f1_ff_vec, imgfeat, B, tt, st, part_o, p.f1_ff_hs));
     } else {
       GMF_HIP(gmf::launch_pack_p32(p_tokens, pimg, B, T, kC, (long)T * kC, kC, 1, st));
       GMF_HIP(gmf::launch_pack_p32(q_tokens, qimg, B, T, kC, (long)T * kC, kC, 1, st));
@@ -713,49 +789,32 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
     }
     // context side of all L Fusion-2 layers in one launch
     if (L > 0) {
-      if (h2) GMF_HIP(gmf::launch_ctx_prep_h2(true, imgfeat, w->ctx_wst_h2, w->ctx_vec, ctxall, B, T, tt, L, w->ctx_wst_stride,
-                                              w->ctx_vec_stride, st));
+      if (p.form != EncoderPlan::kFp32) GMF_HIP(gmf::launch_ctx_prep_h2(true, imgfeat, w->ctx_wst_h2, w->ctx_vec, ctxall, B, T, tt, L,
+                                                                         w->ctx_wst_stride, w->ctx_vec_stride, st));
       else GMF_HIP(gmf::launch_ctx_prep(true, imgfeat, w->ctx_wst, w->ctx_vec, ctxall, B, T, tt, L, w->ctx_wst_stride,
                                         w->ctx_vec_stride, st));
     }
     GMF_HIP(gmf::launch_pack_pts8(src_keypts, tgt_keypts, pts8, B, N, st, ptab, zero_words, n_zero));
-    if (want_cache) GMF_HIP(gmf::launch_compat_build(pts8, c_dense, B, N, tiles, w->sigma_d, cc.fmt, st, ptab));
+    if (p.cache) GMF_HIP(gmf::launch_compat_build(pts8, c_dense, B, N, tiles, w->sigma_d, p.fmt, st, ptab));
   }
 
   float* cur = featA;
   float* nxt = featB;
-  // Two launches per layer (default on the split-fp16 path with the cached, pipelined attention kernel): the layer's PointCN
-  // runs in the PREVIOUS layer's attention epilogue (layer 0: a small f-only kernel), so a layer is
-  //   k_linear_h2 : f -> Q', K, V (split-fp16 images) and x2 = Fusion-2(f)        (small grids: the three split-capable kernels)
+  // The fused forms (the default): the layer's PointCN runs in the PREVIOUS layer's attention epilogue (layer 0: a small f-only
+  // kernel).  kLinear, two launches per layer:
+  //   k_linear_h2 : f -> Q', K, V (split-fp16 images) and x2 = Fusion-2(f)
   //   k_scattn_h2p: Q', K, V, c, x2 -> f_{l+1} = ReLU(PointCN_{l+1}(fc_message(attention) + x2))   (last layer: the features)
-  if (fuse) {
-    const int Wg = ((tiles + 3) / 4) * B;
-    // small grids: when both the attention and the feed-forward are split anyway, their workgroups share launches
-    // ([r5] ragged batches too: the split is planned on the smallest pair's tiles, the role kernels read the pair table)
-    int small_nf = 1, small_ks = 1;
-    gmf::plan_attn_split(h->tune, Wg, ragged ? cc.min_tiles : tiles, cc.part_o ? cc.max_splits : 0, &small_nf, &small_ks);
-    const int ff_hs = cc.part_o ? gmf::plan_ff_split(h->tune, Wg, cc.max_splits) : 1;
-    const bool small3_ok = Wg < 256 && h->tune.small_roles && small_nf == 0 && small_ks > 1 && ff_hs > 1 && ff_part;
-    // below 256 row blocks key / hidden / output splits fill the chip better; a ragged batch takes either the three-launch form of
-    // small grids or the two-launch form (the one-kernel-per-stage form in between has no pair table)
-    const bool one_kernel = Wg >= 256 || (ragged && !small3_ok);
-    const bool small3 = !one_kernel && small3_ok;
-    // parity arithmetic: V with e4m3 cross planes for the pv_fp8 form of the attention body (scattn_h2p_body<3, *, 4, true>), which every
-    // attention kernel of this path instantiates - large grids, split tails and the small-grid role kernels alike
-    // (a weights block without thresholds - filled in by hand, pv_guard = NULL - gets the three-product form under the guarded default,
-    // never the unguarded one)
-    cc.v_scale = ((h->tune.pv_fp8 == 2 || (h->tune.pv_fp8 == 1 && w->pv_guard)) && !cc.half) ? v_scale : nullptr;
-    // [r5] "pv_fp8" = 1: guarded per pair and layer on the device (PvGuard).  The statistics start at zero (k_pack_pts8); f_0's is raised by the
-    // front kernel, f_{l+1}'s by the attention epilogue / merge kernels of layer l - always before the kernels that read it
-    const bool guarded = cc.v_scale && h->tune.pv_fp8 == 1 && w->pv_guard;       // (implies may_guard: launch_pack_pts8 cleared fstat)
-    if (!pro) {                                   // (small grids: the prologue's third launch ran it)
+  if (p.fused()) {
+    if (!p.prologue) {                            // (small grids: the prologue's third launch ran it)
       gmf::PvGuard g0;
-      if (guarded) g0.stat_next = fstat;
-      GMF_HIP(gmf::launch_front_h2(h->tune, 3, corr_pos, w->front_wst_h2, w->front_vec, f, q, k, v, B, N, tiles, st, ptab, nullptr, g0));
+      if (p.guard) g0.stat_next = fstat;
+      GMF_HIP(gmf::launch_front_h2(3, p.front_split, corr_pos, w->front_wst_h2, w->front_vec, f, q, k, v, B, N, tiles, st, ptab, nullptr, g0));
     }
     for (int l = 0; l < L; ++l) {
+      // the guard's statistics: f_0's is raised by the front kernel, f_{l+1}'s by the attention epilogue / merge kernels of layer l -
+      // always before the kernels that read it
       cc.guard = gmf::PvGuard{};
-      if (guarded) cc.guard = gmf::PvGuard{fstat + (size_t)l * B * gmf::kPvStatStride, w->pv_guard + l, fstat + (size_t)(l + 1) * B * gmf::kPvStatStride};
+      if (p.guard) cc.guard = gmf::PvGuard{fstat + (size_t)l * B * gmf::kPvStatStride, w->pv_guard + l, fstat + (size_t)(l + 1) * B * gmf::kPvStatStride};
       const float* fw = w->front_wst_h2 + (size_t)l * w->front_wst_stride;
       const float* fv = w->front_vec + (size_t)l * w->front_vec_stride;
       const float* aw = w->attn_wst_h2 + (size_t)l * w->attn_wst_stride;
@@ -763,46 +822,37 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
       const float* ffw = w->ff_wst_h2 + (size_t)l * w->ff_wst_stride;
       const float* ffv = w->ff_vec + (size_t)l * w->ff_vec_stride;
       const float* ctx_l = ctxall + (size_t)l * tok;
-      if (one_kernel) {
-        // [r4] Q' in the attention kernel's prologue (parity arithmetic of the pipelined kernel; not with the linear kernel as two
-        // roles, whose Q'/K/V role writes the image): k_linear_h2 then projects K and V only
-        const int Wl = ((tiles + 3) / 4) * B;
-        const bool roles = h->tune.mid_grid_roles > 0 && Wl < h->tune.mid_grid_roles;     // ([r5] ragged batches too: the role kernel reads the pair table)
-        const bool qproj = h->tune.q_in_attention && !cc.half && !roles;
-        cc.qf_img = qproj ? f : nullptr;
-        cc.qw_wst = qproj ? fw + 4 * kTileFloats : nullptr;
-        cc.qw_bias = qproj ? fv + kC : nullptr;
-        GMF_HIP(gmf::launch_linear_h2(h->tune, f, fw, fv, ctx_l, aw, av, ffw, ffv, qproj ? nullptr : q, k, v, x2, B, N, tiles, T, tt, st,
-                                      cc.half && h->tune.precision == 2, ptab, cc.v_scale, cc.guard));
-      } else if (small3) {
+      const bool last = (l + 1 == L);
+      cc.tail_wst_h2 = w->tail_wst_h2 + (size_t)l * w->tail_wst_stride;
+      cc.next_wst_h2 = last ? nullptr : w->front_wst_h2 + (size_t)(l + 1) * w->front_wst_stride;
+      cc.next_bias = last ? nullptr : w->front_vec + (size_t)(l + 1) * w->front_vec_stride;
+      if (p.form == EncoderPlan::kLinear) {
+        cc.qf_img = p.q_in_attn ? f : nullptr;
+        cc.qw_wst = p.q_in_attn ? fw + 4 * kTileFloats : nullptr;
+        cc.qw_bias = p.q_in_attn ? fv + kC : nullptr;
+        GMF_HIP(gmf::launch_linear_h2(p.roles, f, fw, fv, ctx_l, aw, av, ffw, ffv, p.q_in_attn ? nullptr : q, k, v, x2, B, N, tiles, T, tt,
+                                      st, p.one_product, ptab, cc.v_scale, cc.guard));
+      } else if (p.form == EncoderPlan::kSmall3) {
         // three launches: {Q' | K | V | cross-attention} -> {key-split attention | hidden-split feed-forward} -> merge
         GMF_HIP(gmf::launch_small_front_fattn(f, fw, fv, ctx_l, aw, av, q, k, v, x1, B, N, tiles, T, tt, st, cc.v_scale, cc.guard,
                                               h->tune.small_fattn_tile, ptab));
-        const bool last3 = (l + 1 == L);
-        cc.tail_wst_h2 = w->tail_wst_h2 + (size_t)l * w->tail_wst_stride;
-        cc.next_wst_h2 = last3 ? nullptr : w->front_wst_h2 + (size_t)(l + 1) * w->front_wst_stride;
-        cc.next_bias = last3 ? nullptr : w->front_vec + (size_t)(l + 1) * w->front_vec_stride;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (int rc = prof_begin(h, st, &e0, &e1)) return rc;
-        GMF_HIP(gmf::launch_small_attn_ff_merge(q, k, v, x1, ffw, ffv, ff_part, ff_hs, w->tail_vec + (size_t)l * w->tail_vec_stride,
-                                                last3 ? cur : f, B, N, tiles, small_ks, st, &cc, h->tune.small_merge_tile));
+        GMF_HIP(gmf::launch_small_attn_ff_merge(q, k, v, x1, ffw, ffv, ff_part, p.ff_hs, w->tail_vec + (size_t)l * w->tail_vec_stride,
+                                                last ? cur : f, B, N, tiles, p.attn_ks, st, &cc, h->tune.small_merge_tile));
         if (e1) GMF_HIP(hipEventRecord(e1, st));
         continue;
       } else {
         // (projecting Q'/K/V on a side stream beside the Fusion-2 kernels, forked and joined with events, was measured at
         // B = 1: 1.62 vs 1.58 ms at N = 5000, 1.08 vs 1.00 ms at N = 1000 - the event round trips cost more than the overlap gives)
-        GMF_HIP(gmf::launch_front_h2(h->tune, 2, f, fw, fv, f, q, k, v, B, N, tiles, st, nullptr, cc.v_scale, cc.guard));
+        GMF_HIP(gmf::launch_front_h2(2, p.front_split, f, fw, fv, f, q, k, v, B, N, tiles, st, nullptr, cc.v_scale, cc.guard));
         GMF_HIP(gmf::launch_fusion_attn_h2(true, f, ctx_l, aw, av, x1, B, N, tiles, T, tt, st));
-        GMF_HIP(gmf::launch_fusion_ff_h2(h->tune, x1, ffw, ffv, x2, B, tiles, st, cc.part_o, cc.max_splits));
+        GMF_HIP(gmf::launch_fusion_ff_h2(x1, ffw, ffv, x2, B, tiles, st, part_o, p.ff_hs));
       }
-      const bool last = (l + 1 == L);
-      cc.tail_wst_h2 = w->tail_wst_h2 + (size_t)l * w->tail_wst_stride;
-      cc.next_wst_h2 = last ? nullptr : w->front_wst_h2 + (size_t)(l + 1) * w->front_wst_stride;
-      cc.next_bias = last ? nullptr : w->front_vec + (size_t)(l + 1) * w->front_vec_stride;
-      if (int rc = run_scattn(h, w, l, q, k, v, pts8, x2, last ? cur : f, B, N, st, nullptr, &cc)) return rc;
+      if (int rc = run_scattn(h, w, p, l, q, k, v, pts8, x2, last ? cur : f, B, N, st, nullptr, cc)) return rc;
     }
     GMF_HIP(gmf::launch_head(cur, w->head_wst, w->head_vec, logits, feat_n, feat, B, N, tiles, st, h->status_dev, ptab,
-                             guarded ? fstat : nullptr, guarded ? w->pv_guard : nullptr, L));
+                             p.guard ? fstat : nullptr, p.guard ? w->pv_guard : nullptr, L));
     return GMF_OK;
   }
   if (L == 0) {
@@ -811,13 +861,13 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
   }
   for (int l = 0; l < L; ++l) {
     const float* in = (l == 0) ? corr_pos : cur;
-    if (h2) GMF_HIP(gmf::launch_front_h2(h->tune, l == 0 ? 1 : 0, in, w->front_wst_h2 + (size_t)l * w->front_wst_stride,
-                                         w->front_vec + (size_t)l * w->front_vec_stride, f, q, k, v, B, N, tiles, st));
+    if (p.form == EncoderPlan::kStages)
+      GMF_HIP(gmf::launch_front_h2(l == 0 ? 1 : 0, p.front_split, in, w->front_wst_h2 + (size_t)l * w->front_wst_stride,
+                                   w->front_vec + (size_t)l * w->front_vec_stride, f, q, k, v, B, N, tiles, st));
     else GMF_HIP(gmf::launch_front(l == 0 ? 1 : 0, in, w->front_wst + (size_t)l * w->front_wst_stride,
                                    w->front_vec + (size_t)l * w->front_vec_stride, f, q, k, v, B, N, tiles, st));
     cc.tail_wst_h2 = w->tail_wst_h2 ? w->tail_wst_h2 + (size_t)l * w->tail_wst_stride : nullptr;
-    if (int rc = run_block_tail(h, w, l, f, q, k, v, pts8, ctxall + (size_t)l * tok, x1, x2, nxt, B, N, T, st, nullptr,
-                                &cc)) return rc;
+    if (int rc = run_block_tail(h, w, p, l, f, q, k, v, pts8, ctxall + (size_t)l * tok, x1, x2, nxt, B, N, T, st, nullptr, cc)) return rc;
     float* t = cur; cur = nxt; nxt = t;
   }
   GMF_HIP(gmf::launch_head(cur, w->head_wst, w->head_vec, logits, feat_n, feat, B, N, tiles, st, h->status_dev));
@@ -837,19 +887,15 @@ int gmf_nonlocal_block_forward(gmf_handle* h, const gmf_encoder_weights* w, int 
   SetDevice sd(h, stream);
   hipStream_t st = S(stream);
   const int tiles = tiles_of(N), tt = tiles_of(T);
-  const size_t act = (size_t)B * tiles * kTileFloats;
-  const size_t tok = (size_t)B * tt * kTileFloats;
-  if (int rc = arena_reserve(h, 6 * arena_need(act, 4) + arena_need(tok, 4))) return rc;
-  float* f = arena_take<float>(h, act);
-  float* q = arena_take<float>(h, act);
-  float* k = arena_take<float>(h, act);
-  float* v = arena_take<float>(h, act);
-  float* x1 = arena_take<float>(h, act);
-  float* x2 = arena_take<float>(h, act);
-  float* ctx = arena_take<float>(h, tok);
+  // one layer: no compat cache, so the kFp32 or kStages form (the dense-compat kernel consumes fp32 images: kFp32)
+  const EncoderPlan p = plan_encoder(h->tune, w, B, N, T, 1, 0, cu_count(), attention != nullptr);
+  float *f, *q, *k, *v, *x1, *x2, *ctx;
+  if (int rc = arena_carve(h, {arena_buf(f, p.act), arena_buf(q, p.act), arena_buf(k, p.act), arena_buf(v, p.act), arena_buf(x1, p.act),
+                               arena_buf(x2, p.act), arena_buf(ctx, p.tok)}))
+    return rc;
   // apply_pointcn = 0: the caller's feat is already the block input (NonLocalBlock.forward, PointDSC.py:40-45)
-  if (use_h2(h, w, attention != nullptr)) {   // (the dense-compat kernel consumes fp32 images: fp32 path)
-    GMF_HIP(gmf::launch_front_h2(h->tune, apply_pointcn ? 0 : 2, feat_img, w->front_wst_h2 + (size_t)layer * w->front_wst_stride,
+  if (p.form == EncoderPlan::kStages) {
+    GMF_HIP(gmf::launch_front_h2(apply_pointcn ? 0 : 2, p.front_split, feat_img, w->front_wst_h2 + (size_t)layer * w->front_wst_stride,
                                  w->front_vec + (size_t)layer * w->front_vec_stride, f, q, k, v, B, N, tiles, st));
     GMF_HIP(gmf::launch_ctx_prep_h2(true, image_feat_img, w->ctx_wst_h2 + (size_t)layer * w->ctx_wst_stride,
                                     w->ctx_vec + (size_t)layer * w->ctx_vec_stride, ctx, B, T, tt, 1, 0, 0, st));
@@ -859,8 +905,8 @@ int gmf_nonlocal_block_forward(gmf_handle* h, const gmf_encoder_weights* w, int 
     GMF_HIP(gmf::launch_ctx_prep(true, image_feat_img, w->ctx_wst + (size_t)layer * w->ctx_wst_stride,
                                  w->ctx_vec + (size_t)layer * w->ctx_vec_stride, ctx, B, T, tt, 1, 0, 0, st));
   }
-  gmf::CompatCache cc{nullptr, w->tail_wst_h2 ? w->tail_wst_h2 + (size_t)layer * w->tail_wst_stride : nullptr, nullptr, nullptr, 0};
-  return run_block_tail(h, w, layer, f, q, k, v, pts8, ctx, x1, x2, out_img, B, N, T, st, attention, &cc);
+  gmf::CompatCache cc{nullptr, w->tail_wst_h2 ? w->tail_wst_h2 + (size_t)layer * w->tail_wst_stride : nullptr, nullptr, nullptr};
+  return run_block_tail(h, w, p, layer, f, q, k, v, pts8, ctx, x1, x2, out_img, B, N, T, st, attention, cc);
 }
 
 int gmf_fusion_layer_forward(gmf_handle* h, int pe, int latent_dim, int d_head, const float* ctx_wst, const float* ctx_vec,
@@ -886,14 +932,10 @@ int gmf_fusion_layer_forward(gmf_handle* h, int pe, int latent_dim, int d_head, 
   // small grids of the wide layer: the feed-forward's hidden chunks are split over hs workgroups per row block
   const int ff_hs_w = (wide && ff_wst_h2 && h->tune.ff_split != 1) ?
                           (h->tune.ff_split > 1 ? h->tune.ff_split : gmf::plan_ff_split_w(((tiles + 3) / 4) * B)) : 1;
-  if (int rc = arena_reserve(h, 3 * arena_need(act, 4) + arena_need(tok, 4) + arena_need(ctxsz, 4) +
-                                    (ff_hs_w > 1 ? arena_need((size_t)ff_hs_w * act, 4) : 0))) return rc;
-  float* xin = arena_take<float>(h, act);
-  float* x1 = arena_take<float>(h, act);
-  float* x2 = arena_take<float>(h, act);
-  float* cimg = arena_take<float>(h, tok);
-  float* ctx = arena_take<float>(h, ctxsz);
-  float* ff_part_w = ff_hs_w > 1 ? arena_take<float>(h, (size_t)ff_hs_w * act) : nullptr;
+  float *xin, *x1, *x2, *cimg, *ctx, *ff_part_w;
+  if (int rc = arena_carve(h, {arena_buf(xin, act), arena_buf(x1, act), arena_buf(x2, act), arena_buf(cimg, tok), arena_buf(ctx, ctxsz),
+                               arena_buf(ff_part_w, ff_hs_w > 1 ? (size_t)ff_hs_w * act : 0)}))
+    return rc;
   // the split-fp16 kernels of the 256-wide layer read the context tokens row-major and (hidden-split feed-forward) write the
   // output through its strides: on the small grids this layer usually runs on, a packing pass is a launch like any other
   const bool wide_direct = wide && attn_wst_h2 != nullptr;
@@ -907,7 +949,7 @@ int gmf_fusion_layer_forward(gmf_handle* h, int pe, int latent_dim, int d_head, 
       GMF_HIP(gmf::launch_ctx_prep(pe != 0, cimg, ctx_wst, ctx_vec, ctx, B, T, tt, 1, 0, 0, st));
       GMF_HIP(gmf::launch_fusion_attn(pe != 0, xin, ctx, attn_wst, attn_vec, x1, B, N, tiles, T, tt, st));
     }
-    if (ff_wst_h2) GMF_HIP(gmf::launch_fusion_ff_h2(h->tune, x1, ff_wst_h2, ff_vec, x2, B, tiles, st));
+    if (ff_wst_h2) GMF_HIP(gmf::launch_fusion_ff_h2(x1, ff_wst_h2, ff_vec, x2, B, tiles, st));
     else GMF_HIP(gmf::launch_fusion_ff(x1, ff_wst, ff_vec, x2, B, tiles, st));
   } else {
     if (attn_wst_h2) {

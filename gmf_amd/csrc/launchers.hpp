@@ -29,13 +29,13 @@ struct PvGuard {
   unsigned* stat_next = nullptr;    // [B] the NEXT layer's statistic: raised (atomic maximum) by whoever produces f_{l+1}; null: nobody asks
 };
 
-// compat matrix built once per batch by launch_compat_build (see k_compat_build): [B, tiles, tiles, 1024] floats
+// compat matrix built once per batch by launch_compat_build (see k_compat_build): [B, tiles, tiles, 1024] floats.  The buffers and
+// per-layer weights of the split-fp16 attention; `half` and `fmt` are copied from the forward's plan (gmf_api.cpp, EncoderPlan)
 struct CompatCache {
   const float* dense;
   const float* tail_wst_h2;   // this layer's fc_message weights as split-fp16 images (epilogue of k_scattn_h2p)
-  float* part_o;              // key-split workspace: [max_splits][B * tiles] P32 tile images (or nullptr)
-  float* part_ml;             // ... [max_splits][B * tiles][32][2] row maximum, row sum
-  int max_splits;
+  float* part_o;              // key-split workspace: [max splits][B * tiles] P32 tile images (or nullptr)
+  float* part_ml;             // ... [max splits][B * tiles][32][2] row maximum, row sum
   // when non-null, the attention epilogue applies the NEXT layer's PointCN (4 split-fp16 weight stages + bias) to the block
   // output and stores f_{l+1} instead of feat (k_scattn_h2p / k_scattn_merge only)
   const float* next_wst_h2 = nullptr;
@@ -43,7 +43,6 @@ struct CompatCache {
   bool half = false;          // `dense` holds fp16 tiles (2 KiB each) and the attention multiplies one fp16 product: the
                               // throughput numerics mode (Tuning::precision = 1), large grids only (then fmt = 1)
   const PairTab* ptab = nullptr;   // ragged batch: per-pair rows (device), else null
-  int min_tiles = 0;               // ragged batch: the smallest pair's 32-row tiles (the key-split plan is made for it)
   int fmt = 0;                // element format of `dense` (k_compat_build): 0 = fp32 (4 KiB per tile); 16-bit, 2 KiB per tile:
                               // 1 = fp16 c (with `half`), 2 = fixed point rint(65535 c)
   unsigned* v_scale = nullptr;   // non-null: the layer's V image carries e4m3 cross planes (store_block_v8) and these are their
@@ -100,9 +99,11 @@ hipError_t launch_front(int mode, const float* in, const float* wst, const float
 hipError_t launch_scattn_fp32(const float* q, const float* k, const float* v, const float* pts8, const float* fus,
                               const float* wst, const float* vecs, float* out, int B, int N, int tiles, float sigma_d,
                               hipStream_t s);
-hipError_t launch_scattn_h2(const Tuning& tune, const float* q, const float* k, const float* v, const float* pts8,
-                            const float* fus, const float* wst, const float* vecs, float* out, int B, int N, int tiles,
-                            float sigma_d, hipStream_t s, const CompatCache* cc);
+hipError_t launch_scattn_h2(const float* q, const float* k, const float* v, const float* pts8, const float* fus, const float* wst,
+                            const float* vecs, float* out, int B, int N, int tiles, float sigma_d, hipStream_t s, const float* c_dense);
+// the cached, pipelined attention (scattn_variant 18): n_full items per XCD whole, the rest split `ksplits` ways by keys
+hipError_t launch_scattn_h2p(const float* q, const float* k, const float* v, const float* fus, const float* vecs, float* out, int B,
+                             int N, int tiles, hipStream_t s, const CompatCache& cc, int n_full, int ksplits);
 hipError_t launch_scattn_dense(const float* q, const float* k, const float* v, const float* compat, const float* fus,
                                const float* wst, const float* vecs, float* out, int B, int N, int tiles, hipStream_t s);
 hipError_t launch_ctx_prep(bool pe, const float* ctx, const float* wst, const float* vecs, float* out, int B, int T,
@@ -127,17 +128,17 @@ hipError_t launch_fusion_ff_w_h2(const float* x1, const float* wst_h2, const flo
                                  float* part = nullptr, int hs = 1, float* out_rm = nullptr, long o_sb = 0, long o_sr = 0,
                                  long o_sk = 0, int n_rows = 0, int* status = nullptr);
 int plan_ff_split_w(int base_wgs);
-hipError_t launch_front_h2(const Tuning& tune, int mode, const float* in, const float* wst, const float* vecs, float* f,
-                           float* q, float* k, float* v, int B, int N, int tiles, hipStream_t s, const PairTab* ptab = nullptr,
-                           unsigned* v_scale = nullptr, PvGuard guard = {});   // v_scale: V with e4m3 cross planes (CompatCache::v_scale)
-// mode 3: corr_pos -> layer0 -> PointCN -> f only.  launch_linear_h2: all linear stages of one layer from f (k_linear_h2)
-hipError_t launch_linear_h2(const Tuning& tune, const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
+// split: one workgroup per output (Q' + f | K | V); v_scale: V with e4m3 cross planes (CompatCache::v_scale)
+hipError_t launch_front_h2(int mode, bool split, const float* in, const float* wst, const float* vecs, float* f, float* q, float* k,
+                           float* v, int B, int N, int tiles, hipStream_t s, const PairTab* ptab = nullptr, unsigned* v_scale = nullptr,
+                           PvGuard guard = {});
+// mode 3: corr_pos -> layer0 -> PointCN -> f only.  launch_linear_h2: all linear stages of one layer from f (k_linear_h2); roles: as
+// two workgroup roles per row block (needs q); q null: no Q' image (CompatCache::qf_img); v_scale: CompatCache::v_scale
+hipError_t launch_linear_h2(bool roles, const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
                             const float* attn_wst, const float* attn_vec, const float* ff_wst, const float* ff_vec, float* q,
                             float* k, float* v, float* x2, int B, int N, int tiles, int T, int ttiles, hipStream_t s, bool one_product = false,
-                            const PairTab* ptab = nullptr, unsigned* v_scale = nullptr, PvGuard guard = {});   // v_scale: CompatCache::v_scale
+                            const PairTab* ptab = nullptr, unsigned* v_scale = nullptr, PvGuard guard = {});
 // small grids: three launches per layer (k_small_front_fattn | k_small_attn_ff | k_scattn_merge)
-void plan_attn_split(const Tuning& tune, int W, int tiles, int max_splits, int* n_full, int* ksplits);
-int plan_ff_split(const Tuning& tune, int base, int max_parts);
 hipError_t launch_small_front_fattn(const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
                                     const float* attn_wst, const float* attn_vec, float* q, float* k, float* v, float* x1, int B,
                                     int N, int tiles, int T, int ttiles, hipStream_t s, unsigned* v_scale = nullptr, PvGuard guard = {},
@@ -156,13 +157,14 @@ hipError_t launch_pro_ctx_pts(const float* p_tokens, const float* wst, const flo
 hipError_t launch_pro_fattn_compat(const float* q_tokens, const float* f1ctx, const float* wst, const float* vecs, float* x1t, int B,
                                    int T, int ttiles, const float* pts8, float* c_dense, int N, int tiles, float sigma_d,
                                    hipStream_t s, const PairTab* ptab);
-hipError_t launch_pro_ff_front(const Tuning& tune, const float* x1t, const float* wst, const float* vecs, float* imgfeat, int B,
-                               int ttiles, float* part, int max_parts, const float* corr_pos, const float* fwst, const float* fvecs,
-                               float* f, float* q, float* k, float* v, int N, int tiles, hipStream_t s, const PairTab* ptab,
-                               PvGuard guard, int* hs_out);
+// hs > 1: the feed-forward role in hs hidden splits into `part`; the caller runs launch_ff_reduce_h2 next
+hipError_t launch_pro_ff_front(const float* x1t, const float* wst, const float* vecs, float* imgfeat, int B, int ttiles, float* part,
+                               int hs, const float* corr_pos, const float* fwst, const float* fvecs, float* f, float* q, float* k,
+                               float* v, int N, int tiles, hipStream_t s, const PairTab* ptab, PvGuard guard);
 hipError_t launch_ff_reduce_h2(const float* part, const float* x1, const float* vecs, float* x2, int B, int tiles, int hs, hipStream_t s);
-hipError_t launch_fusion_ff_h2(const Tuning& tune, const float* x1, const float* wst, const float* vecs, float* x2, int B,
-                               int tiles, hipStream_t s, float* part = nullptr, int max_parts = 0);
+// hs > 1: the 16 hidden chunks over hs workgroups per row block, partials in `part`, then the reduction
+hipError_t launch_fusion_ff_h2(const float* x1, const float* wst, const float* vecs, float* x2, int B, int tiles, hipStream_t s,
+                               float* part = nullptr, int hs = 1);
 int padded_desc_width(int d);
 hipError_t launch_nn_match(const float* F0, const float* F1, float* f0_img, float* f1_img, float* norm2, unsigned long long* best, int* idx,
                            float* dist, int N0, int N1, int d, int mode, hipStream_t s);
