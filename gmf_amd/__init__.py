@@ -18,6 +18,7 @@ from .solvers import (ransac_correspondence_batched, icp_point_to_point_batched,
 from .features import (radius_knn_batched, estimate_normals_batched, compute_fpfh_batched,  # noqa: F401
                        voxel_down_sample_batched, voxel_select_batched, voxel_down_sample, voxel_select, estimate_normals,
                        compute_fpfh_feature, fpfh_descriptors)
+from .sparse import SparsePlan, sparse_conv, ResUNetBN2C, ResUNetBN2CX, inlier_coordinates   # noqa: F401
 from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss, similarity_matrix   # noqa: F401
 
 __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointDSC", "ImageEncoder",
@@ -27,4 +28,4 @@ __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointD
            "icp_point_to_point_batched", "RegistrationResult", "registration_ransac_based_on_correspondence", "registration_icp",
            "icp_refine", "radius_knn_batched", "estimate_normals_batched", "compute_fpfh_batched", "voxel_down_sample_batched",
            "voxel_select_batched", "voxel_down_sample", "voxel_select", "estimate_normals", "compute_fpfh_feature",
-           "fpfh_descriptors"]
+           "fpfh_descriptors", "SparsePlan", "sparse_conv", "ResUNetBN2C", "ResUNetBN2CX", "inlier_coordinates"]

@@ -195,6 +195,11 @@ SIGNATURES = {
     "gmf_compute_fpfh": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _ll, C.c_double, C.c_int, _vp, _vp]),
     "gmf_voxel_down_sample": (C.c_int, [_vp, _vp, _vp, C.c_int, _ll, C.c_double, _vp, _vp, C.POINTER(_ll), _vp]),
     "gmf_voxel_select": (C.c_int, [_vp, _vp, _vp, C.c_int, _ll, C.c_double, _vp, _vp, C.POINTER(_ll), _vp]),
+    "gmf_sparse_plan_bytes": (C.c_int, [_vp, _ll, C.c_int, C.c_int, C.c_int, _i32p, C.POINTER(_ll)]),
+    "gmf_sparse_build_plan": (C.c_int, [_vp, _vp, _ll, C.c_int, C.c_int, C.c_int, _i32p, _vp, _ll, C.POINTER(_ll), _vp]),
+    "gmf_sparse_conv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _ll, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp,
+                                  _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "gmf_sparse_pack_resunet": (C.c_int, [_vp, C.POINTER(Tensor), C.c_int, _vp, _ll, C.POINTER(_ll), C.POINTER(_ll)]),
 }
 
 _lib = None
@@ -225,6 +230,7 @@ def load_library() -> C.CDLL:
 GMF_ERR_WORKSPACE = -6
 GMF_STATUS_NONFINITE = 1
 GMF_STATUS_PV_GUARDED = 2      # informational: the "pv_fp8" guard sent a (pair, layer) to the three-product form
+GMF_STATUS_SPARSE_DUPLICATE = 4   # gmf_sparse_build_plan met a duplicate (batch, coordinates) input row
 
 
 class Handle:
@@ -289,6 +295,11 @@ class Handle:
                 f"gmf_amd: {where}: a non-finite value (NaN / inf) reached an output of an earlier call on this device - "
                 "an input was non-finite, or an activation left the range of the split-fp16 MFMA operands (|x| < 65504; "
                 "INTEGRATION.md, 'Supported value range').  The outputs of that call are not valid.")
+        if f & GMF_STATUS_SPARSE_DUPLICATE:
+            self.status(clear=True)
+            raise RuntimeError(
+                f"gmf_amd: {where}: a sparse tensor of an earlier call on this device had duplicate (batch, coordinates) rows - "
+                "rows must be unique (they are never merged).  The outputs of that call are not valid.")
 
     def __del__(self):
         try:

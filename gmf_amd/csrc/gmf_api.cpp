@@ -18,6 +18,7 @@
 #include "launchers_pose.hpp"
 #include "launchers_solvers.hpp"
 #include "launchers_pointcloud.hpp"
+#include "launchers_sparse.hpp"
 
 namespace {
 
@@ -1434,6 +1435,165 @@ int gmf_conv_nhwc(gmf_handle* h, const float* x, const float* wimg, const float*
               "conv_nhwc: supported are the ResNet-34 layer1 / layer2 shapes (64->64 3x3 s1, 64->128 3x3 s2, 128->128 3x3 s1, 64->128 1x1 s2)");
   SetDevice sd(h, stream);
   GMF_HIP(gmf::launch_conv_nhwc_h2(h->tune, x, wimg, bias, residual, y, B, H, W, cin, cout, ksize, stride, relu, S(stream)));
+  return GMF_OK;
+}
+
+}  // extern "C"
+
+// ---- sparse coordinate engine, sparse convolution, ResUNetBN2C weight pack ------------------------------------------------
+
+namespace {
+
+int sparse_layout(gmf_handle* h, long long M, int D, int levels, int num_maps, const int* maps, gmf::SparsePlanLayout& lay) {
+  GMF_REQUIRE(h && (maps || num_maps == 0), GMF_ERR_BAD_ARG, "sparse plan: null pointer");
+  GMF_REQUIRE(D >= 1 && D <= gmf::kSparseMaxD, GMF_ERR_UNSUPPORTED_SHAPE, "sparse plan: D must be in 1..6");
+  GMF_REQUIRE(M >= 1 && M < (1LL << 28), GMF_ERR_UNSUPPORTED_SHAPE, "sparse plan: the row count must be in 1 .. 2^28 - 1");
+  GMF_REQUIRE(levels >= 1 && levels <= gmf::kSparseMaxLevels && num_maps >= 0 && num_maps <= gmf::kSparseMaxMaps,
+              GMF_ERR_UNSUPPORTED_SHAPE, "sparse plan: 1..8 levels and 0..16 kernel maps");
+  gmf::SparseMapDesc d[gmf::kSparseMaxMaps];
+  for (int m = 0; m < num_maps; ++m) d[m] = {maps[3 * m], maps[3 * m + 1], maps[3 * m + 2]};
+  GMF_REQUIRE(gmf::sparse_plan_layout(M, D, levels, num_maps, d, lay), GMF_ERR_UNSUPPORTED_SHAPE,
+              "sparse plan: a kernel map needs an odd kernel size with k^D <= 1024, levels that exist and differ by at most one, "
+              "and fewer than 2^31 pairs (rows x k^D)");
+  return GMF_OK;
+}
+
+// The convolutions of ResUNetBN2C (resunet_new.py:424-721) in forward order: (kernel key, BatchNorm prefix or "", bias key or "")
+struct ResunetLayer { const char* conv; const char* norm; const char* bias; };
+const ResunetLayer kResunetLayers[GMF_SPARSE_RESUNET_LAYERS] = {
+    {"conv1", "norm1", ""},
+    {"block1.conv1", "block1.norm1", ""}, {"block1.conv2", "block1.norm2", ""},
+    {"conv2", "norm2", ""},
+    {"block2.conv1", "block2.norm1", ""}, {"block2.conv2", "block2.norm2", ""},
+    {"conv3", "norm3", ""},
+    {"block3.conv1", "block3.norm1", ""}, {"block3.conv2", "block3.norm2", ""},
+    {"conv4", "norm4", ""},
+    {"block4.conv1", "block4.norm1", ""}, {"block4.conv2", "block4.norm2", ""},
+    {"conv4_tr", "norm4_tr", ""},
+    {"block4_tr.conv1", "block4_tr.norm1", ""}, {"block4_tr.conv2", "block4_tr.norm2", ""},
+    {"conv3_tr", "norm3_tr", ""},
+    {"block3_tr.conv1", "block3_tr.norm1", ""}, {"block3_tr.conv2", "block3_tr.norm2", ""},
+    {"conv2_tr", "norm2_tr", ""},
+    {"block2_tr.conv1", "block2_tr.norm1", ""}, {"block2_tr.conv2", "block2_tr.norm2", ""},
+    {"conv1_tr", "", ""},
+    {"final", "", "final.bias"},
+};
+
+const gmf_tensor* find_tensor(const gmf_tensor* t, int n, const std::string& name) {
+  for (int i = 0; i < n; ++i)
+    if (t[i].name && name == t[i].name) return &t[i];
+  return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gmf_sparse_plan_bytes(gmf_handle* h, long long M, int D, int levels, int num_maps, const int* maps, long long* bytes) {
+  GMF_REQUIRE(bytes, GMF_ERR_BAD_ARG, "sparse_plan_bytes: null pointer");
+  gmf::SparsePlanLayout lay;
+  if (int rc = sparse_layout(h, M, D, levels, num_maps, maps, lay)) return rc;
+  *bytes = (long long)lay.total;
+  return GMF_OK;
+}
+
+int gmf_sparse_build_plan(gmf_handle* h, const int* coords, long long M, int D, int levels, int num_maps, const int* maps,
+                          void* plan, long long plan_bytes, long long* offsets, gmf_stream_t stream) {
+  GMF_REQUIRE(h && coords && plan && offsets, GMF_ERR_BAD_ARG, "sparse_build_plan: null pointer");
+  gmf::SparsePlanLayout lay;
+  if (int rc = sparse_layout(h, M, D, levels, num_maps, maps, lay)) return rc;
+  GMF_REQUIRE(plan_bytes >= (long long)lay.total, GMF_ERR_BAD_ARG, "sparse_build_plan: the plan block is smaller than gmf_sparse_plan_bytes");
+  int k = 0;
+  offsets[k++] = (long long)lay.counts;
+  for (int l = 0; l < levels; ++l) offsets[k++] = (long long)lay.coords[l];
+  for (int m = 0; m < num_maps; ++m) {
+    offsets[k++] = (long long)lay.row_ptr[m];
+    offsets[k++] = (long long)lay.pairs[m];
+    offsets[k++] = (long long)lay.by_off[m];
+    offsets[k++] = (long long)lay.off_start[m];
+  }
+  SetDevice sd(h, stream);
+  GMF_HIP(gmf::launch_sparse_build_plan(coords, lay, static_cast<char*>(plan), h->status_dev, GMF_STATUS_SPARSE_DUPLICATE,
+                                        S(stream)));
+  return GMF_OK;
+}
+
+int gmf_sparse_conv(gmf_handle* h, const int* row_ptr, const int* pairs, const int* by_off, const int* off_start, int K,
+                    const int* n_out, long long cap_out,
+                    const float* xa, int ca, const float* xb, int cb, const float* W, int cout, const float* scale,
+                    const float* shift, const float* residual, int relu, int nsplit, float* y, gmf_stream_t stream) {
+  GMF_REQUIRE(h && n_out && xa && W && y, GMF_ERR_BAD_ARG, "sparse_conv: null pointer");
+  GMF_REQUIRE((row_ptr == nullptr) == (pairs == nullptr) && (row_ptr == nullptr) == (by_off == nullptr) &&
+                  (row_ptr == nullptr) == (off_start == nullptr),
+              GMF_ERR_BAD_ARG, "sparse_conv: row_ptr, pairs, by_off and off_start go together");
+  GMF_REQUIRE(K >= 1 && K <= gmf::kSparseMaxK && (row_ptr || K == 1), GMF_ERR_UNSUPPORTED_SHAPE,
+              "sparse_conv: K must be in 1..1024 (1 for the identity map)");
+  GMF_REQUIRE(cap_out >= 1 && cap_out < (1LL << 28), GMF_ERR_UNSUPPORTED_SHAPE, "sparse_conv: cap_out must be in 1 .. 2^28 - 1");
+  GMF_REQUIRE(ca >= 1 && cb >= 0 && (cb == 0 || xb) && cout >= 1 && ca + cb <= 4096 && cout <= 4096, GMF_ERR_UNSUPPORTED_SHAPE,
+              "sparse_conv: channel counts must be in 1..4096 (cb may be 0)");
+  GMF_REQUIRE(nsplit >= 1 && nsplit <= K, GMF_ERR_BAD_ARG, "sparse_conv: nsplit must be in 1..K");
+  SetDevice sd(h, stream);
+  GMF_REQUIRE(row_ptr || nsplit == 1, GMF_ERR_BAD_ARG, "sparse_conv: the identity map takes nsplit = 1");
+  gmf::SparseConvArgs a{row_ptr, reinterpret_cast<const int2*>(pairs), by_off, off_start, K, n_out, cap_out, xa, ca,
+                        cb ? xb : nullptr, cb, W, cout, scale, shift, residual, relu, nsplit, nullptr, y};
+  if (row_ptr)
+    if (int rc = arena_carve(h, {arena_buf(a.partial, (size_t)nsplit * cap_out * cout)})) return rc;
+  GMF_HIP(gmf::launch_sparse_conv(a, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_sparse_pack_resunet(gmf_handle* h, const gmf_tensor* tensors, int n_tensors, float* dev, long long dev_floats,
+                            long long* layout, long long* need_floats) {
+  GMF_REQUIRE(h && tensors && layout && need_floats, GMF_ERR_BAD_ARG, "sparse_pack_resunet: null pointer");
+  std::vector<float> blob;
+  auto put = [&](size_t n) { const size_t o = blob.size(); blob.resize(o + (n + 63) / 64 * 64, 0.f); return o; };
+  for (int i = 0; i < GMF_SPARSE_RESUNET_LAYERS; ++i) {
+    const ResunetLayer& L = kResunetLayers[i];
+    const std::string kname = std::string(L.conv) + ".kernel";
+    const gmf_tensor* kt = find_tensor(tensors, n_tensors, kname);
+    GMF_REQUIRE(kt && kt->data, GMF_ERR_BAD_ARG, "sparse_pack_resunet: missing " + kname);
+    // MinkowskiEngine's kernel: [k^D, Cin, Cout], or [Cin, Cout] when k^D = 1 (assumptions)
+    GMF_REQUIRE(kt->ndim == 3 || kt->ndim == 2, GMF_ERR_BAD_ARG, "sparse_pack_resunet: " + kname + " must be [K, Cin, Cout] or [Cin, Cout]");
+    const long long K = kt->ndim == 3 ? kt->shape[0] : 1;
+    const long long cin = kt->ndim == 3 ? kt->shape[1] : kt->shape[0];
+    const long long cout = kt->ndim == 3 ? kt->shape[2] : kt->shape[1];
+    GMF_REQUIRE(K >= 1 && K <= gmf::kSparseMaxK && cin >= 1 && cout >= 1, GMF_ERR_UNSUPPORTED_SHAPE,
+                "sparse_pack_resunet: " + kname + " has an unsupported shape");
+    const size_t wo = put((size_t)(K * cin * cout));
+    std::copy(kt->data, kt->data + K * cin * cout, blob.begin() + wo);
+    long long so = -1, ho = -1;
+    if (*L.norm) {
+      const std::string p = std::string(L.norm) + ".bn.";
+      const gmf_tensor* g = find_tensor(tensors, n_tensors, p + "weight");
+      const gmf_tensor* b = find_tensor(tensors, n_tensors, p + "bias");
+      const gmf_tensor* mu = find_tensor(tensors, n_tensors, p + "running_mean");
+      const gmf_tensor* var = find_tensor(tensors, n_tensors, p + "running_var");
+      GMF_REQUIRE(g && b && mu && var, GMF_ERR_BAD_ARG, "sparse_pack_resunet: missing " + p + "{weight,bias,running_mean,running_var}");
+      for (const gmf_tensor* t : {g, b, mu, var})
+        GMF_REQUIRE(t->ndim == 1 && t->shape[0] == cout, GMF_ERR_BAD_ARG, "sparse_pack_resunet: " + p + "* must be [" + std::to_string(cout) + "]");
+      so = (long long)put((size_t)cout);
+      ho = (long long)put((size_t)cout);
+      for (long long c = 0; c < cout; ++c) {   // eval BatchNorm1d, eps 1e-5, folded in fp64
+        const double sc = (double)g->data[c] / std::sqrt((double)var->data[c] + 1e-5);
+        blob[so + c] = (float)sc;
+        blob[ho + c] = (float)((double)b->data[c] - (double)mu->data[c] * sc);
+      }
+    } else if (*L.bias) {
+      const gmf_tensor* b = find_tensor(tensors, n_tensors, L.bias);
+      // MinkowskiEngine's bias: [1, Cout] (assumptions)
+      GMF_REQUIRE(b && b->data && b->ndim == 2 && b->shape[0] == 1 && b->shape[1] == cout, GMF_ERR_BAD_ARG,
+                  std::string("sparse_pack_resunet: ") + L.bias + " must be [1, " + std::to_string(cout) + "]");
+      ho = (long long)put((size_t)cout);
+      std::copy(b->data, b->data + cout, blob.begin() + ho);
+    }
+    long long* e = layout + 6 * i;
+    e[0] = (long long)wo; e[1] = so; e[2] = ho; e[3] = K; e[4] = cin; e[5] = cout;
+  }
+  *need_floats = (long long)blob.size();
+  if (!dev) return GMF_OK;
+  GMF_REQUIRE(dev_floats >= (long long)blob.size(), GMF_ERR_BAD_ARG, "sparse_pack_resunet: the device block is too small");
+  SetDevice sd(h);
+  GMF_HIP(hipMemcpy(dev, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
   return GMF_OK;
 }
 

@@ -1,0 +1,476 @@
+"""Sparse convolution over up to 6-D coordinates and DGR's inlier network ResUNetBN2C
+(reference: GMF_DeepGlobalRegistration/*/model/resunet_new.py:424-721, model/residual_block.py, model/common.py), eval-mode and
+forward-only.  Kernels: csrc/sparse_kernels.hip.
+
+The coordinate engine (`SparsePlan`) takes MinkowskiEngine's batched coordinates, int32 [M, 1 + D] with the batch index in
+column 0, and builds on the device every coarser level (unique floor(c / 2t) * 2t, batch kept, ascending in (batch, c_1 ..
+c_D); level 0 is the input rows in input order) and every kernel map the network needs.  All buffers are sized from M and k^D
+and the row counts stay on the device, so a forward makes no host synchronisation and can be captured into a graph.
+`sparse_conv` is one convolution over a map of a plan with the fused epilogue (folded BatchNorm, residual, ReLU, bias) and
+two-source input ([x_a | x_b], MinkowskiEngine's ME.cat without materialising it).  fp32 throughout; each output element sums
+its offsets in ascending order and its input channels in order, without float atomics, so results are bitwise repeatable and
+independent of the input row order.
+
+Conventions read from MinkowskiEngine v0.5 and not verified against it ("Sparse inlier network"): the offset
+index inside `kernel` has the first spatial axis varying fastest (`kernel_offsets`); `kernel` is [Cin, Cout] when k^D = 1
+(`kernel_shape`); `bias` is [1, Cout]; a coarse coordinate is floor(c / 2t) * 2t for negative c too (csrc: coarse_coord).
+"""
+from __future__ import annotations
+
+import ctypes
+
+import torch
+from torch import nn
+
+from . import _lib
+from ._util import WeightWatcher, handle_and_stream
+from .perceiver_io import PerceiverIO
+from .pointdsc import ImageEncoder
+
+MAX_D = 6
+MAX_KERNEL_VOLUME = 1024
+MAX_LEVELS = 8
+MAX_MAPS = 16
+
+
+def _fail(what, msg, exc=RuntimeError):
+    raise exc(f"gmf_amd.{what}: {msg}")
+
+
+def kernel_volume(kernel_size: int, D: int) -> int:
+    return int(kernel_size) ** int(D)
+
+
+def kernel_offsets(kernel_size: int, D: int):
+    """The offset of each index d of a hypercube kernel, the first spatial axis varying fastest (MinkowskiEngine's order, an
+    assumption: INTEGRATION.md).  The device maps (csrc: neighbour_key) follow the same rule."""
+    k = int(kernel_size)
+    out = []
+    for d in range(k ** D):
+        out.append(tuple((d // k ** a) % k - k // 2 for a in range(D)))
+    return out
+
+
+def kernel_shape(kernel_size: int, D: int, cin: int, cout: int):
+    """MinkowskiEngine's `kernel` parameter: [k^D, Cin, Cout], or [Cin, Cout] when k^D = 1 (an assumption: INTEGRATION.md)."""
+    K = kernel_volume(kernel_size, D)
+    return (K, cin, cout) if K > 1 else (cin, cout)
+
+
+def _check_map_desc(maps, D, levels, what):
+    out = []
+    for m in maps:
+        k, o, i = (int(v) for v in m)
+        if k < 1 or k % 2 == 0:
+            _fail(what, f"kernel size {k} must be odd and >= 1")
+        if k ** D > MAX_KERNEL_VOLUME:
+            _fail(what, f"kernel volume {k}^{D} = {k ** D} exceeds {MAX_KERNEL_VOLUME}", NotImplementedError)
+        if not (0 <= o < levels and 0 <= i < levels and abs(o - i) <= 1):
+            _fail(what, f"map ({k}, {o}, {i}): levels must exist and differ by at most one")
+        out.append((k, o, i))
+    if len(out) > MAX_MAPS:
+        _fail(what, f"at most {MAX_MAPS} kernel maps")
+    return out
+
+
+def check_coords(coords, what="SparsePlan"):
+    """Shape / dtype / device checks of MinkowskiEngine batched coordinates [M, 1 + D] int32; returns (M, D)."""
+    if not isinstance(coords, torch.Tensor):
+        _fail(what, "`coords` must be a torch tensor")
+    if coords.dtype != torch.int32:
+        _fail(what, f"`coords` must be int32 (got {coords.dtype})")
+    if coords.dim() != 2 or coords.shape[0] == 0 or not (2 <= coords.shape[1] <= 1 + MAX_D):
+        _fail(what, f"`coords` must be a non-empty [M, 1 + D] tensor with D in 1..{MAX_D} (got {tuple(coords.shape)})")
+    if not coords.is_cuda:
+        _fail(what, f"`coords` must live on a HIP device (got {coords.device}); the HIP path is mandatory, there is no CPU fallback")
+    return coords.shape[0], coords.shape[1] - 1
+
+
+class SparsePlan:
+    """Levels and kernel maps of one coordinate set, on the device (`gmf_sparse_build_plan`).
+
+    maps: (k, out level, in level) triples.  Same level: output o reads input o + d t; out = in + 1 (downsampling): o + d t with
+    t the input stride; out = in - 1 (transposed): fine output p reads coarse input o when p = o + d t.  Every level has M
+    row slots; `counts[l]` (device int32) says how many are used.  A duplicate input row raises at the next
+    `gmf_amd.check_status()` (or the next forward of a module on the device)."""
+
+    def __init__(self, coords, levels: int, maps=()):
+        self.M, self.D = check_coords(coords)
+        if not (1 <= levels <= MAX_LEVELS):
+            _fail("SparsePlan", f"levels must be in 1..{MAX_LEVELS}")
+        self.levels = int(levels)
+        self.maps = _check_map_desc(maps, self.D, self.levels, "SparsePlan")
+        self.K = [kernel_volume(k, self.D) for k, _, _ in self.maps]
+        coords = coords.contiguous()
+        h, st = handle_and_stream(coords)
+        flat = [v for m in self.maps for v in m] or [0]
+        desc = (ctypes.c_int * len(flat))(*flat)
+        nbytes = ctypes.c_longlong(0)
+        h.check(h.lib.gmf_sparse_plan_bytes(h.h, self.M, self.D, self.levels, len(self.maps), desc, ctypes.byref(nbytes)),
+                "gmf_sparse_plan_bytes")
+        self.buf = torch.empty(nbytes.value, dtype=torch.uint8, device=coords.device)
+        offs = (ctypes.c_longlong * (1 + self.levels + 4 * len(self.maps)))()
+        h.call("gmf_sparse_build_plan", coords.data_ptr(), self.M, self.D, self.levels, len(self.maps), desc,
+               self.buf.data_ptr(), nbytes.value, offs, st)
+        self._offs = list(offs)
+        self._coords_keepalive = coords
+
+    def _view(self, off, n, dtype):
+        b = self.buf[off:off + n * torch.empty((), dtype=dtype).element_size()]
+        return b.view(dtype)
+
+    @property
+    def counts(self) -> torch.Tensor:
+        """int32 [levels] on the device: rows used in each level."""
+        return self._view(self._offs[0], 16, torch.int32)[:self.levels]
+
+    def count_ptr(self, level: int) -> int:
+        return self.buf.data_ptr() + self._offs[0] + 4 * int(level)
+
+    def level_coords(self, level: int) -> torch.Tensor:
+        """int32 [M, 1 + D] on the device: the rows of a level (only the first counts[level] are valid)."""
+        v = self._view(self._offs[1 + level], self.M * 8, torch.int32).view(self.M, 8)
+        return v[:, :1 + self.D]
+
+    def kernel_map(self, m: int):
+        """(row_ptr int32 [M + 1], pairs int32 [M * K, 2]) of map m, on the device: CSR over the output rows of
+        (offset index, input row), ascending offset per row."""
+        base = 1 + self.levels + 4 * m
+        rp = self._view(self._offs[base], self.M + 1, torch.int32)
+        pairs = self._view(self._offs[base + 1], self.M * self.K[m] * 2, torch.int32).view(self.M * self.K[m], 2)
+        return rp, pairs
+
+    def offset_lists(self, m: int):
+        """(by_off int32 [M * K], off_start int32 [K + 1]) of map m, on the device: the CSR pair indices sorted by offset
+        (ascending output row within one offset); offset d's pairs are by_off[off_start[d]:off_start[d + 1]]."""
+        base = 1 + self.levels + 4 * m
+        return (self._view(self._offs[base + 2], self.M * self.K[m], torch.int32),
+                self._view(self._offs[base + 3], self.K[m] + 1, torch.int32))
+
+    def to_host(self):
+        """Levels and maps as host tensors (synchronises; for tests and tools): {"counts", "levels": [[n_l, 1 + D]], "maps":
+        [(row_ptr [n_out + 1], pairs [nnz, 2])]}."""
+        n = self.counts.cpu().tolist()
+        lv = [self.level_coords(l)[:n[l]].cpu() for l in range(self.levels)]
+        mp = []
+        for m, (_, o, _) in enumerate(self.maps):
+            rp, pairs = self.kernel_map(m)
+            rp = rp[:n[o] + 1].cpu()
+            mp.append((rp, pairs[:int(rp[-1])].cpu()))
+        return {"counts": n, "levels": lv, "maps": mp}
+
+
+def _f32_dev(t, name, what):
+    if not isinstance(t, torch.Tensor):
+        _fail(what, f"`{name}` must be a torch tensor")
+    if not t.is_cuda:
+        _fail(what, f"`{name}` must live on a HIP device (got {t.device}); the HIP path is mandatory, there is no CPU fallback")
+    if t.dtype != torch.float32:
+        _fail(what, f"`{name}` must be float32 (got {t.dtype})")
+    return t.contiguous()
+
+
+def sparse_conv(plan: SparsePlan, map_index, out_level: int, xa, W, xb=None, scale=None, shift=None, residual=None,
+                relu: bool = False, nsplit: int = 1, out=None):
+    """One sparse convolution over kernel map `map_index` of `plan` (None: the identity map, k = 1) into level `out_level`.
+
+    xa [M, ca] (and xb [M, cb]: the input is [xa | xb]) hold the input level's rows; W is MinkowskiEngine's `kernel`,
+    [K, ca + cb, cout] (or [ca + cb, cout] when K = 1).  y = v * scale + shift (one fma; absent: 1 / 0), + residual [M, cout],
+    then ReLU if `relu`.  Returns out [M, cout]; only the first counts[out_level] rows are written.  `out` must not overlap any
+    input (other workgroups would read rows it has already overwritten).  nsplit (1..K; 1 for the identity map) cuts the
+    offsets into fixed slices that run on separate workgroups: it changes how the sum is grouped, so keep it fixed per layer
+    for bitwise-equal results."""
+    what = "sparse_conv"
+    xa = _f32_dev(xa, "xa", what)
+    W = _f32_dev(W, "W", what)
+    M = plan.M
+    if xa.dim() != 2 or xa.shape[0] != M:
+        _fail(what, f"`xa` must be [M = {M}, ca] (got {tuple(xa.shape)})")
+    ca, cb = xa.shape[1], 0
+    if xb is not None:
+        xb = _f32_dev(xb, "xb", what)
+        if xb.dim() != 2 or xb.shape[0] != M:
+            _fail(what, f"`xb` must be [M = {M}, cb] (got {tuple(xb.shape)})")
+        cb = xb.shape[1]
+    if map_index is None:
+        K, rp, pairs, by_off, off_start = 1, None, None, None, None
+    else:
+        K = plan.K[map_index]
+        if plan.maps[map_index][1] != out_level:
+            _fail(what, f"map {map_index} writes level {plan.maps[map_index][1]}, not {out_level}")
+        rp, pairs = plan.kernel_map(map_index)
+        by_off, off_start = plan.offset_lists(map_index)
+    if W.dim() == 2 and K == 1:
+        W = W.unsqueeze(0)
+    if W.dim() != 3 or W.shape[0] != K or W.shape[1] != ca + cb:
+        _fail(what, f"`W` must be [K = {K}, Cin = {ca + cb}, Cout] (got {tuple(W.shape)})")
+    cout = W.shape[2]
+    vecs = []
+    for name, v, shape in (("scale", scale, (cout,)), ("shift", shift, (cout,)), ("residual", residual, (M, cout))):
+        if v is not None:
+            v = _f32_dev(v, name, what)
+            if tuple(v.shape) != shape and not (name != "residual" and v.numel() == cout):
+                _fail(what, f"`{name}` must be {list(shape)} (got {tuple(v.shape)})")
+        vecs.append(v)
+    if not (1 <= int(nsplit) <= K):
+        _fail(what, f"nsplit must be in 1..K = {K}")
+    if out is None:
+        out = torch.empty((M, cout), dtype=torch.float32, device=xa.device)
+    elif out.shape != (M, cout) or out.dtype != torch.float32 or not out.is_contiguous():
+        _fail(what, f"`out` must be a contiguous float32 [{M}, {cout}] tensor")
+    else:
+        for name, t in (("xa", xa), ("xb", xb), ("W", W), ("scale", vecs[0]), ("shift", vecs[1]), ("residual", vecs[2])):
+            if t is not None and _overlap(out, t):
+                _fail(what, f"`out` overlaps `{name}`: the convolution cannot run in place")
+    h, st = handle_and_stream(xa)
+    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    h.call("gmf_sparse_conv", p(rp), p(pairs), p(by_off), p(off_start), K, plan.count_ptr(out_level), M, xa.data_ptr(), ca,
+           p(xb), cb, W.data_ptr(), cout, p(vecs[0]), p(vecs[1]), p(vecs[2]), 1 if relu else 0, int(nsplit), out.data_ptr(), st)
+    return out
+
+
+def _overlap(a, b) -> bool:
+    """Whether two contiguous tensors share any byte."""
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
+def layer_nsplit(K: int, cin: int, cout: int) -> int:
+    """Offset slices of one convolution of the network, a function of its shape alone (so every call groups its sums the same
+    way).  A kernel of more than 16 MiB is read once per 64 pairs of an offset by one output-row group, and the slices give the
+    parallelism: about 256 workgroups (slices x 64-channel blocks).  A smaller kernel runs in 9 slices and the device is filled
+    by output-row groups (csrc: sparse_conv_row_groups).  The workspace holds nsplit x M x cout floats."""
+    if K == 1:
+        return 1
+    if K * cin * cout * 4 > (16 << 20):
+        return min(K, -(-256 // -(-cout // 64)))
+    return min(K, 9)
+
+
+# ---- ResUNetBN2C ------------------------------------------------------------------------------------------------------------
+# The modules below only HOLD parameters under the reference's names (MinkowskiConvolution.kernel / .bias,
+# MinkowskiBatchNorm.bn.*); the forward is `sparse_conv` over one plan per call.
+
+class _MinkowskiConvolution(nn.Module):
+    def __init__(self, cin, cout, kernel_size, D, bias=False):
+        super().__init__()
+        self.kernel_size = int(kernel_size)
+        self.kernel = nn.Parameter(torch.empty(kernel_shape(kernel_size, D, cin, cout)))
+        nn.init.normal_(self.kernel, std=(2.0 / (kernel_volume(kernel_size, D) * cin)) ** 0.5)
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(1, cout))     # [1, Cout] (an assumption: INTEGRATION.md)
+
+
+class _MinkowskiBatchNorm(nn.Module):
+    def __init__(self, C, momentum):
+        super().__init__()
+        self.bn = nn.BatchNorm1d(C, momentum=momentum)
+
+
+class _BasicBlockBN(nn.Module):          # residual_block.py:82-123 (no downsample)
+    def __init__(self, C, momentum, D):
+        super().__init__()
+        self.conv1 = _MinkowskiConvolution(C, C, 3, D)
+        self.norm1 = _MinkowskiBatchNorm(C, momentum)
+        self.conv2 = _MinkowskiConvolution(C, C, 3, D)
+        self.norm2 = _MinkowskiBatchNorm(C, momentum)
+
+
+# state_dict prefixes of the reference's image encoder that its forward never runs (resnet.py:147-152, 209-211); a strict
+# load_state_dict of a DGR checkpoint hands them in, and they are accepted and dropped
+_UNUSED_IMAGE_KEYS = ("img_encoder.backbone.layer3.", "img_encoder.backbone.layer4.", "img_encoder.backbone.fc.")
+
+# Kernel maps of one forward: (k, out level, in level).  0-3 same-stride, 4-6 downsampling, 7-9 their transposes.
+_NET_MAPS = [(3, 0, 0), (3, 1, 1), (3, 2, 2), (3, 3, 3), (3, 1, 0), (3, 2, 1), (3, 3, 2), (3, 0, 1), (3, 1, 2), (3, 2, 3)]
+
+
+class ResUNetBN2C(nn.Module):
+    """DGR's inlier network (resunet_new.py:424-721 with ResUNetBN2C's channels), eval-mode forward on the device.
+
+    forward(coords [M, 1 + D] int32, feats [M, in_channels] float32, p_image, q_image [1, 3, H, W]) -> [M, out_channels],
+    aligned with the input rows.  p_tokens / q_tokens [1, T, 128] may replace the images (the image encoder's output, as in
+    `PointDSC`).  The image pair has batch size 1 and the bottleneck's queries are all stride-8 rows as one sequence
+    (resunet_new.py:694-701), in ascending (batch, coordinates) order: with pe=True the position encoding runs along that order
+    (MinkowskiEngine's order there depends on its hash, so ours is a definition, not parity)."""
+
+    CHANNELS = [None, 32, 64, 128, 256]
+    TR_CHANNELS = [None, 64, 64, 64, 128]
+    REGION_TYPE = "HYPER_CUBE"
+
+    def __init__(self, in_channels=3, out_channels=32, bn_momentum=0.1, conv1_kernel_size=3, normalize_feature=False, D=3,
+                 pe=False):
+        super().__init__()
+        if self.REGION_TYPE != "HYPER_CUBE":
+            raise NotImplementedError(f"gmf_amd.{type(self).__name__}: only the hypercube kernel region is built "
+                                      f"(got {self.REGION_TYPE})")
+        if not (1 <= int(D) <= MAX_D):
+            raise ValueError(f"gmf_amd.ResUNetBN2C: D must be in 1..{MAX_D} (got {D})")
+        for k in (conv1_kernel_size, 3):
+            if k % 2 == 0 or k < 1:
+                raise ValueError(f"gmf_amd.ResUNetBN2C: kernel size {k} must be odd")
+            if kernel_volume(k, D) > MAX_KERNEL_VOLUME:
+                raise NotImplementedError(f"gmf_amd.ResUNetBN2C: kernel volume {k}^{D} exceeds {MAX_KERNEL_VOLUME}")
+        if normalize_feature:
+            raise NotImplementedError("gmf_amd.ResUNetBN2C: normalize_feature=True is not built (DGR's inlier network uses False)")
+        CH, TR = self.CHANNELS, self.TR_CHANNELS
+        self.D, self.pe, self.conv1_kernel_size = int(D), bool(pe), int(conv1_kernel_size)
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.normalize_feature = normalize_feature
+        m = bn_momentum
+        self.conv1 = _MinkowskiConvolution(in_channels, CH[1], conv1_kernel_size, D)
+        self.norm1 = _MinkowskiBatchNorm(CH[1], m)
+        self.block1 = _BasicBlockBN(CH[1], m, D)
+        self.conv2 = _MinkowskiConvolution(CH[1], CH[2], 3, D)
+        self.norm2 = _MinkowskiBatchNorm(CH[2], m)
+        self.block2 = _BasicBlockBN(CH[2], m, D)
+        self.conv3 = _MinkowskiConvolution(CH[2], CH[3], 3, D)
+        self.norm3 = _MinkowskiBatchNorm(CH[3], m)
+        self.block3 = _BasicBlockBN(CH[3], m, D)
+        self.conv4 = _MinkowskiConvolution(CH[3], CH[4], 3, D)
+        self.norm4 = _MinkowskiBatchNorm(CH[4], m)
+        self.perceiver_io = PerceiverIO(depth=0, dim=128, latent_dim=CH[4], cross_heads=1, latent_heads=8,
+                                        cross_dim_head=CH[4] // 2, latent_dim_head=CH[4] // 2, pe=self.pe)
+        self.block4 = _BasicBlockBN(CH[4], m, D)
+        self.conv4_tr = _MinkowskiConvolution(CH[4], TR[4], 3, D)
+        self.norm4_tr = _MinkowskiBatchNorm(TR[4], m)
+        self.block4_tr = _BasicBlockBN(TR[4], m, D)
+        self.conv3_tr = _MinkowskiConvolution(CH[3] + TR[4], TR[3], 3, D)
+        self.norm3_tr = _MinkowskiBatchNorm(TR[3], m)
+        self.block3_tr = _BasicBlockBN(TR[3], m, D)
+        self.conv2_tr = _MinkowskiConvolution(CH[2] + TR[3], TR[2], 3, D)
+        self.norm2_tr = _MinkowskiBatchNorm(TR[2], m)
+        self.block2_tr = _BasicBlockBN(TR[2], m, D)
+        self.conv1_tr = _MinkowskiConvolution(CH[1] + TR[2], TR[1], 1, D)
+        self.final = _MinkowskiConvolution(TR[1], out_channels, 1, D, bias=True)
+        self.img_encoder = ImageEncoder()
+        self.image_fusion = PerceiverIO(depth=0, dim=128, latent_dim=128, cross_heads=1, latent_heads=8, cross_dim_head=64,
+                                        latent_dim_head=64)
+        for f in (self.image_fusion, self.perceiver_io):      # fp32 throughout, as the sparse convolutions
+            f.split_fp16_ff = False
+            f.split_fp16_attn = False
+        self._packed, self._packed_version = None, None
+        self._watch = WeightWatcher(self, skip_prefix="img_encoder.")
+
+    # -- weights --------------------------------------------------------------------------------------------------------------
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        sd = {k: v for k, v in state_dict.items() if not k.startswith(_UNUSED_IMAGE_KEYS)}
+        out = super().load_state_dict(sd, strict=strict, **kw)
+        self._watch.invalidate()
+        self._packed = None
+        return out
+
+    def _apply(self, fn, *a, **kw):
+        out = super()._apply(fn, *a, **kw)
+        if hasattr(self, "_watch"):
+            self._watch.invalidate()
+        return out
+
+    def _weights(self, device):
+        """The 23 convolutions packed with their BatchNorms folded (`gmf_sparse_pack_resunet`), rebuilt when a weight changes."""
+        key = (self._watch.version(), torch.device(device))
+        if self._packed is None or self._packed_version != key:
+            sd = {k: v for k, v in self.state_dict().items()
+                  if not k.startswith(("img_encoder.", "image_fusion.", "perceiver_io."))}
+            arr, keep = _lib.tensor_list(sd)
+            h, _ = handle_and_stream(torch.empty(0, device=device))
+            layout = (ctypes.c_longlong * (6 * 23))()
+            need = ctypes.c_longlong(0)
+            h.check(h.lib.gmf_sparse_pack_resunet(h.h, arr, len(arr), None, 0, layout, ctypes.byref(need)),
+                    "gmf_sparse_pack_resunet")
+            blob = torch.empty(need.value, dtype=torch.float32, device=device)
+            h.check(h.lib.gmf_sparse_pack_resunet(h.h, arr, len(arr), ctypes.c_void_p(blob.data_ptr()), need.value, layout,
+                                                  ctypes.byref(need)), "gmf_sparse_pack_resunet")
+            del keep
+            layers = []
+            for i in range(23):
+                wo, so, ho, K, cin, cout = layout[6 * i:6 * i + 6]
+                W = blob[wo:wo + K * cin * cout].view(K, cin, cout)
+                layers.append((W, None if so < 0 else blob[so:so + cout], None if ho < 0 else blob[ho:ho + cout]))
+            self._packed, self._packed_version = (blob, layers), key
+        return self._packed[1]
+
+    # -- forward --------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_images(p_image, q_image, p_tokens, q_tokens):
+        """Shapes only (no device needed).  The reference fuses ONE image pair: its bottleneck queries are all stride-8 rows as one
+        sequence (resunet_new.py:697), which is ill-defined for an image batch > 1."""
+        if p_tokens is not None or q_tokens is not None:
+            pairs, shape = (("p_tokens", p_tokens), ("q_tokens", q_tokens)), "[1, T, 128]"
+            ok = lambda t: t is not None and t.dim() == 3 and t.shape[0] == 1 and t.shape[2] == 128   # noqa: E731
+        else:
+            pairs, shape = (("p_image", p_image), ("q_image", q_image)), "[1, 3, H, W]"
+            ok = lambda t: t is not None and t.dim() == 4 and t.shape[0] == 1 and t.shape[1] == 3     # noqa: E731
+        for name, t in pairs:
+            if t is None:
+                raise RuntimeError("gmf_amd.ResUNetBN2C: pass p_image and q_image, or p_tokens and q_tokens")
+            if not ok(t):
+                raise RuntimeError(f"gmf_amd.ResUNetBN2C: `{name}` must be {shape}: the reference fuses one image pair "
+                                   f"(got {tuple(t.shape)})")
+
+    def _tokens(self, p_image, q_image, p_tokens, q_tokens):
+        if p_tokens is None:
+            p_tokens = self.img_encoder(p_image).flatten(2).permute(0, 2, 1).contiguous()
+            q_tokens = self.img_encoder(q_image).flatten(2).permute(0, 2, 1).contiguous()
+        return p_tokens, q_tokens
+
+    def forward(self, coords, feats, p_image=None, q_image=None, p_tokens=None, q_tokens=None):
+        if self.training:
+            raise RuntimeError("gmf_amd.ResUNetBN2C: only the eval-mode forward is built - call eval()")
+        self._check_images(p_image, q_image, p_tokens, q_tokens)
+        M, D = check_coords(coords, "ResUNetBN2C")
+        if D != self.D:
+            raise RuntimeError(f"gmf_amd.ResUNetBN2C: coords have D = {D}, the network was built for D = {self.D}")
+        feats = _f32_dev(feats, "feats", "ResUNetBN2C")
+        if feats.dim() != 2 or feats.shape != (M, self.in_channels):
+            raise RuntimeError(f"gmf_amd.ResUNetBN2C: `feats` must be [{M}, {self.in_channels}] (got {tuple(feats.shape)})")
+        with torch.no_grad():                     # forward-only: the image encoder takes its fused eval path too
+            p_tok, q_tok = self._tokens(p_image, q_image, p_tokens, q_tokens)
+            return self._forward(coords, feats, p_tok, q_tok)
+
+    def _forward(self, coords, feats, p_tok, q_tok):
+        L = self._weights(coords.device)
+        maps = list(_NET_MAPS)
+        c1 = self.conv1_kernel_size
+        c1_map = None if c1 == 1 else (0 if c1 == 3 else len(maps))
+        if c1 not in (1, 3):
+            maps.append((c1, 0, 0))
+        plan = SparsePlan(coords, 4, maps)
+        image_feat = self.image_fusion(p_tok, queries_encoder=q_tok)       # resunet_new.py:636
+
+        def conv(i, m, lvl, xa, xb=None, residual=None, relu=False, out=None):
+            W, sc, sh = L[i]
+            return sparse_conv(plan, m, lvl, xa, W, xb=xb, scale=sc, shift=sh, residual=residual, relu=relu,
+                               nsplit=layer_nsplit(W.shape[0], W.shape[1], W.shape[2]), out=out)
+
+        def block(i, lvl, x, out=None):            # residual_block.py:104-123
+            h = conv(i, lvl, lvl, x, relu=True)
+            return conv(i + 1, lvl, lvl, h, residual=x, relu=True, out=out)
+
+        s1 = block(1, 0, conv(0, c1_map, 0, feats))                   # conv1, norm1, block1 (its ReLU makes MEF.relu a no-op)
+        s2 = block(4, 1, conv(3, 4, 1, s1))
+        s4 = block(7, 2, conv(6, 5, 2, s2))
+        # the bottleneck's rows beyond counts[3] are zero: they pad the query sequence of the position encoding (pe=True) as
+        # Conv1d's zero padding does
+        s8 = block(10, 3, conv(9, 6, 3, s4), out=torch.zeros((plan.M, 256), dtype=torch.float32, device=feats.device))
+        f8 = self.perceiver_io(image_feat, queries_encoder=s8.unsqueeze(0))[0]     # resunet_new.py:694-704
+        t4 = block(13, 2, conv(12, 9, 2, f8))
+        t2 = block(16, 1, conv(15, 8, 1, t4, xb=s4))                   # ME.cat(out_s4_tr, out_s4)
+        t1 = block(19, 0, conv(18, 7, 0, t2, xb=s2))
+        o = conv(21, None, 0, t1, xb=s1, relu=True)                    # conv1_tr on ME.cat(out_s1_tr, out_s1), MEF.relu
+        return conv(22, None, 0, o)                                    # final (+ bias)
+
+
+class ResUNetBN2CX(ResUNetBN2C):
+    """resunet_new.py:724-725: the hyper-cross kernel region.  Not built: constructing it raises NotImplementedError."""
+    REGION_TYPE = "HYPER_CROSS"
+
+
+def inlier_coordinates(coords0, coords1, idx0, idx1):
+    """The [M, 7] int32 rows of DGR's inlier network (deep_global_registration.py:297-298): (batch, voxel of the source point,
+    voxel of its correspondence) = cat(coords0[idx0], coords1[idx1, 1:]).  coords0 / coords1 [N, 4] int (batch, x, y, z)."""
+    for name, c in (("coords0", coords0), ("coords1", coords1)):
+        if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != 4 or c.dtype.is_floating_point:
+            _fail("inlier_coordinates", f"`{name}` must be an integer [N, 4] tensor (batch, x, y, z)")
+    if idx0.shape != idx1.shape or idx0.dim() != 1:
+        _fail("inlier_coordinates", "`idx0` and `idx1` must be 1-D and of equal length")
+    return torch.cat((coords0[idx0.long()], coords1[idx1.long(), 1:]), dim=1).to(torch.int32).contiguous()

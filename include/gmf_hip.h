@@ -76,6 +76,9 @@ long long gmf_workspace_wanted(gmf_handle* h);
  * gmf_encoder_forward(_ragged) to the three-product form of P V (the network's attention scores can exceed the bound of
  * gmf_encoder_weights::pv_guard there).  The results are as valid as any; the bit says why a step took ~3 % longer. */
 #define GMF_STATUS_PV_GUARDED 2
+/* gmf_sparse_build_plan met a duplicate (batch, coordinates) input row: rows must be unique, they are never merged; the
+ * plan and everything computed from it are not valid. */
+#define GMF_STATUS_SPARSE_DUPLICATE 4
 int gmf_status_read(gmf_handle* h, int* flags, int clear);
 
 /* [ABI 5] PointDSC's learnable scalar `sigma` (PointDSC.py:164) from DEVICE memory.  While `sigma_dev` is non-NULL every entry point
@@ -495,6 +498,52 @@ int gmf_voxel_down_sample(gmf_handle* h, const float* pts, const int* offsets, i
  * and the errors as gmf_voxel_down_sample. */
 int gmf_voxel_select(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double voxel,
                      int* out_idx, int* out_offsets, long long* num_out, gmf_stream_t stream);
+
+/* ---- sparse convolution over up to 6-D coordinates (MinkowskiEngine's, as DGR's inlier network ResUNetBN2C uses it) ------- */
+
+/* Sizes the device block of a sparse plan: M input rows of D (1..6) spatial coordinates, `levels` (1..8) tensor strides 1, 2,
+ * 4, ... and num_maps (0..16) kernel maps, maps [num_maps][3] = (k, out level, in level): an odd hypercube edge k with
+ * k^D <= 1024 and |out - in| <= 1.  Same level: output o reads input o + d t (t the level's stride); out = in + 1: o + d t (t the
+ * input stride); out = in - 1 (transposed): o - d t (t the output stride), so fine output p reads coarse input o when
+ * p = o + d t.  Offset index d has the first spatial axis varying fastest.  Every buffer is sized from M and k^D. */
+int gmf_sparse_plan_bytes(gmf_handle* h, long long M, int D, int levels, int num_maps, const int* maps, long long* bytes);
+
+/* Builds the plan into `plan` (device, >= gmf_sparse_plan_bytes) from coords [M, 1 + D] int32 (device; the batch index in
+ * column 0, rows unique).  Level 0 is the input rows in input order; level l + 1 holds the unique (batch, floor(c / 2^(l+1)) *
+ * 2^(l+1)) of level l, ascending in (batch, c_1 .. c_D).  Each kernel map is CSR over its output rows: row_ptr [M + 1] int32 and
+ * pairs [M * k^D] of (offset index, input row) int32 pairs, ascending offset per row; rows beyond a level's count have none.  Its
+ * offset-major form: by_off [M * k^D] int32, the CSR pair indices sorted by offset (ascending row within one offset), and
+ * off_start [k^D + 1] int32, offset d's pairs being by_off[off_start[d] .. off_start[d + 1]).
+ * offsets (host, 1 + levels + 4 num_maps) receives byte offsets into `plan`: the int32 row counts of the levels ([16]), the
+ * coordinates of each level ([M][8] int32: batch, c_1 .. c_D, zeros), then (row_ptr, pairs, by_off, off_start) of each map.  A
+ * duplicate input row sets GMF_STATUS_SPARSE_DUPLICATE.  No host synchronisation: graph-capturable. */
+int gmf_sparse_build_plan(gmf_handle* h, const int* coords, long long M, int D, int levels, int num_maps, const int* maps,
+                          void* plan, long long plan_bytes, long long* offsets, gmf_stream_t stream);
+
+/* Sparse convolution, fp32 throughout: y[o] = epilogue(sum over the map's pairs (d, i) of row o of [xa | xb][i] W[d]), W [K, ca + cb,
+ * cout] (MinkowskiEngine's `kernel` layout), xa [*, ca], xb [*, cb] (cb may be 0: one source) row-major.  row_ptr / pairs /
+ * by_off / off_start: a map of gmf_sparse_build_plan, or all NULL for the identity map (K = 1, nsplit = 1).  n_out: device
+ * pointer to the output row count (a plan's level count); rows >= *n_out are not written.  epilogue: v * scale[c] + shift[c]
+ * (one fma; NULL scale = 1, NULL shift = 0: a folded eval BatchNorm or a bias), + residual [*, cout] (may be NULL), then
+ * max(v, 0) if relu.  y must not overlap any input.  The offsets are cut into nsplit (1..K) fixed slices, slice(d) = d nsplit /
+ * K.  The workgroups of a slice walk the offset-major pair lists, so each weight block W[d] is read once per 64 pairs of d (per
+ * output-row group when W is at most 16 MiB), and write per-slice partial sums (workspace nsplit x cap_out x cout floats); a
+ * second pass adds a row's slices in order.  Each output element sums its offsets in ascending order, its input channels as
+ * 16-channel chains in order.  No float atomics: bitwise repeatable and independent of the input row order. */
+int gmf_sparse_conv(gmf_handle* h, const int* row_ptr, const int* pairs, const int* by_off, const int* off_start, int K,
+                    const int* n_out, long long cap_out, const float* xa, int ca, const float* xb, int cb, const float* W, int cout,
+                    const float* scale, const float* shift, const float* residual, int relu, int nsplit, float* y,
+                    gmf_stream_t stream);
+
+/* Packs a ResUNetBN2C state_dict (host tensors) for gmf_sparse_conv: for each of its GMF_SPARSE_RESUNET_LAYERS convolutions in
+ * forward order (conv1, block1.conv1, block1.conv2, conv2, ..., conv2_tr, block2_tr.conv1, block2_tr.conv2, conv1_tr, final) the
+ * kernel ([K, Cin, Cout], or [Cin, Cout] when K = 1), the eval BatchNorm (eps 1e-5) folded in fp64 into scale / shift, and
+ * final.bias ([1, Cout]) as its shift.  layout [GMF_SPARSE_RESUNET_LAYERS][6] receives (kernel, scale, shift offsets in floats
+ * into `dev`, -1 where absent; K, Cin, Cout); need_floats the size of the block.  dev == NULL: layout only; else the block is
+ * copied to `dev` (dev_floats >= *need_floats; synchronous). */
+#define GMF_SPARSE_RESUNET_LAYERS 23
+int gmf_sparse_pack_resunet(gmf_handle* h, const gmf_tensor* tensors, int n_tensors, float* dev, long long dev_floats,
+                            long long* layout, long long* need_floats);
 
 /* ---- validation step: the non-test forward's similarity matrix and the metrics of libs/trainer.py:194-262 ---------- */
 
