@@ -1,6 +1,6 @@
 """bench.py - correspondences/second of the GMF multimodal-fusion hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--sweep] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--sweep] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -22,9 +22,12 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
                  timed in situ with HIP events on the stream it is launched on; HBM traffic per launch from the committed
                  rocprofv3 PMC summary ONLY when that summary was taken on this very source tree (hash match), else null
   step         - the whole step against the same peak (SURVEY.md section 8d F_logits)
-  cpu_baseline - the CPU oracle (a port of the reference's PyTorch CPU path) timed on this host's cores, all cores and 1 thread
   ranks        - per-rank step time and the all-gather's own time (multi-GPU diagnostics)
-  sweep        - with --sweep: N = 1000 / 10000, the KITTI shape and the B = 1 latency points (headline unchanged)
+and, with --full on one GPU only (a plain run times the headline and nothing else):
+  sweep        - N = 1000 / 10000, the KITTI shape, the B = 1 latency points, ragged batches, the DGR rows and the first
+                 throughput numerics mode (headline unchanged); --sweep (which implies --full) adds the rest of them
+  cpu_baseline - the CPU oracle (a port of the reference's PyTorch CPU path) timed on this host's cores, all cores and 1 thread
+  parity       - pair 0 of the timed batch against the CPU oracle and an fp64 evaluation, and one KITTI-shape pair
 
 --dump-outputs DIR writes the last timed step's results (logits, final_trans, final_labels; the gathered all_logits /
 all_trans too with N > 1 ranks) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
@@ -194,7 +197,7 @@ def launch_ranks(n_ranks: int, argv, rehearsal: bool) -> int:
     return worst
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -203,10 +206,13 @@ def main():
     ap.add_argument("--ncorr", type=int, default=5000)
     ap.add_argument("--tokens", type=int, default=196)
     ap.add_argument("--kind", default="3dmatch", choices=["3dmatch", "kitti"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--sweep", action="store_true", help="full sweep: the default size points (N = 1000 / 10000, KITTI shape, B = 1, ragged) plus the "
-                                                       "throughput numerics modes and the DGR rows (rank 0, N = 1 GPU)")
-    ap.add_argument("--no-sweep", action="store_true", help="headline only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the size sweep, the CPU baseline and the parity checks against the CPU oracle "
+                         "(one GPU only; about a minute more); a plain run ends after the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no parity checks")
+    ap.add_argument("--sweep", action="store_true", help="implies --full; the sweep adds the second throughput numerics mode, "
+                                                       "GlobalRegistration and the smaller PerceiverIO voxel counts")
+    ap.add_argument("--no-sweep", action="store_true", help="with --full: no sweep")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / "
                          "float64, at most 64 MB in all (a fixed, seeded sample of every array when more)")
@@ -214,7 +220,13 @@ def main():
                     help="N > 1 ranks on a box with fewer GPUs: ranks share the devices (local_rank %% device_count) and exchange "
                          "through gloo staged over the host.  Exercises the launch line, the sharded step and the JSON line; the "
                          "numbers are NOT a measurement (the line says so)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    args.full = args.full or args.sweep
+    return args
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -352,11 +364,10 @@ def main():
             print(json.dumps(line), file=sys.stderr)
             driver.close()
             sys.exit(3)
-    if world == 1 and not args.no_sweep:
-        # the size points of SURVEY.md section 8d ride in the default line too (~10 s), so that they are in the DRIVER's record
-        # and not only in builder-run files; --sweep adds the throughput modes and the DGR rows
+    if world == 1 and args.full and not args.no_sweep:
+        # the size points of SURVEY.md section 8d (~10 s); --sweep adds the second throughput mode and the slower DGR rows
         line["sweep"] = sweep(dev, full=args.sweep)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"], line["parity"] = cpu_baseline(sd, batch, out, N, T, tau)
         if args.kind == "3dmatch":
             line["parity"]["kitti_shape"] = kitti_parity(dev)
@@ -451,7 +462,7 @@ def sweep(dev, full=False):
     lg0, T0 = model.last_logits.clone(), res0["final_trans"].clone()
     labels = {1: "throughput numerics (precision = 1: fp16 one-product attention, fp16 compat)",
               2: "throughput numerics, level 2 (precision = 2: level 1 + one-product linear stages)"}
-    # (level 1 rides in the DEFAULT line - BASELINE configs 2-3 name bf16-class arithmetic; it is labelled outside the parity gate - level 2
+    # (level 1 rides in every --full line - BASELINE configs 2-3 name bf16-class arithmetic; it is labelled outside the parity gate - level 2
     # only with --sweep)
     for level in ((1, 2) if full else (1,)):
         try:

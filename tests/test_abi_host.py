@@ -344,6 +344,20 @@ def test_bench_launches_its_own_ranks_and_refuses_without_devices():
         assert r.returncode != 0 and r.stderr.count("needs a HIP device") == 2 and not r.stdout.strip()
 
 
+def test_bench_extras_need_full(monkeypatch):
+    """A plain bench.py run times the headline alone: the sweep, the CPU baseline and the parity checks need --full, which
+    --sweep implies; --no-sweep / --no-cpu-baseline trim a --full run."""
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert (plain.full, plain.sweep, plain.steps, plain.warmup, plain.dump_outputs) == (False, False, 20, 5, None)
+    assert bench.parse_args(["--full"]).full and not bench.parse_args(["--full"]).sweep
+    swept = bench.parse_args(["--sweep"])
+    assert swept.full and swept.sweep
+    trimmed = bench.parse_args(["--full", "--no-sweep", "--no-cpu-baseline"])
+    assert trimmed.full and trimmed.no_sweep and trimmed.no_cpu_baseline
+
+
 def test_bench_dump_outputs_budget(tmp_path, monkeypatch):
     """bench.py --dump-outputs: the last step's arrays as float32 / float64 .npy files, whole under the budget; past it every
     array is cut to a seeded sample of its elements - the same sample in every run, the files together inside the budget."""

@@ -3207,3 +3207,27 @@ def test_conv_three_workgroup_form():
     assert torch.equal(outs[0], outs[1])
     want = torch.relu(torch.nn.functional.conv2d(_gpu(x), _gpu(Wt), bg, 1, 1))
     assert _maxerr(outs[0].cpu(), want.cpu()) < 1e-5
+
+
+def test_bench_plain_run_is_the_headline_alone(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` prints one JSON line with the headline, in situ roofline and step figures, and
+    writes --dump-outputs; the sweep, the CPU baseline and the parity checks are left to --full."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["metric"] == "correspondences/sec (whole node)" and line["unit"] == "correspondences/s"
+    assert line["higher_is_better"] is True and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(32 * 5000 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["roofline"]["launches_timed"] > 0 and "step" in line and "ranks" in line
+    assert not {"sweep", "cpu_baseline", "parity"} & set(line)
+    assert sorted(os.listdir(out_dir)) == ["final_labels.npy", "final_trans.npy", "logits.npy"]
+    assert np.load(out_dir / "logits.npy").shape == (32, 5000)
