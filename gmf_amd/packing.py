@@ -43,6 +43,82 @@ def p32(W: torch.Tensor) -> torch.Tensor:
     return W.reshape(M // 32, 32, K // 8, 2, 4).permute(0, 2, 3, 1, 4).reshape(-1)
 
 
+def _pad_rows(X: torch.Tensor) -> torch.Tensor:
+    """[..., rows, D] -> [..., 32 * ceil(rows / 32), D], the added rows zero."""
+    rows = X.shape[-2]
+    pad = -rows % 32
+    if pad == 0:
+        return X
+    return torch.cat([X, X.new_zeros(*X.shape[:-2], pad, X.shape[-1])], -2)
+
+
+def timg(X: torch.Tensor) -> torch.Tensor:
+    """Row-major [..., rows, D] (D % 32 == 0) -> T image [..., tiles * 32 * D] (rows >= `rows` zero), the layout of V
+    (gmf_front_forward) and of the context's Vc (gmf_fusion_ctx_prepare): the MFMA result with the FEATURE on the lane
+    (gmf_amd/csrc/mfma_core.hpp, enc_common.hpp store_block_timg).  Per 32-row tile, float4 (((db * 4 + q) * 64 + lane)
+    holds V[32 tile + 8 q + 4 h + e][32 db + i] for e = 0..3, lane = 32 h + i."""
+    D = X.shape[-1]
+    assert D % 32 == 0, D
+    Xp = _pad_rows(X)
+    lead, tiles = Xp.shape[:-2], Xp.shape[-2] // 32
+    n = len(lead)
+    g = Xp.reshape(*lead, tiles, 4, 2, 4, D // 32, 32)                       # [.., tile, q, h, e, db, i]
+    g = g.permute(*range(n), n, n + 4, n + 1, n + 2, n + 5, n + 3)           # [.., tile, db, q, h, i, e]
+    return g.reshape(*lead, -1)
+
+
+def untimg(img: torch.Tensor, rows: int, D: int) -> torch.Tensor:
+    """Inverse of `timg`: T image [..., tiles * 32 * D] -> row-major [..., rows, D] (the padding rows dropped)."""
+    lead = img.shape[:-1]
+    tiles = img.shape[-1] // (32 * D)
+    assert tiles * 32 * D == img.shape[-1] and rows <= 32 * tiles, (img.shape, rows, D)
+    n = len(lead)
+    g = img.reshape(*lead, tiles, D // 32, 4, 2, 32, 4)                      # [.., tile, db, q, h, i, e]
+    g = g.permute(*range(n), n, n + 2, n + 3, n + 5, n + 1, n + 4)           # [.., tile, q, h, e, db, i]
+    return g.reshape(*lead, tiles * 32, D)[..., :rows, :]
+
+
+def rows_p32(X: torch.Tensor) -> torch.Tensor:
+    """Row-major [..., rows, K] -> P32 image [..., tiles * 32 * K] (rows >= `rows` zero): what gmf_pack_rows_p32 writes."""
+    K = X.shape[-1]
+    assert K % 8 == 0, K
+    Xp = _pad_rows(X)
+    lead, tiles = Xp.shape[:-2], Xp.shape[-2] // 32
+    n = len(lead)
+    g = Xp.reshape(*lead, tiles, 32, K // 8, 2, 4).permute(*range(n), n, n + 2, n + 3, n + 1, n + 4)
+    return g.reshape(*lead, -1)
+
+
+def unrows_p32(img: torch.Tensor, rows: int, K: int) -> torch.Tensor:
+    """Inverse of `rows_p32` (gmf_unpack_rows_p32)."""
+    lead = img.shape[:-1]
+    tiles = img.shape[-1] // (32 * K)
+    assert tiles * 32 * K == img.shape[-1] and rows <= 32 * tiles, (img.shape, rows, K)
+    n = len(lead)
+    g = img.reshape(*lead, tiles, K // 8, 2, 32, 4).permute(*range(n), n, n + 3, n + 1, n + 2, n + 4)
+    return g.reshape(*lead, tiles * 32, K)[..., :rows, :]
+
+
+def ctx_image(Kc: torch.Tensor, Vc: torch.Tensor) -> torch.Tensor:
+    """Context image of gmf_fusion_ctx_prepare / gmf_fusion_attn_forward from row-major Kc, Vc [..., T, 64]: per 32-token
+    tile 4096 floats, Kc as P32 image (K = 64) | Vc as T image (D = 64) -> [..., tiles, 4096] (padding tokens zero)."""
+    assert Kc.shape == Vc.shape and Kc.shape[-1] == DH, (Kc.shape, Vc.shape)
+    lead = Kc.shape[:-2]
+    k = rows_p32(Kc).reshape(*lead, -1, 32 * DH)
+    v = timg(Vc).reshape(*lead, -1, 32 * DH)
+    return torch.cat([k, v], -1)
+
+
+def split_ctx_image(img: torch.Tensor, T: int):
+    """gmf_fusion_ctx_prepare output [..., tiles, 4096] (e.g. [sets, B, Tt, 4096]) -> (Kc, Vc), each row-major [..., T, 64]."""
+    lead = img.shape[:-2]
+    tiles = img.shape[-2]
+    assert img.shape[-1] == 2 * 32 * DH and T <= 32 * tiles, (img.shape, T)
+    Kc = unrows_p32(img[..., :32 * DH].reshape(*lead, tiles * 32 * DH), T, DH)
+    Vc = untimg(img[..., 32 * DH:].reshape(*lead, tiles * 32 * DH), T, DH)
+    return Kc, Vc
+
+
 def _frag_index(K: int, device):
     """Feature index visited by (k-step s, K-half h, element j) of a K-wide fragment: f = 8s + j is the fragment
     index, feature = 32*(f >> 4) + 8*((f & 15) >> 2) + 4h + (f & 3)   (gmf_amd/csrc/mfma_core.hpp)."""

@@ -181,9 +181,17 @@ int gmf_unpack_rows_p32(gmf_handle* h, const float* src_img, int B, int n_rows, 
 int gmf_pack_pts8(gmf_handle* h, const float* src, const float* tgt, int B, int N, float* dst, gmf_stream_t stream);
 
 /* ---- encoder stages (operate on images; weights are packed blobs, layouts in gmf_amd/packing.py) */
-/* layer0 (if first) + PointCN_i + projection_{q,k,v} of NonLocalBlock i.
+/* Images of a stage hold Npad = 32 ceil(N/32) rows per pair, [B, Npad/32 tiles, 32*128] floats:
+ *   P32 image of X[rows, K]: float (((b*tiles + tile)*(K/8) + g)*64 + lane)*4 + e = X[b][32 tile + i][8 g + 4 h + e];
+ *   T   image of V[rows, D]: float ((((b*tiles + tile)*(D/32) + db)*4 + q)*64 + lane)*4 + e = V[b][32 tile + 8 q + 4 h + e][32 db + i];
+ *   lane = 32 h + i, e = 0..3 (gmf_amd/packing.py: rows_p32 / timg and their inverses).
+ * Padding rows (>= N): every stage writes them (finite whenever its inputs' padding rows are finite), and an input's padding rows
+ * reach only the same padding rows of the outputs - except V, whose padding rows are multiplied by P = 0 for every query:
+ * they must be finite (NaN * 0 = NaN).  A chain that starts from gmf_pack_rows_p32 (zero padding) keeps this by itself.
+ * layer0 (if first) + PointCN_i + projection_{q,k,v} of NonLocalBlock i.
  * Replaces GMF_PointDSC/models/PointDSC.py:88,104-109 (NonLocalNet) and :56-58 (NonLocalBlock).
- * in: corr_pos [B,N,6] row-major if first, else feat P32 image.  Outputs f,q,k: P32; v: T image. */
+ * in: corr_pos [B,N,6] row-major if first, else feat P32 image.  Outputs f, q, k: P32 images; v: T image (D = 128).
+ * q = (Wq f + bq) log2(e)/sqrt(128) (the softmax scale folded in, gmf_scattn_forward takes exp2). */
 int gmf_front_forward(gmf_handle* h, int first, const float* in, const float* wst, const float* vecs, float* f,
                       float* q, float* k, float* v, int B, int N, gmf_stream_t stream);
 /* Spatial-consistency self-attention + fc_message + (message + fusion2_out).
@@ -199,7 +207,9 @@ int gmf_scattn_forward_dense(gmf_handle* h, const float* q, const float* k, cons
                              gmf_stream_t stream);
 /* Context side of FusionLayer: [LCPE] + LayerNorm_context + to_kv, for `sets` weight sets at once.
  * Replaces GMF_PointDSC/models/fusion_layer.py:124-126,46-49,86-87 (DGR twin: model/perceiver_io.py:126-128,89-91).
- * ctx: P32 image [B, Tt, 32*128]; out: [sets, B, Tt, 4096] (K image | V image per 32-token tile). */
+ * ctx: P32 image [B, Tt, 32*128], Tt = ceil(T/32); out: [sets, B, Tt, 4096]: per 32-token tile the first 2048 floats are Kc
+ * [32, 64] as a P32 image (K = 64), the next 2048 Vc [32, 64] as a T image (D = 64) (packing.py ctx_image / split_ctx_image).
+ * Set s reads wst + s*wst_stride, vecs + s*vec_stride and writes out + s*B*Tt*4096. */
 int gmf_fusion_ctx_prepare(gmf_handle* h, int pe, const float* ctx, const float* wst, const float* vecs, float* out,
                            int B, int T, int sets, int wst_stride, int vec_stride, gmf_stream_t stream);
 /* Query side up to the first residual: [LCPE] + LayerNorm + to_q + softmax(QK^T)V + to_out + x.
@@ -210,7 +220,9 @@ int gmf_fusion_attn_forward(gmf_handle* h, int pe, const float* x, const float* 
 int gmf_fusion_ff_forward(gmf_handle* h, const float* x1, const float* wst, const float* vecs, float* x2, int B,
                           int N, gmf_stream_t stream);
 /* classification head + F.normalize.  Replaces PointDSC.py:175-181,229,241.
- * Outputs are row-major: logits [B,N], feat_n [B,N,128], feat [B,N,128] (feat may be NULL). */
+ * Outputs are row-major: logits [B,N], feat_n [B,N,128], feat [B,N,128] (feat may be NULL).  A valid row whose features are
+ * not finite sets GMF_STATUS_NONFINITE and gets zeros in feat_n; its logit is not meaningful (the head's ReLUs map NaN to 0,
+ * so it may be finite).  Rows >= N of feat_img affect nothing. */
 int gmf_classifier_forward(gmf_handle* h, const float* feat_img, const float* wst, const float* vecs, float* logits,
                            float* feat_n, float* feat, int B, int N, gmf_stream_t stream);
 

@@ -96,6 +96,58 @@ def test_p32_image_definition():
         assert img[mb, g, lane, e] == W[32 * mb + i, 8 * g + 4 * h + e]
 
 
+def test_t_image_definition():
+    """T image (mfma_core.hpp): per 32-row tile, float4 ((db*4 + q)*64 + lane) = V[32 tile + 8q + 4h + e][32 db + i],
+    lane = 32 h + i - the order store_block_timg writes V (gmf_front_forward) and Vc (gmf_fusion_ctx_prepare)."""
+    from gmf_amd import packing
+    V = torch.arange(70 * 64, dtype=torch.float32).reshape(70, 64)
+    img = packing.timg(V).reshape(3, 2, 4, 64, 4)         # [tile][db][q][lane][e]
+    for t, db, q, lane, e in [(0, 0, 0, 0, 0), (1, 1, 3, 37, 2), (2, 0, 2, 63, 3), (0, 1, 1, 31, 1), (2, 1, 0, 5, 1)]:
+        i, h = lane & 31, lane >> 5
+        row = 32 * t + 8 * q + 4 * h + e
+        assert img[t, db, q, lane, e] == (V[row, 32 * db + i] if row < 70 else 0)
+    assert int((img[2].reshape(-1) != 0).sum()) == 6 * 64          # the last tile holds rows 64..69; its padding rows are zero
+    X = torch.randn(2, 3, 45, 128)
+    assert torch.equal(packing.untimg(packing.timg(X), 45, 128), X)
+    assert torch.equal(packing.unrows_p32(packing.rows_p32(X), 45, 128), X)
+    W = torch.randn(64, 16)
+    assert torch.equal(packing.rows_p32(W), packing.p32(W))
+    # the context image of gmf_fusion_ctx_prepare: per tile Kc as P32 (K = 64) | Vc as T image (D = 64)
+    Kc, Vc = torch.randn(3, 2, 33, 64), torch.randn(3, 2, 33, 64)
+    img = packing.ctx_image(Kc, Vc)
+    assert img.shape == (3, 2, 2, 4096)
+    assert torch.equal(img[1, 0, 1, :2048], packing.rows_p32(Kc[1, 0, 32:]))
+    assert torch.equal(img[1, 0, 1, 2048:], packing.timg(Vc[1, 0, 32:]))
+    k2, v2 = packing.split_ctx_image(img, 33)
+    assert torch.equal(k2, Kc) and torch.equal(v2, Vc)
+
+
+def test_floor_rule_rejects_planted_errors():
+    """The stage tests' accuracy rule (tests/stage_reference.py): err <= 2 err_fp32 + 2 eps32 max|ref|.  It accepts the fp32
+    restatement itself and an error just inside the bound, and rejects one element just beyond it, rows shifted by one and NaN."""
+    from stage_reference import floor_bound, floor_violation
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(2, 70, 128, generator=g, dtype=torch.float64)
+    W = torch.randn(128, 128, generator=g, dtype=torch.float64) / 11.3
+    ref64 = torch.tanh(x @ W)
+    ref32 = torch.tanh(x.float() @ W.float())
+    e32, bound = floor_bound(ref64, ref32)
+    assert 0 < e32 < bound
+    assert floor_violation(ref32, ref64, ref32) is None
+    inside = ref64.clone()
+    inside[1, 69, 127] += 0.99 * bound
+    assert floor_violation(inside, ref64, ref32) is None
+    beyond = ref64.clone()
+    beyond[1, 69, 127] += 1.01 * bound
+    assert floor_violation(beyond, ref64, ref32) is not None
+    beyond[1, 69, 127] = ref64[1, 69, 127] - 1.01 * bound
+    assert floor_violation(beyond, ref64, ref32) is not None
+    assert floor_violation(torch.roll(ref32, 1, dims=1), ref64, ref32) is not None
+    nan = ref32.clone()
+    nan[0, 3, 5] = float("nan")
+    assert floor_violation(nan, ref64, ref32) is not None
+
+
 def test_bn_folding_and_blob_sizes():
     """Folded conv+BN equals conv followed by eval BatchNorm; blob sizes match the kernels' stage counts."""
     from gmf_amd import packing, synthetic

@@ -23,6 +23,9 @@ def _global_batch(B=5, N=37):
     return {"corr_pos": torch.randn(B, N, 6, generator=g), "src_keypts": torch.randn(B, N, 3, generator=g), "testing": True}
 
 
+# Results travel back as numpy arrays: a torch tensor on a multiprocessing queue is sent as a shared-memory file descriptor that
+# the receiver fetches from the SENDING process, which may already have exited by then (ConnectionRefusedError /
+# FileNotFoundError in the parent's q.get).  numpy arrays are pickled by value.
 def _worker(rank, world, port, q, B):
     sys.path.insert(0, ROOT)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -50,7 +53,7 @@ def _worker(rank, world, port, q, B):
     drv.barrier()
     t = drv.max_over_ranks(float(rank + 1))
     per_rank = drv.gather_floats(float(10 + rank))
-    q.put((rank, out["all_logits"].clone(), out["all_trans"].clone(), t, n_collectives, bad, per_rank, ms))
+    q.put((rank, out["all_logits"].numpy().copy(), out["all_trans"].numpy().copy(), t, n_collectives, bad, per_rank, ms))
     drv.close()
 
 
@@ -95,7 +98,7 @@ def _failing_worker(rank, world, port, q):
         msg = str(e)
     # the group is still usable afterwards (nobody is stuck inside a collective)
     out = ShardedBatchDriver(_fake_model, world, rank, torch.device("cpu")).run(_global_batch(B=4))
-    q.put((rank, msg, out["all_logits"].clone()))
+    q.put((rank, msg, out["all_logits"].numpy().copy()))
     drv.close()
 
 
@@ -115,7 +118,7 @@ def test_failure_on_one_rank_raises_on_every_rank():
     for rank, msg, logits in got:
         assert msg is not None and "rank(s) [1]" in msg, msg
         assert ("boom" in msg) == (rank == 1)
-        assert torch.equal(logits, ref["logits"])
+        assert torch.equal(torch.from_numpy(logits), ref["logits"])
 
 
 @pytest.mark.parametrize("B", [6, 5, 1])
@@ -137,8 +140,8 @@ def test_two_rank_gloo_matches_single_process(B):
         assert p.exitcode == 0
     ref = _fake_model(_global_batch(B=B))
     for rank, all_logits, all_trans, t, n_coll, bad, per_rank, ms in got:
-        assert torch.equal(all_logits, ref["logits"])
-        assert torch.equal(all_trans, ref["final_trans"])
+        assert torch.equal(torch.from_numpy(all_logits), ref["logits"])
+        assert torch.equal(torch.from_numpy(all_trans), ref["final_trans"])
         assert t == 2.0          # MAX over ranks of (rank + 1)
         assert n_coll == 1       # one all_gather_into_tensor per step (logits and poses packed together)
         assert per_rank == [10.0, 11.0]
@@ -167,7 +170,8 @@ def _plan_worker(rank, world, port, q, B, N):
     local = int(out["logits"].shape[0])
     t = drv.max_over_ranks(float(rank + 1))
     q.put((rank, local, len(calls), t, float(out["all_logits"].double().sum()), float(out["all_trans"].double().sum()),
-           (out["all_logits"].clone(), out["all_trans"].clone()) if rank == 0 else None, drv.group_size(), drv.backend_name()))
+           (out["all_logits"].numpy().copy(), out["all_trans"].numpy().copy()) if rank == 0 else None, drv.group_size(),
+           drv.backend_name()))
     drv.barrier()
     drv.close()
 
@@ -199,7 +203,8 @@ def test_eight_rank_gloo_config4_plan(B):
         assert cl == s_l and ct == s_t
         assert gsize == world and backend == "gloo"
         if tensors is not None:
-            assert torch.equal(tensors[0], ref["logits"]) and torch.equal(tensors[1], ref["final_trans"])
+            assert torch.equal(torch.from_numpy(tensors[0]), ref["logits"])
+            assert torch.equal(torch.from_numpy(tensors[1]), ref["final_trans"])
 
 
 def test_shard_sizes_match_ranges():
