@@ -101,6 +101,42 @@ GMF_DEVINL void mma_slice(f32x16& acc, const float4* lw, const float (&x)[KF], i
 
 GMF_DEVINL float gelu_erf_w(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
+// sum of a lane's KF values (KF a power of two) as a balanced tree: log2 KF roundings deep instead of KF - 1
+template <int KF>
+GMF_DEVINL float tree_sum(const float (&x)[KF]) {
+  float t[KF / 2];
+#pragma unroll
+  for (int k = 0; k < KF / 2; ++k) t[k] = x[k] + x[k + KF / 2];
+#pragma unroll
+  for (int w = KF / 4; w >= 1; w /= 2)
+#pragma unroll
+    for (int k = 0; k < w; ++k) t[k] += t[k + w];
+  return t[0];
+}
+
+// layernorm_frag (two-pass, eps 1e-5) with the mean and the variance summed as trees.  A sequential sum of a lane's 128 features
+// loses about 128 eps32 |mean| in the mean: with the queries 300 + N(0, 1) that error reached 2.5 x the float32 reference's
+// (tests/test_gpu_fusion_wide.py, the "offset" cases), and 2.6 x on ordinary inputs.
+template <int KF>
+GMF_DEVINL void layernorm_w(float (&y)[KF], const float (&x)[KF], const float* __restrict__ gamma, const float* __restrict__ beta,
+                            int h) {
+  const float mu = xhalf_sum(tree_sum<KF>(x)) * (1.0f / (2 * KF));
+  float d2[KF];
+#pragma unroll
+  for (int k = 0; k < KF; ++k) { const float d = x[k] - mu; d2[k] = d * d; }
+  const float rstd = rsqrtf(xhalf_sum(tree_sum<KF>(d2)) * (1.0f / (2 * KF)) + 1e-5f);
+  const float4* pg = reinterpret_cast<const float4*>(gamma) + h;
+  const float4* pb = reinterpret_cast<const float4*>(beta) + h;
+#pragma unroll
+  for (int g = 0; g < KF / 4; ++g) {
+    const float4 ga = pg[2 * g], be = pb[2 * g];
+    y[4 * g + 0] = fmaf((x[4 * g + 0] - mu) * rstd, ga.x, be.x);
+    y[4 * g + 1] = fmaf((x[4 * g + 1] - mu) * rstd, ga.y, be.y);
+    y[4 * g + 2] = fmaf((x[4 * g + 2] - mu) * rstd, ga.z, be.z);
+    y[4 * g + 3] = fmaf((x[4 * g + 3] - mu) * rstd, ga.w, be.w);
+  }
+}
+
 }  // namespace wide
 
 using namespace wide;
@@ -129,7 +165,7 @@ k_ctx_prep_w(const float* __restrict__ ctx, const float* __restrict__ wst, const
   float x[CXF], cn[CXF];
   if (PE) lcpe_w<CXF>(x, pair_base, tile * 32 + i, T, vecs, h);
   else load_frag_p32<CXF>(x, pair_base + (size_t)tile * (32 * CX), lane);
-  layernorm_frag<CXF>(cn, x, vecs + 4 * CX, vecs + 5 * CX, h);
+  layernorm_w<CXF>(cn, x, vecs + 4 * CX, vecs + 5 * CX, h);
 #pragma unroll
   for (int mb = 0; mb < 4; ++mb) {
     const float4* lw = ss.acquire();
@@ -180,7 +216,7 @@ k_fusion_attn_w(const float* __restrict__ xin, const float* __restrict__ ctx_img
   float qf[DHWF];
   {
     float xn[LATF];
-    layernorm_frag<LATF>(xn, xp, vecs + 4 * LAT, vecs + 5 * LAT, h);
+    layernorm_w<LATF>(xn, xp, vecs + 4 * LAT, vecs + 5 * LAT, h);
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) {
       f32x16 acc = zero16();
@@ -281,7 +317,7 @@ k_fusion_ff_w(const float* __restrict__ x1, const float* __restrict__ wst, const
   {
     float x[LATF];
     load_frag_p32<LATF>(x, x1 + toff, lane);
-    layernorm_frag<LATF>(xn, x, vecs, vecs + LAT, h);
+    layernorm_w<LATF>(xn, x, vecs, vecs + LAT, h);
   }
   f32x16 y[8];
 #pragma unroll
@@ -309,11 +345,19 @@ k_fusion_ff_w(const float* __restrict__ x1, const float* __restrict__ wst, const
 #pragma unroll
       for (int r = 0; r < 16; ++r) ga[r] *= gelu_erf_w(acc[r] + b[r]);
     }
+    // the chunk's 32 hidden features are summed on their own and then added to y: two levels of 32 terms instead of one chain
+    // of 1024 (a chain with one large early term rounded every later term at that term's size: about 3 x the fp32 reference's error
+    // with one W2 entry of 300, tests/test_gpu_fusion_wide.py)
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       const float4* lw = ss.acquire();
 #pragma unroll
-      for (int m4 = 0; m4 < 4; ++m4) mma_wx<16>(y[4 * half + m4], lw + m4 * (32 * 32 / 4), ga);
+      for (int m4 = 0; m4 < 4; ++m4) {
+        f32x16 part = zero16();
+        mma_wx<16>(part, lw + m4 * (32 * 32 / 4), ga);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) y[4 * half + m4][r] += part[r];
+      }
     }
   }
 #pragma unroll
@@ -364,7 +408,7 @@ k_fusion_ff_w_h2(const float* __restrict__ x1, const float* __restrict__ wst, co
     load_frag_p32<LATF>(x, x1 + toff, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    layernorm_frag<LATF>(xn, x, lvec, lvec + LAT, h);
+    layernorm_w<LATF>(xn, x, lvec, lvec + LAT, h);
     nx.set(xn);
   }
   f32x16 y[8];
@@ -533,7 +577,7 @@ k_ctx_prep_w_h2(const float* __restrict__ ctx, const float* __restrict__ wst, co
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (PE) LcpeHalo<CXF>::apply(x, halo, lvec, tile * 32 + i, T, lane);
-    layernorm_frag<CXF>(cn, x, lvec + 4 * CX, lvec + 5 * CX, h);
+    layernorm_w<CXF>(cn, x, lvec + 4 * CX, lvec + 5 * CX, h);
     cx.set(cn);
   }
 #pragma unroll
@@ -593,7 +637,7 @@ k_fusion_attn_w_h2(const float* __restrict__ xin, const float* __restrict__ ctx_
     FragH2<16> nx;
     {
       float xn[LATF];
-      layernorm_frag<LATF>(xn, xp, lvec + 4 * LAT, lvec + 5 * LAT, h);
+      layernorm_w<LATF>(xn, xp, lvec + 4 * LAT, lvec + 5 * LAT, h);
       nx.set(xn);
     }
 #pragma unroll
