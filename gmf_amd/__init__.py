@@ -18,7 +18,9 @@ from .solvers import (ransac_correspondence_batched, icp_point_to_point_batched,
 from .features import (radius_knn_batched, estimate_normals_batched, compute_fpfh_batched,  # noqa: F401
                        voxel_down_sample_batched, voxel_select_batched, voxel_down_sample, voxel_select, estimate_normals,
                        compute_fpfh_feature, fpfh_descriptors)
-from .sparse import SparsePlan, sparse_conv, ResUNetBN2C, ResUNetBN2CX, inlier_coordinates   # noqa: F401
+from .sparse import (SparsePlan, sparse_conv, sparse_conv_narrow, sparse_head_l2, ResUNetBN2C, ResUNetBN2CX,  # noqa: F401
+                     inlier_coordinates)
+from . import fcgf, dgr                          # noqa: F401  (gmf_amd.fcgf.ResUNetBN2C: FCGF; gmf_amd.ResUNetBN2C: the inlier net)
 from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss, similarity_matrix   # noqa: F401
 
 __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointDSC", "ImageEncoder",
@@ -28,4 +30,5 @@ __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointD
            "icp_point_to_point_batched", "RegistrationResult", "registration_ransac_based_on_correspondence", "registration_icp",
            "icp_refine", "radius_knn_batched", "estimate_normals_batched", "compute_fpfh_batched", "voxel_down_sample_batched",
            "voxel_select_batched", "voxel_down_sample", "voxel_select", "estimate_normals", "compute_fpfh_feature",
-           "fpfh_descriptors", "SparsePlan", "sparse_conv", "ResUNetBN2C", "ResUNetBN2CX", "inlier_coordinates"]
+           "fpfh_descriptors", "SparsePlan", "sparse_conv", "sparse_conv_narrow", "sparse_head_l2", "ResUNetBN2C", "ResUNetBN2CX",
+           "inlier_coordinates", "fcgf", "dgr"]

@@ -199,6 +199,10 @@ SIGNATURES = {
     "gmf_sparse_build_plan": (C.c_int, [_vp, _vp, _ll, C.c_int, C.c_int, C.c_int, _i32p, _vp, _ll, C.POINTER(_ll), _vp]),
     "gmf_sparse_conv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _ll, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp,
                                   _vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "gmf_sparse_conv_narrow": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _ll, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, C.c_int,
+                                         _vp, _vp]),
+    "gmf_sparse_head_l2": (C.c_int, [_vp, _vp, _ll, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp,
+                                     _vp]),
     "gmf_sparse_pack_resunet": (C.c_int, [_vp, C.POINTER(Tensor), C.c_int, _vp, _ll, C.POINTER(_ll), C.POINTER(_ll)]),
 }
 

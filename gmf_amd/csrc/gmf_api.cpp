@@ -1542,6 +1542,36 @@ int gmf_sparse_conv(gmf_handle* h, const int* row_ptr, const int* pairs, const i
   return GMF_OK;
 }
 
+int gmf_sparse_conv_narrow(gmf_handle* h, const int* row_ptr, const int* pairs, int K, const int* n_out, long long cap_out,
+                           const float* x, int cin, const float* W, int cout, const float* scale, const float* shift,
+                           const float* residual, int relu, float* y, gmf_stream_t stream) {
+  GMF_REQUIRE(h && row_ptr && pairs && n_out && x && W && y, GMF_ERR_BAD_ARG, "sparse_conv_narrow: null pointer");
+  GMF_REQUIRE(K >= 1 && K <= gmf::kSparseMaxK, GMF_ERR_UNSUPPORTED_SHAPE, "sparse_conv_narrow: K must be in 1..1024");
+  GMF_REQUIRE(cap_out >= 1 && cap_out < (1LL << 28), GMF_ERR_UNSUPPORTED_SHAPE,
+              "sparse_conv_narrow: cap_out must be in 1 .. 2^28 - 1");
+  GMF_REQUIRE(cin >= 1 && cin <= gmf::kSparseNarrowMaxCin && cout >= 1 && cout <= gmf::kSparseNarrowMaxCout,
+              GMF_ERR_UNSUPPORTED_SHAPE, "sparse_conv_narrow: Cin must be in 1..8 and Cout in 1..64");
+  SetDevice sd(h, stream);
+  gmf::SparseNarrowArgs a{row_ptr, reinterpret_cast<const int2*>(pairs), K, n_out, cap_out, x, cin, W, cout, scale, shift,
+                          residual, relu, y};
+  GMF_HIP(gmf::launch_sparse_conv_narrow(a, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_sparse_head_l2(gmf_handle* h, const int* n_out, long long cap_out, const float* xa, int ca, const float* xb, int cb,
+                       const float* W1, int hid, const float* W2, int cout, const float* bias, int normalize, float* y,
+                       gmf_stream_t stream) {
+  GMF_REQUIRE(h && n_out && xa && W1 && W2 && y && (cb == 0 || xb), GMF_ERR_BAD_ARG, "sparse_head_l2: null pointer");
+  GMF_REQUIRE(cap_out >= 1 && cap_out < (1LL << 28), GMF_ERR_UNSUPPORTED_SHAPE, "sparse_head_l2: cap_out must be in 1 .. 2^28 - 1");
+  constexpr int C = gmf::kSparseHeadMaxC;
+  GMF_REQUIRE(ca >= 1 && ca <= C && cb >= 0 && cb <= C && hid >= 1 && hid <= C && cout >= 1 && cout <= C,
+              GMF_ERR_UNSUPPORTED_SHAPE, "sparse_head_l2: ca, hid and cout must be in 1..64, cb in 0..64");
+  SetDevice sd(h, stream);
+  gmf::SparseHeadArgs a{n_out, cap_out, xa, ca, cb ? xb : nullptr, cb, W1, hid, W2, cout, bias, normalize ? 1 : 0, y};
+  GMF_HIP(gmf::launch_sparse_head_l2(a, S(stream)));
+  return GMF_OK;
+}
+
 int gmf_sparse_pack_resunet(gmf_handle* h, const gmf_tensor* tensors, int n_tensors, float* dev, long long dev_floats,
                             long long* layout, long long* need_floats) {
   GMF_REQUIRE(h && tensors && layout && need_floats, GMF_ERR_BAD_ARG, "sparse_pack_resunet: null pointer");

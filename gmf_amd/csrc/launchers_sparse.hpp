@@ -1,5 +1,6 @@
 // Internal C++ launch entry points of the sparse coordinate engine and the sparse convolution (sparse_kernels.hip).
-// Public C ABI: include/gmf_hip.h (gmf_sparse_plan_bytes, gmf_sparse_build_plan, gmf_sparse_conv, gmf_sparse_pack_resunet).
+// Public C ABI: include/gmf_hip.h (gmf_sparse_plan_bytes, gmf_sparse_build_plan, gmf_sparse_conv, gmf_sparse_conv_narrow,
+// gmf_sparse_head_l2, gmf_sparse_pack_resunet).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -58,5 +59,33 @@ struct SparseConvArgs {
 // output-row groups of one convolution (a function of its shape and cap_out; it does not change any result)
 int sparse_conv_row_groups(int K, int cin, int cout, int nsplit, long long cap_out);
 hipError_t launch_sparse_conv(const SparseConvArgs& a, hipStream_t s);
+
+// Narrow-input convolution (FCGF's conv1: Cin = 1, k = 7): y[o] = epilogue(one fma chain over the CSR pairs (d, i) of row o,
+// d ascending, input channels in order within a pair, of x[i][k] W[d][k][c]).  Each output row is computed whole by one group
+// of lanes; W sits in LDS when it fits (kSparseNarrowLdsBytes), else it is read from global memory.
+constexpr int kSparseNarrowMaxCin = 8;
+constexpr int kSparseNarrowMaxCout = 64;
+constexpr long long kSparseNarrowLdsBytes = 64 << 10;
+struct SparseNarrowArgs {
+  const int* row_ptr; const int2* pairs; int K;
+  const int* n_out; long long cap_out;
+  const float* x; int cin;
+  const float* W; int cout;
+  const float* scale; const float* shift; const float* residual; int relu;
+  float* y;
+};
+hipError_t launch_sparse_conv_narrow(const SparseNarrowArgs& a, hipStream_t s);
+
+// Fused FCGF head: per row h = relu([xa | xb] W1) (W1 [ca + cb, hid]), y = h W2 + bias (W2 [hid, cout]), then, if normalize,
+// y / (||y||_2 + 1e-8).  One wave per row; both weight blocks in LDS.
+constexpr int kSparseHeadMaxC = 64;     // ca, cb, hid and cout each
+struct SparseHeadArgs {
+  const int* n_out; long long cap_out;
+  const float* xa; int ca; const float* xb; int cb;
+  const float* W1; int hid; const float* W2; int cout; const float* bias;
+  int normalize;
+  float* y;
+};
+hipError_t launch_sparse_head_l2(const SparseHeadArgs& a, hipStream_t s);
 
 }  // namespace gmf

@@ -20,6 +20,10 @@
 //   output element has one fixed order: per offset, 16-channel FMA chains added in channel order; offsets ascending within a
 //   slice; slices ascending.  No float atomics: results are bitwise repeatable and independent of the input row order and of the
 //   row grouping.
+// Narrow-input convolution (k_sparse_conv_narrow, FCGF's conv1: Cin <= 8, Cout <= 64): one group of lanes per output row reads
+//   the row's CSR pairs directly, one fma chain per element over the pairs in ascending offset; W in LDS when it fits.
+// FCGF head (k_sparse_head_l2): conv1_tr (1x1) on [x_a | x_b], ReLU, final (1x1) + bias and the optional L2 normalisation of
+//   each row, one wave per row, both weight blocks in LDS.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <limits.h>
@@ -347,6 +351,108 @@ __global__ __launch_bounds__(kThreads) void k_split_reduce(const SparseConvArgs 
   a.y[(size_t)o * a.cout + oc] = epilogue(v, o, oc, a);
 }
 
+GMF_DEVINL float narrow_epilogue(float v, int o, int oc, const SparseNarrowArgs& a) {
+  if (a.scale || a.shift) v = fmaf(v, a.scale ? a.scale[oc] : 1.f, a.shift ? a.shift[oc] : 0.f);
+  if (a.residual) v += a.residual[(size_t)o * a.cout + oc];
+  if (a.relu) v = fmaxf(v, 0.f);
+  return v;
+}
+
+// Narrow-input convolution.  A group of L lanes (16, 32 or 64: the fewest that cover cout) owns one output row, lane c its
+// output channel c; a wave holds 64 / L rows.  The group loads L pairs of its row at once, one per lane (the pair, then the
+// input row's cin channels), so a row of ~100 pairs costs two dependent loads per L pairs, and then walks them in ascending
+// order, taking each pair's offset and channels from the lane that loaded it (__shfl within the group).  Every element is one
+// fma chain over the row's pairs, channels in order inside a pair.  A row belongs to one group whatever the grid, so results
+// do not depend on how rows are grouped into workgroups.  kLdsW: W [K][cin][cout] is staged in LDS first.
+template <bool kLdsW>
+__global__ __launch_bounds__(kThreads) void k_sparse_conv_narrow(const SparseNarrowArgs a) {
+  extern __shared__ __align__(16) float narrow_ws[];
+  const float* W = a.W;
+  if (kLdsW) {
+    const int wlen = a.K * a.cin * a.cout;
+    for (int e = threadIdx.x; e < wlen; e += kThreads) narrow_ws[e] = a.W[e];
+    __syncthreads();
+    W = narrow_ws;
+  }
+  const int L = a.cout <= 16 ? 16 : (a.cout <= 32 ? 32 : 64);
+  const int G = 64 / L;
+  const int lane = threadIdx.x & 63, c = lane % L, gbase = lane - c;
+  const int cc = c < a.cout ? c : a.cout - 1;        // lanes past cout compute a copy of the last channel and store nothing
+  const long long n = *a.n_out < a.cap_out ? *a.n_out : a.cap_out;
+  const int waves = gridDim.x * (kThreads / 64);
+  for (long long w = (long long)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); w * G < n; w += waves) {
+    const long long o = w * G + lane / L;
+    int pb = 0, pe = 0;
+    if (o < n) {
+      pb = a.row_ptr[o];
+      pe = a.row_ptr[o + 1];
+    }
+    float acc = 0.f;
+    for (int p0 = pb; p0 < pe; p0 += L) {             // uniform within the group: every source lane below is active
+      const int p = p0 + c;
+      int d = 0;
+      float xv[kSparseNarrowMaxCin];
+#pragma unroll
+      for (int k = 0; k < kSparseNarrowMaxCin; ++k) xv[k] = 0.f;
+      if (p < pe) {
+        const int2 pr = a.pairs[p];
+        d = pr.x;
+        const float* xr = a.x + (size_t)pr.y * a.cin;
+#pragma unroll
+        for (int k = 0; k < kSparseNarrowMaxCin; ++k)
+          if (k < a.cin) xv[k] = xr[k];
+      }
+      const int jn = pe - p0 < L ? pe - p0 : L;
+      for (int j = 0; j < jn; ++j) {
+        const int dj = __shfl(d, gbase + j);
+        const float* wd = W + (size_t)dj * a.cin * a.cout + cc;
+#pragma unroll
+        for (int k = 0; k < kSparseNarrowMaxCin; ++k)
+          if (k < a.cin) acc = fmaf(__shfl(xv[k], gbase + j), wd[k * a.cout], acc);
+      }
+    }
+    if (o < n && c < a.cout) a.y[o * a.cout + c] = narrow_epilogue(acc, (int)o, c, a);
+  }
+}
+
+// Fused FCGF head, one wave per row.  Lane l holds input channel l of x_a and of x_b; lane c computes hidden channel c as an fma
+// chain over the inputs in order (x_a, then x_b), then ReLU; lane j computes output j as an fma chain over the hidden channels in
+// order, plus the bias.  The norm is one fma chain over the outputs in order, the same on every lane.  W1 [ca + cb][hid] and W2
+// [hid][cout] sit in LDS.
+__global__ __launch_bounds__(kThreads) void k_sparse_head_l2(const SparseHeadArgs a) {
+  extern __shared__ __align__(16) float head_ws[];
+  const int cin = a.ca + a.cb;
+  float* W1s = head_ws;
+  float* W2s = head_ws + cin * a.hid;
+  for (int e = threadIdx.x; e < cin * a.hid; e += kThreads) W1s[e] = a.W1[e];
+  for (int e = threadIdx.x; e < a.hid * a.cout; e += kThreads) W2s[e] = a.W2[e];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int ch = lane < a.hid ? lane : a.hid - 1, cy = lane < a.cout ? lane : a.cout - 1;
+  const float b = a.bias ? a.bias[cy] : 0.f;
+  const long long n = *a.n_out < a.cap_out ? *a.n_out : a.cap_out;
+  for (long long o = (long long)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); o < n; o += gridDim.x * (kThreads / 64)) {
+    const float xa = lane < a.ca ? a.xa[o * a.ca + lane] : 0.f;
+    const float xb = lane < a.cb ? a.xb[o * a.cb + lane] : 0.f;
+    float h = 0.f;
+    for (int k = 0; k < a.ca; ++k) h = fmaf(__shfl(xa, k), W1s[k * a.hid + ch], h);
+    for (int k = 0; k < a.cb; ++k) h = fmaf(__shfl(xb, k), W1s[(a.ca + k) * a.hid + ch], h);
+    h = fmaxf(h, 0.f);
+    float y = 0.f;
+    for (int k = 0; k < a.hid; ++k) y = fmaf(__shfl(h, k), W2s[k * a.cout + cy], y);
+    y += b;
+    if (a.normalize) {                                // resunet.py: F / (||F||_2 + 1e-8)
+      float s = 0.f;
+      for (int j = 0; j < a.cout; ++j) {
+        const float v = __shfl(y, j);
+        s = fmaf(v, v, s);
+      }
+      y = y / (sqrtf(s) + 1e-8f);
+    }
+    if (lane < a.cout) a.y[o * a.cout + lane] = y;
+  }
+}
+
 // offset-major lists: the key of CSR pair j is its offset (K past the last pair, so those sort last), the value j
 __global__ __launch_bounds__(kThreads) void k_pair_keys(const int* __restrict__ row_ptr, const int* __restrict__ n_out,
                                                         const int2* __restrict__ pairs, long long total, int K,
@@ -503,6 +609,30 @@ hipError_t launch_sparse_conv(const SparseConvArgs& a, hipStream_t s) {
   dim3 grid(a.nsplit, blocks(a.cout, kTN), sparse_conv_row_groups(a.K, a.ca + a.cb, a.cout, a.nsplit, a.cap_out));
   k_sparse_conv<<<grid, kThreads, 0, s>>>(a);
   if (a.row_ptr) k_split_reduce<<<blocks(a.cap_out * a.cout, kThreads), kThreads, 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_sparse_conv_narrow(const SparseNarrowArgs& a, hipStream_t s) {
+  // Workgroups walk the rows in strides; with W in LDS each one stages it once, so the grid stays near 3 per CU (3 x 43 KiB for
+  // FCGF's conv1 fit the 160 KiB of a CU).  The grid never changes a result.
+  const size_t wbytes = (size_t)a.K * a.cin * a.cout * sizeof(float);
+  const int rows_per_wg = (kThreads / 64) * (64 / (a.cout <= 16 ? 16 : (a.cout <= 32 ? 32 : 64)));
+  long long g = (a.cap_out + rows_per_wg - 1) / rows_per_wg;
+  if ((long long)wbytes <= kSparseNarrowLdsBytes) {
+    if (g > 768) g = 768;
+    k_sparse_conv_narrow<true><<<(int)g, kThreads, wbytes, s>>>(a);
+  } else {
+    if (g > 4096) g = 4096;
+    k_sparse_conv_narrow<false><<<(int)g, kThreads, 0, s>>>(a);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_sparse_head_l2(const SparseHeadArgs& a, hipStream_t s) {
+  const size_t lds = (size_t)((a.ca + a.cb) * a.hid + a.hid * a.cout) * sizeof(float);
+  long long g = (a.cap_out + kThreads / 64 - 1) / (kThreads / 64);
+  if (g > 1024) g = 1024;
+  k_sparse_head_l2<<<(int)g, kThreads, lds, s>>>(a);
   return hipGetLastError();
 }
 

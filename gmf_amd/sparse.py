@@ -229,6 +229,99 @@ def sparse_conv(plan: SparsePlan, map_index, out_level: int, xa, W, xb=None, sca
     return out
 
 
+def _check_out(out, M, cout, inputs, what, device):
+    if out is None:
+        return torch.empty((M, cout), dtype=torch.float32, device=device)
+    if out.shape != (M, cout) or out.dtype != torch.float32 or not out.is_contiguous():
+        _fail(what, f"`out` must be a contiguous float32 [{M}, {cout}] tensor")
+    for name, t in inputs:
+        if t is not None and _overlap(out, t):
+            _fail(what, f"`out` overlaps `{name}`: the convolution cannot run in place")
+    return out
+
+
+def sparse_conv_narrow(plan: SparsePlan, map_index: int, out_level: int, x, W, scale=None, shift=None, residual=None,
+                       relu: bool = False, out=None):
+    """`sparse_conv` for a narrow input (Cin <= 8, Cout <= 64; FCGF's conv1), on `gmf_sparse_conv_narrow`: one fma chain per
+    output element over its row's pairs in ascending offset, channels in order inside a pair.  x [M, Cin], W [K, Cin, Cout]
+    (or [Cin, Cout] for a k = 1 map); map_index must name a map of the plan (the identity map has no CSR).  Same epilogue, row
+    count rule and `out` rule as `sparse_conv`."""
+    what = "sparse_conv_narrow"
+    x = _f32_dev(x, "x", what)
+    W = _f32_dev(W, "W", what)
+    M = plan.M
+    if x.dim() != 2 or x.shape[0] != M:
+        _fail(what, f"`x` must be [M = {M}, cin] (got {tuple(x.shape)})")
+    if map_index is None or not (0 <= int(map_index) < len(plan.maps)):
+        _fail(what, "`map_index` must name a kernel map of the plan")
+    K = plan.K[map_index]
+    if plan.maps[map_index][1] != out_level:
+        _fail(what, f"map {map_index} writes level {plan.maps[map_index][1]}, not {out_level}")
+    if W.dim() == 2 and K == 1:
+        W = W.unsqueeze(0)
+    cin = x.shape[1]
+    if W.dim() != 3 or W.shape[0] != K or W.shape[1] != cin:
+        _fail(what, f"`W` must be [K = {K}, Cin = {cin}, Cout] (got {tuple(W.shape)})")
+    cout = W.shape[2]
+    if not (1 <= cin <= 8 and 1 <= cout <= 64):
+        _fail(what, f"Cin must be in 1..8 and Cout in 1..64 (got {cin}, {cout})", NotImplementedError)
+    vecs = []
+    for name, v, shape in (("scale", scale, (cout,)), ("shift", shift, (cout,)), ("residual", residual, (M, cout))):
+        if v is not None:
+            v = _f32_dev(v, name, what)
+            if tuple(v.shape) != shape and not (name != "residual" and v.numel() == cout):
+                _fail(what, f"`{name}` must be {list(shape)} (got {tuple(v.shape)})")
+        vecs.append(v)
+    out = _check_out(out, M, cout, (("x", x), ("W", W), ("scale", vecs[0]), ("shift", vecs[1]), ("residual", vecs[2])), what,
+                     x.device)
+    rp, pairs = plan.kernel_map(map_index)
+    h, st = handle_and_stream(x)
+    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    h.call("gmf_sparse_conv_narrow", rp.data_ptr(), pairs.data_ptr(), K, plan.count_ptr(out_level), M, x.data_ptr(), cin,
+           W.data_ptr(), cout, p(vecs[0]), p(vecs[1]), p(vecs[2]), 1 if relu else 0, out.data_ptr(), st)
+    return out
+
+
+def sparse_head_l2(plan: SparsePlan, level: int, xa, W1, W2, xb=None, bias=None, normalize: bool = False, out=None):
+    """FCGF's head (resunet.py:641-648) on `gmf_sparse_head_l2`, one launch: y = relu([xa | xb] W1) W2 + bias, then, if
+    `normalize`, y / (||y||_2 + 1e-8) per row.  xa [M, ca], xb [M, cb], W1 [ca + cb, hid] (or [1, ca + cb, hid]), W2 [hid, cout]
+    (or [1, hid, cout]), bias [cout] or [1, cout]; every width at most 64.  Only the first counts[level] rows are written."""
+    what = "sparse_head_l2"
+    xa = _f32_dev(xa, "xa", what)
+    M = plan.M
+    if xa.dim() != 2 or xa.shape[0] != M:
+        _fail(what, f"`xa` must be [M = {M}, ca] (got {tuple(xa.shape)})")
+    ca, cb = xa.shape[1], 0
+    if xb is not None:
+        xb = _f32_dev(xb, "xb", what)
+        if xb.dim() != 2 or xb.shape[0] != M:
+            _fail(what, f"`xb` must be [M = {M}, cb] (got {tuple(xb.shape)})")
+        cb = xb.shape[1]
+    W1 = _f32_dev(W1, "W1", what)
+    W2 = _f32_dev(W2, "W2", what)
+    W1 = W1[0] if W1.dim() == 3 and W1.shape[0] == 1 else W1
+    W2 = W2[0] if W2.dim() == 3 and W2.shape[0] == 1 else W2
+    if W1.dim() != 2 or W1.shape[0] != ca + cb:
+        _fail(what, f"`W1` must be [ca + cb = {ca + cb}, hid] (got {tuple(W1.shape)})")
+    hid = W1.shape[1]
+    if W2.dim() != 2 or W2.shape[0] != hid:
+        _fail(what, f"`W2` must be [hid = {hid}, cout] (got {tuple(W2.shape)})")
+    cout = W2.shape[1]
+    if max(ca, cb, hid, cout) > 64:
+        _fail(what, f"every width must be at most 64 (ca {ca}, cb {cb}, hid {hid}, cout {cout})", NotImplementedError)
+    if bias is not None:
+        bias = _f32_dev(bias, "bias", what)
+        if bias.numel() != cout:
+            _fail(what, f"`bias` must hold {cout} values (got {tuple(bias.shape)})")
+    W1, W2 = W1.contiguous(), W2.contiguous()
+    out = _check_out(out, M, cout, (("xa", xa), ("xb", xb), ("W1", W1), ("W2", W2), ("bias", bias)), what, xa.device)
+    h, st = handle_and_stream(xa)
+    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    h.call("gmf_sparse_head_l2", plan.count_ptr(level), M, xa.data_ptr(), ca, p(xb), cb, W1.data_ptr(), hid, W2.data_ptr(), cout,
+           p(bias), 1 if normalize else 0, out.data_ptr(), st)
+    return out
+
+
 def _overlap(a, b) -> bool:
     """Whether two contiguous tensors share any byte."""
     a0, b0 = a.data_ptr(), b.data_ptr()
@@ -245,6 +338,27 @@ def layer_nsplit(K: int, cin: int, cout: int) -> int:
     if K * cin * cout * 4 > (16 << 20):
         return min(K, -(-256 // -(-cout // 64)))
     return min(K, 9)
+
+
+def pack_resunet(sd, device):
+    """The 23 convolutions of a ResUNetBN2C state_dict (the inlier network's or FCGF's: the same names) packed on `device` with
+    their BatchNorms folded (`gmf_sparse_pack_resunet`): (blob, [(W [K, Cin, Cout], scale or None, shift or None)] in forward
+    order, views into blob)."""
+    arr, keep = _lib.tensor_list(sd)
+    h, _ = handle_and_stream(torch.empty(0, device=device))
+    layout = (ctypes.c_longlong * (6 * 23))()
+    need = ctypes.c_longlong(0)
+    h.check(h.lib.gmf_sparse_pack_resunet(h.h, arr, len(arr), None, 0, layout, ctypes.byref(need)), "gmf_sparse_pack_resunet")
+    blob = torch.empty(need.value, dtype=torch.float32, device=device)
+    h.check(h.lib.gmf_sparse_pack_resunet(h.h, arr, len(arr), ctypes.c_void_p(blob.data_ptr()), need.value, layout,
+                                          ctypes.byref(need)), "gmf_sparse_pack_resunet")
+    del keep
+    layers = []
+    for i in range(23):
+        wo, so, ho, K, cin, cout = layout[6 * i:6 * i + 6]
+        W = blob[wo:wo + K * cin * cout].view(K, cin, cout)
+        layers.append((W, None if so < 0 else blob[so:so + cout], None if ho < 0 else blob[ho:ho + cout]))
+    return blob, layers
 
 
 # ---- ResUNetBN2C ------------------------------------------------------------------------------------------------------------
@@ -371,22 +485,7 @@ class ResUNetBN2C(nn.Module):
         if self._packed is None or self._packed_version != key:
             sd = {k: v for k, v in self.state_dict().items()
                   if not k.startswith(("img_encoder.", "image_fusion.", "perceiver_io."))}
-            arr, keep = _lib.tensor_list(sd)
-            h, _ = handle_and_stream(torch.empty(0, device=device))
-            layout = (ctypes.c_longlong * (6 * 23))()
-            need = ctypes.c_longlong(0)
-            h.check(h.lib.gmf_sparse_pack_resunet(h.h, arr, len(arr), None, 0, layout, ctypes.byref(need)),
-                    "gmf_sparse_pack_resunet")
-            blob = torch.empty(need.value, dtype=torch.float32, device=device)
-            h.check(h.lib.gmf_sparse_pack_resunet(h.h, arr, len(arr), ctypes.c_void_p(blob.data_ptr()), need.value, layout,
-                                                  ctypes.byref(need)), "gmf_sparse_pack_resunet")
-            del keep
-            layers = []
-            for i in range(23):
-                wo, so, ho, K, cin, cout = layout[6 * i:6 * i + 6]
-                W = blob[wo:wo + K * cin * cout].view(K, cin, cout)
-                layers.append((W, None if so < 0 else blob[so:so + cout], None if ho < 0 else blob[ho:ho + cout]))
-            self._packed, self._packed_version = (blob, layers), key
+            self._packed, self._packed_version = pack_resunet(sd, device), key
         return self._packed[1]
 
     # -- forward --------------------------------------------------------------------------------------------------------------

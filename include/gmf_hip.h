@@ -547,7 +547,29 @@ int gmf_sparse_conv(gmf_handle* h, const int* row_ptr, const int* pairs, const i
                     const float* scale, const float* shift, const float* residual, int relu, int nsplit, float* y,
                     gmf_stream_t stream);
 
-/* Packs a ResUNetBN2C state_dict (host tensors) for gmf_sparse_conv: for each of its GMF_SPARSE_RESUNET_LAYERS convolutions in
+/* Narrow-input sparse convolution (FCGF's conv1: Cin = 1, k = 7), fp32: y[o] = epilogue(sum over the CSR pairs (d, i) of row o of
+ * x[i] W[d]), W [K, cin, cout] (K 1..1024, cin 1..8, cout 1..64), x [*, cin] row-major.  row_ptr / pairs: the CSR form of a map
+ * of gmf_sparse_build_plan (the offset-major lists are not read).  n_out, cap_out, the epilogue (scale, shift, residual, relu)
+ * and the rule that y must not overlap an input are gmf_sparse_conv's; rows >= *n_out are not written.  Each output element is
+ * ONE fma chain over its row's pairs in ascending offset, its input channels in order inside a pair; W is held in LDS when
+ * K cin cout x 4 B <= 64 KiB, else read from global memory.  No workspace, no float atomics: bitwise repeatable and independent
+ * of the input row order and of which other rows or batches share the plan.  No host synchronisation. */
+int gmf_sparse_conv_narrow(gmf_handle* h, const int* row_ptr, const int* pairs, int K, const int* n_out, long long cap_out,
+                           const float* x, int cin, const float* W, int cout, const float* scale, const float* shift,
+                           const float* residual, int relu, float* y, gmf_stream_t stream);
+
+/* FCGF's head (model/resunet.py:641-648), fp32, per row o < *n_out (device count, rows >= it are not written):
+ * h = max([xa | xb][o] W1, 0) with W1 [ca + cb, hid] (conv1_tr, 1x1, no bias, then MEF.relu), y = h W2 + bias with W2 [hid, cout]
+ * and bias [cout] (may be NULL: 0) (final), then, if normalize, y / (sqrt(sum_j y_j^2) + 1e-8).  ca, hid, cout 1..64, cb 0..64
+ * (xa [*, ca], xb [*, cb] row-major; xb may be NULL when cb = 0).  Each hidden and output element is one fma chain over its
+ * inputs in order (xa's, then xb's); the squared norm is one fma chain over the outputs in order.  y must not overlap an input.
+ * Both weight blocks are held in LDS; no workspace, no host synchronisation.  An all-zero y gives zeros. */
+int gmf_sparse_head_l2(gmf_handle* h, const int* n_out, long long cap_out, const float* xa, int ca, const float* xb, int cb,
+                       const float* W1, int hid, const float* W2, int cout, const float* bias, int normalize, float* y,
+                       gmf_stream_t stream);
+
+/* Packs a ResUNetBN2C state_dict (host tensors) for gmf_sparse_conv: DGR's inlier network (resunet_new.py) or the FCGF feature
+ * network (resunet.py), whose 23 convolutions have the same names.  For each of its GMF_SPARSE_RESUNET_LAYERS convolutions in
  * forward order (conv1, block1.conv1, block1.conv2, conv2, ..., conv2_tr, block2_tr.conv1, block2_tr.conv2, conv1_tr, final) the
  * kernel ([K, Cin, Cout], or [Cin, Cout] when K = 1), the eval BatchNorm (eps 1e-5) folded in fp64 into scale / shift, and
  * final.bias ([1, Cout]) as its shift.  layout [GMF_SPARSE_RESUNET_LAYERS][6] receives (kernel, scale, shift offsets in floats
