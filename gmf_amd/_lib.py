@@ -204,6 +204,10 @@ SIGNATURES = {
     "gmf_sparse_head_l2": (C.c_int, [_vp, _vp, _ll, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp,
                                      _vp]),
     "gmf_sparse_pack_resunet": (C.c_int, [_vp, C.POINTER(Tensor), C.c_int, _vp, _ll, C.POINTER(_ll), C.POINTER(_ll)]),
+    "gmf_sparse_conv_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, C.c_int, _vp,
+                                        _vp]),
+    "gmf_batchnorm_masked_forward": (C.c_int, [_vp] * 6 + [_ll, C.c_int, C.c_float, C.c_float, C.c_int] + [_vp] * 6),
+    "gmf_batchnorm_masked_backward": (C.c_int, [_vp] * 8 + [_ll, C.c_int] + [_vp] * 5),
 }
 
 _lib = None
@@ -235,6 +239,7 @@ GMF_ERR_WORKSPACE = -6
 GMF_STATUS_NONFINITE = 1
 GMF_STATUS_PV_GUARDED = 2      # informational: the "pv_fp8" guard sent a (pair, layer) to the three-product form
 GMF_STATUS_SPARSE_DUPLICATE = 4   # gmf_sparse_build_plan met a duplicate (batch, coordinates) input row
+GMF_STATUS_BATCHNORM_ROWS = 8     # gmf_batchnorm_masked_forward met a level with fewer than 2 valid rows
 
 
 class Handle:
@@ -304,6 +309,11 @@ class Handle:
             raise RuntimeError(
                 f"gmf_amd: {where}: a sparse tensor of an earlier call on this device had duplicate (batch, coordinates) rows - "
                 "rows must be unique (they are never merged).  The outputs of that call are not valid.")
+        if f & GMF_STATUS_BATCHNORM_ROWS:
+            self.status(clear=True)
+            raise RuntimeError(
+                f"gmf_amd: {where}: a train-mode BatchNorm of an earlier call on this device had fewer than 2 valid rows "
+                "(torch: 'Expected more than 1 value per channel when training').  The outputs of that call are not valid.")
 
     def __del__(self):
         try:

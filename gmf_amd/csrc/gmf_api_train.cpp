@@ -3,6 +3,8 @@
 // (and the source hash bench.py ties its profile to) do not move when the training path grows.
 #include "api_common.hpp"
 #include "launchers_pose.hpp"
+#include "launchers_sparse.hpp"
+#include "launchers_sparse_train.hpp"
 
 extern "C" {
 
@@ -248,6 +250,59 @@ int gmf_weighted_procrustes_backward(gmf_handle* h, const float* X, const float*
   GMF_REQUIRE(B > 0, GMF_ERR_UNSUPPORTED_SHAPE, "weighted_procrustes_backward: empty batch");
   SetDevice sd(h, stream);
   GMF_HIP(gmf::launch_wp_backward(X, Y, w, offsets, B, eps, d_R, d_t, d_w, S(stream)));
+  return GMF_OK;
+}
+
+// ---- training of the sparse network -----------------------------------------------------------------------------------
+
+int gmf_sparse_conv_wgrad(gmf_handle* h, const int* row_ptr, const int* pairs, const int* by_off, const int* off_start, int K,
+                          const int* n_out, const float* xa, int ca, const float* xb, int cb, const float* dy, int cout, float* dW,
+                          gmf_stream_t stream) {
+  GMF_REQUIRE(h && n_out && xa && dy && dW, GMF_ERR_BAD_ARG, "sparse_conv_wgrad: null pointer");
+  GMF_REQUIRE((row_ptr == nullptr) == (pairs == nullptr) && (row_ptr == nullptr) == (by_off == nullptr) &&
+                  (row_ptr == nullptr) == (off_start == nullptr),
+              GMF_ERR_BAD_ARG, "sparse_conv_wgrad: row_ptr, pairs, by_off and off_start go together");
+  GMF_REQUIRE(K >= 1 && K <= gmf::kSparseMaxK && (row_ptr || K == 1), GMF_ERR_UNSUPPORTED_SHAPE,
+              "sparse_conv_wgrad: K must be in 1..1024 (1 for the identity map)");
+  GMF_REQUIRE(ca >= 1 && cb >= 0 && (cb == 0 || xb) && cout >= 1 && ca + cb <= 4096 && cout <= 4096, GMF_ERR_UNSUPPORTED_SHAPE,
+              "sparse_conv_wgrad: channel counts must be in 1..4096 (cb may be 0)");
+  SetDevice sd(h, stream);
+  const int nslots = gmf::sparse_wgrad_slots(K);
+  gmf::SparseWgradArgs a{row_ptr, reinterpret_cast<const int2*>(pairs), by_off, off_start, K, n_out, xa, ca, cb ? xb : nullptr,
+                         cb, dy, cout, nslots, nullptr, nullptr, dW};
+  if (int rc = arena_carve(h, {arena_buf(a.chunk_info, (size_t)K + 2), arena_buf(a.partial, (size_t)nslots * (ca + cb) * cout)}))
+    return rc;
+  GMF_HIP(gmf::launch_sparse_wgrad(a, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_batchnorm_masked_forward(gmf_handle* h, const float* x, const float* residual, const float* gamma, const float* beta,
+                                 const int* n_rows, long long cap, int C, float eps, float momentum, int relu, float* y, float* mean,
+                                 float* rstd, float* running_mean, float* running_var, gmf_stream_t stream) {
+  GMF_REQUIRE(h && x && gamma && beta && n_rows && y && mean && rstd, GMF_ERR_BAD_ARG, "batchnorm_masked_forward: null pointer");
+  GMF_REQUIRE((running_mean == nullptr) == (running_var == nullptr), GMF_ERR_BAD_ARG,
+              "batchnorm_masked_forward: running stats come together");
+  GMF_REQUIRE(cap >= 1 && cap < (1LL << 28) && C >= 1 && C <= 4096, GMF_ERR_UNSUPPORTED_SHAPE,
+              "batchnorm_masked_forward: cap must be in 1 .. 2^28 - 1 and C in 1..4096");
+  SetDevice sd(h, stream);
+  float* part = nullptr;
+  if (int rc = arena_carve(h, {arena_buf(part, gmf::bnm_part_floats(cap, C))})) return rc;
+  GMF_HIP(gmf::launch_bnm_forward(x, residual, gamma, beta, n_rows, cap, C, eps, momentum, relu ? 1 : 0, y, mean, rstd, running_mean,
+                                  running_var, part, h->status_dev, GMF_STATUS_BATCHNORM_ROWS, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_batchnorm_masked_backward(gmf_handle* h, const float* dy, const float* x, const float* y_relu, const float* mean,
+                                  const float* rstd, const float* gamma, const int* n_rows, long long cap, int C, float* g, float* dx,
+                                  float* dgamma, float* dbeta, gmf_stream_t stream) {
+  GMF_REQUIRE(h && dy && x && mean && rstd && gamma && n_rows && g && dx && dgamma && dbeta, GMF_ERR_BAD_ARG,
+              "batchnorm_masked_backward: null pointer");
+  GMF_REQUIRE(cap >= 1 && cap < (1LL << 28) && C >= 1 && C <= 4096, GMF_ERR_UNSUPPORTED_SHAPE,
+              "batchnorm_masked_backward: cap must be in 1 .. 2^28 - 1 and C in 1..4096");
+  SetDevice sd(h, stream);
+  float* part = nullptr;
+  if (int rc = arena_carve(h, {arena_buf(part, gmf::bnm_part_floats(cap, C))})) return rc;
+  GMF_HIP(gmf::launch_bnm_backward(dy, x, y_relu, mean, rstd, gamma, n_rows, cap, C, g, dx, dgamma, dbeta, part, S(stream)));
   return GMF_OK;
 }
 

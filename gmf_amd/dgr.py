@@ -195,3 +195,56 @@ class DeepGlobalRegistration:
         if use_corr:
             return T, xyz0[idx0], xyz1[idx1]
         return T
+
+
+def inlier_training_loss(logits, xyz0s, xyz1s, pred_pairs, is_correct, T_gt, *, clip_weight_thresh=0.05, trans_weight=1.0,
+                         procrustes_loss_weight=1.0, inlier_direct_loss_weight=1.0, use_balanced_loss=False,
+                         inlier_use_direct_loss=True, iter_size=1):
+    """The loss of DGR's inlier-model training step (GMF_DeepGlobalRegistration_fcgf/core/trainer.py:229-270, core/loss.py,
+    core/metrics.py) on the device.  logits [sum n_b] or [sum n_b, 1] (the inlier network's output, batches concatenated in
+    order); xyz0s / xyz1s: per batch [N_b, 3] points; pred_pairs: per batch [n_b, 2] (index into xyz0, index into xyz1);
+    is_correct [sum n_b] 0 / 1; T_gt [B, 4, 4].
+
+    sigmoid, the clip (weights <= clip_weight_thresh -> 0, without an in-place write), one batched weighted Procrustes over the
+    pairs of every batch (eps = fp32 eps, the gradient flows to the weights), rotation error acos(clamp((tr(R^T R_gt) - 1) / 2,
+    -0.999, 0.999)) and translation error |t - t_gt|, the mean of rot + trans_weight trans over the batches with ws > 10 (ws the
+    sum of a batch's clipped weights), plus inlier_direct_loss_weight x BCE-with-logits (UnbalancedLoss, or BalancedLoss: the
+    mean over the two labels present) / iter_size.  Returns (loss, {"rot_error", "trans_error", "ws", "valid"}).  No batch valid:
+    the loss is not finite (the reference then skips the step); nothing raises."""
+    from .registration import weighted_procrustes_batched
+    logits = logits.reshape(-1)
+    weights = logits.sigmoid()
+    if clip_weight_thresh > 0:
+        weights = torch.where(weights > clip_weight_thresh, weights, torch.zeros_like(weights))
+    lens = [int(p.shape[0]) for p in pred_pairs]
+    if sum(lens) != logits.numel():
+        raise RuntimeError(f"gmf_amd.inlier_training_loss: {logits.numel()} logits for {sum(lens)} pairs")
+    X = torch.cat([x0[p[:, 0].long()] for x0, p in zip(xyz0s, pred_pairs)]).float()
+    Y = torch.cat([x1[p[:, 1].long()] for x1, p in zip(xyz1s, pred_pairs)]).float()
+    offsets = [0]
+    for n in lens:
+        offsets.append(offsets[-1] + n)
+    R, t = weighted_procrustes_batched(X, Y, weights, offsets, float(np.finfo(np.float32).eps))
+    seg = torch.repeat_interleave(torch.arange(len(lens), device=logits.device), torch.tensor(lens, device=logits.device))
+    ws = torch.zeros(len(lens), device=logits.device, dtype=weights.dtype).index_add_(0, seg, weights.detach())
+    T_gt = T_gt.to(logits.device).float()
+    R_gt, t_gt = T_gt[:, :3, :3], T_gt[:, :3, 3]
+    rot_error = torch.acos(torch.clamp(((R.reshape(-1, 9) * R_gt.reshape(-1, 9)).sum(1) - 1) / 2, min=-0.999, max=0.999))
+    trans_error = torch.norm(t - t_gt, p=2, dim=1)
+    individual = rot_error + trans_weight * trans_error
+    valid = ws > 10
+    # individual[valid].mean() without the host read of a boolean index: an empty selection gives 0 / 0 = NaN as mean() does
+    loss = procrustes_loss_weight * torch.where(valid, individual, torch.zeros_like(individual)).sum() / valid.sum()
+    if inlier_use_direct_loss:
+        target = torch.as_tensor(is_correct, device=logits.device).reshape(-1).float()
+        bce = torch.nn.functional.binary_cross_entropy_with_logits
+        if use_balanced_loss:
+            crit = logits.new_zeros(())
+            for lab in (0, 1):
+                mask = target == lab
+                if bool(mask.any()):
+                    crit = crit + bce(logits[mask], target[mask]) / 2
+        else:
+            crit = bce(logits, target)
+        loss = loss + inlier_direct_loss_weight * crit / iter_size
+    return loss, {"rot_error": rot_error, "trans_error": trans_error, "ws": ws, "valid": valid}

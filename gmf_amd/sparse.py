@@ -1,6 +1,8 @@
 """Sparse convolution over up to 6-D coordinates and DGR's inlier network ResUNetBN2C
-(reference: GMF_DeepGlobalRegistration/*/model/resunet_new.py:424-721, model/residual_block.py, model/common.py), eval-mode and
-forward-only.  Kernels: csrc/sparse_kernels.hip.
+(reference: GMF_DeepGlobalRegistration/*/model/resunet_new.py:424-721, model/residual_block.py, model/common.py).  The module's
+forward is eval-mode; `sparse_conv_train` (the convolution's autograd Function: weight gradient `sparse_conv_wgrad`, data
+gradient `sparse_conv_dgrad`) and gmf_amd.train.resunet_train are the train-mode path.  Kernels: csrc/sparse_kernels.hip,
+csrc/sparse_train_kernels.hip.
 
 The coordinate engine (`SparsePlan`) takes MinkowskiEngine's batched coordinates, int32 [M, 1 + D] with the batch index in
 column 0, and builds on the device every coarser level (unique floor(c / 2t) * 2t, batch kept, ascending in (batch, c_1 ..
@@ -238,6 +240,121 @@ def _check_out(out, M, cout, inputs, what, device):
         if t is not None and _overlap(out, t):
             _fail(what, f"`out` overlaps `{name}`: the convolution cannot run in place")
     return out
+
+
+def _map_arrays(plan, map_index, out_level, what):
+    if map_index is None:
+        return 1, None, None, None, None
+    if plan.maps[map_index][1] != out_level:
+        _fail(what, f"map {map_index} writes level {plan.maps[map_index][1]}, not {out_level}")
+    rp, pairs = plan.kernel_map(map_index)
+    by_off, off_start = plan.offset_lists(map_index)
+    return plan.K[map_index], rp, pairs, by_off, off_start
+
+
+def sparse_conv_wgrad(plan: SparsePlan, map_index, out_level: int, xa, dy, xb=None):
+    """Weight gradient of `sparse_conv` (`gmf_sparse_conv_wgrad`): dW [K, ca + cb, cout] = per offset d the sum over d's pairs
+    (i -> o, o < counts[out_level]) of [xa | xb][i]^T dy[o]; exactly 0 for an offset without pairs.  Each offset's pair list is
+    cut into fixed chunks added in chunk order (a function of the map and K): bitwise repeatable."""
+    what = "sparse_conv_wgrad"
+    xa = _f32_dev(xa, "xa", what)
+    dy = _f32_dev(dy, "dy", what)
+    M = plan.M
+    if xa.dim() != 2 or xa.shape[0] != M or dy.dim() != 2 or dy.shape[0] != M:
+        _fail(what, f"`xa` and `dy` must be [M = {M}, C] (got {tuple(xa.shape)}, {tuple(dy.shape)})")
+    ca, cb = xa.shape[1], 0
+    if xb is not None:
+        xb = _f32_dev(xb, "xb", what)
+        if xb.dim() != 2 or xb.shape[0] != M:
+            _fail(what, f"`xb` must be [M = {M}, cb] (got {tuple(xb.shape)})")
+        cb = xb.shape[1]
+    K, rp, pairs, by_off, off_start = _map_arrays(plan, map_index, out_level, what)
+    cout = dy.shape[1]
+    dW = torch.empty((K, ca + cb, cout), dtype=torch.float32, device=xa.device)
+    h, st = handle_and_stream(xa)
+    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    h.call("gmf_sparse_conv_wgrad", p(rp), p(pairs), p(by_off), p(off_start), K, plan.count_ptr(out_level), xa.data_ptr(), ca,
+           p(xb), cb, dy.data_ptr(), cout, dW.data_ptr(), st)
+    return dW
+
+
+def transposed_map(plan: SparsePlan, map_index):
+    """(index of the map (k, in, out) of `plan`, flip): the data gradient of a convolution over map (k, out, in) is a convolution
+    over its transposed map with W'[d] = W[s(d)]^T, s the identity for a strided map (down <-> transposed, same offset index) and
+    the flip d -> K - 1 - d for a same-level map (the map is its own transpose; the offset of K - 1 - d is minus that of d).  The
+    identity map (None) is its own transpose."""
+    if map_index is None:
+        return None, False
+    k, o, i = plan.maps[map_index]
+    if o == i:
+        return map_index, True
+    if (k, i, o) not in plan.maps:
+        _fail("sparse_conv_dgrad", f"the plan has no map ({k}, {i}, {o}), the transpose of map {map_index}")
+    return plan.maps.index((k, i, o)), False
+
+
+def sparse_conv_dgrad(plan: SparsePlan, map_index, out_level: int, dy, W):
+    """Data gradient of `sparse_conv` over map `map_index` (out level `out_level`): dx [M, cin] = `sparse_conv` of dy over the
+    transposed map with W'[d] = W[s(d)]^T ([K, cout, cin]), into the input level; rows >= counts[in level] are 0."""
+    W = W if W.dim() == 3 else W.unsqueeze(0)
+    if map_index is None:
+        in_level, tmap, flip = out_level, None, False
+    else:
+        in_level = plan.maps[map_index][2]
+        tmap, flip = transposed_map(plan, map_index)
+    Wt = (W.flip(0) if flip else W).transpose(1, 2).contiguous()
+    K, cout, cin = Wt.shape
+    dx = torch.zeros((plan.M, cin), dtype=torch.float32, device=dy.device)
+    return sparse_conv(plan, tmap, in_level, dy, Wt, nsplit=layer_nsplit(K, cout, cin), out=dx)
+
+
+class _SparseConvFn(torch.autograd.Function):
+    """y = relu?(sparse_conv([xa | xb], W) + bias) over one map of a plan, differentiable in xa, xb, W and bias.  Backward:
+    dW by `sparse_conv_wgrad`, [dxa | dxb] by `sparse_conv_dgrad` (only for an input that needs it), dbias by a column sum; the
+    ReLU masks dy by the saved output (gmf_relu_backward).  Rows of y past counts[out_level] are not written; rows of dx past
+    the input level's count are 0."""
+
+    @staticmethod
+    def forward(ctx, plan, map_index, out_level, xa, xb, W, bias, relu):
+        W3 = W.detach() if W.dim() == 3 else W.detach().unsqueeze(0)
+        y = sparse_conv(plan, map_index, out_level, xa.detach(), W3, xb=None if xb is None else xb.detach(),
+                        shift=None if bias is None else bias.detach().reshape(-1), relu=relu,
+                        nsplit=layer_nsplit(W3.shape[0], W3.shape[1], W3.shape[2]))
+        ctx.plan, ctx.map_index, ctx.out_level, ctx.relu = plan, map_index, out_level, relu
+        ctx.wshape, ctx.has_b, ctx.ca, ctx.has_xb = W.shape, bias is not None, xa.shape[1], xb is not None
+        ctx.save_for_backward(xa.detach(), xb.detach() if xb is not None else None, W3, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xa, xb, W3, y = ctx.saved_tensors
+        plan = ctx.plan
+        dy = _f32_dev(dy, "grad", "sparse_conv backward")
+        if ctx.relu:
+            g = torch.empty_like(dy)
+            h, st = handle_and_stream(dy)
+            h.call("gmf_relu_backward", dy.data_ptr(), y.data_ptr(), g.data_ptr(), dy.numel(), st)
+            dy = g
+        dW = db = dxa = dxb = None
+        if ctx.needs_input_grad[5]:
+            dW = sparse_conv_wgrad(plan, ctx.map_index, ctx.out_level, xa, dy, xb=xb).reshape(ctx.wshape)
+        if ctx.has_b and ctx.needs_input_grad[6]:
+            from .train import colsum
+            db = colsum(dy).reshape(1, -1)
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            dx = sparse_conv_dgrad(plan, ctx.map_index, ctx.out_level, dy, W3)
+            dxa = dx[:, :ctx.ca] if ctx.needs_input_grad[3] else None
+            dxb = dx[:, ctx.ca:] if ctx.has_xb and ctx.needs_input_grad[4] else None
+        return None, None, None, dxa, dxb, dW, db, None
+
+
+def sparse_conv_train(plan: SparsePlan, map_index, out_level: int, xa, W, xb=None, bias=None, relu: bool = False):
+    """Differentiable `sparse_conv` (no folded BatchNorm, no residual): relu?([xa | xb] (*) W + bias).  W is MinkowskiEngine's
+    `kernel` ([K, Cin, Cout], or [Cin, Cout] when K = 1); a bias [1, Cout] only into level 0, where every row is valid (its
+    gradient sums all M rows)."""
+    if bias is not None and out_level != 0:
+        _fail("sparse_conv_train", "a bias is supported into level 0 only")
+    return _SparseConvFn.apply(plan, map_index, out_level, xa, xb, W, bias, bool(relu))
 
 
 def sparse_conv_narrow(plan: SparsePlan, map_index: int, out_level: int, x, W, scale=None, shift=None, residual=None,
@@ -514,7 +631,8 @@ class ResUNetBN2C(nn.Module):
 
     def forward(self, coords, feats, p_image=None, q_image=None, p_tokens=None, q_tokens=None):
         if self.training:
-            raise RuntimeError("gmf_amd.ResUNetBN2C: only the eval-mode forward is built - call eval()")
+            raise RuntimeError("gmf_amd.ResUNetBN2C: forward() is the eval-mode forward - call eval(); the differentiable "
+                               "train-mode forward is gmf_amd.train.resunet_train(model, coords, feats, ...)")
         self._check_images(p_image, q_image, p_tokens, q_tokens)
         M, D = check_coords(coords, "ResUNetBN2C")
         if D != self.D:

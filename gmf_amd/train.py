@@ -631,3 +631,114 @@ class GraphedTrainingStep:
         self.graph.replay()
         return self.loss
 
+
+# =====================================================================================================================
+# DGR's inlier network ResUNetBN2C in training mode (resunet_new.py:627-706 with batch-statistics BatchNorm; the loop of
+# GMF_DeepGlobalRegistration_fcgf/core/trainer.py:159-305).  Activations are the plan's [M, C] level buffers: counts[l] valid rows
+# first, the rest written as 0 by every BatchNorm and every data gradient.
+
+
+class _BatchNormMasked(torch.autograd.Function):
+    """MinkowskiBatchNorm in training mode over the counts[level] valid rows of x [M, C] (`gmf_batchnorm_masked_forward`), + an
+    optional residual, + an optional ReLU; rows past the count are 0 in y and dx; the residual's gradient is the masked upstream
+    gradient g.  Updates running_mean / running_var in place."""
+
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, running_mean, running_var, n_ptr, eps, momentum, relu):
+        x = x.detach().contiguous()
+        cap, C = x.shape
+        res = None if residual is None else residual.detach().contiguous()
+        y = torch.empty_like(x)
+        mean = torch.empty(C, device=x.device, dtype=torch.float32)
+        rstd = torch.empty(C, device=x.device, dtype=torch.float32)
+        h, st = handle_and_stream(x)
+        h.call("gmf_batchnorm_masked_forward", x.data_ptr(), None if res is None else res.data_ptr(), gamma.data_ptr(),
+               beta.data_ptr(), n_ptr, cap, C, float(eps), float(momentum), 1 if relu else 0, y.data_ptr(), mean.data_ptr(),
+               rstd.data_ptr(), None if running_mean is None else running_mean.data_ptr(),
+               None if running_var is None else running_var.data_ptr(), st)
+        ctx.relu, ctx.n_ptr, ctx.has_res = relu, n_ptr, residual is not None
+        ctx.save_for_backward(x, gamma.detach(), mean, rstd, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, mean, rstd, y = ctx.saved_tensors
+        dy = require_cuda_f32(dy, "grad").contiguous()
+        cap, C = x.shape
+        g = torch.empty_like(x)
+        dx = torch.empty_like(x)
+        dg = torch.empty(C, device=x.device, dtype=torch.float32)
+        db = torch.empty(C, device=x.device, dtype=torch.float32)
+        h, st = handle_and_stream(x)
+        h.call("gmf_batchnorm_masked_backward", dy.data_ptr(), x.data_ptr(), y.data_ptr() if ctx.relu else None, mean.data_ptr(),
+               rstd.data_ptr(), gamma.data_ptr(), ctx.n_ptr, cap, C, g.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), st)
+        return dx, (g if ctx.has_res else None), dg, db, None, None, None, None, None, None
+
+
+def batchnorm_masked(x, bn, plan, level: int, residual=None, relu: bool = False):
+    """`bn` (an nn.BatchNorm1d) in train() mode over the valid rows of level `level` of `plan`: relu?(bn(x) + residual), rows past
+    counts[level] written as 0.  Parameters and running statistics are used / updated exactly as torch would."""
+    if bn.momentum is None:
+        raise NotImplementedError("gmf_amd.train: BatchNorm with cumulative moving average (momentum=None) is not used by DGR")
+    track = bn.track_running_stats
+    y = _BatchNormMasked.apply(x, residual, bn.weight, bn.bias, bn.running_mean if track else None,
+                               bn.running_var if track else None, plan.count_ptr(level), bn.eps, bn.momentum, bool(relu))
+    if track and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked += 1
+    return y
+
+
+def resunet_train(model, coords, feats, p_image=None, q_image=None, p_tokens=None, q_tokens=None):
+    """The differentiable train-mode forward of a gmf_amd.ResUNetBN2C (resunet_new.py:627-706, batch-statistics BatchNorm):
+    logits [M, out_channels], aligned with the input rows.  Gradients reach the 23 kernels, final.bias, the 21 BatchNorms, both
+    fusion layers, the image encoder (train-mode stock torch modules) when images are given, and p_tokens / q_tokens when tokens
+    are given; every running statistic is updated as torch does.  The eval path's conventions hold: one image pair, the
+    bottleneck's queries all stride-8 rows in ascending (batch, coordinates) order, zero rows past the level count (the position
+    encoding's zero padding for pe=True).  Reads the four level counts to the host once, to raise as torch's BatchNorm does on
+    a level of fewer than 2 rows."""
+    from .sparse import SparsePlan, _NET_MAPS, check_coords, sparse_conv_train
+    if not model.training:
+        raise RuntimeError("gmf_amd.train.resunet_train: the model is in eval() mode - call train(), or use forward() for inference")
+    if not torch.is_grad_enabled():
+        raise RuntimeError("gmf_amd.train.resunet_train: autograd is disabled (torch.no_grad()); the eval forward is model.forward")
+    model._check_images(p_image, q_image, p_tokens, q_tokens)
+    M, D = check_coords(coords, "resunet_train")
+    if D != model.D:
+        raise RuntimeError(f"gmf_amd.train.resunet_train: coords have D = {D}, the network was built for D = {model.D}")
+    feats = require_cuda_f32(feats, "feats").contiguous()
+    if feats.shape != (M, model.in_channels):
+        raise RuntimeError(f"gmf_amd.train.resunet_train: `feats` must be [{M}, {model.in_channels}] (got {tuple(feats.shape)})")
+    p_tok, q_tok = model._tokens(p_image, q_image, p_tokens, q_tokens)
+    maps = list(_NET_MAPS)
+    c1 = model.conv1_kernel_size
+    c1_map = None if c1 == 1 else (0 if c1 == 3 else len(maps))
+    if c1 not in (1, 3):
+        maps.append((c1, 0, 0))
+    plan = SparsePlan(coords, 4, maps)
+    counts = plan.counts.tolist()
+    if min(counts) < 2:
+        raise RuntimeError(f"gmf_amd.train.resunet_train: a level has fewer than 2 rows (counts {counts}); BatchNorm in training "
+                           "mode needs more than 1 value per channel")
+
+    def conv(mod, m, lvl, xa, xb=None, bias=None, relu=False):
+        return sparse_conv_train(plan, m, lvl, xa, mod.kernel, xb=xb, bias=bias, relu=relu)
+
+    def bn(norm, x, lvl, residual=None, relu=False):
+        return batchnorm_masked(x, norm.bn, plan, lvl, residual=residual, relu=relu)
+
+    def block(b, lvl, x):                       # residual_block.py:104-123
+        h = bn(b.norm1, conv(b.conv1, lvl, lvl, x), lvl, relu=True)
+        return bn(b.norm2, conv(b.conv2, lvl, lvl, h), lvl, residual=x, relu=True)
+
+    image_feat = fusion_layer_train(model.image_fusion, p_tok, q_tok)                  # resunet_new.py:636
+    s1 = block(model.block1, 0, bn(model.norm1, conv(model.conv1, c1_map, 0, feats), 0))
+    s2 = block(model.block2, 1, bn(model.norm2, conv(model.conv2, 4, 1, s1), 1))
+    s4 = block(model.block3, 2, bn(model.norm3, conv(model.conv3, 5, 2, s2), 2))
+    s8 = block(model.block4, 3, bn(model.norm4, conv(model.conv4, 6, 3, s4), 3))     # rows past counts[3]: 0
+    f8 = fusion_layer_train(model.perceiver_io, image_feat, s8.unsqueeze(0))[0]       # resunet_new.py:694-704
+    t4 = block(model.block4_tr, 2, bn(model.norm4_tr, conv(model.conv4_tr, 9, 2, f8), 2))
+    t2 = block(model.block3_tr, 1, bn(model.norm3_tr, conv(model.conv3_tr, 8, 1, t4, xb=s4), 1))
+    t1 = block(model.block2_tr, 0, bn(model.norm2_tr, conv(model.conv2_tr, 7, 0, t2, xb=s2), 0))
+    o = conv(model.conv1_tr, None, 0, t1, xb=s1, relu=True)                          # MEF.relu(conv1_tr(ME.cat(...)))
+    return conv(model.final, None, 0, o, bias=model.final.bias)
+

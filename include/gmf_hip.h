@@ -79,6 +79,9 @@ long long gmf_workspace_wanted(gmf_handle* h);
 /* gmf_sparse_build_plan met a duplicate (batch, coordinates) input row: rows must be unique, they are never merged; the
  * plan and everything computed from it are not valid. */
 #define GMF_STATUS_SPARSE_DUPLICATE 4
+/* gmf_batchnorm_masked_forward met a level with fewer than 2 valid rows (torch's BatchNorm raises there): its outputs and
+ * batch statistics are not valid and the running statistics were left unchanged. */
+#define GMF_STATUS_BATCHNORM_ROWS 8
 int gmf_status_read(gmf_handle* h, int* flags, int clear);
 
 /* [ABI 5] PointDSC's learnable scalar `sigma` (PointDSC.py:164) from DEVICE memory.  While `sigma_dev` is non-NULL every entry point
@@ -578,6 +581,39 @@ int gmf_sparse_head_l2(gmf_handle* h, const int* n_out, long long cap_out, const
 #define GMF_SPARSE_RESUNET_LAYERS 23
 int gmf_sparse_pack_resunet(gmf_handle* h, const gmf_tensor* tensors, int n_tensors, float* dev, long long dev_floats,
                             long long* layout, long long* need_floats);
+
+/* ---- training of the sparse network: sparse-convolution weight gradient, BatchNorm over a level's device-counted rows ---- */
+
+/* Weight gradient of gmf_sparse_conv, fp32: dW[d] = sum over the pairs (d, i) of output rows o < *n_out of [xa | xb][i]^T dy[o],
+ * dW [K, ca + cb, cout] (every offset written; 0 for an offset without pairs).  The map arguments are gmf_sparse_conv's (all NULL:
+ * the identity map, K = 1, pair j = row j).  dy [*, cout] holds the output level's rows.  The data gradient needs no entry point
+ * of its own: it is gmf_sparse_conv over the transposed map with W'[d] = W[s(d)]^T (gmf_amd/sparse.py: sparse_conv_backward).
+ * Sum order: each offset's pair list (by_off, ascending output row) is cut into chunks of P = max(64, ceil(nnz / (S - K))) pairs,
+ * nnz the map's pair count and S = K + max(K, 256) the chunk slots; inside a chunk 16-pair fma chains are added in pair order, and
+ * an offset's chunks are added in chunk order by a second pass.  The order depends only on the map and K: bitwise repeatable, no
+ * float atomics.  Workspace: S x (ca + cb) x cout + K + 2 floats.  No host synchronisation. */
+int gmf_sparse_conv_wgrad(gmf_handle* h, const int* row_ptr, const int* pairs, const int* by_off, const int* off_start, int K,
+                          const int* n_out, const float* xa, int ca, const float* xb, int cb, const float* dy, int cout, float* dW,
+                          gmf_stream_t stream);
+
+/* MinkowskiBatchNorm in TRAINING mode (nn.BatchNorm1d over the valid rows of all batches) on a sparse level: x [cap, C] row-major,
+ * *n_rows (device pointer, a plan's level count) valid rows first.  y = gamma (x - mean) rstd + beta, + residual [cap, C] (may be
+ * NULL), then max(., 0) if relu - plain bn, relu(bn) and the residual block's tail relu(bn(x) + residual); rows >= *n_rows of y are
+ * written as 0.  mean / rstd [C] (biased variance) are returned for the backward; running_mean / running_var (both or neither)
+ * are updated as torch does: r = (1 - momentum) r + momentum v, the variance unbiased over the valid count.  Fewer than 2 valid
+ * rows sets GMF_STATUS_BATCHNORM_ROWS and leaves the running statistics alone.  Column sums run over min(64, ceil(cap / 256))
+ * fixed row chunks of the cap slots (4 row lanes per column added in order, chunks added in order), the variance as a second
+ * pass over the centred rows.  Workspace 2 x chunks x C floats.  No host synchronisation. */
+int gmf_batchnorm_masked_forward(gmf_handle* h, const float* x, const float* residual, const float* gamma, const float* beta,
+                                 const int* n_rows, long long cap, int C, float eps, float momentum, int relu, float* y, float* mean,
+                                 float* rstd, float* running_mean, float* running_var, gmf_stream_t stream);
+/* Backward of gmf_batchnorm_masked_forward: g = dy on valid rows (and where y_relu > 0 when the forward applied the ReLU; y_relu
+ * is then its output, else NULL), 0 elsewhere, written for all cap rows - the upstream gradient of the residual branch; dbeta =
+ * sum g, dgamma = sum g xhat (the forward's chunk order); dx = gamma rstd (g - dbeta / n - xhat dgamma / n) on valid rows, 0
+ * beyond. */
+int gmf_batchnorm_masked_backward(gmf_handle* h, const float* dy, const float* x, const float* y_relu, const float* mean,
+                                  const float* rstd, const float* gamma, const int* n_rows, long long cap, int C, float* g, float* dx,
+                                  float* dgamma, float* dbeta, gmf_stream_t stream);
 
 /* ---- validation step: the non-test forward's similarity matrix and the metrics of libs/trainer.py:194-262 ---------- */
 
