@@ -10,7 +10,7 @@ from .pointdsc import NonLocalBlock, NonLocalNet, PointDSC, ImageEncoder   # noq
 from .common import rigid_transform_3d, knn      # noqa: F401
 from .registration import (weighted_procrustes, weighted_procrustes_batched, GlobalRegistration,  # noqa: F401
                            global_registration_batched, argmin_se3_squared_dist, Transformation, ortho2rotation)
-from .matching import nn_match, find_knn_gpu    # noqa: F401
+from .matching import nn_match, find_knn_gpu, find_knn_gpu_batch, find_knn_batch, find_pairs    # noqa: F401
 from . import se3 as SE3                         # noqa: F401
 from ._lib import check_status, set_handle_per_stream   # noqa: F401
 from .solvers import (ransac_correspondence_batched, icp_point_to_point_batched, RegistrationResult,  # noqa: F401
@@ -21,6 +21,7 @@ from .features import (radius_knn_batched, estimate_normals_batched, compute_fpf
 from .sparse import (SparsePlan, sparse_conv, sparse_conv_narrow, sparse_head_l2, ResUNetBN2C, ResUNetBN2CX,  # noqa: F401
                      inlier_coordinates)
 from . import fcgf, dgr                          # noqa: F401  (gmf_amd.fcgf.ResUNetBN2C: FCGF; gmf_amd.ResUNetBN2C: the inlier net)
+from .dgr import matching_indices_batched, find_correct_correspondence, generate_inlier_input   # noqa: F401
 from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss, similarity_matrix   # noqa: F401
 
 __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointDSC", "ImageEncoder",
@@ -31,4 +32,5 @@ __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointD
            "icp_refine", "radius_knn_batched", "estimate_normals_batched", "compute_fpfh_batched", "voxel_down_sample_batched",
            "voxel_select_batched", "voxel_down_sample", "voxel_select", "estimate_normals", "compute_fpfh_feature",
            "fpfh_descriptors", "SparsePlan", "sparse_conv", "sparse_conv_narrow", "sparse_head_l2", "ResUNetBN2C", "ResUNetBN2CX",
-           "inlier_coordinates", "fcgf", "dgr"]
+           "inlier_coordinates", "fcgf", "dgr", "find_knn_gpu_batch", "find_knn_batch", "find_pairs", "matching_indices_batched",
+           "find_correct_correspondence", "generate_inlier_input"]

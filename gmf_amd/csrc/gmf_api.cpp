@@ -19,6 +19,7 @@
 #include "launchers_solvers.hpp"
 #include "launchers_pointcloud.hpp"
 #include "launchers_sparse.hpp"
+#include "launchers_dgr_input.hpp"
 
 namespace {
 
@@ -1179,6 +1180,135 @@ int gmf_nn_match(gmf_handle* h, const float* F0, const float* F1, int N0, int N1
   float* nb = arena_take<float>(h, (size_t)tiles_of(N1) * 32);       // whole tiles: the padding holds +inf
   unsigned long long* best = arena_take<unsigned long long>(h, (size_t)N0);     // (score, index) of every row's winner: one atomic minimum per key split
   GMF_HIP(gmf::launch_nn_match(F0, F1, i0, i1, nb, best, idx_out, dist_out, N0, N1, d, mode, S(stream)));
+  return GMF_OK;
+}
+
+// `bytes` of the next slot of the handle's pinned ring (the slots of build_pair_table, for a host table of another type); the caller
+// fills it and uploads it with upload_ring_bytes()
+static int take_ring_bytes(gmf_handle* h, size_t bytes, void** host) {
+  h->ptab_cur = h->ptab_next;
+  h->ptab_next = (h->ptab_next + 1) % gmf_handle::kPtabSlots;
+  gmf_handle::PtabSlot& slot = h->ptab_ring[h->ptab_cur];
+  if (slot.pending) {
+    GMF_HIP(hipEventSynchronize(slot.ev));
+    slot.pending = false;
+  }
+  const size_t want = (bytes + sizeof(gmf::PairTab) - 1) / sizeof(gmf::PairTab);
+  if (slot.cap < want) {
+    if (slot.host) GMF_HIP(hipHostFree(slot.host));
+    slot.host = nullptr;
+    slot.cap = 0;
+    const size_t cap = (want + 63) / 64 * 64;
+    GMF_HIP(hipHostMalloc(reinterpret_cast<void**>(&slot.host), cap * sizeof(gmf::PairTab), hipHostMallocDefault));
+    slot.cap = cap;
+  }
+  if (!slot.ev) GMF_HIP(hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming));
+  *host = slot.host;
+  return GMF_OK;
+}
+
+static int upload_ring_bytes(gmf_handle* h, void* dst, size_t bytes, hipStream_t st) {
+  gmf_handle::PtabSlot& slot = h->ptab_ring[h->ptab_cur];
+  GMF_HIP(hipMemcpyAsync(dst, slot.host, bytes, hipMemcpyHostToDevice, st));
+  GMF_HIP(hipEventRecord(slot.ev, st));
+  slot.pending = true;
+  return GMF_OK;
+}
+
+int gmf_nn_match_batched(gmf_handle* h, const float* F0, const float* F1, const int* off0, const int* off1, int B, int d, int mode,
+                         int global_index, int* idx_out, float* dist_out, gmf_stream_t stream) {
+  GMF_REQUIRE(h && off0 && off1, GMF_ERR_BAD_ARG, "nn_match_batched: null pointer");
+  GMF_REQUIRE(B > 0 && d > 0, GMF_ERR_UNSUPPORTED_SHAPE, "nn_match_batched: empty batch");
+  GMF_REQUIRE(mode >= 0 && mode <= 2, GMF_ERR_BAD_ARG, "nn_match_batched: mode must be 0 (PointDSC), 1 (DGR L2) or 2 (DGR SquareL2)");
+  const int K = gmf::padded_desc_width(d);
+  GMF_REQUIRE(K > 0, GMF_ERR_UNSUPPORTED_SHAPE, "nn_match_batched: descriptor width above 128 is not supported");
+  GMF_REQUIRE(off0[0] == 0 && off1[0] == 0, GMF_ERR_BAD_ARG, "nn_match_batched: offsets must start at 0");
+  for (int b = 0; b < B; ++b)
+    GMF_REQUIRE(off0[b + 1] >= off0[b] && off1[b + 1] >= off1[b], GMF_ERR_BAD_ARG, "nn_match_batched: offsets must ascend");
+  if (off0[B] == 0) return GMF_OK;                     // no query rows: nothing to write
+  GMF_REQUIRE(F0 && F1 && idx_out && dist_out, GMF_ERR_BAD_ARG, "nn_match_batched: null pointer");
+  SetDevice sd(h, stream);
+  const size_t tab_bytes = (size_t)(B + 1) * sizeof(gmf::MatchPair);
+  void* host = nullptr;
+  if (int rc = take_ring_bytes(h, tab_bytes, &host)) return rc;
+  gmf::MatchPair* tab = static_cast<gmf::MatchPair*>(host);
+  gmf::MatchTotals tot;
+  GMF_REQUIRE(gmf::plan_nn_match_batched(off0, off1, B, K, tab, &tot), GMF_ERR_UNSUPPORTED_SHAPE,
+              "nn_match_batched: a pair has query rows and no key rows");
+  GMF_REQUIRE(tot.wgs < (1L << 31) && tot.stages * tot.tps * 32 < (1L << 31), GMF_ERR_UNSUPPORTED_SHAPE, "nn_match_batched: batch too large");
+  // the images hold whole tiles (queries) and whole stages (keys) of every pair: no slack behind the last stage is needed
+  const size_t n0 = (size_t)tot.tiles0 * 32 * K, n1 = (size_t)tot.stages * tot.tps * 32 * K, nn = (size_t)tot.stages * tot.tps * 32;
+  float *i0, *i1, *nb;
+  unsigned long long* best;
+  gmf::MatchPair* dtab;
+  if (int rc = arena_carve(h, {arena_buf(i0, n0), arena_buf(i1, n1), arena_buf(nb, nn), arena_buf(best, (size_t)tot.rows0),
+                               arena_buf(dtab, (size_t)B + 1)})) return rc;
+  if (int rc = upload_ring_bytes(h, dtab, tab_bytes, S(stream))) return rc;
+  GMF_HIP(gmf::launch_nn_match_batched(F0, F1, i0, i1, nb, best, dtab, B, tot, d, mode, global_index, idx_out, dist_out, S(stream)));
+  return GMF_OK;
+}
+
+// the checks gmf_matching_indices_count and _fill share
+static int check_matching_args(gmf_handle* h, const char* what, const void* xyz0, const void* off0, const void* xyz1, const void* off1,
+                               int B, long long total0, long long total1, const void* T, double radius) {
+  GMF_REQUIRE(h && xyz0 && off0 && xyz1 && off1 && T, GMF_ERR_BAD_ARG, std::string(what) + ": null pointer");
+  GMF_REQUIRE(B > 0 && total0 > 0 && total1 > 0 && total0 < (1LL << 30) && total1 < (1LL << 30), GMF_ERR_UNSUPPORTED_SHAPE,
+              std::string(what) + ": empty batch, or 2^30 rows or more");
+  GMF_REQUIRE(radius > 0 && std::isfinite(radius), GMF_ERR_BAD_ARG, std::string(what) + ": radius must be > 0 and finite");
+  return GMF_OK;
+}
+
+int gmf_matching_indices_count(gmf_handle* h, const float* xyz0, const int* off0, const float* xyz1, const int* off1, int B,
+                               long long total0, long long total1, const double* T, double radius, long long* row_start,
+                               long long* pair_offsets, long long* num_pairs, gmf_stream_t stream) {
+  if (int rc = check_matching_args(h, "matching_indices_count", xyz0, off0, xyz1, off1, B, total0, total1, T, radius)) return rc;
+  GMF_REQUIRE(row_start && pair_offsets && num_pairs, GMF_ERR_BAD_ARG, "matching_indices_count: null pointer");
+  SetDevice sd(h, stream);
+  const size_t scan_bytes = gmf::matching_indices_scan_bytes(total0);
+  int* cnt;
+  char* scan_tmp;
+  if (int rc = arena_carve(h, {arena_buf(cnt, (size_t)total0 + 1), arena_buf(scan_tmp, scan_bytes + 256)})) return rc;
+  GMF_HIP(gmf::launch_matching_indices_count(xyz0, off0, xyz1, off1, B, total0, T, radius * radius, cnt, scan_tmp, scan_bytes, row_start,
+                                             pair_offsets, S(stream)));
+  long long k = 0;                                   // the one host read: the size of the output
+  GMF_HIP(hipMemcpyAsync(&k, row_start + total0, sizeof(k), hipMemcpyDeviceToHost, S(stream)));
+  GMF_HIP(hipStreamSynchronize(S(stream)));
+  *num_pairs = k;
+  return GMF_OK;
+}
+
+int gmf_matching_indices_fill(gmf_handle* h, const float* xyz0, const int* off0, const float* xyz1, const int* off1, int B,
+                              long long total0, long long total1, const double* T, double radius, const long long* row_start,
+                              long long* pairs, gmf_stream_t stream) {
+  if (int rc = check_matching_args(h, "matching_indices_fill", xyz0, off0, xyz1, off1, B, total0, total1, T, radius)) return rc;
+  GMF_REQUIRE(row_start && pairs, GMF_ERR_BAD_ARG, "matching_indices_fill: null pointer");
+  SetDevice sd(h, stream);
+  GMF_HIP(gmf::launch_matching_indices_fill(xyz0, off0, xyz1, off1, B, total0, T, radius * radius, row_start, pairs, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_inlier_input(gmf_handle* h, const int* nn, const long long* pred, const int* off0, const int* off1, int B, long long M,
+                     long long* pred_out, const int* coords0, const int* coords1, int* coords_out, int feat_type, const float* a0,
+                     const float* a1, int c, float* feats_out, const long long* pos_keys, const long long* pos_off,
+                     const long long* seeds, unsigned char* labels_out, gmf_stream_t stream) {
+  GMF_REQUIRE(h && off0, GMF_ERR_BAD_ARG, "inlier_input: null pointer");
+  GMF_REQUIRE(B > 0 && M > 0 && M < (1LL << 30), GMF_ERR_UNSUPPORTED_SHAPE, "inlier_input: empty batch, or 2^30 pairs or more");
+  GMF_REQUIRE((nn != nullptr) != (pred != nullptr), GMF_ERR_BAD_ARG, "inlier_input: pass the matches `nn` or the pairs `pred`, not both");
+  GMF_REQUIRE(!nn || pred_out, GMF_ERR_BAD_ARG, "inlier_input: `nn` needs pred_out");
+  GMF_REQUIRE(coords_out || labels_out, GMF_ERR_BAD_ARG, "inlier_input: nothing to write");
+  if (coords_out) {
+    GMF_REQUIRE(nn && off1 && coords0 && coords1 && feats_out, GMF_ERR_BAD_ARG, "inlier_input: the rows need nn, off1, both coordinate tensors and feats_out");
+    GMF_REQUIRE(feat_type >= 0 && feat_type <= 2, GMF_ERR_BAD_ARG, "inlier_input: feat_type must be 0 (ones), 1 (feats) or 2 (coords)");
+    GMF_REQUIRE(feat_type == 0 || (a0 && a1), GMF_ERR_BAD_ARG, "inlier_input: the features need their two source tensors");
+    GMF_REQUIRE(feat_type != 1 || (c >= 1 && c <= gmf::kInlierMaxFeat), GMF_ERR_UNSUPPORTED_SHAPE, "inlier_input: 'feats' takes descriptors 1..64 wide");
+  }
+  if (labels_out) GMF_REQUIRE(pos_keys && pos_off && seeds, GMF_ERR_BAD_ARG, "inlier_input: the labels need pos_keys, pos_off and seeds");
+  SetDevice sd(h, stream);
+  gmf::InlierInput in;
+  in.nn = nn; in.pred = pred; in.off0 = off0; in.off1 = off1; in.B = B; in.M = M; in.pred_out = pred_out;
+  in.c0 = coords0; in.c1 = coords1; in.coords_out = coords_out; in.feat_type = feat_type; in.a0 = a0; in.a1 = a1; in.c = c;
+  in.feats_out = feats_out; in.pos_keys = pos_keys; in.pos_off = pos_off; in.seeds = seeds; in.labels_out = labels_out;
+  GMF_HIP(gmf::launch_inlier_input(in, S(stream)));
   return GMF_OK;
 }
 

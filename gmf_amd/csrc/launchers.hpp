@@ -168,6 +168,17 @@ hipError_t launch_fusion_ff_h2(const float* x1, const float* wst, const float* v
 int padded_desc_width(int d);
 hipError_t launch_nn_match(const float* F0, const float* F1, float* f0_img, float* f1_img, float* norm2, unsigned long long* best, int* idx,
                            float* dist, int N0, int N1, int d, int mode, hipStream_t s);
+// Batched matching over B ragged pairs (gmf_nn_match_batched).  Pair b owns rows [row0, row0 + n0) of F0 and [key0, key0 + n1) of
+// F1.  Its query rows are packed into whole 32-row tiles from tile `tile0` of the F0 image, its keys into whole stages from stage
+// `stage0` of the F1 image (and of the norms), and its workgroups are [wg0, wg0 + wgx * ks): wgx query blocks of four tiles times ks
+// key splits.  Entry B of the table holds the totals (an empty range), so every prefix search has its end.
+struct MatchPair { int row0, n0, key0, n1, tile0, stage0, stages, wg0, wgx, ks, pad0, pad1; };
+struct MatchTotals { long tiles0, stages, wgs, rows0; int tps; };
+// fills tab[0 .. B] from the B + 1 host offsets; false: a pair has queries and no keys
+bool plan_nn_match_batched(const int* off0, const int* off1, int B, int K, MatchPair* tab, MatchTotals* tot);
+hipError_t launch_nn_match_batched(const float* F0, const float* F1, float* f0_img, float* f1_img, float* norm2, unsigned long long* best,
+                                   const MatchPair* tab, int B, const MatchTotals& tot, int d, int mode, int global_index, int* idx,
+                                   float* dist, hipStream_t s);
 hipError_t launch_seed_dist(const float* featn_img, const int* seeds, float* dist, int B, int N, int S, hipStream_t s, const PairTab* ptab = nullptr);
 hipError_t launch_pack_p32(const float* src, float* dst, int B, int n_rows, int K, long sb, long sr, long sk, hipStream_t s, const PairTab* ptab = nullptr);
 // row-major [B, n_rows, 128] -> split-fp16 plane image (the operand image of launch_seed_dist)

@@ -3,9 +3,14 @@ model/__init__.py): `load_model` and `DeepGlobalRegistration` with its `register
 
 Every step runs on the device: voxel_select, FCGF (`gmf_amd.fcgf.ResUNetBN2C`, both clouds in one plan), find_knn_gpu, the 6-D
 inlier network (`gmf_amd.ResUNetBN2C`), GlobalRegistration or the safeguard RANSAC, and ICP.
+
+For training, the step between the data loader and the inlier network (core/trainer.py:616-699, core/correspondence.py:14-53,
+util/pointcloud.py:83-96) over a collated batch: `matching_indices_batched` (the ground-truth pairs), `find_correct_correspondence`
+(the labels) and `generate_inlier_input`.  Kernels: csrc/dgr_input_kernels.hip, csrc/match_kernels.hip.
 """
 from __future__ import annotations
 
+import ctypes
 from collections.abc import Mapping
 
 import numpy as np
@@ -13,7 +18,8 @@ import torch
 
 from . import fcgf
 from .features import voxel_select
-from .matching import find_knn_gpu
+from ._util import handle_and_stream
+from .matching import _batch_offsets, _match_batched, find_knn_gpu
 from .registration import GlobalRegistration
 from .solvers import registration_icp, registration_ransac_based_on_correspondence
 from .sparse import ResUNetBN2C as InlierResUNetBN2C, inlier_coordinates
@@ -248,3 +254,236 @@ def inlier_training_loss(logits, xyz0s, xyz1s, pred_pairs, is_correct, T_gt, *, 
             crit = bce(logits, target)
         loss = loss + inlier_direct_loss_weight * crit / iter_size
     return loss, {"rot_error": rot_error, "trans_error": trans_error, "ws": ws, "valid": valid}
+
+
+# ---- the batched input of the inlier network -----------------------------------------------------------------------------------
+
+INLIER_FEATURE_TYPES = ("ones", "feats", "coords")      # gmf_inlier_input's feat_type 0, 1, 2
+
+
+def _offsets_list(offsets, n_rows, name, what):
+    """A host offset sequence checked (B + 1 entries ascending from 0 to n_rows; empty clouds allowed) -> list, or a device int32
+    tensor as it is (the caller vouches for it)."""
+    if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
+        if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2 or not offsets.is_contiguous():
+            raise RuntimeError(f"gmf_amd.{what}: device `{name}` must be a contiguous int32 vector of B + 1 entries")
+        return offsets
+    try:
+        off = [int(o) for o in (offsets.tolist() if isinstance(offsets, (torch.Tensor, np.ndarray)) else offsets)]
+    except (TypeError, ValueError):
+        raise RuntimeError(f"gmf_amd.{what}: `{name}` must be B + 1 integers") from None
+    if len(off) < 2 or off[0] != 0 or off[-1] != n_rows or any(b < a for a, b in zip(off, off[1:])):
+        raise RuntimeError(f"gmf_amd.{what}: `{name}` must ascend from 0 to the row count {n_rows} (got {off})")
+    return off
+
+
+def _dev_i32(off, device):
+    return off if isinstance(off, torch.Tensor) else torch.tensor(off, dtype=torch.int32, device=device)
+
+
+def matching_indices_batched(xyz0, off0, xyz1, off1, T, radius):
+    """The ground-truth pairs of B registration problems on the device: get_matching_indices(source, target, trans,
+    search_voxel_size, K=None) (util/pointcloud.py:83-96) for every pair of a batch, by brute force.
+
+    xyz0 [sum N0, 3], xyz1 [sum N1, 3] float32 on the device; off0 / off1: B + 1 ascending row offsets (a sequence, or an int32
+    device tensor); T [B, 4, 4] (used as float64) with T xyz0 ~ xyz1; radius > 0.
+    Returns (pairs [K, 2] int64, pair_offsets [B + 1] int64), both on the device: pair b owns pairs[pair_offsets[b] :
+    pair_offsets[b + 1]], rows (i, j) local to the pair.
+
+    (i, j) is in when d2 < radius * radius (the product in float64; a pair at exactly `radius` is outside), with, in float64
+    from the float32 coordinates and every operation rounded on its own,
+        p  = ((T[b, r, 0] * x + T[b, r, 1] * y) + T[b, r, 2] * z) + T[b, r, 3]          for r = 0, 1, 2
+        d2 = ((p0 - q0) * (p0 - q0) + (p1 - q1) * (p1 - q1)) + (p2 - q2) * (p2 - q2)
+    Order: by i, then by j ascending.  open3d's search_radius_vector_3d orders each row's neighbours by distance; the labels only
+    use set membership, so this order is a definition of this function, not parity.  One host read (K)."""
+    what = "matching_indices_batched"
+    for name, x in (("xyz0", xyz0), ("xyz1", xyz1)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 3 or x.shape[0] == 0:
+            raise RuntimeError(f"gmf_amd.{what}: `{name}` must be a non-empty float32 [rows, 3] tensor")
+    o0 = _offsets_list(off0, xyz0.shape[0], "off0", what)
+    o1 = _offsets_list(off1, xyz1.shape[0], "off1", what)
+    B = (o0.numel() if isinstance(o0, torch.Tensor) else len(o0)) - 1
+    if (o1.numel() if isinstance(o1, torch.Tensor) else len(o1)) - 1 != B:
+        raise RuntimeError(f"gmf_amd.{what}: off0 and off1 describe different numbers of pairs")
+    T = torch.as_tensor(T)
+    if tuple(T.shape) != (B, 4, 4):
+        raise RuntimeError(f"gmf_amd.{what}: T must be [{B}, 4, 4] (got {tuple(T.shape)})")
+    r = float(radius)
+    if not (r > 0 and np.isfinite(r)):
+        raise RuntimeError(f"gmf_amd.{what}: radius must be > 0 and finite (got {radius})")
+    if not xyz0.is_cuda or xyz1.device != xyz0.device:
+        raise RuntimeError(f"gmf_amd.{what}: xyz0 and xyz1 must live on one HIP device; there is no CPU fallback")
+    dev = xyz0.device
+    xyz0, xyz1 = xyz0.contiguous(), xyz1.contiguous()
+    d0, d1 = _dev_i32(o0, dev), _dev_i32(o1, dev)
+    Td = T.to(dev, torch.float64).contiguous()
+    n0, n1 = xyz0.shape[0], xyz1.shape[0]
+    row_start = torch.empty(n0 + 1, device=dev, dtype=torch.int64)
+    pair_offsets = torch.empty(B + 1, device=dev, dtype=torch.int64)
+    num = ctypes.c_longlong(0)
+    h, st = handle_and_stream(xyz0)
+    h.call("gmf_matching_indices_count", xyz0.data_ptr(), d0.data_ptr(), xyz1.data_ptr(), d1.data_ptr(), B, n0, n1, Td.data_ptr(), r,
+           row_start.data_ptr(), pair_offsets.data_ptr(), ctypes.byref(num), st)
+    pairs = torch.empty((num.value, 2), device=dev, dtype=torch.int64)
+    if num.value:
+        h.call("gmf_matching_indices_fill", xyz0.data_ptr(), d0.data_ptr(), xyz1.data_ptr(), d1.data_ptr(), B, n0, n1, Td.data_ptr(),
+               r, row_start.data_ptr(), pairs.data_ptr(), st)
+    return pairs, pair_offsets
+
+
+def _is_packed(pos_pairs):
+    return (isinstance(pos_pairs, tuple) and len(pos_pairs) == 2 and isinstance(pos_pairs[0], torch.Tensor)
+            and pos_pairs[0].dim() == 2 and isinstance(pos_pairs[1], torch.Tensor) and pos_pairs[1].dim() == 1)
+
+
+def _num_pos(pos_pairs):
+    return pos_pairs[1].numel() - 1 if _is_packed(pos_pairs) else len(pos_pairs)
+
+
+def _label_seeds(n_pairs, hash_seed, len_batch, what):
+    """The asserts of core/correspondence.py:30-32 as RuntimeError, and each pair's hash seed."""
+    if hash_seed is None:
+        if len_batch is None or len(len_batch) != n_pairs:
+            raise RuntimeError(f"gmf_amd.{what}: without hash_seed, len_batch must have one (N0, N1) per pair")
+        return [max(int(a), int(b)) for a, b in len_batch]
+    return [int(hash_seed)] * n_pairs
+
+
+def _positive_keys(pos_pairs, seeds, dev, what):
+    """-> (keys [K] int64 sorted inside each pair's range, pos_off [B + 1] int64, seeds [B] int64), all on `dev`; no host read."""
+    B = len(seeds)
+    seeds_d = torch.tensor(seeds, dtype=torch.int64, device=dev)
+    if _is_packed(pos_pairs):
+        pos = pos_pairs[0].to(dev, torch.int64)
+        pos_off = pos_pairs[1].to(dev, torch.int64).contiguous()
+        seg = torch.searchsorted(pos_off[1:].contiguous(), torch.arange(pos.shape[0], device=dev), right=True)
+    else:
+        parts = []
+        for p in pos_pairs:
+            p = torch.as_tensor(p)
+            if p.dtype.is_floating_point or p.dtype == torch.bool or (p.numel() and (p.dim() != 2 or p.shape[1] != 2)):
+                raise RuntimeError(f"gmf_amd.{what}: every pos_pairs entry must be an integer [K, 2] tensor")
+            parts.append(p.reshape(-1, 2).to(dev, torch.int64))
+        counts = [int(p.shape[0]) for p in parts]
+        pos = torch.cat(parts) if parts else torch.empty((0, 2), dtype=torch.int64, device=dev)
+        pos_off = torch.tensor(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), device=dev)
+        seg = torch.repeat_interleave(torch.arange(B, device=dev), torch.tensor(counts, device=dev), output_size=pos.shape[0])
+    if pos.dim() != 2 or pos.shape[1] != 2:
+        raise RuntimeError(f"gmf_amd.{what}: the packed pos_pairs must be [K, 2]")
+    keys = pos[:, 0] + pos[:, 1] * seeds_d[seg.clamp(max=B - 1)]          # core/correspondence.py:14-26, int64
+    # sorted inside each pair's range: by key, then stably by pair (the ranges are contiguous already, so they keep their place)
+    keys, order = torch.sort(keys, stable=True)
+    keys = keys[torch.sort(seg[order], stable=True)[1]]
+    return keys.contiguous(), pos_off, seeds_d
+
+
+def find_correct_correspondence(pos_pairs, pred_pairs, hash_seed=None, len_batch=None):
+    """DGR find_correct_correspondence (core/correspondence.py:29-53) on the device: for every predicted pair whether it is among
+    its batch entry's positive pairs -> bool tensor [sum n_b] on the device (the reference returns a numpy array).
+
+    pred_pairs: per batch entry an integer [n_b, 2] device tensor.  pos_pairs: per entry an integer [K_b, 2] tensor, on the CPU or
+    the device, or the packed (pairs, pair_offsets) of `matching_indices_batched`.  The test is the reference's: membership of the
+    key p[:, 0] + p[:, 1] * seed (int64) with seed = max(N0, N1) of the entry (len_batch) unless hash_seed is given - a seed that
+    is too small collides exactly as the reference does.  Its asserts are RuntimeError here.  The positive keys are sorted with
+    torch.sort and looked up by one kernel launch for the batch; no host read."""
+    what = "find_correct_correspondence"
+    B = len(pred_pairs)
+    if _num_pos(pos_pairs) != B:
+        raise RuntimeError(f"gmf_amd.{what}: {_num_pos(pos_pairs)} pos_pairs entries for {B} pred_pairs entries")
+    seeds = _label_seeds(B, hash_seed, len_batch, what)
+    if B == 0:
+        raise RuntimeError(f"gmf_amd.{what}: empty batch")
+    for p in pred_pairs:
+        if not isinstance(p, torch.Tensor) or p.dim() != 2 or p.shape[1] != 2 or p.dtype.is_floating_point:
+            raise RuntimeError(f"gmf_amd.{what}: every pred_pairs entry must be an integer [n, 2] tensor")
+        if not p.is_cuda:
+            raise RuntimeError(f"gmf_amd.{what}: pred_pairs must live on a HIP device; there is no CPU fallback")
+    dev = pred_pairs[0].device
+    pred = torch.cat([p.to(torch.int64) for p in pred_pairs]).contiguous()
+    M = pred.shape[0]
+    labels = torch.empty(M, device=dev, dtype=torch.uint8)
+    if M == 0:
+        return labels.bool()
+    off = np.concatenate([[0], np.cumsum([int(p.shape[0]) for p in pred_pairs])])
+    off_d = torch.tensor(off.astype(np.int32), device=dev)
+    keys, pos_off, seeds_d = _positive_keys(pos_pairs, seeds, dev, what)
+    h, st = handle_and_stream(pred)
+    h.call("gmf_inlier_input", None, pred.data_ptr(), off_d.data_ptr(), None, B, M, None, None, None, None, 0, None, None, 0, None,
+           keys.data_ptr(), pos_off.data_ptr(), seeds_d.data_ptr(), labels.data_ptr(), st)
+    return labels.bool()
+
+
+def _packed_points(xyz, n_rows, name, what):
+    if isinstance(xyz, (list, tuple)):
+        xyz = torch.cat([torch.as_tensor(x) for x in xyz], 0)
+    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] != n_rows:
+        raise RuntimeError(f"gmf_amd.{what}: `{name}` must hold {n_rows} points [*, 3] (a tensor, or a list with one tensor per pair)")
+    return xyz
+
+
+def generate_inlier_input(feat_model, xyz0, xyz1, iC0, iC1, iF0, iF1, len_batch, pos_pairs, *, inlier_feature_type, nn_max_n=-1,
+                          knn=1):
+    """WeightedProcrustesTrainer.generate_inlier_input (core/trainer.py:644-678) on the device.
+
+    feat_model: the FCGF network (`gmf_amd.fcgf.ResUNetBN2C`, in eval mode); iC0 / iC1 [sum N, 4] integer rows (batch, x, y, z) of
+    the B source / target clouds, iF0 / iF1 their input features; len_batch: B entries (N0, N1); xyz0 / xyz1: the points, one
+    tensor per pair or packed (read for 'coords' only); pos_pairs as `find_correct_correspondence` takes them, or None.
+    Returns (reg_coords [M, 7] int32, reg_feats [M, c] float32, pred_pairs, is_correct), all on the device: the inlier network's
+    input rows cat(iC0[ind0], iC1[ind1, 1:]) and features over the predicted pairs of the batch (M = sum N0), the per-pair
+    [N0, 2] int64 pairs of `find_pairs`, and the labels (None when pos_pairs is None) - what `train.resunet_train` and
+    `inlier_training_loss` take.  inlier_feature_type: 'ones' (c = 1), 'feats' (both descriptors, c = 2 x the FCGF width) or
+    'coords' (the cos of the two points, c = 6; evaluated in float64 and rounded to float32, within an ulp of torch.cos); 'counts'
+    and anything else raise ValueError, as the reference does.  FCGF runs under no_grad, one call per side with all B clouds in
+    one plan; then three launches match the batch and one writes rows, features, pairs and labels."""
+    what = "generate_inlier_input"
+    if inlier_feature_type not in INLIER_FEATURE_TYPES:
+        raise ValueError("Inlier feature type not defined")
+    if knn != 1:
+        raise NotImplementedError(f"gmf_amd.{what}: GMF-DGR only uses knn = 1 (deep_global_registration.py:300)")
+    for name, c in (("iC0", iC0), ("iC1", iC1)):
+        if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != 4 or c.dtype.is_floating_point:
+            raise RuntimeError(f"gmf_amd.{what}: `{name}` must be an integer [N, 4] tensor (batch, x, y, z)")
+    off0, off1 = _batch_offsets(len_batch, iC0.shape[0], iC1.shape[0], what)
+    B = len(off0) - 1
+    if pos_pairs is not None:
+        if _num_pos(pos_pairs) != B:
+            raise RuntimeError(f"gmf_amd.{what}: {_num_pos(pos_pairs)} pos_pairs entries for {B} pairs")
+        seeds = _label_seeds(B, None, len_batch, what)
+    ftype = INLIER_FEATURE_TYPES.index(inlier_feature_type)
+    if ftype == 2:
+        xyz0 = _packed_points(xyz0, iC0.shape[0], "xyz0", what)
+        xyz1 = _packed_points(xyz1, iC1.shape[0], "xyz1", what)
+    dev = next(feat_model.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError(f"gmf_amd.{what}: feat_model must live on a HIP device; there is no CPU fallback")
+    iC0 = iC0.to(dev, torch.int32).contiguous()
+    iC1 = iC1.to(dev, torch.int32).contiguous()
+    with torch.no_grad():
+        oF0 = feat_model(iC0, iF0.to(dev))
+        oF1 = feat_model(iC1, iF1.to(dev))
+        idx32, _, _, _ = _match_batched(oF0, oF1, len_batch, 1 if nn_max_n > 1 else 2, False, what)
+    M = off0[-1]
+    a0 = a1 = None
+    width = 1
+    if ftype == 1:
+        a0, a1, width = oF0.contiguous(), oF1.contiguous(), 2 * oF0.shape[1]
+        if oF0.shape[1] > 64:
+            raise NotImplementedError(f"gmf_amd.{what}: 'feats' takes descriptors up to 64 wide (got {oF0.shape[1]})")
+    elif ftype == 2:
+        a0, a1, width = xyz0.to(dev, torch.float32).contiguous(), xyz1.to(dev, torch.float32).contiguous(), 6
+    reg_coords = torch.empty((M, 7), device=dev, dtype=torch.int32)
+    reg_feats = torch.empty((M, width), device=dev, dtype=torch.float32)
+    pred = torch.empty((M, 2), device=dev, dtype=torch.int64)
+    labels = keys = pos_off = seeds_d = None
+    if pos_pairs is not None:
+        labels = torch.empty(M, device=dev, dtype=torch.uint8)
+        keys, pos_off, seeds_d = _positive_keys(pos_pairs, seeds, dev, what)
+    if M:
+        p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+        d0, d1 = _dev_i32(off0, dev), _dev_i32(off1, dev)
+        h, st = handle_and_stream(idx32)
+        h.call("gmf_inlier_input", idx32.data_ptr(), None, d0.data_ptr(), d1.data_ptr(), B, M, pred.data_ptr(), iC0.data_ptr(),
+               iC1.data_ptr(), reg_coords.data_ptr(), ftype, p(a0), p(a1), oF0.shape[1] if ftype == 1 else 0, reg_feats.data_ptr(),
+               p(keys), p(pos_off), p(seeds_d), p(labels), st)
+    pred_pairs = [pred[a:b] for a, b in zip(off0, off0[1:])]
+    return reg_coords, reg_feats, pred_pairs, None if labels is None else labels.bool()

@@ -420,6 +420,45 @@ int gmf_knn_from_distances(gmf_handle* h, const float* dist, int B, int N, int S
 int gmf_nn_match(gmf_handle* h, const float* F0, const float* F1, int N0, int N1, int d, int mode, int* idx_out,
                  float* dist_out, gmf_stream_t stream);
 
+/* gmf_nn_match for B ragged pairs in three launches, whatever B (DGR find_knn_gpu_batch, core/knn.py:106-140).  off0 / off1: HOST
+ * arrays of B + 1 ascending row offsets from 0 - pair b matches rows [off0[b], off0[b+1]) of F0 against rows [off1[b], off1[b+1])
+ * of F1.  idx_out [off0[B]] int32 is local to the pair, or, with global_index != 0, a row of F1 (+ off1[b], the reference's
+ * concat_results); dist_out [off0[B]].  Indices and distances are bit for bit those of B gmf_nn_match calls on the slices (first
+ * index among equal scores; a NaN query row gives local index 0 and distance NaN).  A pair without query rows contributes
+ * nothing; a pair with query rows and no key rows is GMF_ERR_UNSUPPORTED_SHAPE, as are B = 0 and d > 128; offsets that do not
+ * ascend are GMF_ERR_BAD_ARG.  No host synchronisation. */
+int gmf_nn_match_batched(gmf_handle* h, const float* F0, const float* F1, const int* off0, const int* off1, int B, int d, int mode,
+                         int global_index, int* idx_out, float* dist_out, gmf_stream_t stream);
+
+/* The ground-truth pairs of B registration problems (DGR get_matching_indices, util/pointcloud.py:83-96, by brute force): every
+ * (i, j), local to pair b, with |R_b x0_i + t_b - x1_j|^2 < radius^2, ordered by i, then j.  xyz0 [total0, 3], xyz1 [total1, 3] fp32;
+ * off0 / off1 [B + 1] int32 DEVICE offsets (ascending from 0 to the totals); T [B, 4, 4] fp64 row-major (device).  In fp64:
+ * p = ((T00 x + T01 y) + T02 z) + T03 (rows 1, 2 likewise), d2 = ((px - qx)^2 + (py - qy)^2) + (pz - qz)^2, every operation
+ * rounded on its own; a pair at exactly `radius` is outside.
+ * _count: row_start [total0 + 1] int64 (the first pair of each source row; the caller keeps it for _fill), pair_offsets [B + 1]
+ * int64, *num_pairs (host) = K.  Synchronises the stream once (K).  _fill: pairs [K, 2] int64.  One launch per pass for the batch. */
+int gmf_matching_indices_count(gmf_handle* h, const float* xyz0, const int* off0, const float* xyz1, const int* off1, int B,
+                               long long total0, long long total1, const double* T, double radius, long long* row_start,
+                               long long* pair_offsets, long long* num_pairs, gmf_stream_t stream);
+int gmf_matching_indices_fill(gmf_handle* h, const float* xyz0, const int* off0, const float* xyz1, const int* off1, int B,
+                              long long total0, long long total1, const double* T, double radius, const long long* row_start,
+                              long long* pairs, gmf_stream_t stream);
+
+/* The batched input of DGR's inlier network in one launch (core/trainer.py:616-678, core/correspondence.py:29-53), M predicted
+ * pairs in all, pair b owning rows [off0[b], off0[b+1]) of them (off0 / off1 [B + 1] int32, device).  The pairs come as `nn` [M]
+ * int32 - row m is source row m of the packed source tensors, its match nn[m] local to the pair's target rows (gmf_nn_match_batched
+ * without global_index); pred_out [M, 2] int64 then receives (m - off0[b], nn[m]) - or as `pred` [M, 2] int64 (labels only).
+ * Rows (coords_out non-NULL, needs `nn`): coords_out [M, 7] int32 = (coords0[m], coords1[off1[b] + nn[m], 1:]) from coords0 /
+ * coords1 [*, 4] int32, and feats_out by feat_type: 0 ones [M, 1]; 1 [M, 2 c] = (a0[m], a1[off1[b] + nn[m]]), a0 / a1 [*, c]
+ * descriptors, c <= 64; 2 [M, 6] = the cos of the two points, a0 / a1 [*, 3], computed in fp64 and rounded to fp32.
+ * Labels (labels_out non-NULL): labels_out [M] 0 / 1 = whether i + j seeds[b] (int64, wrapping) is among pos_keys[pos_off[b] ..
+ * pos_off[b+1]), which must be sorted inside each pair's range (pos_off [B + 1], seeds [B] int64, device).  No workspace, no host
+ * synchronisation. */
+int gmf_inlier_input(gmf_handle* h, const int* nn, const long long* pred, const int* off0, const int* off1, int B, long long M,
+                     long long* pred_out, const int* coords0, const int* coords1, int* coords_out, int feat_type, const float* a0,
+                     const float* a1, int c, float* feats_out, const long long* pos_keys, const long long* pos_off,
+                     const long long* seeds, unsigned char* labels_out, gmf_stream_t stream);
+
 /* rigid_transform_3d(A, B, weights, weight_threshold) (models/common.py:10-50):
  * A,B [n,k,3], weights [n,k] or NULL -> T [n,4,4].  The 3x3 SVD runs on the device. */
 int gmf_procrustes_batched(gmf_handle* h, const float* A, const float* B, const float* weights, int n, int k,
