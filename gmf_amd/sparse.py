@@ -172,41 +172,25 @@ def _f32_dev(t, name, what):
     return t.contiguous()
 
 
-def sparse_conv(plan: SparsePlan, map_index, out_level: int, xa, W, xb=None, scale=None, shift=None, residual=None,
-                relu: bool = False, nsplit: int = 1, out=None):
-    """One sparse convolution over kernel map `map_index` of `plan` (None: the identity map, k = 1) into level `out_level`.
+def _ptr(t):
+    return None if t is None else t.data_ptr()
 
-    xa [M, ca] (and xb [M, cb]: the input is [xa | xb]) hold the input level's rows; W is MinkowskiEngine's `kernel`,
-    [K, ca + cb, cout] (or [ca + cb, cout] when K = 1).  y = v * scale + shift (one fma; absent: 1 / 0), + residual [M, cout],
-    then ReLU if `relu`.  Returns out [M, cout]; only the first counts[out_level] rows are written.  `out` must not overlap any
-    input (other workgroups would read rows it has already overwritten).  nsplit (1..K; 1 for the identity map) cuts the
-    offsets into fixed slices that run on separate workgroups: it changes how the sum is grouped, so keep it fixed per layer
-    for bitwise-equal results."""
-    what = "sparse_conv"
-    xa = _f32_dev(xa, "xa", what)
-    W = _f32_dev(W, "W", what)
-    M = plan.M
+
+def _check_sources(xa, xb, M, what):
+    """The two-source input [xa | xb] of a convolution, xa already through `_f32_dev`: (xb or None, ca, cb)."""
     if xa.dim() != 2 or xa.shape[0] != M:
         _fail(what, f"`xa` must be [M = {M}, ca] (got {tuple(xa.shape)})")
-    ca, cb = xa.shape[1], 0
-    if xb is not None:
-        xb = _f32_dev(xb, "xb", what)
-        if xb.dim() != 2 or xb.shape[0] != M:
-            _fail(what, f"`xb` must be [M = {M}, cb] (got {tuple(xb.shape)})")
-        cb = xb.shape[1]
-    if map_index is None:
-        K, rp, pairs, by_off, off_start = 1, None, None, None, None
-    else:
-        K = plan.K[map_index]
-        if plan.maps[map_index][1] != out_level:
-            _fail(what, f"map {map_index} writes level {plan.maps[map_index][1]}, not {out_level}")
-        rp, pairs = plan.kernel_map(map_index)
-        by_off, off_start = plan.offset_lists(map_index)
-    if W.dim() == 2 and K == 1:
-        W = W.unsqueeze(0)
-    if W.dim() != 3 or W.shape[0] != K or W.shape[1] != ca + cb:
-        _fail(what, f"`W` must be [K = {K}, Cin = {ca + cb}, Cout] (got {tuple(W.shape)})")
-    cout = W.shape[2]
+    if xb is None:
+        return None, xa.shape[1], 0
+    xb = _f32_dev(xb, "xb", what)
+    if xb.dim() != 2 or xb.shape[0] != M:
+        _fail(what, f"`xb` must be [M = {M}, cb] (got {tuple(xb.shape)})")
+    return xb, xa.shape[1], xb.shape[1]
+
+
+def _check_epilogue(scale, shift, residual, M, cout, what):
+    """[scale, shift, residual] of a convolution's fused epilogue, each None or checked: scale / shift hold cout values,
+    residual is [M, cout]."""
     vecs = []
     for name, v, shape in (("scale", scale, (cout,)), ("shift", shift, (cout,)), ("residual", residual, (M, cout))):
         if v is not None:
@@ -214,21 +198,7 @@ def sparse_conv(plan: SparsePlan, map_index, out_level: int, xa, W, xb=None, sca
             if tuple(v.shape) != shape and not (name != "residual" and v.numel() == cout):
                 _fail(what, f"`{name}` must be {list(shape)} (got {tuple(v.shape)})")
         vecs.append(v)
-    if not (1 <= int(nsplit) <= K):
-        _fail(what, f"nsplit must be in 1..K = {K}")
-    if out is None:
-        out = torch.empty((M, cout), dtype=torch.float32, device=xa.device)
-    elif out.shape != (M, cout) or out.dtype != torch.float32 or not out.is_contiguous():
-        _fail(what, f"`out` must be a contiguous float32 [{M}, {cout}] tensor")
-    else:
-        for name, t in (("xa", xa), ("xb", xb), ("W", W), ("scale", vecs[0]), ("shift", vecs[1]), ("residual", vecs[2])):
-            if t is not None and _overlap(out, t):
-                _fail(what, f"`out` overlaps `{name}`: the convolution cannot run in place")
-    h, st = handle_and_stream(xa)
-    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    h.call("gmf_sparse_conv", p(rp), p(pairs), p(by_off), p(off_start), K, plan.count_ptr(out_level), M, xa.data_ptr(), ca,
-           p(xb), cb, W.data_ptr(), cout, p(vecs[0]), p(vecs[1]), p(vecs[2]), 1 if relu else 0, int(nsplit), out.data_ptr(), st)
-    return out
+    return vecs
 
 
 def _check_out(out, M, cout, inputs, what, device):
@@ -252,6 +222,39 @@ def _map_arrays(plan, map_index, out_level, what):
     return plan.K[map_index], rp, pairs, by_off, off_start
 
 
+def sparse_conv(plan: SparsePlan, map_index, out_level: int, xa, W, xb=None, scale=None, shift=None, residual=None,
+                relu: bool = False, nsplit: int = 1, out=None):
+    """One sparse convolution over kernel map `map_index` of `plan` (None: the identity map, k = 1) into level `out_level`.
+
+    xa [M, ca] (and xb [M, cb]: the input is [xa | xb]) hold the input level's rows; W is MinkowskiEngine's `kernel`,
+    [K, ca + cb, cout] (or [ca + cb, cout] when K = 1).  y = v * scale + shift (one fma; absent: 1 / 0), + residual [M, cout],
+    then ReLU if `relu`.  Returns out [M, cout]; only the first counts[out_level] rows are written.  `out` must not overlap any
+    input (other workgroups would read rows it has already overwritten).  nsplit (1..K; 1 for the identity map) cuts the
+    offsets into fixed slices that run on separate workgroups: it changes how the sum is grouped, so keep it fixed per layer
+    for bitwise-equal results."""
+    what = "sparse_conv"
+    xa = _f32_dev(xa, "xa", what)
+    W = _f32_dev(W, "W", what)
+    M = plan.M
+    xb, ca, cb = _check_sources(xa, xb, M, what)
+    K, rp, pairs, by_off, off_start = _map_arrays(plan, map_index, out_level, what)
+    if W.dim() == 2 and K == 1:
+        W = W.unsqueeze(0)
+    if W.dim() != 3 or W.shape[0] != K or W.shape[1] != ca + cb:
+        _fail(what, f"`W` must be [K = {K}, Cin = {ca + cb}, Cout] (got {tuple(W.shape)})")
+    cout = W.shape[2]
+    vecs = _check_epilogue(scale, shift, residual, M, cout, what)
+    if not (1 <= int(nsplit) <= K):
+        _fail(what, f"nsplit must be in 1..K = {K}")
+    out = _check_out(out, M, cout, (("xa", xa), ("xb", xb), ("W", W), ("scale", vecs[0]), ("shift", vecs[1]),
+                                    ("residual", vecs[2])), what, xa.device)
+    h, st = handle_and_stream(xa)
+    h.call("gmf_sparse_conv", _ptr(rp), _ptr(pairs), _ptr(by_off), _ptr(off_start), K, plan.count_ptr(out_level), M,
+           xa.data_ptr(), ca, _ptr(xb), cb, W.data_ptr(), cout, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), 1 if relu else 0,
+           int(nsplit), out.data_ptr(), st)
+    return out
+
+
 def sparse_conv_wgrad(plan: SparsePlan, map_index, out_level: int, xa, dy, xb=None):
     """Weight gradient of `sparse_conv` (`gmf_sparse_conv_wgrad`): dW [K, ca + cb, cout] = per offset d the sum over d's pairs
     (i -> o, o < counts[out_level]) of [xa | xb][i]^T dy[o]; exactly 0 for an offset without pairs.  Each offset's pair list is
@@ -262,19 +265,13 @@ def sparse_conv_wgrad(plan: SparsePlan, map_index, out_level: int, xa, dy, xb=No
     M = plan.M
     if xa.dim() != 2 or xa.shape[0] != M or dy.dim() != 2 or dy.shape[0] != M:
         _fail(what, f"`xa` and `dy` must be [M = {M}, C] (got {tuple(xa.shape)}, {tuple(dy.shape)})")
-    ca, cb = xa.shape[1], 0
-    if xb is not None:
-        xb = _f32_dev(xb, "xb", what)
-        if xb.dim() != 2 or xb.shape[0] != M:
-            _fail(what, f"`xb` must be [M = {M}, cb] (got {tuple(xb.shape)})")
-        cb = xb.shape[1]
+    xb, ca, cb = _check_sources(xa, xb, M, what)
     K, rp, pairs, by_off, off_start = _map_arrays(plan, map_index, out_level, what)
     cout = dy.shape[1]
     dW = torch.empty((K, ca + cb, cout), dtype=torch.float32, device=xa.device)
     h, st = handle_and_stream(xa)
-    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    h.call("gmf_sparse_conv_wgrad", p(rp), p(pairs), p(by_off), p(off_start), K, plan.count_ptr(out_level), xa.data_ptr(), ca,
-           p(xb), cb, dy.data_ptr(), cout, dW.data_ptr(), st)
+    h.call("gmf_sparse_conv_wgrad", _ptr(rp), _ptr(pairs), _ptr(by_off), _ptr(off_start), K, plan.count_ptr(out_level),
+           xa.data_ptr(), ca, _ptr(xb), cb, dy.data_ptr(), cout, dW.data_ptr(), st)
     return dW
 
 
@@ -382,20 +379,13 @@ def sparse_conv_narrow(plan: SparsePlan, map_index: int, out_level: int, x, W, s
     cout = W.shape[2]
     if not (1 <= cin <= 8 and 1 <= cout <= 64):
         _fail(what, f"Cin must be in 1..8 and Cout in 1..64 (got {cin}, {cout})", NotImplementedError)
-    vecs = []
-    for name, v, shape in (("scale", scale, (cout,)), ("shift", shift, (cout,)), ("residual", residual, (M, cout))):
-        if v is not None:
-            v = _f32_dev(v, name, what)
-            if tuple(v.shape) != shape and not (name != "residual" and v.numel() == cout):
-                _fail(what, f"`{name}` must be {list(shape)} (got {tuple(v.shape)})")
-        vecs.append(v)
+    vecs = _check_epilogue(scale, shift, residual, M, cout, what)
     out = _check_out(out, M, cout, (("x", x), ("W", W), ("scale", vecs[0]), ("shift", vecs[1]), ("residual", vecs[2])), what,
                      x.device)
     rp, pairs = plan.kernel_map(map_index)
     h, st = handle_and_stream(x)
-    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
     h.call("gmf_sparse_conv_narrow", rp.data_ptr(), pairs.data_ptr(), K, plan.count_ptr(out_level), M, x.data_ptr(), cin,
-           W.data_ptr(), cout, p(vecs[0]), p(vecs[1]), p(vecs[2]), 1 if relu else 0, out.data_ptr(), st)
+           W.data_ptr(), cout, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), 1 if relu else 0, out.data_ptr(), st)
     return out
 
 
@@ -406,14 +396,7 @@ def sparse_head_l2(plan: SparsePlan, level: int, xa, W1, W2, xb=None, bias=None,
     what = "sparse_head_l2"
     xa = _f32_dev(xa, "xa", what)
     M = plan.M
-    if xa.dim() != 2 or xa.shape[0] != M:
-        _fail(what, f"`xa` must be [M = {M}, ca] (got {tuple(xa.shape)})")
-    ca, cb = xa.shape[1], 0
-    if xb is not None:
-        xb = _f32_dev(xb, "xb", what)
-        if xb.dim() != 2 or xb.shape[0] != M:
-            _fail(what, f"`xb` must be [M = {M}, cb] (got {tuple(xb.shape)})")
-        cb = xb.shape[1]
+    xb, ca, cb = _check_sources(xa, xb, M, what)
     W1 = _f32_dev(W1, "W1", what)
     W2 = _f32_dev(W2, "W2", what)
     W1 = W1[0] if W1.dim() == 3 and W1.shape[0] == 1 else W1
@@ -433,9 +416,8 @@ def sparse_head_l2(plan: SparsePlan, level: int, xa, W1, W2, xb=None, bias=None,
     W1, W2 = W1.contiguous(), W2.contiguous()
     out = _check_out(out, M, cout, (("xa", xa), ("xb", xb), ("W1", W1), ("W2", W2), ("bias", bias)), what, xa.device)
     h, st = handle_and_stream(xa)
-    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    h.call("gmf_sparse_head_l2", plan.count_ptr(level), M, xa.data_ptr(), ca, p(xb), cb, W1.data_ptr(), hid, W2.data_ptr(), cout,
-           p(bias), 1 if normalize else 0, out.data_ptr(), st)
+    h.call("gmf_sparse_head_l2", plan.count_ptr(level), M, xa.data_ptr(), ca, _ptr(xb), cb, W1.data_ptr(), hid, W2.data_ptr(),
+           cout, _ptr(bias), 1 if normalize else 0, out.data_ptr(), st)
     return out
 
 
@@ -507,85 +489,108 @@ class _BasicBlockBN(nn.Module):          # residual_block.py:82-123 (no downsamp
         self.norm2 = _MinkowskiBatchNorm(C, momentum)
 
 
-# state_dict prefixes of the reference's image encoder that its forward never runs (resnet.py:147-152, 209-211); a strict
-# load_state_dict of a DGR checkpoint hands them in, and they are accepted and dropped
-_UNUSED_IMAGE_KEYS = ("img_encoder.backbone.layer3.", "img_encoder.backbone.layer4.", "img_encoder.backbone.fc.")
-
 # Kernel maps of one forward: (k, out level, in level).  0-3 same-stride, 4-6 downsampling, 7-9 their transposes.
 _NET_MAPS = [(3, 0, 0), (3, 1, 1), (3, 2, 2), (3, 3, 3), (3, 1, 0), (3, 2, 1), (3, 3, 2), (3, 0, 1), (3, 1, 2), (3, 2, 3)]
 
+# The 23 convolutions of the network in forward order: (conv, its norm or None, index into _NET_MAPS, output level).  This is
+# the order of kResunetLayers (csrc/gmf_api.cpp), so entry i is also entry i of `pack_resunet`'s list.  Map None is the identity
+# map (k = 1); conv1's map stands for conv1_kernel_size = 3, `_ResUNet._plan` chooses it for the others.
+TRUNK = (
+    ("conv1", "norm1", 0, 0), ("block1.conv1", "block1.norm1", 0, 0), ("block1.conv2", "block1.norm2", 0, 0),                  # 0
+    ("conv2", "norm2", 4, 1), ("block2.conv1", "block2.norm1", 1, 1), ("block2.conv2", "block2.norm2", 1, 1),                  # 3
+    ("conv3", "norm3", 5, 2), ("block3.conv1", "block3.norm1", 2, 2), ("block3.conv2", "block3.norm2", 2, 2),                  # 6
+    ("conv4", "norm4", 6, 3), ("block4.conv1", "block4.norm1", 3, 3), ("block4.conv2", "block4.norm2", 3, 3),                  # 9
+    ("conv4_tr", "norm4_tr", 9, 2), ("block4_tr.conv1", "block4_tr.norm1", 2, 2), ("block4_tr.conv2", "block4_tr.norm2", 2, 2),   # 12
+    ("conv3_tr", "norm3_tr", 8, 1), ("block3_tr.conv1", "block3_tr.norm1", 1, 1), ("block3_tr.conv2", "block3_tr.norm2", 1, 1),   # 15
+    ("conv2_tr", "norm2_tr", 7, 0), ("block2_tr.conv1", "block2_tr.norm1", 0, 0), ("block2_tr.conv2", "block2_tr.norm2", 0, 0),   # 18
+    ("conv1_tr", None, None, 0), ("final", None, None, 0))                                                                     # 21
+CONV1_TR, FINAL = 21, 22
 
-class ResUNetBN2C(nn.Module):
-    """DGR's inlier network (resunet_new.py:424-721 with ResUNetBN2C's channels), eval-mode forward on the device.
 
-    forward(coords [M, 1 + D] int32, feats [M, in_channels] float32, p_image, q_image [1, 3, H, W]) -> [M, out_channels],
-    aligned with the input rows.  p_tokens / q_tokens [1, T, 128] may replace the images (the image encoder's output, as in
-    `PointDSC`).  The image pair has batch size 1 and the bottleneck's queries are all stride-8 rows as one sequence
-    (resunet_new.py:694-701), in ascending (batch, coordinates) order: with pe=True the position encoding runs along that order
-    (MinkowskiEngine's order there depends on its hash, so ours is a definition, not parity)."""
+def resunet_trunk(layer, x, bottleneck=None):
+    """conv1 .. block2_tr of the network (resunet_new.py:637-704, resunet.py:598-640) on level-0 features x: (out_s1_tr, out_s1),
+    the two inputs of the head (conv1_tr on their ME.cat).  `layer(i, xa, xb=None, residual=None, relu=False)` runs convolution i
+    of TRUNK on [xa | xb] with its norm, then the residual, then the ReLU; `bottleneck(out_s8)`, if given, stands between block4
+    and conv4_tr.  Each block ends in a ReLU, so the reference's MEF.relu after it is a no-op."""
+    def block(i, x):                           # residual_block.py:104-123
+        h = layer(i, x, relu=True)
+        return layer(i + 1, h, residual=x, relu=True)
+
+    s1 = block(1, layer(0, x))
+    s2 = block(4, layer(3, s1))
+    s4 = block(7, layer(6, s2))
+    s8 = block(10, layer(9, s4))
+    if bottleneck is not None:
+        s8 = bottleneck(s8)
+    t4 = block(13, layer(12, s8))
+    t2 = block(16, layer(15, t4, xb=s4))       # ME.cat(out_s4_tr, out_s4)
+    t1 = block(19, layer(18, t2, xb=s2))
+    return t1, s1
+
+
+def _folded_conv(plan, where, L, i, xa, xb=None, residual=None, relu=False, out=None):
+    """Convolution i of TRUNK in eval mode: `sparse_conv` with the folded BatchNorm of L (`pack_resunet`'s list) over the
+    (map, level) of `where` (`_ResUNet._plan`)."""
+    W, sc, sh = L[i]
+    m, lvl = where[i]
+    return sparse_conv(plan, m, lvl, xa, W, xb=xb, scale=sc, shift=sh, residual=residual, relu=relu,
+                       nsplit=layer_nsplit(W.shape[0], W.shape[1], W.shape[2]), out=out)
+
+
+class _ResUNet(nn.Module):
+    """What DGR's two ResUNetBN2C networks share (the inlier network below, FCGF in fcgf.py): the constructor checks, the modules
+    of TRUNK under the reference's names, the packed-weight cache, the input checks and the plan of one forward."""
 
     CHANNELS = [None, 32, 64, 128, 256]
     TR_CHANNELS = [None, 64, 64, 64, 128]
     REGION_TYPE = "HYPER_CUBE"
+    _MODULE = ""                 # "fcgf." in gmf_amd.fcgf: the error texts name the class by its import path
+    _NOT_PACKED = ()             # state_dict prefixes that `pack_resunet` does not read
+    _NOT_WATCHED = None          # a prefix of parameters whose changes leave the packed weights valid
 
-    def __init__(self, in_channels=3, out_channels=32, bn_momentum=0.1, conv1_kernel_size=3, normalize_feature=False, D=3,
-                 pe=False):
+    def __init__(self, in_channels, out_channels, conv1_kernel_size, normalize_feature, D):
         super().__init__()
+        what = self._what = self._MODULE + type(self).__name__
         if self.REGION_TYPE != "HYPER_CUBE":
-            raise NotImplementedError(f"gmf_amd.{type(self).__name__}: only the hypercube kernel region is built "
-                                      f"(got {self.REGION_TYPE})")
+            _fail(what, f"only the hypercube kernel region is built (got {self.REGION_TYPE})", NotImplementedError)
         if not (1 <= int(D) <= MAX_D):
-            raise ValueError(f"gmf_amd.ResUNetBN2C: D must be in 1..{MAX_D} (got {D})")
+            _fail(what, f"D must be in 1..{MAX_D} (got {D})", ValueError)
         for k in (conv1_kernel_size, 3):
             if k % 2 == 0 or k < 1:
-                raise ValueError(f"gmf_amd.ResUNetBN2C: kernel size {k} must be odd")
+                _fail(what, f"kernel size {k} must be odd", ValueError)
             if kernel_volume(k, D) > MAX_KERNEL_VOLUME:
-                raise NotImplementedError(f"gmf_amd.ResUNetBN2C: kernel volume {k}^{D} exceeds {MAX_KERNEL_VOLUME}")
-        if normalize_feature:
-            raise NotImplementedError("gmf_amd.ResUNetBN2C: normalize_feature=True is not built (DGR's inlier network uses False)")
-        CH, TR = self.CHANNELS, self.TR_CHANNELS
-        self.D, self.pe, self.conv1_kernel_size = int(D), bool(pe), int(conv1_kernel_size)
-        self.in_channels, self.out_channels = in_channels, out_channels
-        self.normalize_feature = normalize_feature
-        m = bn_momentum
-        self.conv1 = _MinkowskiConvolution(in_channels, CH[1], conv1_kernel_size, D)
-        self.norm1 = _MinkowskiBatchNorm(CH[1], m)
-        self.block1 = _BasicBlockBN(CH[1], m, D)
-        self.conv2 = _MinkowskiConvolution(CH[1], CH[2], 3, D)
-        self.norm2 = _MinkowskiBatchNorm(CH[2], m)
-        self.block2 = _BasicBlockBN(CH[2], m, D)
-        self.conv3 = _MinkowskiConvolution(CH[2], CH[3], 3, D)
-        self.norm3 = _MinkowskiBatchNorm(CH[3], m)
-        self.block3 = _BasicBlockBN(CH[3], m, D)
-        self.conv4 = _MinkowskiConvolution(CH[3], CH[4], 3, D)
-        self.norm4 = _MinkowskiBatchNorm(CH[4], m)
-        self.perceiver_io = PerceiverIO(depth=0, dim=128, latent_dim=CH[4], cross_heads=1, latent_heads=8,
-                                        cross_dim_head=CH[4] // 2, latent_dim_head=CH[4] // 2, pe=self.pe)
-        self.block4 = _BasicBlockBN(CH[4], m, D)
-        self.conv4_tr = _MinkowskiConvolution(CH[4], TR[4], 3, D)
-        self.norm4_tr = _MinkowskiBatchNorm(TR[4], m)
-        self.block4_tr = _BasicBlockBN(TR[4], m, D)
-        self.conv3_tr = _MinkowskiConvolution(CH[3] + TR[4], TR[3], 3, D)
-        self.norm3_tr = _MinkowskiBatchNorm(TR[3], m)
-        self.block3_tr = _BasicBlockBN(TR[3], m, D)
-        self.conv2_tr = _MinkowskiConvolution(CH[2] + TR[3], TR[2], 3, D)
-        self.norm2_tr = _MinkowskiBatchNorm(TR[2], m)
-        self.block2_tr = _BasicBlockBN(TR[2], m, D)
-        self.conv1_tr = _MinkowskiConvolution(CH[1] + TR[2], TR[1], 1, D)
-        self.final = _MinkowskiConvolution(TR[1], out_channels, 1, D, bias=True)
-        self.img_encoder = ImageEncoder()
-        self.image_fusion = PerceiverIO(depth=0, dim=128, latent_dim=128, cross_heads=1, latent_heads=8, cross_dim_head=64,
-                                        latent_dim_head=64)
-        for f in (self.image_fusion, self.perceiver_io):      # fp32 throughout, as the sparse convolutions
-            f.split_fp16_ff = False
-            f.split_fp16_attn = False
+                _fail(what, f"kernel volume {k}^{D} exceeds {MAX_KERNEL_VOLUME}", NotImplementedError)
+        self.D, self.conv1_kernel_size = int(D), int(conv1_kernel_size)
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
+        self.normalize_feature = bool(normalize_feature)
         self._packed, self._packed_version = None, None
-        self._watch = WeightWatcher(self, skip_prefix="img_encoder.")
+        self._watch = WeightWatcher(self, skip_prefix=self._NOT_WATCHED)
+
+    def _build_trunk(self, bn_momentum, before_block4=None):
+        """Registers the modules of TRUNK in the reference's order (it fixes the state_dict's key order and the order of the
+        constructor's random draws); `before_block4()` registers what the reference builds between norm4 and block4."""
+        CH, TR, D = self.CHANNELS, self.TR_CHANNELS, self.D
+
+        def stage(s, cin, cout, k=3):
+            setattr(self, "conv" + s, _MinkowskiConvolution(cin, cout, k, D))
+            setattr(self, "norm" + s, _MinkowskiBatchNorm(cout, bn_momentum))
+            if s == "4" and before_block4 is not None:
+                before_block4()
+            setattr(self, "block" + s, _BasicBlockBN(cout, bn_momentum, D))
+
+        stage("1", self.in_channels, CH[1], self.conv1_kernel_size)
+        stage("2", CH[1], CH[2])
+        stage("3", CH[2], CH[3])
+        stage("4", CH[3], CH[4])
+        stage("4_tr", CH[4], TR[4])
+        stage("3_tr", CH[3] + TR[4], TR[3])
+        stage("2_tr", CH[2] + TR[3], TR[2])
+        self.conv1_tr = _MinkowskiConvolution(CH[1] + TR[2], TR[1], 1, D)
+        self.final = _MinkowskiConvolution(TR[1], self.out_channels, 1, D, bias=True)
 
     # -- weights --------------------------------------------------------------------------------------------------------------
     def load_state_dict(self, state_dict, strict=True, **kw):
-        sd = {k: v for k, v in state_dict.items() if not k.startswith(_UNUSED_IMAGE_KEYS)}
-        out = super().load_state_dict(sd, strict=strict, **kw)
+        out = super().load_state_dict(state_dict, strict=strict, **kw)
         self._watch.invalidate()
         self._packed = None
         return out
@@ -597,13 +602,80 @@ class ResUNetBN2C(nn.Module):
         return out
 
     def _weights(self, device):
-        """The 23 convolutions packed with their BatchNorms folded (`gmf_sparse_pack_resunet`), rebuilt when a weight changes."""
+        """The 23 convolutions packed with their BatchNorms folded (`gmf_sparse_pack_resunet`), rebuilt when a weight changes:
+        [(W [K, Cin, Cout], scale or None, shift or None)] in the order of TRUNK."""
         key = (self._watch.version(), torch.device(device))
         if self._packed is None or self._packed_version != key:
-            sd = {k: v for k, v in self.state_dict().items()
-                  if not k.startswith(("img_encoder.", "image_fusion.", "perceiver_io."))}
+            sd = {k: v for k, v in self.state_dict().items() if not k.startswith(self._NOT_PACKED)}
             self._packed, self._packed_version = pack_resunet(sd, device), key
         return self._packed[1]
+
+    # -- forward --------------------------------------------------------------------------------------------------------------
+    def _check_input(self, coords, feats):
+        what = self._what
+        M, D = check_coords(coords, what)
+        if D != self.D:
+            _fail(what, f"coords have D = {D}, the network was built for D = {self.D}")
+        feats = _f32_dev(feats, "feats", what)
+        if feats.dim() != 2 or feats.shape != (M, self.in_channels):
+            _fail(what, f"`feats` must be [{M}, {self.in_channels}] (got {tuple(feats.shape)})")
+        return feats
+
+    def _plan(self, coords, conv1_needs_pairs=False):
+        """(the plan of one forward, the (map index, level) of every convolution of TRUNK).  conv1 runs over map 0 for
+        conv1_kernel_size 3, over the identity map (None) for 1, and over a map (k, 0, 0) of its own, appended to the plan, for
+        any other size - and for 1 too when its kernel reads the map's pairs (`sparse_conv_narrow` has no identity form)."""
+        maps = list(_NET_MAPS)
+        k = self.conv1_kernel_size
+        if k == 3:
+            c1_map = 0
+        elif k == 1 and not conv1_needs_pairs:
+            c1_map = None
+        else:
+            c1_map = len(maps)
+            maps.append((k, 0, 0))
+        return SparsePlan(coords, 4, maps), [(c1_map, 0)] + [(m, lvl) for _, _, m, lvl in TRUNK[1:]]
+
+
+# state_dict prefixes of the reference's image encoder that its forward never runs (resnet.py:147-152, 209-211); a strict
+# load_state_dict of a DGR checkpoint hands them in, and they are accepted and dropped
+_UNUSED_IMAGE_KEYS = ("img_encoder.backbone.layer3.", "img_encoder.backbone.layer4.", "img_encoder.backbone.fc.")
+
+
+class ResUNetBN2C(_ResUNet):
+    """DGR's inlier network (resunet_new.py:424-721 with ResUNetBN2C's channels), eval-mode forward on the device.
+
+    forward(coords [M, 1 + D] int32, feats [M, in_channels] float32, p_image, q_image [1, 3, H, W]) -> [M, out_channels],
+    aligned with the input rows.  p_tokens / q_tokens [1, T, 128] may replace the images (the image encoder's output, as in
+    `PointDSC`).  The image pair has batch size 1 and the bottleneck's queries are all stride-8 rows as one sequence
+    (resunet_new.py:694-701), in ascending (batch, coordinates) order: with pe=True the position encoding runs along that order
+    (MinkowskiEngine's order there depends on its hash, so ours is a definition, not parity)."""
+
+    _NOT_PACKED = ("img_encoder.", "image_fusion.", "perceiver_io.")
+    _NOT_WATCHED = "img_encoder."
+
+    def __init__(self, in_channels=3, out_channels=32, bn_momentum=0.1, conv1_kernel_size=3, normalize_feature=False, D=3,
+                 pe=False):
+        super().__init__(in_channels, out_channels, conv1_kernel_size, normalize_feature, D)
+        if normalize_feature:
+            _fail(self._what, "normalize_feature=True is not built (DGR's inlier network uses False)", NotImplementedError)
+        self.pe = bool(pe)
+        CH = self.CHANNELS
+
+        def perceiver_io():
+            self.perceiver_io = PerceiverIO(depth=0, dim=128, latent_dim=CH[4], cross_heads=1, latent_heads=8,
+                                            cross_dim_head=CH[4] // 2, latent_dim_head=CH[4] // 2, pe=self.pe)
+        self._build_trunk(bn_momentum, before_block4=perceiver_io)
+        self.img_encoder = ImageEncoder()
+        self.image_fusion = PerceiverIO(depth=0, dim=128, latent_dim=128, cross_heads=1, latent_heads=8, cross_dim_head=64,
+                                        latent_dim_head=64)
+        for f in (self.image_fusion, self.perceiver_io):      # fp32 throughout, as the sparse convolutions
+            f.split_fp16_ff = False
+            f.split_fp16_attn = False
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        sd = {k: v for k, v in state_dict.items() if not k.startswith(_UNUSED_IMAGE_KEYS)}
+        return super().load_state_dict(sd, strict=strict, **kw)
 
     # -- forward --------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -634,47 +706,29 @@ class ResUNetBN2C(nn.Module):
             raise RuntimeError("gmf_amd.ResUNetBN2C: forward() is the eval-mode forward - call eval(); the differentiable "
                                "train-mode forward is gmf_amd.train.resunet_train(model, coords, feats, ...)")
         self._check_images(p_image, q_image, p_tokens, q_tokens)
-        M, D = check_coords(coords, "ResUNetBN2C")
-        if D != self.D:
-            raise RuntimeError(f"gmf_amd.ResUNetBN2C: coords have D = {D}, the network was built for D = {self.D}")
-        feats = _f32_dev(feats, "feats", "ResUNetBN2C")
-        if feats.dim() != 2 or feats.shape != (M, self.in_channels):
-            raise RuntimeError(f"gmf_amd.ResUNetBN2C: `feats` must be [{M}, {self.in_channels}] (got {tuple(feats.shape)})")
+        feats = self._check_input(coords, feats)
         with torch.no_grad():                     # forward-only: the image encoder takes its fused eval path too
             p_tok, q_tok = self._tokens(p_image, q_image, p_tokens, q_tokens)
             return self._forward(coords, feats, p_tok, q_tok)
 
     def _forward(self, coords, feats, p_tok, q_tok):
         L = self._weights(coords.device)
-        maps = list(_NET_MAPS)
-        c1 = self.conv1_kernel_size
-        c1_map = None if c1 == 1 else (0 if c1 == 3 else len(maps))
-        if c1 not in (1, 3):
-            maps.append((c1, 0, 0))
-        plan = SparsePlan(coords, 4, maps)
+        plan, where = self._plan(coords)
         image_feat = self.image_fusion(p_tok, queries_encoder=q_tok)       # resunet_new.py:636
 
-        def conv(i, m, lvl, xa, xb=None, residual=None, relu=False, out=None):
-            W, sc, sh = L[i]
-            return sparse_conv(plan, m, lvl, xa, W, xb=xb, scale=sc, shift=sh, residual=residual, relu=relu,
-                               nsplit=layer_nsplit(W.shape[0], W.shape[1], W.shape[2]), out=out)
+        def layer(i, xa, **kw):
+            if TRUNK[i][0] == "block4.conv2":
+                # the bottleneck's rows beyond counts[3] are zero: they pad the query sequence of the position encoding
+                # (pe=True) as Conv1d's zero padding does
+                kw["out"] = torch.zeros((plan.M, self.CHANNELS[4]), dtype=torch.float32, device=feats.device)
+            return _folded_conv(plan, where, L, i, xa, **kw)
 
-        def block(i, lvl, x, out=None):            # residual_block.py:104-123
-            h = conv(i, lvl, lvl, x, relu=True)
-            return conv(i + 1, lvl, lvl, h, residual=x, relu=True, out=out)
+        def fuse(s8):                              # resunet_new.py:694-704
+            return self.perceiver_io(image_feat, queries_encoder=s8.unsqueeze(0))[0]
 
-        s1 = block(1, 0, conv(0, c1_map, 0, feats))                   # conv1, norm1, block1 (its ReLU makes MEF.relu a no-op)
-        s2 = block(4, 1, conv(3, 4, 1, s1))
-        s4 = block(7, 2, conv(6, 5, 2, s2))
-        # the bottleneck's rows beyond counts[3] are zero: they pad the query sequence of the position encoding (pe=True) as
-        # Conv1d's zero padding does
-        s8 = block(10, 3, conv(9, 6, 3, s4), out=torch.zeros((plan.M, 256), dtype=torch.float32, device=feats.device))
-        f8 = self.perceiver_io(image_feat, queries_encoder=s8.unsqueeze(0))[0]     # resunet_new.py:694-704
-        t4 = block(13, 2, conv(12, 9, 2, f8))
-        t2 = block(16, 1, conv(15, 8, 1, t4, xb=s4))                   # ME.cat(out_s4_tr, out_s4)
-        t1 = block(19, 0, conv(18, 7, 0, t2, xb=s2))
-        o = conv(21, None, 0, t1, xb=s1, relu=True)                    # conv1_tr on ME.cat(out_s1_tr, out_s1), MEF.relu
-        return conv(22, None, 0, o)                                    # final (+ bias)
+        t1, s1 = resunet_trunk(layer, feats, bottleneck=fuse)
+        o = layer(CONV1_TR, t1, xb=s1, relu=True)                     # conv1_tr on ME.cat(out_s1_tr, out_s1), MEF.relu
+        return layer(FINAL, o)                                        # final (+ bias)
 
 
 class ResUNetBN2CX(ResUNetBN2C):

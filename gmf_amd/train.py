@@ -696,7 +696,7 @@ def resunet_train(model, coords, feats, p_image=None, q_image=None, p_tokens=Non
     bottleneck's queries all stride-8 rows in ascending (batch, coordinates) order, zero rows past the level count (the position
     encoding's zero padding for pe=True).  Reads the four level counts to the host once, to raise as torch's BatchNorm does on
     a level of fewer than 2 rows."""
-    from .sparse import SparsePlan, _NET_MAPS, check_coords, sparse_conv_train
+    from .sparse import TRUNK, check_coords, resunet_trunk, sparse_conv_train
     if not model.training:
         raise RuntimeError("gmf_amd.train.resunet_train: the model is in eval() mode - call train(), or use forward() for inference")
     if not torch.is_grad_enabled():
@@ -709,36 +709,23 @@ def resunet_train(model, coords, feats, p_image=None, q_image=None, p_tokens=Non
     if feats.shape != (M, model.in_channels):
         raise RuntimeError(f"gmf_amd.train.resunet_train: `feats` must be [{M}, {model.in_channels}] (got {tuple(feats.shape)})")
     p_tok, q_tok = model._tokens(p_image, q_image, p_tokens, q_tokens)
-    maps = list(_NET_MAPS)
-    c1 = model.conv1_kernel_size
-    c1_map = None if c1 == 1 else (0 if c1 == 3 else len(maps))
-    if c1 not in (1, 3):
-        maps.append((c1, 0, 0))
-    plan = SparsePlan(coords, 4, maps)
+    plan, where = model._plan(coords)
     counts = plan.counts.tolist()
     if min(counts) < 2:
         raise RuntimeError(f"gmf_amd.train.resunet_train: a level has fewer than 2 rows (counts {counts}); BatchNorm in training "
                            "mode needs more than 1 value per channel")
 
-    def conv(mod, m, lvl, xa, xb=None, bias=None, relu=False):
-        return sparse_conv_train(plan, m, lvl, xa, mod.kernel, xb=xb, bias=bias, relu=relu)
-
-    def bn(norm, x, lvl, residual=None, relu=False):
-        return batchnorm_masked(x, norm.bn, plan, lvl, residual=residual, relu=relu)
-
-    def block(b, lvl, x):                       # residual_block.py:104-123
-        h = bn(b.norm1, conv(b.conv1, lvl, lvl, x), lvl, relu=True)
-        return bn(b.norm2, conv(b.conv2, lvl, lvl, h), lvl, residual=x, relu=True)
+    def layer(i, xa, xb=None, residual=None, relu=False):
+        conv, norm = TRUNK[i][:2]
+        m, lvl = where[i]
+        y = sparse_conv_train(plan, m, lvl, xa, model.get_submodule(conv).kernel, xb=xb)
+        return batchnorm_masked(y, model.get_submodule(norm).bn, plan, lvl, residual=residual, relu=relu)
 
     image_feat = fusion_layer_train(model.image_fusion, p_tok, q_tok)                  # resunet_new.py:636
-    s1 = block(model.block1, 0, bn(model.norm1, conv(model.conv1, c1_map, 0, feats), 0))
-    s2 = block(model.block2, 1, bn(model.norm2, conv(model.conv2, 4, 1, s1), 1))
-    s4 = block(model.block3, 2, bn(model.norm3, conv(model.conv3, 5, 2, s2), 2))
-    s8 = block(model.block4, 3, bn(model.norm4, conv(model.conv4, 6, 3, s4), 3))     # rows past counts[3]: 0
-    f8 = fusion_layer_train(model.perceiver_io, image_feat, s8.unsqueeze(0))[0]       # resunet_new.py:694-704
-    t4 = block(model.block4_tr, 2, bn(model.norm4_tr, conv(model.conv4_tr, 9, 2, f8), 2))
-    t2 = block(model.block3_tr, 1, bn(model.norm3_tr, conv(model.conv3_tr, 8, 1, t4, xb=s4), 1))
-    t1 = block(model.block2_tr, 0, bn(model.norm2_tr, conv(model.conv2_tr, 7, 0, t2, xb=s2), 0))
-    o = conv(model.conv1_tr, None, 0, t1, xb=s1, relu=True)                          # MEF.relu(conv1_tr(ME.cat(...)))
-    return conv(model.final, None, 0, o, bias=model.final.bias)
 
+    def fuse(s8):                                # resunet_new.py:694-704; rows of s8 past counts[3] are 0
+        return fusion_layer_train(model.perceiver_io, image_feat, s8.unsqueeze(0))[0]
+
+    t1, s1 = resunet_trunk(layer, feats, bottleneck=fuse)
+    o = sparse_conv_train(plan, None, 0, t1, model.conv1_tr.kernel, xb=s1, relu=True)      # MEF.relu(conv1_tr(ME.cat(...)))
+    return sparse_conv_train(plan, None, 0, o, model.final.kernel, bias=model.final.bias)

@@ -114,6 +114,31 @@ def test_state_dict_matches_reference(pe):
     m.load_state_dict(sd, strict=True)
 
 
+def test_trunk_table_is_in_the_packed_layer_order():
+    """sparse.TRUNK names the 23 convolutions in the order of kResunetLayers (csrc/gmf_api.cpp), which is the order of
+    `pack_resunet`'s list that the forwards index, and in the order the modules are registered; every entry's map writes its
+    level."""
+    import re
+    from gmf_amd import fcgf
+    with open(os.path.join(HERE, "..", "gmf_amd", "csrc", "gmf_api.cpp")) as f:
+        src = f.read()
+    table = src[src.index("kResunetLayers[GMF_SPARSE_RESUNET_LAYERS] = {"):]
+    c_order = re.findall(r'\{"([\w.]+)", "([\w.]*)", "[\w.]*"\}', table[:table.index("};")])
+    assert len(SP.TRUNK) == len(c_order) == 23
+    assert [(conv, norm or "") for conv, norm, _, _ in SP.TRUNK] == c_order
+    assert (SP.TRUNK[SP.CONV1_TR][0], SP.TRUNK[SP.FINAL][0]) == ("conv1_tr", "final")
+    for m in (gmf_amd.ResUNetBN2C(1, 1, D=3, pe=True), fcgf.ResUNetBN2C(1, 32, conv1_kernel_size=7, D=3)):
+        keys = list(m.state_dict())
+        assert [k[:-len(".kernel")] for k in keys if k.endswith(".kernel")] == [conv for conv, _, _, _ in SP.TRUNK]
+        assert [k[:-len(".bn.weight")] for k in keys if k.endswith(".bn.weight")] == [n for _, n, _, _ in SP.TRUNK if n]
+    for conv, _, mi, lvl in SP.TRUNK:
+        assert (mi is None and lvl == 0) or SP._NET_MAPS[mi][1] == lvl, conv
+    # the strided convolutions: down over map (3, l + 1, l), up over its transpose
+    assert {c: SP._NET_MAPS[mi] for c, _, mi, _ in SP.TRUNK if mi is not None and "block" not in c} == {
+        "conv1": (3, 0, 0), "conv2": (3, 1, 0), "conv3": (3, 2, 1), "conv4": (3, 3, 2), "conv4_tr": (3, 2, 3), "conv3_tr": (3, 1, 2),
+        "conv2_tr": (3, 0, 1)}
+
+
 def test_argument_checks_without_device():
     m = gmf_amd.ResUNetBN2C(1, 1, D=6).eval()
     coords = torch.zeros((4, 7), dtype=torch.int32)

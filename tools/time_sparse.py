@@ -52,12 +52,7 @@ def demo_coords(v=0.05):
 
 
 # the convolutions of one forward: (layer index, map index or None, out level, name)
-CONVS = [(0, 0, 0, "conv1"), (1, 0, 0, "block1.conv1"), (2, 0, 0, "block1.conv2"), (3, 4, 1, "conv2"), (4, 1, 1, "block2.conv1"),
-         (5, 1, 1, "block2.conv2"), (6, 5, 2, "conv3"), (7, 2, 2, "block3.conv1"), (8, 2, 2, "block3.conv2"), (9, 6, 3, "conv4"),
-         (10, 3, 3, "block4.conv1"), (11, 3, 3, "block4.conv2"), (12, 9, 2, "conv4_tr"), (13, 2, 2, "block4_tr.conv1"),
-         (14, 2, 2, "block4_tr.conv2"), (15, 8, 1, "conv3_tr"), (16, 1, 1, "block3_tr.conv1"), (17, 1, 1, "block3_tr.conv2"),
-         (18, 7, 0, "conv2_tr"), (19, 0, 0, "block2_tr.conv1"), (20, 0, 0, "block2_tr.conv2"), (21, None, 0, "conv1_tr"),
-         (22, None, 0, "final")]
+CONVS = [(i, m, lvl, conv) for i, (conv, _, m, lvl) in enumerate(SP.TRUNK)]
 
 
 def row_groups(K, cin, cout, nsplit, cap):
