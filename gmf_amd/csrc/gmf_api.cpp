@@ -1399,6 +1399,38 @@ int gmf_icp_point_to_point(gmf_handle* h, const float* src, const int* src_offse
   return GMF_OK;
 }
 
+int gmf_icp_point_to_point_ex(gmf_handle* h, const float* src, const int* src_offsets, const float* tgt, const int* tgt_offsets,
+                              int B, long long total_src, int max_src, int max_tgt, const float* init, float tau, int max_iter,
+                              double rel_fitness, double rel_rmse, float* T_out, float* fitness, float* inlier_rmse,
+                              int* iterations, long long* nn, long long total_tgt, int search, gmf_stream_t stream) {
+  GMF_REQUIRE(h && src && src_offsets && tgt && tgt_offsets && init && T_out && fitness && inlier_rmse && iterations && nn,
+              GMF_ERR_BAD_ARG, "icp_point_to_point_ex: null pointer");
+  GMF_REQUIRE(B > 0 && total_src > 0 && total_src < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "icp_point_to_point_ex: empty batch or more than 2^31 source rows");
+  GMF_REQUIRE(total_tgt > 0 && total_tgt < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "icp_point_to_point_ex: total_tgt must be in 1..2^31 - 1");
+  GMF_REQUIRE(search == 0 || search == 1, GMF_ERR_BAD_ARG, "icp_point_to_point_ex: search must be 0 (brute force) or 1 (grid)");
+  GMF_REQUIRE(tau > 0.f && std::isfinite(tau), GMF_ERR_BAD_ARG, "icp_point_to_point_ex: max_correspondence_distance must be > 0");
+  GMF_REQUIRE(max_iter >= 0 && max_iter <= 100000, GMF_ERR_BAD_ARG, "icp_point_to_point_ex: max_iteration must be in 0..100000");
+  // the grid's table has the next power of two >= 2 total_tgt slots, and its slots and scan are indexed with int32
+  GMF_REQUIRE(search == 0 || total_tgt < (1LL << 29), GMF_ERR_UNSUPPORTED_SHAPE,
+              "icp_point_to_point_ex: the grid search takes fewer than 2^29 target rows");
+  if (search == 0)
+    return gmf_icp_point_to_point(h, src, src_offsets, tgt, tgt_offsets, B, total_src, max_src, max_tgt, init, tau, max_iter,
+                                  rel_fitness, rel_rmse, T_out, fitness, inlier_rmse, iterations, nn, stream);
+  SetDevice sd(h, stream);
+  const size_t icp = gmf::icp_scratch_bytes(total_src, B), grid = gmf::knn_scratch_bytes(total_tgt);
+  if (int rc = arena_reserve(h, icp + grid + 256)) return rc;
+  gmf::IcpScratch ws;
+  gmf::KnnScratch gs;
+  gmf::icp_scratch_carve(arena_take<char>(h, icp), total_src, B, ws);
+  gmf::knn_scratch_carve(arena_take<char>(h, grid), total_tgt, gs);
+  GMF_HIP(gmf::launch_icp(src, src_offsets, tgt, tgt_offsets, B, total_src, max_src > 0 ? max_src : (int)total_src,
+                          max_tgt > 0 ? max_tgt : (int)total_tgt, init, tau, max_iter, rel_fitness, rel_rmse, ws, T_out, fitness,
+                          inlier_rmse, iterations, nn, S(stream), &gs, total_tgt));
+  return GMF_OK;
+}
+
 int gmf_radius_knn(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double radius, int max_nn,
                    int* idx, double* d2, int* count, gmf_stream_t stream) {
   if (int rc = check_cloud_args(h, "radius_knn", pts, offsets, B, total_rows, radius, max_nn)) return rc;

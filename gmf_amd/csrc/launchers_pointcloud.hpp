@@ -25,6 +25,10 @@ struct KnnScratch {
 
 size_t knn_scratch_bytes(long long N);
 void knn_scratch_carve(void* base, long long N, KnnScratch& s);
+// The table alone, for a search of one's own (ICP's, solver_kernels.hip): one memset, k_grid_count, the scan, k_grid_scatter.
+// h: the cell edge; the slot of a row is cell_hash(its cloud, its cell) & (T - 1) (grid_hash.hpp).  Fills start and cell_pts.
+hipError_t launch_grid_build(const float* pts, const int* offsets, int B, long long N, double h, const KnnScratch& ws,
+                             hipStream_t s);
 // idx [N, max_nn] (row within its cloud, -1 padding), d2 [N, max_nn] (fp64, 0 padding; may be null), count [N].
 hipError_t launch_radius_knn(const float* pts, const int* offsets, int B, long long N, double radius, int max_nn,
                              const KnnScratch& ws, int* idx, double* d2, int* count, hipStream_t s);

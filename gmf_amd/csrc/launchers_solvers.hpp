@@ -1,9 +1,11 @@
 // Internal C++ launch entry points of the correspondence RANSAC and point-to-point ICP solvers (solver_kernels.hip).
-// Public C ABI: include/gmf_hip.h (gmf_ransac_correspondence, gmf_icp_point_to_point).
+// Public C ABI: include/gmf_hip.h (gmf_ransac_correspondence, gmf_icp_point_to_point, gmf_icp_point_to_point_ex).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "launchers_pointcloud.hpp"
 
 namespace gmf {
 
@@ -36,9 +38,11 @@ struct IcpScratch {
 
 size_t icp_scratch_bytes(long long total_src, int B);
 void icp_scratch_carve(void* base, long long total_src, int B, IcpScratch& s);
+// grid: null = the brute-force search (k_icp_nn).  Otherwise a KnnScratch carved for total_tgt rows (all targets of the batch):
+// the call builds the hashed grid over the targets first (launch_grid_build) and searches it (k_icp_nn_grid), bit-identically.
 hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, const int* tgt_off, int B, long long total_src,
                       int max_src, int max_tgt, const float* init, float tau, int max_iter, double rel_fitness, double rel_rmse,
                       const IcpScratch& ws, float* T_out, float* fitness, float* rmse, int* iterations, long long* nn,
-                      hipStream_t s);
+                      hipStream_t s, const KnnScratch* grid = nullptr, long long total_tgt = 0);
 
 }  // namespace gmf

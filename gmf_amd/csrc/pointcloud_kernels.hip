@@ -25,6 +25,7 @@
 #include <math.h>
 #include <limits.h>
 
+#include "grid_hash.hpp"
 #include "launchers_pointcloud.hpp"
 
 #pragma clang fp contract(off)
@@ -60,24 +61,6 @@ GMF_DEVINL int cloud_of(const int* __restrict__ off, int B, int i) {
     if (off[mid] <= i) lo = mid; else hi = mid - 1;
   }
   return lo;
-}
-
-GMF_DEVINL unsigned long long mix64(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-GMF_DEVINL unsigned long long cell_hash(int b, long long x, long long y, long long z) {
-  unsigned long long k = mix64((unsigned long long)x * 0x9E3779B97F4A7C15ull ^ ((unsigned long long)b << 40));
-  k = mix64(k ^ (unsigned long long)y * 0xC2B2AE3D27D4EB4Full);
-  return mix64(k ^ (unsigned long long)z * 0x165667B19E3779F9ull);
-}
-
-// search-grid cell of a coordinate (clamped so that a huge or non-finite one still gives a defined integer)
-GMF_DEVINL long long grid_coord(float p, double inv_h) {
-  const double c = fmin(fmax(floor((double)p * inv_h), -1e15), 1e15);
-  return (long long)c;
 }
 
 GMF_DEVINL double dist2(float4 c, float qx, float qy, float qz) {
@@ -676,9 +659,9 @@ void knn_scratch_carve(void* base, long long N, KnnScratch& s) {
   s.scan_tmp = p;
 }
 
-hipError_t launch_radius_knn(const float* pts, const int* offsets, int B, long long N, double radius, int max_nn,
-                             const KnnScratch& ws, int* idx, double* d2, int* count, hipStream_t s) {
-  const double inv_h = 1.0 / (radius * (1.0 + 1.0 / 1024));
+hipError_t launch_grid_build(const float* pts, const int* offsets, int B, long long N, double h, const KnnScratch& ws,
+                             hipStream_t s) {
+  const double inv_h = 1.0 / h;
   const unsigned long long tmask = (unsigned long long)ws.T - 1;
   hipError_t e = hipMemsetAsync(ws.cnt, 0, (ws.T + 1) * 4, s);
   if (e != hipSuccess) return e;
@@ -687,8 +670,16 @@ hipError_t launch_radius_knn(const float* pts, const int* offsets, int B, long l
   e = hipcub::DeviceScan::ExclusiveSum(ws.scan_tmp, sb, ws.cnt, ws.start, (int)(ws.T + 1), s);
   if (e != hipSuccess) return e;
   k_grid_scatter<<<blocks(N, kThreads), kThreads, 0, s>>>(pts, (int)N, ws.slot, ws.start, ws.cnt, ws.cell_pts);
-  k_knn_search<<<blocks(N, kWaves), kThreads, 0, s>>>(pts, offsets, B, (int)N, tmask, inv_h, radius * radius, max_nn, ws.start,
-                                                     ws.cell_pts, idx, d2, count);
+  return hipGetLastError();
+}
+
+hipError_t launch_radius_knn(const float* pts, const int* offsets, int B, long long N, double radius, int max_nn,
+                             const KnnScratch& ws, int* idx, double* d2, int* count, hipStream_t s) {
+  const double h = radius * (1.0 + 1.0 / 1024);
+  hipError_t e = launch_grid_build(pts, offsets, B, N, h, ws, s);
+  if (e != hipSuccess) return e;
+  k_knn_search<<<blocks(N, kWaves), kThreads, 0, s>>>(pts, offsets, B, (int)N, (unsigned long long)ws.T - 1, 1.0 / h,
+                                                     radius * radius, max_nn, ws.start, ws.cell_pts, idx, d2, count);
   return hipGetLastError();
 }
 

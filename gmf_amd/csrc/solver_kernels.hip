@@ -14,11 +14,16 @@
 //   k_icp_init         T = init in fp64, done = 0.
 //   k_icp_nn           exact nearest target of every transformed source row by direct fp32 differences; the targets are split
 //                      over gridDim.y and folded with a 64-bit atomicMin of (d^2 bits | target row): smallest d^2, then row.
+//   k_icp_nn_grid      the same search on a hashed grid of cell edge tau (1 + 2^-10) over the targets, built once per call
+//                      (launch_grid_build: four more launches): 32 lanes per source row, one per cell of the 3 x 3 x 3 block
+//                      around it.  The same d^2 expression and the same (d^2 bits | row) minimum, so every row whose nearest
+//                      target lies within tau gets k_icp_nn's key and the whole result is bit-identical.
 //   k_icp_step         one workgroup per pair: C, fitness, rmse, the convergence test, then Umeyama over C and T <- dT T.
 //   A finished pair's workgroups return at once.
 #include <algorithm>
 #include <math.h>
 
+#include "grid_hash.hpp"
 #include "kabsch.hpp"
 #include "launchers_solvers.hpp"
 #include "ransac_sampler.hpp"
@@ -391,6 +396,70 @@ k_icp_nn(const float* __restrict__ src, const int* __restrict__ soff, const floa
   }
 }
 
+constexpr int kGridLanes = 32;                           // lanes per source row: one per cell of the 3 x 3 x 3 block (27 used)
+constexpr int kGridRows = kThreads / kGridLanes;         // source rows per workgroup pass
+constexpr int kGridBigSlot = 32;                         // a slot with more rows than this is walked by all 32 lanes
+
+// The search of k_icp_nn restricted to the targets that can matter: a target with d^2 < tau^2 lies in one of the 27 cells (edge
+// tau (1 + 2^-10)) around the transformed source row, and among those the minimum key is k_icp_nn's.  When no target is within
+// tau the key stays ~0 or carries a d^2 >= tau^2; k_icp_step reads both as "no neighbour".  grid (B * qtiles): workgroup x takes
+// the row groups x % qtiles, + qtiles, ... of pair x / qtiles.  A lane looks up one cell's slot and walks its rows; a hash
+// collision only adds rows, which the pair test drops (a far cell of the same pair cannot win inside tau), and a slot reached
+// twice changes no minimum.  One writer per key, and k_icp_step has reset it: a plain store.
+__global__ void __launch_bounds__(kThreads)
+k_icp_nn_grid(const float* __restrict__ src, const int* __restrict__ soff, const int* __restrict__ toff, int qtiles,
+              const double* __restrict__ Tst, const int* __restrict__ done, unsigned long long tmask, double inv_h,
+              const int* __restrict__ start, const float4* __restrict__ cell_pts, unsigned long long* __restrict__ key) {
+  const int b = blockIdx.x / qtiles, tid = threadIdx.x;
+  if (done[b]) return;
+  const int g = tid & (kGridLanes - 1), half = (tid & 63) >> 5;
+  const int s0 = soff[b], ns = soff[b + 1] - s0, q0 = toff[b], q1 = toff[b + 1];
+  double T[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[e] = Tst[12 * (size_t)b + e];
+  // (every bound of this loop is uniform over the workgroup: the ballot and the shuffles below see whole waves)
+  for (int qt = blockIdx.x % qtiles; (long long)qt * kGridRows < ns; qt += qtiles) {
+    const int i = qt * kGridRows + tid / kGridLanes;
+    float p[3] = {0.f, 0.f, 0.f};
+    int a = 0, e = 0;                                    // this lane's slot holds cell_pts[a .. e)
+    if (i < ns) {
+      transform_row(T, src + 3 * (size_t)(s0 + i), p);
+      if (g < 27) {
+        const int s = (int)(cell_hash(b, grid_coord(p[0], inv_h) + g % 3 - 1, grid_coord(p[1], inv_h) + (g / 3) % 3 - 1,
+                                      grid_coord(p[2], inv_h) + g / 9 - 1) & tmask);
+        a = start[s];
+        e = start[s + 1];
+      }
+    }
+    unsigned long long best = ~0ull;
+    auto visit = [&](int pos) {
+      const float4 q = cell_pts[pos];
+      const int j = __float_as_int(q.w);
+      if (j >= q0 && j < q1) {
+        const float dx = p[0] - q.x, dy = p[1] - q.y, dz = p[2] - q.z;
+        const float d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));                      // k_icp_nn's expression, operand for operand
+        const unsigned long long c = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)(j - q0);
+        best = c < best ? c : best;
+      }
+    };
+    const bool big = e - a > kGridBigSlot;
+    if (!big)
+      for (int pos = a; pos < e; ++pos) visit(pos);
+    for (unsigned long long m = __ballot(big); m; m &= m - 1) {                    // (rare) a crowded slot: its row's 32 lanes share it
+      const int l = __builtin_ctzll(m);
+      const int a2 = __shfl(a, l), e2 = __shfl(e, l);
+      if (half == l >> 5)
+        for (int pos = a2 + g; pos < e2; pos += kGridLanes) visit(pos);
+    }
+#pragma unroll
+    for (int o = kGridLanes / 2; o > 0; o >>= 1) {
+      const unsigned long long c = __shfl_xor(best, o, kGridLanes);
+      best = c < best ? c : best;
+    }
+    if (g == 0 && i < ns && best != ~0ull) key[s0 + i] = best;
+  }
+}
+
 // pass k of the loop (k = 0: the evaluation at init): C, fitness, rmse; stop on convergence or at k == max_iter, else T <- dT T.
 // Every key is read and reset to the atomicMin identity for the next k_icp_nn.
 __global__ void __launch_bounds__(kThreads)
@@ -496,7 +565,7 @@ void icp_scratch_carve(void* base, long long total_src, int B, IcpScratch& s) {
 hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, const int* tgt_off, int B, long long total_src,
                       int max_src, int max_tgt, const float* init, float tau, int max_iter, double rel_fitness, double rel_rmse,
                       const IcpScratch& ws, float* T_out, float* fitness, float* rmse, int* iterations, long long* nn,
-                      hipStream_t s) {
+                      hipStream_t s, const KnnScratch* grid, long long total_tgt) {
   hipError_t e = hipMemsetAsync(ws.key, 0xff, (size_t)total_src * 8, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_icp_init, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, s, init, B, ws.T, ws.prev, ws.done);
@@ -505,10 +574,22 @@ hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, co
   const long long wg = (long long)stiles * B;
   const int ttiles = std::max(1, (max_tgt + kThreads - 1) / kThreads);
   const int Y = (int)std::max(1LL, std::min<long long>({(2048 + wg - 1) / wg, (long long)ttiles, 256LL}));
+  // grid search: the targets do not move, so one table serves every pass.  Cell edge tau (1 + 2^-10) in fp64: a target with
+  // fp32 d^2 < tau^2 is nearer than that edge, with room for the rounding of p / h.
+  const double h = (double)tau * (1.0 + 1.0 / 1024);
+  const int qtiles = (int)std::max<long long>(1, std::min<long long>(((long long)max_src + kGridRows - 1) / kGridRows, (1LL << 30) / B));
+  if (grid) {
+    e = launch_grid_build(tgt, tgt_off, B, total_tgt, h, *grid, s);
+    if (e != hipSuccess) return e;
+  }
   const float tau2 = tau * tau;
   for (int k = 0; k <= max_iter; ++k) {
-    hipLaunchKernelGGL(k_icp_nn, dim3((unsigned)wg, Y), dim3(kThreads), 0, s, src, src_off, tgt, tgt_off, stiles, ws.T, ws.done,
-                       ws.key);
+    if (grid)
+      hipLaunchKernelGGL(k_icp_nn_grid, dim3((unsigned)((long long)qtiles * B)), dim3(kThreads), 0, s, src, src_off, tgt_off, qtiles,
+                         ws.T, ws.done, (unsigned long long)grid->T - 1, 1.0 / h, grid->start, grid->cell_pts, ws.key);
+    else
+      hipLaunchKernelGGL(k_icp_nn, dim3((unsigned)wg, Y), dim3(kThreads), 0, s, src, src_off, tgt, tgt_off, stiles, ws.T, ws.done,
+                         ws.key);
     hipLaunchKernelGGL(k_icp_step, dim3(B), dim3(kThreads), 0, s, src, src_off, tgt, tgt_off, k, max_iter, tau2, rel_fitness,
                        rel_rmse, ws.T, ws.prev, ws.done, ws.key, T_out, fitness, rmse, iterations, nn);
   }

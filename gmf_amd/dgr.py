@@ -99,6 +99,7 @@ class DeepGlobalRegistration:
         self.clip_weight_thresh = float(_get(config, "clip_weight_thresh"))
         self.device = torch.device(device)
         self.use_icp = True
+        self.icp_search = "brute"            # registration_icp's `search`: "grid" returns the same pose (timings: DESIGN.md 4e)
         if state is None:
             state = torch.load(_get(config, "weights"), map_location="cpu", weights_only=False)
         nc = parse_network_config(state["config"])
@@ -195,8 +196,8 @@ class DeepGlobalRegistration:
         if T is None:
             T = self.safeguard_registration(xyz0, xyz1, idx0, idx1)
         if self.use_icp:
-            T = registration_icp(xyz0, xyz1, 2 * self.voxel_size, init=torch.as_tensor(T, dtype=torch.float32)
-                                 ).transformation.double().cpu().numpy()
+            T = registration_icp(xyz0, xyz1, 2 * self.voxel_size, init=torch.as_tensor(T, dtype=torch.float32),
+                                 search=self.icp_search).transformation.double().cpu().numpy()
         self.last_stats = stats
         if use_corr:
             return T, xyz0[idx0], xyz1[idx1]

@@ -18,6 +18,7 @@ from .registration import _device_offsets
 RegistrationResult = collections.namedtuple("RegistrationResult", "transformation correspondence_set fitness inlier_rmse")
 
 _MAX_HYPOTHESES = 1 << 24
+_ICP_SEARCH = {"brute": 0, "grid": 1}
 
 
 def _fail(what, msg):
@@ -119,17 +120,21 @@ def ransac_correspondence_batched(src, tgt, max_correspondence_distance, offsets
 
 
 def icp_point_to_point_batched(source, target, init, max_correspondence_distance, source_offsets=None, target_offsets=None,
-                               max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6):
+                               max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, search="brute"):
     """Point-to-point ICP over B pairs (open3d's registration_icp loop).
 
     source [B,Ns,3] / ragged [sum Ns,3] with `source_offsets`, target [B,Nt,3] / ragged with its own `target_offsets`,
     init [B,4,4] float32.  C = the exact nearest target row of each transformed source row, kept when d^2 < tau^2.  The loop
     evaluates C at init, then up to `max_iteration` times: dT = Umeyama over C, T <- dT T (fp64), the ORIGINAL source
     transformed by T, C again; it stops when |d fitness| < relative_fitness and |d rmse| < relative_rmse.  Decided on the device.
+    search: "brute" tests every target of the pair per pass; "grid" builds a hashed grid of cell edge tau over the targets once
+    and tests the 27 cells around each transformed source row.  Both return the same bits ("Evaluation solvers").
 
     Returns T [B,4,4] f32, fitness [B] (|C| / Ns), inlier_rmse [B], iterations [B] int32 (loop passes run) and nn (int64,
     source's leading shape: the matched target row within the pair, -1 outside C)."""
     what = "icp_point_to_point_batched"
+    if not isinstance(search, str) or search not in _ICP_SEARCH:
+        _fail(what, f'search must be "brute" or "grid" (got {search!r})')
     if (source_offsets is None) != (target_offsets is None):
         _fail(what, "give both source_offsets and target_offsets, or neither")
     dims = 3 if source_offsets is None else 2
@@ -178,9 +183,13 @@ def icp_point_to_point_batched(source, target, init, max_correspondence_distance
     iters = torch.empty(B, device=dev, dtype=torch.int32)
     nn = torch.empty(source.shape[:-1], device=dev, dtype=torch.int64)
     h, st = handle_and_stream(S)
-    h.call("gmf_icp_point_to_point", S.data_ptr(), dso.data_ptr(), Q.data_ptr(), dto.data_ptr(), B, ns_rows,
-           _max_rows(soff, ns_rows), _max_rows(toff, nt_rows), T0.data_ptr(), tau, it, rf, rr, T.data_ptr(), stats[0].data_ptr(),
-           stats[1].data_ptr(), iters.data_ptr(), nn.data_ptr(), st)
+    args = (S.data_ptr(), dso.data_ptr(), Q.data_ptr(), dto.data_ptr(), B, ns_rows, _max_rows(soff, ns_rows),
+            _max_rows(toff, nt_rows), T0.data_ptr(), tau, it, rf, rr, T.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
+            iters.data_ptr(), nn.data_ptr())
+    if search == "brute":
+        h.call("gmf_icp_point_to_point", *args, st)
+    else:
+        h.call("gmf_icp_point_to_point_ex", *args, nt_rows, _ICP_SEARCH[search], st)
     return T, stats[0], stats[1], iters, nn
 
 
@@ -229,11 +238,14 @@ def registration_ransac_based_on_correspondence(source, target, corres, max_corr
 
 
 def registration_icp(source, target, max_correspondence_distance, init=None, max_iteration=30, relative_fitness=1e-6,
-                     relative_rmse=1e-6):
+                     relative_rmse=1e-6, search="brute"):
     """open3d.registration.registration_icp with TransformationEstimationPointToPoint(): source [Ns,3], target [Nt,3] (tensors
-    or numpy), init [4,4] (default identity).  -> RegistrationResult(transformation [4,4] f32 on the device,
-    correspondence_set [K,2] int64 on the device (source row, nearest target row) of the final C, fitness, inlier_rmse)."""
+    or numpy), init [4,4] (default identity); search: "brute" or "grid", as in icp_point_to_point_batched.
+    -> RegistrationResult(transformation [4,4] f32 on the device, correspondence_set [K,2] int64 on the device (source row,
+    nearest target row) of the final C, fitness, inlier_rmse)."""
     what = "registration_icp"
+    if not isinstance(search, str) or search not in _ICP_SEARCH:
+        _fail(what, f'search must be "brute" or "grid" (got {search!r})')
     dev = _device_of(source, target, init)
     if dev.type != "cuda":
         _fail(what, f"the points must live on a HIP device (got {dev}); the HIP path is mandatory, there is no CPU fallback")
@@ -244,7 +256,7 @@ def registration_icp(source, target, max_correspondence_distance, init=None, max
         _fail(what, f"init must be [4,4] (got {tuple(T0.shape)})")
     T, fit, rmse, _, nn = icp_point_to_point_batched(S[None], Q[None], T0[None], max_correspondence_distance,
                                                      max_iteration=max_iteration, relative_fitness=relative_fitness,
-                                                     relative_rmse=relative_rmse)
+                                                     relative_rmse=relative_rmse, search=search)
     nn = nn[0]
     info = torch.stack([fit[0], rmse[0], (nn >= 0).sum().float()]).cpu().tolist()   # the one synchronisation
     rows = torch.nonzero_static(nn >= 0, size=int(info[2])).view(-1)

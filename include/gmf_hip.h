@@ -43,8 +43,9 @@ enum {
 };
 
 #define GMF_ABI_VERSION 5   /* 5: gmf_encoder_weights gained `pv_guard` (a caller that fills the struct itself must be rebuilt; one that uses
-                             * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  4: + gmf_get_tuning; the pose head /
-                             * pick_seeds take any N */
+                             * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  gmf_icp_point_to_point_ex joined
+                             * under 5: an added entry point, no existing signature or struct changed.  4: + gmf_get_tuning; the
+                             * pose head / pick_seeds take any N */
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
 int gmf_abi_version(void);
@@ -514,6 +515,19 @@ int gmf_icp_point_to_point(gmf_handle* h, const float* src, const int* src_offse
                            int B, long long total_src, int max_src, int max_tgt, const float* init, float tau, int max_iter,
                            double rel_fitness, double rel_rmse, float* T_out, float* fitness, float* inlier_rmse,
                            int* iterations, long long* nn, gmf_stream_t stream);
+
+/* gmf_icp_point_to_point with a choice of nearest-neighbour search.  total_tgt: all target rows of the batch
+ * (tgt_offsets[B], in 1..2^31 - 1).  search 0: the brute-force search, exactly gmf_icp_point_to_point's launches.  search 1: a
+ * hashed uniform grid of cell edge tau (1 + 2^-10) over the targets, built once per call (four more launches, scratch for
+ * total_tgt rows from the workspace), then each pass looks only at the 27 cells around a transformed source row.  The d^2
+ * expression and the (d^2, row) order are the brute-force search's, so every output is bit-identical to search 0; the work
+ * per pass falls from Ns Nt distance tests to the rows of 27 cells per source row (no gain when tau is comparable to the
+ * cloud's extent).  search 1 takes total_tgt < 2^29 (the table's slots are int32).  No host synchronisation;
+ * graph-capturable. */
+int gmf_icp_point_to_point_ex(gmf_handle* h, const float* src, const int* src_offsets, const float* tgt, const int* tgt_offsets,
+                              int B, long long total_src, int max_src, int max_tgt, const float* init, float tau, int max_iter,
+                              double rel_fitness, double rel_rmse, float* T_out, float* fitness, float* inlier_rmse,
+                              int* iterations, long long* nn, long long total_tgt, int search, gmf_stream_t stream);
 
 /* ---- point-cloud descriptors: radius kNN, normals, FPFH, voxel grids (open3d's, as the reference's feature scripts call them) -- */
 

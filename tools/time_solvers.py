@@ -4,6 +4,18 @@
   PointDSC ICP      keypoints, N = 5000 / 5000, tau = 0.10, open3d's default criteria (30 passes at most)
   DGR RANSAC        80 000 hypotheses, ransac_n = 4, N = 8000 and 30 000 correspondences, tau = 0.06
   DGR ICP           brute-force nearest neighbour, clouds of 10k / 10k and 50k / 50k points, tau = 0.05
+  ICP search        search="brute" against search="grid", alternated call by call in this one process: keypoints 5000 / 5000
+                    (tau = 0.10), clouds of 10k / 10k and 50k / 50k (tau = 0.05).  Per shape and search: the whole call at the
+                    default criteria; then, with both relative criteria at 0 so that every pass runs, the call at
+                    max_iteration = 0 (t0) and at 10 (t10).  One pass = (t10 - t0) / 10 is the search AND k_icp_step;
+                    the step is the same kernel on the same data in both columns, so the difference of the columns is the
+                    difference of the two searches.  The grid build = (t0 grid - t0 brute) + (pass brute - pass grid): the
+                    first term is the build plus the difference of one search, the second takes that difference out again.
+                    The search kernels alone (and the build's kernels one by one) are kernel times: run
+                    rocprofv3 --kernel-trace --stats -- python tools/time_solvers.py --icp-shape 50k   (one shape per
+                    process, so that the per-kernel averages belong to one size; shapes: keypoints, 10k, 50k).
+                    tools/icp_trace_passes.py picks the working passes out of such a trace.
+  ICP crossover     whole calls, brute against grid, at keypoint pairs of 125 ... 2000 rows.
 
 Device events around each call, after warm-up; median and spread over repeats.  For RANSAC the row tests per second and the share
 of the fp32 vector peak (15 vector ops per hypothesis-row test, the issue's count, at 157.3 TFLOP/s) are printed too.
@@ -38,6 +50,75 @@ def timed(fn, repeats, warmup=3):
     return statistics.median(ts), min(ts), max(ts)
 
 
+def timed_alternating(fns, repeats, warmup=3):
+    """Medians (us) of several callables timed in turn, one call each per round, so that drift hits all alike."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(repeats):
+        for k, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts[k].append(a.elapsed_time(b) * 1e3)
+    return [statistics.median(t) for t in ts]
+
+
+ICP_SHAPES = ("keypoints", "10k", "50k")
+
+
+def icp_shape(key):
+    if key == "keypoints":
+        p = synthetic.synthetic_pair(1, 5000)
+        return ("keypoints 5000/5000 tau=0.10", torch.as_tensor(p["src_keypts"])[None], torch.as_tensor(p["tgt_keypts"])[None],
+                torch.as_tensor(p["gt_trans"])[None], 0.10)
+    N = {"10k": 10000, "50k": 50000}[key]
+    s, q, T0 = cloud_pair(N, 5)
+    return (f"cloud {key}/{key} tau=0.05", torch.as_tensor(s)[None], torch.as_tensor(q)[None], torch.as_tensor(T0)[None], 0.05)
+
+
+def icp_search_rows(report, repeats, dev, keys=ICP_SHAPES):
+    """search="brute" against search="grid" (the module docstring's "ICP search")."""
+    report("ICP search: brute | grid, alternated; us, median")
+    for name, s, q, T0, tau in (icp_shape(k) for k in keys):
+        s, q, T0 = s.to(dev), q.to(dev), T0.to(dev)
+        out = {k: gmf_amd.icp_point_to_point_batched(s, q, T0, tau, search=k) for k in ("brute", "grid")}
+        same = all(torch.equal(x, y) for x, y in zip(out["brute"], out["grid"]))
+        it = int(out["brute"][3][0])
+
+        def call(search, **kw):
+            return lambda: gmf_amd.icp_point_to_point_batched(s, q, T0, tau, search=search, **kw)
+
+        every = dict(relative_fitness=0.0, relative_rmse=0.0)
+        fns = [call(k, **kw) for kw in ({}, dict(max_iteration=0, **every), dict(max_iteration=10, **every))
+               for k in ("brute", "grid")]
+        (wb, wg, b0, g0, b10, g10) = timed_alternating(fns, repeats)
+        pb, pg = (b10 - b0) / 10, (g10 - g0) / 10
+        report(f"  {name}: outputs bit-identical: {same}; {it} passes")
+        report(f"    whole call        {wb:9.1f} | {wg:9.1f}")
+        report(f"    max_iteration=0   {b0:9.1f} | {g0:9.1f}   (init, for the grid its build, one search, one evaluation)")
+        report(f"    one pass          {pb:9.1f} | {pg:9.1f}   (search + k_icp_step; the searches differ by {pb - pg:.1f})")
+        report(f"    grid build                  | {(g0 - b0) + (pb - pg):9.1f}   ((t0 grid - t0 brute) + (pass brute - pass grid))")
+
+
+def icp_crossover_rows(report, repeats, dev):
+    """Whole calls at small keypoint pairs (tau = 0.10, default criteria, gt pose as init), to find the size below which the
+    grid's four extra launches cost more than its search saves."""
+    report("ICP search, small keypoint pairs: whole call, brute | grid, alternated; us, median")
+    for N in (125, 250, 500, 1000, 2000):
+        p = synthetic.synthetic_pair(1, N)
+        s, q = torch.as_tensor(p["src_keypts"]).to(dev)[None], torch.as_tensor(p["tgt_keypts"]).to(dev)[None]
+        T0 = torch.as_tensor(p["gt_trans"]).to(dev)[None]
+        it = int(gmf_amd.icp_point_to_point_batched(s, q, T0, 0.10)[3][0])
+        fns = [lambda k=k: gmf_amd.icp_point_to_point_batched(s, q, T0, 0.10, search=k) for k in ("brute", "grid")]
+        wb, wg = timed_alternating(fns, repeats)
+        report(f"  keypoints {N}/{N} tau=0.10 ({it} passes): {wb:9.1f} | {wg:9.1f}")
+
+
 def cloud_pair(N, seed):
     r = np.random.default_rng([seed, N])
     X = r.uniform(0, 3, (N, 3))
@@ -53,6 +134,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--icp-shape", choices=ICP_SHAPES, default=None, help="only the ICP search rows of one shape (for a kernel trace)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "time_solvers.py measures on a HIP device"
     dev = "cuda:0"
@@ -63,6 +145,9 @@ def main():
         lines.append(s)
 
     report(f"device: {torch.cuda.get_device_name(0)}; median [min, max] over {a.repeats} repeats, device events")
+    if a.icp_shape:
+        icp_search_rows(report, a.repeats, dev, (a.icp_shape,))
+        return
 
     # PointDSC RANSAC
     p = synthetic.synthetic_pair(1, 5000)
@@ -101,6 +186,8 @@ def main():
         per = med / (it + 1)
         report(f"DGR ICP          N={N}/{N} tau=0.05: {med:8.1f} us [{lo:.1f}, {hi:.1f}]  ({it} passes, {per:.1f} us per "
                f"nearest-neighbour pass, {N * N / per * 1e-3:.0f} G distance tests/s)")
+    icp_search_rows(report, a.repeats, dev)
+    icp_crossover_rows(report, a.repeats, dev)
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
