@@ -1431,6 +1431,52 @@ int gmf_icp_point_to_point_ex(gmf_handle* h, const float* src, const int* src_of
   return GMF_OK;
 }
 
+int gmf_ransac_feature_matching(gmf_handle* h, const float* src, const int* src_offsets, const float* tgt, const int* tgt_offsets,
+                                const long long* nn, int B, long long total_src, long long total_tgt, int max_src, int ransac_n,
+                                int max_iteration, int max_validation, float tau, float checker_distance,
+                                float edge_length_threshold, unsigned long long seed, int first_pair, int search, float* T_out,
+                                float* fitness, float* inlier_rmse, long long* hypothesis, long long* sample, long long* nn_out,
+                                int* validated, int* hyp, int* count, long long* sum, gmf_stream_t stream) {
+  GMF_REQUIRE(h && src && src_offsets && tgt && tgt_offsets && nn && T_out && fitness && inlier_rmse && hypothesis && sample &&
+                  nn_out && validated,
+              GMF_ERR_BAD_ARG, "ransac_feature_matching: null pointer");
+  GMF_REQUIRE(B > 0 && total_src > 0 && total_src < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "ransac_feature_matching: empty batch or more than 2^31 source rows");
+  GMF_REQUIRE(total_tgt > 0 && total_tgt < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "ransac_feature_matching: total_tgt must be in 1..2^31 - 1");
+  GMF_REQUIRE(search == 0 || search == 1, GMF_ERR_BAD_ARG, "ransac_feature_matching: search must be 0 (brute force) or 1 (grid)");
+  GMF_REQUIRE(ransac_n >= 3 && ransac_n <= 8, GMF_ERR_BAD_ARG, "ransac_feature_matching: ransac_n must be in 3..8");
+  GMF_REQUIRE(max_iteration >= 1 && max_iteration <= (1 << 24), GMF_ERR_BAD_ARG,
+              "ransac_feature_matching: max_iteration must be in 1..2^24");
+  GMF_REQUIRE(max_validation >= 1 && max_validation <= 65536, GMF_ERR_BAD_ARG,
+              "ransac_feature_matching: max_validation must be in 1..65536");
+  GMF_REQUIRE(tau > 0.f && std::isfinite(tau), GMF_ERR_BAD_ARG, "ransac_feature_matching: max_correspondence_distance must be > 0");
+  GMF_REQUIRE(!std::isnan(checker_distance) && !std::isinf(checker_distance), GMF_ERR_BAD_ARG,
+              "ransac_feature_matching: checker_distance must be finite (negative: no distance checker)");
+  GMF_REQUIRE(!std::isnan(edge_length_threshold) && edge_length_threshold <= 1.f, GMF_ERR_BAD_ARG,
+              "ransac_feature_matching: edge_length_threshold must be <= 1 (<= 0: no edge-length checker)");
+  GMF_REQUIRE(first_pair >= 0, GMF_ERR_BAD_ARG, "ransac_feature_matching: first_pair must be >= 0");
+  // the grid's table has the next power of two >= 2 total_tgt slots, and its slots and scan are indexed with int32
+  GMF_REQUIRE(search == 0 || total_tgt < (1LL << 29), GMF_ERR_UNSUPPORTED_SHAPE,
+              "ransac_feature_matching: the grid search takes fewer than 2^29 target rows");
+  SetDevice sd(h, stream);
+  const size_t fm = gmf::fm_scratch_bytes(total_src, B, max_iteration, max_validation);
+  const size_t grid = search ? gmf::knn_scratch_bytes(total_tgt) : 0;
+  if (int rc = arena_reserve(h, fm + grid + 256)) return rc;
+  gmf::FmScratch ws;
+  gmf::KnnScratch gs;
+  gmf::fm_scratch_carve(arena_take<char>(h, fm), total_src, B, max_iteration, max_validation, ws);
+  if (search) gmf::knn_scratch_carve(arena_take<char>(h, grid), total_tgt, gs);
+  if (hyp) ws.hyp = hyp;
+  if (count) ws.cnt = reinterpret_cast<unsigned*>(count);
+  if (sum) ws.sq = reinterpret_cast<unsigned long long*>(sum);
+  GMF_HIP(gmf::launch_ransac_feature_matching(src, src_offsets, tgt, tgt_offsets, nn, B, total_src, total_tgt,
+                                              max_src > 0 ? max_src : (int)total_src, ransac_n, max_iteration, max_validation, tau,
+                                              checker_distance, edge_length_threshold, seed, first_pair, ws, search ? &gs : nullptr,
+                                              T_out, fitness, inlier_rmse, hypothesis, sample, nn_out, validated, S(stream)));
+  return GMF_OK;
+}
+
 int gmf_radius_knn(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double radius, int max_nn,
                    int* idx, double* d2, int* count, gmf_stream_t stream) {
   if (int rc = check_cloud_args(h, "radius_knn", pts, offsets, B, total_rows, radius, max_nn)) return rc;

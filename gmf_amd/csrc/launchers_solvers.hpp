@@ -1,5 +1,7 @@
-// Internal C++ launch entry points of the correspondence RANSAC and point-to-point ICP solvers (solver_kernels.hip).
-// Public C ABI: include/gmf_hip.h (gmf_ransac_correspondence, gmf_icp_point_to_point, gmf_icp_point_to_point_ex).
+// Internal C++ launch entry points of the correspondence RANSAC, point-to-point ICP and feature-matching RANSAC solvers
+// (solver_kernels.hip).
+// Public C ABI: include/gmf_hip.h (gmf_ransac_correspondence, gmf_icp_point_to_point, gmf_icp_point_to_point_ex,
+// gmf_ransac_feature_matching).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -44,5 +46,29 @@ hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, co
                       int max_src, int max_tgt, const float* init, float tau, int max_iter, double rel_fitness, double rel_rmse,
                       const IcpScratch& ws, float* T_out, float* fitness, float* rmse, int* iterations, long long* nn,
                       hipStream_t s, const KnnScratch* grid = nullptr, long long total_tgt = 0);
+
+// Device scratch of one feature-matching RANSAC call.  H = max_iteration, V = max_validation.
+struct FmScratch {
+  unsigned char* pass;        // [B, H rounded up to 4] 1 = hypothesis h passed the checkers (zeroed by the launcher)
+  float* thyp;                // [B * H * 12] the fp32 [R | t] of a passing hypothesis
+  int* hyp;                   // [B * V] the validated h in increasing order, -1 padded (the caller may point it at an output)
+  unsigned* cnt;              // [B * V] |C| of each validated hypothesis (likewise)
+  unsigned long long* sq;     // [B * V] sum over C of d^2 in units of tau^2 / 2^24 (likewise)
+  float* tval;                // [B * V * 12] the validated hypotheses' poses
+  int* win;                   // [B] list position of the winner, -1: none
+  unsigned long long* key;    // [total_src] the winner's packed (d^2 bits | target row) per source row
+};
+
+size_t fm_scratch_bytes(long long total_src, int B, int H, int V);
+void fm_scratch_carve(void* base, long long total_src, int B, int H, int V, FmScratch& s);
+// nn [total_src]: the feature-space nearest target row of every source row, numbered within the pair.  checker_distance < 0 and
+// edge_length <= 0 switch the checkers off.  grid: null = every target streams through LDS; otherwise a KnnScratch carved for
+// total_tgt rows, built here (launch_grid_build) and searched, bit-identically.  validated [B]: hypotheses evaluated per pair.
+hipError_t launch_ransac_feature_matching(const float* src, const int* src_off, const float* tgt, const int* tgt_off,
+                                          const long long* nn, int B, long long total_src, long long total_tgt, int max_src,
+                                          int ransac_n, int H, int V, float tau, float checker_distance, float edge_length,
+                                          uint64_t seed, int first_pair, const FmScratch& ws, const KnnScratch* grid, float* T_out,
+                                          float* fitness, float* rmse, long long* hypothesis, long long* sample, long long* nn_out,
+                                          int* validated, hipStream_t s);
 
 }  // namespace gmf

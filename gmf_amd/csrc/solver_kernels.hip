@@ -20,6 +20,16 @@
 //                      target lies within tau gets k_icp_nn's key and the whole result is bit-identical.
 //   k_icp_step         one workgroup per pair: C, fitness, rmse, the convergence test, then Umeyama over C and T <- dT T.
 //   A finished pair's workgroups return at once.
+// Feature-matching RANSAC (open3d's registration_ransac_based_on_feature_matching), three memsets, the grid build and seven
+// launches, none of which the host waits for:
+//   k_fm_propose       one lane per hypothesis: draw, pair each row with its feature-space match, edge-length test, fp64 Kabsch,
+//                      distance test on the fp32 pose.  A flag and the pose per hypothesis.
+//   k_fm_select        one workgroup per pair: the first max_validation passing hypotheses in increasing h (a prefix sum).
+//   k_fm_eval          one lane per (validated hypothesis, source row): the nearest target of the transformed row on the hashed
+//                      grid (or through an LDS tile), |C| and the fixed-point sum of d^2 per hypothesis by integer atomics; run
+//                      once more on the winner alone to leave its keys.
+//   k_fm_winner        one workgroup per pair: argmax over (count, -sum, -h).
+//   k_fm_finish        one workgroup per pair: nn, fitness, rmse (fp64 sums in a fixed tree), pose, hypothesis, sample.
 #include <algorithm>
 #include <math.h>
 
@@ -593,6 +603,402 @@ hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, co
     hipLaunchKernelGGL(k_icp_step, dim3(B), dim3(kThreads), 0, s, src, src_off, tgt, tgt_off, k, max_iter, tau2, rel_fitness,
                        rel_rmse, ws.T, ws.prev, ws.done, ws.key, T_out, fitness, rmse, iterations, nn);
   }
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Feature-matching RANSAC
+// ---------------------------------------------------------------------------------------------------------------------------
+
+// T s in fp32, and |p - q|^2: the two halves of "transform a row and take d^2".  The checker, both evaluation forms and the
+// finish see a pose only through these, with k_icp_nn's d^2 expression, so a (pose, source row, target row) gives one bit pattern
+// everywhere.
+GMF_DEVINL void fm_point(const float* T, float sx, float sy, float sz, float* p) {
+  p[0] = fmaf(T[0], sx, fmaf(T[1], sy, fmaf(T[2], sz, T[3])));
+  p[1] = fmaf(T[4], sx, fmaf(T[5], sy, fmaf(T[6], sz, T[7])));
+  p[2] = fmaf(T[8], sx, fmaf(T[9], sy, fmaf(T[10], sz, T[11])));
+}
+
+GMF_DEVINL float fm_d2(const float* p, float qx, float qy, float qz) {
+  const float dx = p[0] - qx, dy = p[1] - qy, dz = p[2] - qz;
+  return fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+}
+
+GMF_DEVINL unsigned long long fm_key(float d2, int row) {   // d2 >= 0: its bits order as unsigned integers
+  return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)row;
+}
+
+// grid (hb * B): workgroup x proposes hypotheses [256 (x % hb), +256) of pair x / hb.  pass (zeroed by the launcher) gets a 1 and
+// thyp the fp32 [R | t] where the sample survives: nn inside the pair's targets, the edge-length test, a fit, the distance test.
+template <int NS>
+__global__ void __launch_bounds__(kThreads)
+k_fm_propose(const float* __restrict__ src, const int* __restrict__ soff, const float* __restrict__ tgt,
+             const int* __restrict__ toff, const long long* __restrict__ nn, int H, long long Hs, int hb, unsigned long long seed,
+             int first_pair, double edge_r2, float cd2, unsigned char* __restrict__ pass, float* __restrict__ thyp) {
+  const int b = blockIdx.x / hb, h = (blockIdx.x % hb) * kThreads + threadIdx.x;
+  const int s0 = soff[b], ns = soff[b + 1] - s0, q0 = toff[b], nt = toff[b + 1] - q0;
+  if (ns < NS || nt <= 0 || h >= H) return;
+  int rows[NS];
+  ransac_draw<NS>(seed, (uint32_t)(first_pair + b), (uint32_t)h, (uint32_t)ns, rows);
+  float4 a[NS], q[NS];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < NS; ++k) {
+    const long long j = nn[s0 + rows[k]];
+    const bool inside = j >= 0 && j < nt;
+    ok = ok && inside;
+    const float* pa = src + 3 * (size_t)(s0 + rows[k]);
+    const float* pq = tgt + 3 * (size_t)(q0 + (inside ? (int)j : 0));
+    a[k] = make_float4(pa[0], pa[1], pa[2], 0.f);
+    q[k] = make_float4(pq[0], pq[1], pq[2], 0.f);
+  }
+  if (ok && edge_r2 > 0.0) {                             // open3d's edge-length checker on squared lengths, in fp64
+#pragma unroll
+    for (int i = 0; i < NS; ++i)
+#pragma unroll
+      for (int j = i + 1; j < NS; ++j) {
+        const double ax = (double)a[i].x - a[j].x, ay = (double)a[i].y - a[j].y, az = (double)a[i].z - a[j].z;
+        const double bx = (double)q[i].x - q[j].x, by = (double)q[i].y - q[j].y, bz = (double)q[i].z - q[j].z;
+        const double ds = ax * ax + ay * ay + az * az, dt = bx * bx + by * by + bz * bz;
+        ok = ok && ds >= edge_r2 * dt && dt >= edge_r2 * ds;
+      }
+  }
+  if (!ok) return;
+  int id[NS];
+#pragma unroll
+  for (int k = 0; k < NS; ++k) id[k] = k;
+  double Td[12];
+  if (!fit_sample<NS>(a, q, id, Td)) return;
+  float T[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[e] = (float)Td[e];
+  if (cd2 >= 0.f) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      float p[3];
+      fm_point(T, a[k].x, a[k].y, a[k].z, p);
+      ok = ok && fm_d2(p, q[k].x, q[k].y, q[k].z) <= cd2;
+    }
+    if (!ok) return;
+  }
+  pass[(size_t)b * Hs + h] = 1;
+  float* To = thyp + ((size_t)b * H + h) * 12;
+#pragma unroll
+  for (int e = 0; e < 12; ++e) To[e] = T[e];
+}
+
+// One workgroup per pair: the first V passing h in increasing order (open3d's sequential rule without its dependence on the
+// order of execution), by a prefix sum over four flags per thread.  hyp [B, V] (-1 padded), tval [B, V, 12].
+__global__ void __launch_bounds__(kThreads)
+k_fm_select(int H, long long Hs, int V, const unsigned char* __restrict__ pass, const float* __restrict__ thyp,
+            int* __restrict__ hyp, float* __restrict__ tval, int* __restrict__ validated) {
+  __shared__ int wsum[kThreads / 64];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const unsigned* pw = reinterpret_cast<const unsigned*>(pass + (size_t)b * Hs);      // Hs is a multiple of 4, the flags are 0 / 1
+  const int words = (int)(Hs / 4);
+  int* hb = hyp + (size_t)b * V;
+  int base = 0;
+  for (int w0 = 0; w0 < words && base < V; w0 += kThreads) {                           // (uniform bounds)
+    const int w = w0 + tid;
+    const unsigned word = w < words ? pw[w] : 0u;
+    const int c = __popc(word);
+    int inc = c;                                          // inclusive scan over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int up = __shfl_up(inc, o);
+      inc += lane >= o ? up : 0;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < kThreads / 64; ++k) {
+      before += k < wave ? wsum[k] : 0;
+      total += wsum[k];
+    }
+    int pos = base + before + inc - c;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if ((word >> (8 * k)) & 1u) {
+        if (pos < V) hb[pos] = 4 * w + k;
+        ++pos;
+      }
+    base += total;
+    __syncthreads();
+  }
+  const int nv = min(base, V);
+  __syncthreads();                                        // the list above is read back below
+  for (int v = tid; v < V; v += kThreads) {
+    if (v >= nv) { hb[v] = -1; continue; }
+    const float* Ti = thyp + ((size_t)b * H + hb[v]) * 12;
+    float* To = tval + ((size_t)b * V + v) * 12;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) To[e] = Ti[e];
+  }
+  if (tid == 0) validated[b] = nv;
+}
+
+struct FmGridView {
+  unsigned long long tmask;
+  double inv_h;
+  const int* start;
+  const float4* cell_pts;
+};
+
+// The evaluation: one lane per (validated hypothesis, source row); a workgroup holds 256 consecutive rows of one hypothesis, so
+// the pose is uniform over the workgroup and the source loads coalesce.  The lane finds the minimum of (d^2 bits << 32 | target row) over the
+// pair's targets: GRID walks the 27 cells around grid_coord(p) (nine slot bounds in flight at a time, then their rows), the other
+// form streams every target through an LDS tile (a broadcast read).  KEYS = false: per hypothesis |C| and the fixed-point sum of
+// d^2 over C, each wave adding its 64 rows' share by one 32-bit and one 64-bit integer atomic (integers: any split of the rows
+// and any order give the same bits).  KEYS = true: the same search for the winner alone (win[b]), storing each row's key.
+// A workgroup takes work items blockIdx.x, + gridDim.x, ...: item = ((pair, hypothesis), row tile rt0 < rtiles), and in it the
+// tiles rt0, + rtiles, ... of 256 rows; everything that selects an item or a tile (validated, win, the offsets) is uniform over
+// the workgroup, so the barriers of the LDS form are reached by all of it.
+template <bool GRID, bool KEYS>
+__global__ void __launch_bounds__(kThreads)
+k_fm_eval(const float* __restrict__ src, const int* __restrict__ soff, const float* __restrict__ tgt, const int* __restrict__ toff,
+          int B, int V, int rtiles, const int* __restrict__ validated, const int* __restrict__ win,
+          const float* __restrict__ tval, FmGridView g, float tau2, float qscale, unsigned* __restrict__ cnt,
+          unsigned long long* __restrict__ sq, unsigned long long* __restrict__ key) {
+  __shared__ float4 tile[GRID ? 1 : kThreads];
+  const int tid = threadIdx.x;
+  const long long items = (long long)B * (KEYS ? 1 : V) * rtiles;
+  for (long long w = blockIdx.x; w < items; w += gridDim.x) {
+    const int rt0 = (int)(w % rtiles);
+    const long long bv = w / rtiles;
+    const int b = (int)(KEYS ? bv : bv / V);
+    const int v = KEYS ? win[b] : (int)(bv % V);
+    if (KEYS ? v < 0 : v >= validated[b]) continue;
+    const int s0 = soff[b], ns = soff[b + 1] - s0, q0 = toff[b], q1 = toff[b + 1];
+    const size_t slot = (size_t)b * V + v;
+    float T[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) T[e] = tval[slot * 12 + e];
+    // row tiles rt0, + rtiles, ...: every row of the pair is covered whatever max_src said
+    for (int rt = rt0; (long long)rt * kThreads < ns; rt += rtiles) {
+      const int i = rt * kThreads + tid;
+      const bool active = i < ns;
+      float p[3] = {0.f, 0.f, 0.f};
+      if (active) {
+        const float* a = src + 3 * (size_t)(s0 + i);
+        fm_point(T, a[0], a[1], a[2], p);
+      }
+      unsigned long long best = ~0ull;
+      if (GRID) {
+        if (active) {
+          const long long cx = grid_coord(p[0], g.inv_h), cy = grid_coord(p[1], g.inv_h), cz = grid_coord(p[2], g.inv_h);
+#pragma unroll 1
+          for (int ox = -1; ox <= 1; ++ox) {
+            const unsigned long long kx = cell_hash_x(b, cx + ox);
+            int lo[9], hi[9];
+#pragma unroll
+            for (int c = 0; c < 9; ++c) {
+              const int s = (int)(cell_hash_z(cell_hash_y(kx, cy + c / 3 - 1), cz + c % 3 - 1) & g.tmask);
+              lo[c] = g.start[s];
+              hi[c] = g.start[s + 1];
+            }
+#pragma unroll
+            for (int c = 0; c < 9; ++c)
+              for (int pos = lo[c]; pos < hi[c]; ++pos) {
+                const float4 q = g.cell_pts[pos];
+                const int j = __float_as_int(q.w);
+                if (j >= q0 && j < q1) {                     // a colliding slot may list rows of another pair
+                  const unsigned long long c2 = fm_key(fm_d2(p, q.x, q.y, q.z), j - q0);
+                  best = c2 < best ? c2 : best;
+                }
+              }
+          }
+        }
+      } else {
+        const int nt = q1 - q0;
+        for (int jb = 0; jb < nt; jb += kThreads) {
+          const int nrow = min(kThreads, nt - jb);
+          __syncthreads();
+          if (tid < nrow) {
+            const float* q = tgt + 3 * (size_t)(q0 + jb + tid);
+            tile[tid] = make_float4(q[0], q[1], q[2], 0.f);
+          }
+          __syncthreads();
+          for (int j = 0; j < nrow; ++j) {
+            const float4 q = tile[j];
+            const unsigned long long c2 = fm_key(fm_d2(p, q.x, q.y, q.z), jb + j);
+            best = c2 < best ? c2 : best;
+          }
+        }
+      }
+      if (KEYS) {
+        if (active) key[s0 + i] = best;
+      } else {
+        const float d2 = __uint_as_float((unsigned)(best >> 32));
+        const bool in = active && best != ~0ull && d2 < tau2;
+        const unsigned n_in = (unsigned)__popcll(__ballot(in));
+        unsigned part = in ? min(__float2uint_rz(d2 * qscale), 0xFFFFFFu) : 0u;            // 64 rows of < 2^24 each: no overflow
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
+        if ((tid & 63) == 0 && n_in) {
+          atomicAdd(cnt + slot, n_in);
+          atomicAdd(sq + slot, (unsigned long long)part);
+        }
+      }
+    }
+  }
+}
+
+// One workgroup per pair: the argmax over the validated hypotheses in the total order (count larger, then the fixed-point sum
+// smaller, then h smaller; h increases with the list position).  A hypothesis with an empty C cannot win, as in open3d, whose
+// running best starts at fitness 0.  win[b] = the list position, -1: the pair reports identity.
+__global__ void __launch_bounds__(kThreads)
+k_fm_winner(int V, const int* __restrict__ validated, const unsigned* __restrict__ cnt, const unsigned long long* __restrict__ sq,
+            int* __restrict__ win) {
+  __shared__ HypKey kk[kThreads];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int nv = validated[b];
+  HypKey best = {0u, 0u, ~0ull, 0x7fffffff};
+  for (int v = tid; v < nv; v += kThreads) {
+    const size_t slot = (size_t)b * V + v;
+    const HypKey c = {cnt[slot] > 0 ? 1u : 0u, cnt[slot], sq[slot], v};
+    if (better(c, best)) best = c;
+  }
+  kk[tid] = best;
+  __syncthreads();
+  for (int s = kThreads / 2; s > 0; s >>= 1) {
+    if (tid < s && better(kk[tid + s], kk[tid])) kk[tid] = kk[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) win[b] = kk[0].valid ? kk[0].h : -1;
+}
+
+// One workgroup per pair: the winner's C from the keys k_fm_eval<., true> left, fitness and rmse by fp64 sums in a fixed tree
+// (a pair gives the same bits alone and in a batch), the pose, the hypothesis and its sample.
+template <int NS>
+__global__ void __launch_bounds__(kThreads)
+k_fm_finish(const int* __restrict__ soff, int V, unsigned long long seed, int first_pair, float tau2, const int* __restrict__ win,
+            const int* __restrict__ hyp, const float* __restrict__ tval, const unsigned long long* __restrict__ key,
+            float* __restrict__ T_out, float* __restrict__ fitness, float* __restrict__ rmse, long long* __restrict__ hyp_out,
+            long long* __restrict__ sample_out, long long* __restrict__ nn_out) {
+  __shared__ double sh[kThreads * 2];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int s0 = soff[b], ns = soff[b + 1] - s0;
+  const int wv = win[b];
+  const bool have = wv >= 0;
+  double v[2] = {0.0, 0.0};                              // |C|, sum d^2
+  for (int i = tid; i < ns; i += kThreads) {
+    long long j = -1;
+    if (have) {
+      const unsigned long long kv = key[s0 + i];
+      const float d2 = __uint_as_float((unsigned)(kv >> 32));
+      if (kv != ~0ull && d2 < tau2) {
+        j = (long long)(kv & 0xffffffffull);
+        v[0] += 1.0;
+        v[1] += (double)d2;
+      }
+    }
+    nn_out[s0 + i] = j;
+  }
+  tree_sum<2>(v, sh);
+  if (tid == 0) {
+    const size_t slot = (size_t)b * V + (have ? wv : 0);
+    float* To = T_out + 16 * (size_t)b;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) To[e] = have ? tval[slot * 12 + e] : ((e % 5 == 0) ? 1.f : 0.f);
+    To[12] = 0.f; To[13] = 0.f; To[14] = 0.f; To[15] = 1.f;
+    fitness[b] = have ? (float)(v[0] / ns) : 0.f;
+    rmse[b] = (have && v[0] > 0) ? (float)sqrt(v[1] / v[0]) : 0.f;
+    const int h = have ? hyp[slot] : -1;
+    hyp_out[b] = h;
+    int rows[NS];
+    if (have) ransac_draw<NS>(seed, (uint32_t)(first_pair + b), (uint32_t)h, (uint32_t)ns, rows);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) sample_out[(size_t)b * NS + k] = have ? rows[k] : -1;
+  }
+}
+
+static size_t fm_align(size_t v) { return (v + 255) / 256 * 256; }
+
+size_t fm_scratch_bytes(long long total_src, int B, int H, int V) {
+  const size_t Hs = ((size_t)H + 3) / 4 * 4, BV = (size_t)B * V;
+  return fm_align((size_t)B * Hs) + fm_align((size_t)B * H * 48) + fm_align(BV * 4) * 2 + fm_align(BV * 8) + fm_align(BV * 48) +
+         fm_align((size_t)B * 4) + fm_align((size_t)total_src * 8) + 256;
+}
+
+void fm_scratch_carve(void* base, long long total_src, int B, int H, int V, FmScratch& s) {
+  const size_t Hs = ((size_t)H + 3) / 4 * 4, BV = (size_t)B * V;
+  char* p = static_cast<char*>(base);
+  s.pass = reinterpret_cast<unsigned char*>(p); p += fm_align((size_t)B * Hs);
+  s.thyp = reinterpret_cast<float*>(p); p += fm_align((size_t)B * H * 48);
+  s.hyp = reinterpret_cast<int*>(p); p += fm_align(BV * 4);
+  s.cnt = reinterpret_cast<unsigned*>(p); p += fm_align(BV * 4);
+  s.sq = reinterpret_cast<unsigned long long*>(p); p += fm_align(BV * 8);
+  s.tval = reinterpret_cast<float*>(p); p += fm_align(BV * 48);
+  s.win = reinterpret_cast<int*>(p); p += fm_align((size_t)B * 4);
+  s.key = reinterpret_cast<unsigned long long*>(p);
+}
+
+template <bool GRID>
+static void launch_fm_eval(const float* src, const int* soff, const float* tgt, const int* toff, int B, int V, int rtiles,
+                           const int* validated, const FmScratch& ws, const FmGridView& g, float tau2, float qscale, hipStream_t s) {
+  // every validated (hypothesis, row tile) is a work item; past 2^20 workgroups a workgroup takes several
+  const long long all = (long long)B * V * rtiles, one = (long long)B * rtiles;
+  hipLaunchKernelGGL((k_fm_eval<GRID, false>), dim3((unsigned)std::min<long long>(all, 1LL << 20)), dim3(kThreads), 0, s, src, soff,
+                     tgt, toff, B, V, rtiles, validated, ws.win, ws.tval, g, tau2, qscale, ws.cnt, ws.sq, ws.key);
+  hipLaunchKernelGGL(k_fm_winner, dim3(B), dim3(kThreads), 0, s, V, validated, ws.cnt, ws.sq, ws.win);
+  hipLaunchKernelGGL((k_fm_eval<GRID, true>), dim3((unsigned)std::min<long long>(one, 1LL << 20)), dim3(kThreads), 0, s, src, soff,
+                     tgt, toff, B, V, rtiles, validated, ws.win, ws.tval, g, tau2, qscale, ws.cnt, ws.sq, ws.key);
+}
+
+template <int NS>
+static void launch_fm_n(const float* src, const int* soff, const float* tgt, const int* toff, const long long* nn, int B,
+                        int rtiles, int H, int V, float tau, float checker_distance, float edge_length, uint64_t seed,
+                        int first_pair, const FmScratch& ws, const KnnScratch* grid, double h, float* T_out, float* fitness,
+                        float* rmse, long long* hypothesis, long long* sample, long long* nn_out, int* validated, hipStream_t s) {
+  const int hb = (H + kThreads - 1) / kThreads;
+  const long long Hs = ((long long)H + 3) / 4 * 4;
+  const float tau2 = tau * tau, qscale = 16777216.0f / tau2;
+  const float cd2 = checker_distance >= 0.f ? checker_distance * checker_distance : -1.f;
+  const double er2 = edge_length > 0.f ? (double)edge_length * (double)edge_length : 0.0;
+  hipLaunchKernelGGL(k_fm_propose<NS>, dim3((unsigned)((long long)hb * B)), dim3(kThreads), 0, s, src, soff, tgt, toff, nn, H, Hs,
+                     hb, (unsigned long long)seed, first_pair, er2, cd2, ws.pass, ws.thyp);
+  hipLaunchKernelGGL(k_fm_select, dim3(B), dim3(kThreads), 0, s, H, Hs, V, ws.pass, ws.thyp, ws.hyp, ws.tval, validated);
+  FmGridView g = {0ull, 0.0, nullptr, nullptr};
+  if (grid) {
+    g.tmask = (unsigned long long)grid->T - 1;
+    g.inv_h = 1.0 / h;
+    g.start = grid->start;
+    g.cell_pts = grid->cell_pts;
+    launch_fm_eval<true>(src, soff, tgt, toff, B, V, rtiles, validated, ws, g, tau2, qscale, s);
+  } else {
+    launch_fm_eval<false>(src, soff, tgt, toff, B, V, rtiles, validated, ws, g, tau2, qscale, s);
+  }
+  hipLaunchKernelGGL(k_fm_finish<NS>, dim3(B), dim3(kThreads), 0, s, soff, V, (unsigned long long)seed, first_pair, tau2, ws.win,
+                     ws.hyp, ws.tval, ws.key, T_out, fitness, rmse, hypothesis, sample, nn_out);
+}
+
+hipError_t launch_ransac_feature_matching(const float* src, const int* src_off, const float* tgt, const int* tgt_off,
+                                          const long long* nn, int B, long long total_src, long long total_tgt, int max_src,
+                                          int ransac_n, int H, int V, float tau, float checker_distance, float edge_length,
+                                          uint64_t seed, int first_pair, const FmScratch& ws, const KnnScratch* grid, float* T_out,
+                                          float* fitness, float* rmse, long long* hypothesis, long long* sample, long long* nn_out,
+                                          int* validated, hipStream_t s) {
+  const size_t Hs = ((size_t)H + 3) / 4 * 4, BV = (size_t)B * V;
+  hipError_t e = hipMemsetAsync(ws.pass, 0, (size_t)B * Hs, s);
+  if (e != hipSuccess) return e;
+  if ((e = hipMemsetAsync(ws.cnt, 0, BV * 4, s)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(ws.sq, 0, BV * 8, s)) != hipSuccess) return e;
+  // cell edge tau (1 + 2^-10), as for ICP: a target with fp32 d^2 < tau^2 is in one of the 27 cells
+  const double h = (double)tau * (1.0 + 1.0 / 1024);
+  if (grid) {
+    e = launch_grid_build(tgt, tgt_off, B, total_tgt, h, *grid, s);
+    if (e != hipSuccess) return e;
+  }
+  const int rtiles = (int)std::max<long long>(1, ((long long)std::min<long long>(max_src, total_src) + kThreads - 1) / kThreads);
+#define GMF_FM_CASE(n) \
+  case n: launch_fm_n<n>(src, src_off, tgt, tgt_off, nn, B, rtiles, H, V, tau, checker_distance, edge_length, seed, first_pair, ws, \
+                         grid, h, T_out, fitness, rmse, hypothesis, sample, nn_out, validated, s); break;
+  switch (ransac_n) {
+    GMF_FM_CASE(3) GMF_FM_CASE(4) GMF_FM_CASE(5) GMF_FM_CASE(6) GMF_FM_CASE(7) GMF_FM_CASE(8)
+    default: return hipErrorInvalidValue;
+  }
+#undef GMF_FM_CASE
   return hipGetLastError();
 }
 

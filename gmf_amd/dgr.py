@@ -21,7 +21,7 @@ from .features import voxel_select
 from ._util import handle_and_stream
 from .matching import _batch_offsets, _match_batched, find_knn_gpu
 from .registration import GlobalRegistration
-from .solvers import registration_icp, registration_ransac_based_on_correspondence
+from .solvers import ransac_feature_matching_batched, registration_icp, registration_ransac_based_on_correspondence
 from .sparse import ResUNetBN2C as InlierResUNetBN2C, inlier_coordinates
 
 # model/__init__.py collects every class of simpleunet / resunet / pyramidnet; of those only FCGF's ResUNetBN2C is built
@@ -92,7 +92,12 @@ class DeepGlobalRegistration:
     - Nothing is printed: `last_stats` holds wsum, its threshold, the branch taken ('global_registration' or 'safeguard'), the
       GlobalRegistration statistics (or None) and the correspondence count.
     - The images (or their tokens) go to the inlier network as given; inlier_thr is accepted and unused, as in the reference.
-    - inlier_feature_type 'feats' gets a 2 x feat_model_n_out wide inlier network (`inlier_in_channels`)."""
+    - inlier_feature_type 'feats' gets a 2 x feat_model_n_out wide inlier network (`inlier_in_channels`).
+
+    safeguard_method (:271-276): 'correspondence' (the default, as in the reference) or 'fcgf_feature_matching'; any other
+    value makes the safeguard raise ValueError."""
+
+    SAFEGUARD_METHODS = ("correspondence", "fcgf_feature_matching")
 
     def __init__(self, config, device=torch.device("cuda"), state=None, inlier_pe=True):
         self.config = config
@@ -100,6 +105,7 @@ class DeepGlobalRegistration:
         self.device = torch.device(device)
         self.use_icp = True
         self.icp_search = "brute"            # registration_icp's `search`: "grid" returns the same pose (timings: DESIGN.md 4e)
+        self.safeguard_method = "correspondence"
         if state is None:
             state = torch.load(_get(config, "weights"), map_location="cpu", weights_only=False)
         nc = parse_network_config(state["config"])
@@ -157,15 +163,28 @@ class DeepGlobalRegistration:
         return torch.cat((torch.cos(xyz0[idx0]), torch.cos(xyz1[idx1])), dim=1).contiguous()
 
     def safeguard_registration(self, xyz0, xyz1, idx0, idx1):
-        """:256-272 with the correspondence safeguard: RANSAC over the correspondences, ransac_n = 4, 80 000 hypotheses,
-        threshold 2 voxel_size."""
-        res = registration_ransac_based_on_correspondence(xyz0, xyz1, torch.stack([idx0, idx1], 1), 2 * self.voxel_size,
+        """:256-276.  'correspondence': RANSAC over the correspondences, ransac_n = 4, 80 000 hypotheses, threshold
+        2 voxel_size.  'fcgf_feature_matching' (:26-54): feature-matching RANSAC, ransac_n = 4, the distance checker and the
+        correspondence distance at 2 voxel_size, 80 000 proposals, 1000 validations.  idx1 is the feature-space nearest
+        neighbour of every row of xyz0 (`correspondences`), so the descriptors are not needed and not matched again."""
+        if self.safeguard_method not in self.SAFEGUARD_METHODS:
+            raise ValueError(f"gmf_amd.DeepGlobalRegistration: safeguard_method must be one of {self.SAFEGUARD_METHODS} "
+                             f"(got {self.safeguard_method!r})")
+        tau = 2 * self.voxel_size
+        if self.safeguard_method == "fcgf_feature_matching":
+            T = ransac_feature_matching_batched(xyz0[None], xyz1[None], idx1[None], tau, ransac_n=4, checker_distance=tau,
+                                                max_iteration=80000, max_validation=1000)[0]
+            return T[0].double().cpu().numpy()
+        res = registration_ransac_based_on_correspondence(xyz0, xyz1, torch.stack([idx0, idx1], 1), tau,
                                                           ransac_n=4, max_iteration=4000000, max_validation=80000)
         return res.transformation.double().cpu().numpy()
 
     def register(self, xyz0, xyz1, inlier_thr=0.0, p_image=None, q_image=None, use_corr=False, p_tokens=None, q_tokens=None):
         """:281-410.  xyz0, xyz1: [N, 3] numpy arrays or tensors.  The inlier network takes p_image / q_image [1, 3, H, W] or
         p_tokens / q_tokens [1, T, 128].  -> T [4, 4] float64 numpy (use_corr: T, xyz0[idx0], xyz1[idx1])."""
+        if self.safeguard_method not in self.SAFEGUARD_METHODS:
+            raise ValueError(f"gmf_amd.DeepGlobalRegistration: safeguard_method must be one of {self.SAFEGUARD_METHODS} "
+                             f"(got {self.safeguard_method!r})")
         with torch.no_grad():
             xyz0, c0 = self.preprocess(xyz0)
             xyz1, c1 = self.preprocess(xyz1)

@@ -1,6 +1,6 @@
-"""Correspondence RANSAC and point-to-point ICP on the device: the solvers the reference's evaluation scripts run after the network
+"""Correspondence RANSAC, feature-matching RANSAC and point-to-point ICP on the device: the solvers the reference's evaluation scripts run after the network
 through open3d 0.9 / 0.10 on the CPU (GMF_PointDSC/evaluation/test_3DMatch.py:76-96, benchmark_utils.py:40-56;
-GMF_DeepGlobalRegistration/*/core/deep_global_registration.py:57-85, 256-272, 385-405).  Kernels: csrc/solver_kernels.hip.
+GMF_DeepGlobalRegistration/*/core/deep_global_registration.py:26-85, 256-276, 385-405).  Kernels: csrc/solver_kernels.hip.
 
 The batched forms take one stream, make no host synchronisation and can be captured into a graph.  The open3d-shaped wrappers
 read back once to size their correspondence set (and the RANSAC wrapper once more to check the indices of `corres`).
@@ -18,6 +18,7 @@ from .registration import _device_offsets
 RegistrationResult = collections.namedtuple("RegistrationResult", "transformation correspondence_set fitness inlier_rmse")
 
 _MAX_HYPOTHESES = 1 << 24
+_MAX_VALIDATION = 1 << 16
 _ICP_SEARCH = {"brute": 0, "grid": 1}
 
 
@@ -193,6 +194,132 @@ def icp_point_to_point_batched(source, target, init, max_correspondence_distance
     return T, stats[0], stats[1], iters, nn
 
 
+def _check_target_offsets(offsets, n_rows, what):
+    """`_check_offsets` for the targets of the feature-matching RANSAC, where a pair may have no targets."""
+    if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
+        return offsets
+    off = offsets.tolist() if isinstance(offsets, (torch.Tensor, np.ndarray)) else list(offsets)
+    try:
+        off = [int(o) for o in off]
+    except (TypeError, ValueError):
+        _fail(what, "target_offsets must be B + 1 integers")
+    if len(off) < 2 or off[0] != 0 or off[-1] != n_rows or any(b < a for a, b in zip(off, off[1:])):
+        _fail(what, "target_offsets must not decrease, start at 0 and end at the number of target rows")
+    return off
+
+
+def _device_target_offsets(off, n_rows, device, what):
+    if isinstance(off, list) and any(b == a for a, b in zip(off, off[1:])):
+        return torch.tensor(off, dtype=torch.int32, device=device)      # (an empty pair: _device_offsets would refuse it)
+    return _device_offsets(off, n_rows, device, what)[0]
+
+
+def ransac_feature_matching_batched(source, target, nn, max_correspondence_distance, source_offsets=None, target_offsets=None,
+                                    ransac_n=4, max_iteration=100000, max_validation=1000, checker_distance=None,
+                                    edge_length_threshold=None, seed=0, first_pair=0, search="grid", return_hypotheses=False):
+    """Feature-matching RANSAC over B pairs (open3d's registration_ransac_based_on_feature_matching loop, point-to-point
+    estimate without scaling, one similar feature per row).
+
+    source [B,Ns,3] / ragged [sum Ns,3] with `source_offsets`, target [B,Nt,3] / ragged with its own `target_offsets` (a pair
+    may have no targets), nn (integer tensor of source's leading shape): the feature-space nearest target row of every source
+    row, numbered within the pair (`find_knn_gpu`'s result).
+    Hypothesis h in 0 .. max_iteration - 1 of pair first_pair + b draws `ransac_n` distinct source rows with the sampler of
+    csrc/ransac_sampler.hpp over the pair's Ns rows and pairs row i with target nn[i].  It passes when every nn lies inside the
+    pair's targets, when (edge_length_threshold = r given) every two sampled pairs have |s_i - s_j|^2 >= r^2 |q_i - q_j|^2 and
+    the reverse, when the fp64 Kabsch fit succeeds, and when (checker_distance given) every sampled pair has
+    |R s + t - q|^2 <= checker_distance^2 under the fit rounded to fp32.  The first `max_validation` passing h in increasing
+    order are evaluated on the whole clouds (open3d's sequential rule, independent of the order of execution): C = the source
+    rows whose exact nearest target has d^2 < tau^2.  The winner has the largest |C| (at least one row), then the smaller sum of
+    d^2 over C (fixed point), then the smaller h; its T is returned without a refit.
+    search: "grid" looks for the nearest target in the 27 cells of a hashed grid of cell edge tau around the transformed row,
+    "brute" tests every target of the pair; both return the same bits ("Evaluation solvers").
+
+    Returns T [B,4,4] f32, fitness [B] (|C| / Ns), inlier_rmse [B], hypothesis [B] int64 (-1: no winner; then T = identity and
+    fitness = inlier_rmse = 0), sample [B, ransac_n] int64 (the winner's source rows within the pair), nn_out (int64, source's
+    leading shape: the geometric nearest target row within the pair under T, -1 outside C) and validated [B] int32 (hypotheses
+    evaluated).  With return_hypotheses also hyp [B, max_validation] int32 (the evaluated h in order, -1 padded) and their raw
+    scores count [B, max_validation] int32 and sum [B, max_validation] int64 (d^2 in units of tau^2 / 2^24).
+    No host synchronisation; the call can be captured into a graph."""
+    what = "ransac_feature_matching_batched"
+    if not isinstance(search, str) or search not in _ICP_SEARCH:
+        _fail(what, f'search must be "brute" or "grid" (got {search!r})')
+    if (source_offsets is None) != (target_offsets is None):
+        _fail(what, "give both source_offsets and target_offsets, or neither")
+    dims = 3 if source_offsets is None else 2
+    _check_points(source, "source", what, dims)
+    _check_points(target, "target", what, dims)
+    if dims == 3 and source.shape[0] != target.shape[0]:
+        _fail(what, f"source and target must hold the same number of pairs (got {source.shape[0]} / {target.shape[0]})")
+    if not isinstance(nn, torch.Tensor) or nn.dtype not in (torch.int64, torch.int32) or nn.shape != source.shape[:-1]:
+        _fail(what, f"nn must be an int64 or int32 tensor of shape {tuple(source.shape[:-1])}")
+    n = int(ransac_n)
+    if n != ransac_n or not 3 <= n <= 8:
+        _fail(what, f"ransac_n must be an integer in 3..8 (got {ransac_n})")
+    H = int(max_iteration)
+    if H != max_iteration or not 1 <= H <= _MAX_HYPOTHESES:
+        _fail(what, f"max_iteration must be an integer in 1..2**24 (got {max_iteration})")
+    V = int(max_validation)
+    if V != max_validation or not 1 <= V <= _MAX_VALIDATION:
+        _fail(what, f"max_validation must be an integer in 1..65536 (got {max_validation})")
+    tau = float(max_correspondence_distance)
+    if not (tau > 0 and np.isfinite(tau)):
+        _fail(what, f"max_correspondence_distance must be > 0 (got {max_correspondence_distance})")
+    cd = -1.0
+    if checker_distance is not None:
+        cd = float(checker_distance)
+        if not (cd >= 0 and np.isfinite(cd)):
+            _fail(what, f"checker_distance must be >= 0 or None (got {checker_distance})")
+    el = 0.0
+    if edge_length_threshold is not None:
+        el = float(edge_length_threshold)
+        if not 0 < el <= 1:
+            _fail(what, f"edge_length_threshold must be in (0, 1] or None (got {edge_length_threshold})")
+    if int(first_pair) < 0:
+        _fail(what, "first_pair must be >= 0")
+    ns_rows = source.shape[0] * source.shape[1] if dims == 3 else source.shape[0]
+    nt_rows = target.shape[0] * target.shape[1] if dims == 3 else target.shape[0]
+    if dims == 3:
+        soff = list(range(0, ns_rows + 1, source.shape[1]))
+        toff = list(range(0, nt_rows + 1, target.shape[1]))
+    else:
+        soff = _check_offsets(source_offsets, ns_rows, what)
+        toff = _check_target_offsets(target_offsets, nt_rows, what)
+        if isinstance(soff, list) and isinstance(toff, list) and len(soff) != len(toff):
+            _fail(what, "source_offsets and target_offsets must describe the same number of pairs")
+    for x, name in ((source, "source"), (target, "target"), (nn, "nn")):
+        _require_device(x, name, what)
+    if target.device != source.device or nn.device != source.device:
+        _fail(what, "source, target and nn must live on the same device")
+    dev = source.device
+    dso, _ = _device_offsets(soff, ns_rows, dev, what)
+    dto = _device_target_offsets(toff, nt_rows, dev, what)
+    B = dso.numel() - 1
+    if dto.numel() != B + 1:
+        _fail(what, "source_offsets and target_offsets must describe the same number of pairs")
+    S = source.reshape(-1, 3).contiguous()
+    Q = target.reshape(-1, 3).contiguous()
+    J = nn.reshape(-1).to(torch.int64).contiguous()
+    T = torch.empty((B, 4, 4), device=dev, dtype=torch.float32)
+    stats = torch.empty((2, B), device=dev, dtype=torch.float32)
+    ids = torch.empty((B, 1 + n), device=dev, dtype=torch.int64)
+    nn_out = torch.empty(source.shape[:-1], device=dev, dtype=torch.int64)
+    validated = torch.empty(B, device=dev, dtype=torch.int32)
+    hyp = count = total = None
+    if return_hypotheses:
+        hyp = torch.empty((B, V), device=dev, dtype=torch.int32)
+        count = torch.empty((B, V), device=dev, dtype=torch.int32)
+        total = torch.empty((B, V), device=dev, dtype=torch.int64)
+    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
+    h, st = handle_and_stream(S)
+    h.call("gmf_ransac_feature_matching", S.data_ptr(), dso.data_ptr(), Q.data_ptr(), dto.data_ptr(), J.data_ptr(), B, ns_rows,
+           nt_rows, _max_rows(soff, ns_rows), n, H, V, tau, cd, el, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_pair),
+           _ICP_SEARCH[search], T.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), ids.data_ptr(), ids.data_ptr() + 8 * B,
+           nn_out.data_ptr(), validated.data_ptr(), ptr(hyp), ptr(count), ptr(total), st)
+    flat = ids.view(-1)                                      # hypothesis [B] followed by sample [B, n] (one allocation)
+    out = (T, stats[0], stats[1], flat[:B], flat[B:].view(B, n), nn_out, validated)
+    return out + (hyp, count, total) if return_hypotheses else out
+
+
 def _on_device(x, dev, dtype):
     if isinstance(x, np.ndarray):
         x = torch.from_numpy(x)
@@ -235,6 +362,45 @@ def registration_ransac_based_on_correspondence(source, target, corres, max_corr
     info = torch.stack([fit[0], rmse[0], inl[0].sum().float()]).cpu().tolist()     # the result's size
     corr = torch.nonzero_static(inl[0], size=int(info[2])).view(-1)
     return RegistrationResult(T[0], c[corr], info[0], info[1])
+
+
+def registration_ransac_based_on_feature_matching(source, target, source_feature, target_feature, max_correspondence_distance,
+                                                  ransac_n=4, checker_distance=None, edge_length_threshold=None,
+                                                  max_iteration=100000, max_validation=1000, seed=0, search="grid"):
+    """open3d.registration.registration_ransac_based_on_feature_matching with TransformationEstimationPointToPoint(False):
+    source [Ns,3] and target [Nt,3] points, source_feature [Ns,d] and target_feature [Nt,d] descriptors (tensors or numpy),
+    one row per point.  open3d's Feature objects and their [d, N] `data` layout are NOT accepted: pass `feature.data.T`.
+    checker_distance is open3d's CorrespondenceCheckerBasedOnDistance(d), edge_length_threshold its
+    CorrespondenceCheckerBasedOnEdgeLength(r); max_iteration and max_validation are its RANSACConvergenceCriteria.  The
+    descriptors are matched with `find_knn_gpu`, then `ransac_feature_matching_batched` runs (its docstring has the rules).
+    -> RegistrationResult(transformation [4,4] f32 on the device, correspondence_set [K,2] int64 on the device (source row,
+    geometric nearest target row) of the winner's C, fitness, inlier_rmse).  One host read, for the result's size."""
+    from .matching import find_knn_gpu
+    what = "registration_ransac_based_on_feature_matching"
+    for x, f, name in ((source, source_feature, "source"), (target, target_feature, "target")):
+        xs, fs = tuple(np.shape(x)), tuple(np.shape(f))
+        if len(xs) != 2 or xs[1] != 3 or len(fs) != 2 or fs[0] != xs[0]:
+            _fail(what, f"{name} must be [N,3] and {name}_feature [N,d], one row per point (got {xs} / {fs}; open3d's [d,N] "
+                        "Feature layout is not accepted)")
+    if np.shape(source_feature)[1] != np.shape(target_feature)[1]:
+        _fail(what, f"source_feature and target_feature differ in width ({np.shape(source_feature)[1]} / "
+                    f"{np.shape(target_feature)[1]})")
+    dev = _device_of(source, target, source_feature, target_feature)
+    if dev.type != "cuda":
+        _fail(what, f"the points must live on a HIP device (got {dev}); the HIP path is mandatory, there is no CPU fallback")
+    S = _on_device(source, dev, torch.float32)
+    Q = _on_device(target, dev, torch.float32)
+    F0 = _on_device(source_feature, dev, torch.float32)
+    F1 = _on_device(target_feature, dev, torch.float32)
+    nn = find_knn_gpu(F0.contiguous(), F1.contiguous(), nn_max_n=-1, knn=1).reshape(-1)
+    T, fit, rmse, _, _, nn_out, _ = ransac_feature_matching_batched(
+        S[None], Q[None], nn[None], max_correspondence_distance, ransac_n=ransac_n, max_iteration=max_iteration,
+        max_validation=max_validation, checker_distance=checker_distance, edge_length_threshold=edge_length_threshold, seed=seed,
+        search=search)
+    nn_out = nn_out[0]
+    info = torch.stack([fit[0], rmse[0], (nn_out >= 0).sum().float()]).cpu().tolist()   # the one synchronisation
+    rows = torch.nonzero_static(nn_out >= 0, size=int(info[2])).view(-1)
+    return RegistrationResult(T[0], torch.stack([rows, nn_out[rows]], 1), info[0], info[1])
 
 
 def registration_icp(source, target, max_correspondence_distance, init=None, max_iteration=30, relative_fitness=1e-6,

@@ -43,8 +43,8 @@ enum {
 };
 
 #define GMF_ABI_VERSION 5   /* 5: gmf_encoder_weights gained `pv_guard` (a caller that fills the struct itself must be rebuilt; one that uses
-                             * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  gmf_icp_point_to_point_ex joined
-                             * under 5: an added entry point, no existing signature or struct changed.  4: + gmf_get_tuning; the
+                             * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  gmf_icp_point_to_point_ex and
+                             * gmf_ransac_feature_matching joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
                              * pose head / pick_seeds take any N */
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
@@ -528,6 +528,32 @@ int gmf_icp_point_to_point_ex(gmf_handle* h, const float* src, const int* src_of
                               int B, long long total_src, int max_src, int max_tgt, const float* init, float tau, int max_iter,
                               double rel_fitness, double rel_rmse, float* T_out, float* fitness, float* inlier_rmse,
                               int* iterations, long long* nn, long long total_tgt, int search, gmf_stream_t stream);
+
+/* registration_ransac_based_on_feature_matching (GMF_DeepGlobalRegistration/.../core/deep_global_registration.py:26-54) over B
+ * ragged pairs: src [total_src,3] with src_offsets [B+1], tgt [total_tgt,3] with tgt_offsets [B+1] (device int32; a pair may have
+ * no targets), nn [total_src] int64: the feature-space nearest target row of every source row, numbered within the pair.
+ * Hypothesis h in 0 .. max_iteration - 1 (1..2^24) of pair first_pair + b draws ransac_n (3..8) distinct source rows (the
+ * sampler of gmf_amd/csrc/ransac_sampler.hpp over the pair's Ns rows) and pairs each with its nn.  It passes when every nn is a
+ * row of the pair's targets; when, with edge_length_threshold r in (0, 1] (<= 0: off), for every two sampled pairs
+ * |s_i - s_j|^2 >= r^2 |q_i - q_j|^2 and the reverse (fp64); when the unweighted fp64 Kabsch fit succeeds; and when, with
+ * checker_distance >= 0 (negative: off), every sampled pair has fp32 |R s + t - q|^2 <= checker_distance^2 under the fit
+ * rounded to fp32.  The first max_validation (1..65536) passing h in increasing order are evaluated on the whole clouds: C =
+ * the source rows whose exact nearest target (smallest fp32 d^2, then smallest row) has d^2 < tau^2.  The winner has the
+ * largest |C| (at least 1), then the smaller sum over C of rz(d^2 2^24 / tau^2) capped at 2^24 - 1, then the smaller h; no refit.
+ * search 0 tests every target of the pair; search 1 (total_tgt < 2^29) builds a hashed grid of cell edge tau (1 + 2^-10) over
+ * the targets and tests the 27 cells around a transformed row: the same bits.  max_src: the largest pair's source rows if
+ * known (any value >= 1 is correct).  Out: T_out [B,16], fitness [B] (|C| / Ns), inlier_rmse [B], hypothesis [B] int64 (-1:
+ * no winner, T = identity, fitness = rmse = 0), sample [B, ransac_n] int64 (source rows within the pair, -1 without a winner),
+ * nn_out [total_src] int64 (the winner's nearest target row within the pair, -1 outside C), validated [B] int32 (hypotheses
+ * evaluated); optional (NULL: not returned) hyp [B, max_validation] int32 (the evaluated h in order, -1 padded), count
+ * [B, max_validation] int32 and sum [B, max_validation] int64 (their |C| and fixed-point sums, 0 padded).  No host
+ * synchronisation; graph-capturable. */
+int gmf_ransac_feature_matching(gmf_handle* h, const float* src, const int* src_offsets, const float* tgt, const int* tgt_offsets,
+                                const long long* nn, int B, long long total_src, long long total_tgt, int max_src, int ransac_n,
+                                int max_iteration, int max_validation, float tau, float checker_distance,
+                                float edge_length_threshold, unsigned long long seed, int first_pair, int search, float* T_out,
+                                float* fitness, float* inlier_rmse, long long* hypothesis, long long* sample, long long* nn_out,
+                                int* validated, int* hyp, int* count, long long* sum, gmf_stream_t stream);
 
 /* ---- point-cloud descriptors: radius kNN, normals, FPFH, voxel grids (open3d's, as the reference's feature scripts call them) -- */
 

@@ -16,6 +16,12 @@
                     process, so that the per-kernel averages belong to one size; shapes: keypoints, 10k, 50k).
                     tools/icp_trace_passes.py picks the working passes out of such a trace.
   ICP crossover     whole calls, brute against grid, at keypoint pairs of 125 ... 2000 rows.
+  feature-matching RANSAC   DGR's call: ransac_n = 4, the distance checker and tau at 2 voxels (0.10), 80 000 proposals, 1000
+                    validations; clouds of 10k / 10k and 50k / 50k points (40 % of the feature matches right, the others random)
+                    and keypoints 5000 / 5000.  The whole call with search="grid", and search="brute" beside it where the
+                    brute-force search is affordable (not at 50k: 2.5e12 distance tests).  The evaluation kernel alone is a
+                    kernel time: rocprofv3 --kernel-trace --stats -- python tools/time_solvers.py --fm-shape 50k   (one shape
+                    per process; shapes: keypoints, 10k, 50k); searches per second = validated x Ns over k_fm_eval's time.
 
 Device events around each call, after warm-up; median and spread over repeats.  For RANSAC the row tests per second and the share
 of the fp32 vector peak (15 vector ops per hypothesis-row test, the issue's count, at 157.3 TFLOP/s) are printed too.
@@ -119,6 +125,50 @@ def icp_crossover_rows(report, repeats, dev):
         report(f"  keypoints {N}/{N} tau=0.10 ({it} passes): {wb:9.1f} | {wg:9.1f}")
 
 
+FM_SHAPES = ("keypoints", "10k", "50k")
+
+
+def fm_shape(key):
+    """-> (name, src [1,N,3], tgt [1,N,3], nn [1,N], tau): row i of the target is row i of the source moved; nn is i for the
+    right feature matches and a random row for the others."""
+    if key == "keypoints":
+        p = synthetic.synthetic_pair(1, 5000)
+        s, q = p["src_keypts"], p["tgt_keypts"]
+        good = np.asarray(p["gt_labels"]) > 0
+    else:
+        N = {"10k": 10000, "50k": 50000}[key]
+        s, q, _ = cloud_pair(N, 5)
+        good = np.random.default_rng([7, N]).random(N) < 0.4
+    n = len(good)
+    nn = np.where(good, np.arange(n), np.random.default_rng([8, n]).integers(0, n, n))
+    name = f"{'keypoints' if key == 'keypoints' else 'cloud'} {n}/{n} tau=0.10, {good.mean():.0%} right matches"
+    return name, torch.as_tensor(s)[None], torch.as_tensor(q)[None], torch.as_tensor(nn)[None], 0.10
+
+
+def fm_rows(report, repeats, dev, keys=FM_SHAPES):
+    """The module docstring's "feature-matching RANSAC"."""
+    report("feature-matching RANSAC: n=4, 80 000 proposals, 1000 validations, checker = tau; whole call, us, median [min, max]")
+    for key in keys:
+        name, s, q, nn, tau = fm_shape(key)
+        s, q, nn = s.to(dev), q.to(dev), nn.to(dev)
+        kw = dict(ransac_n=4, checker_distance=tau, max_iteration=80000, max_validation=1000, return_hypotheses=True)
+
+        def call(search):
+            return lambda: gmf_amd.ransac_feature_matching_batched(s, q, nn, tau, search=search, **kw)
+
+        grid = call("grid")()
+        nv, last = int(grid[6][0]), int(grid[7][0].max())
+        report(f"  {name}: {nv} validated (the last is proposal {last}), fitness {float(grid[1][0]):.3f}, "
+               f"{nv * s.shape[1] / 1e6:.1f} M searches")
+        if key == "50k":
+            med, lo, hi = timed(call("grid"), repeats)
+            report(f"    grid  {med:10.1f} [{lo:.1f}, {hi:.1f}]   (brute force not run at this size)")
+            continue
+        same = all(torch.equal(x, y) for x, y in zip(grid, call("brute")()))
+        mb, mg = timed_alternating([call("brute"), call("grid")], max(3, repeats // 2), warmup=2)
+        report(f"    brute {mb:10.1f} | grid {mg:10.1f}   (alternated; outputs bit-identical: {same})")
+
+
 def cloud_pair(N, seed):
     r = np.random.default_rng([seed, N])
     X = r.uniform(0, 3, (N, 3))
@@ -135,6 +185,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--icp-shape", choices=ICP_SHAPES, default=None, help="only the ICP search rows of one shape (for a kernel trace)")
+    ap.add_argument("--fm-shape", choices=FM_SHAPES, default=None,
+                    help="only the feature-matching RANSAC rows of one shape (for a kernel trace)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "time_solvers.py measures on a HIP device"
     dev = "cuda:0"
@@ -147,6 +199,9 @@ def main():
     report(f"device: {torch.cuda.get_device_name(0)}; median [min, max] over {a.repeats} repeats, device events")
     if a.icp_shape:
         icp_search_rows(report, a.repeats, dev, (a.icp_shape,))
+        return
+    if a.fm_shape:
+        fm_rows(report, a.repeats, dev, (a.fm_shape,))
         return
 
     # PointDSC RANSAC
@@ -188,6 +243,7 @@ def main():
                f"nearest-neighbour pass, {N * N / per * 1e-3:.0f} G distance tests/s)")
     icp_search_rows(report, a.repeats, dev)
     icp_crossover_rows(report, a.repeats, dev)
+    fm_rows(report, a.repeats, dev)
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
