@@ -17,6 +17,7 @@
 #include "api_common.hpp"
 #include "launchers_pose.hpp"
 #include "launchers_solvers.hpp"
+#include "launchers_spectral.hpp"
 #include "launchers_pointcloud.hpp"
 #include "launchers_sparse.hpp"
 #include "launchers_dgr_input.hpp"
@@ -256,6 +257,11 @@ int gmf_set_tuning(gmf_handle* h, const char* name, int value) {
     t.precision = value;
     return GMF_OK;
   }
+  if (std::strcmp(name, "spectral_col_splits") == 0) { // spectral matching: 0 = column splits from the pair's N (default), 1..32 = forced
+    GMF_REQUIRE(value >= 0 && value <= gmf::kSmMaxSplits, GMF_ERR_BAD_ARG, "set_tuning: spectral_col_splits out of range (0..32)");
+    t.spectral_col_splits = value;
+    return GMF_OK;
+  }
   return fail(h, GMF_ERR_BAD_ARG, std::string("gmf: set_tuning: unknown knob ") + name);
 }
 
@@ -270,7 +276,7 @@ int gmf_get_tuning(gmf_handle* h, const char* name, int* value) {
       {"fused_linear", t.fused_linear ? 1 : 0}, {"compat_cache", t.use_cache ? 1 : 0}, {"conv_lds_patch", t.conv_patch}, {"conv_small_grid", t.conv_small ? 1 : 0}, {"small_prologue_roles", t.small_prologue ? 1 : 0}, {"small_fattn_tile", t.small_fattn_tile ? 1 : 0},
       {"nms_binned", t.nms_binned}, {"topk_select", t.topk_select ? 1 : 0}, {"wide_attn_tile", t.wide_attn_tile ? 1 : 0},
       {"small_merge_tile", t.small_merge_tile ? 1 : 0}, {"mid_grid_roles", t.mid_grid_roles}, {"pv_fp8", t.pv_fp8}, {"q_in_attention", t.q_in_attention ? 1 : 0},
-      {"compat_format", t.compat_format}, {"precision", t.precision}};
+      {"compat_format", t.compat_format}, {"precision", t.precision}, {"spectral_col_splits", t.spectral_col_splits}};
   for (const auto& e : tab) {
     if (std::strcmp(name, e.name) == 0) { *value = e.v; return GMF_OK; }
   }
@@ -1474,6 +1480,28 @@ int gmf_ransac_feature_matching(gmf_handle* h, const float* src, const int* src_
                                               max_src > 0 ? max_src : (int)total_src, ransac_n, max_iteration, max_validation, tau,
                                               checker_distance, edge_length_threshold, seed, first_pair, ws, search ? &gs : nullptr,
                                               T_out, fitness, inlier_rmse, hypothesis, sample, nn_out, validated, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_spectral_matching(gmf_handle* h, const float* corr, const float* src, const float* tgt, const int* offsets, int B, int max_n,
+                          float inlier_threshold, const int* topk, int iterations, float* eig_out, float* labels_out, float* T_out,
+                          gmf_stream_t stream) {
+  GMF_REQUIRE(h && offsets && topk && T_out, GMF_ERR_BAD_ARG, "spectral_matching: null pointer");
+  GMF_REQUIRE(B > 0 && B <= 65535, GMF_ERR_UNSUPPORTED_SHAPE, "spectral_matching: B must be in 1..65535");
+  GMF_REQUIRE(max_n >= 0, GMF_ERR_BAD_ARG, "spectral_matching: max_n must be >= 0");
+  GMF_REQUIRE(max_n == 0 || (corr && src && tgt && eig_out && labels_out), GMF_ERR_BAD_ARG, "spectral_matching: null pointer");
+  GMF_REQUIRE(inlier_threshold > 0.f && std::isfinite(inlier_threshold), GMF_ERR_BAD_ARG,
+              "spectral_matching: inlier_threshold must be finite and > 0");
+  GMF_REQUIRE(iterations >= 1 && iterations <= 1000, GMF_ERR_BAD_ARG, "spectral_matching: iterations must be in 1..1000");
+  SetDevice sd(h, stream);
+  // the partial sums are [splits, total_rows]; the call does not read the offsets back, so total_rows is bounded by B max_n
+  const long long total_rows = (long long)B * max_n;
+  GMF_REQUIRE(total_rows < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE, "spectral_matching: B max_n must be below 2^31");
+  const int forced = h->tune.spectral_col_splits;
+  float* partial = nullptr;
+  if (int rc = arena_carve(h, {arena_buf(partial, gmf::sm_scratch_floats(total_rows, max_n, forced))})) return rc;
+  GMF_HIP(gmf::launch_spectral_matching(corr, src, tgt, offsets, B, total_rows, max_n, inlier_threshold, topk, iterations, forced,
+                                        partial, eig_out, labels_out, T_out, S(stream)));
   return GMF_OK;
 }
 

@@ -44,7 +44,7 @@ enum {
 
 #define GMF_ABI_VERSION 5   /* 5: gmf_encoder_weights gained `pv_guard` (a caller that fills the struct itself must be rebuilt; one that uses
                              * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  gmf_icp_point_to_point_ex and
-                             * gmf_ransac_feature_matching joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
+                             * gmf_ransac_feature_matching, then gmf_spectral_matching joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
                              * pose head / pick_seeds take any N */
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
@@ -160,7 +160,9 @@ int gmf_set_sigma_device(gmf_handle* h, const float* sigma_dev);
  *   "nms_binned"        : 1 = grid-binned NMS candidates on large grids (default), 2 = always, 0 = all pairs.
  *   "topk_select"       : 1 = radix select of the S seeds (default), 0 = full bitonic sort.
  *   "q_in_attention"    : [ABI 4] 1 = on large grids every attention workgroup projects its own Q' in its prologue (default; PointDSC.py:56),
- *                         0 = the linear kernel writes a Q' image.  Bit-identical results. */
+ *                         0 = the linear kernel writes a Q' image.  Bit-identical results.
+ *   "spectral_col_splits": gmf_spectral_matching: 0 = the columns of a pair's sweep are split over workgroups by a rule of its own
+ *                         N (default), 1..32 = that many splits at most (another order of a row's partial sums). */
 int gmf_set_tuning(gmf_handle* h, const char* name, int value);
 /* [ABI 4] The current value of a knob, so that a caller that changes one for a single call can put back what it found
  * (the Python PointDSC module does this for its module-local numerics mode).  Both calls take the handle's lock. */
@@ -554,6 +556,29 @@ int gmf_ransac_feature_matching(gmf_handle* h, const float* src, const int* src_
                                 float edge_length_threshold, unsigned long long seed, int first_pair, int search, float* T_out,
                                 float* fitness, float* inlier_rmse, long long* hypothesis, long long* sample, long long* nn_out,
                                 int* validated, int* hyp, int* count, long long* sum, gmf_stream_t stream);
+
+/* The spectral-matching baseline SM(corr, src_keypts, tgt_keypts, args, top_ratio) of the reference's evaluation
+ * (GMF_PointDSC/baseline_scripts/baseline_3DMatch.py:19-53; baseline_KITTI.py:51) over B ragged pairs, matrix-free: corr
+ * [sum N,6], src / tgt [sum N,3] (float32), offsets [B+1] (device int32; a pair may be empty), topk [B] (device int32: the k
+ * rows to label, int(N top_ratio) in the reference).  Per pair, in fp32:
+ *   d_ij = |c_i[0:3] - c_j[0:3]| - |c_i[3:6] - c_j[3:6]| (coordinate differences, then the root of the sum of squares),
+ *   m_ij = max(0, 4.5 - d_ij^2 / (2 sigma^2)), sigma = inlier_threshold / 3, m_ii = 0;
+ *   v = ones, `iterations` (1..1000; the reference: 10) times v <- M v, v <- v / (|v|_2 + 1e-6);
+ *   labels = 1 on the k rows of largest v, equal values to the smaller row (the reference's argsort leaves ties open);
+ *   T = rigid_transform_3d(src, tgt, v * labels) (GMF_PointDSC/models/common.py:10-50): weights not normalised, centroids over
+ *   sum w + 1e-6, R = V diag(1, 1, det) U^T by the fp64 Kabsch; k = 0, an all-zero v or an empty pair give the identity.
+ * M is never formed: each product recomputes its entries, rows on lanes, the columns streamed through LDS and split over
+ * workgroups by a rule of the pair's own N; the partial sums are added in split order (no floating-point atomics), so a pair has
+ * the same bits alone, in any batch and on every run.  max_n: an upper bound of the largest pair's rows (0: every pair is empty);
+ * it sizes the grid and the workspace (up to 32 B max_n floats: give the largest pair itself where it is known).  B <= 65535,
+ * B max_n < 2^31.  Out: eig_out [sum N] (v), labels_out [sum N] (float 0 / 1), T_out [B,16].  gmf_set_tuning:
+ * "spectral_col_splits" (0 = by the rule, 1..32 = forced).  The two square roots of a matrix entry are v_sqrt_f32 as it comes (1
+ * ulp).  A pair with more than max_n rows, or whose rows end past B max_n, is not computed: its T_out is the identity and its
+ * eig_out and labels_out rows are zeros; no status is raised.  2 iterations + 2 launches, no host synchronisation;
+ * graph-capturable. */
+int gmf_spectral_matching(gmf_handle* h, const float* corr, const float* src, const float* tgt, const int* offsets, int B, int max_n,
+                          float inlier_threshold, const int* topk, int iterations, float* eig_out, float* labels_out, float* T_out,
+                          gmf_stream_t stream);
 
 /* ---- point-cloud descriptors: radius kNN, normals, FPFH, voxel grids (open3d's, as the reference's feature scripts call them) -- */
 
