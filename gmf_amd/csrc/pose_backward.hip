@@ -337,7 +337,10 @@ k_wp_backward(const float* __restrict__ X, const float* __restrict__ Y, const fl
     for (int c = 0; c < 3; ++c) { acc[1 + c] += wj * x[3 * j + c]; acc[4 + c] += wj * y[3 * j + c]; }
   }
   bsum<7>(acc, sh);
-  const double inv = 1.0 / ((double)(float)acc[0] + (double)eps);
+  // sum|w| stays in fp64 here (the forward rounds it to fp32 as the reference does): a rounding of 2^-24 makes sum w~ miss 1 by
+  // that much, and the D terms then put 2 * 2^-24 * my^T gS mx into dL/dw~ of every point - 1e-3 of the largest entry of dw
+  // for a scene 250 from the origin: it cancels against the sgn term where w != 0 and stays whole in the gradient of a zero weight
+  const double inv = 1.0 / (acc[0] + (double)eps);
   const double mx[3] = {acc[1] * inv, acc[2] * inv, acc[3] * inv};
   const double my[3] = {acc[4] * inv, acc[5] * inv, acc[6] * inv};
   double Sm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};

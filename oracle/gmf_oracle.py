@@ -587,11 +587,13 @@ def sm_loss_from_features(corr_features, sigma, gt_labels, balanced: bool = True
     return ((M - gt_M) ** 2).mean()
 
 
-def training_losses(sd: SD, data: dict, num_layers: int, balanced: bool):
+def training_losses(sd: SD, data: dict, num_layers: int, balanced: bool, return_features: bool = False):
     """Differentiable restatement of the reference's default training objective (libs/trainer.py:131-141 with
     config_3DMatch.py:49-52): the model in train() mode (BatchNorm batch statistics) and its non-test forward
     (PointDSC.py:216-241), ClassificationLoss (loss.py:85-93) + SpectralMatchingLoss (loss.py:116-140).  Tensors in `sd` may
-    require grad; returns (logits, M, class_loss, sm_loss) as tensors.  Golden F19 pins it to the reference's gradients."""
+    require grad; returns (logits, M, class_loss, sm_loss) as tensors, followed by the encoder output [B, N, C] with
+    `return_features` (the pose term, `pose_loss_from_features`, starts there).  Golden F19 pins it to the reference's
+    gradients."""
     src, tgt = data["src_keypts"], data["tgt_keypts"]
     with torch.no_grad():
         compat, _ = compat_matrix(src, tgt, float(sd["sigma_spat"]))
@@ -621,6 +623,8 @@ def training_losses(sd: SD, data: dict, num_layers: int, balanced: bool):
         sm = torch.mean(lp * 0.5 + ln * 0.5)
     else:
         sm = ((M - gt_M) ** 2).mean()
+    if return_features:
+        return logits, M, cl, sm, feat
     return logits, M, cl, sm
 
 
@@ -661,3 +665,58 @@ def pose_loss_from_features(corr_features, sigma, logits, src, tgt, sigma_d: flo
             warp = src[i] @ final_T[i, :3, :3].T + final_T[i, :3, 3]
             loss = loss + ((warp[None] - tgt) ** 2).sum(-1).mean()
     return loss / bs, final_T
+
+
+def pose_head_choices(corr_features, sigma, logits, src, tgt, sigma_d: float, ratio: float = 0.1, k: int = 40, iters: int = 10,
+                      tau: float = 0.10):
+    """The discrete choices `pose_loss_from_features` makes on the way, with the margin each one has (no gradient; the tensors'
+    own dtype throughout).  A gradient of the pose head can be compared between two precisions only where both make the same
+    choices.  Returns a dict:
+      seeds [B,S]          the top-S logits' indices, in order;  seed_gap [B]: the smallest gap between two neighbours of the S + 1
+                           largest logits (the order of the seeds and the cut behind rank S)
+      knn_idx [B,S,k]      the neighbour sets;  knn_gap [B,S]: distance of rank k + 1 minus distance of rank k (inf for k = N - 1)
+      stop_it              index of the power iteration whose result is used (the first passing torch.allclose over all B S
+                           seeds, else iters - 1);  stop_ratio [stop_it + 1]: per iteration max |v - last| / (1e-8 + 1e-5 |last|),
+                           > 1 before the exit and <= 1 at it
+      dist [B,S,N]         |R_s p + t_s - q| of every hypothesis;  fitness [B,S] = mean(dist < tau);  best [B] its first argmax"""
+    with torch.no_grad():
+        fn = F.normalize(corr_features, p=2, dim=-1)
+        B, N, _ = fn.shape
+        S = int(N * ratio)
+        k = min(k, N - 1)
+        order = torch.argsort(logits, dim=1, descending=True)
+        seeds = order[:, :S]
+        top = torch.gather(logits, 1, order[:, :min(S + 1, N)])
+        seed_gap = (top[:, :-1] - top[:, 1:]).min(dim=1)[0]
+        d = 2 - 2 * (fn @ fn.transpose(1, 2))
+        dk = torch.gather(d, 1, seeds[:, :, None].expand(-1, -1, N))                  # [B,S,N]
+        vals, idx = dk.topk(min(k + 2, N), dim=-1, largest=False)
+        knn_idx = idx[:, :, 1:k + 1]
+        knn_gap = vals[:, :, k + 1] - vals[:, :, k] if k + 1 < N else torch.full((B, S), float("inf"), dtype=fn.dtype)
+        bi = torch.arange(B)[:, None, None]
+        f = fn[bi, knn_idx]
+        Mf = torch.clamp(1 - (1 - f @ f.transpose(2, 3)) / sigma ** 2, min=0)
+        sk, tk = src[bi, knn_idx], tgt[bi, knn_idx]
+        dd = torch.cdist(sk, sk, compute_mode="donot_use_mm_for_euclid_dist") - \
+            torch.cdist(tk, tk, compute_mode="donot_use_mm_for_euclid_dist")
+        M = (Mf * torch.clamp(1 - dd * dd / sigma_d ** 2, min=0)).reshape(B * S, k, k).clone()
+        ar = torch.arange(k)
+        M[:, ar, ar] = 0
+        v = torch.ones_like(M[:, :, :1])
+        last, ratios, stop_it = v, [], iters - 1
+        for it in range(iters):                                                        # power_iteration, with its margins
+            v = torch.bmm(M, v)
+            v = v / (torch.norm(v, dim=1, keepdim=True) + 1e-6)
+            ratios.append(float(((v - last).abs() / (1e-8 + 1e-5 * last.abs())).max()))
+            if torch.allclose(v, last):
+                stop_it = it
+                break
+            last = v
+        w = v[..., 0].reshape(B, S, k)
+        w = (w / (w.sum(-1, keepdim=True) + 1e-6)).reshape(B * S, k)
+        Ts = rigid_transform_3d(sk.reshape(B * S, k, 3), tk.reshape(B * S, k, 3), w).reshape(B, S, 4, 4)
+        pred = torch.einsum("bsnm,bkm->bskn", Ts[:, :, :3, :3], src) + Ts[:, :, None, :3, 3]
+        dist = torch.norm(pred - tgt[:, None], dim=-1)
+        fit = (dist < tau).float().mean(-1)
+        return {"seeds": seeds, "seed_gap": seed_gap, "knn_idx": knn_idx, "knn_gap": knn_gap, "stop_it": stop_it,
+                "stop_ratio": ratios, "dist": dist, "fitness": fit, "best": fit.argmax(dim=1)}
