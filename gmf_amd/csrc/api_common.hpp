@@ -5,12 +5,12 @@
 
 #include <hip/hip_runtime.h>
 
-#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <utility>
 #include <vector>
 
+#include "arena_list.hpp"
 #include "launchers.hpp"
 
 struct gmf_handle {
@@ -18,7 +18,6 @@ struct gmf_handle {
   std::string err;
   void* arena = nullptr;
   size_t arena_bytes = 0;
-  size_t arena_used = 0;
   // caller-provided workspace (gmf_set_workspace): when set, the library allocates nothing; a call that needs more returns
   // GMF_ERR_WORKSPACE and gmf_workspace_wanted() says how much
   bool arena_external = false;
@@ -77,7 +76,6 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // device, so no kernel can still be using the old block - and it must not happen inside a stream capture: run every shape
 // once before capturing).  Caller-provided (gmf_set_workspace): never allocates; too small -> GMF_ERR_WORKSPACE.
 inline int arena_reserve(gmf_handle* h, size_t bytes) {
-  h->arena_used = 0;
   if (bytes <= h->arena_bytes) return GMF_OK;
   if (h->arena_external) {
     h->arena_wanted = align_up(bytes + bytes / 8, 1 << 20);
@@ -100,27 +98,12 @@ inline int arena_reserve(gmf_handle* h, size_t bytes) {
   return GMF_OK;
 }
 
-template <typename T>
-T* arena_take(gmf_handle* h, size_t count) {
-  const size_t off = align_up(h->arena_used, 256);
-  h->arena_used = off + count * sizeof(T);
-  return reinterpret_cast<T*>(static_cast<char*>(h->arena) + off);
-}
-
-inline size_t arena_need(size_t count, size_t elem) { return align_up(count * elem, 256) + 256; }
-
-// One buffer of a call's workspace: `count` elements of T into `*slot` (count 0: no buffer, *slot = null).  A call lists its buffers
-// once, in arena_carve: the reservation is the sum of the list and the carving follows it, so the two cannot disagree.
-struct ArenaBuf { void* slot; size_t count, elem; void (*set)(void* slot, char* p); };
-template <typename T>
-ArenaBuf arena_buf(T*& slot, size_t count) {
-  return {&slot, count, sizeof(T), [](void* sl, char* p) { *static_cast<T**>(sl) = reinterpret_cast<T*>(p); }};
-}
-inline int arena_carve(gmf_handle* h, std::initializer_list<ArenaBuf> bufs) {
-  size_t need = 0;
-  for (const ArenaBuf& b : bufs) need += b.count ? arena_need(b.count, b.elem) : 0;
-  if (int rc = arena_reserve(h, need)) return rc;
-  for (const ArenaBuf& b : bufs) b.set(b.slot, b.count ? arena_take<char>(h, b.count * b.elem) : nullptr);
+// A call's whole workspace: reserves the sum of the list and places every buffer (arena_list.hpp).  The only caller of
+// arena_reserve.
+inline int arena_carve(gmf_handle* h, const ArenaList& bufs) {
+  if (bufs.overflowed()) return fail(h, GMF_ERR_UNSUPPORTED_SHAPE, "gmf: a call lists more workspace buffers than ArenaList holds");
+  if (int rc = arena_reserve(h, bufs.bytes())) return rc;
+  bufs.place(h->arena);
   return GMF_OK;
 }
 

@@ -46,15 +46,13 @@ struct KnnLists {
 
 int take_knn(gmf_handle* h, long long N, int max_nn, bool spfh, KnnLists& k) {
   const size_t NK = (size_t)N * max_nn;
-  const size_t grid = gmf::knn_scratch_bytes(N);
-  const size_t need = grid + arena_need(NK, 4) + arena_need(NK, 8) + arena_need(N, 4) + (spfh ? arena_need((size_t)N * 33, 8) : 0);
-  if (int rc = arena_reserve(h, need)) return rc;
-  gmf::knn_scratch_carve(arena_take<char>(h, grid), N, k.ws);
-  k.idx = arena_take<int>(h, NK);
-  k.d2 = arena_take<double>(h, NK);
-  k.count = arena_take<int>(h, N);
-  k.spfh = spfh ? arena_take<double>(h, (size_t)N * 33) : nullptr;
-  return GMF_OK;
+  ArenaList bufs;
+  gmf::knn_scratch_list(N, k.ws, bufs);
+  bufs.add(k.idx, NK);
+  bufs.add(k.d2, NK);
+  bufs.add(k.count, (size_t)N);
+  bufs.add(k.spfh, spfh ? (size_t)N * 33 : 0);
+  return arena_carve(h, bufs);
 }
 
 int voxel_call(gmf_handle* h, const char* what, const float* pts, const int* offsets, int B, long long total_rows, double voxel,
@@ -62,10 +60,10 @@ int voxel_call(gmf_handle* h, const char* what, const float* pts, const int* off
   if (int rc = check_cloud_args(h, what, pts, offsets, B, total_rows, voxel, 1)) return rc;
   GMF_REQUIRE((out_pts || out_idx) && out_offsets && num_out, GMF_ERR_BAD_ARG, std::string(what) + ": null pointer");
   SetDevice sd(h, stream);
-  const size_t need = gmf::voxel_scratch_bytes(total_rows, B);
-  if (int rc = arena_reserve(h, need)) return rc;
   gmf::VoxelScratch ws;
-  gmf::voxel_scratch_carve(arena_take<char>(h, need), total_rows, B, ws);
+  ArenaList bufs;
+  gmf::voxel_scratch_list(total_rows, B, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
   int host2[2] = {0, 0};
   GMF_HIP(gmf::launch_voxel(pts, offsets, B, total_rows, voxel, out_pts != nullptr, ws, out_pts, out_idx, out_offsets, host2,
                             S(stream)));
@@ -126,7 +124,6 @@ int gmf_set_workspace(gmf_handle* h, void* device_ptr, long long bytes) {
   h->arena = device_ptr;
   h->arena_bytes = (size_t)bytes;
   h->arena_external = device_ptr != nullptr;
-  h->arena_used = 0;
   return GMF_OK;
 }
 
@@ -987,11 +984,10 @@ int gmf_pick_seeds(gmf_handle* h, const float* src_keypts, const float* scores, 
   SetDevice sd(h, stream);
   hipStream_t st = S(stream);
   const float* keys = scores;
+  float *kbuf, *scr;
+  if (int rc = arena_carve(h, {arena_buf(kbuf, use_nms ? (size_t)B * N : 0), arena_buf(scr, use_nms ? gmf::nms_scratch_floats(B, N) : 0)}))
+    return rc;
   if (use_nms) {
-    const size_t n_scr = gmf::nms_scratch_floats(B, N);
-    if (int rc = arena_reserve(h, arena_need((size_t)B * N, 4) + arena_need(n_scr, 4))) return rc;
-    float* kbuf = arena_take<float>(h, (size_t)B * N);
-    float* scr = arena_take<float>(h, n_scr);
     GMF_HIP(gmf::launch_nms_keys(h->tune, src_keypts, scores, kbuf, B, N, nms_radius, st, scr));
     keys = kbuf;
   }
@@ -1056,30 +1052,20 @@ static int pose_head_impl(gmf_handle* h, const gmf_pose_params* p, const float* 
   GMF_REQUIRE((p->sigma > 0.f || h->sigma_dev) && p->sigma_d > 0.f, GMF_ERR_BAD_ARG, "pose_head: sigma, sigma_d must be positive");
   hipStream_t st = S(stream);
   const size_t BS = (size_t)B * Sn;
-  const size_t need = arena_need((size_t)B * N, 4) + arena_need(BS, 4) + arena_need(BS * k, 4) +
-                      arena_need(BS * iters * k, 4) + arena_need(BS * iters, 1) + arena_need(BS * 16, 4) +
-                      arena_need(BS, 4) + arena_need(BS, 4) + arena_need(B, 4) + arena_need(BS * 15, 8) + arena_need(1, 4) +
-                      arena_need((size_t)B * tiles_of(N) * kTileFloats, 4) + arena_need(BS * tiles_of(N) * 32, 4) +
-                      arena_need((size_t)B, sizeof(gmf::PairTab));
-  if (int rc = arena_reserve(h, need)) return rc;
-  float* fimg = arena_take<float>(h, (size_t)B * tiles_of(N) * kTileFloats);
-  float* dmat = arena_take<float>(h, BS * tiles_of(N) * 32);       // distance rows of the seeds, padded to whole tiles
-  float* keys = arena_take<float>(h, (size_t)B * N);
-  int* seeds = arena_take<int>(h, BS);
-  int* knn = arena_take<int>(h, BS * k);
-  float* snaps = arena_take<float>(h, BS * iters * k);
-  unsigned char* conv = arena_take<unsigned char>(h, BS * iters);
-  float* sT = arena_take<float>(h, BS * 16);
-  int* counts = arena_take<int>(h, BS);
-  float* fit = arena_take<float>(h, BS);
-  int* best = arena_take<int>(h, B);
-  double* hsum = arena_take<double>(h, BS * 15);
-  int* stop_it = arena_take<int>(h, 1);
-  const gmf::PairTab* ptab = nullptr;
+  float *fimg, *dmat, *keys, *snaps, *sT, *fit;
+  int *seeds, *knn, *counts, *best, *stop_it;
+  unsigned char* conv;
+  double* hsum;
+  gmf::PairTab* ptab;
+  if (int rc = arena_carve(h, {arena_buf(fimg, (size_t)B * tiles_of(N) * kTileFloats),
+                               arena_buf(dmat, BS * tiles_of(N) * 32),       // distance rows of the seeds, padded to whole tiles
+                               arena_buf(keys, (size_t)B * N), arena_buf(seeds, BS), arena_buf(knn, BS * k),
+                               arena_buf(snaps, BS * iters * k), arena_buf(conv, BS * iters), arena_buf(sT, BS * 16),
+                               arena_buf(counts, BS), arena_buf(fit, BS), arena_buf(best, (size_t)B), arena_buf(hsum, BS * 15),
+                               arena_buf(stop_it, 1), arena_buf(ptab, ragged ? (size_t)B : 0)}))
+    return rc;
   if (ragged) {
-    gmf::PairTab* dtab = arena_take<gmf::PairTab>(h, (size_t)B);
-    if (int rc = upload_pair_table(h, dtab, B, st)) return rc;
-    ptab = dtab;
+    if (int rc = upload_pair_table(h, ptab, B, st)) return rc;
     // per-seed outputs are [B, S_max, ...] slots: the slots behind a pair's own seeds are defined (zero), not left-over memory
     if (seeds_out) GMF_HIP(hipMemsetAsync(seeds_out, 0, BS * sizeof(int), st));
     if (knn_out) GMF_HIP(hipMemsetAsync(knn_out, 0, BS * k * sizeof(int), st));
@@ -1152,9 +1138,9 @@ int gmf_knn_rows(gmf_handle* h, const float* feat_n, const int* rows, int B, int
   const size_t cap = (size_t)1 << 30;                           // floats
   const bool whole = (size_t)B * Sn * ld <= cap;
   const int slice = whole ? Sn : (int)std::max<size_t>(1, std::min<size_t>((size_t)Sn, cap / ld));
-  if (int rc = arena_reserve(h, arena_need((size_t)B * tiles * kTileFloats, 4) + arena_need((size_t)(whole ? B : 1) * slice * ld, 4))) return rc;
-  float* fimg = arena_take<float>(h, (size_t)B * tiles * kTileFloats);
-  float* dmat = arena_take<float>(h, (size_t)(whole ? B : 1) * slice * ld);
+  float *fimg, *dmat;
+  if (int rc = arena_carve(h, {arena_buf(fimg, (size_t)B * tiles * kTileFloats), arena_buf(dmat, (size_t)(whole ? B : 1) * slice * ld)}))
+    return rc;
   GMF_HIP(gmf::launch_pack_rows_h2(feat_n, fimg, B, N, st, nullptr));
   if (whole) {
     GMF_HIP(gmf::launch_seed_dist(fimg, rows, dmat, B, N, Sn, st, nullptr));
@@ -1180,11 +1166,14 @@ int gmf_nn_match(gmf_handle* h, const float* F0, const float* F1, int N0, int N1
   GMF_REQUIRE(K > 0, GMF_ERR_UNSUPPORTED_SHAPE, "nn_match: descriptor width above 128 is not supported");
   SetDevice sd(h, stream);
   const size_t n0 = (size_t)tiles_of(N0) * 32 * K, n1 = (size_t)tiles_of(N1) * 32 * K + 4096;
-  if (int rc = arena_reserve(h, arena_need(n0, 4) + arena_need(n1, 4) + arena_need((size_t)tiles_of(N1) * 32, 4) + arena_need((size_t)N0, 8))) return rc;
-  float* i0 = arena_take<float>(h, n0);
-  float* i1 = arena_take<float>(h, n1);      // + one stage of slack: the last stage may be read past the final tile
-  float* nb = arena_take<float>(h, (size_t)tiles_of(N1) * 32);       // whole tiles: the padding holds +inf
-  unsigned long long* best = arena_take<unsigned long long>(h, (size_t)N0);     // (score, index) of every row's winner: one atomic minimum per key split
+  float *i0, *i1, *nb;
+  unsigned long long* best;
+  if (int rc = arena_carve(h, {arena_buf(i0, n0),
+                               arena_buf(i1, n1),      // + one stage of slack: the last stage may be read past the final tile
+                               arena_buf(nb, (size_t)tiles_of(N1) * 32),       // whole tiles: the padding holds +inf
+                               // (score, index) of every row's winner: one atomic minimum per key split
+                               arena_buf(best, (size_t)N0)}))
+    return rc;
   GMF_HIP(gmf::launch_nn_match(F0, F1, i0, i1, nb, best, idx_out, dist_out, N0, N1, d, mode, S(stream)));
   return GMF_OK;
 }
@@ -1374,10 +1363,10 @@ int gmf_ransac_correspondence(gmf_handle* h, const float* src, const float* tgt,
   GMF_REQUIRE(tau > 0.f && std::isfinite(tau), GMF_ERR_BAD_ARG, "ransac_correspondence: max_correspondence_distance must be > 0");
   GMF_REQUIRE(first_pair >= 0, GMF_ERR_BAD_ARG, "ransac_correspondence: first_pair must be >= 0");
   SetDevice sd(h, stream);
-  const size_t need = gmf::ransac_scratch_bytes(total_rows, B, num_hypotheses);
-  if (int rc = arena_reserve(h, need)) return rc;
   gmf::RansacScratch ws;
-  gmf::ransac_scratch_carve(arena_take<char>(h, need), total_rows, B, num_hypotheses, ws);
+  ArenaList bufs;
+  gmf::ransac_scratch_list(total_rows, B, num_hypotheses, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
   GMF_HIP(gmf::launch_ransac(src, tgt, offsets, mask, B, total_rows, max_rows > 0 ? max_rows : (int)total_rows, ransac_n,
                              num_hypotheses, tau, seed, first_pair, ws, T_out, inliers, fitness, inlier_rmse, hypothesis, sample,
                              S(stream)));
@@ -1395,10 +1384,10 @@ int gmf_icp_point_to_point(gmf_handle* h, const float* src, const int* src_offse
   GMF_REQUIRE(tau > 0.f && std::isfinite(tau), GMF_ERR_BAD_ARG, "icp_point_to_point: max_correspondence_distance must be > 0");
   GMF_REQUIRE(max_iter >= 0 && max_iter <= 100000, GMF_ERR_BAD_ARG, "icp_point_to_point: max_iteration must be in 0..100000");
   SetDevice sd(h, stream);
-  const size_t need = gmf::icp_scratch_bytes(total_src, B);
-  if (int rc = arena_reserve(h, need)) return rc;
   gmf::IcpScratch ws;
-  gmf::icp_scratch_carve(arena_take<char>(h, need), total_src, B, ws);
+  ArenaList bufs;
+  gmf::icp_scratch_list(total_src, B, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
   GMF_HIP(gmf::launch_icp(src, src_offsets, tgt, tgt_offsets, B, total_src, max_src > 0 ? max_src : (int)total_src,
                           max_tgt > 0 ? max_tgt : (int)total_src, init, tau, max_iter, rel_fitness, rel_rmse, ws, T_out, fitness,
                           inlier_rmse, iterations, nn, S(stream)));
@@ -1425,12 +1414,12 @@ int gmf_icp_point_to_point_ex(gmf_handle* h, const float* src, const int* src_of
     return gmf_icp_point_to_point(h, src, src_offsets, tgt, tgt_offsets, B, total_src, max_src, max_tgt, init, tau, max_iter,
                                   rel_fitness, rel_rmse, T_out, fitness, inlier_rmse, iterations, nn, stream);
   SetDevice sd(h, stream);
-  const size_t icp = gmf::icp_scratch_bytes(total_src, B), grid = gmf::knn_scratch_bytes(total_tgt);
-  if (int rc = arena_reserve(h, icp + grid + 256)) return rc;
   gmf::IcpScratch ws;
   gmf::KnnScratch gs;
-  gmf::icp_scratch_carve(arena_take<char>(h, icp), total_src, B, ws);
-  gmf::knn_scratch_carve(arena_take<char>(h, grid), total_tgt, gs);
+  ArenaList bufs;
+  gmf::icp_scratch_list(total_src, B, ws, bufs);
+  gmf::knn_scratch_list(total_tgt, gs, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
   GMF_HIP(gmf::launch_icp(src, src_offsets, tgt, tgt_offsets, B, total_src, max_src > 0 ? max_src : (int)total_src,
                           max_tgt > 0 ? max_tgt : (int)total_tgt, init, tau, max_iter, rel_fitness, rel_rmse, ws, T_out, fitness,
                           inlier_rmse, iterations, nn, S(stream), &gs, total_tgt));
@@ -1466,13 +1455,12 @@ int gmf_ransac_feature_matching(gmf_handle* h, const float* src, const int* src_
   GMF_REQUIRE(search == 0 || total_tgt < (1LL << 29), GMF_ERR_UNSUPPORTED_SHAPE,
               "ransac_feature_matching: the grid search takes fewer than 2^29 target rows");
   SetDevice sd(h, stream);
-  const size_t fm = gmf::fm_scratch_bytes(total_src, B, max_iteration, max_validation);
-  const size_t grid = search ? gmf::knn_scratch_bytes(total_tgt) : 0;
-  if (int rc = arena_reserve(h, fm + grid + 256)) return rc;
   gmf::FmScratch ws;
   gmf::KnnScratch gs;
-  gmf::fm_scratch_carve(arena_take<char>(h, fm), total_src, B, max_iteration, max_validation, ws);
-  if (search) gmf::knn_scratch_carve(arena_take<char>(h, grid), total_tgt, gs);
+  ArenaList bufs;
+  gmf::fm_scratch_list(total_src, B, max_iteration, max_validation, ws, bufs);
+  if (search) gmf::knn_scratch_list(total_tgt, gs, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
   if (hyp) ws.hyp = hyp;
   if (count) ws.cnt = reinterpret_cast<unsigned*>(count);
   if (sum) ws.sq = reinterpret_cast<unsigned long long*>(sum);
@@ -1510,10 +1498,10 @@ int gmf_radius_knn(gmf_handle* h, const float* pts, const int* offsets, int B, l
   if (int rc = check_cloud_args(h, "radius_knn", pts, offsets, B, total_rows, radius, max_nn)) return rc;
   GMF_REQUIRE(idx && count, GMF_ERR_BAD_ARG, "radius_knn: null pointer");
   SetDevice sd(h, stream);
-  const size_t need = gmf::knn_scratch_bytes(total_rows);
-  if (int rc = arena_reserve(h, need)) return rc;
   gmf::KnnScratch ws;
-  gmf::knn_scratch_carve(arena_take<char>(h, need), total_rows, ws);
+  ArenaList bufs;
+  gmf::knn_scratch_list(total_rows, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
   GMF_HIP(gmf::launch_radius_knn(pts, offsets, B, total_rows, radius, max_nn, ws, idx, d2, count, S(stream)));
   return GMF_OK;
 }
@@ -1562,8 +1550,8 @@ int gmf_similarity_matrix(gmf_handle* h, const float* feat_n, int B, int N, floa
   GMF_REQUIRE(sigma != 0.f || h->sigma_dev, GMF_ERR_BAD_ARG, "similarity_matrix: sigma must be non-zero");
   SetDevice sd(h, stream);
   const size_t n_img = gmf::similarity_image_floats(B, N);
-  if (int rc = arena_reserve(h, arena_need(n_img, 4))) return rc;
-  float* img = arena_take<float>(h, n_img);
+  float* img;
+  if (int rc = arena_carve(h, {arena_buf(img, n_img)})) return rc;
   GMF_HIP(gmf::launch_similarity_matrix(feat_n, img, M, B, N, ldm, sigma, S(stream), h->sigma_dev));
   return GMF_OK;
 }
@@ -1575,9 +1563,8 @@ int gmf_spectral_matching_loss(gmf_handle* h, const float* M, int ldm, const flo
   GMF_REQUIRE(ldm >= N, GMF_ERR_BAD_ARG, "spectral_matching_loss: ldm (row stride of M in floats) must be >= N");
   SetDevice sd(h, stream);
   const size_t n_part = (size_t)2 * B * gmf::sm_parts_per_pair(B, N);
-  if (int rc = arena_reserve(h, arena_need(n_part, 8) + arena_need((size_t)B, 8))) return rc;
-  double* part = arena_take<double>(h, n_part);
-  double* pair_loss = arena_take<double>(h, (size_t)B);
+  double *part, *pair_loss;
+  if (int rc = arena_carve(h, {arena_buf(part, n_part), arena_buf(pair_loss, (size_t)B)})) return rc;
   GMF_HIP(gmf::launch_sm_loss(M, ldm, gt_labels, part, pair_loss, B, N, balanced, loss_out, S(stream)));
   return GMF_OK;
 }
@@ -1590,10 +1577,9 @@ int gmf_spectral_matching_loss_fused(gmf_handle* h, const float* feat_n, const f
   SetDevice sd(h, stream);
   const size_t n_img = gmf::similarity_image_floats(B, N);
   const size_t n_part = (size_t)2 * B * gmf::sm_fused_parts_per_pair(B, N);
-  if (int rc = arena_reserve(h, arena_need(n_img, 4) + arena_need(n_part, 8) + arena_need((size_t)B, 8))) return rc;
-  float* img = arena_take<float>(h, n_img);
-  double* part = arena_take<double>(h, n_part);
-  double* pair_loss = arena_take<double>(h, (size_t)B);
+  float* img;
+  double *part, *pair_loss;
+  if (int rc = arena_carve(h, {arena_buf(img, n_img), arena_buf(part, n_part), arena_buf(pair_loss, (size_t)B)})) return rc;
   GMF_HIP(gmf::launch_sm_loss_fused(feat_n, gt_labels, img, part, pair_loss, B, N, sigma, balanced, loss_out, S(stream), h->sigma_dev));
   return GMF_OK;
 }
@@ -1606,11 +1592,10 @@ int gmf_spectral_matching_backward(gmf_handle* h, const float* feat_n, const flo
   SetDevice sd(h, stream);
   const size_t n_img = gmf::similarity_image_floats(B, N);
   const size_t n_part = (size_t)gmf::sm_backward_parts(B, N);
-  if (int rc = arena_reserve(h, 2 * arena_need(n_img, 4) + arena_need((size_t)4 * B, 4) + arena_need(n_part, 8))) return rc;
-  float* img = arena_take<float>(h, n_img);
-  float* timg = arena_take<float>(h, n_img);
-  float* consts = arena_take<float>(h, (size_t)4 * B);
-  double* part = arena_take<double>(h, n_part);
+  float *img, *timg, *consts;
+  double* part;
+  if (int rc = arena_carve(h, {arena_buf(img, n_img), arena_buf(timg, n_img), arena_buf(consts, (size_t)4 * B), arena_buf(part, n_part)}))
+    return rc;
   GMF_HIP(gmf::launch_sm_backward(feat_n, gt_labels, img, timg, consts, part, B, N, sigma, balanced, d_feat_n, d_sigma, S(stream), h->sigma_dev));
   return GMF_OK;
 }
@@ -1621,8 +1606,8 @@ int gmf_classification_loss(gmf_handle* h, const float* pred, const float* gt, c
   GMF_REQUIRE(B > 0 && N > 0, GMF_ERR_UNSUPPORTED_SHAPE, "classification_loss: empty input");
   SetDevice sd(h, stream);
   const size_t n_part = (size_t)9 * gmf::classification_parts(B, N);
-  if (int rc = arena_reserve(h, arena_need(n_part, 8))) return rc;
-  double* part = arena_take<double>(h, n_part);
+  double* part;
+  if (int rc = arena_carve(h, {arena_buf(part, n_part)})) return rc;
   GMF_HIP(gmf::launch_classification_loss(pred, gt, weight, part, B, N, balanced, out6, S(stream)));
   return GMF_OK;
 }
@@ -1635,8 +1620,8 @@ int gmf_transformation_loss(gmf_handle* h, const float* trans, const float* gt_t
   GMF_REQUIRE(B > 0 && N > 0, GMF_ERR_UNSUPPORTED_SHAPE, "transformation_loss: empty input");
   SetDevice sd(h, stream);
   const size_t n_part = (size_t)3 * B * gmf::transformation_slices(B, N);
-  if (int rc = arena_reserve(h, arena_need(n_part, 8))) return rc;
-  double* part = arena_take<double>(h, n_part);
+  double* part;
+  if (int rc = arena_carve(h, {arena_buf(part, n_part)})) return rc;
   GMF_HIP(gmf::launch_transformation_loss(trans, gt_trans, src_keypts, tgt_keypts, probs, part, B, N, re_thre, te_thre,
                                           out5, S(stream)));
   return GMF_OK;

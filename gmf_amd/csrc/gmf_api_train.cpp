@@ -23,11 +23,8 @@ int gmf_gemm_f32(gmf_handle* h, int trans_a, int trans_b, const float* A, const 
   SetDevice sd(h, stream);
   const int ksplits = gmf::gemm_ksplits(trans_a != 0, trans_b != 0, A, B, M, N, K, (long)lda, (long)ldb, (long)stride_a, (long)stride_b, batch);
   GMF_REQUIRE((long long)batch * ksplits <= 65535, GMF_ERR_UNSUPPORTED_SHAPE, "gemm_f32: batch * k-splits exceeds 65535 workgroups in z: split the batch");
-  float* part = nullptr;
-  if (ksplits > 1) {
-    if (int rc = arena_reserve(h, arena_need((size_t)batch * ksplits * M * N, 4))) return rc;
-    part = arena_take<float>(h, (size_t)batch * ksplits * M * N);
-  }
+  float* part;          // split-K partials
+  if (int rc = arena_carve(h, {arena_buf(part, ksplits > 1 ? (size_t)batch * ksplits * M * N : 0)})) return rc;
   GMF_HIP(gmf::launch_gemm_f32(trans_a != 0, trans_b != 0, A, B, C, bias, residual, M, N, K, (long)lda, (long)ldb, (long)ldc,
                                (long)stride_a, (long)stride_b, (long)stride_c, batch, alpha, part, ksplits, relu ? 1 : 0, S(stream)));
   return GMF_OK;
@@ -88,8 +85,8 @@ int gmf_colsum(gmf_handle* h, const float* x, const float* y, const float* mean,
   SetDevice sd(h, stream);
   GMF_REQUIRE(!dual || y, GMF_ERR_BAD_ARG, "colsum: dual needs y (without y both sums are the same)");
   const size_t n_part = (size_t)gmf::colsum_chunks((long)rows) * C * (dual ? 2 : 1);
-  if (int rc = arena_reserve(h, arena_need(n_part, 4))) return rc;
-  float* part = arena_take<float>(h, n_part);
+  float* part;
+  if (int rc = arena_carve(h, {arena_buf(part, n_part)})) return rc;
   GMF_REQUIRE(!center_x || cmean, GMF_ERR_BAD_ARG, "colsum: center_x needs cmean");
   GMF_HIP(gmf::launch_colsum(x, y, mean, rstd, cmean, crstd, center_x ? 1 : 0, shift, L, (long)rows, C, part, out, S(stream), relu_y,
                              dual != 0));
@@ -104,10 +101,8 @@ int gmf_batchnorm_train_forward(gmf_handle* h, const float* x, const float* gamm
   GMF_REQUIRE(rows > 1 && C > 0, GMF_ERR_UNSUPPORTED_SHAPE, "batchnorm_train_forward: need more than one row");
   SetDevice sd(h, stream);
   const size_t n_part = (size_t)gmf::colsum_chunks((long)rows) * C;
-  if (int rc = arena_reserve(h, arena_need(n_part, 4) + 2 * arena_need((size_t)C, 4))) return rc;
-  float* part = arena_take<float>(h, n_part);
-  float* sum = arena_take<float>(h, (size_t)C);
-  float* sumsq = arena_take<float>(h, (size_t)C);
+  float *part, *sum, *sumsq;
+  if (int rc = arena_carve(h, {arena_buf(part, n_part), arena_buf(sum, (size_t)C), arena_buf(sumsq, (size_t)C)})) return rc;
   hipStream_t st = S(stream);
   GMF_HIP(gmf::launch_colsum(x, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)rows, (long)rows, C, part, sum, st));
   GMF_HIP(gmf::launch_bn_finish(sum, nullptr, mean, rstd, nullptr, nullptr, C, (long)rows, eps, momentum, st));
@@ -125,8 +120,8 @@ int gmf_batchnorm_train_backward(gmf_handle* h, const float* dy, const float* x,
   GMF_REQUIRE(rows > 1 && C > 0, GMF_ERR_UNSUPPORTED_SHAPE, "batchnorm_train_backward: need more than one row");
   SetDevice sd(h, stream);
   const size_t n_part = (size_t)gmf::colsum_chunks((long)rows) * C * 2;
-  if (int rc = arena_reserve(h, arena_need(n_part, 4))) return rc;
-  float* part = arena_take<float>(h, n_part);
+  float* part;
+  if (int rc = arena_carve(h, {arena_buf(part, n_part)})) return rc;
   hipStream_t st = S(stream);
   // ONE pass over dy: dgamma = sum g xhat, dbeta = sum g, with g = dy masked by the output of the ReLU that followed
   GMF_HIP(gmf::launch_colsum(dy, x, nullptr, nullptr, mean, rstd, 0, 0, (int)rows, (long)rows, C, part, dgamma, st, y_relu, true, dbeta));
@@ -156,8 +151,8 @@ int gmf_classification_backward(gmf_handle* h, const float* pred, const float* g
   GMF_REQUIRE(h && pred && gt && d_pred, GMF_ERR_BAD_ARG, "classification_backward: null pointer");
   GMF_REQUIRE(B > 0 && N > 0, GMF_ERR_UNSUPPORTED_SHAPE, "classification_backward: empty input");
   SetDevice sd(h, stream);
-  if (int rc = arena_reserve(h, arena_need(1, 4))) return rc;
-  float* pw = arena_take<float>(h, 1);
+  float* pw;
+  if (int rc = arena_carve(h, {arena_buf(pw, 1)})) return rc;
   GMF_HIP(gmf::launch_bce_bwd(pred, gt, weight, d_pred, pw, balanced, (long)B * N, S(stream)));
   return GMF_OK;
 }
@@ -167,8 +162,8 @@ int gmf_spectral_matching_dense_backward(gmf_handle* h, const float* M, int ldm,
   GMF_REQUIRE(h && M && gt_labels && dM, GMF_ERR_BAD_ARG, "spectral_matching_dense_backward: null pointer");
   GMF_REQUIRE(B > 0 && N > 0 && ldm >= N, GMF_ERR_UNSUPPORTED_SHAPE, "spectral_matching_dense_backward: need ldm >= N > 0");
   SetDevice sd(h, stream);
-  if (int rc = arena_reserve(h, arena_need((size_t)4 * B, 4))) return rc;
-  float* consts = arena_take<float>(h, (size_t)4 * B);
+  float* consts;
+  if (int rc = arena_carve(h, {arena_buf(consts, (size_t)4 * B)})) return rc;
   GMF_HIP(gmf::launch_sm_dense_bwd(M, ldm, gt_labels, consts, dM, B, N, balanced, S(stream)));
   return GMF_OK;
 }
@@ -181,11 +176,8 @@ int gmf_similarity_backward(gmf_handle* h, const float* feat_n, const float* dM,
   SetDevice sd(h, stream);
   const size_t nn = (size_t)B * N * N, rows = (size_t)B * N;
   const size_t n_part = (size_t)gmf::colsum_chunks((long)rows);
-  if (int rc = arena_reserve(h, 2 * arena_need(nn, 4) + arena_need(rows, 4) + arena_need(n_part, 4))) return rc;
-  float* Sm = arena_take<float>(h, nn);
-  float* G = arena_take<float>(h, nn);
-  float* rowdsig = arena_take<float>(h, rows);
-  float* part = arena_take<float>(h, n_part);
+  float *Sm, *G, *rowdsig, *part;
+  if (int rc = arena_carve(h, {arena_buf(Sm, nn), arena_buf(G, nn), arena_buf(rowdsig, rows), arena_buf(part, n_part)})) return rc;
   hipStream_t st = S(stream);
   const long ld = 128, sF = (long)N * 128, sN = (long)N * N;
   // S = Fn Fn^T per pair, G = dM * [0 <= u <= 1] / sigma^2, dFn = G Fn + G^T Fn, dsigma = sum of the row partials
@@ -230,11 +222,10 @@ int gmf_pose_head_backward(gmf_handle* h, const gmf_pose_params* p, const float*
   SetDevice sd(h, stream);
   hipStream_t st = S(stream);
   const size_t BS = (size_t)B * Sn;
-  if (int rc = arena_reserve(h, arena_need(BS * iters * k, 4) + arena_need(BS * iters, 1) + arena_need(1, 4)))
-    return rc;
-  float* snaps = arena_take<float>(h, BS * iters * k);
-  unsigned char* conv = arena_take<unsigned char>(h, BS * iters);
-  int* stop_it = arena_take<int>(h, 1);
+  float* snaps;
+  unsigned char* conv;
+  int* stop_it;
+  if (int rc = arena_carve(h, {arena_buf(snaps, BS * iters * k), arena_buf(conv, BS * iters), arena_buf(stop_it, 1)})) return rc;
   // the forward's iterates and convergence flags of every seed (the stop iteration is a property of all seeds of a pair)
   GMF_HIP(gmf::launch_seed_power(feat_n, src_keypts, tgt_keypts, knn_idx, snaps, conv, nullptr, B, N, Sn, k, iters, p->sigma, p->sigma_d, st, nullptr, h->sigma_dev));
   GMF_HIP(hipMemsetAsync(d_feat_n, 0, (size_t)B * N * kC * sizeof(float), st));

@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "arena_list.hpp"
+
 namespace gmf {
 
 constexpr int kKnnMaxNN = 256;      // largest max_nn of the radius search (the per-wave LDS survivor buffer)
@@ -19,12 +21,13 @@ struct KnnScratch {
   int* cnt;                   // [T + 1] rows per slot (zeroed; the scatter counts it back down)
   int* start;                 // [T + 1] exclusive scan of cnt: slot s holds rows start[s] .. start[s+1)
   float4* cell_pts;           // [N] the rows in slot order, .w = the row's index (bits)
-  void* scan_tmp;             // hipcub scan storage
+  char* scan_tmp;             // hipcub scan storage
   size_t scan_bytes;
 };
 
-size_t knn_scratch_bytes(long long N);
-void knn_scratch_carve(void* base, long long N, KnnScratch& s);
+// Appends the scratch of a search over N rows to a call's workspace list (arena_carve then fills the pointers); T and
+// scan_bytes are set here.
+void knn_scratch_list(long long N, KnnScratch& s, ArenaList& bufs);
 // The table alone, for a search of one's own (ICP's, solver_kernels.hip): one memset, k_grid_count, the scan, k_grid_scatter.
 // h: the cell edge; the slot of a row is cell_hash(its cloud, its cell) & (T - 1) (grid_hash.hpp).  Fills start and cell_pts.
 hipError_t launch_grid_build(const float* pts, const int* offsets, int B, long long N, double h, const KnnScratch& ws,
@@ -51,12 +54,12 @@ struct VoxelScratch {
   int* vstart;                // [N + 1] first sorted position of each voxel
   double* lo;                 // [B * 3] voxel grid origin of each cloud
   int* flag;                  // [1] nonzero: a voxel index outside int32, or a non-finite coordinate
-  void* tmp;                  // hipcub scan / sort storage
+  char* tmp;                  // hipcub scan / sort storage
   size_t tmp_bytes;
 };
 
-size_t voxel_scratch_bytes(long long N, int B);
-void voxel_scratch_carve(void* base, long long N, int B, VoxelScratch& s);
+// Appends the scratch of a voxel grid over N rows of B clouds to a call's workspace list; T and tmp_bytes are set here.
+void voxel_scratch_list(long long N, int B, VoxelScratch& s, ArenaList& bufs);
 // mean = true: voxel_down_sample (origin min - v/2, out_pts [nv, 3] the fp64 means stored as fp32); false: voxel_select
 // (origin 0, out_idx [nv] the smallest row of each voxel, within its cloud).  out_offsets [B + 1].  Writes the voxel count and
 // the range flag to `host2` after synchronising the stream.

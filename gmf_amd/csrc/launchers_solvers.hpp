@@ -17,14 +17,12 @@ struct RansacScratch {
   float4* cq;                 // [total_rows] the matching target rows
   int* cidx;                  // [total_rows] row number within the pair of each compacted row
   int* m;                     // [B] participating rows per pair
-  unsigned* cnt;              // [B * H] inlier count per hypothesis
-  unsigned long long* sq;     // [B * H] sum of the inliers' d^2 in units of tau^2 / 2^24 (integer: order-free)
-  unsigned char* valid;       // [B * H] 1 = the hypothesis's fit succeeded
+  unsigned char* board;       // the scoreboard of the B * H hypotheses, cleared by one memset (RansacBoard, solver_kernels.hip)
   float* thyp;                // [B * H * 12] the hypothesis's [R | t] as scored
 };
 
-size_t ransac_scratch_bytes(long long total_rows, int B, int H);
-void ransac_scratch_carve(void* base, long long total_rows, int B, int H, RansacScratch& s);
+// Appends the scratch to a call's workspace list (arena_carve then fills the pointers).
+void ransac_scratch_list(long long total_rows, int B, int H, RansacScratch& s, ArenaList& bufs);
 hipError_t launch_ransac(const float* src, const float* tgt, const int* offsets, const unsigned char* mask, int B,
                          long long total_rows, int max_rows, int ransac_n, int H, float tau, uint64_t seed, int first_pair,
                          const RansacScratch& ws, float* T_out, unsigned char* inliers, float* fitness, float* rmse,
@@ -38,9 +36,8 @@ struct IcpScratch {
   int* done;                  // [B]
 };
 
-size_t icp_scratch_bytes(long long total_src, int B);
-void icp_scratch_carve(void* base, long long total_src, int B, IcpScratch& s);
-// grid: null = the brute-force search (k_icp_nn).  Otherwise a KnnScratch carved for total_tgt rows (all targets of the batch):
+void icp_scratch_list(long long total_src, int B, IcpScratch& s, ArenaList& bufs);
+// grid: null = the brute-force search (k_icp_nn).  Otherwise a KnnScratch listed for total_tgt rows (all targets of the batch):
 // the call builds the hashed grid over the targets first (launch_grid_build) and searches it (k_icp_nn_grid), bit-identically.
 hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, const int* tgt_off, int B, long long total_src,
                       int max_src, int max_tgt, const float* init, float tau, int max_iter, double rel_fitness, double rel_rmse,
@@ -59,10 +56,9 @@ struct FmScratch {
   unsigned long long* key;    // [total_src] the winner's packed (d^2 bits | target row) per source row
 };
 
-size_t fm_scratch_bytes(long long total_src, int B, int H, int V);
-void fm_scratch_carve(void* base, long long total_src, int B, int H, int V, FmScratch& s);
+void fm_scratch_list(long long total_src, int B, int H, int V, FmScratch& s, ArenaList& bufs);
 // nn [total_src]: the feature-space nearest target row of every source row, numbered within the pair.  checker_distance < 0 and
-// edge_length <= 0 switch the checkers off.  grid: null = every target streams through LDS; otherwise a KnnScratch carved for
+// edge_length <= 0 switch the checkers off.  grid: null = every target streams through LDS; otherwise a KnnScratch listed for
 // total_tgt rows, built here (launch_grid_build) and searched, bit-identically.  validated [B]: hypotheses evaluated per pair.
 hipError_t launch_ransac_feature_matching(const float* src, const int* src_off, const float* tgt, const int* tgt_off,
                                           const long long* nn, int B, long long total_src, long long total_tgt, int max_src,

@@ -39,8 +39,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 
-size_t a256(size_t v) { return (v + 255) / 256 * 256; }
-
 long long table_slots(long long N) {
   long long T = 64;
   while (T < 2 * N) T <<= 1;
@@ -640,23 +638,15 @@ int blocks(long long n, int per) { return (int)((n + per - 1) / per); }
 // host side
 // ---------------------------------------------------------------------------------------------------------------------------
 
-size_t knn_scratch_bytes(long long N) {
-  const long long T = table_slots(N);
-  size_t scan = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan, (int*)nullptr, (int*)nullptr, (int)(T + 1));
-  return a256(N * 4) + 2 * a256((T + 1) * 4) + a256(N * 16) + a256(scan) + 256;
-}
-
-void knn_scratch_carve(void* base, long long N, KnnScratch& s) {
-  char* p = static_cast<char*>(base);
+void knn_scratch_list(long long N, KnnScratch& s, ArenaList& bufs) {
   s.T = table_slots(N);
-  s.slot = reinterpret_cast<int*>(p); p += a256(N * 4);
-  s.cnt = reinterpret_cast<int*>(p); p += a256((s.T + 1) * 4);
-  s.start = reinterpret_cast<int*>(p); p += a256((s.T + 1) * 4);
-  s.cell_pts = reinterpret_cast<float4*>(p); p += a256(N * 16);
   s.scan_bytes = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, s.scan_bytes, (int*)nullptr, (int*)nullptr, (int)(s.T + 1));
-  s.scan_tmp = p;
+  bufs.add(s.slot, (size_t)N);
+  bufs.add(s.cnt, (size_t)s.T + 1);
+  bufs.add(s.start, (size_t)s.T + 1);
+  bufs.add(s.cell_pts, (size_t)N);
+  bufs.add(s.scan_tmp, s.scan_bytes);
 }
 
 hipError_t launch_grid_build(const float* pts, const int* offsets, int B, long long N, double h, const KnnScratch& ws,
@@ -696,34 +686,23 @@ hipError_t launch_fpfh(const float* pts, const float* normals, const int* offset
   return hipGetLastError();
 }
 
-static size_t voxel_tmp_bytes(long long N) {
+void voxel_scratch_list(long long N, int B, VoxelScratch& s, ArenaList& bufs) {
   size_t scan = 0, sort = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan, (int*)nullptr, (int*)nullptr, (int)(N + 1));
   (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)N);
-  return scan > sort ? scan : sort;
-}
-
-size_t voxel_scratch_bytes(long long N, int B) {
-  const long long T = table_slots(N);
-  return 2 * a256(T * 4) + a256(N * 4) + 2 * a256((N + 1) * 4) + 2 * a256(N * 8) + a256((N + 1) * 4) + a256((size_t)B * 24) +
-         a256(4) + a256(voxel_tmp_bytes(N)) + 256;
-}
-
-void voxel_scratch_carve(void* base, long long N, int B, VoxelScratch& s) {
-  char* p = static_cast<char*>(base);
   s.T = table_slots(N);
-  s.table = reinterpret_cast<int*>(p); p += a256(s.T * 4);
-  s.rep = reinterpret_cast<int*>(p); p += a256(s.T * 4);
-  s.slot = reinterpret_cast<int*>(p); p += a256(N * 4);
-  s.head = reinterpret_cast<int*>(p); p += a256((N + 1) * 4);
-  s.vid = reinterpret_cast<int*>(p); p += a256((N + 1) * 4);
-  s.key = reinterpret_cast<unsigned long long*>(p); p += a256(N * 8);
-  s.key_sorted = reinterpret_cast<unsigned long long*>(p); p += a256(N * 8);
-  s.vstart = reinterpret_cast<int*>(p); p += a256((N + 1) * 4);
-  s.lo = reinterpret_cast<double*>(p); p += a256((size_t)B * 24);
-  s.flag = reinterpret_cast<int*>(p); p += a256(4);
-  s.tmp = p;
-  s.tmp_bytes = voxel_tmp_bytes(N);
+  s.tmp_bytes = scan > sort ? scan : sort;
+  bufs.add(s.table, (size_t)s.T);
+  bufs.add(s.rep, (size_t)s.T);
+  bufs.add(s.slot, (size_t)N);
+  bufs.add(s.head, (size_t)N + 1);
+  bufs.add(s.vid, (size_t)N + 1);
+  bufs.add(s.key, (size_t)N);
+  bufs.add(s.key_sorted, (size_t)N);
+  bufs.add(s.vstart, (size_t)N + 1);
+  bufs.add(s.lo, (size_t)B * 3);
+  bufs.add(s.flag, 1);
+  bufs.add(s.tmp, s.tmp_bytes);
 }
 
 hipError_t launch_voxel(const float* pts, const int* offsets, int B, long long N, double voxel, bool mean,

@@ -284,30 +284,31 @@ k_ransac_finish(const float* __restrict__ src, const float* __restrict__ tgt, co
   }
 }
 
-size_t ransac_scratch_bytes(long long total_rows, int B, int H) {
-  const size_t BH = (size_t)B * H;
-  auto a = [](size_t v) { return (v + 255) / 256 * 256; };
-  return a(total_rows * 16) * 2 + a(total_rows * 4) + a((size_t)B * 4) + a(BH * 4) + a(BH * 8) + a(BH) + a(BH * 48) + 256;
-}
+// The scoreboard of a call's B * H hypotheses: one workspace buffer, so that one memset clears it.
+struct RansacBoard {
+  unsigned long long* sq;     // [B * H] sum of the inliers' d^2 in units of tau^2 / 2^24 (integer: order-free)
+  unsigned* cnt;              // [B * H] inlier count per hypothesis
+  unsigned char* valid;       // [B * H] 1 = the hypothesis's fit succeeded
+  static constexpr size_t kBytesPerHyp = 8 + 4 + 1;
+  RansacBoard(unsigned char* base, size_t BH)
+      : sq(reinterpret_cast<unsigned long long*>(base)), cnt(reinterpret_cast<unsigned*>(sq + BH)),
+        valid(reinterpret_cast<unsigned char*>(cnt + BH)) {}
+};
 
-void ransac_scratch_carve(void* base, long long total_rows, int B, int H, RansacScratch& s) {
+void ransac_scratch_list(long long total_rows, int B, int H, RansacScratch& s, ArenaList& bufs) {
   const size_t BH = (size_t)B * H;
-  auto a = [](size_t v) { return (v + 255) / 256 * 256; };
-  char* p = static_cast<char*>(base);
-  s.cs = reinterpret_cast<float4*>(p); p += a(total_rows * 16);
-  s.cq = reinterpret_cast<float4*>(p); p += a(total_rows * 16);
-  s.cidx = reinterpret_cast<int*>(p); p += a(total_rows * 4);
-  s.m = reinterpret_cast<int*>(p); p += a((size_t)B * 4);
-  s.sq = reinterpret_cast<unsigned long long*>(p); p += a(BH * 8);       // cnt, sq, valid adjacent: one memset
-  s.cnt = reinterpret_cast<unsigned*>(p); p += a(BH * 4);
-  s.valid = reinterpret_cast<unsigned char*>(p); p += a(BH);
-  s.thyp = reinterpret_cast<float*>(p);
+  bufs.add(s.cs, (size_t)total_rows);
+  bufs.add(s.cq, (size_t)total_rows);
+  bufs.add(s.cidx, (size_t)total_rows);
+  bufs.add(s.m, (size_t)B);
+  bufs.add(s.board, BH * RansacBoard::kBytesPerHyp);
+  bufs.add(s.thyp, BH * 12);
 }
 
 template <int NS>
 static void launch_ransac_n(const float* src, const float* tgt, const int* off, const unsigned char* mask, int B, int max_rows,
-                            int H, float tau, uint64_t seed, int first_pair, const RansacScratch& ws, float* T_out,
-                            unsigned char* inliers, float* fitness, float* rmse, long long* hyp, long long* sample, hipStream_t s) {
+                            int H, float tau, uint64_t seed, int first_pair, const RansacScratch& ws, const RansacBoard& bd,
+                            float* T_out, unsigned char* inliers, float* fitness, float* rmse, long long* hyp, long long* sample, hipStream_t s) {
   const int hb = (H + kThreads - 1) / kThreads;
   // split the rows when B * hb workgroups alone would leave CUs idle: about 2048 workgroups in all, every split >= 1 tile
   const long long wg = (long long)hb * B;
@@ -317,9 +318,9 @@ static void launch_ransac_n(const float* src, const float* tgt, const int* off, 
   const float qscale = 16777216.0f / tau2;
   hipLaunchKernelGGL(k_ransac_compact, dim3(B), dim3(kThreads), 0, s, src, tgt, off, mask, ws.cs, ws.cq, ws.cidx, ws.m);
   hipLaunchKernelGGL(k_ransac_score<NS>, dim3((unsigned)wg, Y), dim3(kThreads), 0, s, ws.cs, ws.cq, off, ws.m, H, hb,
-                     (unsigned long long)seed, first_pair, tau2, qscale, ws.cnt, ws.sq, ws.valid, ws.thyp);
+                     (unsigned long long)seed, first_pair, tau2, qscale, bd.cnt, bd.sq, bd.valid, ws.thyp);
   hipLaunchKernelGGL(k_ransac_finish<NS>, dim3(B), dim3(kThreads), 0, s, src, tgt, off, mask, ws.cidx, ws.m, H,
-                     (unsigned long long)seed, first_pair, tau2, ws.cnt, ws.sq, ws.valid, ws.thyp, T_out, inliers, fitness, rmse,
+                     (unsigned long long)seed, first_pair, tau2, bd.cnt, bd.sq, bd.valid, ws.thyp, T_out, inliers, fitness, rmse,
                      hyp, sample);
 }
 
@@ -328,13 +329,13 @@ hipError_t launch_ransac(const float* src, const float* tgt, const int* offsets,
                          const RansacScratch& ws, float* T_out, unsigned char* inliers, float* fitness, float* rmse,
                          long long* hypothesis, long long* sample, hipStream_t s) {
   const size_t BH = (size_t)B * H;
-  // sq, cnt and valid are adjacent in the scratch (ransac_scratch_carve)
-  hipError_t e = hipMemsetAsync(ws.sq, 0, reinterpret_cast<char*>(ws.valid + BH) - reinterpret_cast<char*>(ws.sq), s);
+  const RansacBoard bd(ws.board, BH);
+  hipError_t e = hipMemsetAsync(ws.board, 0, BH * RansacBoard::kBytesPerHyp, s);
   if (e != hipSuccess) return e;
   (void)total_rows;
 #define GMF_RANSAC_CASE(n) \
-  case n: launch_ransac_n<n>(src, tgt, offsets, mask, B, max_rows, H, tau, seed, first_pair, ws, T_out, inliers, fitness, rmse, \
-                             hypothesis, sample, s); break;
+  case n: launch_ransac_n<n>(src, tgt, offsets, mask, B, max_rows, H, tau, seed, first_pair, ws, bd, T_out, inliers, fitness, \
+                             rmse, hypothesis, sample, s); break;
   switch (ransac_n) {
     GMF_RANSAC_CASE(3) GMF_RANSAC_CASE(4) GMF_RANSAC_CASE(5) GMF_RANSAC_CASE(6) GMF_RANSAC_CASE(7) GMF_RANSAC_CASE(8)
     default: return hipErrorInvalidValue;
@@ -558,18 +559,11 @@ k_icp_step(const float* __restrict__ src, const int* __restrict__ soff, const fl
   }
 }
 
-size_t icp_scratch_bytes(long long total_src, int B) {
-  auto a = [](size_t v) { return (v + 255) / 256 * 256; };
-  return a(total_src * 8) + a((size_t)B * 96) + a((size_t)B * 16) + a((size_t)B * 4) + 256;
-}
-
-void icp_scratch_carve(void* base, long long total_src, int B, IcpScratch& s) {
-  auto a = [](size_t v) { return (v + 255) / 256 * 256; };
-  char* p = static_cast<char*>(base);
-  s.key = reinterpret_cast<unsigned long long*>(p); p += a(total_src * 8);
-  s.T = reinterpret_cast<double*>(p); p += a((size_t)B * 96);
-  s.prev = reinterpret_cast<double*>(p); p += a((size_t)B * 16);
-  s.done = reinterpret_cast<int*>(p);
+void icp_scratch_list(long long total_src, int B, IcpScratch& s, ArenaList& bufs) {
+  bufs.add(s.key, (size_t)total_src);
+  bufs.add(s.T, (size_t)B * 12);
+  bufs.add(s.prev, (size_t)B * 2);
+  bufs.add(s.done, (size_t)B);
 }
 
 hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, const int* tgt_off, int B, long long total_src,
@@ -913,25 +907,16 @@ k_fm_finish(const int* __restrict__ soff, int V, unsigned long long seed, int fi
   }
 }
 
-static size_t fm_align(size_t v) { return (v + 255) / 256 * 256; }
-
-size_t fm_scratch_bytes(long long total_src, int B, int H, int V) {
+void fm_scratch_list(long long total_src, int B, int H, int V, FmScratch& s, ArenaList& bufs) {
   const size_t Hs = ((size_t)H + 3) / 4 * 4, BV = (size_t)B * V;
-  return fm_align((size_t)B * Hs) + fm_align((size_t)B * H * 48) + fm_align(BV * 4) * 2 + fm_align(BV * 8) + fm_align(BV * 48) +
-         fm_align((size_t)B * 4) + fm_align((size_t)total_src * 8) + 256;
-}
-
-void fm_scratch_carve(void* base, long long total_src, int B, int H, int V, FmScratch& s) {
-  const size_t Hs = ((size_t)H + 3) / 4 * 4, BV = (size_t)B * V;
-  char* p = static_cast<char*>(base);
-  s.pass = reinterpret_cast<unsigned char*>(p); p += fm_align((size_t)B * Hs);
-  s.thyp = reinterpret_cast<float*>(p); p += fm_align((size_t)B * H * 48);
-  s.hyp = reinterpret_cast<int*>(p); p += fm_align(BV * 4);
-  s.cnt = reinterpret_cast<unsigned*>(p); p += fm_align(BV * 4);
-  s.sq = reinterpret_cast<unsigned long long*>(p); p += fm_align(BV * 8);
-  s.tval = reinterpret_cast<float*>(p); p += fm_align(BV * 48);
-  s.win = reinterpret_cast<int*>(p); p += fm_align((size_t)B * 4);
-  s.key = reinterpret_cast<unsigned long long*>(p);
+  bufs.add(s.pass, (size_t)B * Hs);
+  bufs.add(s.thyp, (size_t)B * H * 12);
+  bufs.add(s.hyp, BV);
+  bufs.add(s.cnt, BV);
+  bufs.add(s.sq, BV);
+  bufs.add(s.tval, BV * 12);
+  bufs.add(s.win, (size_t)B);
+  bufs.add(s.key, (size_t)total_src);
 }
 
 template <bool GRID>

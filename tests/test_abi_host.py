@@ -434,3 +434,20 @@ def test_bench_dump_outputs_budget(tmp_path, monkeypatch):
         a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
         assert np.array_equal(a, b)
     assert set(np.load(tmp_path / "a" / "logits.npy").tolist()) <= set(lg.numpy().reshape(-1).tolist())
+
+
+def test_workspace_list_under_sanitizers(tmp_path):
+    """tests/abi_cpp/arena_list_host.cpp, a program of its own built with the host compiler and -fsanitize=address,undefined:
+    the sizing pass and the carving pass of csrc/arena_list.hpp over a malloc'ed block - aligned, apart, inside the block - with
+    every byte of every buffer written."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "arena_list_host")
+    build = subprocess.run([cxx, "-std=c++17", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            os.path.join(ROOT, "tests", "abi_cpp", "arena_list_host.cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and "arena_list_host: ok" in run.stdout, (run.stdout + run.stderr)[-2000:]
