@@ -11,6 +11,7 @@ from .common import rigid_transform_3d, knn      # noqa: F401
 from .registration import (weighted_procrustes, weighted_procrustes_batched, GlobalRegistration,  # noqa: F401
                            global_registration_batched, argmin_se3_squared_dist, Transformation, ortho2rotation)
 from .matching import nn_match, find_knn_gpu, find_knn_gpu_batch, find_knn_batch, find_pairs    # noqa: F401
+from .correspondences import nn_match_mutual, build_correspondences    # noqa: F401
 from . import se3 as SE3                         # noqa: F401
 from ._lib import check_status, set_handle_per_stream   # noqa: F401
 from .solvers import (ransac_correspondence_batched, icp_point_to_point_batched, RegistrationResult,  # noqa: F401
@@ -27,7 +28,7 @@ from .dgr import matching_indices_batched, find_correct_correspondence, generate
 from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss, similarity_matrix   # noqa: F401
 
 __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointDSC", "ImageEncoder",
-           "rigid_transform_3d", "knn", "weighted_procrustes", "weighted_procrustes_batched", "GlobalRegistration", "global_registration_batched", "argmin_se3_squared_dist", "Transformation", "ortho2rotation", "nn_match",
+           "rigid_transform_3d", "knn", "weighted_procrustes", "weighted_procrustes_batched", "GlobalRegistration", "global_registration_batched", "argmin_se3_squared_dist", "Transformation", "ortho2rotation", "nn_match", "nn_match_mutual", "build_correspondences",
            "find_knn_gpu", "SE3", "ClassificationLoss", "SpectralMatchingLoss", "TransformationLoss",
            "similarity_matrix", "check_status", "set_handle_per_stream", "ransac_correspondence_batched",
            "icp_point_to_point_batched", "RegistrationResult", "registration_ransac_based_on_correspondence", "registration_icp",

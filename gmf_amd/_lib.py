@@ -155,6 +155,9 @@ SIGNATURES = {
     "gmf_knn_from_distances": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "gmf_nn_match": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "gmf_nn_match_batched": (C.c_int, [_vp, _vp, _vp, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "gmf_nn_match_mutual_batched": (C.c_int, [_vp, _vp, _vp, _i32p, _i32p, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "gmf_build_correspondences": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_float,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gmf_matching_indices_count": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _ll, _ll, _vp, C.c_double, _vp, _vp, C.POINTER(_ll), _vp]),
     "gmf_matching_indices_fill": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _ll, _ll, _vp, C.c_double, _vp, _vp, _vp]),
     "gmf_inlier_input": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _ll, _vp, _vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp, _vp,

@@ -35,6 +35,7 @@ struct gmf_handle {
   static constexpr int kPtabSlots = 8;
   PtabSlot ptab_ring[kPtabSlots];
   int ptab_next = 0, ptab_cur = 0;
+  std::vector<void*> graph_tables;   // pinned tables that a captured upload (upload_ring_bytes) took out of the ring: freed with the handle
   // sticky status word in host-mapped memory (gmf_status_read): kernels OR bits into it through status_dev
   int* status_host = nullptr;
   int* status_dev = nullptr;

@@ -21,6 +21,7 @@
 #include "launchers_pointcloud.hpp"
 #include "launchers_sparse.hpp"
 #include "launchers_dgr_input.hpp"
+#include "launchers_correspondence.hpp"
 
 namespace {
 
@@ -315,6 +316,7 @@ void gmf_destroy(gmf_handle* h) {
     if (sl.ev) (void)hipEventDestroy(sl.ev);
     if (sl.host) (void)hipHostFree(sl.host);
   }
+  for (void* p : h->graph_tables) (void)hipHostFree(p);
   if (h->status_host) (void)hipHostFree(h->status_host);
   if (prev >= 0 && prev != h->device) (void)hipSetDevice(prev);
   delete h;
@@ -1204,7 +1206,17 @@ static int take_ring_bytes(gmf_handle* h, size_t bytes, void** host) {
 
 static int upload_ring_bytes(gmf_handle* h, void* dst, size_t bytes, hipStream_t st) {
   gmf_handle::PtabSlot& slot = h->ptab_ring[h->ptab_cur];
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(st, &cap);
   GMF_HIP(hipMemcpyAsync(dst, slot.host, bytes, hipMemcpyHostToDevice, st));
+  if (cap == hipStreamCaptureStatusActive) {
+    // a captured copy reads this very memory again at every replay: the slot gives the block up for the life of the handle (and
+    // allocates another when its turn comes again) instead of handing it to the call eight uploads from now
+    h->graph_tables.push_back(slot.host);
+    slot.host = nullptr;
+    slot.cap = 0;
+    return GMF_OK;
+  }
   GMF_HIP(hipEventRecord(slot.ev, st));
   slot.pending = true;
   return GMF_OK;
@@ -1241,6 +1253,100 @@ int gmf_nn_match_batched(gmf_handle* h, const float* F0, const float* F1, const 
   if (int rc = upload_ring_bytes(h, dtab, tab_bytes, S(stream))) return rc;
   GMF_HIP(gmf::launch_nn_match_batched(F0, F1, i0, i1, nb, best, dtab, B, tot, d, mode, global_index, idx_out, dist_out, S(stream)));
   return GMF_OK;
+}
+
+// gmf_nn_match_mutual_batched and gmf_build_correspondences: the checks of gmf_nn_match_batched, the two host plans (matching tables,
+// chunk table) in ONE ring slot and ONE upload, one workspace list, then the chain of launchers_correspondence.hpp
+static int run_correspondences(gmf_handle* h, const char* what, gmf::CorrArgs a, const int* off0, const int* off1, bool build,
+                               gmf_stream_t stream) {
+  const std::string w(what);
+  const int B = a.B, d = a.d;
+  GMF_REQUIRE(h && off0 && off1, GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(B > 0 && d > 0, GMF_ERR_UNSUPPORTED_SHAPE, w + ": empty batch");
+  const int K = gmf::padded_desc_width(d);
+  GMF_REQUIRE(K > 0, GMF_ERR_UNSUPPORTED_SHAPE, w + ": descriptor width above 128 is not supported");
+  GMF_REQUIRE(off0[0] == 0 && off1[0] == 0, GMF_ERR_BAD_ARG, w + ": offsets must start at 0");
+  for (int b = 0; b < B; ++b)
+    GMF_REQUIRE(off0[b + 1] >= off0[b] && off1[b + 1] >= off1[b], GMF_ERR_BAD_ARG, w + ": offsets must ascend");
+  if (build) {
+    GMF_REQUIRE(a.in_dim == 3 || a.in_dim == 6, GMF_ERR_UNSUPPORTED_SHAPE, w + ": in_dim must be 3 or 6");
+    GMF_REQUIRE(a.out_offsets, GMF_ERR_BAD_ARG, w + ": null pointer");
+    GMF_REQUIRE(!a.gt_trans || (a.inlier_threshold > 0 && std::isfinite(a.inlier_threshold)), GMF_ERR_BAD_ARG,
+                w + ": inlier_threshold must be > 0 and finite");
+  }
+  for (int b = 0; b < B; ++b)
+    GMF_REQUIRE(off0[b + 1] == off0[b] || off1[b + 1] > off1[b], GMF_ERR_UNSUPPORTED_SHAPE, w + ": a pair has query rows and no key rows");
+  if (off0[B] == 0) {                                    // no source rows: no output rows
+    if (build) {
+      SetDevice sd(h, stream);
+      GMF_HIP(hipMemsetAsync(a.out_offsets, 0, (size_t)(B + 1) * sizeof(int), S(stream)));
+    }
+    return GMF_OK;
+  }
+  GMF_REQUIRE(a.F0 && a.F1 && (build || (a.idx && a.dist && a.mutual)), GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(!build || (a.kp0 && a.kp1 && a.corr && a.src_out && a.tgt_out && a.corr_pos), GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(!a.gt_trans == !a.labels, GMF_ERR_BAD_ARG, w + ": gt_trans and labels_out go together");
+  GMF_REQUIRE(!a.src_desc_out == !a.tgt_desc_out, GMF_ERR_BAD_ARG, w + ": src_desc_out and tgt_desc_out go together");
+  SetDevice sd(h, stream);
+  // one ring slot: MatchPair [B + 1] | pair_chunk0 [B + 1] | CorrChunk [n_chunks], each part on a 16-byte boundary
+  const long n_chunks = gmf::corr_chunk_count(off0, B);
+  const size_t o_c0 = align_up((size_t)(B + 1) * sizeof(gmf::MatchPair), 16);
+  const size_t o_ck = o_c0 + align_up((size_t)(B + 1) * sizeof(int), 16);
+  const size_t tab_bytes = o_ck + (size_t)n_chunks * sizeof(gmf::CorrChunk);
+  void* host = nullptr;
+  if (int rc = take_ring_bytes(h, tab_bytes, &host)) return rc;
+  char* hb = static_cast<char*>(host);
+  gmf::MatchTotals tot;
+  GMF_REQUIRE(gmf::plan_nn_match_batched(off0, off1, B, K, reinterpret_cast<gmf::MatchPair*>(hb), &tot), GMF_ERR_UNSUPPORTED_SHAPE,
+              w + ": a pair has query rows and no key rows");
+  GMF_REQUIRE(tot.wgs < (1L << 31) && tot.stages * tot.tps * 32 < (1L << 31) && n_chunks < (1L << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              w + ": batch too large");
+  gmf::corr_plan_chunks(off0, B, reinterpret_cast<gmf::CorrChunk*>(hb + o_ck), reinterpret_cast<int*>(hb + o_c0));
+  const size_t rows0 = (size_t)tot.rows0, nck = (size_t)n_chunks;
+  char* dtab;
+  ArenaList bufs{arena_buf(a.f0_img, (size_t)tot.tiles0 * 32 * K), arena_buf(a.f1_img, (size_t)tot.stages * tot.tps * 32 * K),
+                 arena_buf(a.norm2, (size_t)tot.stages * tot.tps * 32), arena_buf(a.best, rows0),
+                 arena_buf(a.colbest, a.use_mutual ? (size_t)off1[B] : 0), arena_buf(dtab, tab_bytes)};
+  if (build) {                                           // (the caller of the flags alone brings idx, dist and mutual itself)
+    bufs.add(a.idx, rows0);
+    bufs.add(a.dist, rows0);
+    bufs.add(a.mutual, rows0);
+    bufs.add(a.rank, rows0);
+    bufs.add(a.chunk_cnt, nck);
+    bufs.add(a.chunk_sum, 6 * nck);
+    bufs.add(a.chunk_excl, nck);
+    bufs.add(a.mean, (size_t)6 * B);
+  }
+  if (int rc = arena_carve(h, bufs)) return rc;
+  if (int rc = upload_ring_bytes(h, dtab, tab_bytes, S(stream))) return rc;
+  a.tab = reinterpret_cast<const gmf::MatchPair*>(dtab);
+  a.pair_chunk0 = reinterpret_cast<const int*>(dtab + o_c0);
+  a.chunks = reinterpret_cast<const gmf::CorrChunk*>(dtab + o_ck);
+  a.n_chunks = (int)n_chunks;
+  a.n_keys = off1[B];
+  GMF_HIP(gmf::launch_corr_match(a, tot, S(stream)));
+  if (build) GMF_HIP(gmf::launch_corr_emit(a, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_nn_match_mutual_batched(gmf_handle* h, const float* F0, const float* F1, const int* off0, const int* off1, int B, int d,
+                                int* idx_out, float* dist_out, unsigned char* mutual_out, gmf_stream_t stream) {
+  gmf::CorrArgs a;
+  a.F0 = F0; a.F1 = F1; a.B = B; a.d = d; a.use_mutual = 1;
+  a.idx = idx_out; a.dist = dist_out; a.mutual = mutual_out;
+  return run_correspondences(h, "nn_match_mutual_batched", a, off0, off1, false, stream);
+}
+
+int gmf_build_correspondences(gmf_handle* h, const float* F0, const float* F1, const float* src_keypts, const float* tgt_keypts,
+                              const int* off0, const int* off1, int B, int d, int use_mutual, int in_dim, const float* gt_trans,
+                              float inlier_threshold, int* out_offsets, long long* corr_out, float* src_out, float* tgt_out,
+                              float* corr_pos_out, float* src_desc_out, float* tgt_desc_out, float* labels_out, gmf_stream_t stream) {
+  gmf::CorrArgs a;
+  a.F0 = F0; a.F1 = F1; a.kp0 = src_keypts; a.kp1 = tgt_keypts; a.B = B; a.d = d;
+  a.use_mutual = use_mutual ? 1 : 0; a.in_dim = in_dim; a.gt_trans = gt_trans; a.inlier_threshold = inlier_threshold;
+  a.out_offsets = out_offsets; a.corr = corr_out; a.src_out = src_out; a.tgt_out = tgt_out; a.corr_pos = corr_pos_out;
+  a.src_desc_out = src_desc_out; a.tgt_desc_out = tgt_desc_out; a.labels = labels_out;
+  return run_correspondences(h, "build_correspondences", a, off0, off1, true, stream);
 }
 
 // the checks gmf_matching_indices_count and _fill share

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include "mfma_core.hpp"
 #include "launchers.hpp"
+#include "match_common.hpp"
 
 namespace gmf {
 
@@ -182,17 +183,6 @@ hipError_t launch_nn_match(const float* F0, const float* F1, float* f0_img, floa
 // depend on the order the keys are met in, and the distance is recomputed from the winner: the results are those of B single calls,
 // bit for bit, whatever tiling and key splits the batch gets.
 
-// the pair whose range holds v: the largest b < B with begin(b) <= v (pairs with an empty range share their begin with the next)
-template <typename F>
-GMF_DEVINL int match_pair_of(int B, long v, F begin) {
-  int lo = 0, hi = B;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if ((long)begin(mid) <= v) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 // k_nn_match for workgroup blockIdx.x of the batch: its pair from the table, then (x, ks) inside the pair's wgx x ks workgroups; it
 // sweeps stages of its own pair only.  Indices are local to the pair.
 template <int KG>
@@ -310,11 +300,11 @@ GMF_DEVINL void pack_desc_batched(const long idx, const float* __restrict__ src,
   reinterpret_cast<float4*>(dst)[idx] = make_float4(v[0], v[1], v[2], v[3]);
 }
 
-// k_match_prep for the batch, the same four workgroup ranges
+// k_match_prep for the batch, the same four workgroup ranges (and a fifth when the caller keeps a column-side array)
 __global__ void k_match_prep_batched(const float* __restrict__ F0, const float* __restrict__ F1, float* __restrict__ f0_img,
                                      float* __restrict__ f1_img, float* __restrict__ n2, unsigned long long* __restrict__ best,
                                      const MatchPair* __restrict__ tab, int B, int tps, int N0, long n_norm, int d, int K, long n40, long n41,
-                                     int unit, int b0, int b1, int b2) {
+                                     int unit, int b0, int b1, int b2, int b3, unsigned long long* __restrict__ colbest, int N1) {
   const int blk = blockIdx.x;
   if (blk < b0) { pack_desc_batched((long)blk * 256 + threadIdx.x, F0, f0_img, tab, B, 0, tps, d, K, n40); return; }
   if (blk < b1) { pack_desc_batched((long)(blk - b0) * 256 + threadIdx.x, F1, f1_img, tab, B, 1, tps, d, K, n41); return; }
@@ -331,8 +321,14 @@ __global__ void k_match_prep_batched(const float* __restrict__ F0, const float* 
     n2[r] = s;
     return;
   }
-  const int r = (blk - b2) * 256 + threadIdx.x;
-  if (r < N0) best[r] = ~0ull;
+  if (blk < b3) {
+    const int r = (blk - b2) * 256 + threadIdx.x;
+    if (r < N0) best[r] = ~0ull;
+    return;
+  }
+  // [b3, ..): the column side of the two-sided sweep (correspondence_kernels.hip), one word per key row of the batch
+  const int r = (blk - b3) * 256 + threadIdx.x;
+  if (r < N1) colbest[r] = ~0ull;
 }
 
 static int match_stage_tiles(int K) { return (4096 / (32 * K)) > 0 ? (4096 / (32 * K)) : 1; }
@@ -365,19 +361,24 @@ bool plan_nn_match_batched(const int* off0, const int* off1, int B, int K, Match
   return true;
 }
 
-hipError_t launch_nn_match_batched(const float* F0, const float* F1, float* f0_img, float* f1_img, float* norm2, unsigned long long* best,
-                                   const MatchPair* tab, int B, const MatchTotals& tot, int d, int mode, int global_index, int* idx,
-                                   float* dist, hipStream_t s) {
+hipError_t launch_match_prep_batched(const float* F0, const float* F1, float* f0_img, float* f1_img, float* norm2, unsigned long long* best,
+                                     unsigned long long* colbest, int n_col, const MatchPair* tab, int B, const MatchTotals& tot, int d,
+                                     int mode, hipStream_t s) {
   const int K = padded_desc_width(d);
   if (K < 0) return hipErrorInvalidValue;
   const int N0 = (int)tot.rows0;
   const long n40 = tot.tiles0 * (K / 8) * 64, n41 = tot.stages * tot.tps * (K / 8) * 64, n_norm = tot.stages * tot.tps * 32;
-  {
-    const int b0 = (int)((n40 + 255) / 256), b1 = b0 + (int)((n41 + 255) / 256), b2 = b1 + (int)((n_norm + 255) / 256),
-              b3 = b2 + (N0 + 255) / 256;
-    hipLaunchKernelGGL(k_match_prep_batched, dim3(b3), dim3(256), 0, s, F0, F1, f0_img, f1_img, norm2, best, tab, B, tot.tps, N0, n_norm,
-                       d, K, n40, n41, mode == 0 ? 1 : 0, b0, b1, b2);
-  }
+  const int b0 = (int)((n40 + 255) / 256), b1 = b0 + (int)((n41 + 255) / 256), b2 = b1 + (int)((n_norm + 255) / 256),
+            b3 = b2 + (N0 + 255) / 256, b4 = b3 + (colbest ? (n_col + 255) / 256 : 0);
+  hipLaunchKernelGGL(k_match_prep_batched, dim3(b4), dim3(256), 0, s, F0, F1, f0_img, f1_img, norm2, best, tab, B, tot.tps, N0, n_norm,
+                     d, K, n40, n41, mode == 0 ? 1 : 0, b0, b1, b2, b3, colbest, n_col);
+  return hipGetLastError();
+}
+
+hipError_t launch_match_sweep_batched(const float* f0_img, const float* f1_img, const float* norm2, unsigned long long* best,
+                                      const MatchPair* tab, int B, const MatchTotals& tot, int d, hipStream_t s) {
+  const int K = padded_desc_width(d);
+  if (K < 0) return hipErrorInvalidValue;
   const dim3 grid((unsigned)tot.wgs);
   switch (K) {
     case 32: hipLaunchKernelGGL(k_nn_match_batched<4>, grid, dim3(256), 0, s, f0_img, f1_img, norm2, best, tab, B); break;
@@ -385,8 +386,16 @@ hipError_t launch_nn_match_batched(const float* F0, const float* F1, float* f0_i
     case 64: hipLaunchKernelGGL(k_nn_match_batched<8>, grid, dim3(256), 0, s, f0_img, f1_img, norm2, best, tab, B); break;
     default: hipLaunchKernelGGL(k_nn_match_batched<16>, grid, dim3(256), 0, s, f0_img, f1_img, norm2, best, tab, B); break;
   }
-  hipLaunchKernelGGL(k_nn_finish_batched, dim3((N0 + 255) / 256), dim3(256), 0, s, best, F0, F1, idx, dist, tab, B, N0, d, mode,
-                     global_index);
+  return hipGetLastError();
+}
+
+hipError_t launch_nn_match_batched(const float* F0, const float* F1, float* f0_img, float* f1_img, float* norm2, unsigned long long* best,
+                                   const MatchPair* tab, int B, const MatchTotals& tot, int d, int mode, int global_index, int* idx,
+                                   float* dist, hipStream_t s) {
+  if (hipError_t e = launch_match_prep_batched(F0, F1, f0_img, f1_img, norm2, best, nullptr, 0, tab, B, tot, d, mode, s)) return e;
+  if (hipError_t e = launch_match_sweep_batched(f0_img, f1_img, norm2, best, tab, B, tot, d, s)) return e;
+  hipLaunchKernelGGL(k_nn_finish_batched, dim3(((int)tot.rows0 + 255) / 256), dim3(256), 0, s, best, F0, F1, idx, dist, tab, B,
+                     (int)tot.rows0, d, mode, global_index);
   return hipGetLastError();
 }
 

@@ -433,6 +433,34 @@ int gmf_nn_match(gmf_handle* h, const float* F0, const float* F1, int N0, int N1
 int gmf_nn_match_batched(gmf_handle* h, const float* F0, const float* F1, const int* off0, const int* off1, int B, int d, int mode,
                          int global_index, int* idx_out, float* dist_out, gmf_stream_t stream);
 
+/* PointDSC matching of B ragged pairs with the mutual-nearest-neighbour flag (datasets/ThreeDMatch.py:164-170, KITTI.py:94-101):
+ * gmf_nn_match_batched in mode 0 without global_index - idx_out [off0[B]] int32 local to the pair and dist_out [off0[B]], bit for
+ * bit - plus mutual_out [off0[B]], one byte per source row: 1 where the row is the best source row of its own winner
+ * (target_idx[source_idx[i]] == i).  Every score is formed once and folded along its row and along its column; among equal scores
+ * the smaller index wins on both sides (numpy's first argmin).  A row without a winner (all scores NaN) is not mutual.  off0 / off1
+ * and the argument errors are those of gmf_nn_match_batched.  No host synchronisation and nothing read back: the call can be
+ * captured into a graph. */
+int gmf_nn_match_mutual_batched(gmf_handle* h, const float* F0, const float* F1, const int* off0, const int* off1, int B, int d,
+                                int* idx_out, float* dist_out, unsigned char* mutual_out, gmf_stream_t stream);
+
+/* The correspondence set of B ragged pairs from descriptors and keypoints, the body of PointDSC's loaders
+ * (datasets/ThreeDMatch.py:163-210, KITTI.py:94-129, demo_registration.py:101-107), in five launches whatever B: the matching above,
+ * the rows kept (use_mutual != 0: the mutual ones; 0: every row with a winner) compacted in source order, per pair.
+ * F0 [off0[B], d], F1 [off1[B], d] unit descriptors; src_keypts [off0[B], 3], tgt_keypts [off1[B], 3]; off0 / off1 HOST arrays as
+ * in gmf_nn_match_batched.  Outputs, all on the device, of capacity off0[B] rows, pair b owning rows [out_offsets[b],
+ * out_offsets[b + 1]) (out_offsets [B + 1] int32, written on the device):
+ *   corr_out [., 2] int64 (source row, target row), local to the pair; src_out / tgt_out [., 3] the gathered keypoints;
+ *   corr_pos_out [., in_dim]: in_dim 6 = (src, tgt) minus the pair's means over its kept rows, in_dim 3 = src - tgt;
+ *   src_desc_out / tgt_desc_out [., d] the gathered descriptor rows (both or neither; NULL: none);
+ *   labels_out [.] fp32 0 / 1 = |R x_src + t - x_tgt| < inlier_threshold with gt_trans [B, 4, 4] fp32 row-major on the device
+ *   (both or neither; NULL: none).
+ * Rows behind out_offsets[B] are left as they were.  A pair's results do not depend on the other pairs of the batch.  Errors as
+ * gmf_nn_match_batched; in_dim other than 3 or 6 is GMF_ERR_UNSUPPORTED_SHAPE.  No host synchronisation and nothing read back. */
+int gmf_build_correspondences(gmf_handle* h, const float* F0, const float* F1, const float* src_keypts, const float* tgt_keypts,
+                              const int* off0, const int* off1, int B, int d, int use_mutual, int in_dim, const float* gt_trans,
+                              float inlier_threshold, int* out_offsets, long long* corr_out, float* src_out, float* tgt_out,
+                              float* corr_pos_out, float* src_desc_out, float* tgt_desc_out, float* labels_out, gmf_stream_t stream);
+
 /* The ground-truth pairs of B registration problems (DGR get_matching_indices, util/pointcloud.py:83-96, by brute force): every
  * (i, j), local to pair b, with |R_b x0_i + t_b - x1_j|^2 < radius^2, ordered by i, then j.  xyz0 [total0, 3], xyz1 [total1, 3] fp32;
  * off0 / off1 [B + 1] int32 DEVICE offsets (ascending from 0 to the totals); T [B, 4, 4] fp64 row-major (device).  In fp64:
