@@ -25,6 +25,8 @@ from .sparse import (SparsePlan, sparse_conv, sparse_conv_narrow, sparse_head_l2
                      inlier_coordinates)
 from . import fcgf, dgr                          # noqa: F401  (gmf_amd.fcgf.ResUNetBN2C: FCGF; gmf_amd.ResUNetBN2C: the inlier net)
 from .dgr import matching_indices_batched, find_correct_correspondence, generate_inlier_input   # noqa: F401
+from .multiway import (information_matrix_batched, global_optimization, local_refinement_batched, loop_closure_mask,  # noqa: F401
+                       odometry_poses, absolute_trajectory_error, multiway_registration)
 from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss, similarity_matrix   # noqa: F401
 
 __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointDSC", "ImageEncoder",
@@ -37,4 +39,6 @@ __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointD
            "fpfh_descriptors", "SparsePlan", "sparse_conv", "sparse_conv_narrow", "sparse_head_l2", "ResUNetBN2C", "ResUNetBN2CX",
            "inlier_coordinates", "fcgf", "dgr", "find_knn_gpu_batch", "find_knn_batch", "find_pairs", "matching_indices_batched",
            "find_correct_correspondence", "generate_inlier_input", "ransac_feature_matching_batched",
-           "registration_ransac_based_on_feature_matching", "spectral_matching_batched", "SM"]
+           "registration_ransac_based_on_feature_matching", "spectral_matching_batched", "SM", "information_matrix_batched",
+           "global_optimization", "local_refinement_batched", "loop_closure_mask", "odometry_poses", "absolute_trajectory_error",
+           "multiway_registration"]

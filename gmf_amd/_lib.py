@@ -102,6 +102,14 @@ class PoseParams(C.Structure):
     ]
 
 
+class PoseGraphOptions(C.Structure):
+    """Mirror of `struct gmf_posegraph_options` (include/gmf_hip.h)."""
+    _fields_ = [("max_iteration", C.c_int), ("max_iteration_lm", C.c_int), ("reference_node", C.c_int),
+                ("min_relative_increment", C.c_double), ("min_relative_residual_increment", C.c_double),
+                ("min_right_term", C.c_double), ("min_residual", C.c_double),
+                ("edge_prune_threshold", C.c_double), ("preference_loop_closure", C.c_double)]
+
+
 # name -> (restype, argtypes).  Every symbol declared in include/gmf_hip.h appears here.
 SIGNATURES = {
     "gmf_abi_version": (C.c_int, []),
@@ -200,6 +208,9 @@ SIGNATURES = {
                                          C.c_double, C.c_double] + [_vp] * 6),
     "gmf_icp_point_to_point_ex": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _ll, C.c_int, C.c_int, _vp, C.c_float, C.c_int,
                                             C.c_double, C.c_double] + [_vp] * 5 + [_ll, C.c_int, _vp]),
+    "gmf_information_matrix": (C.c_int, [_vp, _vp, _i32p, C.c_int, _i32p, _i32p, C.c_int, _vp, C.c_float, _vp, _vp, _vp, _vp]),
+    "gmf_posegraph_optimize": (C.c_int, [_vp, _vp, _i32p, _i32p, C.c_int, _i32p, _i32p] + [_vp] * 4 + [C.POINTER(PoseGraphOptions)]
+                               + [_vp] * 6),
     "gmf_ransac_feature_matching": (C.c_int, [_vp] * 6 + [C.c_int, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                               C.c_float, C.c_float, C.c_ulonglong, C.c_int, C.c_int] + [_vp] * 11),
     "gmf_spectral_matching": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp]),
@@ -253,6 +264,7 @@ GMF_STATUS_NONFINITE = 1
 GMF_STATUS_PV_GUARDED = 2      # informational: the "pv_fp8" guard sent a (pair, layer) to the three-product form
 GMF_STATUS_SPARSE_DUPLICATE = 4   # gmf_sparse_build_plan met a duplicate (batch, coordinates) input row
 GMF_STATUS_BATCHNORM_ROWS = 8     # gmf_batchnorm_masked_forward met a level with fewer than 2 valid rows
+GMF_STATUS_POSEGRAPH_PIVOT = 16   # gmf_posegraph_optimize met a pivot of H + lambda I that was not finite or not positive
 
 
 class Handle:
@@ -327,6 +339,12 @@ class Handle:
             raise RuntimeError(
                 f"gmf_amd: {where}: a train-mode BatchNorm of an earlier call on this device had fewer than 2 valid rows "
                 "(torch: 'Expected more than 1 value per channel when training').  The outputs of that call are not valid.")
+        if f & GMF_STATUS_POSEGRAPH_PIVOT:
+            self.status(clear=True)
+            raise RuntimeError(
+                f"gmf_amd: {where}: a pose-graph optimisation of an earlier call on this device met a pivot of H + lambda I that "
+                "was not finite or not positive (stop code 6 in its stats): an information matrix is not positive semi-definite, "
+                "or a pose or measurement is not finite.  That graph's poses are those of its last accepted step.")
 
     def __del__(self):
         try:

@@ -22,6 +22,7 @@
 #include "launchers_sparse.hpp"
 #include "launchers_dgr_input.hpp"
 #include "launchers_correspondence.hpp"
+#include "launchers_posegraph.hpp"
 
 namespace {
 
@@ -1529,6 +1530,120 @@ int gmf_icp_point_to_point_ex(gmf_handle* h, const float* src, const int* src_of
   GMF_HIP(gmf::launch_icp(src, src_offsets, tgt, tgt_offsets, B, total_src, max_src > 0 ? max_src : (int)total_src,
                           max_tgt > 0 ? max_tgt : (int)total_tgt, init, tau, max_iter, rel_fitness, rel_rmse, ws, T_out, fitness,
                           inlier_rmse, iterations, nn, S(stream), &gs, total_tgt));
+  return GMF_OK;
+}
+
+// The host plan (chunk table, the edges' cloud indices, the cloud offsets) goes up in ONE ring slot and ONE upload.
+int gmf_information_matrix(gmf_handle* h, const float* points, const int* cloud_offsets, int F, const int* edge_source,
+                           const int* edge_target, int E, const double* transformation, float tau, double* info, int* count,
+                           long long* nn, gmf_stream_t stream) {
+  GMF_REQUIRE(h && points && cloud_offsets, GMF_ERR_BAD_ARG, "information_matrix: null pointer");
+  GMF_REQUIRE(F > 0 && E >= 0, GMF_ERR_BAD_ARG, "information_matrix: F must be > 0 and E >= 0");
+  GMF_REQUIRE(tau > 0.f && std::isfinite(tau), GMF_ERR_BAD_ARG, "information_matrix: max_correspondence_distance must be > 0");
+  GMF_REQUIRE(cloud_offsets[0] == 0, GMF_ERR_BAD_ARG, "information_matrix: cloud_offsets must start at 0");
+  for (int f = 0; f < F; ++f)
+    GMF_REQUIRE(cloud_offsets[f + 1] > cloud_offsets[f], GMF_ERR_BAD_ARG, "information_matrix: cloud_offsets must increase (no empty cloud)");
+  const long long N = cloud_offsets[F];
+  // the grid's table has the next power of two >= 2 N slots, and its slots and scan are indexed with int32
+  GMF_REQUIRE(N < (1LL << 29), GMF_ERR_UNSUPPORTED_SHAPE, "information_matrix: the grid takes fewer than 2^29 rows");
+  if (E == 0) return GMF_OK;
+  GMF_REQUIRE(edge_source && edge_target && transformation && info && count, GMF_ERR_BAD_ARG, "information_matrix: null pointer");
+  long out_rows = 0;
+  const long n_chunks = gmf::info_chunk_count(cloud_offsets, F, edge_source, edge_target, E, &out_rows);
+  GMF_REQUIRE(n_chunks != -1, GMF_ERR_BAD_ARG, "information_matrix: an edge names a cloud outside 0..F-1");
+  GMF_REQUIRE(n_chunks >= 0, GMF_ERR_UNSUPPORTED_SHAPE, "information_matrix: 2^31 or more source rows over the edges");
+  SetDevice sd(h, stream);
+  const size_t o_src = align_up((size_t)(F + 1) * sizeof(int), 16);
+  const size_t o_tgt = o_src + align_up((size_t)E * sizeof(int), 16);
+  const size_t o_c0 = o_tgt + align_up((size_t)E * sizeof(int), 16);
+  const size_t o_ck = o_c0 + align_up((size_t)(E + 1) * sizeof(int), 16);
+  const size_t tab_bytes = o_ck + (size_t)n_chunks * sizeof(gmf::InfoChunk);
+  void* host = nullptr;
+  if (int rc = take_ring_bytes(h, tab_bytes, &host)) return rc;
+  char* hb = static_cast<char*>(host);
+  std::memcpy(hb, cloud_offsets, (size_t)(F + 1) * sizeof(int));
+  std::memcpy(hb + o_src, edge_source, (size_t)E * sizeof(int));
+  std::memcpy(hb + o_tgt, edge_target, (size_t)E * sizeof(int));
+  gmf::info_plan_chunks(cloud_offsets, edge_source, E, reinterpret_cast<gmf::InfoChunk*>(hb + o_ck), reinterpret_cast<int*>(hb + o_c0));
+  gmf::InfoScratch ws;
+  char* dtab;
+  ArenaList bufs;
+  gmf::info_scratch_list(N, n_chunks, ws, bufs);
+  bufs.add(dtab, tab_bytes);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  if (int rc = upload_ring_bytes(h, dtab, tab_bytes, S(stream))) return rc;
+  GMF_HIP(gmf::launch_information_matrix(points, reinterpret_cast<const int*>(dtab), F, N, reinterpret_cast<const int*>(dtab + o_src),
+                                         reinterpret_cast<const int*>(dtab + o_tgt), E,
+                                         reinterpret_cast<const gmf::InfoChunk*>(dtab + o_ck), n_chunks,
+                                         reinterpret_cast<const int*>(dtab + o_c0), transformation, tau, ws, info, count, nn, S(stream)));
+  return GMF_OK;
+}
+
+// The host plan: node_off | edge_off | hoff | esrc | etgt | node_list0 | the per-node edge lists, in one ring slot.
+int gmf_posegraph_optimize(gmf_handle* h, double* poses, const int* node_offsets, const int* edge_offsets, int G,
+                           const int* edge_source, const int* edge_target, const double* edge_transformation,
+                           const double* edge_information, const unsigned char* edge_uncertain, const unsigned char* edge_mask,
+                           const gmf_posegraph_options* opt, double* line_process, unsigned char* kept, int* stats, double* residual,
+                           double* trace, gmf_stream_t stream) {
+  GMF_REQUIRE(h && poses && node_offsets && edge_offsets && opt && stats && residual, GMF_ERR_BAD_ARG, "posegraph_optimize: null pointer");
+  GMF_REQUIRE(G > 0, GMF_ERR_BAD_ARG, "posegraph_optimize: G must be > 0");
+  GMF_REQUIRE(opt->max_iteration >= 0 && opt->max_iteration <= 100000 && opt->max_iteration_lm >= 0 && opt->max_iteration_lm <= 100000,
+              GMF_ERR_BAD_ARG, "posegraph_optimize: max_iteration and max_iteration_lm must be in 0..100000");
+  GMF_REQUIRE(opt->preference_loop_closure > 0 && std::isfinite(opt->preference_loop_closure), GMF_ERR_BAD_ARG,
+              "posegraph_optimize: preference_loop_closure must be > 0");
+  const int M = edge_offsets[G];
+  GMF_REQUIRE(M == 0 || (edge_source && edge_target && edge_transformation && edge_information && edge_uncertain && line_process && kept),
+              GMF_ERR_BAD_ARG, "posegraph_optimize: null pointer");
+  const int bad = gmf::posegraph_check(node_offsets, edge_offsets, G, edge_source, edge_target);
+  GMF_REQUIRE(bad != -1, GMF_ERR_BAD_ARG, "posegraph_optimize: offsets must ascend from 0 and every graph needs a node");
+  GMF_REQUIRE(bad != -2, GMF_ERR_BAD_ARG, "posegraph_optimize: an edge names a node outside its graph");
+  GMF_REQUIRE(bad != -3, GMF_ERR_BAD_ARG, "posegraph_optimize: an edge joins a node to itself");
+  GMF_REQUIRE(bad == 0, GMF_ERR_UNSUPPORTED_SHAPE, "posegraph_optimize: a graph has more than 256 nodes or 65536 edges, which is what is built");
+  const int N = node_offsets[G];
+  SetDevice sd(h, stream);
+  const size_t o_eo = align_up((size_t)(G + 1) * sizeof(int), 16);
+  const size_t o_ho = o_eo + align_up((size_t)(G + 1) * sizeof(int), 16);
+  const size_t o_es = o_ho + align_up((size_t)(G + 1) * sizeof(long long), 16);
+  const size_t o_et = o_es + align_up((size_t)M * sizeof(int), 16);
+  const size_t o_n0 = o_et + align_up((size_t)M * sizeof(int), 16);
+  const size_t o_li = o_n0 + align_up((size_t)(N + 1) * sizeof(int), 16);
+  const size_t tab_bytes = o_li + (size_t)2 * M * sizeof(gmf::NodeEdge);
+  void* host = nullptr;
+  if (int rc = take_ring_bytes(h, tab_bytes, &host)) return rc;
+  char* hb = static_cast<char*>(host);
+  std::memcpy(hb, node_offsets, (size_t)(G + 1) * sizeof(int));
+  std::memcpy(hb + o_eo, edge_offsets, (size_t)(G + 1) * sizeof(int));
+  long long* hoff = reinterpret_cast<long long*>(hb + o_ho);
+  hoff[0] = 0;
+  for (int g = 0; g < G; ++g) {
+    const long long n6 = 6LL * (node_offsets[g + 1] - node_offsets[g]);
+    hoff[g + 1] = hoff[g] + n6 * n6;
+  }
+  const long long D = hoff[G];
+  if (M) {
+    std::memcpy(hb + o_es, edge_source, (size_t)M * sizeof(int));
+    std::memcpy(hb + o_et, edge_target, (size_t)M * sizeof(int));
+  }
+  gmf::posegraph_node_lists(node_offsets, edge_offsets, G, edge_source, edge_target, reinterpret_cast<int*>(hb + o_n0),
+                            reinterpret_cast<gmf::NodeEdge*>(hb + o_li));
+  gmf::PoseGraphScratch ws;
+  char* dtab;
+  ArenaList bufs;
+  gmf::posegraph_scratch_list(N, M, D, ws, bufs);
+  bufs.add(dtab, tab_bytes);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  if (int rc = upload_ring_bytes(h, dtab, tab_bytes, S(stream))) return rc;
+  gmf::PoseGraphOptions o;
+  o.max_iteration = opt->max_iteration; o.max_iteration_lm = opt->max_iteration_lm; o.reference_node = opt->reference_node;
+  o.min_relative_increment = opt->min_relative_increment;
+  o.min_relative_residual_increment = opt->min_relative_residual_increment;
+  o.min_right_term = opt->min_right_term; o.min_residual = opt->min_residual;
+  o.edge_prune_threshold = opt->edge_prune_threshold; o.preference_loop_closure = opt->preference_loop_closure;
+  GMF_HIP(gmf::launch_posegraph(poses, reinterpret_cast<const int*>(dtab), reinterpret_cast<const int*>(dtab + o_eo),
+                                reinterpret_cast<const long long*>(dtab + o_ho), G, reinterpret_cast<const int*>(dtab + o_es),
+                                reinterpret_cast<const int*>(dtab + o_et), edge_transformation, edge_information, edge_uncertain,
+                                edge_mask, reinterpret_cast<const int*>(dtab + o_n0), reinterpret_cast<const gmf::NodeEdge*>(dtab + o_li),
+                                o, ws, line_process, kept, stats, residual, trace, h->status_dev, GMF_STATUS_POSEGRAPH_PIVOT, S(stream)));
   return GMF_OK;
 }
 

@@ -83,6 +83,8 @@ long long gmf_workspace_wanted(gmf_handle* h);
 /* gmf_batchnorm_masked_forward met a level with fewer than 2 valid rows (torch's BatchNorm raises there): its outputs and
  * batch statistics are not valid and the running statistics were left unchanged. */
 #define GMF_STATUS_BATCHNORM_ROWS 8
+/* gmf_posegraph_optimize met a pivot of H + lambda I that was not finite or not positive (stop code 6 of that graph and pass) */
+#define GMF_STATUS_POSEGRAPH_PIVOT 16
 int gmf_status_read(gmf_handle* h, int* flags, int clear);
 
 /* [ABI 5] PointDSC's learnable scalar `sigma` (PointDSC.py:164) from DEVICE memory.  While `sigma_dev` is non-NULL every entry point
@@ -584,6 +586,42 @@ int gmf_ransac_feature_matching(gmf_handle* h, const float* src, const int* src_
                                 float edge_length_threshold, unsigned long long seed, int first_pair, int search, float* T_out,
                                 float* fitness, float* inlier_rmse, long long* hypothesis, long long* sample, long long* nn_out,
                                 int* validated, int* hyp, int* count, long long* sum, gmf_stream_t stream);
+
+/* ---- multiway registration (GMF_PointDSC/multiway/test_multi_ate.py) ------------------------------------
+
+ * open3d 0.9's get_information_matrix_from_point_clouds for E edges over F shared clouds.  points [sum N, 3] (device) holds the
+ * clouds packed once; cloud_offsets [F + 1], edge_source and edge_target [E] are HOST arrays (the call plans its chunks from
+ * them; cloud offsets increase strictly from 0).  transformation [E, 16] fp64 (device) maps the source cloud's rows into the
+ * target's frame.  C_e: the source rows whose transformed row has its exact nearest target row within tau, found as
+ * gmf_icp_point_to_point_ex(search = 1, max_iter = 0) finds it, bit for bit.  info [E, 36] fp64 = the sum over C_e of G^T G with
+ * G = [-[q]x | I] at the matched target row q, count [E] = |C_e|, nn (may be null) [the sum of the edges' source rows] the
+ * matched target row within its cloud or -1, edge after edge.  A transformation that is not finite gives zeros.  No floating-point
+ * atomics: an edge's numbers do not depend on the other edges of the call.  E == 0 is legal and does nothing. */
+int gmf_information_matrix(gmf_handle* h, const float* points, const int* cloud_offsets, int F, const int* edge_source,
+                           const int* edge_target, int E, const double* transformation, float tau, double* info, int* count,
+                           long long* nn, gmf_stream_t stream);
+
+/* open3d's GlobalOptimizationConvergenceCriteria and GlobalOptimizationOption */
+typedef struct gmf_posegraph_options {
+  int max_iteration, max_iteration_lm, reference_node;      /* open3d: 100, 20, -1 */
+  double min_relative_increment, min_relative_residual_increment, min_right_term, min_residual;   /* open3d: 1e-6 each */
+  double edge_prune_threshold, preference_loop_closure;     /* open3d: 0.25, 1.0 */
+} gmf_posegraph_options;
+
+/* open3d's global_optimization (Levenberg-Marquardt with a line process per uncertain edge, two passes with the pruning in
+ * between) for G ragged pose graphs, one workgroup each; the algorithm is written out in DESIGN.md section 4m.  node_offsets,
+ * edge_offsets [G + 1], edge_source, edge_target [m] (node indices within the graph) are HOST arrays.  Device: poses [n, 16] fp64
+ * in and out, edge_transformation [m, 16], edge_information [m, 36], edge_uncertain [m], edge_mask [m] or null (0: the edge is
+ * treated as absent), line_process [m] (0 for an edge that is masked or pruned), kept [m], stats [G, 2, 4] int32 (per pass: outer
+ * iterations, rejected steps, stop code, edges that took part), residual [G, 2], trace [G, 2, max_iteration + 1, 2] (residual and
+ * lambda after each outer iteration, NaN padded) or null.  Stop codes: 0 max_iteration, 1 min_right_term, 2 min_relative_increment,
+ * 3 min_relative_residual_increment, 4 min_residual, 5 max_iteration_lm, 6 a pivot was not positive (GMF_STATUS_POSEGRAPH_PIVOT is set).
+ * At most 256 nodes and 65536 edges per graph (GMF_ERR_UNSUPPORTED_SHAPE beyond). */
+int gmf_posegraph_optimize(gmf_handle* h, double* poses, const int* node_offsets, const int* edge_offsets, int G,
+                           const int* edge_source, const int* edge_target, const double* edge_transformation,
+                           const double* edge_information, const unsigned char* edge_uncertain, const unsigned char* edge_mask,
+                           const gmf_posegraph_options* opt, double* line_process, unsigned char* kept, int* stats, double* residual,
+                           double* trace, gmf_stream_t stream);
 
 /* The spectral-matching baseline SM(corr, src_keypts, tgt_keypts, args, top_ratio) of the reference's evaluation
  * (GMF_PointDSC/baseline_scripts/baseline_3DMatch.py:19-53; baseline_KITTI.py:51) over B ragged pairs, matrix-free: corr
