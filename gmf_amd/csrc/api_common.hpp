@@ -1,5 +1,5 @@
-// Private to the C-ABI translation units (gmf_api.cpp, gmf_api_train.cpp): the handle, the workspace arena and the
-// status helpers.  Not installed; the public interface is include/gmf_hip.h.
+// Private to the C-ABI translation units (gmf_api.cpp, gmf_api_train.cpp): the handle, the workspace arena, the ring of
+// pinned host-table slots and the status helpers.  Not installed; the public interface is include/gmf_hip.h.
 #pragma once
 #include "../../include/gmf_hip.h"
 
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "arena_list.hpp"
+#include "host_table.hpp"
 #include "launchers.hpp"
 
 struct gmf_handle {
@@ -28,14 +29,14 @@ struct gmf_handle {
   hipStream_t last_stream = nullptr;
   bool have_last_stream = false;
   hipEvent_t xs_event = nullptr;
-  // host copies of the per-pair tables of ragged calls: a ring of PINNED slots, each guarded by an event recorded behind its
-  // upload - a slot is only rewritten once the copy that read it has run (a pageable std::vector handed to
-  // hipMemcpyAsync is only safe if the runtime happens to stage it synchronously)
-  struct PtabSlot { gmf::PairTab* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool pending = false; };
+  // host copies of the host tables of ragged calls (host_table.hpp): a ring of PINNED slots of `cap` bytes, each guarded by an
+  // event recorded behind its upload - a slot is only rewritten once the copy that read it has run (a pageable
+  // std::vector handed to hipMemcpyAsync is only safe if the runtime happens to stage it synchronously).  ring_take, ring_upload
+  struct PtabSlot { void* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool pending = false; };
   static constexpr int kPtabSlots = 8;
   PtabSlot ptab_ring[kPtabSlots];
-  int ptab_next = 0, ptab_cur = 0;
-  std::vector<void*> graph_tables;   // pinned tables that a captured upload (upload_ring_bytes) took out of the ring: freed with the handle
+  int ptab_next = 0;
+  std::vector<void*> graph_tables;   // pinned tables that a captured upload (ring_upload) took out of the ring: freed with the handle
   // sticky status word in host-mapped memory (gmf_status_read): kernels OR bits into it through status_dev
   int* status_host = nullptr;
   int* status_dev = nullptr;
@@ -105,6 +106,51 @@ inline int arena_carve(gmf_handle* h, const ArenaList& bufs) {
   if (bufs.overflowed()) return fail(h, GMF_ERR_UNSUPPORTED_SHAPE, "gmf: a call lists more workspace buffers than ArenaList holds");
   if (int rc = arena_reserve(h, bufs.bytes())) return rc;
   bufs.place(h->arena);
+  return GMF_OK;
+}
+
+// A call's host table on its way to the device: the slot ring_take took, for the call to fill from `host` and hand to ring_upload.
+struct RingTaken { void* host = nullptr; size_t bytes = 0; int slot = 0; };
+
+// The next slot of the handle's pinned ring, grown to hold the listed table (in steps of 2 KiB).
+inline int ring_take(gmf_handle* h, const HostTable& tab, RingTaken* out) {
+  if (tab.overflowed()) return fail(h, GMF_ERR_UNSUPPORTED_SHAPE, "gmf: a call lists more host-table parts than HostTable holds");
+  const int cur = h->ptab_next;
+  h->ptab_next = (cur + 1) % gmf_handle::kPtabSlots;
+  gmf_handle::PtabSlot& slot = h->ptab_ring[cur];
+  if (slot.pending) {                         // (eight uploads ago: long done unless the host runs far ahead of the device)
+    GMF_HIP(hipEventSynchronize(slot.ev));
+    slot.pending = false;
+  }
+  if (slot.cap < tab.bytes()) {
+    if (slot.host) GMF_HIP(hipHostFree(slot.host));
+    slot.host = nullptr;
+    slot.cap = 0;
+    const size_t cap = align_up(tab.bytes(), 64 * sizeof(gmf::PairTab));
+    GMF_HIP(hipHostMalloc(&slot.host, cap, hipHostMallocDefault));
+    slot.cap = cap;
+  }
+  if (!slot.ev) GMF_HIP(hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming));
+  *out = RingTaken{slot.host, tab.bytes(), cur};
+  return GMF_OK;
+}
+
+// The slot just taken -> device, asynchronously on the call's stream; the slot's event marks the copy.
+inline int ring_upload(gmf_handle* h, const RingTaken& t, void* dst, hipStream_t st) {
+  gmf_handle::PtabSlot& slot = h->ptab_ring[t.slot];
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(st, &cap);
+  GMF_HIP(hipMemcpyAsync(dst, t.host, t.bytes, hipMemcpyHostToDevice, st));
+  if (cap == hipStreamCaptureStatusActive) {
+    // a captured copy reads this very memory again at every replay: the slot gives the block up for the life of the handle (and
+    // allocates another when its turn comes again) instead of handing it to the call eight uploads from now
+    h->graph_tables.push_back(slot.host);
+    slot.host = nullptr;
+    slot.cap = 0;
+    return GMF_OK;
+  }
+  GMF_HIP(hipEventRecord(slot.ev, st));
+  slot.pending = true;
   return GMF_OK;
 }
 

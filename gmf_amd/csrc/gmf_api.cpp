@@ -627,74 +627,11 @@ static int run_block_tail(gmf_handle* h, const gmf_encoder_weights* w, const Enc
   return run_scattn(h, w, p, l, q, k, v, pts8, x2, out, B, N, st, dense_compat, cc);
 }
 
-// Host table of a ragged batch -> the next slot of the handle's pinned ring; returns max n, sum n.
-// ratio < 0: the encoder's table (S, k unused).  The caller uploads it with upload_pair_table().
-static int build_pair_table(gmf_handle* h, const int* n_points, int B, double ratio, int k, int* n_max, long long* n_sum, int* s_max) {
-  for (int b = 0; b < B; ++b) {
-    GMF_REQUIRE(n_points[b] > 0, GMF_ERR_UNSUPPORTED_SHAPE, "ragged batch: every pair needs at least one correspondence");
-  }
-  h->ptab_cur = h->ptab_next;
-  h->ptab_next = (h->ptab_next + 1) % gmf_handle::kPtabSlots;
-  gmf_handle::PtabSlot& slot = h->ptab_ring[h->ptab_cur];
-  if (slot.pending) {                         // (eight uploads ago: long done unless the host runs far ahead of the device)
-    GMF_HIP(hipEventSynchronize(slot.ev));
-    slot.pending = false;
-  }
-  if (slot.cap < (size_t)B) {
-    if (slot.host) GMF_HIP(hipHostFree(slot.host));
-    slot.host = nullptr;
-    slot.cap = 0;
-    const size_t cap = ((size_t)B + 63) / 64 * 64;
-    GMF_HIP(hipHostMalloc(reinterpret_cast<void**>(&slot.host), cap * sizeof(gmf::PairTab), hipHostMallocDefault));
-    slot.cap = cap;
-  }
-  if (!slot.ev) GMF_HIP(hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming));
-  gmf::PairTab* tab = slot.host;
-  long long row = 0;
-  int nm = 0, sm = 0;
-  for (int b = 0; b < B; ++b) {
-    const int n = n_points[b];
-    GMF_REQUIRE(row + n <= 0x7fffffffLL, GMF_ERR_UNSUPPORTED_SHAPE, "ragged batch: more than 2^31 rows");
-    const int Sb = ratio >= 0.0 ? (int)((double)n * ratio) : 0;     // S = int(N * ratio)   PointDSC.py:244
-    tab[b] = gmf::PairTab{(int)row, n, Sb, k, b, 0, 0, 0};
-    row += n;
-    nm = n > nm ? n : nm;
-    sm = Sb > sm ? Sb : sm;
-  }
-  {
-    // slot -> pair: the pairs longest first, each into the XCD run (B / 8 consecutive slots; the first B % 8 runs hold one more) with
-    // the least n^2 so far that still has a free slot; within a run longest first (PairTab::ord, launchers.hpp)
-    std::vector<int> by_len(B);
-    for (int b = 0; b < B; ++b) by_len[b] = b;
-    std::stable_sort(by_len.begin(), by_len.end(), [&](int a, int c) { return n_points[a] > n_points[c]; });
-    const int runs = B < 8 ? 1 : 8;
-    std::vector<std::vector<int>> run(runs);
-    std::vector<double> load(runs, 0.0);
-    std::vector<int> cap(runs);
-    for (int r = 0; r < runs; ++r) cap[r] = B / runs + (r < B % runs ? 1 : 0);
-    for (int b : by_len) {
-      int best = -1;
-      for (int r = 0; r < runs; ++r)
-        if ((int)run[r].size() < cap[r] && (best < 0 || load[r] < load[best])) best = r;
-      run[best].push_back(b);
-      load[best] += (double)n_points[b] * (double)n_points[b];
-    }
-    int slot_i = 0;
-    for (int r = 0; r < runs; ++r)
-      for (int b : run[r]) tab[slot_i++].ord = b;
-  }
-  *n_max = nm;
-  *n_sum = row;
-  if (s_max) *s_max = sm;
-  return GMF_OK;
-}
-
-// the current slot -> device, asynchronously on the call's stream; the slot's event marks the copy
-static int upload_pair_table(gmf_handle* h, gmf::PairTab* dtab, int B, hipStream_t st) {
-  gmf_handle::PtabSlot& slot = h->ptab_ring[h->ptab_cur];
-  GMF_HIP(hipMemcpyAsync(dtab, slot.host, (size_t)B * sizeof(gmf::PairTab), hipMemcpyHostToDevice, st));
-  GMF_HIP(hipEventRecord(slot.ev, st));
-  slot.pending = true;
+// the sizes of a ragged batch (pair_plan.hpp), checked before the call takes a ring slot for its table
+static int check_ragged_sizes(gmf_handle* h, const int* n_points, int B) {
+  const gmf::PairPlanStatus bad = gmf::check_pair_sizes(n_points, B);
+  GMF_REQUIRE(bad != gmf::kPairPlanEmptyPair, GMF_ERR_UNSUPPORTED_SHAPE, "ragged batch: every pair needs at least one correspondence");
+  GMF_REQUIRE(bad != gmf::kPairPlanTooManyRows, GMF_ERR_UNSUPPORTED_SHAPE, "ragged batch: more than 2^31 rows");
   return GMF_OK;
 }
 
@@ -730,9 +667,14 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
   // ragged batch: per-pair sizes from the host; every image keeps a slot of tiles(max n) tiles per pair
   const bool ragged = n_points != nullptr;
   int min_tiles = 0;
+  HostTable tab;
+  const HostPart<gmf::PairTab> pairs = tab.add<gmf::PairTab>(ragged ? (size_t)B : 0);
+  RingTaken ring;
   if (ragged) {
     long long n_sum = 0;
-    if (int rc = build_pair_table(h, n_points, B, -1.0, 0, &N, &n_sum, nullptr)) return rc;
+    if (int rc = check_ragged_sizes(h, n_points, B)) return rc;
+    if (int rc = ring_take(h, tab, &ring)) return rc;
+    gmf::plan_pair_table(n_points, B, -1.0, 0, pairs.host(ring.host), &N, &n_sum, nullptr);
     min_tiles = tiles_of(*std::min_element(n_points, n_points + B));
   }
   const int L = w->num_layers;
@@ -743,11 +685,11 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
               "encoder_forward_ragged: ragged batches run on the default path only (split-fp16 weight images, at least two layers, the "
               "compat cache, \"fused_linear\" = 1, \"scattn_variant\" = 18)");
   const size_t act = p.act, tok = p.tok;
-  gmf::PairTab* ptab;
+  char* dtab;
   float *featA, *featB, *f, *q, *k, *v, *x1, *x2, *pts8, *pimg, *qimg, *f1ctx, *x1t, *imgfeat, *ctxall, *c_dense, *ff_part, *part_o,
       *part_ml;
   unsigned *v_scale, *fstat;
-  if (int rc = arena_carve(h, {arena_buf(ptab, ragged ? (size_t)B : 0), arena_buf(featA, act), arena_buf(featB, act), arena_buf(f, act),
+  if (int rc = arena_carve(h, {arena_buf(dtab, tab.bytes()), arena_buf(featA, act), arena_buf(featB, act), arena_buf(f, act),
                                arena_buf(q, act), arena_buf(k, act), arena_buf(v, act), arena_buf(x1, act), arena_buf(x2, act),
                                arena_buf(pts8, (size_t)B * tiles * 32 * 8), arena_buf(pimg, tok), arena_buf(qimg, tok),
                                arena_buf(f1ctx, tok), arena_buf(x1t, tok), arena_buf(imgfeat, tok),
@@ -762,7 +704,8 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
                                arena_buf(part_o, p.max_splits * act),
                                arena_buf(part_ml, (size_t)p.max_splits * B * tiles * 64)}))
     return rc;
-  if (int rc = ragged ? upload_pair_table(h, ptab, B, st) : GMF_OK) return rc;
+  if (int rc = ragged ? ring_upload(h, ring, dtab, st) : GMF_OK) return rc;
+  const gmf::PairTab* const ptab = ragged ? pairs.dev(dtab) : nullptr;
   gmf::CompatCache cc{c_dense, nullptr, part_o, part_ml};
   cc.half = p.half;
   cc.fmt = p.fmt;
@@ -1036,9 +979,14 @@ static int pose_head_impl(gmf_handle* h, const gmf_pose_params* p, const float* 
   const int k = p->k, iters = p->num_iterations;
   long long n_sum = (long long)B * N;
   SetDevice sd(h, stream);
+  HostTable tab;
+  const HostPart<gmf::PairTab> pairs = tab.add<gmf::PairTab>(ragged ? (size_t)B : 0);
+  RingTaken ring;
   if (ragged) {
     // per-pair sizes from the host: S = int(n * ratio) seeds each; N, Sn below are the largest pair's (grids, buffer strides)
-    if (int rc = build_pair_table(h, n_points, B, ratio, k, &N, &n_sum, &Sn)) return rc;
+    if (int rc = check_ragged_sizes(h, n_points, B)) return rc;
+    if (int rc = ring_take(h, tab, &ring)) return rc;
+    gmf::plan_pair_table(n_points, B, ratio, k, pairs.host(ring.host), &N, &n_sum, &Sn);
     for (int b = 0; b < B; ++b) {
       GMF_REQUIRE(n_points[b] > k, GMF_ERR_UNSUPPORTED_SHAPE, "pose_head_ragged: every pair needs more than k correspondences (k = min(k, N - 1) "
                                                                "per pair is not supported in a ragged batch: run such a pair on its own)");
@@ -1059,16 +1007,17 @@ static int pose_head_impl(gmf_handle* h, const gmf_pose_params* p, const float* 
   int *seeds, *knn, *counts, *best, *stop_it;
   unsigned char* conv;
   double* hsum;
-  gmf::PairTab* ptab;
+  char* dtab;
   if (int rc = arena_carve(h, {arena_buf(fimg, (size_t)B * tiles_of(N) * kTileFloats),
                                arena_buf(dmat, BS * tiles_of(N) * 32),       // distance rows of the seeds, padded to whole tiles
                                arena_buf(keys, (size_t)B * N), arena_buf(seeds, BS), arena_buf(knn, BS * k),
                                arena_buf(snaps, BS * iters * k), arena_buf(conv, BS * iters), arena_buf(sT, BS * 16),
                                arena_buf(counts, BS), arena_buf(fit, BS), arena_buf(best, (size_t)B), arena_buf(hsum, BS * 15),
-                               arena_buf(stop_it, 1), arena_buf(ptab, ragged ? (size_t)B : 0)}))
+                               arena_buf(stop_it, 1), arena_buf(dtab, tab.bytes())}))
     return rc;
+  const gmf::PairTab* const ptab = ragged ? pairs.dev(dtab) : nullptr;
   if (ragged) {
-    if (int rc = upload_pair_table(h, ptab, B, st)) return rc;
+    if (int rc = ring_upload(h, ring, dtab, st)) return rc;
     // per-seed outputs are [B, S_max, ...] slots: the slots behind a pair's own seeds are defined (zero), not left-over memory
     if (seeds_out) GMF_HIP(hipMemsetAsync(seeds_out, 0, BS * sizeof(int), st));
     if (knn_out) GMF_HIP(hipMemsetAsync(knn_out, 0, BS * k * sizeof(int), st));
@@ -1181,45 +1130,14 @@ int gmf_nn_match(gmf_handle* h, const float* F0, const float* F1, int N0, int N1
   return GMF_OK;
 }
 
-// `bytes` of the next slot of the handle's pinned ring (the slots of build_pair_table, for a host table of another type); the caller
-// fills it and uploads it with upload_ring_bytes()
-static int take_ring_bytes(gmf_handle* h, size_t bytes, void** host) {
-  h->ptab_cur = h->ptab_next;
-  h->ptab_next = (h->ptab_next + 1) % gmf_handle::kPtabSlots;
-  gmf_handle::PtabSlot& slot = h->ptab_ring[h->ptab_cur];
-  if (slot.pending) {
-    GMF_HIP(hipEventSynchronize(slot.ev));
-    slot.pending = false;
-  }
-  const size_t want = (bytes + sizeof(gmf::PairTab) - 1) / sizeof(gmf::PairTab);
-  if (slot.cap < want) {
-    if (slot.host) GMF_HIP(hipHostFree(slot.host));
-    slot.host = nullptr;
-    slot.cap = 0;
-    const size_t cap = (want + 63) / 64 * 64;
-    GMF_HIP(hipHostMalloc(reinterpret_cast<void**>(&slot.host), cap * sizeof(gmf::PairTab), hipHostMallocDefault));
-    slot.cap = cap;
-  }
-  if (!slot.ev) GMF_HIP(hipEventCreateWithFlags(&slot.ev, hipEventDisableTiming));
-  *host = slot.host;
-  return GMF_OK;
-}
-
-static int upload_ring_bytes(gmf_handle* h, void* dst, size_t bytes, hipStream_t st) {
-  gmf_handle::PtabSlot& slot = h->ptab_ring[h->ptab_cur];
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(st, &cap);
-  GMF_HIP(hipMemcpyAsync(dst, slot.host, bytes, hipMemcpyHostToDevice, st));
-  if (cap == hipStreamCaptureStatusActive) {
-    // a captured copy reads this very memory again at every replay: the slot gives the block up for the life of the handle (and
-    // allocates another when its turn comes again) instead of handing it to the call eight uploads from now
-    h->graph_tables.push_back(slot.host);
-    slot.host = nullptr;
-    slot.cap = 0;
-    return GMF_OK;
-  }
-  GMF_HIP(hipEventRecord(slot.ev, st));
-  slot.pending = true;
+// the checks the batched matching entries share: the descriptor width (-> *K, its padded width) and the two offset arrays
+static int check_pair_offsets(gmf_handle* h, const char* what, const int* off0, const int* off1, int B, int d, int* K) {
+  const std::string w(what);
+  *K = gmf::padded_desc_width(d);
+  GMF_REQUIRE(*K > 0, GMF_ERR_UNSUPPORTED_SHAPE, w + ": descriptor width above 128 is not supported");
+  GMF_REQUIRE(off0[0] == 0 && off1[0] == 0, GMF_ERR_BAD_ARG, w + ": offsets must start at 0");
+  for (int b = 0; b < B; ++b)
+    GMF_REQUIRE(off0[b + 1] >= off0[b] && off1[b + 1] >= off1[b], GMF_ERR_BAD_ARG, w + ": offsets must ascend");
   return GMF_OK;
 }
 
@@ -1228,31 +1146,29 @@ int gmf_nn_match_batched(gmf_handle* h, const float* F0, const float* F1, const 
   GMF_REQUIRE(h && off0 && off1, GMF_ERR_BAD_ARG, "nn_match_batched: null pointer");
   GMF_REQUIRE(B > 0 && d > 0, GMF_ERR_UNSUPPORTED_SHAPE, "nn_match_batched: empty batch");
   GMF_REQUIRE(mode >= 0 && mode <= 2, GMF_ERR_BAD_ARG, "nn_match_batched: mode must be 0 (PointDSC), 1 (DGR L2) or 2 (DGR SquareL2)");
-  const int K = gmf::padded_desc_width(d);
-  GMF_REQUIRE(K > 0, GMF_ERR_UNSUPPORTED_SHAPE, "nn_match_batched: descriptor width above 128 is not supported");
-  GMF_REQUIRE(off0[0] == 0 && off1[0] == 0, GMF_ERR_BAD_ARG, "nn_match_batched: offsets must start at 0");
-  for (int b = 0; b < B; ++b)
-    GMF_REQUIRE(off0[b + 1] >= off0[b] && off1[b + 1] >= off1[b], GMF_ERR_BAD_ARG, "nn_match_batched: offsets must ascend");
+  int K = 0;
+  if (int rc = check_pair_offsets(h, "nn_match_batched", off0, off1, B, d, &K)) return rc;
   if (off0[B] == 0) return GMF_OK;                     // no query rows: nothing to write
   GMF_REQUIRE(F0 && F1 && idx_out && dist_out, GMF_ERR_BAD_ARG, "nn_match_batched: null pointer");
   SetDevice sd(h, stream);
-  const size_t tab_bytes = (size_t)(B + 1) * sizeof(gmf::MatchPair);
-  void* host = nullptr;
-  if (int rc = take_ring_bytes(h, tab_bytes, &host)) return rc;
-  gmf::MatchPair* tab = static_cast<gmf::MatchPair*>(host);
+  HostTable tab;
+  const HostPart<gmf::MatchPair> pairs = tab.add<gmf::MatchPair>((size_t)B + 1);
+  RingTaken ring;
+  if (int rc = ring_take(h, tab, &ring)) return rc;
   gmf::MatchTotals tot;
-  GMF_REQUIRE(gmf::plan_nn_match_batched(off0, off1, B, K, tab, &tot), GMF_ERR_UNSUPPORTED_SHAPE,
+  GMF_REQUIRE(gmf::plan_nn_match_batched(off0, off1, B, K, pairs.host(ring.host), &tot), GMF_ERR_UNSUPPORTED_SHAPE,
               "nn_match_batched: a pair has query rows and no key rows");
   GMF_REQUIRE(tot.wgs < (1L << 31) && tot.stages * tot.tps * 32 < (1L << 31), GMF_ERR_UNSUPPORTED_SHAPE, "nn_match_batched: batch too large");
   // the images hold whole tiles (queries) and whole stages (keys) of every pair: no slack behind the last stage is needed
   const size_t n0 = (size_t)tot.tiles0 * 32 * K, n1 = (size_t)tot.stages * tot.tps * 32 * K, nn = (size_t)tot.stages * tot.tps * 32;
   float *i0, *i1, *nb;
   unsigned long long* best;
-  gmf::MatchPair* dtab;
+  char* dtab;
   if (int rc = arena_carve(h, {arena_buf(i0, n0), arena_buf(i1, n1), arena_buf(nb, nn), arena_buf(best, (size_t)tot.rows0),
-                               arena_buf(dtab, (size_t)B + 1)})) return rc;
-  if (int rc = upload_ring_bytes(h, dtab, tab_bytes, S(stream))) return rc;
-  GMF_HIP(gmf::launch_nn_match_batched(F0, F1, i0, i1, nb, best, dtab, B, tot, d, mode, global_index, idx_out, dist_out, S(stream)));
+                               arena_buf(dtab, tab.bytes())})) return rc;
+  if (int rc = ring_upload(h, ring, dtab, S(stream))) return rc;
+  GMF_HIP(gmf::launch_nn_match_batched(F0, F1, i0, i1, nb, best, pairs.dev(dtab), B, tot, d, mode, global_index, idx_out, dist_out,
+                                       S(stream)));
   return GMF_OK;
 }
 
@@ -1264,11 +1180,8 @@ static int run_correspondences(gmf_handle* h, const char* what, gmf::CorrArgs a,
   const int B = a.B, d = a.d;
   GMF_REQUIRE(h && off0 && off1, GMF_ERR_BAD_ARG, w + ": null pointer");
   GMF_REQUIRE(B > 0 && d > 0, GMF_ERR_UNSUPPORTED_SHAPE, w + ": empty batch");
-  const int K = gmf::padded_desc_width(d);
-  GMF_REQUIRE(K > 0, GMF_ERR_UNSUPPORTED_SHAPE, w + ": descriptor width above 128 is not supported");
-  GMF_REQUIRE(off0[0] == 0 && off1[0] == 0, GMF_ERR_BAD_ARG, w + ": offsets must start at 0");
-  for (int b = 0; b < B; ++b)
-    GMF_REQUIRE(off0[b + 1] >= off0[b] && off1[b + 1] >= off1[b], GMF_ERR_BAD_ARG, w + ": offsets must ascend");
+  int K = 0;
+  if (int rc = check_pair_offsets(h, what, off0, off1, B, d, &K)) return rc;
   if (build) {
     GMF_REQUIRE(a.in_dim == 3 || a.in_dim == 6, GMF_ERR_UNSUPPORTED_SHAPE, w + ": in_dim must be 3 or 6");
     GMF_REQUIRE(a.out_offsets, GMF_ERR_BAD_ARG, w + ": null pointer");
@@ -1291,23 +1204,23 @@ static int run_correspondences(gmf_handle* h, const char* what, gmf::CorrArgs a,
   SetDevice sd(h, stream);
   // one ring slot: MatchPair [B + 1] | pair_chunk0 [B + 1] | CorrChunk [n_chunks], each part on a 16-byte boundary
   const long n_chunks = gmf::corr_chunk_count(off0, B);
-  const size_t o_c0 = align_up((size_t)(B + 1) * sizeof(gmf::MatchPair), 16);
-  const size_t o_ck = o_c0 + align_up((size_t)(B + 1) * sizeof(int), 16);
-  const size_t tab_bytes = o_ck + (size_t)n_chunks * sizeof(gmf::CorrChunk);
-  void* host = nullptr;
-  if (int rc = take_ring_bytes(h, tab_bytes, &host)) return rc;
-  char* hb = static_cast<char*>(host);
+  HostTable tab;
+  const HostPart<gmf::MatchPair> pairs = tab.add<gmf::MatchPair>((size_t)B + 1);
+  const HostPart<int> pair_chunk0 = tab.add<int>((size_t)B + 1);
+  const HostPart<gmf::CorrChunk> chunks = tab.add<gmf::CorrChunk>((size_t)n_chunks);
+  RingTaken ring;
+  if (int rc = ring_take(h, tab, &ring)) return rc;
   gmf::MatchTotals tot;
-  GMF_REQUIRE(gmf::plan_nn_match_batched(off0, off1, B, K, reinterpret_cast<gmf::MatchPair*>(hb), &tot), GMF_ERR_UNSUPPORTED_SHAPE,
+  GMF_REQUIRE(gmf::plan_nn_match_batched(off0, off1, B, K, pairs.host(ring.host), &tot), GMF_ERR_UNSUPPORTED_SHAPE,
               w + ": a pair has query rows and no key rows");
   GMF_REQUIRE(tot.wgs < (1L << 31) && tot.stages * tot.tps * 32 < (1L << 31) && n_chunks < (1L << 31), GMF_ERR_UNSUPPORTED_SHAPE,
               w + ": batch too large");
-  gmf::corr_plan_chunks(off0, B, reinterpret_cast<gmf::CorrChunk*>(hb + o_ck), reinterpret_cast<int*>(hb + o_c0));
+  gmf::corr_plan_chunks(off0, B, chunks.host(ring.host), pair_chunk0.host(ring.host));
   const size_t rows0 = (size_t)tot.rows0, nck = (size_t)n_chunks;
   char* dtab;
   ArenaList bufs{arena_buf(a.f0_img, (size_t)tot.tiles0 * 32 * K), arena_buf(a.f1_img, (size_t)tot.stages * tot.tps * 32 * K),
                  arena_buf(a.norm2, (size_t)tot.stages * tot.tps * 32), arena_buf(a.best, rows0),
-                 arena_buf(a.colbest, a.use_mutual ? (size_t)off1[B] : 0), arena_buf(dtab, tab_bytes)};
+                 arena_buf(a.colbest, a.use_mutual ? (size_t)off1[B] : 0), arena_buf(dtab, tab.bytes())};
   if (build) {                                           // (the caller of the flags alone brings idx, dist and mutual itself)
     bufs.add(a.idx, rows0);
     bufs.add(a.dist, rows0);
@@ -1319,10 +1232,10 @@ static int run_correspondences(gmf_handle* h, const char* what, gmf::CorrArgs a,
     bufs.add(a.mean, (size_t)6 * B);
   }
   if (int rc = arena_carve(h, bufs)) return rc;
-  if (int rc = upload_ring_bytes(h, dtab, tab_bytes, S(stream))) return rc;
-  a.tab = reinterpret_cast<const gmf::MatchPair*>(dtab);
-  a.pair_chunk0 = reinterpret_cast<const int*>(dtab + o_c0);
-  a.chunks = reinterpret_cast<const gmf::CorrChunk*>(dtab + o_ck);
+  if (int rc = ring_upload(h, ring, dtab, S(stream))) return rc;
+  a.tab = pairs.dev(dtab);
+  a.pair_chunk0 = pair_chunk0.dev(dtab);
+  a.chunks = chunks.dev(dtab);
   a.n_chunks = (int)n_chunks;
   a.n_keys = off1[B];
   GMF_HIP(gmf::launch_corr_match(a, tot, S(stream)));
@@ -1553,29 +1466,25 @@ int gmf_information_matrix(gmf_handle* h, const float* points, const int* cloud_
   GMF_REQUIRE(n_chunks != -1, GMF_ERR_BAD_ARG, "information_matrix: an edge names a cloud outside 0..F-1");
   GMF_REQUIRE(n_chunks >= 0, GMF_ERR_UNSUPPORTED_SHAPE, "information_matrix: 2^31 or more source rows over the edges");
   SetDevice sd(h, stream);
-  const size_t o_src = align_up((size_t)(F + 1) * sizeof(int), 16);
-  const size_t o_tgt = o_src + align_up((size_t)E * sizeof(int), 16);
-  const size_t o_c0 = o_tgt + align_up((size_t)E * sizeof(int), 16);
-  const size_t o_ck = o_c0 + align_up((size_t)(E + 1) * sizeof(int), 16);
-  const size_t tab_bytes = o_ck + (size_t)n_chunks * sizeof(gmf::InfoChunk);
-  void* host = nullptr;
-  if (int rc = take_ring_bytes(h, tab_bytes, &host)) return rc;
-  char* hb = static_cast<char*>(host);
-  std::memcpy(hb, cloud_offsets, (size_t)(F + 1) * sizeof(int));
-  std::memcpy(hb + o_src, edge_source, (size_t)E * sizeof(int));
-  std::memcpy(hb + o_tgt, edge_target, (size_t)E * sizeof(int));
-  gmf::info_plan_chunks(cloud_offsets, edge_source, E, reinterpret_cast<gmf::InfoChunk*>(hb + o_ck), reinterpret_cast<int*>(hb + o_c0));
+  HostTable tab;
+  const HostPart<int> cloud_off = tab.add<int>((size_t)F + 1), esrc = tab.add<int>((size_t)E), etgt = tab.add<int>((size_t)E);
+  const HostPart<int> edge_chunk0 = tab.add<int>((size_t)E + 1);
+  const HostPart<gmf::InfoChunk> chunks = tab.add<gmf::InfoChunk>((size_t)n_chunks);
+  RingTaken ring;
+  if (int rc = ring_take(h, tab, &ring)) return rc;
+  std::copy_n(cloud_offsets, F + 1, cloud_off.host(ring.host));
+  std::copy_n(edge_source, E, esrc.host(ring.host));
+  std::copy_n(edge_target, E, etgt.host(ring.host));
+  gmf::info_plan_chunks(cloud_offsets, edge_source, E, chunks.host(ring.host), edge_chunk0.host(ring.host));
   gmf::InfoScratch ws;
   char* dtab;
   ArenaList bufs;
   gmf::info_scratch_list(N, n_chunks, ws, bufs);
-  bufs.add(dtab, tab_bytes);
+  bufs.add(dtab, tab.bytes());
   if (int rc = arena_carve(h, bufs)) return rc;
-  if (int rc = upload_ring_bytes(h, dtab, tab_bytes, S(stream))) return rc;
-  GMF_HIP(gmf::launch_information_matrix(points, reinterpret_cast<const int*>(dtab), F, N, reinterpret_cast<const int*>(dtab + o_src),
-                                         reinterpret_cast<const int*>(dtab + o_tgt), E,
-                                         reinterpret_cast<const gmf::InfoChunk*>(dtab + o_ck), n_chunks,
-                                         reinterpret_cast<const int*>(dtab + o_c0), transformation, tau, ws, info, count, nn, S(stream)));
+  if (int rc = ring_upload(h, ring, dtab, S(stream))) return rc;
+  GMF_HIP(gmf::launch_information_matrix(points, cloud_off.dev(dtab), F, N, esrc.dev(dtab), etgt.dev(dtab), E, chunks.dev(dtab), n_chunks,
+                                         edge_chunk0.dev(dtab), transformation, tau, ws, info, count, nn, S(stream)));
   return GMF_OK;
 }
 
@@ -1601,48 +1510,40 @@ int gmf_posegraph_optimize(gmf_handle* h, double* poses, const int* node_offsets
   GMF_REQUIRE(bad == 0, GMF_ERR_UNSUPPORTED_SHAPE, "posegraph_optimize: a graph has more than 256 nodes or 65536 edges, which is what is built");
   const int N = node_offsets[G];
   SetDevice sd(h, stream);
-  const size_t o_eo = align_up((size_t)(G + 1) * sizeof(int), 16);
-  const size_t o_ho = o_eo + align_up((size_t)(G + 1) * sizeof(int), 16);
-  const size_t o_es = o_ho + align_up((size_t)(G + 1) * sizeof(long long), 16);
-  const size_t o_et = o_es + align_up((size_t)M * sizeof(int), 16);
-  const size_t o_n0 = o_et + align_up((size_t)M * sizeof(int), 16);
-  const size_t o_li = o_n0 + align_up((size_t)(N + 1) * sizeof(int), 16);
-  const size_t tab_bytes = o_li + (size_t)2 * M * sizeof(gmf::NodeEdge);
-  void* host = nullptr;
-  if (int rc = take_ring_bytes(h, tab_bytes, &host)) return rc;
-  char* hb = static_cast<char*>(host);
-  std::memcpy(hb, node_offsets, (size_t)(G + 1) * sizeof(int));
-  std::memcpy(hb + o_eo, edge_offsets, (size_t)(G + 1) * sizeof(int));
-  long long* hoff = reinterpret_cast<long long*>(hb + o_ho);
+  HostTable tab;
+  const HostPart<int> node_off = tab.add<int>((size_t)G + 1), edge_off = tab.add<int>((size_t)G + 1);
+  const HostPart<long long> h_off = tab.add<long long>((size_t)G + 1);
+  const HostPart<int> esrc = tab.add<int>((size_t)M), etgt = tab.add<int>((size_t)M), node_list0 = tab.add<int>((size_t)N + 1);
+  const HostPart<gmf::NodeEdge> lists = tab.add<gmf::NodeEdge>((size_t)2 * M);
+  RingTaken ring;
+  if (int rc = ring_take(h, tab, &ring)) return rc;
+  std::copy_n(node_offsets, G + 1, node_off.host(ring.host));
+  std::copy_n(edge_offsets, G + 1, edge_off.host(ring.host));
+  long long* hoff = h_off.host(ring.host);
   hoff[0] = 0;
   for (int g = 0; g < G; ++g) {
     const long long n6 = 6LL * (node_offsets[g + 1] - node_offsets[g]);
     hoff[g + 1] = hoff[g] + n6 * n6;
   }
   const long long D = hoff[G];
-  if (M) {
-    std::memcpy(hb + o_es, edge_source, (size_t)M * sizeof(int));
-    std::memcpy(hb + o_et, edge_target, (size_t)M * sizeof(int));
-  }
-  gmf::posegraph_node_lists(node_offsets, edge_offsets, G, edge_source, edge_target, reinterpret_cast<int*>(hb + o_n0),
-                            reinterpret_cast<gmf::NodeEdge*>(hb + o_li));
+  std::copy_n(edge_source, M, esrc.host(ring.host));      // (M = 0: nothing to copy, and the caller's arrays may be null)
+  std::copy_n(edge_target, M, etgt.host(ring.host));
+  gmf::posegraph_node_lists(node_offsets, edge_offsets, G, edge_source, edge_target, node_list0.host(ring.host), lists.host(ring.host));
   gmf::PoseGraphScratch ws;
   char* dtab;
   ArenaList bufs;
   gmf::posegraph_scratch_list(N, M, D, ws, bufs);
-  bufs.add(dtab, tab_bytes);
+  bufs.add(dtab, tab.bytes());
   if (int rc = arena_carve(h, bufs)) return rc;
-  if (int rc = upload_ring_bytes(h, dtab, tab_bytes, S(stream))) return rc;
+  if (int rc = ring_upload(h, ring, dtab, S(stream))) return rc;
   gmf::PoseGraphOptions o;
   o.max_iteration = opt->max_iteration; o.max_iteration_lm = opt->max_iteration_lm; o.reference_node = opt->reference_node;
   o.min_relative_increment = opt->min_relative_increment;
   o.min_relative_residual_increment = opt->min_relative_residual_increment;
   o.min_right_term = opt->min_right_term; o.min_residual = opt->min_residual;
   o.edge_prune_threshold = opt->edge_prune_threshold; o.preference_loop_closure = opt->preference_loop_closure;
-  GMF_HIP(gmf::launch_posegraph(poses, reinterpret_cast<const int*>(dtab), reinterpret_cast<const int*>(dtab + o_eo),
-                                reinterpret_cast<const long long*>(dtab + o_ho), G, reinterpret_cast<const int*>(dtab + o_es),
-                                reinterpret_cast<const int*>(dtab + o_et), edge_transformation, edge_information, edge_uncertain,
-                                edge_mask, reinterpret_cast<const int*>(dtab + o_n0), reinterpret_cast<const gmf::NodeEdge*>(dtab + o_li),
+  GMF_HIP(gmf::launch_posegraph(poses, node_off.dev(dtab), edge_off.dev(dtab), h_off.dev(dtab), G, esrc.dev(dtab), etgt.dev(dtab),
+                                edge_transformation, edge_information, edge_uncertain, edge_mask, node_list0.dev(dtab), lists.dev(dtab),
                                 o, ws, line_process, kept, stats, residual, trace, h->status_dev, GMF_STATUS_POSEGRAPH_PIVOT, S(stream)));
   return GMF_OK;
 }

@@ -2,18 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "pair_plan.hpp"
+
 namespace gmf {
 
-// Ragged batches (gmf_encoder_forward_ragged / gmf_pose_head_ragged): pair b owns rows [row0, row0 + n) of the caller's packed
-// row-major tensors ([sum n, ...]); S = int(n * ratio) seeds and k = min(k, n - 1) neighbours in the pose head.  The table is
-// built on the host from the caller's per-pair sizes and uploaded with the call.  Kernels take a nullable pointer: null =
-// the uniform batch [B, N, ...].  Internally every pair keeps a slot of tiles(max n) tiles; a pair's tiles beyond its own are
-// neither computed nor read.
-// ord [r5]: the attention grid's pair SLOT -> pair map of a ragged batch.  The attention items are dealt to the 8 XCDs in contiguous runs of
-// slots (attn_item), and an item costs n^2: with the pairs in the caller's order an XCD's share of the work is whatever its four pairs
-// happen to be (32 pairs with N ~ U[4000, 5500]: +-9 % around the mean, and the launch ends with the slowest XCD).  build_pair_table
-// deals the pairs to the XCD runs longest first, each to the run with the least work so far.  Results do not depend on it.
-struct PairTab { int row0, n, S, k, ord, pad0, pad1, pad2; };
+// struct PairTab, the per-pair table of a ragged batch, and its host plan: pair_plan.hpp
 
 // The "pv_fp8" guard (gmf_set_tuning "pv_fp8" = 1, the default): which of a layer's pairs run the P V cross products of
 // the spatial-consistency attention on the fp8 pipe is decided ON THE DEVICE, per pair, from a statistic the previous kernel
@@ -174,6 +167,7 @@ hipError_t launch_nn_match(const float* F0, const float* F1, float* f0_img, floa
 // `stage0` of the F1 image (and of the norms), and its workgroups are [wg0, wg0 + wgx * ks): wgx query blocks of four tiles times ks
 // key splits.  Entry B of the table holds the totals (an empty range), so every prefix search has its end.
 struct MatchPair { int row0, n0, key0, n1, tile0, stage0, stages, wg0, wgx, ks, pad0, pad1; };
+static_assert(sizeof(MatchPair) == 48, "tests/abi_cpp/host_table_host.cpp lays the correspondence table out with a 48-byte stand-in");
 struct MatchTotals { long tiles0, stages, wgs, rows0; int tps; };
 // fills tab[0 .. B] from the B + 1 host offsets; false: a pair has queries and no keys
 bool plan_nn_match_batched(const int* off0, const int* off1, int B, int K, MatchPair* tab, MatchTotals* tot);

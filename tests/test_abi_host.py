@@ -451,3 +451,21 @@ def test_workspace_list_under_sanitizers(tmp_path):
     assert build.returncode == 0, build.stderr[-2000:]
     run = subprocess.run([exe], capture_output=True, text=True)
     assert run.returncode == 0 and "arena_list_host: ok" in run.stdout, (run.stdout + run.stderr)[-2000:]
+
+
+def test_host_table_and_pair_plan_under_sanitizers(tmp_path):
+    """tests/abi_cpp/host_table_host.cpp, a program of its own built with the host compiler and -fsanitize=address,undefined:
+    the host-table list of csrc/host_table.hpp over a malloc'ed block of exactly bytes() - aligned, apart, in list order, every
+    byte written, the three real layouts against the offset ladders they replaced - and csrc/pair_plan.hpp's plan_pair_table
+    against two slot orders derived by hand, its sizes, and its two refusals."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    exe = str(tmp_path / "host_table_host")
+    build = subprocess.run([cxx, "-std=c++17", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                            os.path.join(ROOT, "tests", "abi_cpp", "host_table_host.cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-2000:]
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and "host_table_host: ok" in run.stdout, (run.stdout + run.stderr)[-2000:]

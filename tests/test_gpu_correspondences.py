@@ -323,3 +323,63 @@ def test_graph_capture_of_the_c_entry_replays_the_eager_bits():
     torch.cuda.synchronize()
     for k in eager:
         assert _same_bits(eager[k], captured[k]), k
+
+
+# ---- 9. the handle's ring of pinned table slots: wrap-around and regrowth -------------------------------------------------------------
+
+def _ring_batch(len_batch, seed):
+    """A batch from the fixture recipe (no top-2 gap within the fp32 error of the scores) as the C entry takes it."""
+    fx = R.make_fixture(32, seed, len_batch)
+    gap, bound, _ = R.check_fixture(fx, THR)
+    assert gap > bound, (gap, bound)
+    B = len(len_batch)
+    off0 = np.r_[0, np.cumsum([a for a, _ in len_batch])].astype(int)
+    off1 = np.r_[0, np.cumsum([b for _, b in len_batch])].astype(int)
+    return {"F0": _g(fx["src_desc"]), "F1": _g(fx["tgt_desc"]), "B": B, "rows": int(off0[-1]),
+            "off0": (ctypes.c_int * (B + 1))(*[int(x) for x in off0]), "off1": (ctypes.c_int * (B + 1))(*[int(x) for x in off1])}
+
+
+def _ring_call(h, st, bt, retry):
+    """One gmf_nn_match_batched into outputs of its own.  retry False: the entry itself, so a call the library refuses for want of
+    workspace (it would have taken a ring slot, and Handle.call would repeat it) fails here instead of shifting the slots."""
+    idx = torch.full((bt["rows"],), -1, device=DEV, dtype=torch.int32)
+    dist = torch.full((bt["rows"],), float("nan"), device=DEV)
+    args = (bt["F0"].data_ptr(), bt["F1"].data_ptr(), bt["off0"], bt["off1"], bt["B"], 32, 0, 0, idx.data_ptr(), dist.data_ptr(), st)
+    if retry:
+        h.call("gmf_nn_match_batched", *args)
+    else:
+        h.check(h.lib.gmf_nn_match_batched(h.h, *args), "gmf_nn_match_batched")
+    return idx, dist
+
+
+def test_back_to_back_calls_wrap_the_table_ring_and_regrow_its_slots():
+    """Twenty gmf_nn_match_batched calls on one handle and one stream with no synchronisation between them, over a batch whose host
+    table fits a fresh 2 KiB slot (X: 4 x 48 B) and one whose table does not (Y: 101 x 48 B).  The handle is given its workspace
+    beforehand, so every call succeeds at once and call i takes slot i % 8 of the ring.  The batches alternate in runs of eight (X
+    for calls 0-7, Y for 8-15, X for 16-19; alternating call by call would tie each table to the slots of one parity, which then
+    would never regrow and would be rewritten with the bytes they already hold).  So every slot is taken at least twice, always
+    with its earlier upload's event pending and always for the other batch's table, and each of the eight slots is regrown by a Y
+    call from a 2 KiB block that X filled.  Every call writes its own outputs; all X results are one set of bits, all Y results
+    another, and both are those of a call alone on a fresh handle."""
+    from gmf_amd import _lib
+    X = _ring_batch([(20, 33), (40, 25), (31, 40)], 0)
+    Y = _ring_batch([((7 * b) % 5, 1 + (3 * b) % 4) for b in range(100)], 0)      # 1-4 rows; every fifth pair has no query rows
+    assert X["B"] == 3 and (X["B"] + 1) * 48 <= 2048 and Y["B"] == 100 and (Y["B"] + 1) * 48 > 2048
+    kinds = [(X, Y)[(i // 8) % 2] for i in range(20)]
+    for s in range(8):                                        # what the docstring says of the order, slot by slot
+        held = kinds[s::8]
+        assert len(held) >= 2 and all(a is not b for a, b in zip(held, held[1:])) and held[0] is X and held[1] is Y
+    st = torch.cuda.current_stream().cuda_stream
+    h = _lib.Handle(0)
+    h._ws = torch.empty(64 << 20, dtype=torch.uint8, device=DEV)           # far more than either batch needs
+    h.check(h.lib.gmf_set_workspace(h.h, h._ws.data_ptr(), h._ws.numel()), "gmf_set_workspace")
+    outs = [_ring_call(h, st, bt, False) for bt in kinds]
+    fresh = [_lib.Handle(0), _lib.Handle(0)]                  # (alive until the synchronise)
+    refs = [_ring_call(hf, st, bt, True) for hf, bt in zip(fresh, (X, Y))]
+    torch.cuda.synchronize()
+    first = {id(X): outs[0], id(Y): outs[8]}
+    for i, (idx, dist) in enumerate(outs):
+        for want_idx, want_dist in (first[id(kinds[i])], refs[kinds[i] is Y]):
+            assert torch.equal(idx, want_idx) and _same_bits(dist, want_dist), i
+    for (idx, dist), bt in zip(refs, (X, Y)):
+        assert int(idx.min()) >= 0 and bool(torch.isfinite(dist).all()) and idx.shape[0] == bt["rows"]
