@@ -1,7 +1,10 @@
 // Image encoder (ResNet-34 truncated after layer2, GMF_PointDSC/models/resnet.py:195-216).
-// The convolutions stay with MIOpen (PyTorch-ROCm, NHWC fp32); what the framework leaves un-fused around them - the folded
-// BatchNorm bias, the residual add and the ReLU, three element-wise passes per convolution - is one pass here:
-//   y = max(y + bias[c] (+ residual), 0)   in place on an NHWC tensor (resnet.py:59-75, BasicBlock.forward).
+// Every convolution is a native kernel, NHWC fp32 in and out, on the f16 MFMA with split-fp16 operands: the stem (k_stem_h2:
+// 7x7 stride 2 + bias + ReLU + max-pool) and the layer1 / layer2 shapes (k_conv_nhwc_h2, k_conv3x3_patch_h2, and k_conv_small_h2
+// on grids of a few images), each with the folded BatchNorm bias, the residual add and the ReLU in its epilogue
+// (resnet.py:59-75, BasicBlock.forward).  MIOpen runs only a convolution whose folded weights left the fp16 range of the split
+// operands; the three element-wise passes the framework leaves un-fused behind it are then one pass, k_bias_relu_nhwc:
+//   y = max(y + bias[c] (+ residual), 0)   in place on an NHWC tensor.
 #include <hip/hip_runtime.h>
 
 #include "mfma_core.hpp"

@@ -1490,8 +1490,8 @@ def _image_model(seed):
 
 @pytest.mark.parametrize("graph", [True, False])
 def test_f11_image_tokens_small_batch(golden_dir, graph):
-    """Golden F11 on the GPU: 2 images through NonLocalNet.image_tokens (below the native-convolution threshold: folded
-    BatchNorms, NHWC, MIOpen convolutions + the HIP bias/ReLU pass), captured graph and eager."""
+    """Golden F11 on the GPU: 2 images through NonLocalNet.image_tokens (folded BatchNorms, NHWC, the fused stem kernel and the
+    native convolutions in their small-grid forms: k_stem_h2<4>, k_conv_small_h2), captured graph and eager."""
     g = _load(golden_dir, "f11_image_encoder.npz")
     m = _image_model(int(g["seed"]))
     m.encoder.graph_image_encoder = graph
@@ -3152,7 +3152,9 @@ def test_bias_relu_nhwc_epilogue():
                                                       (128, 128, 3, 1, 5, 48), (64, 64, 3, 1, 3, 50)])
 def test_conv_nhwc_matches_torch(cin, cout, ks, stride, H, W):
     """gmf_conv_nhwc (implicit GEMM, split-fp16 MFMA) against torch's fp64 convolution of the same fp32 inputs: ResNet-34
-    layer1 / layer2 shapes, odd sizes, residual and ReLU on and off."""
+    layer1 / layer2 shapes, odd sizes, residual and ReLU on and off.  Three images are a small grid: every case here runs
+    k_conv_small_h2 whatever conv_lds_patch says; the 128-pixel kernels at these sizes, and each case's kernel by name, are in
+    test_gpu_image_encoder.py."""
     from gmf_amd import _lib, packing
     h = _lib.handle_for(0)
     st = torch.cuda.current_stream().cuda_stream
