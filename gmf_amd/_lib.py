@@ -190,6 +190,12 @@ SIGNATURES = {
     "gmf_colsum": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _ll, C.c_int, _vp, C.c_int, _vp, _vp]),
     "gmf_batchnorm_train_forward": (C.c_int, [_vp] * 9 + [_ll, C.c_int, C.c_float, C.c_float, C.c_int, _vp]),
     "gmf_batchnorm_train_backward": (C.c_int, [_vp] * 10 + [_ll, C.c_int, _vp]),
+    "gmf_conv2d_forward_f32": (C.c_int, [_vp, _vp, _ll, _ll, _ll, _ll, _vp, _vp] + [C.c_int] * 7 + [_vp]),
+    "gmf_conv2d_dgrad": (C.c_int, [_vp, _vp, _vp, _vp, _vp] + [C.c_int] * 7 + [_vp]),
+    "gmf_conv2d_wgrad": (C.c_int, [_vp, _vp, _ll, _ll, _ll, _ll, _vp, _vp] + [C.c_int] * 7 + [_vp]),
+    "gmf_maxpool3x3s2_forward": (C.c_int, [_vp, _vp, _vp] + [C.c_int] * 4 + [_vp]),
+    "gmf_maxpool3x3s2_backward": (C.c_int, [_vp, _vp, _vp, _vp] + [C.c_int] * 4 + [_vp]),
+    "gmf_batchnorm_residual_forward": (C.c_int, [_vp] * 10 + [_ll, C.c_int, C.c_float, C.c_float, C.c_int, _vp]),
     "gmf_normalize_rows": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _ll, C.c_int, _vp]),
     "gmf_relu_backward": (C.c_int, [_vp, _vp, _vp, _vp, _ll, _vp]),
     "gmf_classification_backward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),

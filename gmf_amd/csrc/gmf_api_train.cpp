@@ -5,6 +5,7 @@
 #include "launchers_pose.hpp"
 #include "launchers_sparse.hpp"
 #include "launchers_sparse_train.hpp"
+#include "launchers_image_train.hpp"
 
 extern "C" {
 
@@ -294,6 +295,112 @@ int gmf_batchnorm_masked_backward(gmf_handle* h, const float* dy, const float* x
   float* part = nullptr;
   if (int rc = arena_carve(h, {arena_buf(part, gmf::bnm_part_floats(cap, C))})) return rc;
   GMF_HIP(gmf::launch_bnm_backward(dy, x, y_relu, mean, rstd, gamma, n_rows, cap, C, g, dx, dgamma, dbeta, part, S(stream)));
+  return GMF_OK;
+}
+
+// ---- training of the image encoder (image_train_kernels.hip) ------------------------------------------------------------
+
+// the checks the three convolution passes share: one of the five shapes, an image the kernel fits, pixel counts that index in int
+static int conv2d_check(gmf_handle* h, const char* who, const gmf::Conv2dShape& s) {
+  const std::string shape = std::string(who) + ": (cin, cout, ksize, stride) = (" + std::to_string(s.cin) + ", " + std::to_string(s.cout) +
+                            ", " + std::to_string(s.ks) + ", " + std::to_string(s.stride) + ")";
+  if (!gmf::conv2d_shape_ok(s))
+    return fail(h, GMF_ERR_UNSUPPORTED_SHAPE, "gmf: " + shape + " is none of (3,64,7,2), (64,64,3,1), (128,128,3,1), (64,128,3,2), (64,128,1,2)");
+  if (s.B <= 0 || s.H <= 0 || s.W <= 0)
+    return fail(h, GMF_ERR_UNSUPPORTED_SHAPE, "gmf: " + std::string(who) + ": empty input [" + std::to_string(s.B) + ", " +
+                                                  std::to_string(s.H) + ", " + std::to_string(s.W) + "]");
+  if (s.in_pixels() >= (1LL << 30) || s.out_pixels() >= (1LL << 30))
+    return fail(h, GMF_ERR_UNSUPPORTED_SHAPE, "gmf: " + std::string(who) + ": B * H * W must stay below 2^30 pixels: split the batch");
+  return GMF_OK;
+}
+
+static bool dense_nhwc(const gmf::Conv2dShape& s, long long sb, long long sc, long long sh, long long sw) {
+  return sc == 1 && sw == s.cin && sh == (long long)s.W * s.cin && sb == (long long)s.H * s.W * s.cin;
+}
+
+int gmf_conv2d_forward_f32(gmf_handle* h, const float* x, long long sb, long long sc, long long sh, long long sw, const float* w,
+                           float* y, int B, int H, int W, int cin, int cout, int ksize, int stride, gmf_stream_t stream) {
+  GMF_REQUIRE(h && x && w && y, GMF_ERR_BAD_ARG, "conv2d_forward_f32: null pointer");
+  const gmf::Conv2dShape s{B, H, W, cin, cout, ksize, stride};
+  if (int rc = conv2d_check(h, "conv2d_forward_f32", s)) return rc;
+  GMF_REQUIRE(s.stem() ? (sb >= 0 && sc >= 0 && sh >= 0 && sw >= 0) : dense_nhwc(s, sb, sc, sh, sw), GMF_ERR_BAD_ARG,
+              "conv2d_forward_f32: x must be dense NHWC (only the 3-channel stem reads through non-negative element strides)");
+  SetDevice sd(h, stream);
+  float* wp;
+  if (int rc = arena_carve(h, {arena_buf(wp, s.weight_floats())})) return rc;
+  GMF_HIP(gmf::launch_conv2d_forward(s, x, sb, sc, sh, sw, w, wp, y, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_conv2d_dgrad(gmf_handle* h, const float* dy, const float* w, const float* dx_add, float* dx, int B, int H, int W, int cin,
+                     int cout, int ksize, int stride, gmf_stream_t stream) {
+  GMF_REQUIRE(h && dy && w && dx, GMF_ERR_BAD_ARG, "conv2d_dgrad: null pointer");
+  const gmf::Conv2dShape s{B, H, W, cin, cout, ksize, stride};
+  if (int rc = conv2d_check(h, "conv2d_dgrad", s)) return rc;
+  GMF_REQUIRE(!s.stem(), GMF_ERR_UNSUPPORTED_SHAPE, "conv2d_dgrad: the stem (3, 64, 7, 2) has no dgrad (images carry no gradient)");
+  SetDevice sd(h, stream);
+  float* wp;
+  if (int rc = arena_carve(h, {arena_buf(wp, s.weight_floats())})) return rc;
+  GMF_HIP(gmf::launch_conv2d_dgrad(s, dy, w, wp, dx_add, dx, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_conv2d_wgrad(gmf_handle* h, const float* x, long long sb, long long sc, long long sh, long long sw, const float* dy, float* dw,
+                     int B, int H, int W, int cin, int cout, int ksize, int stride, gmf_stream_t stream) {
+  GMF_REQUIRE(h && x && dy && dw, GMF_ERR_BAD_ARG, "conv2d_wgrad: null pointer");
+  const gmf::Conv2dShape s{B, H, W, cin, cout, ksize, stride};
+  if (int rc = conv2d_check(h, "conv2d_wgrad", s)) return rc;
+  GMF_REQUIRE(s.stem() ? (sb >= 0 && sc >= 0 && sh >= 0 && sw >= 0) : dense_nhwc(s, sb, sc, sh, sw), GMF_ERR_BAD_ARG,
+              "conv2d_wgrad: x must be dense NHWC (only the 3-channel stem reads through non-negative element strides)");
+  SetDevice sd(h, stream);
+  float* part;
+  if (int rc = arena_carve(h, {arena_buf(part, (size_t)gmf::conv2d_wgrad_slabs(s) * s.weight_floats())})) return rc;
+  GMF_HIP(gmf::launch_conv2d_wgrad(s, x, sb, sc, sh, sw, dy, part, dw, S(stream)));
+  return GMF_OK;
+}
+
+static int maxpool_check(gmf_handle* h, const char* who, int B, int H, int W, int C) {
+  if (B <= 0 || H <= 0 || W <= 0) return fail(h, GMF_ERR_UNSUPPORTED_SHAPE, std::string("gmf: ") + who + ": empty input");
+  if (C <= 0 || C % 4 != 0) return fail(h, GMF_ERR_UNSUPPORTED_SHAPE, std::string("gmf: ") + who + ": C = " + std::to_string(C) + " must be a positive multiple of 4");
+  if ((long long)B * H * W * (C / 4) >= (1LL << 38))
+    return fail(h, GMF_ERR_UNSUPPORTED_SHAPE, std::string("gmf: ") + who + ": B * H * W * C / 4 exceeds one launch: split the batch");
+  return GMF_OK;
+}
+
+int gmf_maxpool3x3s2_forward(gmf_handle* h, const float* x, float* y, int B, int H, int W, int C, gmf_stream_t stream) {
+  GMF_REQUIRE(h && x && y, GMF_ERR_BAD_ARG, "maxpool3x3s2_forward: null pointer");
+  if (int rc = maxpool_check(h, "maxpool3x3s2_forward", B, H, W, C)) return rc;
+  SetDevice sd(h, stream);
+  GMF_HIP(gmf::launch_maxpool_fwd(x, y, B, H, W, C, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_maxpool3x3s2_backward(gmf_handle* h, const float* x, const float* dy, float* dx, int B, int H, int W, int C,
+                              gmf_stream_t stream) {
+  GMF_REQUIRE(h && x && dy && dx, GMF_ERR_BAD_ARG, "maxpool3x3s2_backward: null pointer");
+  if (int rc = maxpool_check(h, "maxpool3x3s2_backward", B, H, W, C)) return rc;
+  SetDevice sd(h, stream);
+  GMF_HIP(gmf::launch_maxpool_bwd(x, dy, dx, B, H, W, C, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_batchnorm_residual_forward(gmf_handle* h, const float* x, const float* residual, const float* gamma, const float* beta,
+                                   float* y, float* mean, float* rstd, float* running_mean, float* running_var, long long rows, int C,
+                                   float eps, float momentum, int relu, gmf_stream_t stream) {
+  GMF_REQUIRE(h && x && residual && gamma && beta && y && mean && rstd, GMF_ERR_BAD_ARG, "batchnorm_residual_forward: null pointer");
+  GMF_REQUIRE((running_mean == nullptr) == (running_var == nullptr), GMF_ERR_BAD_ARG, "batchnorm_residual_forward: running stats come together");
+  GMF_REQUIRE(rows > 1 && C > 0, GMF_ERR_UNSUPPORTED_SHAPE, "batchnorm_residual_forward: need more than one row");
+  SetDevice sd(h, stream);
+  const size_t n_part = (size_t)gmf::colsum_chunks((long)rows) * C;
+  float *part, *sum, *sumsq;
+  if (int rc = arena_carve(h, {arena_buf(part, n_part), arena_buf(sum, (size_t)C), arena_buf(sumsq, (size_t)C)})) return rc;
+  hipStream_t st = S(stream);
+  // the statistics exactly as gmf_batchnorm_train_forward takes them; only the apply differs
+  GMF_HIP(gmf::launch_colsum(x, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)rows, (long)rows, C, part, sum, st));
+  GMF_HIP(gmf::launch_bn_finish(sum, nullptr, mean, rstd, nullptr, nullptr, C, (long)rows, eps, momentum, st));
+  GMF_HIP(gmf::launch_colsum(x, x, nullptr, nullptr, mean, nullptr, 1, 0, (int)rows, (long)rows, C, part, sumsq, st));
+  GMF_HIP(gmf::launch_bn_finish(sum, sumsq, mean, rstd, running_mean, running_var, C, (long)rows, eps, momentum, st));
+  GMF_HIP(gmf::launch_bn_apply_residual(x, residual, mean, rstd, gamma, beta, y, (long)rows, C, relu ? 1 : 0, st));
   return GMF_OK;
 }
 

@@ -170,10 +170,16 @@ class ImageEncoder(nn.Module):
 
     forward(image [B,3,H,W]) -> [B,128,H',W'] (models/resnet.py:195-216).  On a HIP device in eval mode the pass runs as
     `_FusedResNet` (BatchNorms folded, NHWC, the fused stem kernel and the native layer1 / layer2 convolutions) and, per input
-    shape, as a captured HIP graph (~75 launches of a few microseconds of work each; `graph = False` keeps it eager).  In
-    train() mode it is the stock torch module (it trains as one: DESIGN section 7)."""
+    shape, as a captured HIP graph (~75 launches of a few microseconds of work each; `graph = False` keeps it eager).
+
+    In train() mode on a HIP device with autograd enabled it is `gmf_amd.train.image_encoder_train`: the same function as the
+    stock modules in train() (batch statistics, running statistics and num_batches_tracked updated as torch does, gradients for
+    all 48 trained tensors), every operation a HIP kernel of this library.  `native_train = False` keeps the
+    stock torch modules (MIOpen convolutions, torch autograd) - the A/B partner.  The stock modules also serve the two cases
+    the native pass does not cover: an image that itself requires grad, and train() under `torch.no_grad()`."""
 
     graph = True
+    native_train = True
 
     def __init__(self):
         super().__init__()
@@ -190,6 +196,9 @@ class ImageEncoder(nn.Module):
         return self._fused
 
     def forward(self, x):
+        if self.training and x.is_cuda and self.native_train and torch.is_grad_enabled() and not x.requires_grad:
+            from .train import image_encoder_train
+            return image_encoder_train(self, x)
         if self.training or not x.is_cuda:
             return self.backbone(x)
         # eval() with autograd on and something to differentiate (fine-tuning with frozen BatchNorm statistics): the fused,
@@ -560,7 +569,7 @@ class PointDSC(nn.Module):
         tgt = require_cuda_f32(data["tgt_keypts"], "tgt_keypts").contiguous()
         if "p_tokens" in data:
             p_tok, q_tok = data["p_tokens"], data["q_tokens"]
-        else:       # the ResNet image encoder trains as a stock torch module (MIOpen convolutions, torch autograd)
+        else:       # the ResNet image encoder trains on the HIP kernels of train.image_encoder_train, once per image as the reference does
             enc = self.encoder.image_encoder
             p_tok = enc(data["p_image"]).flatten(2).permute(0, 2, 1).contiguous()
             q_tok = enc(data["q_image"]).flatten(2).permute(0, 2, 1).contiguous()

@@ -691,7 +691,7 @@ def batchnorm_masked(x, bn, plan, level: int, residual=None, relu: bool = False)
 def resunet_train(model, coords, feats, p_image=None, q_image=None, p_tokens=None, q_tokens=None):
     """The differentiable train-mode forward of a gmf_amd.ResUNetBN2C (resunet_new.py:627-706, batch-statistics BatchNorm):
     logits [M, out_channels], aligned with the input rows.  Gradients reach the 23 kernels, final.bias, the 21 BatchNorms, both
-    fusion layers, the image encoder (train-mode stock torch modules) when images are given, and p_tokens / q_tokens when tokens
+    fusion layers, the image encoder (`image_encoder_train`, HIP kernels) when images are given, and p_tokens / q_tokens when tokens
     are given; every running statistic is updated as torch does.  The eval path's conventions hold: one image pair, the
     bottleneck's queries all stride-8 rows in ascending (batch, coordinates) order, zero rows past the level count (the position
     encoding's zero padding for pe=True).  Reads the four level counts to the host once, to raise as torch's BatchNorm does on
@@ -729,3 +729,175 @@ def resunet_train(model, coords, feats, p_image=None, q_image=None, p_tokens=Non
     t1, s1 = resunet_trunk(layer, feats, bottleneck=fuse)
     o = sparse_conv_train(plan, None, 0, t1, model.conv1_tr.kernel, xb=s1, relu=True)      # MEF.relu(conv1_tr(ME.cat(...)))
     return sparse_conv_train(plan, None, 0, o, model.final.kernel, bias=model.final.bias)
+
+
+# =====================================================================================================================
+# The image encoder in train() mode (ResNet-34 -> layer2, GMF_PointDSC/models/resnet.py:36-75,195-216; trained by both
+# plugins, PointDSC.py:129-135): every operation a HIP kernel of this library (gmf_amd/csrc/image_train_kernels.hip and the
+# BatchNorm / ReLU / column-sum primitives above).  Activations travel as dense NHWC fp32, i.e. as [B * H * W, C] row
+# matrices with their (B, H, W) beside them; weights are the nn.Conv2d parameters themselves.
+# =====================================================================================================================
+_CONV2D_SHAPES = ((3, 64, 7, 2), (64, 64, 3, 1), (128, 128, 3, 1), (64, 128, 3, 2), (64, 128, 1, 2))
+
+
+def conv2d_out_size(H, W, ks, stride):
+    pad = ks // 2
+    return (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+
+
+class _Conv2dTrain(torch.autograd.Function):
+    """y [B*Ho*Wo, cout] = conv2d(x, W) without bias, pad = ks // 2.  x: rows [B*H*W, cin] of a dense NHWC activation with
+    geom = (B, H, W), or (the stem) the image itself [B, 3, H, W] in any layout - read through its strides, no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, W, geom, stride):
+        B, H, Wd = geom
+        cout, cin, ks, _ = W.shape
+        image = x.dim() == 4
+        if not image:
+            x = x.contiguous()
+        Wc = W.detach().contiguous()
+        strides = tuple(x.stride()) if image else (H * Wd * cin, 1, Wd * cin, cin)          # (sb, sc, sh, sw) in elements
+        Ho, Wo = conv2d_out_size(H, Wd, ks, stride)
+        y = torch.empty((B * Ho * Wo, cout), device=x.device, dtype=torch.float32)
+        h, st = handle_and_stream(x)
+        h.call("gmf_conv2d_forward_f32", x.data_ptr(), *strides, Wc.data_ptr(), y.data_ptr(), B, H, Wd, cin, cout, ks, stride, st)
+        ctx.geom, ctx.stride, ctx.strides, ctx.image = (B, H, Wd, cin, cout, ks), stride, strides, image
+        ctx.save_for_backward(x, Wc)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, Wc = ctx.saved_tensors
+        B, H, Wd, cin, cout, ks = ctx.geom
+        dy = dy.contiguous()
+        h, st = handle_and_stream(dy)
+        dW = torch.empty_like(Wc)
+        h.call("gmf_conv2d_wgrad", x.data_ptr(), *ctx.strides, dy.data_ptr(), dW.data_ptr(), B, H, Wd, cin, cout, ks, ctx.stride, st)
+        dx = None
+        if not ctx.image and ctx.needs_input_grad[0]:
+            dx = torch.empty((B * H * Wd, cin), device=dy.device, dtype=torch.float32)
+            h.call("gmf_conv2d_dgrad", dy.data_ptr(), Wc.data_ptr(), None, dx.data_ptr(), B, H, Wd, cin, cout, ks, ctx.stride, st)
+        return dx, dW, None, None
+
+
+def conv2d_train(x, conv, geom):
+    """`conv`: a bias-free nn.Conv2d of one of the encoder's five shapes -> (rows [B*Ho*Wo, cout], (B, Ho, Wo))."""
+    cout, cin, ks, _ = conv.weight.shape
+    stride = conv.stride[0]
+    if (cin, cout, ks, stride) not in _CONV2D_SHAPES or conv.bias is not None or conv.padding[0] != ks // 2:
+        raise NotImplementedError(f"gmf_amd.train: convolution (cin, cout, ks, stride) = {(cin, cout, ks, stride)} is not one of the "
+                                  f"image encoder's shapes {_CONV2D_SHAPES} (bias-free, pad = ks // 2)")
+    B, H, W = geom
+    return _Conv2dTrain.apply(x, conv.weight, geom, stride), (B, *conv2d_out_size(H, W, ks, stride))
+
+
+class _MaxPoolTrain(torch.autograd.Function):
+    """nn.MaxPool2d(3, 2, 1) on rows [B*H*W, C] of an NHWC activation; the backward recomputes each window's argmax from x."""
+
+    @staticmethod
+    def forward(ctx, x, geom):
+        x = x.contiguous()
+        B, H, W = geom
+        C = x.shape[1]
+        Hp, Wp = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        y = torch.empty((B * Hp * Wp, C), device=x.device, dtype=torch.float32)
+        h, st = handle_and_stream(x)
+        h.call("gmf_maxpool3x3s2_forward", x.data_ptr(), y.data_ptr(), B, H, W, C, st)
+        ctx.geom = geom
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        B, H, W = ctx.geom
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        h, st = handle_and_stream(x)
+        h.call("gmf_maxpool3x3s2_backward", x.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, H, W, x.shape[1], st)
+        return dx, None
+
+
+def maxpool_train(x, geom):
+    B, H, W = geom
+    return _MaxPoolTrain.apply(x, geom), (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
+
+
+class _BatchNormResidualTrain(torch.autograd.Function):
+    """relu(bn(x) + residual) in training mode on rows [rows, C] (BasicBlock.forward, resnet.py:59-75); the residual form of
+    `_BatchNormTrain`.  Backward: the BatchNorm's, masked by the block's output, and the ReLU's for the identity branch."""
+
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, running_mean, running_var, eps, momentum):
+        x, residual = x.contiguous(), residual.contiguous()
+        rows, C = x.shape
+        y = torch.empty_like(x)
+        mean = torch.empty(C, device=x.device, dtype=torch.float32)
+        rstd = torch.empty(C, device=x.device, dtype=torch.float32)
+        h, st = handle_and_stream(x)
+        h.call("gmf_batchnorm_residual_forward", x.data_ptr(), residual.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
+               mean.data_ptr(), rstd.data_ptr(), None if running_mean is None else running_mean.data_ptr(),
+               None if running_var is None else running_var.data_ptr(), rows, C, float(eps), float(momentum), 1, st)
+        ctx.save_for_backward(x, gamma.detach(), mean, rstd, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, mean, rstd, y = ctx.saved_tensors
+        dy = dy.contiguous()
+        rows, C = x.shape
+        dx = torch.empty_like(x)
+        dres = torch.empty_like(x)
+        dg = torch.empty(C, device=x.device, dtype=torch.float32)
+        db = torch.empty(C, device=x.device, dtype=torch.float32)
+        h, st = handle_and_stream(x)
+        h.call("gmf_batchnorm_train_backward", dy.data_ptr(), x.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+               gamma.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), rows, C, st)
+        h.call("gmf_relu_backward", dy.data_ptr(), y.data_ptr(), dres.data_ptr(), dy.numel(), st)
+        return dx, dres, dg, db, None, None, None, None
+
+
+def batchnorm_residual_train(x, residual, bn):
+    """relu(bn(x) + residual) with `bn`'s parameters and running statistics used / updated as torch would in train()."""
+    if bn.momentum is None:
+        raise NotImplementedError("gmf_amd.train: BatchNorm with cumulative moving average (momentum=None) is not used by GMF")
+    y = _BatchNormResidualTrain.apply(x, residual, bn.weight, bn.bias, bn.running_mean if bn.track_running_stats else None,
+                                      bn.running_var if bn.track_running_stats else None, bn.eps, bn.momentum)
+    if bn.track_running_stats and bn.num_batches_tracked is not None:
+        bn.num_batches_tracked += 1
+    return y
+
+
+def image_encoder_train(enc, image):
+    """The differentiable train-mode pass of a gmf_amd ImageEncoder: image [B, 3, H, W] fp32 on a HIP device (any layout, no
+    gradient) -> [B, 128, H', W'] (a channels-last view of the NHWC result), the same function as `enc.backbone(image)` in
+    train(): batch statistics, running statistics and num_batches_tracked updated per BatchNorm per call, gradients for all 48
+    trained tensors.  Walks enc.backbone's own modules and parameters; no host read, capturable after a warm-up."""
+    bb = enc.backbone
+    require_cuda_f32(image, "image")
+    if image.dim() != 4 or image.shape[1] != 3:
+        raise ValueError(f"gmf_amd.train: image must be [B, 3, H, W], got {tuple(image.shape)}")
+    B, _, H, W = image.shape
+    Hc, Wc = conv2d_out_size(H, W, 7, 2) if H > 0 and W > 0 else (0, 0)
+    Hf, Wf = (((Hc - 1) // 2 + 1) - 1) // 2 + 1, (((Wc - 1) // 2 + 1) - 1) // 2 + 1      # max-pool, then layer2's stride
+    if B < 1 or H < 1 or W < 1 or B * Hf * Wf < 2:
+        # torch's BatchNorm raises the same way ("Expected more than 1 value per channel when training"); nothing is launched
+        raise ValueError(f"gmf_amd.train: image {tuple(image.shape)} leaves the encoder's last BatchNorms {B * max(Hf, 0) * max(Wf, 0)} "
+                         f"row(s) ([{B}, 128, {Hf}, {Wf}]); training-mode batch statistics need more than one")
+    x, g = conv2d_train(image.detach(), bb.conv1, (B, H, W))
+    x = batchnorm_train(x, bb.bn1, relu=True)
+    x, g = maxpool_train(x, g)
+    for layer in (bb.layer1, bb.layer2):
+        for blk in layer:
+            if blk.downsample is None:
+                idt = x
+            else:
+                idt, _ = conv2d_train(x, blk.downsample[0], g)
+                idt = batchnorm_train(idt, blk.downsample[1])
+            out, g2 = conv2d_train(x, blk.conv1, g)
+            out = batchnorm_train(out, blk.bn1, relu=True)
+            out, g2 = conv2d_train(out, blk.conv2, g2)
+            x, g = batchnorm_residual_train(out, idt, blk.bn2), g2
+    Bo, Ho, Wo = g
+    return x.view(Bo, Ho, Wo, x.shape[1]).permute(0, 3, 1, 2)

@@ -914,6 +914,35 @@ int gmf_pose_head_backward(gmf_handle* h, const gmf_pose_params* p, const float*
 int gmf_weighted_procrustes_backward(gmf_handle* h, const float* X, const float* Y, const float* w, const int* offsets, int B,
                                      float eps, const float* d_R, const float* d_t, float* d_w, gmf_stream_t stream);
 
+/* ---- training of the image encoder (ResNet-34 -> layer2 in train(), GMF_PointDSC/models/resnet.py:36-75,195-216) -------
+ * Dense NHWC fp32 activations [B,H,W,C] (= rows x channels matrices: BatchNorm, ReLU and the column sums above apply as they
+ * are), weights as the nn.Conv2d parameter [cout,cin,ksize,ksize] fp32, pad = ksize / 2, no bias.  Supported
+ * (cin, cout, ksize, stride): (3,64,7,2) the stem, (64,64,3,1), (128,128,3,1), (64,128,3,2), (64,128,1,2).  All three passes
+ * contract on the fp32 MFMA; every sum has a fixed order (no float atomics): equal inputs give equal bits. */
+
+/* y [B,Ho,Wo,cout] = conv(x, w), Ho = (H + 2 pad - ksize) / stride + 1.  x is read through its element strides (sb, sc, sh, sw):
+ * dense NHWC for the four layer shapes; any non-negative strides (NCHW as the reference passes images) for the stem. */
+int gmf_conv2d_forward_f32(gmf_handle* h, const float* x, long long sb, long long sc, long long sh, long long sw, const float* w,
+                           float* y, int B, int H, int W, int cin, int cout, int ksize, int stride, gmf_stream_t stream);
+/* dx [B,H,W,cin] = the input gradient of that convolution for dy [B,Ho,Wo,cout] (+ dx_add when non-NULL: the residual
+ * branch's gradient); a gather, every entry written (0 where no output pixel reads the input pixel).  Not for the stem. */
+int gmf_conv2d_dgrad(gmf_handle* h, const float* dy, const float* w, const float* dx_add, float* dx, int B, int H, int W, int cin,
+                     int cout, int ksize, int stride, gmf_stream_t stream);
+/* dw [cout,cin,ksize,ksize] = sum over output pixels of dy[p][co] x[p stride + k - pad][ci]; the pixel range is split over
+ * workgroups into workspace slabs that are added in index order.  x strides as in the forward. */
+int gmf_conv2d_wgrad(gmf_handle* h, const float* x, long long sb, long long sc, long long sh, long long sw, const float* dy, float* dw,
+                     int B, int H, int W, int cin, int cout, int ksize, int stride, gmf_stream_t stream);
+/* nn.MaxPool2d(3, 2, 1) on NHWC (C % 4 == 0): y [B,Hp,Wp,C], Hp = (H - 1) / 2 + 1.  Backward: dx [B,H,W,C] from the saved input
+ * x and dy; each window's gradient goes to its first maximum in row-major window order (torch's rule). */
+int gmf_maxpool3x3s2_forward(gmf_handle* h, const float* x, float* y, int B, int H, int W, int C, gmf_stream_t stream);
+int gmf_maxpool3x3s2_backward(gmf_handle* h, const float* x, const float* dy, float* dx, int B, int H, int W, int C,
+                              gmf_stream_t stream);
+/* gmf_batchnorm_train_forward with the BasicBlock's identity branch: y = relu?(bn(x) + residual), residual [rows, C].  The
+ * backward is gmf_batchnorm_train_backward (y_relu = this y) for x and gmf_relu_backward(dy, y) for the residual. */
+int gmf_batchnorm_residual_forward(gmf_handle* h, const float* x, const float* residual, const float* gamma, const float* beta,
+                                   float* y, float* mean, float* rstd, float* running_mean, float* running_var, long long rows, int C,
+                                   float eps, float momentum, int relu, gmf_stream_t stream);
+
 /* ---- image encoder epilogue (ResNet BasicBlock, GMF_PointDSC/models/resnet.py:59-75) ------------------------------- */
 
 /* y = max(y + bias[c] (+ residual), 0) in place on an NHWC fp32 tensor of n_pixels x C (C % 4 == 0): the folded
