@@ -94,12 +94,13 @@ int gmf_colsum(gmf_handle* h, const float* x, const float* y, const float* mean,
   return GMF_OK;
 }
 
-int gmf_batchnorm_train_forward(gmf_handle* h, const float* x, const float* gamma, const float* beta, float* y, float* mean,
-                                float* rstd, float* running_mean, float* running_var, long long rows, int C, float eps,
-                                float momentum, int relu, gmf_stream_t stream) {
-  GMF_REQUIRE(h && x && gamma && beta && y && mean && rstd, GMF_ERR_BAD_ARG, "batchnorm_train_forward: null pointer");
-  GMF_REQUIRE((running_mean == nullptr) == (running_var == nullptr), GMF_ERR_BAD_ARG, "batchnorm_train_forward: running stats come together");
-  GMF_REQUIRE(rows > 1 && C > 0, GMF_ERR_UNSUPPORTED_SHAPE, "batchnorm_train_forward: need more than one row");
+// Dense train-mode BatchNorm, both exported forms: y = relu?(bn(x) (+ residual)); `who` prefixes the messages.
+static int bn_dense_forward(gmf_handle* h, const char* who, const float* x, const float* residual, const float* gamma, const float* beta,
+                            float* y, float* mean, float* rstd, float* running_mean, float* running_var, long long rows, int C,
+                            float eps, float momentum, int relu, gmf_stream_t stream) {
+  GMF_REQUIRE(h && x && gamma && beta && y && mean && rstd, GMF_ERR_BAD_ARG, std::string(who) + ": null pointer");
+  GMF_REQUIRE((running_mean == nullptr) == (running_var == nullptr), GMF_ERR_BAD_ARG, std::string(who) + ": running stats come together");
+  GMF_REQUIRE(rows > 1 && C > 0, GMF_ERR_UNSUPPORTED_SHAPE, std::string(who) + ": need more than one row");
   SetDevice sd(h, stream);
   const size_t n_part = (size_t)gmf::colsum_chunks((long)rows) * C;
   float *part, *sum, *sumsq;
@@ -110,8 +111,15 @@ int gmf_batchnorm_train_forward(gmf_handle* h, const float* x, const float* gamm
   // sum of squared deviations: x' = x - mean (centred), y' = (x - mean) * 1
   GMF_HIP(gmf::launch_colsum(x, x, nullptr, nullptr, mean, nullptr, 1, 0, (int)rows, (long)rows, C, part, sumsq, st));
   GMF_HIP(gmf::launch_bn_finish(sum, sumsq, mean, rstd, running_mean, running_var, C, (long)rows, eps, momentum, st));
-  GMF_HIP(gmf::launch_bn_apply(x, mean, rstd, gamma, beta, y, (long)rows, C, relu ? 1 : 0, st));
+  GMF_HIP(gmf::launch_bn_apply(x, mean, rstd, gamma, beta, y, (long)rows, C, relu ? 1 : 0, residual, st));
   return GMF_OK;
+}
+
+int gmf_batchnorm_train_forward(gmf_handle* h, const float* x, const float* gamma, const float* beta, float* y, float* mean,
+                                float* rstd, float* running_mean, float* running_var, long long rows, int C, float eps,
+                                float momentum, int relu, gmf_stream_t stream) {
+  return bn_dense_forward(h, "batchnorm_train_forward", x, nullptr, gamma, beta, y, mean, rstd, running_mean, running_var, rows, C, eps,
+                          momentum, relu, stream);
 }
 
 int gmf_batchnorm_train_backward(gmf_handle* h, const float* dy, const float* x, const float* y_relu, const float* mean,
@@ -387,21 +395,9 @@ int gmf_maxpool3x3s2_backward(gmf_handle* h, const float* x, const float* dy, fl
 int gmf_batchnorm_residual_forward(gmf_handle* h, const float* x, const float* residual, const float* gamma, const float* beta,
                                    float* y, float* mean, float* rstd, float* running_mean, float* running_var, long long rows, int C,
                                    float eps, float momentum, int relu, gmf_stream_t stream) {
-  GMF_REQUIRE(h && x && residual && gamma && beta && y && mean && rstd, GMF_ERR_BAD_ARG, "batchnorm_residual_forward: null pointer");
-  GMF_REQUIRE((running_mean == nullptr) == (running_var == nullptr), GMF_ERR_BAD_ARG, "batchnorm_residual_forward: running stats come together");
-  GMF_REQUIRE(rows > 1 && C > 0, GMF_ERR_UNSUPPORTED_SHAPE, "batchnorm_residual_forward: need more than one row");
-  SetDevice sd(h, stream);
-  const size_t n_part = (size_t)gmf::colsum_chunks((long)rows) * C;
-  float *part, *sum, *sumsq;
-  if (int rc = arena_carve(h, {arena_buf(part, n_part), arena_buf(sum, (size_t)C), arena_buf(sumsq, (size_t)C)})) return rc;
-  hipStream_t st = S(stream);
-  // the statistics exactly as gmf_batchnorm_train_forward takes them; only the apply differs
-  GMF_HIP(gmf::launch_colsum(x, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, (int)rows, (long)rows, C, part, sum, st));
-  GMF_HIP(gmf::launch_bn_finish(sum, nullptr, mean, rstd, nullptr, nullptr, C, (long)rows, eps, momentum, st));
-  GMF_HIP(gmf::launch_colsum(x, x, nullptr, nullptr, mean, nullptr, 1, 0, (int)rows, (long)rows, C, part, sumsq, st));
-  GMF_HIP(gmf::launch_bn_finish(sum, sumsq, mean, rstd, running_mean, running_var, C, (long)rows, eps, momentum, st));
-  GMF_HIP(gmf::launch_bn_apply_residual(x, residual, mean, rstd, gamma, beta, y, (long)rows, C, relu ? 1 : 0, st));
-  return GMF_OK;
+  GMF_REQUIRE(residual, GMF_ERR_BAD_ARG, "batchnorm_residual_forward: null pointer");
+  return bn_dense_forward(h, "batchnorm_residual_forward", x, residual, gamma, beta, y, mean, rstd, running_mean, running_var, rows, C,
+                          eps, momentum, relu, stream);
 }
 
 }  // extern "C"

@@ -8,7 +8,6 @@
 //   k_stem_wgrad          dW of the stem (K = 147 taps x 64 outputs)
 //   k_conv_wgrad_reduce   the slabs added in index order
 //   k_maxpool_fwd / _bwd  max-pool 3x3 stride 2 pad 1; the backward a gather that recomputes each window's argmax
-//   k_bn_apply_res        relu(bn(x) + identity)
 // Every contraction runs on v_mfma_f32_32x32x2_f32 (exact fp32 products, a k-ordered fma chain): no operand ranges to
 // guard, no weight image to re-pack per optimiser step.  No float atomics: every sum has one fixed order, so two runs give
 // the same bits.  MFMA operand layout as in train_kernels.hip: lane (h, i) = (lane >> 5, lane & 31) holds for its row
@@ -387,16 +386,6 @@ k_maxpool_bwd(const float* __restrict__ x, const float* __restrict__ dy, float* 
   reinterpret_cast<float4*>(dx)[idx] = make_float4(g[0], g[1], g[2], g[3]);
 }
 
-__global__ void __launch_bounds__(256)
-k_bn_apply_res(const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ mean, const float* __restrict__ rstd,
-               const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ y, int C, int relu, long total) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= total) return;
-  const int c = (int)(idx % C);
-  const float v = fmaf((x[idx] - mean[c]) * rstd[c], gamma[c], beta[c]) + res[idx];
-  y[idx] = relu ? fmaxf(v, 0.f) : v;
-}
-
 // ---- launchers --------------------------------------------------------------------------------------------------------
 bool conv2d_shape_ok(const Conv2dShape& s) {
   const int f[5][4] = {{3, 64, 7, 2}, {64, 64, 3, 1}, {128, 128, 3, 1}, {64, 128, 3, 2}, {64, 128, 1, 2}};
@@ -496,14 +485,6 @@ hipError_t launch_maxpool_bwd(const float* x, const float* dy, float* dx, int B,
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   hipLaunchKernelGGL(k_maxpool_bwd, dim3(blocks_of_256((size_t)B * H * W * (C / 4))), dim3(256), 0, st, x, dy, dx, B, H, W, Ho, Wo,
                      C / 4);
-  return hipGetLastError();
-}
-
-hipError_t launch_bn_apply_residual(const float* x, const float* residual, const float* mean, const float* rstd, const float* gamma,
-                                    const float* beta, float* y, long rows, int C, int relu, hipStream_t st) {
-  const long total = rows * C;
-  hipLaunchKernelGGL(k_bn_apply_res, dim3(blocks_of_256((size_t)total)), dim3(256), 0, st, x, residual, mean, rstd, gamma, beta, y, C,
-                     relu, total);
   return hipGetLastError();
 }
 

@@ -226,8 +226,9 @@ hipError_t launch_colsum(const float* x, const float* y, const float* mean, cons
                          const float* relu_y = nullptr, bool dual = false, float* out2 = nullptr);
 hipError_t launch_bn_finish(const float* sum, const float* sumsq, float* mean, float* rstd, float* run_mean, float* run_var, int C,
                             long rows, float eps, float momentum, hipStream_t s);
+// y = relu?((x - mean) rstd gamma + beta (+ residual)); residual may be nullptr
 hipError_t launch_bn_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y,
-                           long rows, int C, int relu, hipStream_t s);
+                           long rows, int C, int relu, const float* residual, hipStream_t s);
 hipError_t launch_bn_bwd(const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma, const float* sdy,
                          const float* sdyx, float* dx, long rows, int C, hipStream_t s, const float* relu_y = nullptr);
 hipError_t launch_relu_bwd(const float* dy, const float* y, float* out, long total, hipStream_t s);

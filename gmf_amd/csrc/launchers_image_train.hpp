@@ -44,8 +44,4 @@ hipError_t launch_conv2d_wgrad(const Conv2dShape& s, const float* x, long long s
 hipError_t launch_maxpool_fwd(const float* x, float* y, int B, int H, int W, int C, hipStream_t st);
 hipError_t launch_maxpool_bwd(const float* x, const float* dy, float* dx, int B, int H, int W, int C, hipStream_t st);
 
-// y = relu?((x - mean) rstd gamma + beta + residual): launch_bn_apply's sibling with the block's identity branch.
-hipError_t launch_bn_apply_residual(const float* x, const float* residual, const float* mean, const float* rstd, const float* gamma,
-                                    const float* beta, float* y, long rows, int C, int relu, hipStream_t st);
-
 }  // namespace gmf

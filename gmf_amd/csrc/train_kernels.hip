@@ -648,16 +648,19 @@ k_normalize_bwd(const float* __restrict__ y, const float* __restrict__ dy, const
 // =========================================================================================
 // BatchNorm1d in TRAINING mode over the rows of x [rows, C] (the reference's BatchNorm1d on [B, C, N], PointDSC.py:13-21,
 // 104-109: statistics per channel over batch and positions): the column statistics come from k_colsum_*; here the
-// element-wise halves.  forward: y = (x - mean[c]) * rstd[c] * gamma[c] + beta[c] (-> ReLU).
+// element-wise halves.  forward: y = (x - mean[c]) * rstd[c] * gamma[c] + beta[c] (kRes: + res, a BasicBlock's identity
+// branch, resnet.py:59-75; only that instance reads `res`) (-> ReLU).
 // backward (dy already masked by the ReLU): dx = gamma rstd (dy - sdy / R - xhat sdyx / R), sdy = sum_r dy, sdyx = sum_r dy xhat.
 // =========================================================================================
+template <bool kRes>
 __global__ void __launch_bounds__(256)
-k_bn_apply(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ gamma,
-           const float* __restrict__ beta, float* __restrict__ y, int C, int relu, long total) {
+k_bn_apply(const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ mean, const float* __restrict__ rstd,
+           const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ y, int C, int relu, long total) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const int c = (int)(idx % C);
-  const float v = fmaf((x[idx] - mean[c]) * rstd[c], gamma[c], beta[c]);
+  float v = fmaf((x[idx] - mean[c]) * rstd[c], gamma[c], beta[c]);
+  if (kRes) v += res[idx];
   y[idx] = relu ? fmaxf(v, 0.f) : v;
 }
 
@@ -929,9 +932,10 @@ hipError_t launch_bn_finish(const float* sum, const float* sumsq, float* mean, f
 }
 
 hipError_t launch_bn_apply(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y,
-                           long rows, int C, int relu, hipStream_t s) {
+                           long rows, int C, int relu, const float* residual, hipStream_t s) {
   const long total = rows * C;
-  hipLaunchKernelGGL(k_bn_apply, dim3(blocks_of(total)), dim3(256), 0, s, x, mean, rstd, gamma, beta, y, C, relu, total);
+  if (residual) hipLaunchKernelGGL(k_bn_apply<true>, dim3(blocks_of(total)), dim3(256), 0, s, x, residual, mean, rstd, gamma, beta, y, C, relu, total);
+  else hipLaunchKernelGGL(k_bn_apply<false>, dim3(blocks_of(total)), dim3(256), 0, s, x, residual, mean, rstd, gamma, beta, y, C, relu, total);
   return hipGetLastError();
 }
 

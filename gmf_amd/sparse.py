@@ -172,10 +172,6 @@ def _f32_dev(t, name, what):
     return t.contiguous()
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def _check_sources(xa, xb, M, what):
     """The two-source input [xa | xb] of a convolution, xa already through `_f32_dev`: (xb or None, ca, cb)."""
     if xa.dim() != 2 or xa.shape[0] != M:
@@ -249,9 +245,9 @@ def sparse_conv(plan: SparsePlan, map_index, out_level: int, xa, W, xb=None, sca
     out = _check_out(out, M, cout, (("xa", xa), ("xb", xb), ("W", W), ("scale", vecs[0]), ("shift", vecs[1]),
                                     ("residual", vecs[2])), what, xa.device)
     h, st = handle_and_stream(xa)
-    h.call("gmf_sparse_conv", _ptr(rp), _ptr(pairs), _ptr(by_off), _ptr(off_start), K, plan.count_ptr(out_level), M,
-           xa.data_ptr(), ca, _ptr(xb), cb, W.data_ptr(), cout, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), 1 if relu else 0,
-           int(nsplit), out.data_ptr(), st)
+    h.call("gmf_sparse_conv", _lib.ptr(rp), _lib.ptr(pairs), _lib.ptr(by_off), _lib.ptr(off_start), K, plan.count_ptr(out_level), M,
+           xa.data_ptr(), ca, _lib.ptr(xb), cb, W.data_ptr(), cout, _lib.ptr(vecs[0]), _lib.ptr(vecs[1]), _lib.ptr(vecs[2]),
+           1 if relu else 0, int(nsplit), out.data_ptr(), st)
     return out
 
 
@@ -270,8 +266,8 @@ def sparse_conv_wgrad(plan: SparsePlan, map_index, out_level: int, xa, dy, xb=No
     cout = dy.shape[1]
     dW = torch.empty((K, ca + cb, cout), dtype=torch.float32, device=xa.device)
     h, st = handle_and_stream(xa)
-    h.call("gmf_sparse_conv_wgrad", _ptr(rp), _ptr(pairs), _ptr(by_off), _ptr(off_start), K, plan.count_ptr(out_level),
-           xa.data_ptr(), ca, _ptr(xb), cb, dy.data_ptr(), cout, dW.data_ptr(), st)
+    h.call("gmf_sparse_conv_wgrad", _lib.ptr(rp), _lib.ptr(pairs), _lib.ptr(by_off), _lib.ptr(off_start), K, plan.count_ptr(out_level),
+           xa.data_ptr(), ca, _lib.ptr(xb), cb, dy.data_ptr(), cout, dW.data_ptr(), st)
     return dW
 
 
@@ -324,19 +320,16 @@ class _SparseConvFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        from .train import colsum, relu_backward
         xa, xb, W3, y = ctx.saved_tensors
         plan = ctx.plan
         dy = _f32_dev(dy, "grad", "sparse_conv backward")
         if ctx.relu:
-            g = torch.empty_like(dy)
-            h, st = handle_and_stream(dy)
-            h.call("gmf_relu_backward", dy.data_ptr(), y.data_ptr(), g.data_ptr(), dy.numel(), st)
-            dy = g
+            dy = relu_backward(dy, y)
         dW = db = dxa = dxb = None
         if ctx.needs_input_grad[5]:
             dW = sparse_conv_wgrad(plan, ctx.map_index, ctx.out_level, xa, dy, xb=xb).reshape(ctx.wshape)
         if ctx.has_b and ctx.needs_input_grad[6]:
-            from .train import colsum
             db = colsum(dy).reshape(1, -1)
         if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
             dx = sparse_conv_dgrad(plan, ctx.map_index, ctx.out_level, dy, W3)
@@ -385,7 +378,7 @@ def sparse_conv_narrow(plan: SparsePlan, map_index: int, out_level: int, x, W, s
     rp, pairs = plan.kernel_map(map_index)
     h, st = handle_and_stream(x)
     h.call("gmf_sparse_conv_narrow", rp.data_ptr(), pairs.data_ptr(), K, plan.count_ptr(out_level), M, x.data_ptr(), cin,
-           W.data_ptr(), cout, _ptr(vecs[0]), _ptr(vecs[1]), _ptr(vecs[2]), 1 if relu else 0, out.data_ptr(), st)
+           W.data_ptr(), cout, _lib.ptr(vecs[0]), _lib.ptr(vecs[1]), _lib.ptr(vecs[2]), 1 if relu else 0, out.data_ptr(), st)
     return out
 
 
@@ -416,8 +409,8 @@ def sparse_head_l2(plan: SparsePlan, level: int, xa, W1, W2, xb=None, bias=None,
     W1, W2 = W1.contiguous(), W2.contiguous()
     out = _check_out(out, M, cout, (("xa", xa), ("xb", xb), ("W1", W1), ("W2", W2), ("bias", bias)), what, xa.device)
     h, st = handle_and_stream(xa)
-    h.call("gmf_sparse_head_l2", plan.count_ptr(level), M, xa.data_ptr(), ca, _ptr(xb), cb, W1.data_ptr(), hid, W2.data_ptr(),
-           cout, _ptr(bias), 1 if normalize else 0, out.data_ptr(), st)
+    h.call("gmf_sparse_head_l2", plan.count_ptr(level), M, xa.data_ptr(), ca, _lib.ptr(xb), cb, W1.data_ptr(), hid, W2.data_ptr(),
+           cout, _lib.ptr(bias), 1 if normalize else 0, out.data_ptr(), st)
     return out
 
 

@@ -19,6 +19,13 @@ def _p(t, off=0):
     return t.data_ptr() + 4 * off
 
 
+def _call(name, on, *args):
+    """C function `name` on the handle and current stream of tensor `on`: a tensor goes as its data_ptr(), None as NULL, a bool
+    as 0 / 1, anything else (numbers, raw pointers such as `_p(...)`) as it is; the stream goes last."""
+    h, st = handle_and_stream(on)
+    h.call(name, *[a.data_ptr() if isinstance(a, torch.Tensor) else int(a) if isinstance(a, bool) else a for a in args], st)
+
+
 SIGMA_ON_DEVICE = object()       # [r5] marker in place of sigma's host value: the kernels read the parameter's device memory
 
 
@@ -51,10 +58,8 @@ def gemm(a, b, ta=False, tb=False, bias=None, residual=None, alpha=1.0, out=None
     if out is None:
         out = torch.empty((batch, m, n) if batch > 1 else (m, n), device=a.device, dtype=torch.float32)
         ldc, sc = n, m * n
-    h, st = handle_and_stream(a)
-    h.call("gmf_gemm_f32", 1 if ta else 0, 1 if tb else 0, _p(a, a_off), _p(b, b_off), _p(out, c_off),
-           None if bias is None else bias.data_ptr(), None if residual is None else _p(residual, c_off), m, n, k, lda, ldb,
-           ldc, sa, sb, sc, batch, float(alpha), 1 if relu else 0, st)
+    _call("gmf_gemm_f32", a, bool(ta), bool(tb), _p(a, a_off), _p(b, b_off), _p(out, c_off), bias,
+          None if residual is None else _p(residual, c_off), m, n, k, lda, ldb, ldc, sa, sb, sc, batch, float(alpha), bool(relu))
     return out
 
 
@@ -63,10 +68,8 @@ def colsum(x, y=None, mean=None, rstd=None, shift=0, L=None, dual=False, relu_y=
     from ONE pass; relu_y: x is masked by the saved output of a ReLU first."""
     rows, C = x.shape
     out = torch.empty(2 * C if dual else C, device=x.device, dtype=torch.float32)
-    h, st = handle_and_stream(x)
-    h.call("gmf_colsum", x.data_ptr(), None if y is None else y.data_ptr(), None if mean is None else mean.data_ptr(),
-           None if rstd is None else rstd.data_ptr(), None, None, 0, int(shift), int(L if L is not None else rows), rows, C,
-           None if relu_y is None else relu_y.data_ptr(), 1 if dual else 0, out.data_ptr(), st)
+    _call("gmf_colsum", x, x, y, mean, rstd, None, None, 0, int(shift), int(L if L is not None else rows), rows, C, relu_y, bool(dual),
+          out)
     return (out[:C], out[C:]) if dual else out
 
 
@@ -75,64 +78,59 @@ def layernorm_fwd(x, gamma, beta):
     y = torch.empty_like(x)
     mean = torch.empty(rows, device=x.device, dtype=torch.float32)
     rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
-    h, st = handle_and_stream(x)
-    h.call("gmf_layernorm_forward", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(),
-           rstd.data_ptr(), rows, C, st)
+    _call("gmf_layernorm_forward", x, x, gamma, beta, y, mean, rstd, rows, C)
     return y, mean, rstd
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dx_add=None):
     rows, C = x.shape
     dx = torch.empty_like(x)
-    h, st = handle_and_stream(x)
-    h.call("gmf_layernorm_backward", dy.data_ptr(), x.data_ptr(), gamma.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-           None if dx_add is None else dx_add.data_ptr(), dx.data_ptr(), rows, C, st)
+    _call("gmf_layernorm_backward", x, dy, x, gamma, mean, rstd, dx_add, dx, rows, C)
     return dx
 
 
 def lcpe_fwd(x2d, w, b, L):
     y = torch.empty_like(x2d)
-    h, st = handle_and_stream(x2d)
-    h.call("gmf_lcpe", 0, x2d.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), x2d.shape[0], L, x2d.shape[1], st)
+    _call("gmf_lcpe", x2d, 0, x2d, w, b, y, x2d.shape[0], L, x2d.shape[1])
     return y
 
 
 def lcpe_bwd(dy2d, w, L):
     dx = torch.empty_like(dy2d)
-    h, st = handle_and_stream(dy2d)
-    h.call("gmf_lcpe", 1, dy2d.data_ptr(), w.data_ptr(), None, dx.data_ptr(), dy2d.shape[0], L, dy2d.shape[1], st)
+    _call("gmf_lcpe", dy2d, 1, dy2d, w, None, dx, dy2d.shape[0], L, dy2d.shape[1])
     return dx
 
 
 def softmax_rows(S2d, scale, mul=None):
     P = torch.empty_like(S2d)
-    h, st = handle_and_stream(S2d)
-    h.call("gmf_softmax_rows", 0, S2d.data_ptr(), None, None if mul is None else mul.data_ptr(), P.data_ptr(), S2d.shape[0],
-           S2d.shape[1], float(scale), st)
+    _call("gmf_softmax_rows", S2d, 0, S2d, None, mul, P, S2d.shape[0], S2d.shape[1], float(scale))
     return P
 
 
 def softmax_rows_bwd(P2d, dP2d, scale, mul=None):
     dS = torch.empty_like(P2d)
-    h, st = handle_and_stream(P2d)
-    h.call("gmf_softmax_rows", 1, P2d.data_ptr(), dP2d.data_ptr(), None if mul is None else mul.data_ptr(), dS.data_ptr(),
-           P2d.shape[0], P2d.shape[1], float(scale), st)
+    _call("gmf_softmax_rows", P2d, 1, P2d, dP2d, mul, dS, P2d.shape[0], P2d.shape[1], float(scale))
     return dS
 
 
 def geglu_fwd(hdn):
     rows, H2 = hdn.shape
     g = torch.empty((rows, H2 // 2), device=hdn.device, dtype=torch.float32)
-    h, st = handle_and_stream(hdn)
-    h.call("gmf_geglu", 0, hdn.data_ptr(), None, g.data_ptr(), rows, H2 // 2, st)
+    _call("gmf_geglu", hdn, 0, hdn, None, g, rows, H2 // 2)
     return g
 
 
 def geglu_bwd(hdn, dg):
     dh = torch.empty_like(hdn)
-    h, st = handle_and_stream(hdn)
-    h.call("gmf_geglu", 1, hdn.data_ptr(), dg.data_ptr(), dh.data_ptr(), hdn.shape[0], hdn.shape[1] // 2, st)
+    _call("gmf_geglu", hdn, 1, hdn, dg, dh, hdn.shape[0], hdn.shape[1] // 2)
     return dh
+
+
+def relu_backward(dy, y):
+    """dy masked by the saved output y of a ReLU: y > 0 ? dy : 0 (gmf_relu_backward)."""
+    g = torch.empty_like(dy)
+    _call("gmf_relu_backward", dy, dy, y, g, dy.numel())
+    return g
 
 
 class _FusionLayerTrain(torch.autograd.Function):
@@ -277,10 +275,7 @@ class _Linear(torch.autograd.Function):
         x, W2, y = ctx.saved_tensors
         dy = dy.contiguous()
         if ctx.relu:
-            g = torch.empty_like(dy)
-            h, st = handle_and_stream(dy)
-            h.call("gmf_relu_backward", dy.data_ptr(), y.data_ptr(), g.data_ptr(), dy.numel(), st)
-            dy = g
+            dy = relu_backward(dy, y)
         dW = gemm(dy, x, ta=True).reshape(ctx.wshape)
         db = colsum(dy) if ctx.has_b else None
         dx = gemm(dy, W2)
@@ -292,19 +287,21 @@ def linear(x, W, b=None, residual=None, relu=False):
 
 
 class _BatchNormTrain(torch.autograd.Function):
-    """nn.BatchNorm1d in training mode on rows [rows, C] (+ fused ReLU); updates running_mean / running_var in place."""
+    """relu?(bn(x) (+ residual)) with nn.BatchNorm1d / 2d in training mode on rows [rows, C] (the residual: a BasicBlock's identity
+    branch, resnet.py:59-75); updates running_mean / running_var in place.  The residual's gradient is dy masked by the ReLU."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, relu):
+    def forward(ctx, x, residual, gamma, beta, running_mean, running_var, eps, momentum, relu):
         x = x.contiguous()
         rows, C = x.shape
         y = torch.empty_like(x)
         mean = torch.empty(C, device=x.device, dtype=torch.float32)
         rstd = torch.empty(C, device=x.device, dtype=torch.float32)
-        h, st = handle_and_stream(x)
-        h.call("gmf_batchnorm_train_forward", x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), mean.data_ptr(),
-               rstd.data_ptr(), None if running_mean is None else running_mean.data_ptr(),
-               None if running_var is None else running_var.data_ptr(), rows, C, float(eps), float(momentum), 1 if relu else 0, st)
+        tail = (gamma, beta, y, mean, rstd, running_mean, running_var, rows, C, float(eps), float(momentum), bool(relu))
+        if residual is None:
+            _call("gmf_batchnorm_train_forward", x, x, *tail)
+        else:
+            _call("gmf_batchnorm_residual_forward", x, x, residual.contiguous(), *tail)
         ctx.relu = relu
         ctx.save_for_backward(x, gamma.detach(), mean, rstd, y if relu else x.new_empty(0))
         return y
@@ -317,21 +314,30 @@ class _BatchNormTrain(torch.autograd.Function):
         dx = torch.empty_like(x)
         dg = torch.empty(C, device=x.device, dtype=torch.float32)
         db = torch.empty(C, device=x.device, dtype=torch.float32)
-        h, st = handle_and_stream(x)
-        h.call("gmf_batchnorm_train_backward", dy.data_ptr(), x.data_ptr(), y.data_ptr() if ctx.relu else None, mean.data_ptr(),
-               rstd.data_ptr(), gamma.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), rows, C, st)
-        return dx, dg, db, None, None, None, None, None
+        _call("gmf_batchnorm_train_backward", x, dy, x, y if ctx.relu else None, mean, rstd, gamma, dx, dg, db, rows, C)
+        dres = None
+        if ctx.needs_input_grad[1]:
+            dres = relu_backward(dy, y) if ctx.relu else dy
+        return dx, dres, dg, db, None, None, None, None, None
 
 
-def batchnorm_train(x, bn, relu=False):
-    """`bn`: an nn.BatchNorm1d whose parameters and running statistics are used / updated exactly as torch would in train()."""
+def _bn_tracked(bn, who, apply):
+    """torch's train-mode bookkeeping around `apply(running_mean, running_var)` ((None, None) when `bn` tracks none):
+    num_batches_tracked advances after the call.  Shared by the dense and the masked form."""
     if bn.momentum is None:
-        raise NotImplementedError("gmf_amd.train: BatchNorm with cumulative moving average (momentum=None) is not used by GMF")
-    y = _BatchNormTrain.apply(x, bn.weight, bn.bias, bn.running_mean if bn.track_running_stats else None,
-                              bn.running_var if bn.track_running_stats else None, bn.eps, bn.momentum, relu)
-    if bn.track_running_stats and bn.num_batches_tracked is not None:
+        raise NotImplementedError(f"gmf_amd.train: BatchNorm with cumulative moving average (momentum=None) is not used by {who}")
+    track = bn.track_running_stats
+    y = apply(*((bn.running_mean, bn.running_var) if track else (None, None)))
+    if track and bn.num_batches_tracked is not None:
         bn.num_batches_tracked += 1
     return y
+
+
+def batchnorm_train(x, bn, relu=False, residual=None):
+    """relu?(bn(x) (+ residual)); `bn`: an nn.BatchNorm1d / 2d whose parameters and running statistics are used / updated
+    exactly as torch would in train()."""
+    return _bn_tracked(bn, "GMF", lambda rm, rv: _BatchNormTrain.apply(x, residual, bn.weight, bn.bias, rm, rv, bn.eps, bn.momentum,
+                                                                      bool(relu)))
 
 
 class _SCAttention(torch.autograd.Function):
@@ -424,8 +430,7 @@ class _Normalize(torch.autograd.Function):
         x = x.contiguous()
         nrm = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
         y = torch.empty_like(x)
-        h, st = handle_and_stream(x)
-        h.call("gmf_normalize_rows", 0, x.data_ptr(), None, nrm.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], st)
+        _call("gmf_normalize_rows", x, 0, x, None, nrm, y, x.shape[0], x.shape[1])
         ctx.save_for_backward(y, nrm)
         return y
 
@@ -434,8 +439,7 @@ class _Normalize(torch.autograd.Function):
         y, nrm = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(y)
-        h, st = handle_and_stream(y)
-        h.call("gmf_normalize_rows", 1, y.data_ptr(), dy.data_ptr(), nrm.data_ptr(), dx.data_ptr(), y.shape[0], y.shape[1], st)
+        _call("gmf_normalize_rows", y, 1, y, dy, nrm, dx, y.shape[0], y.shape[1])
         return dx
 
 
@@ -454,9 +458,9 @@ class _SimilarityMatrix(torch.autograd.Function):
         on_dev = sigma_value is SIGMA_ON_DEVICE          # [r5] no host read: the kernels take sigma from the parameter's own memory
         sig = 1.0 if on_dev else (float(sigma) if sigma_value is None else float(sigma_value))     # (a caller that already read the scalar passes it)
         M = torch.empty((B, N, N), device=f.device, dtype=torch.float32)
-        h, st = handle_and_stream(f)
+        h, _ = handle_and_stream(f)
         with sigma_device(h, sigma if on_dev else None):
-            h.call("gmf_similarity_matrix", f.data_ptr(), B, N, sig, M.data_ptr(), N, st)
+            _call("gmf_similarity_matrix", f, f, B, N, sig, M, N)
         ctx.sig, ctx.sigma_is_tensor, ctx.sigma_dev = sig, torch.is_tensor(sigma), (sigma if on_dev else None)
         ctx.save_for_backward(f)
         return M
@@ -468,9 +472,9 @@ class _SimilarityMatrix(torch.autograd.Function):
         dM = dM.contiguous()
         dF = torch.empty_like(f)
         dsig = torch.empty(1, device=f.device, dtype=torch.float32)
-        h, st = handle_and_stream(f)
+        h, _ = handle_and_stream(f)
         with sigma_device(h, ctx.sigma_dev):
-            h.call("gmf_similarity_backward", f.data_ptr(), dM.data_ptr(), B, N, ctx.sig, dF.data_ptr(), dsig.data_ptr(), st)
+            _call("gmf_similarity_backward", f, f, dM, B, N, ctx.sig, dF, dsig)
         return dF, dsig if ctx.sigma_is_tensor else None, None
 
 
@@ -485,9 +489,7 @@ class _ClassificationLossFn(torch.autograd.Function):
     def forward(ctx, pred, gt, weight, balanced):
         pred = pred.contiguous()
         out = torch.empty(6, device=pred.device, dtype=torch.float32)
-        h, st = handle_and_stream(pred)
-        h.call("gmf_classification_loss", pred.data_ptr(), gt.data_ptr(), None if weight is None else weight.data_ptr(),
-               pred.shape[0], pred.shape[1], 1 if balanced else 0, out.data_ptr(), st)
+        _call("gmf_classification_loss", pred, pred, gt, weight, pred.shape[0], pred.shape[1], bool(balanced), out)
         ctx.balanced = balanced
         ctx.save_for_backward(pred, gt, weight if weight is not None else pred.new_empty(0))
         ctx.has_w = weight is not None
@@ -498,9 +500,8 @@ class _ClassificationLossFn(torch.autograd.Function):
     def backward(ctx, dloss, _dstats):
         pred, gt, weight = ctx.saved_tensors
         d = torch.empty_like(pred)
-        h, st = handle_and_stream(pred)
-        h.call("gmf_classification_backward", pred.data_ptr(), gt.data_ptr(), weight.data_ptr() if ctx.has_w else None,
-               pred.shape[0], pred.shape[1], 1 if ctx.balanced else 0, d.data_ptr(), st)
+        _call("gmf_classification_backward", pred, pred, gt, weight if ctx.has_w else None, pred.shape[0], pred.shape[1],
+              bool(ctx.balanced), d)
         return dloss * d, None, None, None
 
 
@@ -517,9 +518,7 @@ class _SpectralMatchingDense(torch.autograd.Function):
         if not (M.stride(2) == 1 and M.stride(1) >= N and M.stride(0) == N * M.stride(1)):
             M = M.contiguous()
         out = torch.empty(1, device=M.device, dtype=torch.float32)
-        h, st = handle_and_stream(M)
-        h.call("gmf_spectral_matching_loss", M.data_ptr(), M.stride(1), gt.data_ptr(), M.shape[0], N, 1 if balanced else 0,
-               out.data_ptr(), st)
+        _call("gmf_spectral_matching_loss", M, M, M.stride(1), gt, M.shape[0], N, bool(balanced), out)
         ctx.balanced = balanced
         ctx.save_for_backward(M, gt)
         return out[0].clone()
@@ -529,9 +528,7 @@ class _SpectralMatchingDense(torch.autograd.Function):
         M, gt = ctx.saved_tensors
         B, N = M.shape[0], M.shape[1]
         dM = torch.empty((B, N, N), device=M.device, dtype=torch.float32)
-        h, st = handle_and_stream(M)
-        h.call("gmf_spectral_matching_dense_backward", M.data_ptr(), M.stride(1), gt.data_ptr(), B, N, 1 if ctx.balanced else 0,
-               dM.data_ptr(), st)
+        _call("gmf_spectral_matching_dense_backward", M, M, M.stride(1), gt, B, N, bool(ctx.balanced), dM)
         return dloss * dM, None, None
 
 
@@ -543,8 +540,7 @@ def compat_dense(src, tgt, sigma_d):
     """[B, N, N] spatial-consistency matrix of PointDSC.py:216-221 (no gradient, as in the reference)."""
     B, N, _ = src.shape
     out = torch.empty((B, N, N), device=src.device, dtype=torch.float32)
-    h, st = handle_and_stream(src)
-    h.call("gmf_compat_dense", src.data_ptr(), tgt.data_ptr(), B, N, float(sigma_d), out.data_ptr(), st)
+    _call("gmf_compat_dense", src, src, tgt, B, N, float(sigma_d), out)
     return out
 
 
@@ -575,10 +571,9 @@ class _PoseHeadTrain(torch.autograd.Function):
         dT = dT.contiguous()
         dF = torch.empty_like(f)
         dsig = torch.empty(B, device=f.device, dtype=torch.float32)
-        h, st = handle_and_stream(f)
+        h, _ = handle_and_stream(f)
         with sigma_device(h, ctx.sigma_dev):
-            h.call("gmf_pose_head_backward", pp, f.data_ptr(), src.data_ptr(), tgt.data_ptr(), knn_idx.data_ptr(), fitness.data_ptr(),
-                   dT.data_ptr(), B, N, dF.data_ptr(), dsig.data_ptr(), st)
+            _call("gmf_pose_head_backward", f, pp, f, src, tgt, knn_idx, fitness, dT, B, N, dF, dsig)
         return dF, (dsig.sum().reshape(1) if ctx.sigma_is_tensor else None), None, None, None, None, None
 
 
@@ -638,6 +633,7 @@ class GraphedTrainingStep:
 # first, the rest written as 0 by every BatchNorm and every data gradient.
 
 
+# Not merged with the dense `_BatchNormTrain`: k_bnm_* chunk differently, take 1 / sqrtf for rsqrtf, write zero rows - other bits.
 class _BatchNormMasked(torch.autograd.Function):
     """MinkowskiBatchNorm in training mode over the counts[level] valid rows of x [M, C] (`gmf_batchnorm_masked_forward`), + an
     optional residual, + an optional ReLU; rows past the count are 0 in y and dx; the residual's gradient is the masked upstream
@@ -651,11 +647,8 @@ class _BatchNormMasked(torch.autograd.Function):
         y = torch.empty_like(x)
         mean = torch.empty(C, device=x.device, dtype=torch.float32)
         rstd = torch.empty(C, device=x.device, dtype=torch.float32)
-        h, st = handle_and_stream(x)
-        h.call("gmf_batchnorm_masked_forward", x.data_ptr(), None if res is None else res.data_ptr(), gamma.data_ptr(),
-               beta.data_ptr(), n_ptr, cap, C, float(eps), float(momentum), 1 if relu else 0, y.data_ptr(), mean.data_ptr(),
-               rstd.data_ptr(), None if running_mean is None else running_mean.data_ptr(),
-               None if running_var is None else running_var.data_ptr(), st)
+        _call("gmf_batchnorm_masked_forward", x, x, res, gamma, beta, n_ptr, cap, C, float(eps), float(momentum), bool(relu), y, mean,
+              rstd, running_mean, running_var)
         ctx.relu, ctx.n_ptr, ctx.has_res = relu, n_ptr, residual is not None
         ctx.save_for_backward(x, gamma.detach(), mean, rstd, y if relu else None)
         return y
@@ -669,23 +662,15 @@ class _BatchNormMasked(torch.autograd.Function):
         dx = torch.empty_like(x)
         dg = torch.empty(C, device=x.device, dtype=torch.float32)
         db = torch.empty(C, device=x.device, dtype=torch.float32)
-        h, st = handle_and_stream(x)
-        h.call("gmf_batchnorm_masked_backward", dy.data_ptr(), x.data_ptr(), y.data_ptr() if ctx.relu else None, mean.data_ptr(),
-               rstd.data_ptr(), gamma.data_ptr(), ctx.n_ptr, cap, C, g.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), st)
+        _call("gmf_batchnorm_masked_backward", x, dy, x, y if ctx.relu else None, mean, rstd, gamma, ctx.n_ptr, cap, C, g, dx, dg, db)
         return dx, (g if ctx.has_res else None), dg, db, None, None, None, None, None, None
 
 
 def batchnorm_masked(x, bn, plan, level: int, residual=None, relu: bool = False):
     """`bn` (an nn.BatchNorm1d) in train() mode over the valid rows of level `level` of `plan`: relu?(bn(x) + residual), rows past
     counts[level] written as 0.  Parameters and running statistics are used / updated exactly as torch would."""
-    if bn.momentum is None:
-        raise NotImplementedError("gmf_amd.train: BatchNorm with cumulative moving average (momentum=None) is not used by DGR")
-    track = bn.track_running_stats
-    y = _BatchNormMasked.apply(x, residual, bn.weight, bn.bias, bn.running_mean if track else None,
-                               bn.running_var if track else None, plan.count_ptr(level), bn.eps, bn.momentum, bool(relu))
-    if track and bn.num_batches_tracked is not None:
-        bn.num_batches_tracked += 1
-    return y
+    return _bn_tracked(bn, "DGR", lambda rm, rv: _BatchNormMasked.apply(x, residual, bn.weight, bn.bias, rm, rv, plan.count_ptr(level),
+                                                                       bn.eps, bn.momentum, bool(relu)))
 
 
 def resunet_train(model, coords, feats, p_image=None, q_image=None, p_tokens=None, q_tokens=None):
@@ -760,8 +745,7 @@ class _Conv2dTrain(torch.autograd.Function):
         strides = tuple(x.stride()) if image else (H * Wd * cin, 1, Wd * cin, cin)          # (sb, sc, sh, sw) in elements
         Ho, Wo = conv2d_out_size(H, Wd, ks, stride)
         y = torch.empty((B * Ho * Wo, cout), device=x.device, dtype=torch.float32)
-        h, st = handle_and_stream(x)
-        h.call("gmf_conv2d_forward_f32", x.data_ptr(), *strides, Wc.data_ptr(), y.data_ptr(), B, H, Wd, cin, cout, ks, stride, st)
+        _call("gmf_conv2d_forward_f32", x, x, *strides, Wc, y, B, H, Wd, cin, cout, ks, stride)
         ctx.geom, ctx.stride, ctx.strides, ctx.image = (B, H, Wd, cin, cout, ks), stride, strides, image
         ctx.save_for_backward(x, Wc)
         return y
@@ -771,13 +755,12 @@ class _Conv2dTrain(torch.autograd.Function):
         x, Wc = ctx.saved_tensors
         B, H, Wd, cin, cout, ks = ctx.geom
         dy = dy.contiguous()
-        h, st = handle_and_stream(dy)
         dW = torch.empty_like(Wc)
-        h.call("gmf_conv2d_wgrad", x.data_ptr(), *ctx.strides, dy.data_ptr(), dW.data_ptr(), B, H, Wd, cin, cout, ks, ctx.stride, st)
+        _call("gmf_conv2d_wgrad", dy, x, *ctx.strides, dy, dW, B, H, Wd, cin, cout, ks, ctx.stride)
         dx = None
         if not ctx.image and ctx.needs_input_grad[0]:
             dx = torch.empty((B * H * Wd, cin), device=dy.device, dtype=torch.float32)
-            h.call("gmf_conv2d_dgrad", dy.data_ptr(), Wc.data_ptr(), None, dx.data_ptr(), B, H, Wd, cin, cout, ks, ctx.stride, st)
+            _call("gmf_conv2d_dgrad", dy, dy, Wc, None, dx, B, H, Wd, cin, cout, ks, ctx.stride)
         return dx, dW, None, None
 
 
@@ -802,8 +785,7 @@ class _MaxPoolTrain(torch.autograd.Function):
         C = x.shape[1]
         Hp, Wp = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         y = torch.empty((B * Hp * Wp, C), device=x.device, dtype=torch.float32)
-        h, st = handle_and_stream(x)
-        h.call("gmf_maxpool3x3s2_forward", x.data_ptr(), y.data_ptr(), B, H, W, C, st)
+        _call("gmf_maxpool3x3s2_forward", x, x, y, B, H, W, C)
         ctx.geom = geom
         ctx.save_for_backward(x)
         return y
@@ -814,59 +796,13 @@ class _MaxPoolTrain(torch.autograd.Function):
         B, H, W = ctx.geom
         dy = dy.contiguous()
         dx = torch.empty_like(x)
-        h, st = handle_and_stream(x)
-        h.call("gmf_maxpool3x3s2_backward", x.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, H, W, x.shape[1], st)
+        _call("gmf_maxpool3x3s2_backward", x, x, dy, dx, B, H, W, x.shape[1])
         return dx, None
 
 
 def maxpool_train(x, geom):
     B, H, W = geom
     return _MaxPoolTrain.apply(x, geom), (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
-
-
-class _BatchNormResidualTrain(torch.autograd.Function):
-    """relu(bn(x) + residual) in training mode on rows [rows, C] (BasicBlock.forward, resnet.py:59-75); the residual form of
-    `_BatchNormTrain`.  Backward: the BatchNorm's, masked by the block's output, and the ReLU's for the identity branch."""
-
-    @staticmethod
-    def forward(ctx, x, residual, gamma, beta, running_mean, running_var, eps, momentum):
-        x, residual = x.contiguous(), residual.contiguous()
-        rows, C = x.shape
-        y = torch.empty_like(x)
-        mean = torch.empty(C, device=x.device, dtype=torch.float32)
-        rstd = torch.empty(C, device=x.device, dtype=torch.float32)
-        h, st = handle_and_stream(x)
-        h.call("gmf_batchnorm_residual_forward", x.data_ptr(), residual.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(),
-               mean.data_ptr(), rstd.data_ptr(), None if running_mean is None else running_mean.data_ptr(),
-               None if running_var is None else running_var.data_ptr(), rows, C, float(eps), float(momentum), 1, st)
-        ctx.save_for_backward(x, gamma.detach(), mean, rstd, y)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, gamma, mean, rstd, y = ctx.saved_tensors
-        dy = dy.contiguous()
-        rows, C = x.shape
-        dx = torch.empty_like(x)
-        dres = torch.empty_like(x)
-        dg = torch.empty(C, device=x.device, dtype=torch.float32)
-        db = torch.empty(C, device=x.device, dtype=torch.float32)
-        h, st = handle_and_stream(x)
-        h.call("gmf_batchnorm_train_backward", dy.data_ptr(), x.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-               gamma.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), rows, C, st)
-        h.call("gmf_relu_backward", dy.data_ptr(), y.data_ptr(), dres.data_ptr(), dy.numel(), st)
-        return dx, dres, dg, db, None, None, None, None
-
-
-def batchnorm_residual_train(x, residual, bn):
-    """relu(bn(x) + residual) with `bn`'s parameters and running statistics used / updated as torch would in train()."""
-    if bn.momentum is None:
-        raise NotImplementedError("gmf_amd.train: BatchNorm with cumulative moving average (momentum=None) is not used by GMF")
-    y = _BatchNormResidualTrain.apply(x, residual, bn.weight, bn.bias, bn.running_mean if bn.track_running_stats else None,
-                                      bn.running_var if bn.track_running_stats else None, bn.eps, bn.momentum)
-    if bn.track_running_stats and bn.num_batches_tracked is not None:
-        bn.num_batches_tracked += 1
-    return y
 
 
 def image_encoder_train(enc, image):
@@ -898,6 +834,6 @@ def image_encoder_train(enc, image):
             out, g2 = conv2d_train(x, blk.conv1, g)
             out = batchnorm_train(out, blk.bn1, relu=True)
             out, g2 = conv2d_train(out, blk.conv2, g2)
-            x, g = batchnorm_residual_train(out, idt, blk.bn2), g2
+            x, g = batchnorm_train(out, blk.bn2, relu=True, residual=idt), g2          # resnet.py:59-75
     Bo, Ho, Wo = g
     return x.view(Bo, Ho, Wo, x.shape[1]).permute(0, 3, 1, 2)

@@ -159,11 +159,13 @@ def bn_residual_case(rows, C, seed):
     return c
 
 
-def bn_residual_autograd(c, dtype, eps=1e-5, momentum=0.1):
-    """relu(batch_norm(x) + res) in training mode: outputs, the four gradients and the updated running statistics."""
+def bn_residual_autograd(c, dtype, relu=True, eps=1e-5, momentum=0.1):
+    """relu?(batch_norm(x) + res) in training mode: outputs, the four gradients and the updated running statistics."""
     x, res, gamma, beta = (c[k].detach().clone().to(dtype).requires_grad_(True) for k in ("x", "res", "gamma", "beta"))
     rm, rv = c["rm"].to(dtype).clone(), c["rv"].to(dtype).clone()
-    y = torch.relu(F.batch_norm(x, rm, rv, gamma, beta, True, momentum, eps) + res)
+    y = F.batch_norm(x, rm, rv, gamma, beta, True, momentum, eps) + res
+    if relu:
+        y = torch.relu(y)
     y.backward(c["dy"].to(dtype))
     return {"y": y.detach(), "dx": x.grad, "dres": res.grad, "dgamma": gamma.grad, "dbeta": beta.grad, "running_mean": rm,
             "running_var": rv}

@@ -169,11 +169,13 @@ def test_maxpool_matches_fp64(B, H, W, ties):
 
 
 # ---- 3. residual BatchNorm + ReLU ---------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C", [64, 128])
-def test_batchnorm_residual_matches_fp64(C):
-    """relu(bn(x) + identity) in training mode at 297 rows, forward and backward, running statistics included."""
+@pytest.mark.parametrize("C,relu", [pytest.param(64, True, id="64"), pytest.param(128, True, id="128"),
+                                    pytest.param(64, False, id="64-norelu"), pytest.param(128, False, id="128-norelu")])
+def test_batchnorm_residual_matches_fp64(C, relu):
+    """relu?(bn(x) + identity) in training mode at 297 rows, forward and backward, running statistics included: the residual
+    instance of k_bn_apply and not the plain one; without the ReLU no k_relu_bwd, and the residual's gradient is dy's bits."""
     c = T.bn_residual_case(297, C, seed=C)
-    ref, f32 = T.bn_residual_autograd(c, torch.float64), T.bn_residual_autograd(c, torch.float32)
+    ref, f32 = T.bn_residual_autograd(c, torch.float64, relu), T.bn_residual_autograd(c, torch.float32, relu)
     bn = torch.nn.BatchNorm1d(C)
     with torch.no_grad():
         bn.weight.copy_(c["gamma"]); bn.bias.copy_(c["beta"]); bn.running_mean.copy_(c["rm"]); bn.running_var.copy_(c["rv"])
@@ -181,12 +183,15 @@ def test_batchnorm_residual_matches_fp64(C):
     x, res = c["x"].to(DEV).requires_grad_(True), c["res"].to(DEV).requires_grad_(True)
 
     def run():
-        y = TR.batchnorm_residual_train(x, res, bn)
+        y = TR.batchnorm_train(x, bn, relu=relu, residual=res)
         y.backward(c["dy"].to(DEV))
         return y
     y, names = R.launched(run)
-    assert "k_bn_apply_res" in _names(names) and "k_bn_bwd" in _names(names) and "k_relu_bwd" in _names(names), dict(names)
-    got = {"y": y.detach(), "dx": x.grad, "dres": res.grad, "dgamma": bn.weight.grad, "dbeta": bn.bias.grad,
+    assert ("k_bn_apply", (True,)) in names and ("k_bn_apply", (False,)) not in names, dict(names)
+    assert "k_bn_bwd" in _names(names) and ("k_relu_bwd" in _names(names)) == relu, dict(names)
+    if not relu:
+        assert torch.equal(res.grad, c["dy"].to(DEV))
+    got ={"y": y.detach(), "dx": x.grad, "dres": res.grad, "dgamma": bn.weight.grad, "dbeta": bn.bias.grad,
            "running_mean": bn.running_mean, "running_var": bn.running_var}
     for k in got:
         _report(check_close({k: got[k]}, {k: ref[k]}, {k: f32[k]}, what=f"bn residual C={C} {k}: "))
@@ -258,8 +263,10 @@ def test_encoder_train_matches_stock_backbone_fp64(shape):
     bad = [k for k in foreign if any(w in k.lower() for w in ("miopen", "conv", "pool", "batch_norm", "batchnorm", "gemm", "cijk"))]
     assert not bad, bad
     for name in ("k_stem_f32", "k_stem_wgrad", "k_conv2d_f32", "k_conv2d_wgrad", "k_conv_wgrad_reduce", "k_maxpool_fwd",
-                 "k_maxpool_bwd", "k_bn_apply_res", "k_bn_apply", "k_bn_bwd"):
+                 "k_maxpool_bwd", "k_bn_apply", "k_bn_bwd"):
         assert name in ours, (name, sorted(ours))
+    instances = {R.parse_kernel(k) for k in keys if R.parse_kernel(k)}
+    assert {("k_bn_apply", (True,)), ("k_bn_apply", (False,))} <= instances, sorted(instances, key=str)
     assert len(g64) == 48
     assert o64["out0"].shape == outs["out0"].shape
     _report(check_close(outs, o64, o32, what="output "))

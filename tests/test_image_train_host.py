@@ -41,8 +41,26 @@ def test_encoder_exposes_native_train():
     import gmf_amd
     from gmf_amd import train
     assert gmf_amd.ImageEncoder.native_train is True
-    for name in ("_Conv2dTrain", "_MaxPoolTrain", "_BatchNormResidualTrain", "image_encoder_train"):
+    for name in ("_Conv2dTrain", "_MaxPoolTrain", "_BatchNormTrain", "image_encoder_train"):
         assert hasattr(train, name), name
+
+
+def test_call_converts_arguments(monkeypatch):
+    """train._call with a stub handle: tensor -> data_ptr(), None -> NULL, bool -> 0 / 1, numbers and raw pointers untouched,
+    the stream last, the handle taken from the tensor named first."""
+    from gmf_amd import train
+
+    class Stub:
+        def call(self, *a):
+            self.args = a
+    stub, asked = Stub(), []
+    monkeypatch.setattr(train, "handle_and_stream", lambda t: (asked.append(t), (stub, 77))[1])
+    on, t = torch.zeros(3), torch.ones(2, 2)
+    raw = t.data_ptr() + 8
+    train._call("gmf_name", on, t, None, True, False, 5, 0.25, raw)
+    assert len(asked) == 1 and asked[0] is on
+    assert stub.args == ("gmf_name", t.data_ptr(), None, 1, 0, 5, 0.25, raw, 77)
+    assert [type(a) for a in stub.args[3:8]] == [int, int, int, float, int]
 
 
 SIZES = {1: [(3, 9, 11)], 2: [(3, 9, 11), (3, 10, 12)]}
