@@ -18,6 +18,7 @@ from .solvers import (ransac_correspondence_batched, icp_point_to_point_batched,
                       registration_ransac_based_on_correspondence, registration_icp, icp_refine,
                       ransac_feature_matching_batched, registration_ransac_based_on_feature_matching)
 from .spectral import spectral_matching_batched, SM   # noqa: F401
+from .clique import max_clique_batched, PMC, compatibility_graph   # noqa: F401
 from .features import (radius_knn_batched, estimate_normals_batched, compute_fpfh_batched,  # noqa: F401
                        voxel_down_sample_batched, voxel_select_batched, voxel_down_sample, voxel_select, estimate_normals,
                        compute_fpfh_feature, fpfh_descriptors)
@@ -39,6 +40,7 @@ __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointD
            "fpfh_descriptors", "SparsePlan", "sparse_conv", "sparse_conv_narrow", "sparse_head_l2", "ResUNetBN2C", "ResUNetBN2CX",
            "inlier_coordinates", "fcgf", "dgr", "find_knn_gpu_batch", "find_knn_batch", "find_pairs", "matching_indices_batched",
            "find_correct_correspondence", "generate_inlier_input", "ransac_feature_matching_batched",
-           "registration_ransac_based_on_feature_matching", "spectral_matching_batched", "SM", "information_matrix_batched",
+           "registration_ransac_based_on_feature_matching", "spectral_matching_batched", "SM", "max_clique_batched", "PMC",
+           "compatibility_graph", "information_matrix_batched",
            "global_optimization", "local_refinement_batched", "loop_closure_mask", "odometry_poses", "absolute_trajectory_error",
            "multiway_registration"]

@@ -220,6 +220,8 @@ SIGNATURES = {
     "gmf_ransac_feature_matching": (C.c_int, [_vp] * 6 + [C.c_int, _ll, _ll, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                               C.c_float, C.c_float, C.c_ulonglong, C.c_int, C.c_int] + [_vp] * 11),
     "gmf_spectral_matching": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "gmf_max_clique": (C.c_int, [_vp] * 5 + [C.c_int, _ll, C.c_int, C.c_float, C.c_int, _ll] + [_vp] * 7),
+    "gmf_pmc_graph": (C.c_int, [_vp, _vp, _vp, C.c_int, _ll, C.c_int, C.c_float, C.c_int, _vp, _vp, _vp]),
     "gmf_radius_knn": (C.c_int, [_vp, _vp, _vp, C.c_int, _ll, C.c_double, C.c_int, _vp, _vp, _vp, _vp]),
     "gmf_estimate_normals": (C.c_int, [_vp, _vp, _vp, C.c_int, _ll, C.c_double, C.c_int, _vp, _vp]),
     "gmf_compute_fpfh": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _ll, C.c_double, C.c_int, _vp, _vp]),

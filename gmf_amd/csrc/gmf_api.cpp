@@ -23,6 +23,7 @@
 #include "launchers_dgr_input.hpp"
 #include "launchers_correspondence.hpp"
 #include "launchers_posegraph.hpp"
+#include "launchers_clique.hpp"
 
 namespace {
 
@@ -34,6 +35,23 @@ int check_cloud_args(gmf_handle* h, const char* what, const void* pts, const voi
               std::string(what) + ": empty batch, more clouds than rows, or 2^30 rows or more");
   GMF_REQUIRE(r > 0 && std::isfinite(r), GMF_ERR_BAD_ARG, std::string(what) + ": radius / voxel size must be > 0 and finite");
   GMF_REQUIRE(max_nn >= 1 && max_nn <= gmf::kKnnMaxNN, GMF_ERR_BAD_ARG, std::string(what) + ": max_nn must be in 1..256");
+  return GMF_OK;
+}
+
+// the checks gmf_pmc_graph and gmf_max_clique share
+int check_pmc_args(gmf_handle* h, const char* what, const void* corr, const int* offsets, int B, long long total_rows, int max_n,
+                          float inlier_threshold, int metric) {
+  const std::string w(what);
+  GMF_REQUIRE(h && offsets, GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(B > 0 && B <= 65535, GMF_ERR_UNSUPPORTED_SHAPE, w + ": B must be in 1..65535");
+  GMF_REQUIRE(max_n >= 0 && total_rows >= 0, GMF_ERR_BAD_ARG, w + ": max_n and total_rows must be >= 0");
+  GMF_REQUIRE(max_n <= gmf::kPmcMaxN, GMF_ERR_UNSUPPORTED_SHAPE, w + ": a pair holds at most 8192 rows");
+  GMF_REQUIRE(total_rows < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE, w + ": total_rows must be below 2^31");
+  GMF_REQUIRE(max_n == 0 || total_rows == 0 || corr, GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(inlier_threshold > 0.f && std::isfinite(inlier_threshold), GMF_ERR_BAD_ARG,
+              w + ": inlier_threshold must be finite and > 0");
+  GMF_REQUIRE(metric == gmf::kPmcSquared || metric == gmf::kPmcLength, GMF_ERR_BAD_ARG,
+              w + ": metric must be 0 (squared lengths) or 1 (lengths)");
   return GMF_OK;
 }
 
@@ -261,6 +279,11 @@ int gmf_set_tuning(gmf_handle* h, const char* name, int value) {
     t.spectral_col_splits = value;
     return GMF_OK;
   }
+  if (std::strcmp(name, "clique_local_rows") == 0) {   // maximum clique: roots of up to this many candidates are searched in LDS (default 384), 0 = none
+    GMF_REQUIRE(value >= 0 && value <= gmf::kPmcLocal, GMF_ERR_BAD_ARG, "set_tuning: clique_local_rows out of range (0..384)");
+    t.clique_local_rows = value;
+    return GMF_OK;
+  }
   return fail(h, GMF_ERR_BAD_ARG, std::string("gmf: set_tuning: unknown knob ") + name);
 }
 
@@ -275,7 +298,8 @@ int gmf_get_tuning(gmf_handle* h, const char* name, int* value) {
       {"fused_linear", t.fused_linear ? 1 : 0}, {"compat_cache", t.use_cache ? 1 : 0}, {"conv_lds_patch", t.conv_patch}, {"conv_small_grid", t.conv_small ? 1 : 0}, {"small_prologue_roles", t.small_prologue ? 1 : 0}, {"small_fattn_tile", t.small_fattn_tile ? 1 : 0},
       {"nms_binned", t.nms_binned}, {"topk_select", t.topk_select ? 1 : 0}, {"wide_attn_tile", t.wide_attn_tile ? 1 : 0},
       {"small_merge_tile", t.small_merge_tile ? 1 : 0}, {"mid_grid_roles", t.mid_grid_roles}, {"pv_fp8", t.pv_fp8}, {"q_in_attention", t.q_in_attention ? 1 : 0},
-      {"compat_format", t.compat_format}, {"precision", t.precision}, {"spectral_col_splits", t.spectral_col_splits}};
+      {"compat_format", t.compat_format}, {"precision", t.precision}, {"spectral_col_splits", t.spectral_col_splits},
+      {"clique_local_rows", t.clique_local_rows}};
   for (const auto& e : tab) {
     if (std::strcmp(name, e.name) == 0) { *value = e.v; return GMF_OK; }
   }
@@ -1612,6 +1636,33 @@ int gmf_spectral_matching(gmf_handle* h, const float* corr, const float* src, co
   if (int rc = arena_carve(h, {arena_buf(partial, gmf::sm_scratch_floats(total_rows, max_n, forced))})) return rc;
   GMF_HIP(gmf::launch_spectral_matching(corr, src, tgt, offsets, B, total_rows, max_n, inlier_threshold, topk, iterations, forced,
                                         partial, eig_out, labels_out, T_out, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_pmc_graph(gmf_handle* h, const float* corr, const int* offsets, int B, long long total_rows, int max_n,
+                  float inlier_threshold, int metric, unsigned long long* bits_out, int* degree_out, gmf_stream_t stream) {
+  if (int rc = check_pmc_args(h, "pmc_graph", corr, offsets, B, total_rows, max_n, inlier_threshold, metric)) return rc;
+  GMF_REQUIRE(max_n == 0 || total_rows == 0 || (bits_out && degree_out), GMF_ERR_BAD_ARG, "pmc_graph: null pointer");
+  SetDevice sd(h, stream);
+  GMF_HIP(gmf::launch_pmc_graph(corr, offsets, B, total_rows, max_n, inlier_threshold, metric, bits_out, degree_out, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_max_clique(gmf_handle* h, const float* corr, const float* src, const float* tgt, const int* offsets, int B,
+                   long long total_rows, int max_n, float inlier_threshold, int metric, long long max_steps, float* labels_out,
+                   float* T_out, int* size_out, int* exact_out, long long* steps_out, int* degree_out, gmf_stream_t stream) {
+  if (int rc = check_pmc_args(h, "max_clique", corr, offsets, B, total_rows, max_n, inlier_threshold, metric)) return rc;
+  GMF_REQUIRE(T_out && size_out && exact_out && steps_out, GMF_ERR_BAD_ARG, "max_clique: null pointer");
+  GMF_REQUIRE(max_n == 0 || total_rows == 0 || (src && tgt && labels_out && degree_out), GMF_ERR_BAD_ARG,
+              "max_clique: null pointer");
+  GMF_REQUIRE(max_steps >= 1, GMF_ERR_BAD_ARG, "max_clique: max_steps must be >= 1");
+  SetDevice sd(h, stream);
+  gmf::PmcScratch ws;
+  ArenaList bufs;
+  gmf::pmc_scratch_list(B, total_rows, max_n, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  GMF_HIP(gmf::launch_max_clique(corr, src, tgt, offsets, B, total_rows, max_n, inlier_threshold, metric, max_steps,
+                                 h->tune.clique_local_rows, ws, labels_out, T_out, size_out, exact_out, steps_out, degree_out, S(stream)));
   return GMF_OK;
 }
 

@@ -84,6 +84,7 @@ struct Tuning {
                              // 1 = throughput numerics: the spatial-consistency attention multiplies plain
                              // fp16 operands (one product, fp32 accumulation) and streams c as fp16 - outside the 1e-4 gate
   int spectral_col_splits = 0;   // spectral matching: column splits of a pair's sweep, 0 = from the pair's N (launchers_spectral.hpp), 1..32 = forced
+  int clique_local_rows = 384;   // maximum clique: a root with at most this many candidates is searched in LDS (launchers_clique.hpp), 0..384
 };
 
 hipError_t launch_compat_build(const float* pts8, float* c_dense, int B, int N, int tiles, float sigma_d, int fmt, hipStream_t s,

@@ -42,4 +42,9 @@ hipError_t launch_spectral_matching(const float* corr, const float* src, const f
                                     int forced_splits, float* partial, float* eig, float* labels, float* T_out,
                                     hipStream_t s);
 
+// k_sm_pose alone, for every caller of rigid_transform_3d with per-row weights eig * labels (the maximum-clique baseline passes
+// its 0 / 1 labels as both): T_out [B,16].  One launch.
+hipError_t launch_sm_pose(const float* src, const float* tgt, float* eig, float* labels, const int* offsets, int B,
+                          long long total_rows, int max_n, float* T_out, hipStream_t s);
+
 }  // namespace gmf

@@ -226,6 +226,12 @@ k_sm_pose(const float* __restrict__ src, const float* __restrict__ tgt, float* _
   T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
 }
 
+hipError_t launch_sm_pose(const float* src, const float* tgt, float* eig, float* labels, const int* offsets, int B,
+                          long long total_rows, int max_n, float* T_out, hipStream_t s) {
+  hipLaunchKernelGGL(k_sm_pose, dim3(B), dim3(256), 0, s, src, tgt, eig, labels, offsets, T_out, total_rows, max_n);
+  return hipGetLastError();
+}
+
 hipError_t launch_spectral_matching(const float* corr, const float* src, const float* tgt, const int* offsets, int B,
                                     long long total_rows, int max_n, float inlier_threshold, const int* topk, int iterations,
                                     int forced_splits, float* partial, float* eig, float* labels, float* T_out,
@@ -242,8 +248,7 @@ hipError_t launch_spectral_matching(const float* corr, const float* src, const f
     }
     hipLaunchKernelGGL(k_sm_rank, dim3((max_n + 63) / 64, B), dim3(256), 0, s, eig, offsets, topk, labels, total_rows, max_n);
   }
-  hipLaunchKernelGGL(k_sm_pose, dim3(B), dim3(256), 0, s, src, tgt, eig, labels, offsets, T_out, total_rows, max_n);
-  return hipGetLastError();
+  return launch_sm_pose(src, tgt, eig, labels, offsets, B, total_rows, max_n, T_out, s);
 }
 
 }  // namespace gmf

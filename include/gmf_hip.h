@@ -44,7 +44,7 @@ enum {
 
 #define GMF_ABI_VERSION 5   /* 5: gmf_encoder_weights gained `pv_guard` (a caller that fills the struct itself must be rebuilt; one that uses
                              * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  gmf_icp_point_to_point_ex and
-                             * gmf_ransac_feature_matching, then gmf_spectral_matching joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
+                             * gmf_ransac_feature_matching, then gmf_spectral_matching, then gmf_max_clique and gmf_pmc_graph joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
                              * pose head / pick_seeds take any N */
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
@@ -164,7 +164,10 @@ int gmf_set_sigma_device(gmf_handle* h, const float* sigma_dev);
  *   "q_in_attention"    : [ABI 4] 1 = on large grids every attention workgroup projects its own Q' in its prologue (default; PointDSC.py:56),
  *                         0 = the linear kernel writes a Q' image.  Bit-identical results.
  *   "spectral_col_splits": gmf_spectral_matching: 0 = the columns of a pair's sweep are split over workgroups by a rule of its own
- *                         N (default), 1..32 = that many splits at most (another order of a row's partial sums). */
+ *                         N (default), 1..32 = that many splits at most (another order of a row's partial sums).
+ *   "clique_local_rows" : gmf_max_clique: a root of the search with at most this many candidates is searched in LDS with
+ *                         one candidate set per level; wider roots keep no sets and read the bit matrix.  0..384, default 384.
+ *                         Both have the same search tree and return the same clique. */
 int gmf_set_tuning(gmf_handle* h, const char* name, int value);
 /* [ABI 4] The current value of a knob, so that a caller that changes one for a single call can put back what it found
  * (the Python PointDSC module does this for its module-local numerics mode).  Both calls take the handle's lock. */
@@ -645,6 +648,33 @@ int gmf_posegraph_optimize(gmf_handle* h, double* poses, const int* node_offsets
 int gmf_spectral_matching(gmf_handle* h, const float* corr, const float* src, const float* tgt, const int* offsets, int B, int max_n,
                           float inlier_threshold, const int* topk, int iterations, float* eig_out, float* labels_out, float* T_out,
                           gmf_stream_t stream);
+
+/* The maximum-clique baseline PMC(corr, src_keypts, tgt_keypts, args) of the reference's evaluation
+ * (GMF_PointDSC/baseline_scripts/baseline_3DMatch.py:56-77) over B ragged pairs, exact [joined under ABI 5: added entry points]:
+ * corr [total_rows,6], src / tgt [total_rows,3] (float32), offsets [B+1] (device int32; a pair may be empty).  Per pair of N rows:
+ *   graph   in fp32, every operation rounded on its own: a = ((dx^2 + dy^2) + dz^2) on the differences of columns 0..2, b alike
+ *           on columns 3..5; metric 0: edge iff |a - b| < inlier_threshold (the reference's rule: squared lengths); metric 1:
+ *           edge iff |sqrt(a) - sqrt(b)| < inlier_threshold (correctly rounded roots).  No diagonal.
+ *   clique  a maximum clique of that graph: a pure function of the pair's rows whenever exact_out is 1 - the same alone, in any
+ *           batch and on every run.  A graph without edges gives the smallest row alone.
+ *   pose    rigid_transform_3d(src, tgt, labels) (GMF_PointDSC/models/common.py:10-50) with 0 / 1 weights: centroids over
+ *           sum w + 1e-6, the fp64 Kabsch of gmf_spectral_matching.  An empty pair gives the identity.
+ * max_steps (>= 1) bounds the branch-and-bound nodes expanded per pair; the count can pass it by 256 at most (one per search
+ * wave).  Where it ends a search exact_out is 0 and the labels are the largest clique found.  max_n: an upper bound of the largest
+ * pair's rows, at most 8192 (GMF_ERR_UNSUPPORTED_SHAPE above); total_rows: the rows of corr.  They size the grid and the
+ * workspace (2 total_rows ceil(max_n / 64) words of bit rows and 512 B max_n bytes of clique lists).  A pair with more than
+ * max_n rows, or whose rows end past total_rows, is not computed: identity, zeros, size 0, exact 0.  B <= 65535.
+ * Out: labels_out [total_rows] (float 0 / 1), T_out [B,16], size_out [B], exact_out [B], steps_out [B], degree_out [total_rows]
+ * (the graph's row sums).  7 launches, no host synchronisation; graph-capturable. */
+int gmf_max_clique(gmf_handle* h, const float* corr, const float* src, const float* tgt, const int* offsets, int B,
+                   long long total_rows, int max_n, float inlier_threshold, int metric, long long max_steps, float* labels_out,
+                   float* T_out, int* size_out, int* exact_out, long long* steps_out, int* degree_out, gmf_stream_t stream);
+
+/* The graph of gmf_max_clique alone: bits_out [total_rows, ceil(max_n / 64)] 64-bit words, bit j % 64 of word j / 64 of row
+ * offsets[b] + i = edge (i, j) of pair b; bits past a pair's last column are zero, words past its last word are not written.
+ * degree_out [total_rows].  One launch. */
+int gmf_pmc_graph(gmf_handle* h, const float* corr, const int* offsets, int B, long long total_rows, int max_n,
+                  float inlier_threshold, int metric, unsigned long long* bits_out, int* degree_out, gmf_stream_t stream);
 
 /* ---- point-cloud descriptors: radius kNN, normals, FPFH, voxel grids (open3d's, as the reference's feature scripts call them) -- */
 
