@@ -222,6 +222,11 @@ SIGNATURES = {
     "gmf_spectral_matching": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_float, _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "gmf_max_clique": (C.c_int, [_vp] * 5 + [C.c_int, _ll, C.c_int, C.c_float, C.c_int, _ll] + [_vp] * 7),
     "gmf_pmc_graph": (C.c_int, [_vp, _vp, _vp, C.c_int, _ll, C.c_int, C.c_float, C.c_int, _vp, _vp, _vp]),
+    "gmf_tsdf_allocate": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp] + [C.c_int] * 4 + [C.c_double] * 8 + [C.c_int, C.c_int, _vp, _vp, _vp,
+                                    C.POINTER(_ll), _vp]),
+    "gmf_tsdf_integrate": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp] + [C.c_int] * 4 + [C.c_double] * 8 + [_vp, _vp, _vp, C.c_int, _vp, _vp,
+                                     _vp]),
+    "gmf_tsdf_extract": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, C.c_double, _vp, _ll, _vp, C.POINTER(_ll), _vp]),
     "gmf_radius_knn": (C.c_int, [_vp, _vp, _vp, C.c_int, _ll, C.c_double, C.c_int, _vp, _vp, _vp, _vp]),
     "gmf_estimate_normals": (C.c_int, [_vp, _vp, _vp, C.c_int, _ll, C.c_double, C.c_int, _vp, _vp]),
     "gmf_compute_fpfh": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _ll, C.c_double, C.c_int, _vp, _vp]),

@@ -24,6 +24,7 @@
 #include "launchers_correspondence.hpp"
 #include "launchers_posegraph.hpp"
 #include "launchers_clique.hpp"
+#include "launchers_tsdf.hpp"
 
 namespace {
 
@@ -52,6 +53,26 @@ int check_pmc_args(gmf_handle* h, const char* what, const void* corr, const int*
               w + ": inlier_threshold must be finite and > 0");
   GMF_REQUIRE(metric == gmf::kPmcSquared || metric == gmf::kPmcLength, GMF_ERR_BAD_ARG,
               w + ": metric must be 0 (squared lengths) or 1 (lengths)");
+  return GMF_OK;
+}
+
+// the checks gmf_tsdf_allocate and gmf_tsdf_integrate share; fills `p`
+int check_tsdf_args(gmf_handle* h, const char* what, const void* depth, const double* poses, const int* frame_offsets, int G, int F,
+                    int H, int W, double fx, double fy, double cx, double cy, double voxel_length, double sdf_trunc,
+                    double depth_scale, double depth_trunc, gmf::TsdfParams& p) {
+  const std::string w(what);
+  GMF_REQUIRE(h && frame_offsets, GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(G >= 1 && G <= gmf::kTsdfMaxFragments, GMF_ERR_UNSUPPORTED_SHAPE, w + ": G must be in 1..65535");
+  GMF_REQUIRE(F >= 0 && H >= 1 && W >= 1 && (long long)F * H * W < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              w + ": F must be >= 0, H and W >= 1 and F H W below 2^31");
+  GMF_REQUIRE(F == 0 || (depth && poses), GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(fx > 0 && fy > 0 && std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy), GMF_ERR_BAD_ARG,
+              w + ": the intrinsics must be finite, fx and fy > 0");
+  GMF_REQUIRE(voxel_length > 0 && std::isfinite(voxel_length) && sdf_trunc > 0 && std::isfinite(sdf_trunc), GMF_ERR_BAD_ARG,
+              w + ": voxel_length and sdf_trunc must be finite and > 0");
+  GMF_REQUIRE(depth_scale > 0 && std::isfinite(depth_scale) && depth_trunc > 0 && !std::isnan(depth_trunc), GMF_ERR_BAD_ARG,
+              w + ": depth_scale must be finite and > 0, depth_trunc > 0");
+  p = gmf::TsdfParams{G, F, H, W, fx, fy, cx, cy, voxel_length, sdf_trunc, (float)depth_scale, (float)depth_trunc};
   return GMF_OK;
 }
 
@@ -1663,6 +1684,82 @@ int gmf_max_clique(gmf_handle* h, const float* corr, const float* src, const flo
   if (int rc = arena_carve(h, bufs)) return rc;
   GMF_HIP(gmf::launch_max_clique(corr, src, tgt, offsets, B, total_rows, max_n, inlier_threshold, metric, max_steps,
                                  h->tune.clique_local_rows, ws, labels_out, T_out, size_out, exact_out, steps_out, degree_out, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_tsdf_allocate(gmf_handle* h, const void* depth, int depth_is_u16, const double* poses, const int* frame_offsets, int G, int F,
+                      int H, int W, double fx, double fy, double cx, double cy, double voxel_length, double sdf_trunc,
+                      double depth_scale, double depth_trunc, int stride, int max_units, int* unit_keys_out, int* birth_out,
+                      int* unit_offsets_out, long long* num_units, gmf_stream_t stream) {
+  gmf::TsdfParams p;
+  if (int rc = check_tsdf_args(h, "tsdf_allocate", depth, poses, frame_offsets, G, F, H, W, fx, fy, cx, cy, voxel_length, sdf_trunc,
+                               depth_scale, depth_trunc, p))
+    return rc;
+  GMF_REQUIRE(unit_keys_out && birth_out && unit_offsets_out && num_units, GMF_ERR_BAD_ARG, "tsdf_allocate: null pointer");
+  GMF_REQUIRE(stride >= 1, GMF_ERR_BAD_ARG, "tsdf_allocate: stride must be >= 1");
+  GMF_REQUIRE(max_units >= 1 && max_units <= (1 << 22), GMF_ERR_BAD_ARG, "tsdf_allocate: max_units must be in 1..2^22");
+  SetDevice sd(h, stream);
+  gmf::TsdfAllocScratch ws;
+  ArenaList bufs;
+  gmf::tsdf_alloc_scratch_list(G, max_units, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  int host2[2] = {0, 0};
+  GMF_HIP(gmf::launch_tsdf_allocate(depth, depth_is_u16 != 0, poses, frame_offsets, p, stride, max_units, ws, unit_keys_out, birth_out,
+                                    unit_offsets_out, host2, S(stream)));
+  GMF_REQUIRE(!(host2[1] & gmf::kTsdfRange), GMF_ERR_UNSUPPORTED_SHAPE,
+              "tsdf_allocate: a unit index lies outside +-32767 (or a pose is not finite): raise voxel_length");
+  GMF_REQUIRE(!(host2[1] & gmf::kTsdfOverflow) && host2[0] <= max_units, GMF_ERR_UNSUPPORTED_SHAPE,
+              "tsdf_allocate: the frames touch more than max_units = " + std::to_string(max_units) + " volume units: raise max_units");
+  *num_units = host2[0];
+  return GMF_OK;
+}
+
+int gmf_tsdf_integrate(gmf_handle* h, const void* depth, int depth_is_u16, const double* poses_inv, const int* frame_offsets, int G,
+                       int F, int H, int W, double fx, double fy, double cx, double cy, double voxel_length, double sdf_trunc,
+                       double depth_scale, double depth_trunc, const int* unit_keys, const int* unit_offsets, const int* birth,
+                       int num_units, float* tsdf_out, float* weight_out, gmf_stream_t stream) {
+  gmf::TsdfParams p;
+  if (int rc = check_tsdf_args(h, "tsdf_integrate", depth, poses_inv, frame_offsets, G, F, H, W, fx, fy, cx, cy, voxel_length,
+                               sdf_trunc, depth_scale, depth_trunc, p))
+    return rc;
+  GMF_REQUIRE(num_units >= 0 && num_units <= (1 << 22), GMF_ERR_BAD_ARG, "tsdf_integrate: num_units must be in 0..2^22");
+  if (num_units == 0) return GMF_OK;
+  GMF_REQUIRE(F >= 1 && unit_keys && unit_offsets && birth && tsdf_out && weight_out, GMF_ERR_BAD_ARG,
+              "tsdf_integrate: null pointer, or units without frames");
+  SetDevice sd(h, stream);
+  gmf::TsdfIntegrateScratch ws;
+  ArenaList bufs;
+  gmf::tsdf_integrate_scratch_list(p, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  GMF_HIP(gmf::launch_tsdf_integrate(depth, depth_is_u16 != 0, poses_inv, frame_offsets, p, unit_keys, unit_offsets, birth, num_units,
+                                     ws, tsdf_out, weight_out, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_tsdf_extract(gmf_handle* h, const int* unit_keys, const int* unit_offsets, int G, int num_units, const float* tsdf,
+                     const float* weight, double voxel_length, float* points_out, long long max_points, int* point_offsets_out,
+                     long long* num_points, gmf_stream_t stream) {
+  GMF_REQUIRE(h && unit_offsets && point_offsets_out, GMF_ERR_BAD_ARG, "tsdf_extract: null pointer");
+  GMF_REQUIRE(points_out || num_points, GMF_ERR_BAD_ARG, "tsdf_extract: without points_out the call counts into num_points");
+  GMF_REQUIRE(G >= 1 && G <= gmf::kTsdfMaxFragments, GMF_ERR_UNSUPPORTED_SHAPE, "tsdf_extract: G must be in 1..65535");
+  GMF_REQUIRE(num_units >= 0 && num_units <= (1 << 22), GMF_ERR_BAD_ARG, "tsdf_extract: num_units must be in 0..2^22");
+  GMF_REQUIRE(num_units == 0 || (unit_keys && tsdf && weight), GMF_ERR_BAD_ARG, "tsdf_extract: null pointer");
+  GMF_REQUIRE(voxel_length > 0 && std::isfinite(voxel_length), GMF_ERR_BAD_ARG, "tsdf_extract: voxel_length must be finite and > 0");
+  GMF_REQUIRE(max_points >= 0, GMF_ERR_BAD_ARG, "tsdf_extract: max_points must be >= 0");
+  SetDevice sd(h, stream);
+  if (num_units == 0) {
+    GMF_HIP(hipMemsetAsync(point_offsets_out, 0, ((size_t)G + 1) * 4, S(stream)));
+    if (!points_out) *num_points = 0;
+    return GMF_OK;
+  }
+  gmf::TsdfExtractScratch ws;
+  ArenaList bufs;
+  gmf::tsdf_extract_scratch_list(num_units, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  int host_count = 0;
+  GMF_HIP(gmf::launch_tsdf_extract(unit_keys, unit_offsets, G, num_units, tsdf, weight, voxel_length, ws, points_out, max_points,
+                                   point_offsets_out, &host_count, S(stream)));
+  if (!points_out) *num_points = host_count;
   return GMF_OK;
 }
 

@@ -1,0 +1,161 @@
+"""Fragments on the device: TSDF fusion of posed depth frames to a cloud, as the reference makes them
+(GMF_PointDSC/multiway/make_fragments.py:112-140 and GMF_DeepGlobalRegistration/*/util/integration.py:44-71: open3d's
+ScalableTSDFVolume, integrate() per frame, extract_triangle_mesh(), of which make_fragments.py keeps the vertices).  Kernels:
+csrc/tsdf_kernels.hip; C ABI: gmf_tsdf_allocate, gmf_tsdf_integrate, gmf_tsdf_extract.
+
+The contract is DESIGN.md section 4o, restated in numpy by tests/tsdf_reference.py; where it knowingly differs from open3d is
+listed there.  Colours, triangles, normals, extract_point_cloud, file reading and RGB-D odometry are not here."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ._util import handle_and_stream
+from .registration import _device_offsets
+from .spectral import _fail
+
+MAX_FRAMES = 65535            # frames of one fragment, at most
+MAX_FRAGMENTS = 65535         # fragments of one call, at most (kTsdfMaxFragments)
+MAX_UNITS = 1 << 22           # the largest max_units the library takes
+
+
+def _positive(what, name, v, allow_inf=False):
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        _fail(what, f"{name} must be a number (got {v!r})")
+    if not f > 0 or (not allow_inf and not np.isfinite(f)):
+        _fail(what, f"{name} must be {'' if allow_inf else 'finite and '}> 0 (got {v})")
+    return f
+
+
+def _nothing(points_off, return_volume):
+    """The result of a call whose frames touch no unit."""
+    dev = points_off.device
+    pts = torch.zeros((0, 3), device=dev, dtype=torch.float32)
+    if not return_volume:
+        return pts, points_off
+    return (pts, points_off, torch.zeros((0, 3), device=dev, dtype=torch.int32), torch.zeros_like(points_off),
+            torch.zeros(0, device=dev, dtype=torch.int32), torch.zeros((0, 16, 16, 16), device=dev),
+            torch.zeros((0, 16, 16, 16), device=dev))
+
+
+def tsdf_fragments(depth, poses, intrinsic, frame_offsets=None, voxel_length=0.008, sdf_trunc=0.04, depth_scale=1000.0,
+                   depth_trunc=4.5, depth_sampling_stride=4, max_units=1 << 18, return_volume=False):
+    """G fragments from posed depth frames: per fragment a ScalableTSDFVolume(voxel_length, sdf_trunc) with 16^3-voxel units, every
+    frame integrated in order, and the vertices of the marching-cubes mesh.
+
+    depth [F,H,W] on the device: uint16 (sensor values, d = v / depth_scale) or float32 (metres; negative and non-finite are 0);
+    d >= depth_trunc is 0, and 0 is no measurement.  poses [F,4,4] float64 camera-to-world, on the host (a device tensor is
+    copied to the host first, which synchronises); they are inverted in fp64 on the host.  intrinsic (fx, fy, cx, cy): one camera
+    per call.  frame_offsets: G + 1 ints, fragment g owns frames frame_offsets[g] .. frame_offsets[g+1] - 1 (possibly none);
+    None: one fragment.  At most 65535 frames per fragment and 65535 fragments.
+      allocation: every depth_sampling_stride-th pixel of every such row is back-projected (fp64) and the units within sdf_trunc
+      of it exist; a unit's birth is the first frame of its fragment that touches it; units are listed per fragment in ascending
+      (x, y, z) order;
+      integration: a unit takes the frames from its birth on (open3d creates a unit when a frame first touches it), fp32,
+      weight 1 per update;
+      extraction: one vertex per sign-changing edge between observed voxels that lies in a fully observed 2x2x2 cube, ordered
+      by fragment, unit, voxel, axis.
+    Returns points [M,3] float32 and point_offsets [G+1] int32 (device); with return_volume also unit_keys [U,3] int32,
+    unit_offsets [G+1] int32, birth [U] int32, tsdf [U,16,16,16] and weight [U,16,16,16] float32.
+    A function of the inputs alone: the same bits on every run, and a fragment has the same bits alone and in any batch.
+    Two host synchronisations per call (the unit count, the vertex count).  Raises when the frames touch more than max_units
+    units (raise max_units) or a unit index leaves +-32767 (raise voxel_length)."""
+    what = "tsdf_fragments"
+    if not isinstance(depth, torch.Tensor):
+        _fail(what, "`depth` must be a torch tensor")
+    if depth.dtype not in (torch.uint16, torch.float32):
+        _fail(what, f"`depth` must be uint16 (sensor values) or float32 (metres) (got {depth.dtype})")
+    if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
+        _fail(what, f"`depth` must be a [F,H,W] tensor (got {tuple(depth.shape)})")
+    F, H, W = depth.shape
+    if F * H * W >= 2 ** 31:
+        _fail(what, f"`depth` must hold fewer than 2^31 pixels (got {F * H * W})")
+    if not isinstance(poses, torch.Tensor):
+        _fail(what, "`poses` must be a torch tensor")
+    if poses.dtype != torch.float64:
+        _fail(what, f"`poses` must be float64 (got {poses.dtype})")
+    if poses.dim() != 3 or tuple(poses.shape) != (F, 4, 4):
+        _fail(what, f"`poses` must be [F,4,4] with depth's F = {F} (got {tuple(poses.shape)})")
+    try:
+        fx, fy, cx, cy = (float(v) for v in intrinsic)
+    except (TypeError, ValueError):
+        _fail(what, f"intrinsic must be four numbers (fx, fy, cx, cy) (got {intrinsic!r})")
+    if not (np.isfinite([fx, fy, cx, cy]).all() and fx > 0 and fy > 0):
+        _fail(what, f"intrinsic must be finite with fx, fy > 0 (got {intrinsic!r})")
+    if frame_offsets is None:
+        off = [0, F]
+    else:
+        if isinstance(frame_offsets, torch.Tensor) and frame_offsets.is_cuda:
+            _fail(what, "frame_offsets must be G + 1 host integers (they size the call)")
+        try:
+            seq = frame_offsets.tolist() if isinstance(frame_offsets, (torch.Tensor, np.ndarray)) else list(frame_offsets)
+            off = [int(o) for o in seq]
+            if any(o != s for o, s in zip(off, seq)):
+                raise ValueError
+        except (TypeError, ValueError):
+            _fail(what, "frame_offsets must be G + 1 integers")
+        if len(off) < 2 or off[0] != 0 or off[-1] != F or any(b < a for a, b in zip(off, off[1:])):
+            _fail(what, "frame_offsets must not decrease, start at 0 and end at F")
+    G = len(off) - 1
+    if G > MAX_FRAGMENTS:
+        _fail(what, f"a call holds at most {MAX_FRAGMENTS} fragments (got {G})")
+    if max(b - a for a, b in zip(off, off[1:])) > MAX_FRAMES:
+        _fail(what, f"a fragment holds at most {MAX_FRAMES} frames (got {max(b - a for a, b in zip(off, off[1:]))})")
+    vl = _positive(what, "voxel_length", voxel_length)
+    trunc = _positive(what, "sdf_trunc", sdf_trunc)
+    scale = _positive(what, "depth_scale", depth_scale)
+    far = _positive(what, "depth_trunc", depth_trunc, allow_inf=True)
+    stride = int(depth_sampling_stride) if isinstance(depth_sampling_stride, (int, np.integer)) else 0
+    if stride < 1:
+        _fail(what, f"depth_sampling_stride must be an integer >= 1 (got {depth_sampling_stride!r})")
+    units_cap = int(max_units) if isinstance(max_units, (int, np.integer)) else 0
+    if not 1 <= units_cap <= MAX_UNITS:
+        _fail(what, f"max_units must be an integer in 1..{MAX_UNITS} (got {max_units!r})")
+    P = np.ascontiguousarray(poses.detach().cpu().numpy())
+    if not np.isfinite(P).all():
+        _fail(what, "`poses` must be finite")
+    try:
+        Pinv = np.linalg.inv(P)
+    except np.linalg.LinAlgError:
+        _fail(what, "`poses` must be invertible")
+    if not depth.is_cuda:
+        _fail(what, f"`depth` must live on a HIP device (got {depth.device}); the HIP path is mandatory, there is no CPU fallback")
+    dev = depth.device
+
+    points_off = torch.zeros(G + 1, device=dev, dtype=torch.int32)
+    if F == 0:
+        return _nothing(points_off, return_volume)
+
+    D = depth.contiguous()
+    u16 = 1 if depth.dtype == torch.uint16 else 0
+    both = torch.from_numpy(np.stack([P, Pinv])).pin_memory().to(dev, non_blocking=True)      # [2,F,4,4] fp64, no synchronisation
+    dev_off, _ = _device_offsets(off, F, dev, what, allow_empty=True)
+    h, st = handle_and_stream(D)
+    shared = (D.data_ptr(), u16)
+    camera = (G, F, H, W, fx, fy, cx, cy, vl, trunc, scale, far)
+
+    keys = torch.empty((units_cap, 3), device=dev, dtype=torch.int32)
+    birth = torch.empty(units_cap, device=dev, dtype=torch.int32)
+    unit_off = torch.empty(G + 1, device=dev, dtype=torch.int32)
+    n = C.c_longlong(0)
+    h.call("gmf_tsdf_allocate", *shared, both[0].data_ptr(), dev_off.data_ptr(), *camera, stride, units_cap, keys.data_ptr(),
+           birth.data_ptr(), unit_off.data_ptr(), C.byref(n), st)
+    U = int(n.value)
+    keys, birth = keys[:U].clone(), birth[:U].clone()
+    if U == 0:
+        return _nothing(points_off, return_volume)
+    tsdf = torch.empty((U, 16, 16, 16), device=dev, dtype=torch.float32)
+    weight = torch.empty((U, 16, 16, 16), device=dev, dtype=torch.float32)
+    h.call("gmf_tsdf_integrate", *shared, both[1].data_ptr(), dev_off.data_ptr(), *camera, keys.data_ptr(), unit_off.data_ptr(),
+           birth.data_ptr(), U, tsdf.data_ptr(), weight.data_ptr(), st)
+    volume = (keys.data_ptr(), unit_off.data_ptr(), G, U, tsdf.data_ptr(), weight.data_ptr(), vl)
+    h.call("gmf_tsdf_extract", *volume, None, 0, points_off.data_ptr(), C.byref(n), st)
+    M = int(n.value)
+    pts = torch.empty((M, 3), device=dev, dtype=torch.float32)
+    if M:
+        h.call("gmf_tsdf_extract", *volume, pts.data_ptr(), M, points_off.data_ptr(), None, st)
+    return (pts, points_off) + ((keys, unit_off, birth, tsdf, weight) if return_volume else ())

@@ -44,7 +44,7 @@ enum {
 
 #define GMF_ABI_VERSION 5   /* 5: gmf_encoder_weights gained `pv_guard` (a caller that fills the struct itself must be rebuilt; one that uses
                              * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  gmf_icp_point_to_point_ex and
-                             * gmf_ransac_feature_matching, then gmf_spectral_matching, then gmf_max_clique and gmf_pmc_graph joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
+                             * gmf_ransac_feature_matching, then gmf_spectral_matching, then gmf_max_clique and gmf_pmc_graph, then gmf_tsdf_allocate, gmf_tsdf_integrate and gmf_tsdf_extract joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
                              * pose head / pick_seeds take any N */
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
@@ -675,6 +675,50 @@ int gmf_max_clique(gmf_handle* h, const float* corr, const float* src, const flo
  * degree_out [total_rows].  One launch. */
 int gmf_pmc_graph(gmf_handle* h, const float* corr, const int* offsets, int B, long long total_rows, int max_n,
                   float inlier_threshold, int metric, unsigned long long* bits_out, int* degree_out, gmf_stream_t stream);
+
+/* ---- fragments from depth frames: TSDF fusion (open3d's ScalableTSDFVolume, as the reference's make_fragments.py drives it) ---- */
+
+/* G ragged fragments of posed depth frames -> the vertices of each fragment's marching-cubes mesh, in three calls [joined under
+ * ABI 5: added entry points].  The arithmetic, step by step, is DESIGN.md section 4o (tests/tsdf_reference.py restates it and the
+ * kernels equal it bit for bit); a volume unit is 16^3 voxels, unit_length = 16 voxel_length.
+ *
+ * Shared inputs: depth [F,H,W] on the device, uint16 sensor values (depth_is_u16 != 0: d = float(v) / float(depth_scale)) or
+ * float32 metres (a negative or non-finite value is 0); d >= float(depth_trunc) is 0; 0 is "no measurement".  frame_offsets [G+1]
+ * (device int32, not decreasing, from 0 to F: fragment g owns frames frame_offsets[g] .. frame_offsets[g+1] - 1, possibly none).
+ * One pinhole camera (fx, fy, cx, cy) per call.  G <= 65535, F H W < 2^31.
+ *
+ * gmf_tsdf_allocate: poses [F,16] camera-to-world, fp64 row-major, on the device.  Every stride-th pixel of every stride-th row
+ * with d > 0 is back-projected in fp64 and every unit of the box floor((p -+ sdf_trunc) / unit_length) exists.  Out (device):
+ * unit_keys_out [max_units,3] int32 and birth_out [max_units] int32, of which the first *num_units rows are written - the units of
+ * fragment 0 in ascending (x, y, z) order, then fragment 1's, ...; birth = the first frame (counted within the fragment) that
+ * touches the unit; unit_offsets_out [G+1] int32.  *num_units (host).  Synchronises the stream once.  GMF_ERR_UNSUPPORTED_SHAPE
+ * when the frames touch more than max_units (1..2^22) units, or a unit index leaves +-32767; the outputs are then not valid.
+ * Workspace: 12 bytes per table slot (a power of two >= 2 max_units, at least 1024), 16 per max_units and the radix sort's. */
+int gmf_tsdf_allocate(gmf_handle* h, const void* depth, int depth_is_u16, const double* poses, const int* frame_offsets, int G, int F,
+                      int H, int W, double fx, double fy, double cx, double cy, double voxel_length, double sdf_trunc,
+                      double depth_scale, double depth_trunc, int stride, int max_units, int* unit_keys_out, int* birth_out,
+                      int* unit_offsets_out, long long* num_units, gmf_stream_t stream);
+
+/* gmf_tsdf_integrate: poses_inv [F,16] world-to-camera, fp64 (the caller inverts; the kernel rounds them to float32).  unit_keys
+ * [num_units,3], unit_offsets [G+1], birth [num_units] as gmf_tsdf_allocate wrote them.  Every unit takes the frames >= its birth
+ * of its fragment, in order: projective update with weight 1, tsdf = (tsdf w + min(1, sdf / sdf_trunc)) / (w + 1), in fp32.
+ * Out: tsdf_out, weight_out [num_units,16,16,16] float32, voxel (x, y, z) of a unit at x 256 + y 16 + z; every voxel is written
+ * (0 / 0 where no frame reached it).  Workspace: 4 (F + 1) H W bytes.  2 launches, no host synchronisation. */
+int gmf_tsdf_integrate(gmf_handle* h, const void* depth, int depth_is_u16, const double* poses_inv, const int* frame_offsets, int G,
+                       int F, int H, int W, double fx, double fy, double cx, double cy, double voxel_length, double sdf_trunc,
+                       double depth_scale, double depth_trunc, const int* unit_keys, const int* unit_offsets, const int* birth,
+                       int num_units, float* tsdf_out, float* weight_out, gmf_stream_t stream);
+
+/* gmf_tsdf_extract: the vertex set of the marching-cubes mesh of the volume.  An edge between two voxels adjacent along an axis
+ * yields a vertex when both have weight > 0, their tsdf differ in sign (< 0 against >= 0) and one of the four 2x2x2 cubes around
+ * the edge has eight voxels of weight > 0 (neighbouring units of the same fragment included); it lies on the edge at
+ * |tsdf_a| / (|tsdf_a| + |tsdf_b|), computed in fp64.  Order: fragment, unit, voxel index, axis.
+ * points_out NULL: counts - point_offsets_out [G+1] (device int32) is written and *num_points (host) after synchronising the
+ * stream once.  points_out [max_points,3] float32: the vertices are written as well (any past max_points are dropped: give what
+ * the counting call reported), nothing is read back and num_points is not touched.  Fewer than 2^31 vertices per call. */
+int gmf_tsdf_extract(gmf_handle* h, const int* unit_keys, const int* unit_offsets, int G, int num_units, const float* tsdf,
+                     const float* weight, double voxel_length, float* points_out, long long max_points, int* point_offsets_out,
+                     long long* num_points, gmf_stream_t stream);
 
 /* ---- point-cloud descriptors: radius kNN, normals, FPFH, voxel grids (open3d's, as the reference's feature scripts call them) -- */
 
