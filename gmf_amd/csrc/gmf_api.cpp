@@ -25,6 +25,7 @@
 #include "launchers_posegraph.hpp"
 #include "launchers_clique.hpp"
 #include "launchers_tsdf.hpp"
+#include "launchers_rgbd.hpp"
 
 namespace {
 
@@ -73,6 +74,30 @@ int check_tsdf_args(gmf_handle* h, const char* what, const void* depth, const do
   GMF_REQUIRE(depth_scale > 0 && std::isfinite(depth_scale) && depth_trunc > 0 && !std::isnan(depth_trunc), GMF_ERR_BAD_ARG,
               w + ": depth_scale must be finite and > 0, depth_trunc > 0");
   p = gmf::TsdfParams{G, F, H, W, fx, fy, cx, cy, voxel_length, sdf_trunc, (float)depth_scale, (float)depth_trunc};
+  return GMF_OK;
+}
+
+// the checks the gmf_rgbd_* entries share; fills `s`
+int check_rgbd_shape(gmf_handle* h, const char* what, int F, int H, int W, int levels, gmf::RgbdShape& s) {
+  const std::string w(what);
+  GMF_REQUIRE(h, GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(F >= 1 && H >= 1 && W >= 1 && (long long)F * H * W < (1LL << 31) / gmf::kRgbdPlanes, GMF_ERR_UNSUPPORTED_SHAPE,
+              w + ": F, H and W must be >= 1 and 6 F H W below 2^31");
+  GMF_REQUIRE(levels >= 1 && levels <= gmf::kRgbdMaxLevels && (H >> (levels - 1)) >= 1 && (W >> (levels - 1)) >= 1,
+              GMF_ERR_UNSUPPORTED_SHAPE, w + ": levels must be in 1..8 and leave the coarsest level a pixel");
+  s = gmf::RgbdShape{F, H, W, levels};
+  return GMF_OK;
+}
+
+// the checks gmf_rgbd_correspondences and gmf_rgbd_odometry share
+int check_rgbd_pairs(gmf_handle* h, const char* what, const float* planes, const int* pair_source, const int* pair_target, int E,
+                     double fx, double fy, double cx, double cy, double max_depth_diff) {
+  const std::string w(what);
+  GMF_REQUIRE(planes && pair_source && pair_target, GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(E >= 1 && E < (1 << 24), GMF_ERR_UNSUPPORTED_SHAPE, w + ": E must be in 1..2^24-1");
+  GMF_REQUIRE(fx > 0 && fy > 0 && std::isfinite(fx) && std::isfinite(fy) && std::isfinite(cx) && std::isfinite(cy), GMF_ERR_BAD_ARG,
+              w + ": the intrinsics must be finite, fx and fy > 0");
+  GMF_REQUIRE(max_depth_diff >= 0 && std::isfinite(max_depth_diff), GMF_ERR_BAD_ARG, w + ": max_depth_diff must be finite and >= 0");
   return GMF_OK;
 }
 
@@ -1760,6 +1785,68 @@ int gmf_tsdf_extract(gmf_handle* h, const int* unit_keys, const int* unit_offset
   GMF_HIP(gmf::launch_tsdf_extract(unit_keys, unit_offsets, G, num_units, tsdf, weight, voxel_length, ws, points_out, max_points,
                                    point_offsets_out, &host_count, S(stream)));
   if (!points_out) *num_points = host_count;
+  return GMF_OK;
+}
+
+int gmf_rgbd_pyramids(gmf_handle* h, const void* color, int color_kind, const void* depth, int depth_is_u16, int F, int H, int W,
+                      double depth_scale, double depth_trunc, double min_depth, double max_depth, int levels, float* planes_out,
+                      gmf_stream_t stream) {
+  gmf::RgbdShape s;
+  if (int rc = check_rgbd_shape(h, "rgbd_pyramids", F, H, W, levels, s)) return rc;
+  GMF_REQUIRE(color && depth && planes_out, GMF_ERR_BAD_ARG, "rgbd_pyramids: null pointer");
+  GMF_REQUIRE(color_kind >= gmf::kRgbdGray8 && color_kind <= gmf::kRgbdFloat, GMF_ERR_BAD_ARG,
+              "rgbd_pyramids: color_kind must be 0 (uint8), 1 (uint8 RGB) or 2 (float32)");
+  GMF_REQUIRE(depth_scale > 0 && std::isfinite(depth_scale) && depth_trunc > 0 && !std::isnan(depth_trunc), GMF_ERR_BAD_ARG,
+              "rgbd_pyramids: depth_scale must be finite and > 0, depth_trunc > 0");
+  GMF_REQUIRE(min_depth >= 0 && std::isfinite(min_depth) && max_depth > min_depth && !std::isnan(max_depth), GMF_ERR_BAD_ARG,
+              "rgbd_pyramids: min_depth must be finite and >= 0, max_depth above it");
+  SetDevice sd(h, stream);
+  gmf::RgbdPyramidScratch ws;
+  ArenaList bufs;
+  gmf::rgbd_pyramid_scratch_list(s, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  GMF_HIP(gmf::launch_rgbd_pyramids(color, color_kind, depth, depth_is_u16 != 0, s, (float)depth_scale, (float)depth_trunc,
+                                    (float)min_depth, (float)max_depth, ws, planes_out, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_rgbd_correspondences(gmf_handle* h, const float* planes, int F, int H, int W, int levels, int level, const int* pair_source,
+                             const int* pair_target, int E, const double* transformation, double fx, double fy, double cx, double cy,
+                             double max_depth_diff, int* map_out, gmf_stream_t stream) {
+  gmf::RgbdShape s;
+  if (int rc = check_rgbd_shape(h, "rgbd_correspondences", F, H, W, levels, s)) return rc;
+  if (int rc = check_rgbd_pairs(h, "rgbd_correspondences", planes, pair_source, pair_target, E, fx, fy, cx, cy, max_depth_diff)) return rc;
+  GMF_REQUIRE(transformation && map_out, GMF_ERR_BAD_ARG, "rgbd_correspondences: null pointer");
+  GMF_REQUIRE(level >= 0 && level < levels, GMF_ERR_BAD_ARG, "rgbd_correspondences: level must be in 0..levels-1");
+  SetDevice sd(h, stream);
+  gmf::RgbdOdometryScratch ws;
+  ArenaList bufs;
+  gmf::rgbd_odometry_scratch_list(s, E, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  GMF_HIP(gmf::launch_rgbd_correspondences(planes, s, level, pair_source, pair_target, E, transformation, gmf::RgbdCamera{fx, fy, cx, cy},
+                                           max_depth_diff, ws, map_out, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_rgbd_odometry(gmf_handle* h, const float* planes, int F, int H, int W, int levels, const int* pair_source, const int* pair_target,
+                      int E, const double* odo_init, double fx, double fy, double cx, double cy, double max_depth_diff,
+                      const int* iterations, unsigned char* success_out, double* transformation_out, double* information_out,
+                      double* scales_out, int* trace_n_out, double* trace_out, gmf_stream_t stream) {
+  gmf::RgbdShape s;
+  if (int rc = check_rgbd_shape(h, "rgbd_odometry", F, H, W, levels, s)) return rc;
+  if (int rc = check_rgbd_pairs(h, "rgbd_odometry", planes, pair_source, pair_target, E, fx, fy, cx, cy, max_depth_diff)) return rc;
+  GMF_REQUIRE(iterations && success_out && transformation_out && information_out, GMF_ERR_BAD_ARG, "rgbd_odometry: null pointer");
+  GMF_REQUIRE(!trace_n_out == !trace_out, GMF_ERR_BAD_ARG, "rgbd_odometry: trace_n_out and trace_out go together");
+  for (int l = 0; l < levels; ++l)
+    GMF_REQUIRE(iterations[l] >= 0 && iterations[l] <= 10000, GMF_ERR_BAD_ARG, "rgbd_odometry: iterations must be in 0..10000");
+  SetDevice sd(h, stream);
+  gmf::RgbdOdometryScratch ws;
+  ArenaList bufs;
+  gmf::rgbd_odometry_scratch_list(s, E, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  GMF_HIP(gmf::launch_rgbd_odometry(planes, s, pair_source, pair_target, E, odo_init, gmf::RgbdCamera{fx, fy, cx, cy}, max_depth_diff,
+                                    iterations, ws, success_out, transformation_out, information_out, scales_out, trace_n_out, trace_out,
+                                    S(stream)));
   return GMF_OK;
 }
 

@@ -4,7 +4,8 @@ ScalableTSDFVolume, integrate() per frame, extract_triangle_mesh(), of which mak
 csrc/tsdf_kernels.hip; C ABI: gmf_tsdf_allocate, gmf_tsdf_integrate, gmf_tsdf_extract.
 
 The contract is DESIGN.md section 4o, restated in numpy by tests/tsdf_reference.py; where it knowingly differs from open3d is
-listed there.  Colours, triangles, normals, extract_point_cloud, file reading and RGB-D odometry are not here."""
+listed there.  Colours, triangles, normals, extract_point_cloud and file reading are not here; the RGB-D odometry that gives the
+poses is gmf_amd/rgbd.py."""
 from __future__ import annotations
 
 import ctypes as C

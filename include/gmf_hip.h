@@ -44,7 +44,8 @@ enum {
 
 #define GMF_ABI_VERSION 5   /* 5: gmf_encoder_weights gained `pv_guard` (a caller that fills the struct itself must be rebuilt; one that uses
                              * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  gmf_icp_point_to_point_ex and
-                             * gmf_ransac_feature_matching, then gmf_spectral_matching, then gmf_max_clique and gmf_pmc_graph, then gmf_tsdf_allocate, gmf_tsdf_integrate and gmf_tsdf_extract joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
+                             * gmf_ransac_feature_matching, then gmf_spectral_matching, then gmf_max_clique and gmf_pmc_graph, then gmf_tsdf_allocate, gmf_tsdf_integrate and gmf_tsdf_extract, then gmf_rgbd_pyramids, gmf_rgbd_correspondences and
+                             * gmf_rgbd_odometry joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
                              * pose head / pick_seeds take any N */
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
@@ -719,6 +720,45 @@ int gmf_tsdf_integrate(gmf_handle* h, const void* depth, int depth_is_u16, const
 int gmf_tsdf_extract(gmf_handle* h, const int* unit_keys, const int* unit_offsets, int G, int num_units, const float* tsdf,
                      const float* weight, double voxel_length, float* points_out, long long max_points, int* point_offsets_out,
                      long long* num_points, gmf_stream_t stream);
+
+/* ---- RGB-D odometry (open3d 0.9's compute_rgbd_odometry with the hybrid Jacobian, as make_fragments.py calls it) -------------- */
+
+/* The contract is DESIGN.md section 4p.  The pyramid of F frames of H x W is ONE float32 buffer: level l (0 .. levels-1) is
+ * [F,6,h_l,w_l] with h_l = H >> l, w_l = W >> l and the planes I, D, Idx, Idy, Ddx, Ddy, and starts where level l-1 ends
+ * (6 F (h_0 w_0 + ... + h_l-1 w_l-1) floats in).  6 F H W must stay below 2^31; levels in 1..8.
+ *
+ * gmf_rgbd_pyramids: color [F,H,W] uint8 (color_kind 0: I = v / 255), [F,H,W,3] uint8 (1: I = ((0.2990 R + 0.5870 G) + 0.1140 B) / 255
+ * in float32) or [F,H,W] float32 (2: as it is); depth [F,H,W] uint16 (d = v / depth_scale) or float32 (metres; negative and
+ * non-finite are none); d >= depth_trunc, d < min_depth, d > max_depth and d <= 0 become NaN.  Level 0 is the 3 x 3 Gaussian of
+ * both, level l+1 the 2 x 2 mean of the Gaussian of I_l and of D_l, the gradients are 3 x 3 Sobel filters; every filter is two
+ * 3-tap passes (rows, then columns; indices clamped; fp64 accumulator, float32 result).  planes_out: every level.  No host
+ * synchronisation. */
+int gmf_rgbd_pyramids(gmf_handle* h, const void* color, int color_kind, const void* depth, int depth_is_u16, int F, int H, int W,
+                      double depth_scale, double depth_trunc, double min_depth, double max_depth, int levels, float* planes_out,
+                      gmf_stream_t stream);
+
+/* gmf_rgbd_correspondences: for E pairs (pair_source[e], pair_target[e]; device int32, frames of `planes`) and poses
+ * transformation [E,16] (fp64, source camera to target camera), at `level` with the intrinsics (fx, fy, cx, cy) * 2^-level: every
+ * source pixel with depth d_s goes to p = d_s (K R K^-1 (u, v, 1)) + K t, (u_t, v_t) = trunc(p_xy / p_z + 0.5), and is a candidate
+ * of that target pixel when it is inside, has depth d_t and |p_z - d_t| <= max_depth_diff; the candidate of smallest d_s, then of
+ * smallest source index, wins.  map_out [E,h,w] int32: the winning source pixel v_s w + u_s, or -1.  A pair that names a frame
+ * outside 0..F-1 gets -1 everywhere.  No host synchronisation. */
+int gmf_rgbd_correspondences(gmf_handle* h, const float* planes, int F, int H, int W, int levels, int level, const int* pair_source,
+                             const int* pair_target, int E, const double* transformation, double fx, double fy, double cx, double cy,
+                             double max_depth_diff, int* map_out, gmf_stream_t stream);
+
+/* gmf_rgbd_odometry: E pairs from odo_init [E,16] (fp64, its last row taken as 0 0 0 1; NULL: identity).  iterations [levels] (HOST ints): iterations[0] runs
+ * at the coarsest level.  Out (device): success_out [E] bytes (1 / 0), transformation_out [E,16] and information_out [E,36] fp64
+ * (both the identity for a failed pair).  Optional (NULL: not written): scales_out [E,2] (s_src, s_tgt; not written for a pair
+ * without level-0 correspondences), and, together, trace_n_out [E,N] int32 and trace_out [E,N,65] fp64 with N = sum of
+ * iterations, per iteration the count, then A (36), b (6), r2, x (6) and the pose after the update (16); an iteration that fails
+ * writes its count, A, b and r2 only, the iterations after a failure write nothing.  3 launches per iteration for all pairs; the
+ * sums are a function of the pair alone (no floating-point atomics, a block partition fixed by the level).  No host
+ * synchronisation. */
+int gmf_rgbd_odometry(gmf_handle* h, const float* planes, int F, int H, int W, int levels, const int* pair_source, const int* pair_target,
+                      int E, const double* odo_init, double fx, double fy, double cx, double cy, double max_depth_diff,
+                      const int* iterations, unsigned char* success_out, double* transformation_out, double* information_out,
+                      double* scales_out, int* trace_n_out, double* trace_out, gmf_stream_t stream);
 
 /* ---- point-cloud descriptors: radius kNN, normals, FPFH, voxel grids (open3d's, as the reference's feature scripts call them) -- */
 
