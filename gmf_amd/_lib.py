@@ -40,6 +40,7 @@ class EncoderWeights(C.Structure):
         ("f1_ctx_wst_h2", _vp), ("f1_attn_wst_h2", _vp), ("f1_ff_wst_h2", _vp),
         ("tail_wst_h2", _vp),
         ("pv_guard", _vp),
+        ("kv_fold", _vp),
     ]
 
 

@@ -721,7 +721,10 @@ constexpr int kLinLdsFloats = 4 * kStageFloats + 7 * C + (3 * C + 2 * FFH) + kWa
 
 // QSKIP [r4]: the Q' projection is left to the attention kernel's prologue (scattn_h2p_body, qf_img): 8 instead of 12 projection
 // stages, 32 instead of 48 KiB of stores per wave in the kernel's write-bound phase
-template <int PART, int NP = 3, bool QSKIP = false>
+// KVF ("kv_fold"; NP = 3): no K and V projections - the K and V images are the layer input f itself (key image: the
+// planes of f as loaded; value image: f transposed, 32 x 32 blocks through the ring slot the primed stages leave free), in the formats and
+// under the per-pair decision of the projected images; a Q' image (QSKIP = false) holds q~ = (Wk^T Wq') f + Wk^T bq' (kvf_wst, kvf_bias).
+template <int PART, int NP = 3, bool QSKIP = false, bool KVF = false>
 GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const float* __restrict__ front_wst,
                                const float* __restrict__ front_vec, const float* __restrict__ ctx_img,
                                const float* __restrict__ attn_wst, const float* __restrict__ attn_vec,
@@ -729,7 +732,9 @@ GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const
                                float* __restrict__ k_out, float* __restrict__ v_out, float* __restrict__ x2_out, int N, int tiles,
                                int T, int ttiles, const PairTab* __restrict__ ptab = nullptr,
                                unsigned* __restrict__ v_scale = nullptr,     // non-null: V with e4m3 cross planes (store_block_v8) ...
-                               const PvGuard guard = {}) {                   // ... for the pairs the guard lets through (pv_planes_on)
+                               const PvGuard guard = {},                     // ... for the pairs the guard lets through (pv_planes_on)
+                               const float* __restrict__ kvf_wst = nullptr, const float* __restrict__ kvf_bias = nullptr) {
+  static_assert(!KVF || (NP == 3 && PART != 2), "the folded form: parity numerics, the kernel or its projection role");
   const int lane = threadIdx.x & 63, h = lane >> 5, i = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int pair = blockIdx.y;
@@ -757,14 +762,18 @@ GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const
   float* const lvec_f = lvec_a + 7 * C;
   float* const halo = lvec_f + (3 * C + 2 * FFH) + wave * (2 * C);
   float* const lvec_p = lvec_f + (3 * C + 2 * FFH) + kWavesPerWG * (2 * C);      // bq' | bk | bv
-  if (PART != 2) dma_vec(front_vec + C, lvec_p, 3 * C, wave, kWavesPerWG, lane);
+  if (PART != 2 && KVF) { if (!QSKIP) dma_vec(kvf_bias, lvec_p, C, wave, kWavesPerWG, lane); }
+  else if (PART != 2) dma_vec(front_vec + C, lvec_p, 3 * C, wave, kWavesPerWG, lane);
   if (PART != 1) {
     dma_vec(attn_vec, lvec_a, 7 * C, wave, kWavesPerWG, lane);
     dma_vec(ff_vec, lvec_f, 3 * C + 2 * FFH, wave, kWavesPerWG, lane);
     LcpeHalo<CF>::issue(pair_base, tile, tiles_p, halo, lane);
   }
   StageRing<4> ss;
-  if (PART == 0) ss.init(lds, wave, lane, front_wst + (QSKIP ? 8 : 4) * kStageFloats, QSKIP ? 8 : 12, attn_wst, 2,
+  if (KVF && PART == 1) ss.init(lds, wave, lane, kvf_wst, 4);
+  else if (KVF && QSKIP) ss.init(lds, wave, lane, attn_wst, 2, ctx_img + (size_t)pair * ttiles * kStageFloats, ttiles, attn_wst + 2 * kStageFloats, 2);
+  else if (KVF) ss.init(lds, wave, lane, kvf_wst, 4, attn_wst, 2, ctx_img + (size_t)pair * ttiles * kStageFloats, ttiles, attn_wst + 2 * kStageFloats, 2);
+  else if (PART == 0) ss.init(lds, wave, lane, front_wst + (QSKIP ? 8 : 4) * kStageFloats, QSKIP ? 8 : 12, attn_wst, 2,
                          ctx_img + (size_t)pair * ttiles * kStageFloats, ttiles, attn_wst + 2 * kStageFloats, 2);
   else if (PART == 1) ss.init(lds, wave, lane, front_wst + 4 * kStageFloats, 12);
   else ss.init(lds, wave, lane, attn_wst, 2, ctx_img + (size_t)pair * ttiles * kStageFloats, ttiles, attn_wst + 2 * kStageFloats, 2);
@@ -783,9 +792,48 @@ GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const
     ss.prime();                                  // AFTER the load above: its wait then leaves the three primed stages in flight
     const bool v8 = pv_planes_on(v_scale, guard, pair);          // [r5] decides the K image's cross planes as well as V's
     unsigned* const sw_tile = v_scale ? v_scale + ((size_t)pair * tiles + tile) * 128 + lane : nullptr;     // [V: 64 lanes | K: 64 lanes]
-    unsigned ksw = 0;
+    unsigned ksw = 0, vsw = 0;
+    if (KVF) {
+      // everything issued before the ring's three primed stages (12 pieces) has landed: the vectors and halo rows for every wave
+      asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+      __syncthreads();
+      // K image = f as it lies in the registers; V image = its transpose.  Slot 3 of the ring is idle until the first acquire:
+      // 4 waves x (32 keys x 32 features) floats, column index XOR row (conflict-free writes by key and reads by feature)
+      float* const mt = lds + 3 * kStageFloats + wave * 1024;
 #pragma unroll
-    for (int which = (QSKIP ? 1 : 0); which < 2; ++which) {   // Q', K
+      for (int mb = 0; mb < 4; ++mb) {
+        float t[16], td[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) t[r] = f[16 * mb + r];
+        if (v8) store_block_v8(k_out + toff, mb, t, lane, ksw);
+        else store_block_h2(k_out + toff, mb, t, lane);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mt[i * 32 + (frag_feature(r, h) ^ i)] = t[r];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { const int kk = frag_feature(r, h); td[r] = mt[kk * 32 + (i ^ kk)]; }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (v8) store_block_v8(v_out + toff, mb, td, lane, vsw);
+        else store_block_h2(v_out + toff, mb, td, lane);
+      }
+      // (32 stores so far: the counted waits of the stages that follow rely on them as a lower bound)
+      if (v_scale) { sw_tile[0] = vsw; sw_tile[64] = ksw; }
+      if (!QSKIP) {
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {           // q~, the arithmetic of the attention prologue bit for bit
+          const f16x8* lw = as_h2(ss.acquire());
+          f32x16 acc = zero16();
+          mma_wx_h2n<8, NP>(acc, lw, fx);
+          float t[16], bb[16];
+          load_vec_block(bb, lvec_p, mb, h);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) t[r] = fmaf(acc[r], kH2Inv, bb[r]);
+          store_block_h2(q_out + toff, mb, t, lane);
+        }
+      }
+    }
+#pragma unroll
+    for (int which = (KVF ? 2 : QSKIP ? 1 : 0); which < 2; ++which) {   // Q', K
       float* dst = (which == 0 ? q_out : k_out) + toff;
 #pragma unroll
       for (int mb = 0; mb < 4; ++mb) {
@@ -805,9 +853,8 @@ GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const
         else store_block_h2(dst, mb, t, lane);
       }
     }
-    unsigned vsw = 0;
 #pragma unroll
-    for (int db = 0; db < 4; ++db) {             // V (feature on lane)
+    for (int db = (KVF ? 4 : 0); db < 4; ++db) {             // V (feature on lane)
       const f16x8* lw = as_h2(PART == 1 ? ss.acquire() : ss.acquire_counted<20>());
       f32x16 acc = zero16();
       mma_xw_h2n<8, NP>(acc, lw, fx);
@@ -820,7 +867,7 @@ GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const
     }
     // one more store than the counted waits of the stages that follow assume: their counts are lower bounds, it only makes them
     // wait for one operation more
-    if (v_scale) { sw_tile[0] = vsw; sw_tile[64] = ksw; }     // (written either way: one store count for both forms)
+    if (v_scale && !KVF) { sw_tile[0] = vsw; sw_tile[64] = ksw; }     // (written either way: one store count for both forms)
   }
 
   if (PART == 1) {
@@ -853,7 +900,9 @@ GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const
         }
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
-          const f16x8* lw = as_h2(ss.acquire());
+          // KVF without a Q' image: behind the pieces of these two stages lie those of the next two stages (8; 4 + 4 for the second, whose
+          // successor the first acquire issued) and the 32 image stores - they stay in flight across the stage barriers
+          const f16x8* lw = as_h2((KVF && QSKIP && PART == 0) ? ss.acquire_counted<40>() : ss.acquire());
           f32x16 acc = zero16();
           mma_wx_h2n<8, NP>(acc, lw, nx);
           float t[16];
@@ -972,30 +1021,33 @@ GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const
 // NP = 3: the parity kernel.  NP = 1: the throughput numerics mode (gmf_set_tuning "precision" = 1) - every product of the layer's
 // linear part on the high fp16 planes only (a third of the MFMAs, half the LDS reads); LayerNorms, softmax, GELU, biases and
 // residuals stay fp32.  NOT within the parity gate.
-template <int NP, bool QSKIP = false>
+template <int NP, bool QSKIP = false, bool KVF = false>
 __global__ void __launch_bounds__(256, 2)
 k_linear_h2(const float* __restrict__ f_in, const float* __restrict__ front_wst, const float* __restrict__ front_vec,
             const float* __restrict__ ctx_img, const float* __restrict__ attn_wst, const float* __restrict__ attn_vec,
             const float* __restrict__ ff_wst, const float* __restrict__ ff_vec, float* __restrict__ q_out,
             float* __restrict__ k_out, float* __restrict__ v_out, float* __restrict__ x2_out, int N, int tiles, int T,
-            int ttiles, const PairTab* __restrict__ ptab, unsigned* __restrict__ v_scale, const PvGuard guard) {
+            int ttiles, const PairTab* __restrict__ ptab, unsigned* __restrict__ v_scale, const PvGuard guard,
+            const float* __restrict__ kvf_wst, const float* __restrict__ kvf_bias) {
   __shared__ __attribute__((aligned(16))) float lds[kLinLdsFloats];
   tail_priority(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-  linear_h2_body<0, NP, QSKIP>(lds, f_in, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst, ff_vec, q_out, k_out, v_out, x2_out, N,
-                               tiles, T, ttiles, ptab, v_scale, guard);
+  linear_h2_body<0, NP, QSKIP, KVF>(lds, f_in, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst, ff_vec, q_out, k_out, v_out, x2_out, N,
+                                    tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias);
 }
 
 // grid (ceil(tiles / 4), B, 2): blockIdx.z = 0 the Q'/K/V role, 1 the Fusion-2 role of the same 128 rows
+template <bool KVF>
 __global__ void __launch_bounds__(256, 2)
 k_linear_roles(const float* __restrict__ f_in, const float* __restrict__ front_wst, const float* __restrict__ front_vec,
                const float* __restrict__ ctx_img, const float* __restrict__ attn_wst, const float* __restrict__ attn_vec,
                const float* __restrict__ ff_wst, const float* __restrict__ ff_vec, float* __restrict__ q_out,
                float* __restrict__ k_out, float* __restrict__ v_out, float* __restrict__ x2_out, int N, int tiles, int T,
-               int ttiles, unsigned* __restrict__ v_scale, const PvGuard guard, const PairTab* __restrict__ ptab) {   // [r5] ragged batches too
+               int ttiles, unsigned* __restrict__ v_scale, const PvGuard guard, const PairTab* __restrict__ ptab,   // [r5] ragged batches too
+               const float* __restrict__ kvf_wst, const float* __restrict__ kvf_bias) {
   __shared__ __attribute__((aligned(16))) float lds[kLinLdsFloats];
   if (blockIdx.z == 0)
-    linear_h2_body<1>(lds, f_in, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst, ff_vec, q_out, k_out, v_out, x2_out, N,
-                      tiles, T, ttiles, ptab, v_scale, guard);
+    linear_h2_body<1, 3, false, KVF>(lds, f_in, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst, ff_vec, q_out, k_out, v_out, x2_out, N,
+                                     tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias);
   else
     linear_h2_body<2>(lds, f_in, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst, ff_vec, q_out, k_out, v_out, x2_out, N,
                       tiles, T, ttiles, ptab);
@@ -1049,19 +1101,30 @@ hipError_t launch_front_h2(int mode, bool split, const float* in, const float* w
 hipError_t launch_linear_h2(bool roles, const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
                             const float* attn_wst, const float* attn_vec, const float* ff_wst, const float* ff_vec, float* q,
                             float* k, float* v, float* x2, int B, int N, int tiles, int T, int ttiles, hipStream_t s,
-                            bool one_product, const PairTab* ptab, unsigned* v_scale, PvGuard guard) {
-  if (roles)
-    hipLaunchKernelGGL(k_linear_roles, tgrid(tiles, B, 2), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec,
-                       ff_wst, ff_vec, q, k, v, x2, N, tiles, T, ttiles, v_scale, guard, ptab);
+                            bool one_product, const PairTab* ptab, unsigned* v_scale, PvGuard guard, const float* kvf_wst,
+                            const float* kvf_bias) {
+  const float* const none = nullptr;
+  if (roles && kvf_wst)
+    hipLaunchKernelGGL(k_linear_roles<true>, tgrid(tiles, B, 2), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec,
+                       ff_wst, ff_vec, q, k, v, x2, N, tiles, T, ttiles, v_scale, guard, ptab, kvf_wst, kvf_bias);
+  else if (roles)
+    hipLaunchKernelGGL(k_linear_roles<false>, tgrid(tiles, B, 2), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec,
+                       ff_wst, ff_vec, q, k, v, x2, N, tiles, T, ttiles, v_scale, guard, ptab, none, none);
+  else if (kvf_wst && !q)                          // "kv_fold": K and V images of f, Fusion-2; q~ in the attention prologue
+    hipLaunchKernelGGL((k_linear_h2<3, true, true>), tgrid(tiles, B), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
+                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias);
+  else if (kvf_wst)                                // ... with a q~ image
+    hipLaunchKernelGGL((k_linear_h2<3, false, true>), tgrid(tiles, B), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
+                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias);
   else if (one_product)                            // throughput numerics mode: high planes only
     hipLaunchKernelGGL(k_linear_h2<1>, tgrid(tiles, B), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard);
+                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none);
   else if (!q)                                     // [r4] no Q' image: the attention kernel projects its own (CompatCache::qf_img)
     hipLaunchKernelGGL((k_linear_h2<3, true>), tgrid(tiles, B), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard);
+                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none);
   else
     hipLaunchKernelGGL(k_linear_h2<3>, tgrid(tiles, B), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard);
+                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none);
   return hipGetLastError();
 }
 

@@ -687,7 +687,11 @@ constexpr float kInvU16 = 1.0f / 65535.0f;
 // pl8 = e4m3 of the residual, and the row sum is taken over exactly those values - numerator and denominator of the softmax see the
 // same probabilities, so what is left of the e4m3 rounding is (v_j - o) weighted: 1.5e-6 ... 2.5e-6 on the logits in the fp64
 // emulation of the whole encoder (tests/tools/mx_cross_emulation.py; 2e-5 with the row sum over the unrounded values).
-template <int NPROD = 3, int CFMT = 0, int WAVES = 4, bool PVF8 = false>
+// FOLD ("kv_fold"): k_img and v_img hold the layer input f itself (key image = the planes of f, value image = f
+// transposed; written by the fold form of k_linear_h2), the projection stages qw_wst / the Q' image carry q~ = (Wk^T Wq') f + Wk^T bq',
+// every score accumulator starts from the query's beta = (Wq'^T bk) . f + bk . bq' (kvf_vec: Wq'^T bk [128] | bk . bq'), and Wv, bv are
+// composed into the first layer of the epilogue's weights (wst, vecs).  The tile loop and the image formats are the unfolded ones.
+template <int NPROD = 3, int CFMT = 0, int WAVES = 4, bool PVF8 = false, bool FOLD = false>
 GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restrict__ q_img, const float* __restrict__ k_img,
                                 const float* __restrict__ v_img, const float* __restrict__ fus, const float* __restrict__ wst,
                                 const float* __restrict__ vecs, float* out, int N, int tiles, int wgs_per_pair,
@@ -702,8 +706,10 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
                                 // LATER merge launch (split items): no tile is written before its last reader is done.  ADVICE r4)
                                 const float* qf_img = nullptr, const float* __restrict__ qw_wst = nullptr,
                                 const float* __restrict__ qw_bias = nullptr,
-                                unsigned* __restrict__ stat_next = nullptr) {     // [r5] PvGuard::stat_next (whole items with the next PointCN)
+                                unsigned* __restrict__ stat_next = nullptr,       // [r5] PvGuard::stat_next (whole items with the next PointCN)
+                                const float* __restrict__ kvf_vec = nullptr) {    // FOLD: Wq'^T bk [128] | bk . bq'
   static_assert(!PVF8 || NPROD == 3, "the fp8 cross products belong to the three-product form");
+  static_assert(!FOLD || (NPROD == 3 && WAVES == 4), "the folded form belongs to the parity kernels");
   float* const ldsK = lds;
   float* const ldsV = lds + 2 * kStageFloats;
   const int lane = threadIdx.x & 63, h = lane >> 5;
@@ -730,7 +736,15 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
   const size_t toff = (pbase + tile) * (32 * C);
 
   f16x8 qh[8], ql[8];
-  if (NPROD == 3 && WAVES == 4 && qf_img) {
+  float beta = 0.f;                              // FOLD: this lane's query's score offset (the accumulator column is the query)
+  auto fold_beta = [&](const float (&fq)[CF]) {
+    float uv[CF], bs = 0.f;
+    load_vec_frag<CF>(uv, kvf_vec, h);
+#pragma unroll
+    for (int e = 0; e < CF; ++e) bs = fmaf(fq[e], uv[e], bs);
+    beta = xhalf_sum(bs) + kvf_vec[C];
+  };
+  if (NPROD == 3 && WAVES == 4 && qw_wst) {
     // [r4] Q' = Wq' f + bq' for this workgroup's 128 query rows HERE instead of in k_linear_h2 (PointDSC.py:56: projection_q).  Q'
     // is the one projection only its own workgroup consumes: computing it in the linear kernel meant 82 MB written and read
     // back per layer and a third of the stores of that kernel's write-bound Q'/K/V phase (k_linear_h2 without it: 307 -> 272 us).
@@ -742,6 +756,7 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
       float fq[CF];
       load_frag_p32<CF>(fq, qf_img + toff, lane);
       fx.set(fq);
+      if (FOLD) fold_beta(fq);
     }
 #pragma unroll
     for (int st = 0; st < 4; ++st) dma_4k_s(qw_wst + st * kStageFloats + wave * 1024, lds + st * kStageFloats + wave * 1024, lane_off16);
@@ -767,7 +782,25 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
       qh[s] = qp[(0 * 8 + s) * 64];
       if (NPROD == 3) ql[s] = qp[(1 * 8 + s) * 64];
     }
+    if (FOLD) {                                    // (the Q' image holds q~; beta comes from the f tile all the same)
+      float fq[CF];
+      load_frag_p32<CF>(fq, qf_img + toff, lane);
+      fold_beta(fq);
+    }
   }
+  // the start of a score accumulator: zero, or (FOLD) the query's beta in every row.  The 16 copies are made afresh for every tile (the
+  // value is opaque to the compiler at each use): held across the tile loop they were 16 more live registers in a kernel that has
+  // three to spare, and the loop spilled (31 registers to scratch memory)
+  auto s_start = [&]() -> f32x16 {
+    f32x16 z = zero16();
+    if (FOLD) {
+      float b = beta;
+      asm volatile("" : "+v"(b));
+#pragma unroll
+      for (int r = 0; r < 16; ++r) z[r] = b;
+    }
+    return z;
+  };
   // [r5] PVF8: the two CROSS products of S = K Q'^T run on the block-scaled fp8 pipe as well - per key tile 8 f16 MFMAs (K_hi Q'_hi) and 4
   // v_mfma_scale_f32_32x32x64_f8f6f4 (one per 32-channel block: [e4m3(k - k_hi) | e4m3(k)] x [e4m3(q) | e4m3(q_lo)]) instead of 24 f16
   // MFMAs: 512 instead of 768 matrix-pipe cycles.  Allowed by the same device-side guard as the P V form (a layer whose scores can
@@ -877,7 +910,7 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
   fetch_c(t_begin);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  f32x16 s_a = zero16(), s_b;
+  f32x16 s_a = s_start(), s_b;
   // S of one key tile in the fp8 form: 8 f16 MFMAs on the high planes + 4 scaled fp8 MFMAs on the cross planes
   auto s_cross8 = [&](f32x16 acc, const f16x8* lkt, const int cb, const unsigned kscale) -> f32x16 {
     const i32x4* l8 = reinterpret_cast<const i32x4*>(lkt);
@@ -965,7 +998,7 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
       m_off = m_new - 10.0f;                 // P' = 2^10 P
       rescale(moved, alpha);
     }
-    s_next = zero16();
+    s_next = s_start();
     // ---- phase 1: S_{t+1} on the matrix pipe, tile t's scores / max / first exponentials in its issue gaps ----
     {
       f16x8 kh = lk[0], kl = kh;
@@ -1042,7 +1075,7 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
     i32x8 pb;
     f16x8 vr[3];
     auto hslot = [](int u) { return (0 * 8 + 2 * (u & 3) + (u >> 2)) * 64; };
-    s_next = zero16();
+    s_next = s_start();
     {
       // [r5] 12 matrix instructions in the phase's 24 units: K_hi Q'_hi of k-step s at unit 3 s + 2, the scaled fp8 MFMA of channel block
       // cb (k-steps 2 cb, 2 cb + 1) at unit 6 cb + 3; its two 16-byte K fragments are requested one k-step earlier (unit 6 cb)
@@ -1267,7 +1300,7 @@ GMF_DEVINL bool attn_pv_on(const unsigned* __restrict__ v_scale, const PvGuard& 
   return pv_planes_on(v_scale, guard, ptab ? ptab[slot].ord : slot);
 }
 
-template <int NPROD, int CFMT, bool PVF8 = false>
+template <int NPROD, int CFMT, bool PVF8 = false, bool FOLD = false>
 __global__ void __launch_bounds__(256, 2)
 k_scattn_h2p(const float* __restrict__ q_img, const float* __restrict__ k_img, const float* __restrict__ v_img,
              const float* __restrict__ fus, const float* __restrict__ wst, const float* __restrict__ vecs,
@@ -1275,17 +1308,17 @@ k_scattn_h2p(const float* __restrict__ q_img, const float* __restrict__ k_img, c
              int n_items, int n_full, int ksplits, float* __restrict__ part_o, float* __restrict__ part_ml,
              const float* __restrict__ next_wst, const float* __restrict__ next_bias, const PairTab* __restrict__ ptab,
              const unsigned* __restrict__ v_scale, const float* qf_img, const float* __restrict__ qw_wst,
-             const float* __restrict__ qw_bias, const PvGuard guard) {
+             const float* __restrict__ qw_bias, const PvGuard guard, const float* __restrict__ kvf_vec) {
   __shared__ __attribute__((aligned(16))) float lds[4 * kStageFloats];
   tail_priority(blockIdx.x, gridDim.x);
   if (!PVF8 || attn_pv_on(v_scale, guard, blockIdx.x, n_items, n_full, ksplits, wgs_per_pair, ptab))
-    scattn_h2p_body<NPROD, CFMT, 4, PVF8>(lds, blockIdx.x, q_img, k_img, v_img, fus, wst, vecs, out, N, tiles, wgs_per_pair, c_dense, n_items,
-                                          n_full, ksplits, part_o, part_ml, next_wst, next_bias, ptab, v_scale, qf_img, qw_wst, qw_bias,
-                                          guard.stat_next);
+    scattn_h2p_body<NPROD, CFMT, 4, PVF8, FOLD>(lds, blockIdx.x, q_img, k_img, v_img, fus, wst, vecs, out, N, tiles, wgs_per_pair, c_dense, n_items,
+                                                n_full, ksplits, part_o, part_ml, next_wst, next_bias, ptab, v_scale, qf_img, qw_wst, qw_bias,
+                                                guard.stat_next, kvf_vec);
   else
-    scattn_h2p_body<NPROD, CFMT, 4, false>(lds, blockIdx.x, q_img, k_img, v_img, fus, wst, vecs, out, N, tiles, wgs_per_pair, c_dense, n_items,
-                                           n_full, ksplits, part_o, part_ml, next_wst, next_bias, ptab, nullptr, qf_img, qw_wst, qw_bias,
-                                           guard.stat_next);
+    scattn_h2p_body<NPROD, CFMT, 4, false, FOLD>(lds, blockIdx.x, q_img, k_img, v_img, fus, wst, vecs, out, N, tiles, wgs_per_pair, c_dense, n_items,
+                                                 n_full, ksplits, part_o, part_ml, next_wst, next_bias, ptab, nullptr, qf_img, qw_wst, qw_bias,
+                                                 guard.stat_next, kvf_vec);
 }
 
 // =========================================================================================
@@ -2372,19 +2405,25 @@ hipError_t launch_scattn_h2p(const float* q, const float* k, const float* v, con
                        cc.next_wst_h2, cc.next_bias);
   else if (cc.half)  // ... with a split tail: one fp16 product, c streamed as fp16 (the cache was built that way)
     hipLaunchKernelGGL((k_scattn_h2p<1, 1>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense, W,
-                       n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, PvGuard{});
+                       n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, PvGuard{}, (const float*)nullptr);
   else if (cc.fmt == 2 && cc.v_scale)   // parity arithmetic, c streamed as 16-bit fixed point; fp8 cross products of P V
     hipLaunchKernelGGL((k_scattn_h2p<3, 2, true>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
-                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, cc.v_scale, cc.qf_img, cc.qw_wst, cc.qw_bias, cc.guard);
+                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, cc.v_scale, cc.qf_img, cc.qw_wst, cc.qw_bias, cc.guard, (const float*)nullptr);
   else if (cc.fmt == 2)
     hipLaunchKernelGGL((k_scattn_h2p<3, 2>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
-                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, cc.qf_img, cc.qw_wst, cc.qw_bias, PvGuard{});
+                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, cc.qf_img, cc.qw_wst, cc.qw_bias, PvGuard{}, (const float*)nullptr);
+  else if (cc.kvf_vec && cc.v_scale)   // "kv_fold" (the plan grants it on the fp32 cache only): keys = values = f
+    hipLaunchKernelGGL((k_scattn_h2p<3, 0, true, true>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
+                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, cc.v_scale, cc.qf_img, cc.qw_wst, cc.qw_bias, cc.guard, cc.kvf_vec);
+  else if (cc.kvf_vec)
+    hipLaunchKernelGGL((k_scattn_h2p<3, 0, false, true>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
+                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, cc.qf_img, cc.qw_wst, cc.qw_bias, PvGuard{}, cc.kvf_vec);
   else if (cc.v_scale)    // the default: V image with e4m3 cross planes (k_linear_h2 wrote it that way)
     hipLaunchKernelGGL((k_scattn_h2p<3, 0, true>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
-                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, cc.v_scale, cc.qf_img, cc.qw_wst, cc.qw_bias, cc.guard);
+                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, cc.v_scale, cc.qf_img, cc.qw_wst, cc.qw_bias, cc.guard, (const float*)nullptr);
   else
     hipLaunchKernelGGL((k_scattn_h2p<3, 0>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
-                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, cc.qf_img, cc.qw_wst, cc.qw_bias, PvGuard{});
+                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, cc.qf_img, cc.qw_wst, cc.qw_bias, PvGuard{}, (const float*)nullptr);
   if (max_tail > 0)
     hipLaunchKernelGGL(k_scattn_merge, dim3(8 * max_tail), dim3(256), 0, s, cc.part_o, cc.part_ml, fus, cc.tail_wst_h2, vecs, out,
                        tiles, wpp, W, n_full, ksplits, cc.next_wst_h2, cc.next_bias, (const float*)nullptr, 0,

@@ -305,6 +305,11 @@ int gmf_set_tuning(gmf_handle* h, const char* name, int value) {
     t.q_in_attention = value != 0;
     return GMF_OK;
   }
+  if (std::strcmp(name, "kv_fold") == 0) {             // 1 = large grids: keys = values = f, K / V projections composed into the weights (default), 0 = the unfolded form
+    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: kv_fold must be 0 or 1");
+    t.kv_fold = value != 0;
+    return GMF_OK;
+  }
   if (std::strcmp(name, "pv_fp8") == 0) {       // large grids: the cross products of O += P V on the block-scaled fp8 pipe (default 1)
     GMF_REQUIRE(value >= 0 && value <= 2, GMF_ERR_BAD_ARG, "set_tuning: pv_fp8 must be 0 (three f16 products), 1 (guarded, default) or 2 (always)");
     t.pv_fp8 = value;
@@ -344,7 +349,7 @@ int gmf_get_tuning(gmf_handle* h, const char* name, int* value) {
       {"fused_linear", t.fused_linear ? 1 : 0}, {"compat_cache", t.use_cache ? 1 : 0}, {"conv_lds_patch", t.conv_patch}, {"conv_small_grid", t.conv_small ? 1 : 0}, {"small_prologue_roles", t.small_prologue ? 1 : 0}, {"small_fattn_tile", t.small_fattn_tile ? 1 : 0},
       {"nms_binned", t.nms_binned}, {"topk_select", t.topk_select ? 1 : 0}, {"wide_attn_tile", t.wide_attn_tile ? 1 : 0},
       {"small_merge_tile", t.small_merge_tile ? 1 : 0}, {"mid_grid_roles", t.mid_grid_roles}, {"pv_fp8", t.pv_fp8}, {"q_in_attention", t.q_in_attention ? 1 : 0},
-      {"compat_format", t.compat_format}, {"precision", t.precision}, {"spectral_col_splits", t.spectral_col_splits},
+      {"kv_fold", t.kv_fold ? 1 : 0}, {"compat_format", t.compat_format}, {"precision", t.precision}, {"spectral_col_splits", t.spectral_col_splits},
       {"clique_local_rows", t.clique_local_rows}};
   for (const auto& e : tab) {
     if (std::strcmp(name, e.name) == 0) { *value = e.v; return GMF_OK; }
@@ -576,6 +581,7 @@ struct EncoderPlan {
   int ff_hs = 1, f1_ff_hs = 1;    // hidden splits of the layers' feed-forward and of Fusion-1's
   bool roles = false;        // k_linear_h2 as two workgroup roles per row block
   bool q_in_attn = false;    // no Q' image: the attention projects its own (CompatCache::qf_img)
+  bool kv_fold = false;      // keys = values = f: no K / V projections, composed weights (gmf_encoder_weights::kv_fold)
   bool v_fp8 = false;        // V carries e4m3 cross planes (CompatCache::v_scale) ...
   bool guard = false;        // ... chosen per pair and layer on the device (PvGuard)
   bool clear_stats = false;  // the key-point packing clears the guard's statistics
@@ -628,6 +634,11 @@ static EncoderPlan plan_encoder(const gmf::Tuning& t, const gmf_encoder_weights*
   // [r4] Q' in the attention kernel's prologue (parity arithmetic of the pipelined kernel; not with the linear kernel as two roles,
   // whose Q'/K/V role writes the image): k_linear_h2 then projects K and V only
   p.q_in_attn = p.form == EncoderPlan::kLinear && t.q_in_attention && !p.half && !p.roles;
+  // "kv_fold": the two-launch plan with the parity numerics of the pipelined kernel on the fp32 cache - uniform or ragged, the linear
+  // kernel whole or as two roles, Q' in the attention prologue or as an image (one rule for all of them: the forms that are compared
+  // bit for bit fold together).  Everything else - small grids, "precision" 1 / 2, the 16-bit cache, weights without the composed
+  // block - runs the unfolded form
+  p.kv_fold = t.kv_fold && p.form == EncoderPlan::kLinear && p.pipelined && !p.half && p.fmt == 0 && w->kv_fold != nullptr;
   // parity arithmetic: V with e4m3 cross planes for the pv_fp8 form of every attention kernel of the fused forms (a weights block
   // without thresholds, pv_guard = NULL, gets the three-product form under the guarded default, never the unguarded one).  [r5]
   // "pv_fp8" = 1: guarded per pair and layer on the device; the key-point packing clears the statistics (a superset of the readers)
@@ -663,10 +674,10 @@ static int prof_begin(gmf_handle* h, hipStream_t st, hipEvent_t* ev0, hipEvent_t
 // pipelined kernel, the split-fp16 kernel of the kStages form (c from the cache when there is one, else recomputed), or fp32.
 static int run_scattn(gmf_handle* h, const gmf_encoder_weights* w, const EncoderPlan& p, int l, const float* q, const float* k,
                       const float* v, const float* pts8, const float* x2, float* out, int B, int N, hipStream_t st,
-                      const float* dense_compat, const gmf::CompatCache& cc) {
+                      const float* dense_compat, const gmf::CompatCache& cc, const float* tail_vecs = nullptr) {
   const int tiles = tiles_of(N);
   const float* wst = w->tail_wst + (size_t)l * w->tail_wst_stride;
-  const float* vecs = w->tail_vec + (size_t)l * w->tail_vec_stride;
+  const float* vecs = tail_vecs ? tail_vecs : w->tail_vec + (size_t)l * w->tail_vec_stride;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (int rc = prof_begin(h, st, &ev0, &ev1)) return rc;
   if (dense_compat) GMF_HIP(gmf::launch_scattn_dense(q, k, v, dense_compat, x2, wst, vecs, out, B, N, tiles, st));
@@ -844,6 +855,7 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
       const float* ffv = w->ff_vec + (size_t)l * w->ff_vec_stride;
       const float* ctx_l = ctxall + (size_t)l * tok;
       const bool last = (l + 1 == L);
+      const float* tail_vecs = nullptr;            // "kv_fold": the epilogue's vectors with Wa bv + ba (else the layer's own, run_scattn)
       cc.tail_wst_h2 = w->tail_wst_h2 + (size_t)l * w->tail_wst_stride;
       cc.next_wst_h2 = last ? nullptr : w->front_wst_h2 + (size_t)(l + 1) * w->front_wst_stride;
       cc.next_bias = last ? nullptr : w->front_vec + (size_t)(l + 1) * w->front_vec_stride;
@@ -851,8 +863,18 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
         cc.qf_img = p.q_in_attn ? f : nullptr;
         cc.qw_wst = p.q_in_attn ? fw + 4 * kTileFloats : nullptr;
         cc.qw_bias = p.q_in_attn ? fv + kC : nullptr;
+        const float* kvf = p.kv_fold ? w->kv_fold + (size_t)l * GMF_KV_FOLD_STRIDE : nullptr;
+        const float* kvf_vecs = kvf ? kvf + 9 * kTileFloats : nullptr;        // Wk^T bq' | Wq'^T bk | bk . bq' (128) | the epilogue's vectors
+        if (kvf) {
+          cc.qf_img = f;                                                       // (beta comes from the f tile with or without a Q' image)
+          cc.qw_wst = p.q_in_attn ? kvf : nullptr;
+          cc.qw_bias = p.q_in_attn ? kvf_vecs : nullptr;
+          cc.tail_wst_h2 = kvf + 4 * kTileFloats;
+          cc.kvf_vec = kvf_vecs + kC;
+          tail_vecs = kvf_vecs + 3 * kC;
+        }
         GMF_HIP(gmf::launch_linear_h2(p.roles, f, fw, fv, ctx_l, aw, av, ffw, ffv, p.q_in_attn ? nullptr : q, k, v, x2, B, N, tiles, T, tt,
-                                      st, p.one_product, ptab, cc.v_scale, cc.guard));
+                                      st, p.one_product, ptab, cc.v_scale, cc.guard, kvf, kvf_vecs));
       } else if (p.form == EncoderPlan::kSmall3) {
         // three launches: {Q' | K | V | cross-attention} -> {key-split attention | hidden-split feed-forward} -> merge
         GMF_HIP(gmf::launch_small_front_fattn(f, fw, fv, ctx_l, aw, av, q, k, v, x1, B, N, tiles, T, tt, st, cc.v_scale, cc.guard,
@@ -870,7 +892,7 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
         GMF_HIP(gmf::launch_fusion_attn_h2(true, f, ctx_l, aw, av, x1, B, N, tiles, T, tt, st));
         GMF_HIP(gmf::launch_fusion_ff_h2(x1, ffw, ffv, x2, B, tiles, st, part_o, p.ff_hs));
       }
-      if (int rc = run_scattn(h, w, p, l, q, k, v, pts8, x2, last ? cur : f, B, N, st, nullptr, cc)) return rc;
+      if (int rc = run_scattn(h, w, p, l, q, k, v, pts8, x2, last ? cur : f, B, N, st, nullptr, cc, tail_vecs)) return rc;
     }
     GMF_HIP(gmf::launch_head(cur, w->head_wst, w->head_vec, logits, feat_n, feat, B, N, tiles, st, h->status_dev, ptab,
                              p.guard ? fstat : nullptr, p.guard ? w->pv_guard : nullptr, L));

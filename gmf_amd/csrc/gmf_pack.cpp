@@ -336,6 +336,65 @@ void pack_tail(const StateDict& sd, int layer, Img kind, Ctx& cx, std::vector<fl
   append(*vec, vec_of(sd, p + "6.bias", kCw));
 }
 
+// The "kv_fold" weights of layer `layer` (gmf_encoder_weights::kv_fold; PointDSC.py:56-64): the key and value
+// tiles of the large-grid attention are the layer input f itself,
+//     q'_i . (Wk f_j + bk) = f_j . q~_i + beta_i          q~ = (Wk^T Wq') f + Wk^T bq',   beta = (Wq'^T bk) . f + bk . bq'
+//     sum_j p_ij (Wv f_j + bv) = Wv (sum_j p_ij f_j) + bv  (a softmax row sums to 1): Wv, bv compose with fc_message's first layer.
+// Every composed value is formed in fp64 from the fp32 factors and rounded ONCE.  GMF_KV_FOLD_STRIDE floats:
+//   Wk^T Wq' [4 stages] | Wa Wv, Wb, Wc [5 stages] | Wk^T bq' [128] | Wq'^T bk [128] | bk . bq' [1 + 127 zeros] | Wa bv + ba [64] | bb | bc
+void pack_kv_fold(const StateDict& sd, int layer, Ctx& cx, std::vector<float>& out) {
+  const std::string n = "encoder.blocks.NonLocal_layer_" + std::to_string(layer) + ".";
+  const size_t base = out.size();
+  const float cq = (float)(kLog2e / std::sqrt((double)kCw));
+  const Mat Wq = scaled(mat_of(sd, n + "projection_q.weight", kCw, kCw), cq);          // (the very fp32 values of pack_front)
+  std::vector<float> bq = vec_of(sd, n + "projection_q.bias", kCw);
+  for (float& x : bq) x = x * cq;
+  const Mat Wk = mat_of(sd, n + "projection_k.weight", kCw, kCw), Wv = mat_of(sd, n + "projection_v.weight", kCw, kCw);
+  const std::vector<float> bk = vec_of(sd, n + "projection_k.bias", kCw), bv = vec_of(sd, n + "projection_v.bias", kCw);
+  Mat Wa = mat_of(sd, n + "fc_message.0.weight", 64, kCw);
+  std::vector<float> ba = vec_of(sd, n + "fc_message.0.bias", 64);
+  fold_bn(Wa, ba, sd, n + "fc_message.1.");
+  Mat Wqf(kCw, kCw), Waf(64, kCw);
+  std::vector<float> bqf(kCw), u(kCw), baf(64);
+  double b0 = 0.0;
+  for (int c = 0; c < kCw; ++c) {
+    for (int j = 0; j < kCw; ++j) {
+      double a = 0.0;
+      for (int m = 0; m < kCw; ++m) a += (double)Wk.at(m, c) * (double)Wq.at(m, j);
+      Wqf.at(c, j) = (float)a;
+    }
+    double a = 0.0, b = 0.0;
+    for (int m = 0; m < kCw; ++m) { a += (double)Wk.at(m, c) * (double)bq[m]; b += (double)bk[m] * (double)Wq.at(m, c); }
+    bqf[c] = (float)a;
+    u[c] = (float)b;
+    b0 += (double)bk[c] * (double)bq[c];
+  }
+  for (int r = 0; r < 64; ++r) {
+    for (int j = 0; j < kCw; ++j) {
+      double a = 0.0;
+      for (int m = 0; m < kCw; ++m) a += (double)Wa.at(r, m) * (double)Wv.at(m, j);
+      Waf.at(r, j) = (float)a;
+    }
+    double a = (double)ba[r];
+    for (int m = 0; m < kCw; ++m) a += (double)Wa.at(r, m) * (double)bv[m];
+    baf[r] = (float)a;
+  }
+  cx.img(out, Wqf, Img::H2S);
+  cx.img(out, Waf, Img::H2S);
+  Ctx copy;                                       // (Wb, Wc, bb, bc: the values of pack_tail)
+  std::vector<float> tw, tv;
+  pack_tail(sd, layer, Img::H2S, copy, tw, &tv);
+  if (!copy.ok) cx.ok = false;
+  out.insert(out.end(), tw.begin() + 2 * 4096, tw.end());
+  append(out, bqf);
+  append(out, u);
+  out.push_back((float)b0);
+  append_zeros(out, kCw - 1);
+  append(out, baf);
+  out.insert(out.end(), tv.begin() + 64, tv.end());
+  if (out.size() - base != (size_t)GMF_KV_FOLD_STRIDE) throw PackError{GMF_ERR_BAD_ARG, "gmf: pack: kv_fold block size"};
+}
+
 // classification head (PointDSC.py:175-181)   (packing.pack_head)
 void pack_head(const StateDict& sd, std::vector<float>& wst, std::vector<float>& vec) {
   p32(wst, mat_of(sd, "classification.0.weight", 32, kCw));
@@ -450,8 +509,8 @@ int gmf_encoder_pack_weights(gmf_handle* h, const gmf_tensor* tensors, int n_ten
     Block blk;
     struct Off { size_t v = 0; bool set = false; };
     auto put = [&](Off& o, const std::vector<float>& v) { o.v = blk.add(v); o.set = true; };
-    Off f1[6], f1h[3], ctx[2], attn[2], ff[2], front[2], tail[2], head[2], ctxh, attnh, ffh, fronth, tailh, pvgo;
-    Ctx c32, ch2;
+    Off f1[6], f1h[3], ctx[2], attn[2], ff[2], front[2], tail[2], head[2], ctxh, attnh, ffh, fronth, tailh, pvgo, kvfo;
+    Ctx c32, ch2, ckv;
     if (has_f1) {
       FusionBlobs b = pack_fusion(sd, "encoder.fusion_layer_1.", false, Img::F32, c32);
       if (b.lat != 128) throw PackError{GMF_ERR_UNSUPPORTED_SHAPE, "gmf: pack: fusion_layer_1 must be 128 wide"};
@@ -460,7 +519,7 @@ int gmf_encoder_pack_weights(gmf_handle* h, const gmf_tensor* tensors, int n_ten
       put(f1h[0], bh.ctx_wst); put(f1h[1], bh.attn_wst); put(f1h[2], bh.ff_wst);
     }
     if (L > 0) {
-      std::vector<float> cw, cv, aw, av, fw, fv, cwh, awh, fwh, frw, frv, frwh, tw, tv, twh, pvg;
+      std::vector<float> cw, cv, aw, av, fw, fv, cwh, awh, fwh, frw, frv, frwh, tw, tv, twh, pvg, kvf;
       for (int l = 0; l < L; ++l) {
         const std::string pre = "encoder.blocks.NonLocal_layer_" + std::to_string(l) + ".fusion_layer_2.";
         FusionBlobs b = pack_fusion(sd, pre, true, Img::F32, c32);
@@ -473,10 +532,11 @@ int gmf_encoder_pack_weights(gmf_handle* h, const gmf_tensor* tensors, int n_ten
         pack_tail(sd, l, Img::F32, c32, tw, &tv);
         pack_tail(sd, l, Img::H2S, ch2, twh, nullptr);
         pvg.push_back(pv_guard_threshold(sd, l));
+        pack_kv_fold(sd, l, ckv, kvf);
       }
       put(ctx[0], cw); put(ctx[1], cv); put(attn[0], aw); put(attn[1], av); put(ff[0], fw); put(ff[1], fv);
       put(front[0], frw); put(front[1], frv); put(tail[0], tw); put(tail[1], tv);
-      put(ctxh, cwh); put(attnh, awh); put(ffh, fwh); put(fronth, frwh); put(tailh, twh); put(pvgo, pvg);
+      put(ctxh, cwh); put(attnh, awh); put(ffh, fwh); put(fronth, frwh); put(tailh, twh); put(pvgo, pvg); put(kvfo, kvf);
     }
     if (has_head) {
       std::vector<float> hw, hv;
@@ -506,6 +566,7 @@ int gmf_encoder_pack_weights(gmf_handle* h, const gmf_tensor* tensors, int n_ten
       w.front_wst_h2 = at(fronth); w.ctx_wst_h2 = at(ctxh); w.attn_wst_h2 = at(attnh); w.ff_wst_h2 = at(ffh);
       w.f1_ctx_wst_h2 = at(f1h[0]); w.f1_attn_wst_h2 = at(f1h[1]); w.f1_ff_wst_h2 = at(f1h[2]);
       w.tail_wst_h2 = at(tailh);
+      if (ckv.ok) w.kv_fold = at(kvfo);      // (a composed weight outside the fp16 range: no folded form)
     }
   } catch (const PackError& e) {
     delete p;
@@ -635,7 +696,7 @@ int gmf_packed_encoder_place(gmf_handle* h, gmf_packed_encoder* p, void* device_
   const float** ptrs[] = {&w.f1_ctx_wst, &w.f1_ctx_vec, &w.f1_attn_wst, &w.f1_attn_vec, &w.f1_ff_wst, &w.f1_ff_vec, &w.ctx_wst, &w.ctx_vec,
                           &w.attn_wst, &w.attn_vec, &w.ff_wst, &w.ff_vec, &w.front_wst, &w.front_vec, &w.tail_wst, &w.tail_vec, &w.head_wst,
                           &w.head_vec, &w.front_wst_h2, &w.ctx_wst_h2, &w.attn_wst_h2, &w.ff_wst_h2, &w.f1_ctx_wst_h2, &w.f1_attn_wst_h2,
-                          &w.f1_ff_wst_h2, &w.tail_wst_h2, &w.pv_guard};
+                          &w.f1_ff_wst_h2, &w.tail_wst_h2, &w.pv_guard, &w.kv_fold};
   for (const float** q : ptrs) rebase_ptr(*q, from, n, to);
   p->placed = to;
   return GMF_OK;

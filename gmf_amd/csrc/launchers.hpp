@@ -46,6 +46,9 @@ struct CompatCache {
   const float* qw_wst = nullptr;
   const float* qw_bias = nullptr;
   PvGuard guard;              // [r5] per pair: e4m3 cross planes or V's low fp16 plane (with v_scale)
+  // "kv_fold" (EncoderPlan::kv_fold): non-null = the K and V images hold the layer input f, tail_wst_h2 / the epilogue's vectors / qw_* are
+  // the composed weights of gmf_encoder_weights::kv_fold, qf_img is always the layer's f image, and these are Wq'^T bk [128] | bk . bq'
+  const float* kvf_vec = nullptr;
 };
 
 // Per-handle tuning knobs (gmf_set_tuning).  Every value selects between forms that compute the same result up to
@@ -72,6 +75,8 @@ struct Tuning {
   bool topk_select = true;   // radix select of the S seeds (false = full bitonic sort)
   int mid_grid_roles = 512;  // two-launch form on grids below this many base workgroups (>= 256): the linear kernel runs as two
                              // workgroup roles per row block (Q'/K/V | Fusion-2); 0 = never
+  bool kv_fold = true;          // large grids (two-launch plan, parity numerics, fp32 cache): keys = values = the layer input f, the K and V
+                                // projections composed into the query side and fc_message's first layer (false: the unfolded form, bit for bit)
   bool q_in_attention = true;   // [r4] large grids: Q' is projected in the attention kernel's prologue, not written by k_linear_h2 (bit-identical)
   int pv_fp8 = 1;            // parity arithmetic of the default path: the two cross products of O += P V on the block-scaled fp8 matrix
                              // pipe (scattn_h2p_body<3, *, 4, true>).  1 = guarded per pair and layer on the device
@@ -132,7 +137,8 @@ hipError_t launch_front_h2(int mode, bool split, const float* in, const float* w
 hipError_t launch_linear_h2(bool roles, const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
                             const float* attn_wst, const float* attn_vec, const float* ff_wst, const float* ff_vec, float* q,
                             float* k, float* v, float* x2, int B, int N, int tiles, int T, int ttiles, hipStream_t s, bool one_product = false,
-                            const PairTab* ptab = nullptr, unsigned* v_scale = nullptr, PvGuard guard = {});
+                            const PairTab* ptab = nullptr, unsigned* v_scale = nullptr, PvGuard guard = {}, const float* kvf_wst = nullptr,
+                            const float* kvf_bias = nullptr);   // kvf_*: "kv_fold" - the 4 stages of Wk^T Wq' and Wk^T bq'; K and V become images of f
 // small grids: three launches per layer (k_small_front_fattn | k_small_attn_ff | k_scattn_merge)
 hipError_t launch_small_front_fattn(const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
                                     const float* attn_wst, const float* attn_vec, float* q, float* k, float* v, float* x1, int B,

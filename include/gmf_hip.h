@@ -164,6 +164,11 @@ int gmf_set_sigma_device(gmf_handle* h, const float* sigma_dev);
  *   "topk_select"       : 1 = radix select of the S seeds (default), 0 = full bitonic sort.
  *   "q_in_attention"    : [ABI 4] 1 = on large grids every attention workgroup projects its own Q' in its prologue (default; PointDSC.py:56),
  *                         0 = the linear kernel writes a Q' image.  Bit-identical results.
+ *   "kv_fold"           : 1 = on the two-launch plan of large grids (parity numerics, fp32 compat cache) the attention's key and value
+ *                         tiles are the layer input f itself: projection_k is composed into the query side, projection_v into
+ *                         fc_message's first layer (gmf_encoder_weights::kv_fold; PointDSC.py:56-64; default).  Same guard rule as
+ *                         "pv_fp8".  0 = the K and V projections are computed: the unfolded code, bit for bit.  The staged entry
+ *                         points never fold.  Rounding-equivalent (logits within 4e-5 of the unfolded form, inside the parity gate).
  *   "spectral_col_splits": gmf_spectral_matching: 0 = the columns of a pair's sweep are split over workgroups by a rule of its own
  *                         N (default), 1..32 = that many splits at most (another order of a row's partial sums).
  *   "clique_local_rows" : gmf_max_clique: a root of the search with at most this many candidates is searched in LDS with
@@ -267,7 +272,14 @@ typedef struct gmf_encoder_weights {
    * gmf_encoder_pack_weights from the spectral norms of projection_q / projection_k, PointDSC.py:23-25,56-64); NULL = no thresholds:
    * the guarded default ("pv_fp8" = 1) then runs the three-product form (as "pv_fp8" = 0), never the unguarded one. */
   const float* pv_guard;
+  /* optional (appended; NULL in a zero-initialised struct), per layer GMF_KV_FOLD_STRIDE floats: the weights of the "kv_fold" form of the
+   * large-grid attention (keys = values = the layer input f; written by gmf_encoder_pack_weights, composed in fp64 and rounded once) -
+   *   4 split-fp16 stages of Wk^T Wq' | 5 stages of fc_message with its first layer composed with projection_v (Wa Wv | Wb | Wc) |
+   *   Wk^T bq' [128] | Wq'^T bk [128] | bk . bq' [1, padded to 128] | Wa bv + ba [64] | bb [64] | bc [128].
+   * NULL (or a composed weight outside the fp16 range): every plan runs the unfolded form. */
+  const float* kv_fold;
 } gmf_encoder_weights;
+#define GMF_KV_FOLD_STRIDE 37504
 
 /* ---- weight packing ---------------------------------------------------------------------------
  * The reference keeps its weights as a PyTorch state_dict (588 non-image tensors under the names of SURVEY.md section 8b) and
