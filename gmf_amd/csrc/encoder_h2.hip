@@ -1018,6 +1018,19 @@ GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const
   }
 }
 
+// "compat_16": the lazily built fp32 cache as a workgroup role (LazyCompat, launchers.hpp).  grid (ceil(tiles / 4), B, .): workgroup x of pair
+// blockIdx.y takes every gridDim.x-th (query tile, key-tile block) of k_compat_build's grid.  No workgroup barrier inside.
+GMF_DEVINL void compat_tripped_role(float* tr, const LazyCompat& lz, int N, int tiles, const PairTab* __restrict__ ptab) {
+  const int pair = blockIdx.y, B = gridDim.y;
+  auto trips = [&](int l) { return !(__uint_as_float(lz.fstat[((size_t)l * B + pair) * kPvStatStride]) <= lz.thr2[l]); };
+  if (!trips(lz.layer)) return;
+  for (int l = 0; l < lz.layer; ++l)
+    if (trips(l)) return;
+  const int gy = (tiles + 4 * kJPerWave - 1) / (4 * kJPerWave);
+  for (int w = blockIdx.x; w < tiles * gy; w += gridDim.x)
+    compat_build_body<0>(tr, w % tiles, w / tiles, pair, lz.pts8, lz.c_dense, N, tiles, lz.inv_sig2, ptab);
+}
+
 // NP = 3: the parity kernel.  NP = 1: the throughput numerics mode (gmf_set_tuning "precision" = 1) - every product of the layer's
 // linear part on the high fp16 planes only (a third of the MFMAs, half the LDS reads); LayerNorms, softmax, GELU, biases and
 // residuals stay fp32.  NOT within the parity gate.
@@ -1028,14 +1041,16 @@ k_linear_h2(const float* __restrict__ f_in, const float* __restrict__ front_wst,
             const float* __restrict__ ff_wst, const float* __restrict__ ff_vec, float* __restrict__ q_out,
             float* __restrict__ k_out, float* __restrict__ v_out, float* __restrict__ x2_out, int N, int tiles, int T,
             int ttiles, const PairTab* __restrict__ ptab, unsigned* __restrict__ v_scale, const PvGuard guard,
-            const float* __restrict__ kvf_wst, const float* __restrict__ kvf_bias) {
+            const float* __restrict__ kvf_wst, const float* __restrict__ kvf_bias, const LazyCompat lazy) {
   __shared__ __attribute__((aligned(16))) float lds[kLinLdsFloats];
+  static_assert(kLinLdsFloats >= kCompatLdsFloats, "the compat role's transposes fit the kernel's LDS");
+  if (blockIdx.z == 1) return compat_tripped_role(lds, lazy, N, tiles, ptab);      // ("compat_16": grid z = 2 only with that role)
   tail_priority(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
   linear_h2_body<0, NP, QSKIP, KVF>(lds, f_in, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst, ff_vec, q_out, k_out, v_out, x2_out, N,
                                     tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias);
 }
 
-// grid (ceil(tiles / 4), B, 2): blockIdx.z = 0 the Q'/K/V role, 1 the Fusion-2 role of the same 128 rows
+// grid (ceil(tiles / 4), B, 2): blockIdx.z = 0 the Q'/K/V role, 1 the Fusion-2 role of the same 128 rows (2, "compat_16": compat_tripped_role)
 template <bool KVF>
 __global__ void __launch_bounds__(256, 2)
 k_linear_roles(const float* __restrict__ f_in, const float* __restrict__ front_wst, const float* __restrict__ front_vec,
@@ -1043,8 +1058,9 @@ k_linear_roles(const float* __restrict__ f_in, const float* __restrict__ front_w
                const float* __restrict__ ff_wst, const float* __restrict__ ff_vec, float* __restrict__ q_out,
                float* __restrict__ k_out, float* __restrict__ v_out, float* __restrict__ x2_out, int N, int tiles, int T,
                int ttiles, unsigned* __restrict__ v_scale, const PvGuard guard, const PairTab* __restrict__ ptab,   // [r5] ragged batches too
-               const float* __restrict__ kvf_wst, const float* __restrict__ kvf_bias) {
+               const float* __restrict__ kvf_wst, const float* __restrict__ kvf_bias, const LazyCompat lazy) {
   __shared__ __attribute__((aligned(16))) float lds[kLinLdsFloats];
+  if (blockIdx.z == 2) return compat_tripped_role(lds, lazy, N, tiles, ptab);
   if (blockIdx.z == 0)
     linear_h2_body<1, 3, false, KVF>(lds, f_in, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst, ff_vec, q_out, k_out, v_out, x2_out, N,
                                      tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias);
@@ -1102,29 +1118,30 @@ hipError_t launch_linear_h2(bool roles, const float* f, const float* front_wst, 
                             const float* attn_wst, const float* attn_vec, const float* ff_wst, const float* ff_vec, float* q,
                             float* k, float* v, float* x2, int B, int N, int tiles, int T, int ttiles, hipStream_t s,
                             bool one_product, const PairTab* ptab, unsigned* v_scale, PvGuard guard, const float* kvf_wst,
-                            const float* kvf_bias) {
+                            const float* kvf_bias, LazyCompat lazy) {
   const float* const none = nullptr;
+  const int lz = lazy.c_dense ? 1 : 0;             // one more set of workgroups: the lazily built fp32 compat cache
   if (roles && kvf_wst)
-    hipLaunchKernelGGL(k_linear_roles<true>, tgrid(tiles, B, 2), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec,
-                       ff_wst, ff_vec, q, k, v, x2, N, tiles, T, ttiles, v_scale, guard, ptab, kvf_wst, kvf_bias);
+    hipLaunchKernelGGL(k_linear_roles<true>, tgrid(tiles, B, 2 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec,
+                       ff_wst, ff_vec, q, k, v, x2, N, tiles, T, ttiles, v_scale, guard, ptab, kvf_wst, kvf_bias, lazy);
   else if (roles)
-    hipLaunchKernelGGL(k_linear_roles<false>, tgrid(tiles, B, 2), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec,
-                       ff_wst, ff_vec, q, k, v, x2, N, tiles, T, ttiles, v_scale, guard, ptab, none, none);
+    hipLaunchKernelGGL(k_linear_roles<false>, tgrid(tiles, B, 2 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec,
+                       ff_wst, ff_vec, q, k, v, x2, N, tiles, T, ttiles, v_scale, guard, ptab, none, none, lazy);
   else if (kvf_wst && !q)                          // "kv_fold": K and V images of f, Fusion-2; q~ in the attention prologue
-    hipLaunchKernelGGL((k_linear_h2<3, true, true>), tgrid(tiles, B), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias);
+    hipLaunchKernelGGL((k_linear_h2<3, true, true>), tgrid(tiles, B, 1 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
+                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias, lazy);
   else if (kvf_wst)                                // ... with a q~ image
-    hipLaunchKernelGGL((k_linear_h2<3, false, true>), tgrid(tiles, B), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias);
+    hipLaunchKernelGGL((k_linear_h2<3, false, true>), tgrid(tiles, B, 1 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
+                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias, lazy);
   else if (one_product)                            // throughput numerics mode: high planes only
-    hipLaunchKernelGGL(k_linear_h2<1>, tgrid(tiles, B), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none);
+    hipLaunchKernelGGL(k_linear_h2<1>, tgrid(tiles, B, 1 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
+                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none, lazy);
   else if (!q)                                     // [r4] no Q' image: the attention kernel projects its own (CompatCache::qf_img)
-    hipLaunchKernelGGL((k_linear_h2<3, true>), tgrid(tiles, B), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none);
+    hipLaunchKernelGGL((k_linear_h2<3, true>), tgrid(tiles, B, 1 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
+                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none, lazy);
   else
-    hipLaunchKernelGGL(k_linear_h2<3>, tgrid(tiles, B), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none);
+    hipLaunchKernelGGL(k_linear_h2<3>, tgrid(tiles, B, 1 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
+                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none, lazy);
   return hipGetLastError();
 }
 

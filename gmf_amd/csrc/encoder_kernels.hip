@@ -1300,7 +1300,10 @@ GMF_DEVINL bool attn_pv_on(const unsigned* __restrict__ v_scale, const PvGuard& 
   return pv_planes_on(v_scale, guard, ptab ? ptab[slot].ord : slot);
 }
 
-template <int NPROD, int CFMT, bool PVF8 = false, bool FOLD = false>
+// CFB: the cache format of the guarded (three-product) body.  CFB = CFMT: one cache for both bodies.  CFMT = 2, CFB = 0 is the guarded
+// 16-bit cache ("compat_16"): the branch that picks the fp8 body picks the 16-bit cache with it, and a pair the
+// guard trips streams the exact fp32 cache `c_dense_fb`, which the layer's linear launch filled for it (compat_tripped_role).
+template <int NPROD, int CFMT, bool PVF8 = false, bool FOLD = false, int CFB = CFMT>
 __global__ void __launch_bounds__(256, 2)
 k_scattn_h2p(const float* __restrict__ q_img, const float* __restrict__ k_img, const float* __restrict__ v_img,
              const float* __restrict__ fus, const float* __restrict__ wst, const float* __restrict__ vecs,
@@ -1308,7 +1311,9 @@ k_scattn_h2p(const float* __restrict__ q_img, const float* __restrict__ k_img, c
              int n_items, int n_full, int ksplits, float* __restrict__ part_o, float* __restrict__ part_ml,
              const float* __restrict__ next_wst, const float* __restrict__ next_bias, const PairTab* __restrict__ ptab,
              const unsigned* __restrict__ v_scale, const float* qf_img, const float* __restrict__ qw_wst,
-             const float* __restrict__ qw_bias, const PvGuard guard, const float* __restrict__ kvf_vec) {
+             const float* __restrict__ qw_bias, const PvGuard guard, const float* __restrict__ kvf_vec,
+             const float* __restrict__ c_dense_fb) {
+  static_assert(CFB == CFMT || PVF8, "a second cache format belongs to the guarded fp8 form");
   __shared__ __attribute__((aligned(16))) float lds[4 * kStageFloats];
   tail_priority(blockIdx.x, gridDim.x);
   if (!PVF8 || attn_pv_on(v_scale, guard, blockIdx.x, n_items, n_full, ksplits, wgs_per_pair, ptab))
@@ -1316,9 +1321,10 @@ k_scattn_h2p(const float* __restrict__ q_img, const float* __restrict__ k_img, c
                                                 n_full, ksplits, part_o, part_ml, next_wst, next_bias, ptab, v_scale, qf_img, qw_wst, qw_bias,
                                                 guard.stat_next, kvf_vec);
   else
-    scattn_h2p_body<NPROD, CFMT, 4, false, FOLD>(lds, blockIdx.x, q_img, k_img, v_img, fus, wst, vecs, out, N, tiles, wgs_per_pair, c_dense, n_items,
-                                                 n_full, ksplits, part_o, part_ml, next_wst, next_bias, ptab, nullptr, qf_img, qw_wst, qw_bias,
-                                                 guard.stat_next, kvf_vec);
+    scattn_h2p_body<NPROD, CFB, 4, false, FOLD>(lds, blockIdx.x, q_img, k_img, v_img, fus, wst, vecs, out, N, tiles, wgs_per_pair,
+                                                CFB == CFMT ? c_dense : c_dense_fb, n_items,
+                                                n_full, ksplits, part_o, part_ml, next_wst, next_bias, ptab, nullptr, qf_img, qw_wst, qw_bias,
+                                                guard.stat_next, kvf_vec);
 }
 
 // =========================================================================================
@@ -2400,30 +2406,28 @@ hipError_t launch_scattn_h2p(const float* q, const float* k, const float* v, con
   const int per_xcd = (W >> 3) + ((W & 7) ? 1 : 0);
   const int max_tail = std::max(0, per_xcd - n_full);
   const dim3 grid(8 * (std::min(n_full, per_xcd) + max_tail * ksplits));
+  // every form of k_scattn_h2p takes the same arguments; `pvf8`: the V image carries e4m3 cross planes (the guard decides per pair)
+  auto go = [&](auto kern, bool pvf8) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense, W, n_full, ksplits,
+                       cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, pvf8 ? (const unsigned*)cc.v_scale : nullptr, cc.qf_img,
+                       cc.qw_wst, cc.qw_bias, pvf8 ? cc.guard : PvGuard{}, cc.kvf_vec, cc.dense_fb);
+  };
+  const bool pvf8 = cc.v_scale != nullptr, fold = cc.kvf_vec != nullptr;   // (default: V with e4m3 cross planes; "kv_fold": keys = values = f)
   if (cc.half && max_tail == 0)   // throughput numerics mode, whole items only: the three-tiles-in-flight form
     hipLaunchKernelGGL(k_scattn_fast, dim3(8 * per_xcd), dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense, W,
                        cc.next_wst_h2, cc.next_bias);
   else if (cc.half)  // ... with a split tail: one fp16 product, c streamed as fp16 (the cache was built that way)
-    hipLaunchKernelGGL((k_scattn_h2p<1, 1>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense, W,
-                       n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, PvGuard{}, (const float*)nullptr);
-  else if (cc.fmt == 2 && cc.v_scale)   // parity arithmetic, c streamed as 16-bit fixed point; fp8 cross products of P V
-    hipLaunchKernelGGL((k_scattn_h2p<3, 2, true>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
-                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, cc.v_scale, cc.qf_img, cc.qw_wst, cc.qw_bias, cc.guard, (const float*)nullptr);
+    go(k_scattn_h2p<1, 1>, false);
+  else if (cc.fmt == 2 && cc.dense_fb && pvf8)   // "compat_16": 16 bits where the guard lets the pair through, the exact fp32 cache where it trips
+    fold ? go(k_scattn_h2p<3, 2, true, true, 0>, true) : go(k_scattn_h2p<3, 2, true, false, 0>, true);
+  else if (cc.fmt == 2 && pvf8)   // parity arithmetic, c streamed as 16-bit fixed point by both bodies
+    fold ? go(k_scattn_h2p<3, 2, true, true>, true) : go(k_scattn_h2p<3, 2, true>, true);
   else if (cc.fmt == 2)
-    hipLaunchKernelGGL((k_scattn_h2p<3, 2>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
-                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, cc.qf_img, cc.qw_wst, cc.qw_bias, PvGuard{}, (const float*)nullptr);
-  else if (cc.kvf_vec && cc.v_scale)   // "kv_fold" (the plan grants it on the fp32 cache only): keys = values = f
-    hipLaunchKernelGGL((k_scattn_h2p<3, 0, true, true>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
-                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, cc.v_scale, cc.qf_img, cc.qw_wst, cc.qw_bias, cc.guard, cc.kvf_vec);
-  else if (cc.kvf_vec)
-    hipLaunchKernelGGL((k_scattn_h2p<3, 0, false, true>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
-                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, cc.qf_img, cc.qw_wst, cc.qw_bias, PvGuard{}, cc.kvf_vec);
-  else if (cc.v_scale)    // the default: V image with e4m3 cross planes (k_linear_h2 wrote it that way)
-    hipLaunchKernelGGL((k_scattn_h2p<3, 0, true>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
-                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, cc.v_scale, cc.qf_img, cc.qw_wst, cc.qw_bias, cc.guard, (const float*)nullptr);
+    fold ? go(k_scattn_h2p<3, 2, false, true>, false) : go(k_scattn_h2p<3, 2>, false);
+  else if (pvf8)    // the fp32 cache
+    fold ? go(k_scattn_h2p<3, 0, true, true>, true) : go(k_scattn_h2p<3, 0, true>, true);
   else
-    hipLaunchKernelGGL((k_scattn_h2p<3, 0>), grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense,
-                       W, n_full, ksplits, cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, (const unsigned*)nullptr, cc.qf_img, cc.qw_wst, cc.qw_bias, PvGuard{}, (const float*)nullptr);
+    fold ? go(k_scattn_h2p<3, 0, false, true>, false) : go(k_scattn_h2p<3, 0>, false);
   if (max_tail > 0)
     hipLaunchKernelGGL(k_scattn_merge, dim3(8 * max_tail), dim3(256), 0, s, cc.part_o, cc.part_ml, fus, cc.tail_wst_h2, vecs, out,
                        tiles, wpp, W, n_full, ksplits, cc.next_wst_h2, cc.next_bias, (const float*)nullptr, 0,

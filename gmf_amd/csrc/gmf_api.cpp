@@ -315,9 +315,14 @@ int gmf_set_tuning(gmf_handle* h, const char* name, int value) {
     t.pv_fp8 = value;
     return GMF_OK;
   }
-  if (std::strcmp(name, "compat_format") == 0) {       // element format of the compat cache: 0 = fp32 (default), 2 = 16-bit fixed point (opt-in)
+  if (std::strcmp(name, "compat_format") == 0) {       // element format of the compat cache: 0 = the plan's ("compat_16"; default), 2 = 16-bit fixed point for everyone (opt-in)
     GMF_REQUIRE(value == 0 || value == 2, GMF_ERR_BAD_ARG, "set_tuning: compat_format must be 0 (fp32) or 2 (16-bit fixed point of c)");
     t.compat_format = value;
+    return GMF_OK;
+  }
+  if (std::strcmp(name, "compat_16") == 0) {           // 1 = large grids: the 16-bit compat cache under the "pv_fp8" guard (default), 2 = every grid of the two-launch plan, 0 = fp32 for everyone
+    GMF_REQUIRE(value >= 0 && value <= 2, GMF_ERR_BAD_ARG, "set_tuning: compat_16 must be 0, 1 or 2");
+    t.compat_16 = value;
     return GMF_OK;
   }
   if (std::strcmp(name, "precision") == 0) {           // 0 = parity numerics (default), 1 / 2 = throughput numerics (NOT within 1e-4)
@@ -349,7 +354,7 @@ int gmf_get_tuning(gmf_handle* h, const char* name, int* value) {
       {"fused_linear", t.fused_linear ? 1 : 0}, {"compat_cache", t.use_cache ? 1 : 0}, {"conv_lds_patch", t.conv_patch}, {"conv_small_grid", t.conv_small ? 1 : 0}, {"small_prologue_roles", t.small_prologue ? 1 : 0}, {"small_fattn_tile", t.small_fattn_tile ? 1 : 0},
       {"nms_binned", t.nms_binned}, {"topk_select", t.topk_select ? 1 : 0}, {"wide_attn_tile", t.wide_attn_tile ? 1 : 0},
       {"small_merge_tile", t.small_merge_tile ? 1 : 0}, {"mid_grid_roles", t.mid_grid_roles}, {"pv_fp8", t.pv_fp8}, {"q_in_attention", t.q_in_attention ? 1 : 0},
-      {"kv_fold", t.kv_fold ? 1 : 0}, {"compat_format", t.compat_format}, {"precision", t.precision}, {"spectral_col_splits", t.spectral_col_splits},
+      {"kv_fold", t.kv_fold ? 1 : 0}, {"compat_format", t.compat_format}, {"compat_16", t.compat_16}, {"precision", t.precision}, {"spectral_col_splits", t.spectral_col_splits},
       {"clique_local_rows", t.clique_local_rows}};
   for (const auto& e : tab) {
     if (std::strcmp(name, e.name) == 0) { *value = e.v; return GMF_OK; }
@@ -582,10 +587,12 @@ struct EncoderPlan {
   bool roles = false;        // k_linear_h2 as two workgroup roles per row block
   bool q_in_attn = false;    // no Q' image: the attention projects its own (CompatCache::qf_img)
   bool kv_fold = false;      // keys = values = f: no K / V projections, composed weights (gmf_encoder_weights::kv_fold)
+  bool c16_guard = false;    // "compat_16": fmt = 2 for the pairs and layers the guard lets through, a lazily built fp32 cache for the rest
   bool v_fp8 = false;        // V carries e4m3 cross planes (CompatCache::v_scale) ...
   bool guard = false;        // ... chosen per pair and layer on the device (PvGuard)
   bool clear_stats = false;  // the key-point packing clears the guard's statistics
   size_t act = 0, tok = 0, cache_floats = 0;   // floats of an activation image, a token image, the cache
+  size_t cache_fb_floats = 0;                  // ... and of the guarded form's fp32 cache (c16_guard)
 };
 
 // min_tiles > 0: a ragged batch whose smallest pair has that many tiles.  dense: the caller passes the attention matrix.
@@ -608,7 +615,8 @@ static EncoderPlan plan_encoder(const gmf::Tuning& t, const gmf_encoder_weights*
   // (variant 18) is the cache's only reader.  4 KiB per pair of 32-row tiles as fp32, 2 KiB in the 16-bit formats
   const int fmt = half ? 1 : t.scattn_variant == 18 ? t.compat_format : 0;
   const size_t cache_floats = (size_t)B * tiles * tiles * (fmt ? 512 : 1024);
-  p.cache = h2 && L > 1 && t.use_cache && cache_floats * 4 <= ((size_t)96 << 30);
+  const size_t cache_cap = (size_t)96 << 30;      // above it the cache is not used
+  p.cache = h2 && L > 1 && t.use_cache && cache_floats * 4 <= cache_cap;
   const bool fused = fusable && p.cache;
   if (p.cache) { p.cache_floats = cache_floats; p.fmt = fmt; p.half = half; }
   p.one_product = p.half && t.precision == 2;
@@ -634,22 +642,41 @@ static EncoderPlan plan_encoder(const gmf::Tuning& t, const gmf_encoder_weights*
   // [r4] Q' in the attention kernel's prologue (parity arithmetic of the pipelined kernel; not with the linear kernel as two roles,
   // whose Q'/K/V role writes the image): k_linear_h2 then projects K and V only
   p.q_in_attn = p.form == EncoderPlan::kLinear && t.q_in_attention && !p.half && !p.roles;
-  // "kv_fold": the two-launch plan with the parity numerics of the pipelined kernel on the fp32 cache - uniform or ragged, the linear
-  // kernel whole or as two roles, Q' in the attention prologue or as an image (one rule for all of them: the forms that are compared
-  // bit for bit fold together).  Everything else - small grids, "precision" 1 / 2, the 16-bit cache, weights without the composed
-  // block - runs the unfolded form
-  p.kv_fold = t.kv_fold && p.form == EncoderPlan::kLinear && p.pipelined && !p.half && p.fmt == 0 && w->kv_fold != nullptr;
+  p.f1_h2 = h2 && w->f1_ctx_wst_h2 && w->f1_attn_wst_h2 && w->f1_ff_wst_h2;
+  const bool pro_grid = t.small_prologue && fused && p.f1_h2 && W < 256;    // grids whose prologue runs as roles (below; fp32 cache only)
+  // "compat_16" (the default): on the two-launch plan with the parity numerics of the pipelined kernel the cache format
+  // follows the fp8 decision - uniform or ragged, the linear kernel whole or as two roles, Q' in the attention prologue or as an image,
+  // folded or not.  "pv_fp8" = 1 with thresholds: 16 bits where the guard lets a pair's layer through, and a second, fp32 cache that the
+  // device fills for the pairs that trip (c16_guard); "pv_fp8" = 2: 16 bits for everyone, as the fp8 products; three products ("pv_fp8"
+  // = 0, pv_guard = NULL) keep fp32.  The size cap counts both caches; beyond it the plan is the fp32 one.  Everything else - small
+  // grids, "precision" 1 / 2 - keeps what it has: the default asks for 256 row blocks, as the two-launch plan of uniform batches does
+  // (a smaller ragged batch on that plan keeps the fp32 cache and the role prologue, whatever its knobs say); "compat_16" = 2 takes
+  // every grid of the two-launch plan, with the prologue as kernels of its own (what the tests of small shapes use)
+  if ((t.compat_16 == 2 || (t.compat_16 == 1 && W >= 256)) && p.form == EncoderPlan::kLinear && p.pipelined && !p.half && p.fmt == 0 &&
+      (t.pv_fp8 == 2 || (t.pv_fp8 == 1 && w->pv_guard))) {
+    const size_t fb = t.pv_fp8 == 1 ? cache_floats : 0;
+    if ((cache_floats / 2 + fb) * 4 <= cache_cap) {
+      p.fmt = 2;
+      p.cache_floats = cache_floats / 2;
+      p.cache_fb_floats = fb;
+      p.c16_guard = fb != 0;
+    }
+  }
+  // "kv_fold": the two-launch plan with the parity numerics of the pipelined kernel - uniform or ragged, the linear kernel whole or as
+  // two roles, Q' in the attention prologue or as an image, either cache format (one rule for all of them: the forms that are compared
+  // bit for bit fold together).  Everything else - small grids, "precision" 1 / 2, weights without the composed block - runs the
+  // unfolded form
+  p.kv_fold = t.kv_fold && p.form == EncoderPlan::kLinear && p.pipelined && !p.half && w->kv_fold != nullptr;
   // parity arithmetic: V with e4m3 cross planes for the pv_fp8 form of every attention kernel of the fused forms (a weights block
   // without thresholds, pv_guard = NULL, gets the three-product form under the guarded default, never the unguarded one).  [r5]
   // "pv_fp8" = 1: guarded per pair and layer on the device; the key-point packing clears the statistics (a superset of the readers)
   p.v_fp8 = fused && !p.half && (t.pv_fp8 == 2 || (t.pv_fp8 == 1 && w->pv_guard));
   p.clear_stats = fused && t.pv_fp8 == 1 && w->pv_guard;
   p.guard = p.clear_stats && !p.half;
-  p.f1_h2 = h2 && w->f1_ctx_wst_h2 && w->f1_attn_wst_h2 && w->f1_ff_wst_h2;
   // [r5] small grids: the prologue is two independent chains of few-workgroup kernels - image side (Fusion-1 context, cross-attention,
   // feed-forward) and point side (key points, compat cache, layer 0 + first PointCN).  Three launches carry one link of each
   // (k_pro_*, encoder_h2.hip): the point side runs under the image side instead of behind it.  Same bodies: bit-identical.
-  p.prologue = t.small_prologue && fused && p.f1_h2 && p.fmt == 0 && W < 256;
+  p.prologue = pro_grid && p.fmt == 0;
   return p;
 }
 
@@ -767,8 +794,8 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
               "compat cache, \"fused_linear\" = 1, \"scattn_variant\" = 18)");
   const size_t act = p.act, tok = p.tok;
   char* dtab;
-  float *featA, *featB, *f, *q, *k, *v, *x1, *x2, *pts8, *pimg, *qimg, *f1ctx, *x1t, *imgfeat, *ctxall, *c_dense, *ff_part, *part_o,
-      *part_ml;
+  float *featA, *featB, *f, *q, *k, *v, *x1, *x2, *pts8, *pimg, *qimg, *f1ctx, *x1t, *imgfeat, *ctxall, *c_dense, *c_dense_fb, *ff_part,
+      *part_o, *part_ml;
   unsigned *v_scale, *fstat;
   if (int rc = arena_carve(h, {arena_buf(dtab, tab.bytes()), arena_buf(featA, act), arena_buf(featB, act), arena_buf(f, act),
                                arena_buf(q, act), arena_buf(k, act), arena_buf(v, act), arena_buf(x1, act), arena_buf(x2, act),
@@ -780,6 +807,7 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
                                // "pv_fp8" guard: [layer][pair] max row |f_l|^2 (float bits), one 128-byte line per pair
                                arena_buf(fstat, (size_t)(L + 1) * B * gmf::kPvStatStride),
                                arena_buf(c_dense, p.cache_floats),
+                               arena_buf(c_dense_fb, p.cache_fb_floats),      // "compat_16": the fp32 cache of the pairs the guard trips
                                // small grids: feed-forward partials beside the attention's
                                arena_buf(ff_part, p.max_splits == 8 ? 8 * act : 0),
                                arena_buf(part_o, p.max_splits * act),
@@ -790,6 +818,7 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
   gmf::CompatCache cc{c_dense, nullptr, part_o, part_ml};
   cc.half = p.half;
   cc.fmt = p.fmt;
+  cc.dense_fb = p.c16_guard ? c_dense_fb : nullptr;
   cc.ptab = ptab;
   cc.v_scale = p.v_fp8 ? v_scale : nullptr;
   unsigned* const zero_words = p.clear_stats ? fstat : nullptr;
@@ -873,8 +902,12 @@ static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, con
           cc.kvf_vec = kvf_vecs + kC;
           tail_vecs = kvf_vecs + 3 * kC;
         }
+        // "compat_16": a pair that trips the guard at this layer for the first time gets its fp32 cache from one more role of this
+        // launch (fstat[l] is complete: the front kernel / the previous layer's attention and merge raised it)
+        gmf::LazyCompat lazy;
+        if (p.c16_guard) lazy = gmf::LazyCompat{c_dense_fb, pts8, fstat, w->pv_guard, l, 1.0f / (w->sigma_d * w->sigma_d)};
         GMF_HIP(gmf::launch_linear_h2(p.roles, f, fw, fv, ctx_l, aw, av, ffw, ffv, p.q_in_attn ? nullptr : q, k, v, x2, B, N, tiles, T, tt,
-                                      st, p.one_product, ptab, cc.v_scale, cc.guard, kvf, kvf_vecs));
+                                      st, p.one_product, ptab, cc.v_scale, cc.guard, kvf, kvf_vecs, lazy));
       } else if (p.form == EncoderPlan::kSmall3) {
         // three launches: {Q' | K | V | cross-attention} -> {key-split attention | hidden-split feed-forward} -> merge
         GMF_HIP(gmf::launch_small_front_fattn(f, fw, fv, ctx_l, aw, av, q, k, v, x1, B, N, tiles, T, tt, st, cc.v_scale, cc.guard,

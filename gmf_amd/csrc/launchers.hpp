@@ -49,6 +49,24 @@ struct CompatCache {
   // "kv_fold" (EncoderPlan::kv_fold): non-null = the K and V images hold the layer input f, tail_wst_h2 / the epilogue's vectors / qw_* are
   // the composed weights of gmf_encoder_weights::kv_fold, qf_img is always the layer's f image, and these are Wq'^T bk [128] | bk . bq'
   const float* kvf_vec = nullptr;
+  // "compat_16" (EncoderPlan::c16_guard): non-null = `dense` holds the 16-bit cache (fmt = 2) for the pairs the guard lets through at
+  // this layer, and this is the exact fp32 cache of the pairs it trips (the layer's linear launch fills it: LazyCompat)
+  const float* dense_fb = nullptr;
+};
+
+// "compat_16": the exact cache of the guarded 16-bit form, built lazily by one more workgroup role of the layer's linear launch (the
+// launch between the attention that completes the layer's statistic and the attention that streams the cache): ceil(tiles / 4)
+// workgroups per pair, which return at once unless the pair trips the guard at `layer` and tripped it at no earlier layer - then
+// they write the pair's fp32 tiles, the bytes k_compat_build<0> writes, once per forward.  Both facts come from the words every
+// other kernel of the guard compares (the comparison of pv_planes_on, so a NaN statistic trips): no flag, no atomic, no order
+// between workgroups.
+struct LazyCompat {
+  float* c_dense = nullptr;         // the fp32 cache [B, tiles, tiles, 1024]; null: no such role in the launch
+  const float* pts8 = nullptr;      // the packed key points (k_pack_pts8)
+  const unsigned* fstat = nullptr;  // [layer][B][kPvStatStride] the guard's statistics from layer 0 on
+  const float* thr2 = nullptr;      // [layer] the guard's thresholds from layer 0 on
+  int layer = 0;
+  float inv_sig2 = 0.f;
 };
 
 // Per-handle tuning knobs (gmf_set_tuning).  Every value selects between forms that compute the same result up to
@@ -81,10 +99,14 @@ struct Tuning {
   int pv_fp8 = 1;            // parity arithmetic of the default path: the two cross products of O += P V on the block-scaled fp8 matrix
                              // pipe (scattn_h2p_body<3, *, 4, true>).  1 = guarded per pair and layer on the device
                              // (PvGuard), 2 = unconditionally, 0 = all three products on the f16 pipe
-  int compat_format = 0;     // element format of the compat cache on the cached, pipelined path: 0 = fp32 (default); 2 = 16-bit fixed
-                             // point, rint(65535 c): half the attention's c stream and half the build, -4 % per step, absolute
-                             // error <= 7.6e-6 on c.  Measured: inside the parity contract on 3DMatch-shape
-                             // inputs, 4-8x the reference's own fp32 noise on KITTI-shape inputs - so it is opt-in, not the default
+  int compat_format = 0;     // element format of the compat cache on the cached, pipelined path: 0 = the plan's choice ("compat_16"); 2 =
+                             // 16-bit fixed point, rint(65535 c), UNCONDITIONALLY: half the attention's c stream and half the build,
+                             // absolute error <= 7.6e-6 on c.  Measured: inside the parity contract on 3DMatch-shape
+                             // inputs, 4-8x the reference's own fp32 noise on ill-conditioned KITTI-shape inputs - so it is opt-in
+  int compat_16 = 1;         // two-launch plan, parity numerics, the guarded fp8 form: the 16-bit cache under the "pv_fp8" guard - per pair
+                             // and layer, 16 bits where the guard lets the fp8 products through, the exact fp32 cache (built on the device
+                             // for the pairs that trip, once per forward) where it does not.  1 = on grids of 256 row blocks and more
+                             // (default), 2 = on every grid of that plan, 0 = fp32 for everyone
   int precision = 0;         // NOT rounding-equivalent: 0 = parity numerics (fp32-equivalent split-fp16 products, the default);
                              // 1 = throughput numerics: the spatial-consistency attention multiplies plain
                              // fp16 operands (one product, fp32 accumulation) and streams c as fp16 - outside the 1e-4 gate
@@ -138,7 +160,7 @@ hipError_t launch_linear_h2(bool roles, const float* f, const float* front_wst, 
                             const float* attn_wst, const float* attn_vec, const float* ff_wst, const float* ff_vec, float* q,
                             float* k, float* v, float* x2, int B, int N, int tiles, int T, int ttiles, hipStream_t s, bool one_product = false,
                             const PairTab* ptab = nullptr, unsigned* v_scale = nullptr, PvGuard guard = {}, const float* kvf_wst = nullptr,
-                            const float* kvf_bias = nullptr);   // kvf_*: "kv_fold" - the 4 stages of Wk^T Wq' and Wk^T bq'; K and V become images of f
+                            const float* kvf_bias = nullptr, LazyCompat lazy = {});   // kvf_*: "kv_fold" - the 4 stages of Wk^T Wq' and Wk^T bq'; K and V become images of f
 // small grids: three launches per layer (k_small_front_fattn | k_small_attn_ff | k_scattn_merge)
 hipError_t launch_small_front_fattn(const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
                                     const float* attn_wst, const float* attn_vec, float* q, float* k, float* v, float* x1, int B,

@@ -118,10 +118,16 @@ int gmf_set_sigma_device(gmf_handle* h, const float* sigma_dev);
  *   "compat_cache"      : 1 = build the compat matrix once per batch (default), 0 = recompute c_ij in the attention kernel
  *                         (what the library does by itself when the cache would exceed 96 GB); 0 implies the
  *                         non-pipelined kernel.
- *   "compat_format"     : element format of the compat cache on the pipelined path: 0 = fp32 (default); 2 = 16-bit fixed point
- *                         rint(65535 c) - half the cache, half its stream, -4 % per step, |dc| <= 7.6e-6.  Opt-in: measured inside
- *                         the 1e-4 gate on 3DMatch-shape inputs, but 4-8x the reference's own fp32 noise on KITTI-shape inputs
- *                         (profiles/r03_compat_formats.txt).
+ *   "compat_format"     : element format of the compat cache on the pipelined path: 0 = the plan's choice ("compat_16"; default); 2 =
+ *                         16-bit fixed point rint(65535 c) UNCONDITIONALLY - half the cache, half its stream, |dc| <= 7.6e-6.  Opt-in:
+ *                         measured inside the 1e-4 gate on 3DMatch-shape inputs, but 4-8x the reference's own fp32 noise on
+ *                         ill-conditioned KITTI-shape inputs (profiles/r03_compat_formats.txt).
+ *   "compat_16"         : 1 = on the two-launch plan of large grids (parity numerics) the compat cache is 16-bit fixed point under the
+ *                         "pv_fp8" guard (default): per pair and layer the attention streams 16 bits where the guard lets the fp8
+ *                         products through, and an exact fp32 cache - built on the device for the pairs that trip, once per forward -
+ *                         where it does not ("pv_fp8" = 2: 16 bits for everyone; "pv_fp8" = 0 or pv_guard = NULL: fp32).  The
+ *                         workspace holds both caches.  1 applies to grids of 256 row blocks and more, 2 to every grid of the
+ *                         two-launch plan; 0 = the fp32 cache for everyone: the earlier results, bit for bit.
  *   "pv_fp8"            : parity arithmetic of the default path (scattn_variant 18, fused_linear 1): the two CROSS products of the
  *                         attention's O += P V (P_hi V_lo + P_lo V_hi) on the block-scaled fp8 matrix pipe - one
  *                         v_mfma_scale_f32_32x32x64_f8f6f4 per feature block and key tile, e4m3 operands, one scale per (feature,
@@ -164,7 +170,7 @@ int gmf_set_sigma_device(gmf_handle* h, const float* sigma_dev);
  *   "topk_select"       : 1 = radix select of the S seeds (default), 0 = full bitonic sort.
  *   "q_in_attention"    : [ABI 4] 1 = on large grids every attention workgroup projects its own Q' in its prologue (default; PointDSC.py:56),
  *                         0 = the linear kernel writes a Q' image.  Bit-identical results.
- *   "kv_fold"           : 1 = on the two-launch plan of large grids (parity numerics, fp32 compat cache) the attention's key and value
+ *   "kv_fold"           : 1 = on the two-launch plan of large grids (parity numerics, either compat cache format) the attention's key and value
  *                         tiles are the layer input f itself: projection_k is composed into the query side, projection_v into
  *                         fc_message's first layer (gmf_encoder_weights::kv_fold; PointDSC.py:56-64; default).  Same guard rule as
  *                         "pv_fp8".  0 = the K and V projections are computed: the unfolded code, bit for bit.  The staged entry
