@@ -1,4 +1,4 @@
-// Private to the C-ABI translation units (gmf_api.cpp, gmf_api_train.cpp): the handle, the workspace arena, the ring of
+// Private to the C-ABI translation units (gmf_api.cpp, gmf_api_encoder.cpp, gmf_api_train.cpp): the handle, the workspace arena, the ring of
 // pinned host-table slots and the status helpers.  Not installed; the public interface is include/gmf_hip.h.
 #pragma once
 #include "../../include/gmf_hip.h"
@@ -49,9 +49,6 @@ struct gmf_handle {
 };
 
 
-constexpr int kC = 128;
-constexpr size_t kTileFloats = 32 * kC;
-
 inline int fail(gmf_handle* h, int code, const std::string& msg) {
   if (h) h->err = msg;
   return code;
@@ -71,6 +68,14 @@ inline int hip_fail(gmf_handle* h, hipError_t e, const char* where) {
   do {                                                        \
     if (!(cond)) return fail(h, code, std::string("gmf: ") + msg); \
   } while (0)
+
+// the sizes of a ragged batch (pair_plan.hpp), checked before the call takes a ring slot for its table
+inline int check_ragged_sizes(gmf_handle* h, const int* n_points, int B) {
+  const gmf::PairPlanStatus bad = gmf::check_pair_sizes(n_points, B);
+  GMF_REQUIRE(bad != gmf::kPairPlanEmptyPair, GMF_ERR_UNSUPPORTED_SHAPE, "ragged batch: every pair needs at least one correspondence");
+  GMF_REQUIRE(bad != gmf::kPairPlanTooManyRows, GMF_ERR_UNSUPPORTED_SHAPE, "ragged batch: more than 2^31 rows");
+  return GMF_OK;
+}
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -155,7 +160,6 @@ inline int ring_upload(gmf_handle* h, const RingTaken& t, void* dst, hipStream_t
 }
 
 inline hipStream_t S(gmf_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
-inline int tiles_of(int n) { return (n + 31) / 32; }
 
 // Entered by every entry point after its argument checks: takes the handle's lock, makes the handle's device current for the
 // duration of the call and restores the caller's device afterwards, and orders this call's stream behind the previous

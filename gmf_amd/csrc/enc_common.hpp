@@ -403,7 +403,7 @@ constexpr int kJPerWave = 8;
 // c is exactly symmetric (the squared differences do not see the sign of s_i - s_j), so only tiles J >= I are
 // evaluated; a tile with J > I is also written as tile (J, I) after a 32 x 32 transpose through a per-wave LDS buffer
 // (16 ds_write_b32 + 16 ds_read_b32 instead of 16 x ~26 vector instructions with two correctly rounded square roots).
-// FMT (CompatCache::fmt): 0 = fp32, 4 KiB per tile.  The 16-bit formats are 2 KiB per tile ([q2][lane][8 x 16 bit], registers
+// FMT (ForwardBuffers::fmt): 0 = fp32, 4 KiB per tile.  The 16-bit formats are 2 KiB per tile ([q2][lane][8 x 16 bit], registers
 // r = 8 q2 .. 8 q2 + 7) - half the stream of the 12 attention launches:
 //   1 = c as fp16 (the throughput numerics mode, gmf_set_tuning "precision" = 1);
 //   2 = c as 16-bit fixed point, u = rint(65535 c) (uniform absolute error <= 7.6e-6; gmf_set_tuning "compat_format" = 2, opt-in).

@@ -149,7 +149,7 @@ GMF_DEVINL void front_h2_body(float* lds, const int bx, const int pair, const in
 #pragma unroll
     for (int r = 0; r < 16; ++r) t[r] = fmaf(acc[r], kH2Inv, bv);
     if (active) {
-      if (v8) store_block_v8(v_out + toff, db, t, lane, vsw);     // the attention's pv_fp8 form (CompatCache::v_scale)
+      if (v8) store_block_v8(v_out + toff, db, t, lane, vsw);     // the attention's pv_fp8 form (ForwardBuffers::v_scale)
       else store_block_h2(v_out + toff, db, t, lane);
     }
   }
@@ -1104,7 +1104,7 @@ k_ff_reduce(const float* __restrict__ part, const float* __restrict__ x1, const 
 static inline dim3 tgrid(int tiles, int B, int sets = 1) { return dim3((tiles + kWavesPerWG - 1) / kWavesPerWG, B, sets); }
 
 hipError_t launch_front_h2(int mode, bool split, const float* in, const float* wst, const float* vecs, float* f, float* q, float* k,
-                           float* v, int B, int N, int tiles, hipStream_t s, const PairTab* ptab, unsigned* v_scale, PvGuard guard) {
+                           float* v, int B, int N, int tiles, const PairTab* ptab, unsigned* v_scale, PvGuard guard, hipStream_t s) {
   dim3 g = tgrid(tiles, B);
   if (split) g.z = 3;
   if (mode == 3) { g.z = 1; hipLaunchKernelGGL(k_front_h2<3>, g, dim3(256), 0, s, in, wst, vecs, f, q, k, v, N, tiles, ptab, v_scale, guard); }
@@ -1114,34 +1114,25 @@ hipError_t launch_front_h2(int mode, bool split, const float* in, const float* w
   return hipGetLastError();
 }
 
-hipError_t launch_linear_h2(bool roles, const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
-                            const float* attn_wst, const float* attn_vec, const float* ff_wst, const float* ff_vec, float* q,
-                            float* k, float* v, float* x2, int B, int N, int tiles, int T, int ttiles, hipStream_t s,
-                            bool one_product, const PairTab* ptab, unsigned* v_scale, PvGuard guard, const float* kvf_wst,
-                            const float* kvf_bias, LazyCompat lazy) {
-  const float* const none = nullptr;
-  const int lz = lazy.c_dense ? 1 : 0;             // one more set of workgroups: the lazily built fp32 compat cache
-  if (roles && kvf_wst)
-    hipLaunchKernelGGL(k_linear_roles<true>, tgrid(tiles, B, 2 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec,
-                       ff_wst, ff_vec, q, k, v, x2, N, tiles, T, ttiles, v_scale, guard, ptab, kvf_wst, kvf_bias, lazy);
-  else if (roles)
-    hipLaunchKernelGGL(k_linear_roles<false>, tgrid(tiles, B, 2 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec,
-                       ff_wst, ff_vec, q, k, v, x2, N, tiles, T, ttiles, v_scale, guard, ptab, none, none, lazy);
-  else if (kvf_wst && !q)                          // "kv_fold": K and V images of f, Fusion-2; q~ in the attention prologue
-    hipLaunchKernelGGL((k_linear_h2<3, true, true>), tgrid(tiles, B, 1 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias, lazy);
-  else if (kvf_wst)                                // ... with a q~ image
-    hipLaunchKernelGGL((k_linear_h2<3, false, true>), tgrid(tiles, B, 1 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, kvf_wst, kvf_bias, lazy);
-  else if (one_product)                            // throughput numerics mode: high planes only
-    hipLaunchKernelGGL(k_linear_h2<1>, tgrid(tiles, B, 1 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none, lazy);
-  else if (!q)                                     // [r4] no Q' image: the attention kernel projects its own (CompatCache::qf_img)
-    hipLaunchKernelGGL((k_linear_h2<3, true>), tgrid(tiles, B, 1 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none, lazy);
-  else
-    hipLaunchKernelGGL(k_linear_h2<3>, tgrid(tiles, B, 1 + lz), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec, ff_wst,
-                       ff_vec, q, k, v, x2, N, tiles, T, ttiles, ptab, v_scale, guard, none, none, lazy);
+hipError_t launch_linear_h2(bool roles, bool one_product, const float* f, const float* ctx_img, float* q, float* k, float* v, float* x2,
+                            int B, int N, int tiles, int T, int ttiles, const ForwardBuffers& fb, const LayerRun& lr, hipStream_t s) {
+  const LayerWeights& w = lr.w;
+  const bool fold = lr.kvf_vec != nullptr;        // "kv_fold": q~ from the block's four stages and Wk^T bq'; K and V images of f
+  const float *kvf_wst = fold ? w.kvf_q_wst : nullptr, *kvf_bias = fold ? w.kvf_q_bias : nullptr;
+  const int lz = lr.lazy.c_dense ? 1 : 0;          // one more set of workgroups: the lazily built fp32 compat cache
+  auto whole = [&](auto kern) {                    // every form of k_linear_h2 takes the same arguments
+    hipLaunchKernelGGL(kern, tgrid(tiles, B, 1 + lz), dim3(256), 0, s, f, w.front_wst_h2, w.front_vec, ctx_img, w.attn_wst_h2, w.attn_vec,
+                       w.ff_wst_h2, w.ff_vec, q, k, v, x2, N, tiles, T, ttiles, fb.ptab, fb.v_scale, lr.guard, kvf_wst, kvf_bias, lr.lazy);
+  };
+  auto two_roles = [&](auto kern) {
+    hipLaunchKernelGGL(kern, tgrid(tiles, B, 2 + lz), dim3(256), 0, s, f, w.front_wst_h2, w.front_vec, ctx_img, w.attn_wst_h2, w.attn_vec,
+                       w.ff_wst_h2, w.ff_vec, q, k, v, x2, N, tiles, T, ttiles, fb.v_scale, lr.guard, fb.ptab, kvf_wst, kvf_bias, lr.lazy);
+  };
+  if (roles) fold ? two_roles(k_linear_roles<true>) : two_roles(k_linear_roles<false>);
+  else if (fold) !q ? whole(k_linear_h2<3, true, true>) : whole(k_linear_h2<3, false, true>);   // q~ in the attention prologue | as an image
+  else if (one_product) whole(k_linear_h2<1>);     // throughput numerics mode: high planes only
+  else if (!q) whole(k_linear_h2<3, true>);        // [r4] no Q' image: the attention kernel projects its own (LayerRun::qf_img)
+  else whole(k_linear_h2<3>);
   return hipGetLastError();
 }
 
@@ -1207,15 +1198,13 @@ hipError_t launch_ff_reduce_h2(const float* part, const float* x1, const float* 
   return hipGetLastError();
 }
 
-hipError_t launch_small_front_fattn(const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
-                                    const float* attn_wst, const float* attn_vec, float* q, float* k, float* v, float* x1, int B,
-                                    int N, int tiles, int T, int ttiles, hipStream_t s, unsigned* v_scale, PvGuard guard, bool tile_role,
-                                    const PairTab* ptab) {
+hipError_t launch_small_front_fattn(bool tile_role, const float* f, const float* ctx_img, float* q, float* k, float* v, float* x1, int B,
+                                    int N, int tiles, int T, int ttiles, const ForwardBuffers& fb, const LayerRun& lr, hipStream_t s) {
   // [r5] the cross-attention role per query tile (its waves split the context tiles) wherever that leaves the chip room: the role's
   // workgroups quadruple, so up to 256 query tiles; beyond, one workgroup per four tiles as before
   const bool per_tile = tile_role && ttiles >= 2 && (long)tiles * B <= 256;
-  hipLaunchKernelGGL(k_small_front_fattn, tgrid(tiles, B, per_tile ? 7 : 4), dim3(256), 0, s, f, front_wst, front_vec, ctx_img, attn_wst, attn_vec,
-                     q, k, v, x1, N, tiles, T, ttiles, v_scale, guard, ptab);
+  hipLaunchKernelGGL(k_small_front_fattn, tgrid(tiles, B, per_tile ? 7 : 4), dim3(256), 0, s, f, lr.w.front_wst_h2, lr.w.front_vec, ctx_img,
+                     lr.w.attn_wst_h2, lr.w.attn_vec, q, k, v, x1, N, tiles, T, ttiles, fb.v_scale, lr.guard, fb.ptab);
   return hipGetLastError();
 }
 

@@ -677,9 +677,9 @@ GMF_DEVINL AttnItem attn_item(int L, int n_items, int n_full, int ksplits) {
 // fp16 planes of Q', K, V and of the probabilities are multiplied (one product, fp32 accumulation; the softmax statistics,
 // the compat product and the epilogue stay as they are) and c is streamed as fp16 - NOT within the 1e-4 parity gate.
 constexpr float kInvU16 = 1.0f / 65535.0f;
-// (WAVES = 8 - one 256-query workgroup per CU, every K / V tile fetched once per 256 queries, half the LDS-DMA pieces per wave - was
+// (Eight waves - one 256-query workgroup per CU, every K / V tile fetched once per 256 queries, half the LDS-DMA pieces per wave - were
 // built and measured in round 3: bit-identical results, 19.2 instead of 18.4 ms per step; eight waves behind each tile barrier
-// cost more than the halved stream saves.  The parameter stays, the instantiation is gone.)
+// cost more than the halved stream saves.  The body is written for four.)
 // PVF8 (with NPROD = 3): the two CROSS products of O += P V (P_hi V_lo + P_lo V_hi) on the block-scaled fp8 matrix pipe - ONE
 // v_mfma_scale_f32_32x32x64_f8f6f4 per feature block and tile instead of four f16 MFMAs; P_hi V_hi and all of S = Q' K^T stay
 // three-product split-fp16.  The V image then carries e4m3 planes with one scale per (feature, tile) in place of its low fp16
@@ -691,7 +691,7 @@ constexpr float kInvU16 = 1.0f / 65535.0f;
 // transposed; written by the fold form of k_linear_h2), the projection stages qw_wst / the Q' image carry q~ = (Wk^T Wq') f + Wk^T bq',
 // every score accumulator starts from the query's beta = (Wq'^T bk) . f + bk . bq' (kvf_vec: Wq'^T bk [128] | bk . bq'), and Wv, bv are
 // composed into the first layer of the epilogue's weights (wst, vecs).  The tile loop and the image formats are the unfolded ones.
-template <int NPROD = 3, int CFMT = 0, int WAVES = 4, bool PVF8 = false, bool FOLD = false>
+template <int NPROD = 3, int CFMT = 0, bool PVF8 = false, bool FOLD = false>
 GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restrict__ q_img, const float* __restrict__ k_img,
                                 const float* __restrict__ v_img, const float* __restrict__ fus, const float* __restrict__ wst,
                                 const float* __restrict__ vecs, float* out, int N, int tiles, int wgs_per_pair,
@@ -709,7 +709,8 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
                                 unsigned* __restrict__ stat_next = nullptr,       // [r5] PvGuard::stat_next (whole items with the next PointCN)
                                 const float* __restrict__ kvf_vec = nullptr) {    // FOLD: Wq'^T bk [128] | bk . bq'
   static_assert(!PVF8 || NPROD == 3, "the fp8 cross products belong to the three-product form");
-  static_assert(!FOLD || (NPROD == 3 && WAVES == 4), "the folded form belongs to the parity kernels");
+  static_assert(!FOLD || NPROD == 3, "the folded form belongs to the parity kernels");
+  constexpr int WAVES = 4;
   float* const ldsK = lds;
   float* const ldsV = lds + 2 * kStageFloats;
   const int lane = threadIdx.x & 63, h = lane >> 5;
@@ -744,7 +745,7 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
     for (int e = 0; e < CF; ++e) bs = fmaf(fq[e], uv[e], bs);
     beta = xhalf_sum(bs) + kvf_vec[C];
   };
-  if (NPROD == 3 && WAVES == 4 && qw_wst) {
+  if (NPROD == 3 && qw_wst) {
     // [r4] Q' = Wq' f + bq' for this workgroup's 128 query rows HERE instead of in k_linear_h2 (PointDSC.py:56: projection_q).  Q'
     // is the one projection only its own workgroup consumes: computing it in the linear kernel meant 82 MB written and read
     // back per layer and a third of the stores of that kernel's write-bound Q'/K/V phase (k_linear_h2 without it: 307 -> 272 us).
@@ -962,11 +963,11 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
   };
   // the same refills as ONE statement per tile and wave (dma_4k_s: the wave's four consecutive KiB under one M0 / address setup)
   auto issue_k4 = [&](const int t) {
-    if (WAVES == 4 && t + 2 < t_end && (NPROD == 3 || wave < 2))
+    if (t + 2 < t_end && (NPROD == 3 || wave < 2))
       dma_4k_s(gk + (size_t)(t + 2) * kStageFloats + wave * 1024, ldsK + (t & 1) * kStageFloats + wave * 1024, lane_off16);
   };
   auto issue_v4 = [&](const int t) {
-    if (WAVES == 4 && (NPROD == 3 || wave < 2))
+    if (NPROD == 3 || wave < 2)
       dma_4k_s(gv + (size_t)(t + 1) * kStageFloats + wave * 1024, ldsV + ((t + 1) & 1) * kStageFloats + wave * 1024, lane_off16);
   };
   auto rescale = [&](const bool moved, const float alpha) {
@@ -1317,11 +1318,11 @@ k_scattn_h2p(const float* __restrict__ q_img, const float* __restrict__ k_img, c
   __shared__ __attribute__((aligned(16))) float lds[4 * kStageFloats];
   tail_priority(blockIdx.x, gridDim.x);
   if (!PVF8 || attn_pv_on(v_scale, guard, blockIdx.x, n_items, n_full, ksplits, wgs_per_pair, ptab))
-    scattn_h2p_body<NPROD, CFMT, 4, PVF8, FOLD>(lds, blockIdx.x, q_img, k_img, v_img, fus, wst, vecs, out, N, tiles, wgs_per_pair, c_dense, n_items,
+    scattn_h2p_body<NPROD, CFMT, PVF8, FOLD>(lds, blockIdx.x, q_img, k_img, v_img, fus, wst, vecs, out, N, tiles, wgs_per_pair, c_dense, n_items,
                                                 n_full, ksplits, part_o, part_ml, next_wst, next_bias, ptab, v_scale, qf_img, qw_wst, qw_bias,
                                                 guard.stat_next, kvf_vec);
   else
-    scattn_h2p_body<NPROD, CFB, 4, false, FOLD>(lds, blockIdx.x, q_img, k_img, v_img, fus, wst, vecs, out, N, tiles, wgs_per_pair,
+    scattn_h2p_body<NPROD, CFB, false, FOLD>(lds, blockIdx.x, q_img, k_img, v_img, fus, wst, vecs, out, N, tiles, wgs_per_pair,
                                                 CFB == CFMT ? c_dense : c_dense_fb, n_items,
                                                 n_full, ksplits, part_o, part_ml, next_wst, next_bias, ptab, nullptr, qf_img, qw_wst, qw_bias,
                                                 guard.stat_next, kvf_vec);
@@ -1533,10 +1534,10 @@ k_small_attn_ff(const int n_attn, const float* __restrict__ q_img, const float* 
     // (n_full = 0: every item is split and leaves through the partial-result branch; `fus` / `out` of the whole-item epilogue
     // are never touched - they get valid pointers all the same, a literal null there crashes this compiler's optimiser)
     if (!PVF8 || attn_pv_on(v_scale, guard, blockIdx.x, n_items, 0, ksplits, wgs_per_pair, ptab))
-      scattn_h2p_body<3, CFMT, 4, PVF8>(lds, blockIdx.x, q_img, k_img, v_img, x1, tail_wst, tail_vecs, ff_part, N, tiles, wgs_per_pair, c_dense,
+      scattn_h2p_body<3, CFMT, PVF8>(lds, blockIdx.x, q_img, k_img, v_img, x1, tail_wst, tail_vecs, ff_part, N, tiles, wgs_per_pair, c_dense,
                                         n_items, 0, ksplits, part_o, part_ml, nullptr, nullptr, ptab, v_scale);
     else
-      scattn_h2p_body<3, CFMT, 4, false>(lds, blockIdx.x, q_img, k_img, v_img, x1, tail_wst, tail_vecs, ff_part, N, tiles, wgs_per_pair, c_dense,
+      scattn_h2p_body<3, CFMT, false>(lds, blockIdx.x, q_img, k_img, v_img, x1, tail_wst, tail_vecs, ff_part, N, tiles, wgs_per_pair, c_dense,
                                          n_items, 0, ksplits, part_o, part_ml, nullptr, nullptr, ptab, nullptr);
   } else {
     const int id = (int)blockIdx.x - n_attn;           // (bx, pair, z) with z fastest: the splits of a row block start together
@@ -2325,7 +2326,7 @@ __global__ void k_pack_pts8(const float* __restrict__ src, const float* __restri
 // -----------------------------------------------------------------------------------------
 
 // -----------------------------------------------------------------------------------------
-// host-side launchers (C++ linkage inside the library; the C ABI in gmf_api.cpp calls these)
+// host-side launchers (C++ linkage inside the library; the C ABI in gmf_api*.cpp calls these)
 // -----------------------------------------------------------------------------------------
 #include "launchers.hpp"
 
@@ -2364,33 +2365,32 @@ hipError_t launch_scattn_fp32(const float* q, const float* k, const float* v, co
 
 // Small grids, launches two and three of a layer (after k_small_front_fattn): key-split attention workgroups beside the
 // hidden-split feed-forward workgroups, then the merge kernel (partials of both -> block output / next layer's f).
-// Preconditions (the forward's plan, gmf_api.cpp): every attention item is split, ff_hs > 1.
-hipError_t launch_small_attn_ff_merge(const float* q, const float* k, const float* v, const float* x1, const float* ff_wst,
-                                      const float* ff_vecs, float* ff_part, int ff_hs, const float* tail_vecs, float* out, int B,
-                                      int N, int tiles, int ksplits, hipStream_t s, const CompatCache* cc, bool tile_merge) {
+// Preconditions (the forward's plan, encoder_plan.hpp): every attention item is split, ff_hs > 1.
+hipError_t launch_small_attn_ff_merge(bool tile_merge, const float* q, const float* k, const float* v, const float* x1, float* ff_part,
+                                      int ff_hs, float* out, int B, int N, int tiles, int ksplits, const ForwardBuffers& fb,
+                                      const LayerRun& lr, hipStream_t s) {
   const int wpp = (tiles + 3) / 4, W = wpp * B;
   const int per_xcd = (W >> 3) + ((W & 7) ? 1 : 0);
   const int n_attn = 8 * per_xcd * ksplits, n_ff = W * ff_hs;
-  if (cc->fmt == 2 && cc->v_scale)
-    hipLaunchKernelGGL((k_small_attn_ff<2, true>), dim3(n_attn + n_ff), dim3(256), 0, s, n_attn, q, k, v, cc->tail_wst_h2, tail_vecs, N, tiles, wpp,
-                       cc->dense, W, ksplits, cc->part_o, cc->part_ml, x1, ff_wst, ff_vecs, ff_part, B, ff_hs, cc->v_scale, cc->guard, cc->ptab);
-  else if (cc->fmt == 2)
-    hipLaunchKernelGGL(k_small_attn_ff<2>, dim3(n_attn + n_ff), dim3(256), 0, s, n_attn, q, k, v, cc->tail_wst_h2, tail_vecs, N, tiles, wpp,
-                       cc->dense, W, ksplits, cc->part_o, cc->part_ml, x1, ff_wst, ff_vecs, ff_part, B, ff_hs, (const unsigned*)nullptr, PvGuard{}, cc->ptab);
-  else if (cc->v_scale)
-    hipLaunchKernelGGL((k_small_attn_ff<0, true>), dim3(n_attn + n_ff), dim3(256), 0, s, n_attn, q, k, v, cc->tail_wst_h2, tail_vecs, N, tiles, wpp,
-                       cc->dense, W, ksplits, cc->part_o, cc->part_ml, x1, ff_wst, ff_vecs, ff_part, B, ff_hs, cc->v_scale, cc->guard, cc->ptab);
-  else
-    hipLaunchKernelGGL(k_small_attn_ff<0>, dim3(n_attn + n_ff), dim3(256), 0, s, n_attn, q, k, v, cc->tail_wst_h2, tail_vecs, N, tiles, wpp,
-                       cc->dense, W, ksplits, cc->part_o, cc->part_ml, x1, ff_wst, ff_vecs, ff_part, B, ff_hs, (const unsigned*)nullptr, PvGuard{}, cc->ptab);
+  const float *ff_wst = lr.w.ff_wst_h2, *ff_vecs = lr.w.ff_vec;
+  // every form of k_small_attn_ff takes the same arguments; `pvf8`: the V image carries e4m3 cross planes (the guard decides per pair)
+  auto go = [&](auto kern, bool pvf8) {
+    hipLaunchKernelGGL(kern, dim3(n_attn + n_ff), dim3(256), 0, s, n_attn, q, k, v, lr.epi_wst, lr.epi_vec, N, tiles, wpp, fb.dense, W,
+                       ksplits, fb.part_o, fb.part_ml, x1, ff_wst, ff_vecs, ff_part, B, ff_hs, pvf8 ? (const unsigned*)fb.v_scale : nullptr,
+                       pvf8 ? lr.guard : PvGuard{}, fb.ptab);
+  };
+  if (fb.fmt == 2 && fb.v_scale) go(k_small_attn_ff<2, true>, true);
+  else if (fb.fmt == 2) go(k_small_attn_ff<2>, false);
+  else if (fb.v_scale) go(k_small_attn_ff<0, true>, true);
+  else go(k_small_attn_ff<0>, false);
   if (tile_merge)
-    hipLaunchKernelGGL(k_scattn_merge_tile, dim3(tiles, B), dim3(256), 0, s, cc->part_o, cc->part_ml, cc->tail_wst_h2, tail_vecs, out,
-                       tiles, ksplits, cc->next_wst_h2, cc->next_bias, (const float*)ff_part, ff_hs, x1, ff_vecs + 2 * C + 2 * FFH,
-                       cc->guard.stat_next, N, cc->ptab);
+    hipLaunchKernelGGL(k_scattn_merge_tile, dim3(tiles, B), dim3(256), 0, s, fb.part_o, fb.part_ml, lr.epi_wst, lr.epi_vec, out,
+                       tiles, ksplits, lr.epi_next_wst, lr.epi_next_bias, (const float*)ff_part, ff_hs, x1, ff_vecs + 2 * C + 2 * FFH,
+                       lr.guard.stat_next, N, fb.ptab);
   else
-    hipLaunchKernelGGL(k_scattn_merge, dim3(8 * per_xcd), dim3(256), 0, s, cc->part_o, cc->part_ml, x1, cc->tail_wst_h2, tail_vecs, out,
-                       tiles, wpp, W, 0, ksplits, cc->next_wst_h2, cc->next_bias, (const float*)ff_part, ff_hs, x1,
-                       ff_vecs + 2 * C + 2 * FFH, cc->guard.stat_next, N, cc->ptab);
+    hipLaunchKernelGGL(k_scattn_merge, dim3(8 * per_xcd), dim3(256), 0, s, fb.part_o, fb.part_ml, x1, lr.epi_wst, lr.epi_vec, out,
+                       tiles, wpp, W, 0, ksplits, lr.epi_next_wst, lr.epi_next_bias, (const float*)ff_part, ff_hs, x1,
+                       ff_vecs + 2 * C + 2 * FFH, lr.guard.stat_next, N, fb.ptab);
   return hipGetLastError();
 }
 
@@ -2400,38 +2400,39 @@ hipError_t launch_small_attn_ff_merge(const float* q, const float* k, const floa
 //   (KSPLIT form) and k_scattn_merge finishes.
 // launch_scattn_h2 (scattn_variant 9): k_scattn_h2 - not pipelined, c from the cache when there is one (c_dense), else recomputed per
 //   (i, j) from pts8 (also the fallback when the cache would not fit); fp32-MFMA fc_message epilogue (wst = fp32 images).
-hipError_t launch_scattn_h2p(const float* q, const float* k, const float* v, const float* fus, const float* vecs, float* out, int B,
-                             int N, int tiles, hipStream_t s, const CompatCache& cc, int n_full, int ksplits) {
+hipError_t launch_scattn_h2p(const float* q, const float* k, const float* v, const float* fus, float* out, int B, int N, int tiles,
+                             const ForwardBuffers& fb, const LayerRun& lr, int n_full, int ksplits, hipStream_t s) {
+  const float* const vecs = lr.epi_vec;
   const int wpp = (tiles + 3) / 4, W = wpp * B;
   const int per_xcd = (W >> 3) + ((W & 7) ? 1 : 0);
   const int max_tail = std::max(0, per_xcd - n_full);
   const dim3 grid(8 * (std::min(n_full, per_xcd) + max_tail * ksplits));
   // every form of k_scattn_h2p takes the same arguments; `pvf8`: the V image carries e4m3 cross planes (the guard decides per pair)
   auto go = [&](auto kern, bool pvf8) {
-    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense, W, n_full, ksplits,
-                       cc.part_o, cc.part_ml, cc.next_wst_h2, cc.next_bias, cc.ptab, pvf8 ? (const unsigned*)cc.v_scale : nullptr, cc.qf_img,
-                       cc.qw_wst, cc.qw_bias, pvf8 ? cc.guard : PvGuard{}, cc.kvf_vec, cc.dense_fb);
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, q, k, v, fus, lr.epi_wst, vecs, out, N, tiles, wpp, fb.dense, W, n_full, ksplits,
+                       fb.part_o, fb.part_ml, lr.epi_next_wst, lr.epi_next_bias, fb.ptab, pvf8 ? (const unsigned*)fb.v_scale : nullptr, lr.qf_img,
+                       lr.qw_wst, lr.qw_bias, pvf8 ? lr.guard : PvGuard{}, lr.kvf_vec, fb.dense_fb);
   };
-  const bool pvf8 = cc.v_scale != nullptr, fold = cc.kvf_vec != nullptr;   // (default: V with e4m3 cross planes; "kv_fold": keys = values = f)
-  if (cc.half && max_tail == 0)   // throughput numerics mode, whole items only: the three-tiles-in-flight form
-    hipLaunchKernelGGL(k_scattn_fast, dim3(8 * per_xcd), dim3(256), 0, s, q, k, v, fus, cc.tail_wst_h2, vecs, out, N, tiles, wpp, cc.dense, W,
-                       cc.next_wst_h2, cc.next_bias);
-  else if (cc.half)  // ... with a split tail: one fp16 product, c streamed as fp16 (the cache was built that way)
+  const bool pvf8 = fb.v_scale != nullptr, fold = lr.kvf_vec != nullptr;   // (default: V with e4m3 cross planes; "kv_fold": keys = values = f)
+  if (fb.half && max_tail == 0)   // throughput numerics mode, whole items only: the three-tiles-in-flight form
+    hipLaunchKernelGGL(k_scattn_fast, dim3(8 * per_xcd), dim3(256), 0, s, q, k, v, fus, lr.epi_wst, vecs, out, N, tiles, wpp, fb.dense, W,
+                       lr.epi_next_wst, lr.epi_next_bias);
+  else if (fb.half)  // ... with a split tail: one fp16 product, c streamed as fp16 (the cache was built that way)
     go(k_scattn_h2p<1, 1>, false);
-  else if (cc.fmt == 2 && cc.dense_fb && pvf8)   // "compat_16": 16 bits where the guard lets the pair through, the exact fp32 cache where it trips
+  else if (fb.fmt == 2 && fb.dense_fb && pvf8)   // "compat_16": 16 bits where the guard lets the pair through, the exact fp32 cache where it trips
     fold ? go(k_scattn_h2p<3, 2, true, true, 0>, true) : go(k_scattn_h2p<3, 2, true, false, 0>, true);
-  else if (cc.fmt == 2 && pvf8)   // parity arithmetic, c streamed as 16-bit fixed point by both bodies
+  else if (fb.fmt == 2 && pvf8)   // parity arithmetic, c streamed as 16-bit fixed point by both bodies
     fold ? go(k_scattn_h2p<3, 2, true, true>, true) : go(k_scattn_h2p<3, 2, true>, true);
-  else if (cc.fmt == 2)
+  else if (fb.fmt == 2)
     fold ? go(k_scattn_h2p<3, 2, false, true>, false) : go(k_scattn_h2p<3, 2>, false);
   else if (pvf8)    // the fp32 cache
     fold ? go(k_scattn_h2p<3, 0, true, true>, true) : go(k_scattn_h2p<3, 0, true>, true);
   else
     fold ? go(k_scattn_h2p<3, 0, false, true>, false) : go(k_scattn_h2p<3, 0>, false);
   if (max_tail > 0)
-    hipLaunchKernelGGL(k_scattn_merge, dim3(8 * max_tail), dim3(256), 0, s, cc.part_o, cc.part_ml, fus, cc.tail_wst_h2, vecs, out,
-                       tiles, wpp, W, n_full, ksplits, cc.next_wst_h2, cc.next_bias, (const float*)nullptr, 0,
-                       (const float*)nullptr, (const float*)nullptr, cc.guard.stat_next, N, cc.ptab);
+    hipLaunchKernelGGL(k_scattn_merge, dim3(8 * max_tail), dim3(256), 0, s, fb.part_o, fb.part_ml, fus, lr.epi_wst, vecs, out,
+                       tiles, wpp, W, n_full, ksplits, lr.epi_next_wst, lr.epi_next_bias, (const float*)nullptr, 0,
+                       (const float*)nullptr, (const float*)nullptr, lr.guard.stat_next, N, fb.ptab);
   return hipGetLastError();
 }
 

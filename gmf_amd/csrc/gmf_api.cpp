@@ -209,157 +209,22 @@ int gmf_set_sigma_device(gmf_handle* h, const float* sigma_dev) {
   return GMF_OK;
 }
 
+static_assert(gmf::kSmMaxSplits == 32 && gmf::kPmcLocal == 384, "the ranges of spectral_col_splits and clique_local_rows in gmf::kKnobs");
+
 int gmf_set_tuning(gmf_handle* h, const char* name, int value) {
   GMF_REQUIRE(h && name, GMF_ERR_BAD_ARG, "set_tuning: null pointer");
   std::lock_guard<std::mutex> lock(h->mu);        // (forwards read h->tune under the same lock)
-  gmf::Tuning& t = h->tune;
-  if (std::strcmp(name, "scattn_variant") == 0) {
-    GMF_REQUIRE(value == 0 || value == 9 || value == 18, GMF_ERR_BAD_ARG,
-                "set_tuning: scattn_variant must be 18 (cached, pipelined split-fp16; default), 9 (split-fp16, not pipelined) or 0 (fp32 MFMA)");
-    t.scattn_variant = value;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "front_output_split") == 0) {  // 1 = small grids use one workgroup per output of k_front_h2 (default), 0 = never
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: front_output_split must be 0 or 1");
-    t.front_split = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "ff_hidden_splits") == 0) {    // 0 = automatic (small grids only), 1 = off, 2 / 4 / 8 = forced
-    GMF_REQUIRE(value == 0 || value == 1 || value == 2 || value == 4 || value == 8, GMF_ERR_BAD_ARG,
-                "set_tuning: ff_hidden_splits must be 0, 1, 2, 4 or 8");
-    t.ff_split = value;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "attn_key_splits") == 0) {     // 0 = automatic (small grids only), 1 = off, n = force n splits
-    GMF_REQUIRE(value >= 0 && value <= 8, GMF_ERR_BAD_ARG, "set_tuning: attn_key_splits out of range (0..8)");
-    t.key_splits = value;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "attn_tail_split") == 0) {     // 1 = split the last partial round of a large attention grid by keys (default 0)
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: attn_tail_split must be 0 or 1");
-    t.tail_split = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "small_grid_roles") == 0) {    // 1 = small grids: three launches per layer with mixed workgroup roles (default), 0 = one kernel per stage
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: small_grid_roles must be 0 or 1");
-    t.small_roles = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "fused_linear") == 0) {        // 1 = two launches per layer (k_linear_h2 + attention with the next PointCN; default), 0 = four
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: fused_linear must be 0 or 1");
-    t.fused_linear = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "compat_cache") == 0) {
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: compat_cache must be 0 or 1");
-    t.use_cache = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "conv_lds_patch") == 0) {      // 1 = stride-1 3x3 convolutions stage their activations through LDS (default), 2 = same without the three-workgroup form, 0 = gather form
-    GMF_REQUIRE(value >= 0 && value <= 2, GMF_ERR_BAD_ARG, "set_tuning: conv_lds_patch must be 0, 1 or 2");
-    t.conv_patch = value;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "small_fattn_tile") == 0) {    // [ABI 5] 1 = small grids: the cross-attention role per query tile (default), 0 = per four tiles
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: small_fattn_tile must be 0 or 1");
-    t.small_fattn_tile = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "small_prologue_roles") == 0) { // [ABI 5] 1 = small grids: the prologue's image-side and point-side chains share three launches (default), 0 = six kernels
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: small_prologue_roles must be 0 or 1");
-    t.small_prologue = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "conv_small_grid") == 0) {     // [ABI 5] 1 = grids of a few images run the K-split convolution kernel (default), 0 = the 128-pixel kernels at every size
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: conv_small_grid must be 0 or 1");
-    t.conv_small = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "nms_binned") == 0) {          // 1 = grid-binned NMS candidates on large grids (default), 2 = always, 0 = all pairs
-    GMF_REQUIRE(value >= 0 && value <= 2, GMF_ERR_BAD_ARG, "set_tuning: nms_binned must be 0, 1 or 2");
-    t.nms_binned = value;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "topk_select") == 0) {         // 1 = radix select of the S seeds (default), 0 = full bitonic sort
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: topk_select must be 0 or 1");
-    t.topk_select = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "wide_attn_tile") == 0) {      // 256-wide layer: cross-attention per tile (1, default; grids of up to 256 tiles) or per four tiles (0)
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: wide_attn_tile must be 0 or 1");
-    t.wide_attn_tile = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "small_merge_tile") == 0) {    // small grids: merge step per query tile (1, default) or per four (0)
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: small_merge_tile must be 0 or 1");
-    t.small_merge_tile = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "mid_grid_roles") == 0) {      // two-launch form below this many base workgroups: linear kernel as two roles (0 = never)
-    GMF_REQUIRE(value >= 0 && value <= 4096, GMF_ERR_BAD_ARG, "set_tuning: mid_grid_roles out of range (0..4096)");
-    t.mid_grid_roles = value;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "q_in_attention") == 0) {      // 1 = large grids: every attention workgroup projects its own Q' (default), 0 = k_linear_h2 writes a Q' image
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: q_in_attention must be 0 or 1");
-    t.q_in_attention = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "kv_fold") == 0) {             // 1 = large grids: keys = values = f, K / V projections composed into the weights (default), 0 = the unfolded form
-    GMF_REQUIRE(value == 0 || value == 1, GMF_ERR_BAD_ARG, "set_tuning: kv_fold must be 0 or 1");
-    t.kv_fold = value != 0;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "pv_fp8") == 0) {       // large grids: the cross products of O += P V on the block-scaled fp8 pipe (default 1)
-    GMF_REQUIRE(value >= 0 && value <= 2, GMF_ERR_BAD_ARG, "set_tuning: pv_fp8 must be 0 (three f16 products), 1 (guarded, default) or 2 (always)");
-    t.pv_fp8 = value;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "compat_format") == 0) {       // element format of the compat cache: 0 = the plan's ("compat_16"; default), 2 = 16-bit fixed point for everyone (opt-in)
-    GMF_REQUIRE(value == 0 || value == 2, GMF_ERR_BAD_ARG, "set_tuning: compat_format must be 0 (fp32) or 2 (16-bit fixed point of c)");
-    t.compat_format = value;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "compat_16") == 0) {           // 1 = large grids: the 16-bit compat cache under the "pv_fp8" guard (default), 2 = every grid of the two-launch plan, 0 = fp32 for everyone
-    GMF_REQUIRE(value >= 0 && value <= 2, GMF_ERR_BAD_ARG, "set_tuning: compat_16 must be 0, 1 or 2");
-    t.compat_16 = value;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "precision") == 0) {           // 0 = parity numerics (default), 1 / 2 = throughput numerics (NOT within 1e-4)
-    GMF_REQUIRE(value >= 0 && value <= 2, GMF_ERR_BAD_ARG, "set_tuning: precision must be 0 (parity), 1 or 2 (throughput numerics)");
-    t.precision = value;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "spectral_col_splits") == 0) { // spectral matching: 0 = column splits from the pair's N (default), 1..32 = forced
-    GMF_REQUIRE(value >= 0 && value <= gmf::kSmMaxSplits, GMF_ERR_BAD_ARG, "set_tuning: spectral_col_splits out of range (0..32)");
-    t.spectral_col_splits = value;
-    return GMF_OK;
-  }
-  if (std::strcmp(name, "clique_local_rows") == 0) {   // maximum clique: roots of up to this many candidates are searched in LDS (default 384), 0 = none
-    GMF_REQUIRE(value >= 0 && value <= gmf::kPmcLocal, GMF_ERR_BAD_ARG, "set_tuning: clique_local_rows out of range (0..384)");
-    t.clique_local_rows = value;
-    return GMF_OK;
-  }
-  return fail(h, GMF_ERR_BAD_ARG, std::string("gmf: set_tuning: unknown knob ") + name);
+  std::string why;                                // the knobs, their fields and the values they accept: gmf::kKnobs (encoder_plan.hpp)
+  if (!gmf::set_knob(h->tune, name, value, &why)) return fail(h, GMF_ERR_BAD_ARG, "gmf: set_tuning: " + why);
+  return GMF_OK;
 }
 
 // The current value of a knob (the counterpart of gmf_set_tuning: a caller that changes a knob for one call can put back what it found).
 int gmf_get_tuning(gmf_handle* h, const char* name, int* value) {
   GMF_REQUIRE(h && name && value, GMF_ERR_BAD_ARG, "get_tuning: null pointer");
   std::lock_guard<std::mutex> lock(h->mu);
-  const gmf::Tuning& t = h->tune;
-  const struct { const char* name; int v; } tab[] = {
-      {"scattn_variant", t.scattn_variant}, {"front_output_split", t.front_split ? 1 : 0}, {"ff_hidden_splits", t.ff_split},
-      {"attn_key_splits", t.key_splits}, {"attn_tail_split", t.tail_split ? 1 : 0}, {"small_grid_roles", t.small_roles ? 1 : 0},
-      {"fused_linear", t.fused_linear ? 1 : 0}, {"compat_cache", t.use_cache ? 1 : 0}, {"conv_lds_patch", t.conv_patch}, {"conv_small_grid", t.conv_small ? 1 : 0}, {"small_prologue_roles", t.small_prologue ? 1 : 0}, {"small_fattn_tile", t.small_fattn_tile ? 1 : 0},
-      {"nms_binned", t.nms_binned}, {"topk_select", t.topk_select ? 1 : 0}, {"wide_attn_tile", t.wide_attn_tile ? 1 : 0},
-      {"small_merge_tile", t.small_merge_tile ? 1 : 0}, {"mid_grid_roles", t.mid_grid_roles}, {"pv_fp8", t.pv_fp8}, {"q_in_attention", t.q_in_attention ? 1 : 0},
-      {"kv_fold", t.kv_fold ? 1 : 0}, {"compat_format", t.compat_format}, {"compat_16", t.compat_16}, {"precision", t.precision}, {"spectral_col_splits", t.spectral_col_splits},
-      {"clique_local_rows", t.clique_local_rows}};
-  for (const auto& e : tab) {
-    if (std::strcmp(name, e.name) == 0) { *value = e.v; return GMF_OK; }
-  }
-  return fail(h, GMF_ERR_BAD_ARG, std::string("gmf: get_tuning: unknown knob ") + name);
+  if (!gmf::get_knob(h->tune, name, value)) return fail(h, GMF_ERR_BAD_ARG, std::string("gmf: get_tuning: unknown knob ") + name);
+  return GMF_OK;
 }
 
 int gmf_profile_enable(gmf_handle* h, int on) {
@@ -406,645 +271,6 @@ void gmf_destroy(gmf_handle* h) {
 const char* gmf_last_error_string(gmf_handle* h) { return h ? h->err.c_str() : "gmf: null handle"; }
 
 long long gmf_workspace_bytes(gmf_handle* h) { return h ? (long long)h->arena_bytes : 0; }
-
-// ---------------------------------------------------------------------------------------------
-int gmf_pack_rows_p32(gmf_handle* h, const float* src, long long sb, long long sr, long long sk, int B, int n_rows,
-                      int K, float* dst, gmf_stream_t stream) {
-  GMF_REQUIRE(h && src && dst, GMF_ERR_BAD_ARG, "pack_rows_p32: null pointer");
-  GMF_REQUIRE(B > 0 && n_rows > 0 && K > 0 && K % 8 == 0, GMF_ERR_UNSUPPORTED_SHAPE, "pack_rows_p32: K must be a positive multiple of 8");
-  SetDevice sd(h, stream);
-  GMF_HIP(gmf::launch_pack_p32(src, dst, B, n_rows, K, sb, sr, sk, S(stream)));
-  return GMF_OK;
-}
-
-int gmf_unpack_rows_p32(gmf_handle* h, const float* src_img, int B, int n_rows, int K, float* dst, long long sb,
-                        long long sr, long long sk, gmf_stream_t stream) {
-  GMF_REQUIRE(h && src_img && dst, GMF_ERR_BAD_ARG, "unpack_rows_p32: null pointer");
-  GMF_REQUIRE(B > 0 && n_rows > 0 && K > 0 && K % 8 == 0, GMF_ERR_UNSUPPORTED_SHAPE, "unpack_rows_p32: K must be a positive multiple of 8");
-  SetDevice sd(h, stream);
-  GMF_HIP(gmf::launch_unpack_p32(src_img, dst, B, n_rows, K, sb, sr, sk, S(stream)));
-  return GMF_OK;
-}
-
-int gmf_pack_pts8(gmf_handle* h, const float* src, const float* tgt, int B, int N, float* dst, gmf_stream_t stream) {
-  GMF_REQUIRE(h && src && tgt && dst, GMF_ERR_BAD_ARG, "pack_pts8: null pointer");
-  GMF_REQUIRE(B > 0 && N > 0, GMF_ERR_UNSUPPORTED_SHAPE, "pack_pts8: empty input");
-  SetDevice sd(h, stream);
-  GMF_HIP(gmf::launch_pack_pts8(src, tgt, dst, B, N, S(stream)));
-  return GMF_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-int gmf_front_forward(gmf_handle* h, int first, const float* in, const float* wst, const float* vecs, float* f,
-                      float* q, float* k, float* v, int B, int N, gmf_stream_t stream) {
-  GMF_REQUIRE(h && in && wst && vecs && f && q && k && v, GMF_ERR_BAD_ARG, "front_forward: null pointer");
-  GMF_REQUIRE(B > 0 && N > 0, GMF_ERR_UNSUPPORTED_SHAPE, "front_forward: empty input");
-  SetDevice sd(h, stream);
-  GMF_HIP(gmf::launch_front(first ? 1 : 0, in, wst, vecs, f, q, k, v, B, N, tiles_of(N), S(stream)));
-  return GMF_OK;
-}
-
-int gmf_scattn_forward(gmf_handle* h, const float* q, const float* k, const float* v, const float* pts8,
-                       const float* fusion2_out, const float* wst, const float* vecs, float* out, int B, int N,
-                       float sigma_d, gmf_stream_t stream) {
-  GMF_REQUIRE(h && q && k && v && pts8 && fusion2_out && wst && vecs && out, GMF_ERR_BAD_ARG, "scattn_forward: null pointer");
-  GMF_REQUIRE(B > 0 && N > 0, GMF_ERR_UNSUPPORTED_SHAPE, "scattn_forward: empty input");
-  GMF_REQUIRE(sigma_d > 0.f, GMF_ERR_BAD_ARG, "scattn_forward: sigma_d must be positive");
-  SetDevice sd(h, stream);
-  GMF_HIP(gmf::launch_scattn_fp32(q, k, v, pts8, fusion2_out, wst, vecs, out, B, N, tiles_of(N), sigma_d, S(stream)));
-  return GMF_OK;
-}
-
-int gmf_scattn_forward_dense(gmf_handle* h, const float* q, const float* k, const float* v, const float* attention,
-                             const float* fusion2_out, const float* wst, const float* vecs, float* out, int B, int N,
-                             gmf_stream_t stream) {
-  GMF_REQUIRE(h && q && k && v && attention && fusion2_out && wst && vecs && out, GMF_ERR_BAD_ARG, "scattn_forward_dense: null pointer");
-  GMF_REQUIRE(B > 0 && N > 0, GMF_ERR_UNSUPPORTED_SHAPE, "scattn_forward_dense: empty input");
-  SetDevice sd(h, stream);
-  GMF_HIP(gmf::launch_scattn_dense(q, k, v, attention, fusion2_out, wst, vecs, out, B, N, tiles_of(N), S(stream)));
-  return GMF_OK;
-}
-
-int gmf_fusion_ctx_prepare(gmf_handle* h, int pe, const float* ctx, const float* wst, const float* vecs, float* out,
-                           int B, int T, int sets, int wst_stride, int vec_stride, gmf_stream_t stream) {
-  GMF_REQUIRE(h && ctx && wst && vecs && out, GMF_ERR_BAD_ARG, "fusion_ctx_prepare: null pointer");
-  GMF_REQUIRE(B > 0 && T > 0 && sets > 0, GMF_ERR_UNSUPPORTED_SHAPE, "fusion_ctx_prepare: empty input");
-  SetDevice sd(h, stream);
-  GMF_HIP(gmf::launch_ctx_prep(pe != 0, ctx, wst, vecs, out, B, T, tiles_of(T), sets, wst_stride, vec_stride, S(stream)));
-  return GMF_OK;
-}
-
-int gmf_fusion_attn_forward(gmf_handle* h, int pe, const float* x, const float* ctx_img, const float* wst,
-                            const float* vecs, float* x1, int B, int N, int T, gmf_stream_t stream) {
-  GMF_REQUIRE(h && x && ctx_img && wst && vecs && x1, GMF_ERR_BAD_ARG, "fusion_attn_forward: null pointer");
-  GMF_REQUIRE(B > 0 && N > 0 && T > 0, GMF_ERR_UNSUPPORTED_SHAPE, "fusion_attn_forward: empty input");
-  SetDevice sd(h, stream);
-  GMF_HIP(gmf::launch_fusion_attn(pe != 0, x, ctx_img, wst, vecs, x1, B, N, tiles_of(N), T, tiles_of(T), S(stream)));
-  return GMF_OK;
-}
-
-int gmf_fusion_ff_forward(gmf_handle* h, const float* x1, const float* wst, const float* vecs, float* x2, int B,
-                          int N, gmf_stream_t stream) {
-  GMF_REQUIRE(h && x1 && wst && vecs && x2, GMF_ERR_BAD_ARG, "fusion_ff_forward: null pointer");
-  GMF_REQUIRE(B > 0 && N > 0, GMF_ERR_UNSUPPORTED_SHAPE, "fusion_ff_forward: empty input");
-  SetDevice sd(h, stream);
-  GMF_HIP(gmf::launch_fusion_ff(x1, wst, vecs, x2, B, tiles_of(N), S(stream)));
-  return GMF_OK;
-}
-
-int gmf_classifier_forward(gmf_handle* h, const float* feat_img, const float* wst, const float* vecs, float* logits,
-                           float* feat_n, float* feat, int B, int N, gmf_stream_t stream) {
-  GMF_REQUIRE(h && feat_img && wst && vecs && logits && feat_n, GMF_ERR_BAD_ARG, "classifier_forward: null pointer");
-  GMF_REQUIRE(B > 0 && N > 0, GMF_ERR_UNSUPPORTED_SHAPE, "classifier_forward: empty input");
-  SetDevice sd(h, stream);
-  GMF_HIP(gmf::launch_head(feat_img, wst, vecs, logits, feat_n, feat, B, N, tiles_of(N), S(stream), h->status_dev));
-  return GMF_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-static int check_weights(gmf_handle* h, const gmf_encoder_weights* w) {
-  GMF_REQUIRE(w, GMF_ERR_BAD_ARG, "encoder weights: null");
-  GMF_REQUIRE(w->num_layers >= 0 && w->num_layers <= 64, GMF_ERR_BAD_ARG, "encoder weights: bad num_layers");
-  GMF_REQUIRE(w->sigma_d > 0.f, GMF_ERR_BAD_ARG, "encoder weights: sigma_d must be positive");
-  return GMF_OK;
-}
-
-// compute units of the current device (256 on MI355X); queried once per process and device
-static int cu_count() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 256;
-  static int cached[16] = {0};
-  if (dev >= 0 && dev < 16 && cached[dev] > 0) return cached[dev];
-  int n = 0;
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  if (dev >= 0 && dev < 16) cached[dev] = n;
-  return n;
-}
-
-// Work split of the attention grid (attn_item): W items on `slots` resident workgroups (2 per CU).  n_full = items per XCD
-// that run whole; the rest are split `ksplits` ways by key range (ksplits = 1: none).
-static void plan_attn_split(const gmf::Tuning& tune, int cus, int W, int tiles, int max_splits, bool ragged, int* n_full_out,
-                            int* ksplits_out) {
-  const int slots = 2 * cus;
-  const int per_xcd = (W >> 3) + ((W & 7) ? 1 : 0);
-  int n_full = per_xcd, ksplits = 1;                                    // default: every item whole
-  if (max_splits > 1 && tiles >= 8) {
-    const int cap = std::min(max_splits, std::max(1, tiles / 4));
-    if (tune.key_splits > 1) { n_full = 0; ksplits = std::min(tune.key_splits, cap); }             // forced: every item split
-    else if (tune.key_splits == 0) {
-      // small grid: ONE workgroup per CU - a workgroup alone on its CU runs its tiles almost twice as fast as two
-      // co-resident ones (B = 1, N = 5000: 6 splits = 240 workgroups 1.64 ms per forward, 8 splits = 320 workgroups 1.75 ms)
-      if (W < slots / 2) { n_full = 0; ksplits = std::min(std::max(2, (slots / 2) / W), cap); }
-      else if (W < 3 * slots / 4 && tiles >= 64) { n_full = 0; ksplits = std::min(2, cap); }       // measured break-even
-      else if (W > slots && tune.tail_split && !ragged) {
-        // large grid: whole rounds run whole; a last partial round of at most half the slots is split to fill them (the split
-        // tail assumes items of one length: not for ragged batches)
-        const int full = (W / slots) * slots, rest = W - full;
-        if (rest > 0 && 2 * rest <= slots && tiles >= 16) { n_full = full / 8; ksplits = std::min(std::min(slots / rest, 4), cap); }
-      }
-    }
-    if (ksplits <= 1) { n_full = per_xcd; ksplits = 1; }
-  }
-  *n_full_out = n_full;
-  *ksplits_out = ksplits;
-}
-
-// hidden splits of the feed-forward on a grid of `base` workgroups (tune.ff_split: 0 = automatic, 1 = off, 2 / 4 / 8 = forced)
-static int plan_ff_split(const gmf::Tuning& tune, int base, int max_parts) {
-  int hs = 1;
-  if (max_parts >= 2) {
-    if (tune.ff_split > 0) hs = tune.ff_split;
-    else if (base < 256) hs = base <= 32 ? 8 : base <= 64 ? 4 : 2;   // (measured at B = 1 .. 4: the merge reads every partial)
-    hs = std::min(hs, max_parts);
-    if (hs != 2 && hs != 4 && hs != 8) hs = 1;
-  }
-  return hs;
-}
-
-// How one encoder forward runs: every launch decision, made once (plan_encoder) from the handle's knobs, the weight images
-// present and the shape, with the sizes of the buffers that depend on them.  The launchers are told; none reads the knobs.
-struct EncoderPlan {
-  enum Form {
-    kFp32,          // fp32 images and kernels for every stage (split-fp16 weight images missing, "scattn_variant" 0, dense attention)
-    kStages,        // split-fp16, one kernel per stage; the attention writes the block output
-    kFusedStages,   // the cached, pipelined attention applies the next layer's PointCN in its epilogue; one kernel per other stage
-    kLinear,        // ... and k_linear_h2 for Q'/K/V + Fusion-2: two launches per layer (the default)
-    kSmall3,        // ... small grids: three launches per layer with two workgroup roles each
-  };
-  Form form = kFp32;
-  bool fused() const { return form >= kFusedStages; }
-  bool f1_h2 = false;        // Fusion-1 on split-fp16 images
-  bool prologue = false;     // small grids: the prologue's two chains as roles of three shared launches (k_pro_*)
-  bool cache = false;        // compat cache, built once per batch
-  bool pipelined = false;    // attention: k_scattn_h2p streaming c from the cache (scattn_variant 18)
-  int fmt = 0;               // the cache's element format (CompatCache::fmt)
-  bool half = false;         // throughput numerics (CompatCache::half) ...
-  bool one_product = false;  // ... and the linear stages multiply one product as well ("precision" = 2)
-  bool front_split = false;  // k_front_h2 with one workgroup per output
-  int max_splits = 0;        // capacity of the key- and hidden-split partials (0: no workspace for them)
-  int attn_nf = 0, attn_ks = 1;   // attention items per XCD that run whole, key splits of the rest
-  int ff_hs = 1, f1_ff_hs = 1;    // hidden splits of the layers' feed-forward and of Fusion-1's
-  bool roles = false;        // k_linear_h2 as two workgroup roles per row block
-  bool q_in_attn = false;    // no Q' image: the attention projects its own (CompatCache::qf_img)
-  bool kv_fold = false;      // keys = values = f: no K / V projections, composed weights (gmf_encoder_weights::kv_fold)
-  bool c16_guard = false;    // "compat_16": fmt = 2 for the pairs and layers the guard lets through, a lazily built fp32 cache for the rest
-  bool v_fp8 = false;        // V carries e4m3 cross planes (CompatCache::v_scale) ...
-  bool guard = false;        // ... chosen per pair and layer on the device (PvGuard)
-  bool clear_stats = false;  // the key-point packing clears the guard's statistics
-  size_t act = 0, tok = 0, cache_floats = 0;   // floats of an activation image, a token image, the cache
-  size_t cache_fb_floats = 0;                  // ... and of the guarded form's fp32 cache (c16_guard)
-};
-
-// min_tiles > 0: a ragged batch whose smallest pair has that many tiles.  dense: the caller passes the attention matrix.
-static EncoderPlan plan_encoder(const gmf::Tuning& t, const gmf_encoder_weights* w, int B, int N, int T, int L, int min_tiles, int cus,
-                                bool dense = false) {
-  EncoderPlan p;
-  const int tiles = tiles_of(N), tt = tiles_of(T);
-  const int W = ((tiles + 3) / 4) * B;     // workgroups of 128 query rows
-  const bool ragged = min_tiles > 0;
-  p.act = (size_t)B * tiles * kTileFloats;
-  p.tok = (size_t)B * tt * kTileFloats;
-  // split-fp16 path: needs every split-fp16 weight image; the dense-`attention` drop-in and scattn_variant 0 run on fp32 images
-  const bool h2 = !dense && t.scattn_variant >= 9 && w->front_wst_h2 && w->ctx_wst_h2 && w->attn_wst_h2 && w->ff_wst_h2 && w->tail_wst_h2;
-  const bool fusable = h2 && t.fused_linear && t.scattn_variant == 18;
-  // throughput numerics ("precision" = 1, 2): on the two-launch path of large grids the attention multiplies one fp16 product and
-  // streams the compat matrix as fp16 (level 2: the layer's linear stages multiply one product as well); every other path keeps the
-  // parity numerics
-  const bool half = t.precision >= 1 && fusable && W >= 256 && !ragged;
-  // the cache's element format: fp16 c in the throughput mode; else the handle's "compat_format" wherever the pipelined kernel
-  // (variant 18) is the cache's only reader.  4 KiB per pair of 32-row tiles as fp32, 2 KiB in the 16-bit formats
-  const int fmt = half ? 1 : t.scattn_variant == 18 ? t.compat_format : 0;
-  const size_t cache_floats = (size_t)B * tiles * tiles * (fmt ? 512 : 1024);
-  const size_t cache_cap = (size_t)96 << 30;      // above it the cache is not used
-  p.cache = h2 && L > 1 && t.use_cache && cache_floats * 4 <= cache_cap;
-  const bool fused = fusable && p.cache;
-  if (p.cache) { p.cache_floats = cache_floats; p.fmt = fmt; p.half = half; }
-  p.one_product = p.half && t.precision == 2;
-  p.pipelined = p.cache && t.scattn_variant == 18;
-  p.front_split = t.front_split && W < 128;
-  // partials of the key / hidden splits: small grids up to 8 splits of every query block, large grids 2..4 of the last partial round
-  p.max_splits = (p.cache && tiles >= 8) ? (W < 384 ? 8 : 4) : 0;
-  // ragged batch: planned on the SMALLEST pair's tiles (every pair then has at least four key tiles per split); either every item is
-  // split - small grids: a handful of whole items walking all their keys alone left most of the chip idle (4 pairs x 1000: 1.50 ms
-  // against 0.74 for the uniform batch) - or none is
-  plan_attn_split(t, cus, W, ragged ? min_tiles : tiles, p.max_splits, ragged, &p.attn_nf, &p.attn_ks);
-  p.ff_hs = plan_ff_split(t, W, p.max_splits);
-  p.f1_ff_hs = tt <= tiles ? plan_ff_split(t, ((tt + 3) / 4) * B, p.max_splits) : 1;   // (into the attention's partials)
-  if (!h2) p.form = EncoderPlan::kFp32;
-  else if (!fused) p.form = EncoderPlan::kStages;
-  // small grids: when both the attention and the feed-forward are split anyway, their workgroups share launches
-  else if (W < 256 && t.small_roles && p.attn_nf == 0 && p.attn_ks > 1 && p.ff_hs > 1 && p.max_splits == 8) p.form = EncoderPlan::kSmall3;
-  // below 256 row blocks key / hidden / output splits fill the chip better; a ragged batch takes either the three-launch form of
-  // small grids or the two-launch form (the one-kernel-per-stage form in between has no pair table)
-  else p.form = (W >= 256 || ragged) ? EncoderPlan::kLinear : EncoderPlan::kFusedStages;
-  // grids that give a CU about one workgroup: k_linear_h2 as two roles per row block (the Q'/K/V projections | Fusion-2) in one launch
-  p.roles = p.form == EncoderPlan::kLinear && t.mid_grid_roles > 0 && W < t.mid_grid_roles;
-  // [r4] Q' in the attention kernel's prologue (parity arithmetic of the pipelined kernel; not with the linear kernel as two roles,
-  // whose Q'/K/V role writes the image): k_linear_h2 then projects K and V only
-  p.q_in_attn = p.form == EncoderPlan::kLinear && t.q_in_attention && !p.half && !p.roles;
-  p.f1_h2 = h2 && w->f1_ctx_wst_h2 && w->f1_attn_wst_h2 && w->f1_ff_wst_h2;
-  const bool pro_grid = t.small_prologue && fused && p.f1_h2 && W < 256;    // grids whose prologue runs as roles (below; fp32 cache only)
-  // "compat_16" (the default): on the two-launch plan with the parity numerics of the pipelined kernel the cache format
-  // follows the fp8 decision - uniform or ragged, the linear kernel whole or as two roles, Q' in the attention prologue or as an image,
-  // folded or not.  "pv_fp8" = 1 with thresholds: 16 bits where the guard lets a pair's layer through, and a second, fp32 cache that the
-  // device fills for the pairs that trip (c16_guard); "pv_fp8" = 2: 16 bits for everyone, as the fp8 products; three products ("pv_fp8"
-  // = 0, pv_guard = NULL) keep fp32.  The size cap counts both caches; beyond it the plan is the fp32 one.  Everything else - small
-  // grids, "precision" 1 / 2 - keeps what it has: the default asks for 256 row blocks, as the two-launch plan of uniform batches does
-  // (a smaller ragged batch on that plan keeps the fp32 cache and the role prologue, whatever its knobs say); "compat_16" = 2 takes
-  // every grid of the two-launch plan, with the prologue as kernels of its own (what the tests of small shapes use)
-  if ((t.compat_16 == 2 || (t.compat_16 == 1 && W >= 256)) && p.form == EncoderPlan::kLinear && p.pipelined && !p.half && p.fmt == 0 &&
-      (t.pv_fp8 == 2 || (t.pv_fp8 == 1 && w->pv_guard))) {
-    const size_t fb = t.pv_fp8 == 1 ? cache_floats : 0;
-    if ((cache_floats / 2 + fb) * 4 <= cache_cap) {
-      p.fmt = 2;
-      p.cache_floats = cache_floats / 2;
-      p.cache_fb_floats = fb;
-      p.c16_guard = fb != 0;
-    }
-  }
-  // "kv_fold": the two-launch plan with the parity numerics of the pipelined kernel - uniform or ragged, the linear kernel whole or as
-  // two roles, Q' in the attention prologue or as an image, either cache format (one rule for all of them: the forms that are compared
-  // bit for bit fold together).  Everything else - small grids, "precision" 1 / 2, weights without the composed block - runs the
-  // unfolded form
-  p.kv_fold = t.kv_fold && p.form == EncoderPlan::kLinear && p.pipelined && !p.half && w->kv_fold != nullptr;
-  // parity arithmetic: V with e4m3 cross planes for the pv_fp8 form of every attention kernel of the fused forms (a weights block
-  // without thresholds, pv_guard = NULL, gets the three-product form under the guarded default, never the unguarded one).  [r5]
-  // "pv_fp8" = 1: guarded per pair and layer on the device; the key-point packing clears the statistics (a superset of the readers)
-  p.v_fp8 = fused && !p.half && (t.pv_fp8 == 2 || (t.pv_fp8 == 1 && w->pv_guard));
-  p.clear_stats = fused && t.pv_fp8 == 1 && w->pv_guard;
-  p.guard = p.clear_stats && !p.half;
-  // [r5] small grids: the prologue is two independent chains of few-workgroup kernels - image side (Fusion-1 context, cross-attention,
-  // feed-forward) and point side (key points, compat cache, layer 0 + first PointCN).  Three launches carry one link of each
-  // (k_pro_*, encoder_h2.hip): the point side runs under the image side instead of behind it.  Same bodies: bit-identical.
-  p.prologue = pro_grid && p.fmt == 0;
-  return p;
-}
-
-// in-situ profiling: an event pair around the attention launch(es) of a layer, recorded on the caller's stream
-static int prof_begin(gmf_handle* h, hipStream_t st, hipEvent_t* ev0, hipEvent_t* ev1) {
-  *ev0 = *ev1 = nullptr;
-  if (!h->profile) return GMF_OK;
-  if (h->prof_used == h->prof_events.size()) {
-    hipEvent_t a, b;
-    GMF_HIP(hipEventCreate(&a));
-    GMF_HIP(hipEventCreate(&b));
-    h->prof_events.emplace_back(a, b);
-  }
-  *ev0 = h->prof_events[h->prof_used].first;
-  *ev1 = h->prof_events[h->prof_used].second;
-  ++h->prof_used;
-  GMF_HIP(hipEventRecord(*ev0, st));
-  return GMF_OK;
-}
-
-// The attention launch of layer `l` (bracketed by the in-situ profiling events when enabled): the dense-`attention` drop-in, the
-// pipelined kernel, the split-fp16 kernel of the kStages form (c from the cache when there is one, else recomputed), or fp32.
-static int run_scattn(gmf_handle* h, const gmf_encoder_weights* w, const EncoderPlan& p, int l, const float* q, const float* k,
-                      const float* v, const float* pts8, const float* x2, float* out, int B, int N, hipStream_t st,
-                      const float* dense_compat, const gmf::CompatCache& cc, const float* tail_vecs = nullptr) {
-  const int tiles = tiles_of(N);
-  const float* wst = w->tail_wst + (size_t)l * w->tail_wst_stride;
-  const float* vecs = tail_vecs ? tail_vecs : w->tail_vec + (size_t)l * w->tail_vec_stride;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (int rc = prof_begin(h, st, &ev0, &ev1)) return rc;
-  if (dense_compat) GMF_HIP(gmf::launch_scattn_dense(q, k, v, dense_compat, x2, wst, vecs, out, B, N, tiles, st));
-  else if (p.pipelined) GMF_HIP(gmf::launch_scattn_h2p(q, k, v, x2, vecs, out, B, N, tiles, st, cc, p.attn_nf, p.attn_ks));
-  else if (p.form == EncoderPlan::kStages)
-    GMF_HIP(gmf::launch_scattn_h2(q, k, v, pts8, x2, wst, vecs, out, B, N, tiles, w->sigma_d, st, cc.dense));
-  else GMF_HIP(gmf::launch_scattn_fp32(q, k, v, pts8, x2, wst, vecs, out, B, N, tiles, w->sigma_d, st));
-  if (ev1) GMF_HIP(hipEventRecord(ev1, st));
-  return GMF_OK;
-}
-
-// Runs Fusion-2 + the spatial-consistency block of layer `l` given f,q,k,v (the kFp32 and kStages forms).
-static int run_block_tail(gmf_handle* h, const gmf_encoder_weights* w, const EncoderPlan& p, int l, const float* f, const float* q,
-                          const float* k, const float* v, const float* pts8, const float* ctx_l, float* x1, float* x2,
-                          float* out, int B, int N, int T, hipStream_t st, const float* dense_compat, const gmf::CompatCache& cc) {
-  const int tiles = tiles_of(N), tt = tiles_of(T);
-  if (p.form == EncoderPlan::kStages) {
-    GMF_HIP(gmf::launch_fusion_attn_h2(true, f, ctx_l, w->attn_wst_h2 + (size_t)l * w->attn_wst_stride,
-                                       w->attn_vec + (size_t)l * w->attn_vec_stride, x1, B, N, tiles, T, tt, st));
-    GMF_HIP(gmf::launch_fusion_ff_h2(x1, w->ff_wst_h2 + (size_t)l * w->ff_wst_stride, w->ff_vec + (size_t)l * w->ff_vec_stride, x2, B,
-                                     tiles, st, cc.part_o, p.ff_hs));   // the attention's partial buffer is free here
-  } else {
-    GMF_HIP(gmf::launch_fusion_attn(true, f, ctx_l, w->attn_wst + (size_t)l * w->attn_wst_stride,
-                                    w->attn_vec + (size_t)l * w->attn_vec_stride, x1, B, N, tiles, T, tt, st));
-    GMF_HIP(gmf::launch_fusion_ff(x1, w->ff_wst + (size_t)l * w->ff_wst_stride, w->ff_vec + (size_t)l * w->ff_vec_stride,
-                                  x2, B, tiles, st));
-  }
-  return run_scattn(h, w, p, l, q, k, v, pts8, x2, out, B, N, st, dense_compat, cc);
-}
-
-// the sizes of a ragged batch (pair_plan.hpp), checked before the call takes a ring slot for its table
-static int check_ragged_sizes(gmf_handle* h, const int* n_points, int B) {
-  const gmf::PairPlanStatus bad = gmf::check_pair_sizes(n_points, B);
-  GMF_REQUIRE(bad != gmf::kPairPlanEmptyPair, GMF_ERR_UNSUPPORTED_SHAPE, "ragged batch: every pair needs at least one correspondence");
-  GMF_REQUIRE(bad != gmf::kPairPlanTooManyRows, GMF_ERR_UNSUPPORTED_SHAPE, "ragged batch: more than 2^31 rows");
-  return GMF_OK;
-}
-
-static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, const float* corr_pos, const float* src_keypts,
-                                const float* tgt_keypts, const float* p_tokens, const float* q_tokens, int B, int N, int T,
-                                float* logits, float* feat_n, float* feat, gmf_stream_t stream, const int* n_points);
-
-int gmf_encoder_forward(gmf_handle* h, const gmf_encoder_weights* w, const float* corr_pos, const float* src_keypts,
-                        const float* tgt_keypts, const float* p_tokens, const float* q_tokens, int B, int N, int T,
-                        float* logits, float* feat_n, float* feat, gmf_stream_t stream) {
-  GMF_REQUIRE(h, GMF_ERR_BAD_ARG, "encoder_forward: null handle");
-  GMF_REQUIRE(B > 0 && N > 0 && T > 0, GMF_ERR_UNSUPPORTED_SHAPE, "encoder_forward: empty input");
-  return encoder_forward_impl(h, w, corr_pos, src_keypts, tgt_keypts, p_tokens, q_tokens, B, N, T, logits, feat_n, feat, stream, nullptr);
-}
-
-int gmf_encoder_forward_ragged(gmf_handle* h, const gmf_encoder_weights* w, const float* corr_pos, const float* src_keypts,
-                               const float* tgt_keypts, const float* p_tokens, const float* q_tokens, const int* n_points, int B,
-                               int T, float* logits, float* feat_n, float* feat, gmf_stream_t stream) {
-  GMF_REQUIRE(h, GMF_ERR_BAD_ARG, "encoder_forward_ragged: null handle");
-  GMF_REQUIRE(n_points, GMF_ERR_BAD_ARG, "encoder_forward_ragged: null n_points");
-  GMF_REQUIRE(B > 0 && T > 0, GMF_ERR_UNSUPPORTED_SHAPE, "encoder_forward_ragged: empty input");
-  return encoder_forward_impl(h, w, corr_pos, src_keypts, tgt_keypts, p_tokens, q_tokens, B, 0, T, logits, feat_n, feat, stream, n_points);
-}
-
-static int encoder_forward_impl(gmf_handle* h, const gmf_encoder_weights* w, const float* corr_pos, const float* src_keypts,
-                                const float* tgt_keypts, const float* p_tokens, const float* q_tokens, int B, int N, int T,
-                                float* logits, float* feat_n, float* feat, gmf_stream_t stream, const int* n_points) {
-  if (int rc = check_weights(h, w)) return rc;
-  GMF_REQUIRE(corr_pos && src_keypts && tgt_keypts && p_tokens && q_tokens && logits && feat_n, GMF_ERR_BAD_ARG,
-              "encoder_forward: null pointer");
-  SetDevice sd(h, stream);
-  hipStream_t st = S(stream);
-  // ragged batch: per-pair sizes from the host; every image keeps a slot of tiles(max n) tiles per pair
-  const bool ragged = n_points != nullptr;
-  int min_tiles = 0;
-  HostTable tab;
-  const HostPart<gmf::PairTab> pairs = tab.add<gmf::PairTab>(ragged ? (size_t)B : 0);
-  RingTaken ring;
-  if (ragged) {
-    long long n_sum = 0;
-    if (int rc = check_ragged_sizes(h, n_points, B)) return rc;
-    if (int rc = ring_take(h, tab, &ring)) return rc;
-    gmf::plan_pair_table(n_points, B, -1.0, 0, pairs.host(ring.host), &N, &n_sum, nullptr);
-    min_tiles = tiles_of(*std::min_element(n_points, n_points + B));
-  }
-  const int L = w->num_layers;
-  const int tiles = tiles_of(N), tt = tiles_of(T);
-  const EncoderPlan p = plan_encoder(h->tune, w, B, N, T, L, min_tiles, cu_count());
-  // checked BEFORE the workspace is reserved and anything is launched
-  GMF_REQUIRE(p.fused() || !ragged, GMF_ERR_UNSUPPORTED_SHAPE,
-              "encoder_forward_ragged: ragged batches run on the default path only (split-fp16 weight images, at least two layers, the "
-              "compat cache, \"fused_linear\" = 1, \"scattn_variant\" = 18)");
-  const size_t act = p.act, tok = p.tok;
-  char* dtab;
-  float *featA, *featB, *f, *q, *k, *v, *x1, *x2, *pts8, *pimg, *qimg, *f1ctx, *x1t, *imgfeat, *ctxall, *c_dense, *c_dense_fb, *ff_part,
-      *part_o, *part_ml;
-  unsigned *v_scale, *fstat;
-  if (int rc = arena_carve(h, {arena_buf(dtab, tab.bytes()), arena_buf(featA, act), arena_buf(featB, act), arena_buf(f, act),
-                               arena_buf(q, act), arena_buf(k, act), arena_buf(v, act), arena_buf(x1, act), arena_buf(x2, act),
-                               arena_buf(pts8, (size_t)B * tiles * 32 * 8), arena_buf(pimg, tok), arena_buf(qimg, tok),
-                               arena_buf(f1ctx, tok), arena_buf(x1t, tok), arena_buf(imgfeat, tok),
-                               arena_buf(ctxall, (size_t)(L > 0 ? L : 1) * tok),
-                               // scale words of the V and K images' e4m3 planes ("pv_fp8"): per tile [V: 64 | K: 64]
-                               arena_buf(v_scale, (size_t)B * tiles * 128),
-                               // "pv_fp8" guard: [layer][pair] max row |f_l|^2 (float bits), one 128-byte line per pair
-                               arena_buf(fstat, (size_t)(L + 1) * B * gmf::kPvStatStride),
-                               arena_buf(c_dense, p.cache_floats),
-                               arena_buf(c_dense_fb, p.cache_fb_floats),      // "compat_16": the fp32 cache of the pairs the guard trips
-                               // small grids: feed-forward partials beside the attention's
-                               arena_buf(ff_part, p.max_splits == 8 ? 8 * act : 0),
-                               arena_buf(part_o, p.max_splits * act),
-                               arena_buf(part_ml, (size_t)p.max_splits * B * tiles * 64)}))
-    return rc;
-  if (int rc = ragged ? ring_upload(h, ring, dtab, st) : GMF_OK) return rc;
-  const gmf::PairTab* const ptab = ragged ? pairs.dev(dtab) : nullptr;
-  gmf::CompatCache cc{c_dense, nullptr, part_o, part_ml};
-  cc.half = p.half;
-  cc.fmt = p.fmt;
-  cc.dense_fb = p.c16_guard ? c_dense_fb : nullptr;
-  cc.ptab = ptab;
-  cc.v_scale = p.v_fp8 ? v_scale : nullptr;
-  unsigned* const zero_words = p.clear_stats ? fstat : nullptr;
-  const int n_zero = p.clear_stats ? (L + 1) * B * gmf::kPvStatStride : 0;
-  if (p.prologue) {
-    GMF_HIP(gmf::launch_pro_ctx_pts(p_tokens, w->f1_ctx_wst_h2, w->f1_ctx_vec, f1ctx, B, T, tt, src_keypts, tgt_keypts, pts8, N, st, ptab,
-                                    zero_words, n_zero));
-    GMF_HIP(gmf::launch_pro_fattn_compat(q_tokens, f1ctx, w->f1_attn_wst_h2, w->f1_attn_vec, x1t, B, T, tt, pts8, c_dense, N, tiles,
-                                         w->sigma_d, st, ptab));
-    gmf::PvGuard g0;
-    if (p.guard) g0.stat_next = fstat;
-    GMF_HIP(gmf::launch_pro_ff_front(x1t, w->f1_ff_wst_h2, w->f1_ff_vec, imgfeat, B, tt, part_o, p.f1_ff_hs, corr_pos, w->front_wst_h2,
-                                     w->front_vec, f, q, k, v, N, tiles, st, ptab, g0));
-    if (p.f1_ff_hs > 1) GMF_HIP(gmf::launch_ff_reduce_h2(part_o, x1t, w->f1_ff_vec, imgfeat, B, tt, p.f1_ff_hs, st));
-    GMF_HIP(gmf::launch_ctx_prep_h2(true, imgfeat, w->ctx_wst_h2, w->ctx_vec, ctxall, B, T, tt, L, w->ctx_wst_stride, w->ctx_vec_stride, st));
-  } else {
-    // Fusion-1: image_feat = FusionLayer(p_tok (context), queries = q_tok), pe = False (PointDSC.py:137)
-    if (p.f1_h2) {
-      // (the two token tensors are read row-major: no packing launches in front of these few-workgroup kernels)
-      GMF_HIP(gmf::launch_ctx_prep_h2(false, p_tokens, w->f1_ctx_wst_h2, w->f1_ctx_vec, f1ctx, B, T, tt, 1, 0, 0, st, true));
-      GMF_HIP(gmf::launch_fusion_attn_h2(false, q_tokens, f1ctx, w->f1_attn_wst_h2, w->f1_attn_vec, x1t, B, T, tt, T, tt, st, true));
-      GMF_HIP(gmf::launch_fusion_ff_h2(x1t, w->f1_ff_wst_h2, w->f1_ff_vec, imgfeat, B, tt, st, part_o, p.f1_ff_hs));
-    } else {
-      GMF_HIP(gmf::launch_pack_p32(p_tokens, pimg, B, T, kC, (long)T * kC, kC, 1, st));
-      GMF_HIP(gmf::launch_pack_p32(q_tokens, qimg, B, T, kC, (long)T * kC, kC, 1, st));
-      GMF_HIP(gmf::launch_ctx_prep(false, pimg, w->f1_ctx_wst, w->f1_ctx_vec, f1ctx, B, T, tt, 1, 0, 0, st));
-      GMF_HIP(gmf::launch_fusion_attn(false, qimg, f1ctx, w->f1_attn_wst, w->f1_attn_vec, x1t, B, T, tt, T, tt, st));
-      GMF_HIP(gmf::launch_fusion_ff(x1t, w->f1_ff_wst, w->f1_ff_vec, imgfeat, B, tt, st));
-    }
-    // context side of all L Fusion-2 layers in one launch
-    if (L > 0) {
-      if (p.form != EncoderPlan::kFp32) GMF_HIP(gmf::launch_ctx_prep_h2(true, imgfeat, w->ctx_wst_h2, w->ctx_vec, ctxall, B, T, tt, L,
-                                                                         w->ctx_wst_stride, w->ctx_vec_stride, st));
-      else GMF_HIP(gmf::launch_ctx_prep(true, imgfeat, w->ctx_wst, w->ctx_vec, ctxall, B, T, tt, L, w->ctx_wst_stride,
-                                        w->ctx_vec_stride, st));
-    }
-    GMF_HIP(gmf::launch_pack_pts8(src_keypts, tgt_keypts, pts8, B, N, st, ptab, zero_words, n_zero));
-    if (p.cache) GMF_HIP(gmf::launch_compat_build(pts8, c_dense, B, N, tiles, w->sigma_d, p.fmt, st, ptab));
-  }
-
-  float* cur = featA;
-  float* nxt = featB;
-  // The fused forms (the default): the layer's PointCN runs in the PREVIOUS layer's attention epilogue (layer 0: a small f-only
-  // kernel).  kLinear, two launches per layer:
-  //   k_linear_h2 : f -> Q', K, V (split-fp16 images) and x2 = Fusion-2(f)
-  //   k_scattn_h2p: Q', K, V, c, x2 -> f_{l+1} = ReLU(PointCN_{l+1}(fc_message(attention) + x2))   (last layer: the features)
-  if (p.fused()) {
-    if (!p.prologue) {                            // (small grids: the prologue's third launch ran it)
-      gmf::PvGuard g0;
-      if (p.guard) g0.stat_next = fstat;
-      GMF_HIP(gmf::launch_front_h2(3, p.front_split, corr_pos, w->front_wst_h2, w->front_vec, f, q, k, v, B, N, tiles, st, ptab, nullptr, g0));
-    }
-    for (int l = 0; l < L; ++l) {
-      // the guard's statistics: f_0's is raised by the front kernel, f_{l+1}'s by the attention epilogue / merge kernels of layer l -
-      // always before the kernels that read it
-      cc.guard = gmf::PvGuard{};
-      if (p.guard) cc.guard = gmf::PvGuard{fstat + (size_t)l * B * gmf::kPvStatStride, w->pv_guard + l, fstat + (size_t)(l + 1) * B * gmf::kPvStatStride};
-      const float* fw = w->front_wst_h2 + (size_t)l * w->front_wst_stride;
-      const float* fv = w->front_vec + (size_t)l * w->front_vec_stride;
-      const float* aw = w->attn_wst_h2 + (size_t)l * w->attn_wst_stride;
-      const float* av = w->attn_vec + (size_t)l * w->attn_vec_stride;
-      const float* ffw = w->ff_wst_h2 + (size_t)l * w->ff_wst_stride;
-      const float* ffv = w->ff_vec + (size_t)l * w->ff_vec_stride;
-      const float* ctx_l = ctxall + (size_t)l * tok;
-      const bool last = (l + 1 == L);
-      const float* tail_vecs = nullptr;            // "kv_fold": the epilogue's vectors with Wa bv + ba (else the layer's own, run_scattn)
-      cc.tail_wst_h2 = w->tail_wst_h2 + (size_t)l * w->tail_wst_stride;
-      cc.next_wst_h2 = last ? nullptr : w->front_wst_h2 + (size_t)(l + 1) * w->front_wst_stride;
-      cc.next_bias = last ? nullptr : w->front_vec + (size_t)(l + 1) * w->front_vec_stride;
-      if (p.form == EncoderPlan::kLinear) {
-        cc.qf_img = p.q_in_attn ? f : nullptr;
-        cc.qw_wst = p.q_in_attn ? fw + 4 * kTileFloats : nullptr;
-        cc.qw_bias = p.q_in_attn ? fv + kC : nullptr;
-        const float* kvf = p.kv_fold ? w->kv_fold + (size_t)l * GMF_KV_FOLD_STRIDE : nullptr;
-        const float* kvf_vecs = kvf ? kvf + 9 * kTileFloats : nullptr;        // Wk^T bq' | Wq'^T bk | bk . bq' (128) | the epilogue's vectors
-        if (kvf) {
-          cc.qf_img = f;                                                       // (beta comes from the f tile with or without a Q' image)
-          cc.qw_wst = p.q_in_attn ? kvf : nullptr;
-          cc.qw_bias = p.q_in_attn ? kvf_vecs : nullptr;
-          cc.tail_wst_h2 = kvf + 4 * kTileFloats;
-          cc.kvf_vec = kvf_vecs + kC;
-          tail_vecs = kvf_vecs + 3 * kC;
-        }
-        // "compat_16": a pair that trips the guard at this layer for the first time gets its fp32 cache from one more role of this
-        // launch (fstat[l] is complete: the front kernel / the previous layer's attention and merge raised it)
-        gmf::LazyCompat lazy;
-        if (p.c16_guard) lazy = gmf::LazyCompat{c_dense_fb, pts8, fstat, w->pv_guard, l, 1.0f / (w->sigma_d * w->sigma_d)};
-        GMF_HIP(gmf::launch_linear_h2(p.roles, f, fw, fv, ctx_l, aw, av, ffw, ffv, p.q_in_attn ? nullptr : q, k, v, x2, B, N, tiles, T, tt,
-                                      st, p.one_product, ptab, cc.v_scale, cc.guard, kvf, kvf_vecs, lazy));
-      } else if (p.form == EncoderPlan::kSmall3) {
-        // three launches: {Q' | K | V | cross-attention} -> {key-split attention | hidden-split feed-forward} -> merge
-        GMF_HIP(gmf::launch_small_front_fattn(f, fw, fv, ctx_l, aw, av, q, k, v, x1, B, N, tiles, T, tt, st, cc.v_scale, cc.guard,
-                                              h->tune.small_fattn_tile, ptab));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (int rc = prof_begin(h, st, &e0, &e1)) return rc;
-        GMF_HIP(gmf::launch_small_attn_ff_merge(q, k, v, x1, ffw, ffv, ff_part, p.ff_hs, w->tail_vec + (size_t)l * w->tail_vec_stride,
-                                                last ? cur : f, B, N, tiles, p.attn_ks, st, &cc, h->tune.small_merge_tile));
-        if (e1) GMF_HIP(hipEventRecord(e1, st));
-        continue;
-      } else {
-        // (projecting Q'/K/V on a side stream beside the Fusion-2 kernels, forked and joined with events, was measured at
-        // B = 1: 1.62 vs 1.58 ms at N = 5000, 1.08 vs 1.00 ms at N = 1000 - the event round trips cost more than the overlap gives)
-        GMF_HIP(gmf::launch_front_h2(2, p.front_split, f, fw, fv, f, q, k, v, B, N, tiles, st, nullptr, cc.v_scale, cc.guard));
-        GMF_HIP(gmf::launch_fusion_attn_h2(true, f, ctx_l, aw, av, x1, B, N, tiles, T, tt, st));
-        GMF_HIP(gmf::launch_fusion_ff_h2(x1, ffw, ffv, x2, B, tiles, st, part_o, p.ff_hs));
-      }
-      if (int rc = run_scattn(h, w, p, l, q, k, v, pts8, x2, last ? cur : f, B, N, st, nullptr, cc, tail_vecs)) return rc;
-    }
-    GMF_HIP(gmf::launch_head(cur, w->head_wst, w->head_vec, logits, feat_n, feat, B, N, tiles, st, h->status_dev, ptab,
-                             p.guard ? fstat : nullptr, p.guard ? w->pv_guard : nullptr, L));
-    return GMF_OK;
-  }
-  if (L == 0) {
-    // degenerate: features are layer0(corr_pos) only
-    GMF_HIP(gmf::launch_front(1, corr_pos, w->front_wst, w->front_vec, cur, q, k, v, B, N, tiles, st));
-  }
-  for (int l = 0; l < L; ++l) {
-    const float* in = (l == 0) ? corr_pos : cur;
-    if (p.form == EncoderPlan::kStages)
-      GMF_HIP(gmf::launch_front_h2(l == 0 ? 1 : 0, p.front_split, in, w->front_wst_h2 + (size_t)l * w->front_wst_stride,
-                                   w->front_vec + (size_t)l * w->front_vec_stride, f, q, k, v, B, N, tiles, st));
-    else GMF_HIP(gmf::launch_front(l == 0 ? 1 : 0, in, w->front_wst + (size_t)l * w->front_wst_stride,
-                                   w->front_vec + (size_t)l * w->front_vec_stride, f, q, k, v, B, N, tiles, st));
-    cc.tail_wst_h2 = w->tail_wst_h2 ? w->tail_wst_h2 + (size_t)l * w->tail_wst_stride : nullptr;
-    if (int rc = run_block_tail(h, w, p, l, f, q, k, v, pts8, ctxall + (size_t)l * tok, x1, x2, nxt, B, N, T, st, nullptr, cc)) return rc;
-    float* t = cur; cur = nxt; nxt = t;
-  }
-  GMF_HIP(gmf::launch_head(cur, w->head_wst, w->head_vec, logits, feat_n, feat, B, N, tiles, st, h->status_dev));
-  return GMF_OK;
-}
-
-int gmf_nonlocal_block_forward(gmf_handle* h, const gmf_encoder_weights* w, int layer, int apply_pointcn,
-                               const float* feat_img, const float* pts8, const float* attention,
-                               const float* image_feat_img, float* out_img, int B, int N, int T, gmf_stream_t stream) {
-  GMF_REQUIRE(h, GMF_ERR_BAD_ARG, "nonlocal_block_forward: null handle");
-  if (int rc = check_weights(h, w)) return rc;
-  GMF_REQUIRE(feat_img && image_feat_img && out_img, GMF_ERR_BAD_ARG, "nonlocal_block_forward: null pointer");
-  GMF_REQUIRE((pts8 != nullptr) != (attention != nullptr), GMF_ERR_BAD_ARG, "nonlocal_block_forward: pass exactly one of pts8 / attention");
-  GMF_REQUIRE(layer >= 0 && layer < w->num_layers, GMF_ERR_BAD_ARG, "nonlocal_block_forward: layer out of range");
-  GMF_REQUIRE(B > 0 && N > 0 && T > 0, GMF_ERR_UNSUPPORTED_SHAPE, "nonlocal_block_forward: empty input");
-  GMF_REQUIRE(apply_pointcn == 0 || apply_pointcn == 1, GMF_ERR_BAD_ARG, "nonlocal_block_forward: bad flag");
-  SetDevice sd(h, stream);
-  hipStream_t st = S(stream);
-  const int tiles = tiles_of(N), tt = tiles_of(T);
-  // one layer: no compat cache, so the kFp32 or kStages form (the dense-compat kernel consumes fp32 images: kFp32)
-  const EncoderPlan p = plan_encoder(h->tune, w, B, N, T, 1, 0, cu_count(), attention != nullptr);
-  float *f, *q, *k, *v, *x1, *x2, *ctx;
-  if (int rc = arena_carve(h, {arena_buf(f, p.act), arena_buf(q, p.act), arena_buf(k, p.act), arena_buf(v, p.act), arena_buf(x1, p.act),
-                               arena_buf(x2, p.act), arena_buf(ctx, p.tok)}))
-    return rc;
-  // apply_pointcn = 0: the caller's feat is already the block input (NonLocalBlock.forward, PointDSC.py:40-45)
-  if (p.form == EncoderPlan::kStages) {
-    GMF_HIP(gmf::launch_front_h2(apply_pointcn ? 0 : 2, p.front_split, feat_img, w->front_wst_h2 + (size_t)layer * w->front_wst_stride,
-                                 w->front_vec + (size_t)layer * w->front_vec_stride, f, q, k, v, B, N, tiles, st));
-    GMF_HIP(gmf::launch_ctx_prep_h2(true, image_feat_img, w->ctx_wst_h2 + (size_t)layer * w->ctx_wst_stride,
-                                    w->ctx_vec + (size_t)layer * w->ctx_vec_stride, ctx, B, T, tt, 1, 0, 0, st));
-  } else {
-    GMF_HIP(gmf::launch_front(apply_pointcn ? 0 : 2, feat_img, w->front_wst + (size_t)layer * w->front_wst_stride,
-                              w->front_vec + (size_t)layer * w->front_vec_stride, f, q, k, v, B, N, tiles, st));
-    GMF_HIP(gmf::launch_ctx_prep(true, image_feat_img, w->ctx_wst + (size_t)layer * w->ctx_wst_stride,
-                                 w->ctx_vec + (size_t)layer * w->ctx_vec_stride, ctx, B, T, tt, 1, 0, 0, st));
-  }
-  gmf::CompatCache cc{nullptr, w->tail_wst_h2 ? w->tail_wst_h2 + (size_t)layer * w->tail_wst_stride : nullptr, nullptr, nullptr};
-  return run_block_tail(h, w, p, layer, f, q, k, v, pts8, ctx, x1, x2, out_img, B, N, T, st, attention, cc);
-}
-
-int gmf_fusion_layer_forward(gmf_handle* h, int pe, int latent_dim, int d_head, const float* ctx_wst, const float* ctx_vec,
-                             const float* attn_wst, const float* attn_vec, const float* ff_wst, const float* ff_vec,
-                             const float* data, const float* queries, long long q_sb, long long q_sr, long long q_sk,
-                             float* out, long long o_sb, long long o_sr, long long o_sk, int B, int N, int T,
-                             gmf_stream_t stream, const float* ff_wst_h2, const float* ctx_wst_h2, const float* attn_wst_h2) {
-  GMF_REQUIRE(h && ctx_wst && ctx_vec && attn_wst && attn_vec && ff_wst && ff_vec && data && queries && out,
-              GMF_ERR_BAD_ARG, "fusion_layer_forward: null pointer");
-  GMF_REQUIRE((ctx_wst_h2 == nullptr) == (attn_wst_h2 == nullptr), GMF_ERR_BAD_ARG,
-              "fusion_layer_forward: ctx_wst_h2 and attn_wst_h2 go together (the attention reads the context image the "
-              "context kernel of the same kind writes)");
-  GMF_REQUIRE(B > 0 && N > 0 && T > 0, GMF_ERR_UNSUPPORTED_SHAPE, "fusion_layer_forward: empty input");
-  const bool narrow = (latent_dim == 128 && d_head == 64), wide = (latent_dim == 256 && d_head == 128);
-  GMF_REQUIRE(narrow || wide, GMF_ERR_UNSUPPORTED_SHAPE,
-              "fusion_layer_forward: kernels exist for (latent_dim, d_head) = (128, 64) and (256, 128), context dim 128");
-  SetDevice sd(h, stream);
-  hipStream_t st = S(stream);
-  const int tiles = tiles_of(N), tt = tiles_of(T);
-  const size_t act = (size_t)B * tiles * 32 * latent_dim;
-  const size_t tok = (size_t)B * tt * kTileFloats;
-  const size_t ctxsz = wide ? 2 * tok : tok;
-  // small grids of the wide layer: the feed-forward's hidden chunks are split over hs workgroups per row block
-  const int ff_hs_w = (wide && ff_wst_h2 && h->tune.ff_split != 1) ?
-                          (h->tune.ff_split > 1 ? h->tune.ff_split : gmf::plan_ff_split_w(((tiles + 3) / 4) * B)) : 1;
-  float *xin, *x1, *x2, *cimg, *ctx, *ff_part_w;
-  if (int rc = arena_carve(h, {arena_buf(xin, act), arena_buf(x1, act), arena_buf(x2, act), arena_buf(cimg, tok), arena_buf(ctx, ctxsz),
-                               arena_buf(ff_part_w, ff_hs_w > 1 ? (size_t)ff_hs_w * act : 0)}))
-    return rc;
-  // the split-fp16 kernels of the 256-wide layer read the context tokens row-major and (hidden-split feed-forward) write the
-  // output through its strides: on the small grids this layer usually runs on, a packing pass is a launch like any other
-  const bool wide_direct = wide && attn_wst_h2 != nullptr;
-  if (!wide_direct) GMF_HIP(gmf::launch_pack_p32(data, cimg, B, T, kC, (long)T * kC, kC, 1, st));
-  GMF_HIP(gmf::launch_pack_p32(queries, xin, B, N, latent_dim, q_sb, q_sr, q_sk, st));
-  if (narrow) {
-    if (attn_wst_h2) {
-      GMF_HIP(gmf::launch_ctx_prep_h2(pe != 0, cimg, ctx_wst_h2, ctx_vec, ctx, B, T, tt, 1, 0, 0, st));
-      GMF_HIP(gmf::launch_fusion_attn_h2(pe != 0, xin, ctx, attn_wst_h2, attn_vec, x1, B, N, tiles, T, tt, st));
-    } else {
-      GMF_HIP(gmf::launch_ctx_prep(pe != 0, cimg, ctx_wst, ctx_vec, ctx, B, T, tt, 1, 0, 0, st));
-      GMF_HIP(gmf::launch_fusion_attn(pe != 0, xin, ctx, attn_wst, attn_vec, x1, B, N, tiles, T, tt, st));
-    }
-    if (ff_wst_h2) GMF_HIP(gmf::launch_fusion_ff_h2(x1, ff_wst_h2, ff_vec, x2, B, tiles, st));
-    else GMF_HIP(gmf::launch_fusion_ff(x1, ff_wst, ff_vec, x2, B, tiles, st));
-  } else {
-    if (attn_wst_h2) {
-      GMF_HIP(gmf::launch_ctx_prep_w_h2(pe != 0, data, ctx_wst_h2, ctx_vec, ctx, B, T, tt, st, true));
-      GMF_HIP(gmf::launch_fusion_attn_w_h2(pe != 0, xin, ctx, attn_wst_h2, attn_vec, x1, B, N, tiles, T, tt, st, h->tune.wide_attn_tile));
-    } else {
-      GMF_HIP(gmf::launch_ctx_prep_w(pe != 0, cimg, ctx_wst, ctx_vec, ctx, B, T, tt, st));
-      GMF_HIP(gmf::launch_fusion_attn_w(pe != 0, xin, ctx, attn_wst, attn_vec, x1, B, N, tiles, T, tt, st));
-    }
-    if (ff_wst_h2 && ff_hs_w > 1) {                 // the partials' reduction writes the caller's tensor
-      GMF_HIP(gmf::launch_fusion_ff_w_h2(x1, ff_wst_h2, ff_vec, x2, B, tiles, st, ff_part_w, ff_hs_w, out, o_sb, o_sr, o_sk, N, h->status_dev));
-      return GMF_OK;
-    }
-    if (ff_wst_h2) GMF_HIP(gmf::launch_fusion_ff_w_h2(x1, ff_wst_h2, ff_vec, x2, B, tiles, st, ff_part_w, ff_hs_w));
-    else GMF_HIP(gmf::launch_fusion_ff_w(x1, ff_wst, ff_vec, x2, B, tiles, st));
-  }
-  GMF_HIP(gmf::launch_unpack_p32(x2, out, B, N, latent_dim, o_sb, o_sr, o_sk, st, h->status_dev));
-  return GMF_OK;
-}
 
 // ---------------------------------------------------------------------------------------------
 int gmf_pick_seeds(gmf_handle* h, const float* src_keypts, const float* scores, int B, int N, float nms_radius,

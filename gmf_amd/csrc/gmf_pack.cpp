@@ -340,7 +340,8 @@ void pack_tail(const StateDict& sd, int layer, Img kind, Ctx& cx, std::vector<fl
 // tiles of the large-grid attention are the layer input f itself,
 //     q'_i . (Wk f_j + bk) = f_j . q~_i + beta_i          q~ = (Wk^T Wq') f + Wk^T bq',   beta = (Wq'^T bk) . f + bk . bq'
 //     sum_j p_ij (Wv f_j + bv) = Wv (sum_j p_ij f_j) + bv  (a softmax row sums to 1): Wv, bv compose with fc_message's first layer.
-// Every composed value is formed in fp64 from the fp32 factors and rounded ONCE.  GMF_KV_FOLD_STRIDE floats:
+// Every composed value is formed in fp64 from the fp32 factors and rounded ONCE.  GMF_KV_FOLD_STRIDE floats, each piece at its named
+// offset (layer_weights.hpp, where the forward finds it):
 //   Wk^T Wq' [4 stages] | Wa Wv, Wb, Wc [5 stages] | Wk^T bq' [128] | Wq'^T bk [128] | bk . bq' [1 + 127 zeros] | Wa bv + ba [64] | bb | bc
 void pack_kv_fold(const StateDict& sd, int layer, Ctx& cx, std::vector<float>& out) {
   const std::string n = "encoder.blocks.NonLocal_layer_" + std::to_string(layer) + ".";
@@ -379,20 +380,28 @@ void pack_kv_fold(const StateDict& sd, int layer, Ctx& cx, std::vector<float>& o
     for (int m = 0; m < kCw; ++m) a += (double)Wa.at(r, m) * (double)bv[m];
     baf[r] = (float)a;
   }
+  auto starts = [&](size_t piece) {              // the next piece begins at its offset in the block
+    if (out.size() - base != piece) throw PackError{GMF_ERR_BAD_ARG, "gmf: pack: kv_fold block layout"};
+  };
+  starts(gmf::kKvfQWst);
   cx.img(out, Wqf, Img::H2S);
+  starts(gmf::kKvfTailWst);
   cx.img(out, Waf, Img::H2S);
   Ctx copy;                                       // (Wb, Wc, bb, bc: the values of pack_tail)
   std::vector<float> tw, tv;
   pack_tail(sd, layer, Img::H2S, copy, tw, &tv);
   if (!copy.ok) cx.ok = false;
   out.insert(out.end(), tw.begin() + 2 * 4096, tw.end());
+  starts(gmf::kKvfQBias);
   append(out, bqf);
+  starts(gmf::kKvfVec);
   append(out, u);
   out.push_back((float)b0);
   append_zeros(out, kCw - 1);
+  starts(gmf::kKvfTailVec);
   append(out, baf);
   out.insert(out.end(), tv.begin() + 64, tv.end());
-  if (out.size() - base != (size_t)GMF_KV_FOLD_STRIDE) throw PackError{GMF_ERR_BAD_ARG, "gmf: pack: kv_fold block size"};
+  starts(GMF_KV_FOLD_STRIDE);
 }
 
 // classification head (PointDSC.py:175-181)   (packing.pack_head)

@@ -1,12 +1,17 @@
-// Internal C++ launch entry points (one per kernel family).  The public C ABI is include/gmf_hip.h.
+// Internal C++ launch entry points of the encoder, matching, validation, training and image kernels, with the structs their
+// kernels take by value (PvGuard, LazyCompat) and the two argument blocks of the encoder's layer launches (ForwardBuffers, LayerRun).
+// The other kernel families have a launchers_*.hpp each.  The public C ABI is include/gmf_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "layer_weights.hpp"
 #include "pair_plan.hpp"
 
 namespace gmf {
 
 // struct PairTab, the per-pair table of a ragged batch, and its host plan: pair_plan.hpp
+// struct Tuning, the per-handle knobs with their table, and the plan of an encoder forward: encoder_plan.hpp (free of HIP)
+// struct LayerWeights, one layer's weight pointers, and the layout of a kv_fold block: layer_weights.hpp (free of HIP)
 
 // The "pv_fp8" guard (gmf_set_tuning "pv_fp8" = 1, the default): which of a layer's pairs run the P V cross products of
 // the spatial-consistency attention on the fp8 pipe is decided ON THE DEVICE, per pair, from a statistic the previous kernel
@@ -20,38 +25,6 @@ struct PvGuard {
   const unsigned* stat = nullptr;   // [B][kPvStatStride] float bits of max row |f_l|^2 per pair (word 0 of its line), complete before the layer's first launch; null: unguarded
   const float* thr2 = nullptr;      // the layer's threshold: fp8 cross products while stat <= *thr2
   unsigned* stat_next = nullptr;    // [B] the NEXT layer's statistic: raised (atomic maximum) by whoever produces f_{l+1}; null: nobody asks
-};
-
-// compat matrix built once per batch by launch_compat_build (see k_compat_build): [B, tiles, tiles, 1024] floats.  The buffers and
-// per-layer weights of the split-fp16 attention; `half` and `fmt` are copied from the forward's plan (gmf_api.cpp, EncoderPlan)
-struct CompatCache {
-  const float* dense;
-  const float* tail_wst_h2;   // this layer's fc_message weights as split-fp16 images (epilogue of k_scattn_h2p)
-  float* part_o;              // key-split workspace: [max splits][B * tiles] P32 tile images (or nullptr)
-  float* part_ml;             // ... [max splits][B * tiles][32][2] row maximum, row sum
-  // when non-null, the attention epilogue applies the NEXT layer's PointCN (4 split-fp16 weight stages + bias) to the block
-  // output and stores f_{l+1} instead of feat (k_scattn_h2p / k_scattn_merge only)
-  const float* next_wst_h2 = nullptr;
-  const float* next_bias = nullptr;
-  bool half = false;          // `dense` holds fp16 tiles (2 KiB each) and the attention multiplies one fp16 product: the
-                              // throughput numerics mode (Tuning::precision = 1), large grids only (then fmt = 1)
-  const PairTab* ptab = nullptr;   // ragged batch: per-pair rows (device), else null
-  int fmt = 0;                // element format of `dense` (k_compat_build): 0 = fp32 (4 KiB per tile); 16-bit, 2 KiB per tile:
-                              // 1 = fp16 c (with `half`), 2 = fixed point rint(65535 c)
-  unsigned* v_scale = nullptr;   // non-null: the layer's V image carries e4m3 cross planes (store_block_v8) and these are their
-                                 // scale words, [B * tiles][64]; k_linear_h2 writes both, k_scattn_h2p<3, *, true> reads them
-  // [r4] non-null: no Q' image exists - every attention workgroup projects its own Q' in its prologue from the layer's f image
-  // (qf_img), the four Q' weight stages (qw_wst) and bq' (qw_bias, 128 floats); parity kernels of the pipelined form only
-  const float* qf_img = nullptr;
-  const float* qw_wst = nullptr;
-  const float* qw_bias = nullptr;
-  PvGuard guard;              // [r5] per pair: e4m3 cross planes or V's low fp16 plane (with v_scale)
-  // "kv_fold" (EncoderPlan::kv_fold): non-null = the K and V images hold the layer input f, tail_wst_h2 / the epilogue's vectors / qw_* are
-  // the composed weights of gmf_encoder_weights::kv_fold, qf_img is always the layer's f image, and these are Wq'^T bk [128] | bk . bq'
-  const float* kvf_vec = nullptr;
-  // "compat_16" (EncoderPlan::c16_guard): non-null = `dense` holds the 16-bit cache (fmt = 2) for the pairs the guard lets through at
-  // this layer, and this is the exact fp32 cache of the pairs it trips (the layer's linear launch fills it: LazyCompat)
-  const float* dense_fb = nullptr;
 };
 
 // "compat_16": the exact cache of the guarded 16-bit form, built lazily by one more workgroup role of the layer's linear launch (the
@@ -69,49 +42,45 @@ struct LazyCompat {
   float inv_sig2 = 0.f;
 };
 
-// Per-handle tuning knobs (gmf_set_tuning).  Every value selects between forms that compute the same result up to
-// rounding; there is no process-global state and no environment variable behind any of them.
-struct Tuning {
-  int scattn_variant = 18;   // 18 = cached, software-pipelined split-fp16 attention; 9 = split-fp16 without the pipelining
-                             // (and without the cache when compat_cache = 0); 0 = fp32 MFMA path for every stage
-  bool use_cache = true;     // compat cache (built once per batch) for variants 9 / 18
-  int key_splits = 0;        // attention key splits: 0 = automatic (small grids, and the tail of large ones), 1 = off, n = forced
-  bool tail_split = false;   // large grids: split the last partial round of attention workgroups by keys.  Off by default: a CU
-                             // left with one resident workgroup runs it almost twice as fast, so the "half-empty last round" costs
-                             // little (32 x 5000: 1.10 ms split vs 1.07 ms whole, measured)
-  int ff_split = 0;          // feed-forward hidden splits on small grids: 0 = automatic, 1 = off, 2 / 4 / 8 = forced
-  bool front_split = true;   // small grids: one workgroup per output (Q' + f | K | V) of k_front_h2
-  bool wide_attn_tile = true;     // 256-wide layer: cross-attention with one workgroup per tile on grids of up to 256 tiles
-  bool small_merge_tile = true;   // small grids: the merge step with one workgroup per query tile, its waves splitting the feature blocks
-  bool small_fattn_tile = true;   // [r5] small grids: the cross-attention role of the layer's first launch per query tile, context tiles dealt to its waves
-  bool small_roles = true;   // small grids: three launches per layer with two kinds of workgroups each (else five or six)
-  bool fused_linear = true;  // one kernel per layer for Q'/K/V + Fusion-2 (k_linear_h2) with the next PointCN in the attention epilogue
-  int conv_patch = 1;        // stride-1 3x3 convolutions: 1 = LDS patch kernel (automatic form), 2 = never three workgroups per CU, 0 = gather kernel
-  bool small_prologue = true;   // [r5] small grids: the prologue's two chains as roles of shared launches
-  bool conv_small = true;    // [r5] grids of fewer than 128 workgroups of the 128-pixel convolution kernels (a few images): the K-split kernel
-  int nms_binned = 1;        // 1 = grid-binned NMS candidates on large grids, 2 = always, 0 = all pairs
-  bool topk_select = true;   // radix select of the S seeds (false = full bitonic sort)
-  int mid_grid_roles = 512;  // two-launch form on grids below this many base workgroups (>= 256): the linear kernel runs as two
-                             // workgroup roles per row block (Q'/K/V | Fusion-2); 0 = never
-  bool kv_fold = true;          // large grids (two-launch plan, parity numerics, fp32 cache): keys = values = the layer input f, the K and V
-                                // projections composed into the query side and fc_message's first layer (false: the unfolded form, bit for bit)
-  bool q_in_attention = true;   // [r4] large grids: Q' is projected in the attention kernel's prologue, not written by k_linear_h2 (bit-identical)
-  int pv_fp8 = 1;            // parity arithmetic of the default path: the two cross products of O += P V on the block-scaled fp8 matrix
-                             // pipe (scattn_h2p_body<3, *, 4, true>).  1 = guarded per pair and layer on the device
-                             // (PvGuard), 2 = unconditionally, 0 = all three products on the f16 pipe
-  int compat_format = 0;     // element format of the compat cache on the cached, pipelined path: 0 = the plan's choice ("compat_16"); 2 =
-                             // 16-bit fixed point, rint(65535 c), UNCONDITIONALLY: half the attention's c stream and half the build,
-                             // absolute error <= 7.6e-6 on c.  Measured: inside the parity contract on 3DMatch-shape
-                             // inputs, 4-8x the reference's own fp32 noise on ill-conditioned KITTI-shape inputs - so it is opt-in
-  int compat_16 = 1;         // two-launch plan, parity numerics, the guarded fp8 form: the 16-bit cache under the "pv_fp8" guard - per pair
-                             // and layer, 16 bits where the guard lets the fp8 products through, the exact fp32 cache (built on the device
-                             // for the pairs that trip, once per forward) where it does not.  1 = on grids of 256 row blocks and more
-                             // (default), 2 = on every grid of that plan, 0 = fp32 for everyone
-  int precision = 0;         // NOT rounding-equivalent: 0 = parity numerics (fp32-equivalent split-fp16 products, the default);
-                             // 1 = throughput numerics: the spatial-consistency attention multiplies plain
-                             // fp16 operands (one product, fp32 accumulation) and streams c as fp16 - outside the 1e-4 gate
-  int spectral_col_splits = 0;   // spectral matching: column splits of a pair's sweep, 0 = from the pair's N (launchers_spectral.hpp), 1..32 = forced
-  int clique_local_rows = 384;   // maximum clique: a root with at most this many candidates is searched in LDS (launchers_clique.hpp), 0..384
+// What one encoder forward fixes before its layer loop: the compat cache (built once per batch by launch_compat_build, k_compat_build:
+// [B, tiles, tiles, 1024] floats), the key-split partials, the pair table and V's scale words.  `half` and `fmt` are the plan's
+// (encoder_plan.hpp, EncoderPlan).
+struct ForwardBuffers {
+  const float* dense = nullptr;      // the cache; element format `fmt` (k_compat_build): 0 = fp32 (4 KiB per tile); 16-bit, 2 KiB per tile:
+  int fmt = 0;                       // 1 = fp16 c (with `half`), 2 = fixed point rint(65535 c)
+  bool half = false;                 // `dense` holds fp16 tiles and the attention multiplies one fp16 product: the throughput numerics
+                                     // mode (Tuning::precision = 1), large grids only
+  // "compat_16" (EncoderPlan::c16_guard): non-null = `dense` holds the 16-bit cache (fmt = 2) for the pairs the guard lets through at a
+  // layer, and this is the exact fp32 cache of the pairs it trips (the layer's linear launch fills it: LazyCompat)
+  const float* dense_fb = nullptr;
+  float* part_o = nullptr;           // key-split workspace: [max splits][B * tiles] P32 tile images (or nullptr)
+  float* part_ml = nullptr;          // ... [max splits][B * tiles][32][2] row maximum, row sum
+  const PairTab* ptab = nullptr;     // ragged batch: per-pair rows (device), else null
+  unsigned* v_scale = nullptr;       // non-null: the layers' V images carry e4m3 cross planes (store_block_v8) and these are their
+                                     // scale words, [B * tiles][64]; k_linear_h2 writes both, k_scattn_h2p<3, *, true> reads them
+};
+
+// What one layer of it fixes, built in one place from (plan, layer view, buffers): gmf_api_encoder.cpp, layer_run
+struct LayerRun {
+  LayerWeights w;
+  PvGuard guard;                     // per pair: e4m3 cross planes or V's low fp16 plane (with ForwardBuffers::v_scale)
+  // What the attention epilogue (and the merge) runs on: the launchers read these, never w.tail_* / w.next_*.  epi_wst, epi_vec:
+  // fc_message, weights (split-fp16) and vectors - the layer's own or, under "kv_fold", the composed ones.  epi_next_*: the fused forms,
+  // every layer but the last - non-null = the NEXT layer's PointCN (w.next_*) is applied to the block output and f_{l+1} is stored
+  // instead of feat; null: the block output itself (the forms with a front kernel per layer)
+  const float* epi_wst = nullptr;
+  const float* epi_vec = nullptr;
+  const float* epi_next_wst = nullptr;
+  const float* epi_next_bias = nullptr;
+  // qw_wst non-null: no Q' image exists - every attention workgroup projects its own Q' in its prologue from the layer's f image
+  // (qf_img), four weight stages (qw_wst) and a bias (qw_bias, 128 floats); parity kernels of the pipelined form only
+  const float* qf_img = nullptr;
+  const float* qw_wst = nullptr;
+  const float* qw_bias = nullptr;
+  // "kv_fold" (EncoderPlan::kv_fold): non-null = the K and V images hold the layer input f, epi_* / qw_* are the composed weights of
+  // the layer's kv_fold block, qf_img is always the layer's f image, and these are Wq'^T bk [128] | bk . bq'
+  const float* kvf_vec = nullptr;
+  LazyCompat lazy;                   // "compat_16": one more role of the layer's linear launch
 };
 
 hipError_t launch_compat_build(const float* pts8, float* c_dense, int B, int N, int tiles, float sigma_d, int fmt, hipStream_t s,
@@ -124,8 +93,8 @@ hipError_t launch_scattn_fp32(const float* q, const float* k, const float* v, co
 hipError_t launch_scattn_h2(const float* q, const float* k, const float* v, const float* pts8, const float* fus, const float* wst,
                             const float* vecs, float* out, int B, int N, int tiles, float sigma_d, hipStream_t s, const float* c_dense);
 // the cached, pipelined attention (scattn_variant 18): n_full items per XCD whole, the rest split `ksplits` ways by keys
-hipError_t launch_scattn_h2p(const float* q, const float* k, const float* v, const float* fus, const float* vecs, float* out, int B,
-                             int N, int tiles, hipStream_t s, const CompatCache& cc, int n_full, int ksplits);
+hipError_t launch_scattn_h2p(const float* q, const float* k, const float* v, const float* fus, float* out, int B, int N, int tiles,
+                             const ForwardBuffers& fb, const LayerRun& lr, int n_full, int ksplits, hipStream_t s);
 hipError_t launch_scattn_dense(const float* q, const float* k, const float* v, const float* compat, const float* fus,
                                const float* wst, const float* vecs, float* out, int B, int N, int tiles, hipStream_t s);
 hipError_t launch_ctx_prep(bool pe, const float* ctx, const float* wst, const float* vecs, float* out, int B, int T,
@@ -150,25 +119,21 @@ hipError_t launch_fusion_ff_w_h2(const float* x1, const float* wst_h2, const flo
                                  float* part = nullptr, int hs = 1, float* out_rm = nullptr, long o_sb = 0, long o_sr = 0,
                                  long o_sk = 0, int n_rows = 0, int* status = nullptr);
 int plan_ff_split_w(int base_wgs);
-// split: one workgroup per output (Q' + f | K | V); v_scale: V with e4m3 cross planes (CompatCache::v_scale)
+// split: one workgroup per output (Q' + f | K | V); mode 3: corr_pos -> layer0 -> PointCN -> f only; ptab, v_scale, guard: as in
+// ForwardBuffers and LayerRun, null / empty where the caller has none (it serves forms that build neither struct, so it takes the fields)
 hipError_t launch_front_h2(int mode, bool split, const float* in, const float* wst, const float* vecs, float* f, float* q, float* k,
-                           float* v, int B, int N, int tiles, hipStream_t s, const PairTab* ptab = nullptr, unsigned* v_scale = nullptr,
-                           PvGuard guard = {});
-// mode 3: corr_pos -> layer0 -> PointCN -> f only.  launch_linear_h2: all linear stages of one layer from f (k_linear_h2); roles: as
-// two workgroup roles per row block (needs q); q null: no Q' image (CompatCache::qf_img); v_scale: CompatCache::v_scale
-hipError_t launch_linear_h2(bool roles, const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
-                            const float* attn_wst, const float* attn_vec, const float* ff_wst, const float* ff_vec, float* q,
-                            float* k, float* v, float* x2, int B, int N, int tiles, int T, int ttiles, hipStream_t s, bool one_product = false,
-                            const PairTab* ptab = nullptr, unsigned* v_scale = nullptr, PvGuard guard = {}, const float* kvf_wst = nullptr,
-                            const float* kvf_bias = nullptr, LazyCompat lazy = {});   // kvf_*: "kv_fold" - the 4 stages of Wk^T Wq' and Wk^T bq'; K and V become images of f
-// small grids: three launches per layer (k_small_front_fattn | k_small_attn_ff | k_scattn_merge)
-hipError_t launch_small_front_fattn(const float* f, const float* front_wst, const float* front_vec, const float* ctx_img,
-                                    const float* attn_wst, const float* attn_vec, float* q, float* k, float* v, float* x1, int B,
-                                    int N, int tiles, int T, int ttiles, hipStream_t s, unsigned* v_scale = nullptr, PvGuard guard = {},
-                                    bool tile_role = true, const PairTab* ptab = nullptr);   // tile_role: the cross-attention role per query tile (Tuning::small_fattn_tile)
-hipError_t launch_small_attn_ff_merge(const float* q, const float* k, const float* v, const float* x1, const float* ff_wst,
-                                      const float* ff_vecs, float* ff_part, int ff_hs, const float* tail_vecs, float* out, int B,
-                                      int N, int tiles, int ksplits, hipStream_t s, const CompatCache* cc, bool tile_merge = true);
+                           float* v, int B, int N, int tiles, const PairTab* ptab, unsigned* v_scale, PvGuard guard, hipStream_t s);
+// all linear stages of one layer from f (k_linear_h2); roles: as two workgroup roles per row block (needs q); q null: no Q' image
+// (LayerRun::qf_img); lr.kvf_vec non-null: "kv_fold" - q~ from the block's four stages and Wk^T bq', K and V become images of f
+hipError_t launch_linear_h2(bool roles, bool one_product, const float* f, const float* ctx_img, float* q, float* k, float* v, float* x2,
+                            int B, int N, int tiles, int T, int ttiles, const ForwardBuffers& fb, const LayerRun& lr, hipStream_t s);
+// small grids: three launches per layer (k_small_front_fattn | k_small_attn_ff | k_scattn_merge); tile_role, tile_merge: the
+// cross-attention role and the merge per query tile (Tuning::small_fattn_tile, Tuning::small_merge_tile)
+hipError_t launch_small_front_fattn(bool tile_role, const float* f, const float* ctx_img, float* q, float* k, float* v, float* x1, int B,
+                                    int N, int tiles, int T, int ttiles, const ForwardBuffers& fb, const LayerRun& lr, hipStream_t s);
+hipError_t launch_small_attn_ff_merge(bool tile_merge, const float* q, const float* k, const float* v, const float* x1, float* ff_part,
+                                      int ff_hs, float* out, int B, int N, int tiles, int ksplits, const ForwardBuffers& fb,
+                                      const LayerRun& lr, hipStream_t s);
 hipError_t launch_ctx_prep_h2(bool pe, const float* ctx, const float* wst, const float* vecs, float* out, int B, int T,
                               int ttiles, int sets, int wst_stride, int vec_stride, hipStream_t s, bool rowmajor = false);
 hipError_t launch_fusion_attn_h2(bool pe, const float* x, const float* ctx_img, const float* wst, const float* vecs,
