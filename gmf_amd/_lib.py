@@ -161,6 +161,7 @@ SIGNATURES = {
                                 _vp, _vp, _vp, _vp]),
     "gmf_pick_seeds": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _vp, _vp]),
     "gmf_knn_rows": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    "gmf_knn_rows_self_first": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "gmf_knn_from_distances": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "gmf_nn_match": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "gmf_nn_match_batched": (C.c_int, [_vp, _vp, _vp, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),

@@ -34,10 +34,12 @@ def rigid_transform_3d(A, B, weights=None, weight_threshold=0):
     return T
 
 
-def _knn_general(x, kk, normalized):
+def _knn_general(x, kk, normalized, self_first=False):
     """The kk nearest rows BEHIND rank 0 for any feature width and either distance form (common.py:64-69): the distance rows
     xx_j - 2 x_i.x_j (+ xx_i, constant along a row: it does not move the order and is left out) from the library's fp32-MFMA GEMM -
-    exact fp32 products, no operand-range assumptions - then the library's row selection (gmf_knn_from_distances)."""
+    exact fp32 products, no operand-range assumptions - then the library's row selection (gmf_knn_from_distances).
+    `self_first`: the diagonal of the distance rows (they are this function's own) is set to -inf, so rank 0 is the row itself
+    whatever ties with it, and an exact duplicate of the row at a lower index stays among the neighbours."""
     from . import train as T
     bs, N, C = x.shape
     ld = ((N + 31) // 32) * 32
@@ -51,6 +53,8 @@ def _knn_general(x, kk, normalized):
         nbat = min(slab, bs - b0)
         for b in range(nbat):
             T.gemm(x[b0 + b], x[b0 + b], tb=True, alpha=-2.0, bias=col[b0 + b], out=dist[b], m=N, n=N, k=C, lda=C, ldb=C, ldc=ld)
+        if self_first:
+            dist[:nbat].diagonal(dim1=1, dim2=2).fill_(float("-inf"))
         h.call("gmf_knn_from_distances", dist.data_ptr(), nbat, N, N, kk, nb[b0:b0 + nbat].data_ptr(), st)
     return nb
 
@@ -61,9 +65,14 @@ def knn(x, k, ignore_self=False, normalized=True):
     `normalized=True` (unit rows, distance 2 - 2 x x^T - what GMF feeds, PointDSC.py:229,327) at 128 channels runs the pose head's
     path (split-fp16 MFMA distance rows + threshold selection).  [r5] `normalized=False` (xx - 2 x x^T + xx^T, common.py:66-68: the
     form the reference's unused EdgeConv asks for, :94) and any other channel count form the distance rows with the fp32-MFMA GEMM
-    instead (`_knn_general`).  `ignore_self=True`: top-(k+1) with rank 0 dropped; `ignore_self=False`: the row's own index (its
-    distance is the row minimum: 0) followed by its k - 1 nearest - the reference's top-k except among exact duplicates of a row,
-    whose order torch.topk leaves unspecified."""
+    instead (`_knn_general`).
+
+    The order is (distance ascending, index ascending).  `ignore_self=True`: the top-(k+1) with rank 0 dropped, as the reference
+    does it - for a row with a bitwise duplicate at a lower index, rank 0 is that duplicate and the row itself is its first
+    neighbour.  `ignore_self=False`: the row's own index, followed by the k - 1 nearest OTHER rows (the row's own distance entry
+    is forced to rank 0: gmf_knn_rows_self_first / `_knn_general(self_first=True)`).  As a set that is the reference's top-k
+    under (distance, index) whenever the row belongs to it, duplicates of the row included - torch.topk leaves only their order
+    unspecified; indices within a row are pairwise distinct in both forms."""
     x = require_cuda_f32(x, "x").contiguous()
     bs, N, C = x.shape
     kk = k if ignore_self else k - 1                   # neighbours behind rank 0
@@ -81,14 +90,15 @@ def knn(x, k, ignore_self=False, normalized=True):
         nb = torch.empty((bs, N, max(kk, 1)), device=x.device, dtype=torch.int32)
     if kk > 0:
         if general:
-            got = _knn_general(x, kk, normalized)
+            got = _knn_general(x, kk, normalized, self_first=not ignore_self)
             if ignore_self:
                 out = got
             else:
                 out[:, :, 1:] = got
         else:
             h, st = handle_and_stream(x)
-            h.call("gmf_knn_rows", x.data_ptr(), rows.data_ptr(), bs, N, N, kk, nb.data_ptr(), st)
+            h.call("gmf_knn_rows" if ignore_self else "gmf_knn_rows_self_first", x.data_ptr(), rows.data_ptr(), bs, N, N, kk,
+                   nb.data_ptr(), st)
             if not ignore_self:
                 out[:, :, 1:] = nb[:, :, :kk]
     return out.long()

@@ -421,16 +421,19 @@ int gmf_knn_from_distances(gmf_handle* h, const float* dist, int B, int N, int S
   return GMF_OK;
 }
 
-int gmf_knn_rows(gmf_handle* h, const float* feat_n, const int* rows, int B, int N, int Sn, int k, int* knn_out,
-                 gmf_stream_t stream) {
+// self_first: the listed row itself is rank 0 of its distance row whatever ties with it (gmf_knn_rows_self_first)
+static int knn_rows_impl(gmf_handle* h, const float* feat_n, const int* rows, int B, int N, int Sn, int k, int* knn_out,
+                         gmf_stream_t stream, bool self_first) {
   GMF_REQUIRE(h && feat_n && rows && knn_out, GMF_ERR_BAD_ARG, "knn_rows: null pointer");
   GMF_REQUIRE(B > 0 && N > 1 && Sn > 0 && k > 0 && k <= N - 1, GMF_ERR_UNSUPPORTED_SHAPE, "knn_rows: need 0 < k <= N-1");
   SetDevice sd(h, stream);
   hipStream_t st = S(stream);
   if (k > 63) {            // (the selection kernels behind the distance rows rank up to 64 candidates: larger k keeps the in-LDS kNN)
     GMF_REQUIRE((size_t)N * 4 <= 150 * 1024, GMF_ERR_UNSUPPORTED_SHAPE, "knn_rows: k > 63 needs N <= 38400 (the in-LDS kNN)");
-    GMF_HIP(gmf::launch_knn_seeds(feat_n, rows, nullptr, knn_out, B, N, Sn, k, st));
-    return GMF_OK;
+    if (!self_first) {
+      GMF_HIP(gmf::launch_knn_seeds(feat_n, rows, nullptr, knn_out, B, N, Sn, k, st));
+      return GMF_OK;
+    }
   }
   // [r4] the pose head's own path (common.py:53-75 is what both compute): the rows' distances to every row of their pair by
   // MFMA (k_seed_dist on the split-fp16 feature image) and a threshold selection per row - 8 x 5000 x 5000: 10.7 ms -> below 1 ms
@@ -445,19 +448,33 @@ int gmf_knn_rows(gmf_handle* h, const float* feat_n, const int* rows, int B, int
   if (int rc = arena_carve(h, {arena_buf(fimg, (size_t)B * tiles * kTileFloats), arena_buf(dmat, (size_t)(whole ? B : 1) * slice * ld)}))
     return rc;
   GMF_HIP(gmf::launch_pack_rows_h2(feat_n, fimg, B, N, st, nullptr));
-  if (whole) {
-    GMF_HIP(gmf::launch_seed_dist(fimg, rows, dmat, B, N, Sn, st, nullptr));
-    GMF_HIP(gmf::launch_knn_seeds(feat_n, rows, dmat, knn_out, B, N, Sn, k, st, nullptr));
+  // distance rows -> [self first] -> selection, for nb pairs of n rows each
+  auto select = [&](const float* img, const float* f, const int* rb, int* out, int nb, int n) -> int {
+    GMF_HIP(gmf::launch_seed_dist(img, rb, dmat, nb, N, n, st, nullptr));
+    if (self_first) GMF_HIP(gmf::launch_self_first(dmat, rb, nb, N, n, st));
+    if (k > 63) GMF_HIP(gmf::launch_knn_lds(dmat, out, nb, N, n, k, st));
+    else GMF_HIP(gmf::launch_knn_seeds(f, rb, dmat, out, nb, N, n, k, st, nullptr));
     return GMF_OK;
-  }
+  };
+  if (whole) return select(fimg, feat_n, rows, knn_out, B, Sn);
   for (int b = 0; b < B; ++b)
     for (int r0 = 0; r0 < Sn; r0 += slice) {
       const int n = std::min(slice, Sn - r0);
-      const int* rb = rows + (size_t)b * Sn + r0;
-      GMF_HIP(gmf::launch_seed_dist(fimg + (size_t)b * tiles * kTileFloats, rb, dmat, 1, N, n, st, nullptr));
-      GMF_HIP(gmf::launch_knn_seeds(feat_n + (size_t)b * N * 128, rb, dmat, knn_out + ((size_t)b * Sn + r0) * k, 1, N, n, k, st, nullptr));
+      if (int rc = select(fimg + (size_t)b * tiles * kTileFloats, feat_n + (size_t)b * N * 128, rows + (size_t)b * Sn + r0,
+                          knn_out + ((size_t)b * Sn + r0) * k, 1, n))
+        return rc;
     }
   return GMF_OK;
+}
+
+int gmf_knn_rows(gmf_handle* h, const float* feat_n, const int* rows, int B, int N, int Sn, int k, int* knn_out,
+                 gmf_stream_t stream) {
+  return knn_rows_impl(h, feat_n, rows, B, N, Sn, k, knn_out, stream, false);
+}
+
+int gmf_knn_rows_self_first(gmf_handle* h, const float* feat_n, const int* rows, int B, int N, int Sn, int k, int* knn_out,
+                            gmf_stream_t stream) {
+  return knn_rows_impl(h, feat_n, rows, B, N, Sn, k, knn_out, stream, true);
 }
 
 int gmf_nn_match(gmf_handle* h, const float* F0, const float* F1, int N0, int N1, int d, int mode, int* idx_out,

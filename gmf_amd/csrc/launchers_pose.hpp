@@ -13,6 +13,10 @@ size_t nms_scratch_floats(int B, int N);
 hipError_t launch_sort_topk(const Tuning& tune, const float* keys, int* out_idx, int B, int N, int S, hipStream_t s, const PairTab* ptab = nullptr);
 hipError_t launch_knn_seeds(const float* feat_n, const int* seeds, const float* dist_in, int* knn_idx, int B, int N, int S,
                             int k, hipStream_t s, const PairTab* ptab = nullptr);
+// dist [B, S, ld] rows of launch_seed_dist: dist[b][s][rows[b][s]] = -inf, so that the listed row itself is rank 0 of its distance row
+hipError_t launch_self_first(float* dist, const int* rows, int B, int N, int S, hipStream_t s);
+// the in-LDS selection (k_knn_seeds: any k <= N - 1, N <= 38 400) on given distance rows
+hipError_t launch_knn_lds(const float* dist_in, int* knn_idx, int B, int N, int S, int k, hipStream_t s);
 // hsum non-null ([B,S,15] doubles): the centroids and H of the weighted Kabsch problem of the LAST power iterate are summed
 // in the same kernel; launch_seed_kabsch given the same buffer then only runs the SVD (and redoes the sums of pairs whose
 // iteration stopped earlier)

@@ -572,9 +572,13 @@ k_knn_select_fast(const float* __restrict__ dist_in, int* __restrict__ knn_idx, 
   // a row with NaN distances yields fewer than k + 1 candidates: every slot holds an in-range index before the ranks are
   // written (the barriers below order this store before theirs), so no consumer ever gathers through an uninitialised index
   if (tid < k) out[tid] = min(tid + 1, N - 1);
+  // the register slots behind the row (j >= N) hold NaN, not +inf: a NaN is below no minimum and at or below no threshold, so a slot
+  // that is no element of the row can never be a candidate.  (With +inf there, a row with fewer than k + 1 finite entries has
+  // T = +inf, the slots j >= N became candidates and, where fewer than kCandMax of them exist - N = 4999: 121 -, their indices
+  // >= N were written as neighbours.)
   float v[EPT];
 #pragma unroll
-  for (int m = 0; m < EPT; ++m) { const int j = tid + 256 * m; v[m] = (j < N) ? dr[j] : INFINITY; }
+  for (int m = 0; m < EPT; ++m) { const int j = tid + 256 * m; v[m] = (j < N) ? dr[j] : __builtin_nanf(""); }
   float bv = INFINITY; int bm = 0;
 #pragma unroll
   for (int m = 0; m < EPT; ++m) if (v[m] < bv) { bv = v[m]; bm = m; }
@@ -706,7 +710,8 @@ k_knn_select_fast(const float* __restrict__ dist_in, int* __restrict__ knn_idx, 
 // in registers but streamed from global memory twice - once for the per-thread minima that give the threshold T (the (k + 1)-th
 // smallest of the 64 group minima, exactly as above), once to collect the candidates <= T (one LDS atomic per candidate: ~1.5 k of
 // them per row) - and the candidates are ranked under (distance, index) as above.  The output is a function of the row alone, so it
-// equals k_knn_select_fast's wherever both apply (test_knn_stream_equals_register_form).  Adversarial rows (more than kCandMax
+// is the one k_knn_select_fast computes (the two are dispatched at disjoint N; tests/test_gpu_knn_select.py::test_selection_is_stable_argsort
+// holds both, N <= 16 384 and beyond, to the same stable argsort of the row).  Adversarial rows (more than kCandMax
 // candidates) take k + 1 streamed rounds: the next element in (distance, index) order behind the last one extracted.
 // grid (S, B), block 256.
 // ---------------------------------------------------------------------------------------
@@ -1758,6 +1763,31 @@ hipError_t launch_knn_seeds(const float* feat_n, const int* seeds, const float* 
     return hipGetLastError();
   }
   hipLaunchKernelGGL(k_knn_seeds, dim3(S, B), dim3(256), (size_t)N * 4, s, feat_n, seeds, dist_in, knn_idx, N, S, k, ptab, ld);
+  return hipGetLastError();
+}
+
+// The listed row itself becomes rank 0 of its distance row, whatever ties with it: its own entry is set to -inf.  The selection
+// behind it then drops the row and nothing else - a bitwise duplicate at a lower index stays a neighbour.  One thread per row.
+__global__ void __launch_bounds__(256)
+k_self_first(float* __restrict__ dist, const int* __restrict__ rows, long total, int ld) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t < total) dist[(size_t)t * ld + rows[t]] = -INFINITY;
+}
+
+hipError_t launch_self_first(float* dist, const int* rows, int B, int N, int S, hipStream_t s) {
+  const long total = (long)B * S;
+  const int ld = ((N + 31) / 32) * 32;
+  hipLaunchKernelGGL(k_self_first, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dist, rows, total, ld);
+  return hipGetLastError();
+}
+
+// the in-LDS selection (any k <= N - 1) on given distance rows; N <= 38 400
+hipError_t launch_knn_lds(const float* dist_in, int* knn_idx, int B, int N, int S, int k, hipStream_t s) {
+  if (!dist_in || (size_t)N * 4 > 150 * 1024) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_knn_seeds), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_knn_seeds, dim3(S, B), dim3(256), (size_t)N * 4, s, nullptr, nullptr, dist_in, knn_idx, N, S, k, nullptr,
+                     ((N + 31) / 32) * 32);
   return hipGetLastError();
 }
 

@@ -430,6 +430,14 @@ int gmf_pick_seeds(gmf_handle* h, const float* src_keypts, const float* scores, 
 int gmf_knn_rows(gmf_handle* h, const float* feat_n, const int* rows, int B, int N, int S, int k, int* knn_out,
                  gmf_stream_t stream);
 
+/* gmf_knn_rows with the listed row itself as rank 0 WHATEVER ties with it: the k nearest OTHER rows under (distance, index), so a
+ * bitwise duplicate of the row at a lower index is a neighbour like any other (gmf_knn_rows drops it as rank 0 and returns the
+ * row itself instead).  knn(x, k, ignore_self=False) of models/common.py:70-71 = the row followed by the k - 1 rows this returns.
+ * Same distance rows as gmf_knn_rows, the row's own entry set to -inf before the selection; k > 63: the in-LDS selection on
+ * those rows (N <= 38400). */
+int gmf_knn_rows_self_first(gmf_handle* h, const float* feat_n, const int* rows, int B, int N, int S, int k, int* knn_out,
+                            gmf_stream_t stream);
+
 /* [ABI 5] The selection step alone: the k smallest entries behind rank 0 of every given DISTANCE row, under the order (distance,
  * index) - `topk(k + 1, largest=False)[1][..., 1:]` of models/common.py:71-74 for rows the caller has formed itself (gmf_amd.knn with
  * `normalized=False` or a feature width other than 128: distances xx_i - 2 x_i.x_j + xx_j from gmf_gemm_f32, common.py:64-69).
