@@ -2,6 +2,7 @@
 #pragma once
 #include "mfma_core.hpp"
 #include "launchers.hpp"
+#include "kv_share_layout.hpp"
 
 namespace gmf {
 
@@ -69,6 +70,13 @@ GMF_DEVINL void store_block_h2(float* __restrict__ tile_base, int blk, const flo
 // with ONE power-of-two scale s per (feature, 32-key tile): the tile's largest |v| of that feature lands in [128, 256).  The
 // E8M0 bytes of the two blocks go to `scale_word` (byte db: lanes 0..31 carry the low block's, lanes 32..63 the high block's -
 // where v_mfma_scale_f32_32x32x64_f8f6f4 reads them), one dword per lane and tile.  t: the lane's feature, 16 keys (V^T block).
+// HI: where the high fp16 plane goes.  kHiFrag: as above (fragment-major, the image of store_block_h2).  "kv_fold" on the fp8 path,
+// where keys = values = f and both high planes hold the same numbers: kHiShared (the K block) - the plane's ONE
+// image, laid out for the row reads of S and the transposed reads of O alike (kv_share_layout.hpp; the lane's 16 bytes of k-step
+// 2 db + half at off(key, 2 (2 db + half) + h)); kHiNone (the V^T block) - no high plane: the cross planes and the scale only, the
+// first 8 KiB of the tile's slot are left as they are.  The e4m3 planes and the scale bytes are the same in every form.
+enum { kHiFrag = 0, kHiShared = 1, kHiNone = 2 };
+template <int HI = kHiFrag>
 GMF_DEVINL void store_block_v8(float* __restrict__ tile_base, int db, const float (&t)[16], int lane, unsigned& scale_word) {
   f16x8* base = reinterpret_cast<f16x8*>(tile_base);
   float mx = 0.f;
@@ -100,7 +108,8 @@ GMF_DEVINL void store_block_v8(float* __restrict__ tile_base, int db, const floa
       if (j & 2) { v8[w] = cvt2_fp8_f32<true>(v8[w], x0, x1, s_hi); l8[w] = cvt2_fp8_f32<true>(l8[w], rl[0], rl[1], s_lo); }
       else { v8[w] = cvt2_fp8_f32<false>(0, x0, x1, s_hi); l8[w] = cvt2_fp8_f32<false>(0, rl[0], rl[1], s_lo); }
     }
-    base[(0 * 8 + 2 * db + half) * 64 + lane] = hi;
+    if (HI == kHiFrag) base[(0 * 8 + 2 * db + half) * 64 + lane] = hi;
+    else if (HI == kHiShared) base[kvshare::row_read_addr(lane, 2 * db + half) / 16] = hi;
   }
   reinterpret_cast<i32x4*>(tile_base)[(1 * 8 + 2 * db) * 64 + lane] = l8;
   reinterpret_cast<i32x4*>(tile_base)[(1 * 8 + 2 * db + 1) * 64 + lane] = v8;

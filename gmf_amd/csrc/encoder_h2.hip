@@ -805,7 +805,9 @@ GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const
         float t[16], td[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) t[r] = f[16 * mb + r];
-        if (v8) store_block_v8(k_out + toff, mb, t, lane, ksw);
+        // a pair on the fp8 path: fp16(f) ONCE, in the image both of the attention's products read (kv_share_layout.hpp) - the V side
+        // then stores its two cross planes only (24 stores of 16 bytes per tile, 32 for a pair the guard trips)
+        if (v8) store_block_v8<kHiShared>(k_out + toff, mb, t, lane, ksw);
         else store_block_h2(k_out + toff, mb, t, lane);
 #pragma unroll
         for (int r = 0; r < 16; ++r) mt[i * 32 + (frag_feature(r, h) ^ i)] = t[r];
@@ -813,10 +815,11 @@ GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const
 #pragma unroll
         for (int r = 0; r < 16; ++r) { const int kk = frag_feature(r, h); td[r] = mt[kk * 32 + (i ^ kk)]; }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (v8) store_block_v8(v_out + toff, mb, td, lane, vsw);
+        if (v8) store_block_v8<kHiNone>(v_out + toff, mb, td, lane, vsw);
         else store_block_h2(v_out + toff, mb, td, lane);
       }
-      // (32 stores so far: the counted waits of the stages that follow rely on them as a lower bound)
+      // (at least 24 image stores so far, on every wave - padding waves included - and on either path: the counted waits of the
+      // stages that follow rely on that number as a lower bound)
       if (v_scale) { sw_tile[0] = vsw; sw_tile[64] = ksw; }
       if (!QSKIP) {
 #pragma unroll
@@ -901,8 +904,9 @@ GMF_DEVINL void linear_h2_body(float* lds, const float* __restrict__ f_in, const
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
           // KVF without a Q' image: behind the pieces of these two stages lie those of the next two stages (8; 4 + 4 for the second, whose
-          // successor the first acquire issued) and the 32 image stores - they stay in flight across the stage barriers
-          const f16x8* lw = as_h2((KVF && QSKIP && PART == 0) ? ss.acquire_counted<40>() : ss.acquire());
+          // successor the first acquire issued) and the image stores, 24 of them on the fp8 path (32 for a tripped pair, which waits for
+          // 8 of its stores here) - they stay in flight across the stage barriers
+          const f16x8* lw = as_h2((KVF && QSKIP && PART == 0) ? ss.acquire_counted<32>() : ss.acquire());
           f32x16 acc = zero16();
           mma_wx_h2n<8, NP>(acc, lw, nx);
           float t[16];

@@ -716,6 +716,48 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
   const int lane = threadIdx.x & 63, h = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const unsigned lane_off16 = lane * 16;
+  // SHARE (the folded fp8 form): keys = values = f, so the high fp16 planes of the K and the V image hold the same numbers
+  // - the linear kernel writes ONE image of them (kv_share_layout.hpp, in the K tile's first 8 KiB) and the V tile carries its two cross
+  // planes only.  LDS: a ring of 4 high planes (slot t & 3: tile t is read transposed in phase 2 of tile t, tile t + 1 by rows in phase 1
+  // of tile t, tile t + 2 is landing) | the K cross planes [2][8 KiB] | the V cross planes [2][8 KiB] - the same 64 KiB; per key tile and
+  // workgroup 24 instead of 32 KiB come in, with 6 instead of 8 LDS-DMA instructions per wave.
+  constexpr bool SHARE = PVF8 && FOLD;
+  constexpr int kPlaneFloats = kStageFloats / 2;       // 8 KiB
+  float* const ldsH = lds;
+  float* const ldsKx = lds + 2 * kStageFloats;
+  float* const ldsVx = lds + 3 * kStageFloats;
+  const unsigned lds_h0 = (unsigned)(uintptr_t)(void __attribute__((address_space(3)))*)(lds);
+  // the two address registers of each kind of read; everything else is an immediate (kv_share_layout.hpp)
+  const unsigned row_b0 = lds_h0 + kvshare::row_read_addr(lane, 0), row_b1 = lds_h0 + kvshare::row_read_addr(lane, 1);
+  const unsigned tr_b0 = lds_h0 + kvshare::tr_read_addr(lane, 0, h), tr_b1 = lds_h0 + kvshare::tr_read_addr(lane, 0, 2 + h);
+  // SHARE: the two address registers of tile t's plane for one kind of read.  Opaque to the compiler: left to itself it keeps the
+  // slot's offset in a scalar register and spends a vector add on EVERY read instead of two per phase
+  struct PlaneAddr { unsigned a, b; };
+  auto plane_addr = [&](const int t, const unsigned b0, const unsigned b1) -> PlaneAddr {
+    PlaneAddr pa{b0 + (t & 3) * kvshare::kPlaneBytes, b1 + (t & 3) * kvshare::kPlaneBytes};
+    if (SHARE) asm("" : "+v"(pa.a), "+v"(pa.b));
+    return pa;
+  };
+  auto k_addr = [&](const int t) { return plane_addr(t, row_b0, row_b1); };
+  auto v_addr = [&](const int t) { return plane_addr(t, tr_b0, tr_b1); };
+  // this lane's A operand of S: the high plane of key tile t (SHARE: at `ka` = k_addr(t)), k-step s
+  auto k_rows = [&](const int t, const PlaneAddr& ka, const int s) -> f16x8 {
+    if (SHARE) return lds_read_f16x8(((s & 1) ? ka.b : ka.a) + 512 * (s >> 1));
+    return (reinterpret_cast<const f16x8*>(ldsK + (t & 1) * kStageFloats) + lane)[(0 * 8 + s) * 64];
+  };
+  // this lane's A operand of O^T: the high plane of value tile t (SHARE: at `va` = v_addr(t), two transposed reads of four keys each),
+  // feature block db, k-step s2
+  auto v_cols = [&](const int t, const PlaneAddr& va, const int db, const int s2) -> f16x8 {
+    if (SHARE) return lds_read_tr16x8(va.a + 512 * db + 4096 * s2, va.b + 512 * db + 4096 * s2);
+    return (reinterpret_cast<const f16x8*>(ldsV + (t & 1) * kStageFloats) + lane)[(0 * 8 + 2 * db + s2) * 64];
+  };
+  // the e4m3 cross planes of K / V tile t (+ lane): 16-byte units (2 b) * 64 and (2 b + 1) * 64 of block b
+  auto k_cross = [&](const int t) -> const i32x4* {
+    return reinterpret_cast<const i32x4*>(SHARE ? ldsKx + (t & 1) * kPlaneFloats : ldsK + (t & 1) * kStageFloats + kPlaneFloats) + lane;
+  };
+  auto v_cross = [&](const int t) -> const i32x4* {
+    return reinterpret_cast<const i32x4*>(SHARE ? ldsVx + (t & 1) * kPlaneFloats : ldsV + (t & 1) * kStageFloats + kPlaneFloats) + lane;
+  };
   const AttnItem it = attn_item(bid, n_items, n_full, ksplits);
   if (!it.valid) return;                       // grid padding of the split tail (uniform per workgroup)
   const bool split = it.split;
@@ -897,8 +939,20 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
 #pragma unroll
     for (int q = 0; q < kPiecesPerWave; ++q) dma_piece_1k_s(g + (wave + WAVES * q) * 256, l + (wave + WAVES * q) * 256, lane_off16);
   };
-  auto issueK = [&](int t) { issue16k(gk + (size_t)t * kStageFloats, ldsK + (t & 1) * kStageFloats); };
-  auto issueV = [&](int t) { issue16k(gv + (size_t)t * kStageFloats, ldsV + (t & 1) * kStageFloats); };
+  auto issue8k = [&](const float* g, float* l) {       // this wave's 2 of the 8 KiB-pieces of one plane pair
+#pragma unroll
+    for (int q = 0; q < 2; ++q) dma_piece_1k_s(g + (wave + WAVES * q) * 256, l + (wave + WAVES * q) * 256, lane_off16);
+  };
+  auto issueK = [&](int t) {
+    if (SHARE) {                                       // the high plane into its ring, the cross planes into theirs
+      issue8k(gk + (size_t)t * kStageFloats, ldsH + (t & 3) * kPlaneFloats);
+      issue8k(gk + (size_t)t * kStageFloats + kPlaneFloats, ldsKx + (t & 1) * kPlaneFloats);
+    } else issue16k(gk + (size_t)t * kStageFloats, ldsK + (t & 1) * kStageFloats);
+  };
+  auto issueV = [&](int t) {
+    if (SHARE) issue8k(gv + (size_t)t * kStageFloats + kPlaneFloats, ldsVx + (t & 1) * kPlaneFloats);     // (the V tile's first 8 KiB: not written)
+    else issue16k(gv + (size_t)t * kStageFloats, ldsV + (t & 1) * kStageFloats);
+  };
 
   f32x16 oacc[4];
 #pragma unroll
@@ -913,9 +967,8 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
   __syncthreads();
   f32x16 s_a = s_start(), s_b;
   // S of one key tile in the fp8 form: 8 f16 MFMAs on the high planes + 4 scaled fp8 MFMAs on the cross planes
-  auto s_cross8 = [&](f32x16 acc, const f16x8* lkt, const int cb, const unsigned kscale) -> f32x16 {
-    const i32x4* l8 = reinterpret_cast<const i32x4*>(lkt);
-    const i32x4 a_lo = l8[(1 * 8 + 2 * cb) * 64], a_hi = l8[(1 * 8 + 2 * cb + 1) * 64];
+  auto s_cross8 = [&](f32x16 acc, const i32x4* l8, const int cb, const unsigned kscale) -> f32x16 {
+    const i32x4 a_lo = l8[(2 * cb) * 64], a_hi = l8[(2 * cb + 1) * 64];
     const i32x8 ka = {a_lo[0], a_lo[1], a_lo[2], a_lo[3], a_hi[0], a_hi[1], a_hi[2], a_hi[3]};
     return mfma_f8s2(ka, qb[cb], acc, cb, (int)kscale, (int)qsw);
   };
@@ -923,10 +976,11 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
     const f16x8* lk = reinterpret_cast<const f16x8*>(ldsK + (t_begin & 1) * kStageFloats) + lane;
     if (PVF8) {
       const unsigned ks0 = vsrow[(size_t)t_begin * 128 + 64];
+      const PlaneAddr ka = k_addr(t_begin);
 #pragma unroll
-      for (int s = 0; s < 8; ++s) s_a = mfma_h16(lk[(0 * 8 + s) * 64], qh[s], s_a);
+      for (int s = 0; s < 8; ++s) s_a = mfma_h16(k_rows(t_begin, ka, s), qh[s], s_a);
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb) s_a = s_cross8(s_a, lk, cb, ks0);
+      for (int cb = 0; cb < 4; ++cb) s_a = s_cross8(s_a, k_cross(t_begin), cb, ks0);
     } else {
 #pragma unroll
       for (int s = 0; s < 8; ++s) mma_n(s_a, lk[(0 * 8 + s) * 64], lk[(1 * 8 + s) * 64], qh[s], ql[s]);
@@ -962,12 +1016,21 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
     }
   };
   // the same refills as ONE statement per tile and wave (dma_4k_s: the wave's four consecutive KiB under one M0 / address setup)
+  // SHARE: of K tile t + 2, waves 0 and 1 fetch the high plane into slot (t + 2) & 3 of its ring (it held tile t - 2, last read in
+  // phase 2 of tile t - 2), waves 2 and 3 the cross planes into the slot K_t's left (read in phase 1 of tile t - 1); of V tile t + 1
+  // there are only the cross planes, 2 KiB per wave, into the slot of tile t - 1
   auto issue_k4 = [&](const int t) {
-    if (t + 2 < t_end && (NPROD == 3 || wave < 2))
+    if (SHARE) {
+      if (t + 2 < t_end)
+        dma_4k_s(gk + (size_t)(t + 2) * kStageFloats + wave * 1024,
+                 wave < 2 ? ldsH + ((t + 2) & 3) * kPlaneFloats + wave * 1024 : ldsKx + (t & 1) * kPlaneFloats + (wave - 2) * 1024, lane_off16);
+    } else if (t + 2 < t_end && (NPROD == 3 || wave < 2))
       dma_4k_s(gk + (size_t)(t + 2) * kStageFloats + wave * 1024, ldsK + (t & 1) * kStageFloats + wave * 1024, lane_off16);
   };
   auto issue_v4 = [&](const int t) {
-    if (NPROD == 3 || wave < 2)
+    if (SHARE)
+      dma_2k_s(gv + (size_t)(t + 1) * kStageFloats + kPlaneFloats + wave * 512, ldsVx + ((t + 1) & 1) * kPlaneFloats + wave * 512, lane_off16);
+    else if (NPROD == 3 || wave < 2)
       dma_4k_s(gv + (size_t)(t + 1) * kStageFloats + wave * 1024, ldsV + ((t + 1) & 1) * kStageFloats + wave * 1024, lane_off16);
   };
   auto rescale = [&](const bool moved, const float alpha) {
@@ -1070,30 +1133,30 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
     __syncthreads();
     vsw = vsw_next;
     ksw = ksw_next;
-    const f16x8* lv = reinterpret_cast<const f16x8*>(ldsV + (t & 1) * kStageFloats) + lane;
-    const f16x8* lk = reinterpret_cast<const f16x8*>(ldsK + ((t + 1) & 1) * kStageFloats) + lane;
     f16x8 ph0, pl0, ph1, pl1;
     i32x8 pb;
     f16x8 vr[3];
-    auto hslot = [](int u) { return (0 * 8 + 2 * (u & 3) + (u >> 2)) * 64; };
+    PlaneAddr va{0u, 0u};
+    auto v_hi = [&](const int u) { return v_cols(t, va, u & 3, u >> 2); };      // the operand of phase-2 unit u: feature block u & 3, k-step u >> 2
     s_next = s_start();
     {
       // [r5] 12 matrix instructions in the phase's 24 units: K_hi Q'_hi of k-step s at unit 3 s + 2, the scaled fp8 MFMA of channel block
       // cb (k-steps 2 cb, 2 cb + 1) at unit 6 cb + 3; its two 16-byte K fragments are requested one k-step earlier (unit 6 cb)
-      const i32x4* lk8 = reinterpret_cast<const i32x4*>(lk);
-      f16x8 kh = lk[0];
+      const i32x4* lk8 = k_cross(t + 1);
+      const PlaneAddr ka = k_addr(t + 1);
+      f16x8 kh = k_rows(t + 1, ka, 0);
       f16x8 kh_n = kh;
-      i32x4 k8a = lk8[(1 * 8) * 64], k8b = lk8[(1 * 8 + 1) * 64];
+      i32x4 k8a = lk8[0], k8b = lk8[64];
 #pragma unroll
       for (int u = 0; u < 24; ++u) {
         const int s = u / 3, pr = u % 3;
-        if (pr == 0 && s < 7) kh_n = lk[(0 * 8 + s + 1) * 64];
+        if (pr == 0 && s < 7) kh_n = k_rows(t + 1, ka, s + 1);
         if (pr == 2) s_next = mfma_h16(kh, qh[s], s_next);
         if (pr == 0 && (s & 1)) {
           const int cb = s >> 1;
           const i32x8 ka = {k8a[0], k8a[1], k8a[2], k8a[3], k8b[0], k8b[1], k8b[2], k8b[3]};
           s_next = mfma_f8s2(ka, qb[cb], s_next, cb, (int)ksw, (int)qsw);
-          if (cb < 3) { k8a = lk8[(1 * 8 + 2 * cb + 2) * 64]; k8b = lk8[(1 * 8 + 2 * cb + 3) * 64]; }
+          if (cb < 3) { k8a = lk8[(2 * cb + 2) * 64]; k8b = lk8[(2 * cb + 3) * 64]; }
         }
         if (pr == 2) kh = kh_n;
         if (u < 4) {
@@ -1136,27 +1199,28 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
         // pass of 12 launches, (12, 20) 11.67-11.69, (8, 16) 12.05, (0, 8) 12.54, V in phase 2 11.74-11.90 (profiles/r05_attention_notes.txt)
         if (u == 16) issue_k4(t);
         if (u == 23) issue_v4(t);
-        if (u >= 21) vr[u - 21] = lv[hslot(u - 21)];
+        if (u == 21) va = v_addr(t);
+        if (u >= 21) vr[u - 21] = v_hi(u - 21);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
     {
-      const i32x4* lv8 = reinterpret_cast<const i32x4*>(lv);
+      const i32x4* lv8 = v_cross(t);
       i32x4 fa[2][2];
 #pragma unroll
       for (int u = 0; u < 12; ++u) {
         if (u < 8) {
           const int s2 = u >> 2, db = u & 3;
           oacc[db] = mfma_h16(vr[u % 3], s2 ? ph1 : ph0, oacc[db]);
-          if (u + 3 < 8) vr[u % 3] = lv[hslot(u + 3)];
-          if (u == 4 || u == 6) { const int fd = (u - 4) >> 1; fa[fd][0] = lv8[(1 * 8 + 2 * fd) * 64]; fa[fd][1] = lv8[(1 * 8 + 2 * fd + 1) * 64]; }
+          if (u + 3 < 8) vr[u % 3] = v_hi(u + 3);
+          if (u == 4 || u == 6) { const int fd = (u - 4) >> 1; fa[fd][0] = lv8[(2 * fd) * 64]; fa[fd][1] = lv8[(2 * fd + 1) * 64]; }
           planes_f8(u < 4 ? ph0 : ph1, u < 4 ? pl0 : pl1, 2 * (u & 3), u, pb, ls, ls_l);
         } else {
           const int db = u - 8;
           const i32x4 a_lo = fa[db & 1][0], a_hi = fa[db & 1][1];
           const i32x8 va = {a_lo[0], a_lo[1], a_lo[2], a_lo[3], a_hi[0], a_hi[1], a_hi[2], a_hi[3]};
           oacc[db] = mfma_f8s(va, pb, oacc[db], db, (int)vsw, psc);
-          if (db < 2) { fa[db & 1][0] = lv8[(1 * 8 + 2 * db + 4) * 64]; fa[db & 1][1] = lv8[(1 * 8 + 2 * db + 5) * 64]; }
+          if (db < 2) { fa[db & 1][0] = lv8[(2 * db + 4) * 64]; fa[db & 1][1] = lv8[(2 * db + 5) * 64]; }
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1190,6 +1254,7 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
     if (PVF8) {
       i32x8 pb;
       float ls_l = 0.f;
+      const PlaneAddr va = v_addr(t);
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         f16x8 ph, pl;
@@ -1197,13 +1262,13 @@ GMF_DEVINL void scattn_h2p_body(float* lds, const int bid, const float* __restri
 #pragma unroll
         for (int j = 0; j < 8; j += 2) planes_f8(ph, pl, j, 4 * s2 + (j >> 1), pb, ls, ls_l);
 #pragma unroll
-        for (int db = 0; db < 4; ++db) oacc[db] = mfma_h16(lv[(0 * 8 + 2 * db + s2) * 64], ph, oacc[db]);
+        for (int db = 0; db < 4; ++db) oacc[db] = mfma_h16(v_cols(t, va, db, s2), ph, oacc[db]);
       }
       ls += ls_l;
-      const i32x4* lv8 = reinterpret_cast<const i32x4*>(lv);
+      const i32x4* lv8 = v_cross(t);
 #pragma unroll
       for (int db = 0; db < 4; ++db) {
-        const i32x4 a_lo = lv8[(1 * 8 + 2 * db) * 64], a_hi = lv8[(1 * 8 + 2 * db + 1) * 64];
+        const i32x4 a_lo = lv8[(2 * db) * 64], a_hi = lv8[(2 * db + 1) * 64];
         const i32x8 va = {a_lo[0], a_lo[1], a_lo[2], a_lo[3], a_hi[0], a_hi[1], a_hi[2], a_hi[3]};
         oacc[db] = mfma_f8s(va, pb, oacc[db], db, (int)vsw, psc);
       }

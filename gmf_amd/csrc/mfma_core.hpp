@@ -348,6 +348,31 @@ GMF_DEVINL void dma_4k_s(const float* __restrict__ gsrc_uniform, float* lds_dst_
                : "=&s"(keep) : "v"(lane_off16), "s"(gsrc_uniform), "s"(lds_dst) : "memory");
 }
 
+// TWO consecutive KiB in the same form (a wave's quarter of an 8 KiB plane pair)
+GMF_DEVINL void dma_2k_s(const float* __restrict__ gsrc_uniform, float* lds_dst_base, unsigned lane_off16) {
+  unsigned keep;
+  const unsigned lds_dst = (unsigned)(uintptr_t)(void __attribute__((address_space(3)))*)(lds_dst_base);
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+               "global_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(lane_off16), "s"(gsrc_uniform), "s"(lds_dst) : "memory");
+}
+
+// One operand half of a transposed LDS read (ds_read_b64_tr_b16, gfx950): per 16-lane group a block of 4 rows x 16 columns of 16-bit
+// values, lane i receives column i.  `addr`: the byte address in the LDS this lane SUPPLIES (kv_share_layout.hpp, tr_read_addr).
+// The gather crosses lanes: EXEC must be all ones, i.e. every branch around a call is wave-uniform.
+typedef __fp16 h16x4_tr __attribute__((__vector_size__(8)));
+GMF_DEVINL f16x8 lds_read_tr16x8(unsigned addr_a, unsigned addr_b) {
+  typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
+  const f16x4v a = __builtin_bit_cast(f16x4v, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+      (h16x4_tr __attribute__((address_space(3)))*)(uintptr_t)addr_a));
+  const f16x4v b = __builtin_bit_cast(f16x4v, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+      (h16x4_tr __attribute__((address_space(3)))*)(uintptr_t)addr_b));
+  return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+GMF_DEVINL f16x8 lds_read_f16x8(unsigned addr) {
+  return *(const f16x8 __attribute__((address_space(3)))*)(uintptr_t)addr;
+}
+
 // Copy a per-feature vector block of n_floats (a multiple of 4) to the LDS, 1 KiB pieces round-robin over the waves; the last
 // piece is cut by the execution mask (nothing is read behind the block).
 GMF_DEVINL void dma_vec(const float* __restrict__ gsrc, float* lds_dst, int n_floats, int wave, int n_waves, int lane) {

@@ -131,8 +131,10 @@ int gmf_set_sigma_device(gmf_handle* h, const float* sigma_dev);
  *   "pv_fp8"            : parity arithmetic of the default path (scattn_variant 18, fused_linear 1): the two CROSS products of the
  *                         attention's O += P V (P_hi V_lo + P_lo V_hi) on the block-scaled fp8 matrix pipe - one
  *                         v_mfma_scale_f32_32x32x64_f8f6f4 per feature block and key tile, e4m3 operands, one scale per (feature,
- *                         tile), the softmax row sum taken over exactly the probabilities the pipe multiplies; P_hi V_hi and all of
- *                         Q'K^T keep the three-product split-fp16 form.  1 (default) = GUARDED [ABI 5]: per pair and layer, on the
+ *                         tile), the softmax row sum taken over exactly the probabilities the pipe multiplies - and likewise the two
+ *                         cross products of S = K Q'^T (one scale per (key, 32 channels) and per (query, 32 channels)); only
+ *                         P_hi V_hi and K_hi Q'_hi stay on the f16 pipe.  With "kv_fold" the two high planes are the same numbers
+ *                         and are stored once.  1 (default) = GUARDED [ABI 5]: per pair and layer, on the
  *                         device, from the largest row norm of the layer's input features against gmf_encoder_weights::pv_guard
  *                         (a bound on the attention scores the layer can form): layers whose softmax can collapse onto single keys
  *                         - where the e4m3 rounding of one key's V reaches the output whole - take the three-product form, every

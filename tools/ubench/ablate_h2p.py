@@ -114,8 +114,8 @@ PATCHES = {
                 '    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");\n    __syncthreads();\n    vsw = vsw_next;\n')],
     "r5_vm4_mid": [(EK, '    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");\n    __syncthreads();\n    vsw = vsw_next;\n',
                     '    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");\n    __syncthreads();\n    vsw = vsw_next;\n'),
-                   (EK, "        if (u >= 21) vr[u - 21] = lv[hslot(u - 21)];\n        __builtin_amdgcn_sched_barrier(0);\n",
-                    '        if (u == 21) { asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); __syncthreads(); }\n        if (u >= 21) vr[u - 21] = lv[hslot(u - 21)];\n        __builtin_amdgcn_sched_barrier(0);\n')],
+                   (EK, "        if (u >= 21) vr[u - 21] = v_hi(u - 21);\n        __builtin_amdgcn_sched_barrier(0);\n",
+                    '        if (u == 21) { asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); __syncthreads(); }\n        if (u >= 21) vr[u - 21] = v_hi(u - 21);\n        __builtin_amdgcn_sched_barrier(0);\n')],
     # the compat cache written with non-temporal stores (3.2 GB per forward at 32 x 5000, re-read by 12 streaming launches)
     "r5_c_nt_store": [("enc_common.hpp", "      for (int q = 0; q < 4; ++q) ct[q * 64] = make_float4(c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]);",
                        "      for (int q = 0; q < 4; ++q) { const f32x4 w = {c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]}; __builtin_nontemporal_store(w, reinterpret_cast<f32x4*>(ct + q * 64)); }")],
@@ -123,6 +123,14 @@ PATCHES = {
     "r5_dma_14_22": [(EK, "        if (u == 16) issue_k4(t);\n        if (u == 23) issue_v4(t);\n", "        if (u == 14) issue_k4(t);\n        if (u == 22) issue_v4(t);\n")],
     "r5_dma_12_p2": [(EK, "        if (u == 16) issue_k4(t);\n        if (u == 23) issue_v4(t);\n", "        if (u == 12) issue_k4(t);\n"), (EK, "          planes_f8(u < 4 ? ph0 : ph1, u < 4 ? pl0 : pl1, 2 * (u & 3), u, pb, ls, ls_l);\n", "          planes_f8(u < 4 ? ph0 : ph1, u < 4 ? pl0 : pl1, 2 * (u & 3), u, pb, ls, ls_l);\n" "          if (u == 2) issue_v4(t);\n")],
     "r5_dma_20_p2": [(EK, "        if (u == 16) issue_k4(t);\n        if (u == 23) issue_v4(t);\n", "        if (u == 20) issue_k4(t);\n"), (EK, "          planes_f8(u < 4 ? ph0 : ph1, u < 4 ? pl0 : pl1, 2 * (u & 3), u, pb, ls, ls_l);\n", "          planes_f8(u < 4 ? ph0 : ph1, u < 4 ? pl0 : pl1, 2 * (u & 3), u, pb, ls, ls_l);\n" "          if (u == 4) issue_v4(t);\n")],
+    # The shared high plane of the folded fp8 body, timing only: every operand of O^T += V^T P^T comes from ONE row read of
+    # the plane instead of two transposed reads (wrong values of V) - what the 16 ds_read_b64_tr_b16 per tile cost against the 8
+    # ds_read_b128 of the fragment-major V image.  (The other side of the price - the parent's kernels with the V high plane neither
+    # stored nor fetched - is a patch of the parent's source, not of this one: profiles/kv_share_ab_rounds.txt has its rounds.)
+    "kvs_rows_for_tr": [
+        (EK, "    if (SHARE) return lds_read_tr16x8(va.a + 512 * db + 4096 * s2, va.b + 512 * db + 4096 * s2);",
+             "    if (SHARE) return lds_read_f16x8((va.a & ~15u) + 512 * db + 4096 * s2);"),
+    ],
     "p8_no_consist": [     # timing only: the row sum without the decoded low plane (what the consistent sum costs: nothing measurable)
         (EK, "      ls_l = __builtin_amdgcn_fdot2(dec2_fp8_f16<true>(pb[4 + w], 0x1p-10f), ones, ls_l, false);", ""),
         (EK, "      ls_l = __builtin_amdgcn_fdot2(dec2_fp8_f16<false>(pb[4 + w], 0x1p-10f), ones, ls_l, false);", ""),
@@ -221,9 +229,11 @@ def build(only=None):
     for name, patches in PATCHES.items():
         if only and name not in only:
             continue
-        work = os.path.join(OUT, "src_" + name)
-        shutil.rmtree(work, ignore_errors=True)
+        top = os.path.join(OUT, "src_" + name)
+        work = os.path.join(top, "gmf_amd", "csrc")          # (the sources include ../../include/gmf_hip.h)
+        shutil.rmtree(top, ignore_errors=True)
         os.makedirs(work)
+        shutil.copytree(os.path.join(ROOT, "include"), os.path.join(top, "include"))
         for f in os.listdir(CSRC):
             if f.endswith((".hpp", ".hip")):
                 shutil.copy(os.path.join(CSRC, f), work)
@@ -244,7 +254,7 @@ def build(only=None):
         rest = [os.path.join(CSRC, o) for o in os.listdir(CSRC) if o.endswith(".o") and o[:-2] not in rebuild]
         lib = os.path.join(OUT, f"libgmf_hip_{name}.so")
         subprocess.check_call(["/opt/rocm/bin/hipcc", "-shared", "-fPIC", "--offload-arch=gfx950"] + objs + rest + ["-o", lib])
-        shutil.rmtree(work)
+        shutil.rmtree(top)
         print("built", lib, flush=True)
 
 

@@ -39,8 +39,8 @@ def build():
         "  auto tile_step_f8 = [&](const int t, const f32x16& s_cur, f32x16& s_next) {\n    TL(t, 0);\n    float x[16];\n")
     rep('    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");\n    __syncthreads();\n    vsw = vsw_next;\n',
         '    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");\n    TL(t, 9);\n    __syncthreads();\n    TL(t, 1);\n    vsw = vsw_next;\n')
-    rep("        if (u >= 21) vr[u - 21] = lv[hslot(u - 21)];\n        __builtin_amdgcn_sched_barrier(0);\n      }\n    }\n",
-        "        if (u >= 21) vr[u - 21] = lv[hslot(u - 21)];\n        __builtin_amdgcn_sched_barrier(0);\n"
+    rep("        if (u >= 21) vr[u - 21] = v_hi(u - 21);\n        __builtin_amdgcn_sched_barrier(0);\n      }\n    }\n",
+        "        if (u >= 21) vr[u - 21] = v_hi(u - 21);\n        __builtin_amdgcn_sched_barrier(0);\n"
         "        if (u == 3) TL(t, 2); if (u == 7) TL(t, 3); if (u == 11) TL(t, 4); if (u == 19) TL(t, 5);\n      }\n    }\n    TL(t, 6);\n")
     rep("          planes_f8(u < 4 ? ph0 : ph1, u < 4 ? pl0 : pl1, 2 * (u & 3), u, pb, ls, ls_l);\n        } else {",
         "          planes_f8(u < 4 ? ph0 : ph1, u < 4 ? pl0 : pl1, 2 * (u & 3), u, pb, ls, ls_l);\n          if (u == 7) TL(t, 7);\n        } else {")
