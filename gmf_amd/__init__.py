@@ -22,8 +22,8 @@ from .clique import max_clique_batched, PMC, compatibility_graph   # noqa: F401
 from .features import (radius_knn_batched, estimate_normals_batched, compute_fpfh_batched,  # noqa: F401
                        voxel_down_sample_batched, voxel_select_batched, voxel_down_sample, voxel_select, estimate_normals,
                        compute_fpfh_feature, fpfh_descriptors)
-from .sparse import (SparsePlan, sparse_conv, sparse_conv_narrow, sparse_head_l2, ResUNetBN2C, ResUNetBN2CX,  # noqa: F401
-                     inlier_coordinates)
+from .sparse import (SparsePlan, sparse_conv, sparse_conv_narrow, sparse_conv_narrow_wgrad, sparse_head_l2, ResUNetBN2C,  # noqa: F401
+                     ResUNetBN2CX, inlier_coordinates)
 from . import fcgf, dgr                          # noqa: F401  (gmf_amd.fcgf.ResUNetBN2C: FCGF; gmf_amd.ResUNetBN2C: the inlier net)
 from .dgr import matching_indices_batched, find_correct_correspondence, generate_inlier_input   # noqa: F401
 from .multiway import (information_matrix_batched, global_optimization, local_refinement_batched, loop_closure_mask,  # noqa: F401
@@ -39,7 +39,8 @@ __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointD
            "icp_point_to_point_batched", "RegistrationResult", "registration_ransac_based_on_correspondence", "registration_icp",
            "icp_refine", "radius_knn_batched", "estimate_normals_batched", "compute_fpfh_batched", "voxel_down_sample_batched",
            "voxel_select_batched", "voxel_down_sample", "voxel_select", "estimate_normals", "compute_fpfh_feature",
-           "fpfh_descriptors", "SparsePlan", "sparse_conv", "sparse_conv_narrow", "sparse_head_l2", "ResUNetBN2C", "ResUNetBN2CX",
+           "fpfh_descriptors", "SparsePlan", "sparse_conv", "sparse_conv_narrow", "sparse_conv_narrow_wgrad", "sparse_head_l2",
+           "ResUNetBN2C", "ResUNetBN2CX",
            "inlier_coordinates", "fcgf", "dgr", "find_knn_gpu_batch", "find_knn_batch", "find_pairs", "matching_indices_batched",
            "find_correct_correspondence", "generate_inlier_input", "ransac_feature_matching_batched",
            "registration_ransac_based_on_feature_matching", "spectral_matching_batched", "SM", "max_clique_batched", "PMC",

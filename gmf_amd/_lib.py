@@ -250,6 +250,13 @@ SIGNATURES = {
                                         _vp]),
     "gmf_batchnorm_masked_forward": (C.c_int, [_vp] * 6 + [_ll, C.c_int, C.c_float, C.c_float, C.c_int] + [_vp] * 6),
     "gmf_batchnorm_masked_backward": (C.c_int, [_vp] * 8 + [_ll, C.c_int] + [_vp] * 5),
+    "gmf_sparse_conv_narrow_wgrad": (C.c_int, [_vp] * 5 + [C.c_int, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "gmf_rownorm_eps": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _ll, C.c_int, _vp]),
+    "gmf_hardest_contrastive_forward": (C.c_int, [_vp, _vp, _ll, _vp, _ll, C.c_int, _vp, _ll, _vp, _vp, _ll, _vp, _ll, _vp, _ll,
+                                                  C.c_float, C.c_float] + [_vp] * 9),
+    "gmf_hardest_contrastive_backward": (C.c_int, [_vp, _vp, _ll, _vp, _ll, C.c_int, _vp, _ll, _vp, _ll] + [_vp] * 8 + [C.c_float] +
+                                         [_vp] * 7),
+    "gmf_rows_sum_by_dest": (C.c_int, [_vp, _vp, _ll, _vp, _vp, _ll, C.c_int, _vp, _vp]),
 }
 
 _lib = None
@@ -283,6 +290,7 @@ GMF_STATUS_PV_GUARDED = 2      # informational: the "pv_fp8" guard sent a (pair,
 GMF_STATUS_SPARSE_DUPLICATE = 4   # gmf_sparse_build_plan met a duplicate (batch, coordinates) input row
 GMF_STATUS_BATCHNORM_ROWS = 8     # gmf_batchnorm_masked_forward met a level with fewer than 2 valid rows
 GMF_STATUS_POSEGRAPH_PIVOT = 16   # gmf_posegraph_optimize met a pivot of H + lambda I that was not finite or not positive
+GMF_STATUS_LOSS_INDEX = 32        # gmf_hardest_contrastive_forward met a row index outside its tensor
 
 
 class Handle:
@@ -363,6 +371,11 @@ class Handle:
                 f"gmf_amd: {where}: a pose-graph optimisation of an earlier call on this device met a pivot of H + lambda I that "
                 "was not finite or not positive (stop code 6 in its stats): an information matrix is not positive semi-definite, "
                 "or a pose or measurement is not finite.  That graph's poses are those of its last accepted step.")
+        if f & GMF_STATUS_LOSS_INDEX:
+            self.status(clear=True)
+            raise RuntimeError(
+                f"gmf_amd: {where}: a hardest-contrastive loss of an earlier call on this device met a row index outside its "
+                "tensor (positive_pairs, pos_sel, sel0 or sel1).  That loss is not valid.")
 
     def __del__(self):
         try:

@@ -276,6 +276,85 @@ int gmf_sparse_conv_wgrad(gmf_handle* h, const int* row_ptr, const int* pairs, c
   return GMF_OK;
 }
 
+int gmf_sparse_conv_narrow_wgrad(gmf_handle* h, const int* row_ptr, const int* pairs, const int* by_off, const int* off_start, int K,
+                                 const int* n_out, const float* x, int cin, const float* dy, int cout, float* dW,
+                                 gmf_stream_t stream) {
+  GMF_REQUIRE(h && row_ptr && pairs && by_off && off_start && n_out && x && dy && dW, GMF_ERR_BAD_ARG,
+              "sparse_conv_narrow_wgrad: null pointer (the identity map has no narrow form)");
+  GMF_REQUIRE(K >= 1 && K <= gmf::kSparseMaxK, GMF_ERR_UNSUPPORTED_SHAPE, "sparse_conv_narrow_wgrad: K must be in 1..1024");
+  GMF_REQUIRE(cin >= 1 && cin <= gmf::kWgradNarrowMaxCin && cout >= 1 && cout <= gmf::kWgradNarrowMaxCout, GMF_ERR_UNSUPPORTED_SHAPE,
+              "sparse_conv_narrow_wgrad: Cin must be in 1..8 and Cout in 1..64");
+  SetDevice sd(h, stream);
+  const int nslots = gmf::sparse_wgrad_narrow_slots(K);
+  gmf::SparseWgradArgs a{row_ptr, reinterpret_cast<const int2*>(pairs), by_off, off_start, K, n_out, x, cin, nullptr, 0, dy, cout,
+                         nslots, nullptr, nullptr, dW};
+  if (int rc = arena_carve(h, {arena_buf(a.chunk_info, (size_t)K + 2), arena_buf(a.partial, (size_t)nslots * cin * cout)})) return rc;
+  GMF_HIP(gmf::launch_sparse_wgrad_narrow(a, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_rownorm_eps(gmf_handle* h, int backward, const float* x, const float* dy, float* nrm, float* out, long long rows, int C,
+                    gmf_stream_t stream) {
+  GMF_REQUIRE(h && x && nrm && out && (!backward || dy), GMF_ERR_BAD_ARG, "rownorm_eps: null pointer");
+  GMF_REQUIRE(rows > 0 && rows < (1LL << 31) && C > 0 && C <= 4096, GMF_ERR_UNSUPPORTED_SHAPE,
+              "rownorm_eps: rows must be in 1 .. 2^31 - 1 and C in 1..4096");
+  SetDevice sd(h, stream);
+  GMF_HIP(gmf::launch_rownorm_eps(backward != 0, x, dy, nrm, out, rows, C, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_hardest_contrastive_forward(gmf_handle* h, const float* F0, long long N0, const float* F1, long long N1, int C,
+                                    const long long* pairs, long long K, const long long* keys, const long long* pos_sel, long long P,
+                                    const long long* sel0, long long H0, const long long* sel1, long long H1, float pos_thresh,
+                                    float neg_thresh, long long* h01, long long* h10, unsigned char* keep0, unsigned char* keep1,
+                                    float* D01, float* D10, float* terms, float* out, gmf_stream_t stream) {
+  GMF_REQUIRE(h && F0 && F1 && pairs && keys && sel0 && sel1 && h01 && h10 && keep0 && keep1 && D01 && D10 && terms && out,
+              GMF_ERR_BAD_ARG, "hardest_contrastive_forward: null pointer");
+  GMF_REQUIRE(C >= 1 && C <= 64, GMF_ERR_UNSUPPORTED_SHAPE, "hardest_contrastive_forward: C must be in 1..64");
+  GMF_REQUIRE(N0 >= 1 && N1 >= 1 && N0 < (1LL << 31) && N1 < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "hardest_contrastive_forward: N0 and N1 must be in 1 .. 2^31 - 1");
+  GMF_REQUIRE(K >= 1 && P >= 1 && P < (1LL << 24) && (pos_sel || P == K), GMF_ERR_UNSUPPORTED_SHAPE,
+              "hardest_contrastive_forward: K >= 1 and P in 1 .. 2^24 - 1 (P = K without pos_sel)");
+  GMF_REQUIRE(H0 >= 1 && H1 >= 1 && H0 < (1LL << 31) && H1 < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "hardest_contrastive_forward: sel0 and sel1 must hold 1 .. 2^31 - 1 rows");
+  SetDevice sd(h, stream);
+  gmf::HclArgs a{F0, F1, (int)N0, (int)N1, C, pairs, K, keys, pos_sel, (int)P, sel0, (int)H0, sel1, (int)H1, pos_thresh, neg_thresh,
+                 h01, h10, keep0, keep1, D01, D10, terms, out, h->status_dev, GMF_STATUS_LOSS_INDEX};
+  GMF_HIP(gmf::launch_hcl_forward(a, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_hardest_contrastive_backward(gmf_handle* h, const float* F0, long long N0, const float* F1, long long N1, int C,
+                                     const long long* pairs, long long K, const long long* pos_sel, long long P, const long long* h01,
+                                     const long long* h10, const unsigned char* keep0, const unsigned char* keep1, const float* D01,
+                                     const float* D10, const float* terms, const float* out, float neg_thresh, const float* g_pos,
+                                     const float* g_neg, float* rows0, long long* dest0, float* rows1, long long* dest1,
+                                     gmf_stream_t stream) {
+  GMF_REQUIRE(h && F0 && F1 && pairs && h01 && h10 && keep0 && keep1 && D01 && D10 && terms && out && g_pos && g_neg && rows0 &&
+                  dest0 && rows1 && dest1,
+              GMF_ERR_BAD_ARG, "hardest_contrastive_backward: null pointer");
+  GMF_REQUIRE(C >= 1 && C <= 64, GMF_ERR_UNSUPPORTED_SHAPE, "hardest_contrastive_backward: C must be in 1..64");
+  GMF_REQUIRE(N0 >= 1 && N1 >= 1 && N0 < (1LL << 31) && N1 < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "hardest_contrastive_backward: N0 and N1 must be in 1 .. 2^31 - 1");
+  GMF_REQUIRE(K >= 1 && P >= 1 && P < (1LL << 24) && (pos_sel || P == K), GMF_ERR_UNSUPPORTED_SHAPE,
+              "hardest_contrastive_backward: K >= 1 and P in 1 .. 2^24 - 1 (P = K without pos_sel)");
+  SetDevice sd(h, stream);
+  gmf::HclBwdArgs a{F0, F1, (int)N0, (int)N1, C, pairs, K, pos_sel, (int)P, h01, h10, keep0, keep1, D01, D10, terms, out, neg_thresh,
+                    g_pos, g_neg, rows0, dest0, rows1, dest1};
+  GMF_HIP(gmf::launch_hcl_backward(a, S(stream)));
+  return GMF_OK;
+}
+
+int gmf_rows_sum_by_dest(gmf_handle* h, const float* rows, long long E, const long long* order, const long long* row_start,
+                         long long N, int C, float* out, gmf_stream_t stream) {
+  GMF_REQUIRE(h && rows && order && row_start && out, GMF_ERR_BAD_ARG, "rows_sum_by_dest: null pointer");
+  GMF_REQUIRE(E >= 1 && N >= 1 && N < (1LL << 31) && C >= 1 && C <= 64, GMF_ERR_UNSUPPORTED_SHAPE,
+              "rows_sum_by_dest: E >= 1, N in 1 .. 2^31 - 1 and C in 1..64");
+  SetDevice sd(h, stream);
+  GMF_HIP(gmf::launch_rows_sum_by_dest(rows, E, order, row_start, N, C, out, S(stream)));
+  return GMF_OK;
+}
+
 int gmf_batchnorm_masked_forward(gmf_handle* h, const float* x, const float* residual, const float* gamma, const float* beta,
                                  const int* n_rows, long long cap, int C, float eps, float momentum, int relu, float* y, float* mean,
                                  float* rstd, float* running_mean, float* running_var, gmf_stream_t stream) {

@@ -382,6 +382,59 @@ def sparse_conv_narrow(plan: SparsePlan, map_index: int, out_level: int, x, W, s
     return out
 
 
+def sparse_conv_narrow_wgrad(plan: SparsePlan, map_index: int, out_level: int, x, dy):
+    """Weight gradient of `sparse_conv_narrow` (`gmf_sparse_conv_narrow_wgrad`; Cin <= 8, Cout <= 64, FCGF's conv1): dW [K, Cin,
+    Cout] as `sparse_conv_wgrad` defines it, exactly 0 for an offset without pairs.  x [M, Cin], dy [M, Cout]; map_index must name
+    a map of the plan.  One wave per chunk of an offset's pair list, lane = output channel; chunks of a fixed size added in chunk
+    order (a function of the map, K and Cout): bitwise repeatable."""
+    what = "sparse_conv_narrow_wgrad"
+    x = _f32_dev(x, "x", what)
+    dy = _f32_dev(dy, "dy", what)
+    M = plan.M
+    if x.dim() != 2 or x.shape[0] != M or dy.dim() != 2 or dy.shape[0] != M:
+        _fail(what, f"`x` and `dy` must be [M = {M}, C] (got {tuple(x.shape)}, {tuple(dy.shape)})")
+    if map_index is None or not (0 <= int(map_index) < len(plan.maps)):
+        _fail(what, "`map_index` must name a kernel map of the plan")
+    cin, cout = x.shape[1], dy.shape[1]
+    if not (1 <= cin <= 8 and 1 <= cout <= 64):
+        _fail(what, f"Cin must be in 1..8 and Cout in 1..64 (got {cin}, {cout})", NotImplementedError)
+    K, rp, pairs, by_off, off_start = _map_arrays(plan, map_index, out_level, what)
+    dW = torch.empty((K, cin, cout), dtype=torch.float32, device=x.device)
+    h, st = handle_and_stream(x)
+    h.call("gmf_sparse_conv_narrow_wgrad", rp.data_ptr(), pairs.data_ptr(), by_off.data_ptr(), off_start.data_ptr(), K,
+           plan.count_ptr(out_level), x.data_ptr(), cin, dy.data_ptr(), cout, dW.data_ptr(), st)
+    return dW
+
+
+class _SparseConvNarrowFn(torch.autograd.Function):
+    """y = sparse_conv_narrow(x, W) over one map of a plan, differentiable in W only (a network's first convolution: its input
+    needs no gradient).  Backward: `sparse_conv_narrow_wgrad`."""
+
+    @staticmethod
+    def forward(ctx, plan, map_index, out_level, x, W):
+        W3 = W.detach() if W.dim() == 3 else W.detach().unsqueeze(0)
+        ctx.plan, ctx.map_index, ctx.out_level, ctx.wshape = plan, map_index, out_level, W.shape
+        ctx.save_for_backward(x.detach())
+        return sparse_conv_narrow(plan, map_index, out_level, x.detach(), W3)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        dW = None
+        if ctx.needs_input_grad[4]:
+            dy = _f32_dev(dy, "grad", "sparse_conv_narrow backward")
+            dW = sparse_conv_narrow_wgrad(ctx.plan, ctx.map_index, ctx.out_level, x, dy).reshape(ctx.wshape)
+        return None, None, None, None, dW
+
+
+def sparse_conv_narrow_train(plan: SparsePlan, map_index: int, out_level: int, x, W):
+    """`sparse_conv_narrow` with its weight gradient (`sparse_conv_narrow_wgrad`); x gets no gradient and must not need one."""
+    if isinstance(x, torch.Tensor) and x.requires_grad:
+        _fail("sparse_conv_narrow_train", "`x` requires a gradient: the narrow convolution has no data gradient "
+              "(use sparse_conv_train)", NotImplementedError)
+    return _SparseConvNarrowFn.apply(plan, map_index, out_level, x, W)
+
+
 def sparse_head_l2(plan: SparsePlan, level: int, xa, W1, W2, xb=None, bias=None, normalize: bool = False, out=None):
     """FCGF's head (resunet.py:641-648) on `gmf_sparse_head_l2`, one launch: y = relu([xa | xb] W1) W2 + bias, then, if
     `normalize`, y / (||y||_2 + 1e-8) per row.  xa [M, ca], xb [M, cb], W1 [ca + cb, hid] (or [1, ca + cb, hid]), W2 [hid, cout]

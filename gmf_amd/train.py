@@ -717,6 +717,91 @@ def resunet_train(model, coords, feats, p_image=None, q_image=None, p_tokens=Non
 
 
 # =====================================================================================================================
+# FCGF's ResUNetBN2C in training mode (GMF_DeepGlobalRegistration_fcgf/model/resunet.py:598-650 with batch-statistics BatchNorm):
+# the trunk above without a bottleneck, conv1 on the narrow-input kernels, and the head composed of two 1x1 convolutions and the
+# row normalisation (the eval forward's one-launch head, `sparse_head_l2`, has no backward and stays eval-only).
+
+
+# Not `_Normalize`: that is F.normalize's x / max(||x||, 1e-12); this is FCGF's x / (||x|| + 1e-8) - other bits, another kernel.
+class _RowNormEps(torch.autograd.Function):
+    """y = x / (||x||_2 + 1e-8) per row of x [rows, C] (resunet.py:647-648; `gmf_rownorm_eps`): dx = dy / s - x <x, dy> / (||x|| s^2)
+    with s = ||x|| + 1e-8.  A zero row gives a zero row and a zero gradient."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.detach().contiguous()
+        nrm = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
+        y = torch.empty_like(x)
+        _call("gmf_rownorm_eps", x, 0, x, None, nrm, y, x.shape[0], x.shape[1])
+        ctx.save_for_backward(x, nrm)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, nrm = ctx.saved_tensors
+        dy = require_cuda_f32(dy, "grad").contiguous()
+        dx = torch.empty_like(x)
+        _call("gmf_rownorm_eps", x, 1, x, dy, nrm, dx, x.shape[0], x.shape[1])
+        return dx
+
+
+def normalize_rows_eps(x):
+    """FCGF's feature normalisation x / (||x||_2 + 1e-8) on the rows of x [rows, C] (float32, on the device), differentiable."""
+    x = require_cuda_f32(x, "x")
+    if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] == 0:
+        raise RuntimeError(f"gmf_amd.train.normalize_rows_eps: `x` must be a non-empty [rows, C] tensor (got {tuple(x.shape)})")
+    return _RowNormEps.apply(x)
+
+
+def fcgf_train(model, coords, feats):
+    """The differentiable train-mode forward of a gmf_amd.fcgf.ResUNetBN2C (resunet.py:598-650, batch-statistics BatchNorm):
+    features [M, out_channels], aligned with the input rows; several clouds go through as batches of one plan (column 0 of
+    coords), as in the eval forward - the BatchNorm statistics then span the whole batch, as MinkowskiEngine's do.  Gradients
+    reach the 23 kernels, final.bias and the 21 BatchNorms; every running statistic is updated as torch does.  conv1 runs on the
+    narrow-input kernels (`sparse_conv_narrow`, weight gradient `sparse_conv_narrow_wgrad`) when model.narrow_conv1 is set and
+    in_channels <= 8, else on the generic ones; `feats` gets no gradient on the narrow path.  The head is conv1_tr (+ ReLU), final
+    (+ bias) and, with normalize_feature, y / (||y|| + 1e-8), each its own differentiable call.  Reads the four level counts to the
+    host once, to raise as torch's BatchNorm does on a level of fewer than 2 rows."""
+    from . import sparse as SP
+    from .fcgf import NARROW_MAX_CIN
+    from .fcgf import ResUNetBN2C as _FCGF
+    what = "gmf_amd.train.fcgf_train"
+    if not isinstance(model, _FCGF):
+        raise RuntimeError(f"{what}: `model` must be a gmf_amd.fcgf.ResUNetBN2C (got {type(model).__name__})")
+    if not model.training:
+        raise RuntimeError(f"{what}: the model is in eval() mode - call train(), or use forward() for inference")
+    if not torch.is_grad_enabled():
+        raise RuntimeError(f"{what}: autograd is disabled (torch.no_grad()); the eval forward is model.forward")
+    M, D = SP.check_coords(coords, "fcgf_train")
+    if D != model.D:
+        raise RuntimeError(f"{what}: coords have D = {D}, the network was built for D = {model.D}")
+    feats = require_cuda_f32(feats, "feats").contiguous()
+    if feats.shape != (M, model.in_channels):
+        raise RuntimeError(f"{what}: `feats` must be [{M}, {model.in_channels}] (got {tuple(feats.shape)})")
+    narrow = bool(model.narrow_conv1) and model.in_channels <= NARROW_MAX_CIN and not feats.requires_grad
+    plan, where = model._plan(coords, conv1_needs_pairs=narrow)
+    counts = plan.counts.tolist()
+    if min(counts) < 2:
+        raise RuntimeError(f"{what}: a level has fewer than 2 rows (counts {counts}); BatchNorm in training mode needs more than "
+                           "1 value per channel")
+
+    def layer(i, xa, xb=None, residual=None, relu=False):
+        conv, norm = SP.TRUNK[i][:2]
+        m, lvl = where[i]
+        W = model.get_submodule(conv).kernel
+        if i == 0 and narrow:
+            y = SP.sparse_conv_narrow_train(plan, m, lvl, xa, W)
+        else:
+            y = SP.sparse_conv_train(plan, m, lvl, xa, W, xb=xb)
+        return batchnorm_masked(y, model.get_submodule(norm).bn, plan, lvl, residual=residual, relu=relu)
+
+    t1, s1 = SP.resunet_trunk(layer, feats)
+    o = SP.sparse_conv_train(plan, None, 0, t1, model.conv1_tr.kernel, xb=s1, relu=True)     # :641-643 MEF.relu(conv1_tr(ME.cat(..)))
+    y = SP.sparse_conv_train(plan, None, 0, o, model.final.kernel, bias=model.final.bias)    # :644 final (+ bias)
+    return _RowNormEps.apply(y) if model.normalize_feature else y                            # :647-648
+
+
+# =====================================================================================================================
 # The image encoder in train() mode (ResNet-34 -> layer2, GMF_PointDSC/models/resnet.py:36-75,195-216; trained by both
 # plugins, PointDSC.py:129-135): every operation a HIP kernel of this library (gmf_amd/csrc/image_train_kernels.hip and the
 # BatchNorm / ReLU / column-sum primitives above).  Activations travel as dense NHWC fp32, i.e. as [B * H * W, C] row

@@ -86,6 +86,9 @@ long long gmf_workspace_wanted(gmf_handle* h);
 #define GMF_STATUS_BATCHNORM_ROWS 8
 /* gmf_posegraph_optimize met a pivot of H + lambda I that was not finite or not positive (stop code 6 of that graph and pass) */
 #define GMF_STATUS_POSEGRAPH_PIVOT 16
+/* gmf_hardest_contrastive_forward met a row index outside its tensor (positive_pairs, pos_sel, sel0 or sel1): that index was
+ * read as 0 and the loss is not valid. */
+#define GMF_STATUS_LOSS_INDEX 32
 int gmf_status_read(gmf_handle* h, int* flags, int clear);
 
 /* [ABI 5] PointDSC's learnable scalar `sigma` (PointDSC.py:164) from DEVICE memory.  While `sigma_dev` is non-NULL every entry point
@@ -907,6 +910,56 @@ int gmf_sparse_pack_resunet(gmf_handle* h, const gmf_tensor* tensors, int n_tens
 int gmf_sparse_conv_wgrad(gmf_handle* h, const int* row_ptr, const int* pairs, const int* by_off, const int* off_start, int K,
                           const int* n_out, const float* xa, int ca, const float* xb, int cb, const float* dy, int cout, float* dW,
                           gmf_stream_t stream);
+
+/* Weight gradient of gmf_sparse_conv_narrow (FCGF's conv1), fp32: dW [K, cin, cout] as gmf_sparse_conv_wgrad defines it, for
+ * cin 1..8 and cout 1..64 over a map of gmf_sparse_build_plan (all four map arrays; the identity map has no narrow form).  One
+ * wave per chunk walks the offset-major list with lane = output channel, cin accumulators per lane, dy rows read coalesced and
+ * the input values broadcast.  Sum order: each offset's pair list is cut into chunks of P = max(64, ceil(nnz / 2048)) pairs over
+ * S = K + 2048 slots; inside a chunk, with G = 1, 2, 4 lane groups for cout > 32, > 16, <= 16, group g adds pairs g, g + G, .. as
+ * one fma chain in pair order and the groups are added in group order; an offset's chunks are added in chunk order by a second
+ * pass.  The order depends only on the map, K and cout: bitwise repeatable, no float atomics; 0 for an offset without pairs.
+ * Workspace: S x cin x cout + K + 2 floats.  No host synchronisation. */
+int gmf_sparse_conv_narrow_wgrad(gmf_handle* h, const int* row_ptr, const int* pairs, const int* by_off, const int* off_start, int K,
+                                 const int* n_out, const float* x, int cin, const float* dy, int cout, float* dW,
+                                 gmf_stream_t stream);
+
+/* FCGF's row normalisation (model/resunet.py:647-648) and its backward on x [rows, C], fp32, C 1..4096.  backward == 0: nrm[r] =
+ * sqrt(sum_c x_c^2), out[r] = x[r] / (nrm[r] + 1e-8).  backward != 0: out = dx = dy / s - x <x, dy> / (nrm s^2), s = nrm + 1e-8,
+ * from the forward's x and nrm.  A row with nrm == 0 gets a zero row in either direction.  (gmf_normalize_rows is F.normalize's
+ * x / max(||x||, 1e-12): another function.)  One wave per row; no workspace, no host synchronisation. */
+int gmf_rownorm_eps(gmf_handle* h, int backward, const float* x, const float* dy, float* nrm, float* out, long long rows, int C,
+                    gmf_stream_t stream);
+
+/* FCGF's hardest-contrastive loss with the random draws as arguments.  F0 [N0, C], F1 [N1, C] fp32 (C 1..64); pairs [K, 2] int64
+ * rows (i, j) into F0 / F1; keys [K] int64: i + j max(N0, N1) of all K pairs, sorted ascending; pos_sel [P] int64 indices into
+ * pairs (NULL: all pairs, P = K); sel0 [H0], sel1 [H1] int64 candidate-negative rows of F0 / F1.  For every sampled pair k = (i, j):
+ *   h01[k] = the row s of sel1 with the smallest sum_c (F0[i] - F1[s])^2 (one fp32 fma chain over c; equal scores: the first
+ *   position in sel1), D01[k] = sqrt(that sum + 1e-7), keep0[k] = (i, h01[k]) is not among the K pairs (binary search in keys);
+ *   h10 / D10 / keep1 likewise over sel0 against F1[j], the pair tested being (h10[k], j).
+ *   terms [3, P] = relu(sum_c (F0[i] - F1[j])^2 - pos_thresh), keep0 relu(neg_thresh - D01)^2, keep1 relu(neg_thresh - D10)^2.
+ * out [4] = (pos_loss = mean of terms[0], neg_loss = (mean over keep0 of terms[1] + mean over keep1 of terms[2]) / 2 with a mean
+ * over no rows 0, the count of keep0, the count of keep1).  Sums: thread-strided over k, then a fixed tree - bitwise repeatable.
+ * An index outside its tensor sets GMF_STATUS_LOSS_INDEX and is read as 0.  No workspace, no host synchronisation. */
+int gmf_hardest_contrastive_forward(gmf_handle* h, const float* F0, long long N0, const float* F1, long long N1, int C,
+                                    const long long* pairs, long long K, const long long* keys, const long long* pos_sel, long long P,
+                                    const long long* sel0, long long H0, const long long* sel1, long long H1, float pos_thresh,
+                                    float neg_thresh, long long* h01, long long* h10, unsigned char* keep0, unsigned char* keep1,
+                                    float* D01, float* D10, float* terms, float* out, gmf_stream_t stream);
+/* Backward of gmf_hardest_contrastive_forward from its outputs, first half: g_pos / g_neg (device scalars) are the gradients of
+ * pos_loss / neg_loss.  rows0 [3P, C] with dest0 [3P] int64 are the gradient rows into F0 and their rows: 3k the positive term
+ * -> i_k, 3k + 1 the negative term of side 0 -> i_k, 3k + 2 the negative term of side 1 -> h10[k]; rows1 / dest1 into F1 (-> j_k,
+ * j_k, h01[k]).  An inactive hinge or a dropped row writes zeros.  gmf_rows_sum_by_dest adds them per destination row. */
+int gmf_hardest_contrastive_backward(gmf_handle* h, const float* F0, long long N0, const float* F1, long long N1, int C,
+                                     const long long* pairs, long long K, const long long* pos_sel, long long P, const long long* h01,
+                                     const long long* h10, const unsigned char* keep0, const unsigned char* keep1, const float* D01,
+                                     const float* D10, const float* terms, const float* out, float neg_thresh, const float* g_pos,
+                                     const float* g_neg, float* rows0, long long* dest0, float* rows1, long long* dest1,
+                                     gmf_stream_t stream);
+/* out [N, C] (C 1..64): out[r] = sum over e in [row_start[r], row_start[r + 1]) of rows[order[e]], added in that order; rows
+ * [E, C], order [E] and row_start [N + 1] int64 - a CSR by destination row (a stable sort of the destinations gives a fixed order:
+ * bitwise repeatable, no float atomics).  A row without entries gets zeros. */
+int gmf_rows_sum_by_dest(gmf_handle* h, const float* rows, long long E, const long long* order, const long long* row_start,
+                         long long N, int C, float* out, gmf_stream_t stream);
 
 /* MinkowskiBatchNorm in TRAINING mode (nn.BatchNorm1d over the valid rows of all batches) on a sparse level: x [cap, C] row-major,
  * *n_rows (device pointer, a plan's level count) valid rows first.  y = gamma (x - mean) rstd + beta, + residual [cap, C] (may be
