@@ -17,6 +17,7 @@
 
 #include "mfma_core.hpp"
 #include "launchers.hpp"
+#include "gemm_plan.hpp"
 
 namespace gmf {
 
@@ -31,6 +32,8 @@ namespace gmf {
 //   part[(b * ksplits + ks)][M][N]; k_gemm_reduce adds them in index order and applies alpha / bias / R.
 //   grid (ceil(N / 128), ceil(M / 128), batch * ksplits), block 256.
 // =========================================================================================
+// The fused ReLU of every epilogue here is relu_nan (mfma_core.hpp), which keeps a NaN as torch's relu does: fmaxf(NaN, 0) is 0
+// and would turn a non-finite product into a clean zero.
 template <bool TA, bool TB, int RB>
 __global__ void __launch_bounds__(256, 2)
 k_gemm_f32(const float* __restrict__ A, const float* __restrict__ Bm, float* __restrict__ C, const float* __restrict__ bias,
@@ -185,7 +188,7 @@ k_gemm_f32(const float* __restrict__ A, const float* __restrict__ Bm, float* __r
           float v = alpha * acc[rb][cb][r];
           if (bias) v += bias[col];
           if (R) v += R[(size_t)b * sC + (size_t)row * ldc + col];
-          C[(size_t)b * sC + (size_t)row * ldc + col] = relu ? fmaxf(v, 0.f) : v;
+          C[(size_t)b * sC + (size_t)row * ldc + col] = relu ? relu_nan(v) : v;
         }
       }
     }
@@ -351,7 +354,7 @@ k_gemm_lds(const float* __restrict__ A, const float* __restrict__ Bm, float* __r
           float v = alpha * acc[rb][cb][r];
           if (bias) v += bias[col];
           if (R) v += R[(size_t)b * sC + (size_t)row * ldc + col];
-          C[(size_t)b * sC + (size_t)row * ldc + col] = relu ? fmaxf(v, 0.f) : v;
+          C[(size_t)b * sC + (size_t)row * ldc + col] = relu ? relu_nan(v) : v;
         }
       }
     }
@@ -382,7 +385,7 @@ k_gemm_reduce(const float* __restrict__ part, float* __restrict__ C, const float
   float v = alpha * t;
   if (bias) v += bias[col];
   if (R) v += R[(size_t)b * sC + (size_t)row * ldc + col];
-  C[(size_t)b * sC + (size_t)row * ldc + col] = relu ? fmaxf(v, 0.f) : v;
+  C[(size_t)b * sC + (size_t)row * ldc + col] = relu ? relu_nan(v) : v;
 }
 
 // =========================================================================================
@@ -413,7 +416,7 @@ k_lcpe_bwd(const float* __restrict__ dy, const float* __restrict__ w, float* __r
 }
 
 // =========================================================================================
-// LayerNorm over the last dim (C <= 1024, one wave per row).  Forward saves mean and rstd per row.
+// LayerNorm over the last dim (any C: one wave per row, its lanes loop over the row).  Forward saves mean and rstd per row.
 // Backward: g = dy * gamma ; dx = rstd * (g - mean(g) - xhat * mean(g * xhat)) (+ dx_add when given: the residual path).
 // =========================================================================================
 GMF_DEVINL float wave_sum_f(float v) {
@@ -467,7 +470,8 @@ k_ln_bwd(const float* __restrict__ dy, const float* __restrict__ x, const float*
 }
 
 // =========================================================================================
-// Row softmax of scale * S (T <= 4096, one wave per row) and its backward dS = scale * P * (dP - sum_j dP_j P_j).
+// Row softmax of scale * S (any T: one wave per row, its lanes loop over the row) and its backward
+// dS = scale * P * (dP - sum_j dP_j P_j).
 // =========================================================================================
 __global__ void __launch_bounds__(256)
 k_softmax_fwd(const float* __restrict__ S, const float* __restrict__ mul, float* __restrict__ P, long rows, int T, float scale) {
@@ -661,7 +665,7 @@ k_bn_apply(const float* __restrict__ x, const float* __restrict__ res, const flo
   const int c = (int)(idx % C);
   float v = fmaf((x[idx] - mean[c]) * rstd[c], gamma[c], beta[c]);
   if (kRes) v += res[idx];
-  y[idx] = relu ? fmaxf(v, 0.f) : v;
+  y[idx] = relu ? relu_nan(v) : v;
 }
 
 __global__ void __launch_bounds__(256)
@@ -797,49 +801,25 @@ k_sm_consts(const float* __restrict__ gt, float* __restrict__ consts, int B, int
 // -----------------------------------------------------------------------------------------
 static inline unsigned blocks_of(long total) { return (unsigned)((total + 255) / 256); }
 
-// Workgroup tile of a product: 128 x 128 when that alone gives the chip two workgroups per CU; else 64-row tiles, and 64-column
-// tiles too (LDS-staged kernel only) when the 64 x 128 tiling would still have to split a contraction it can do whole
-static inline void gemm_tile(int M, int N, int K, int batch, bool lds_ok, int* bm, int* bn) {
-  const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128) * batch;
-  *bm = (t128 < 512 && M > 64) ? 64 : 128;
-  *bn = 128;
-  const long t64 = (long)((M + *bm - 1) / *bm) * ((N + 127) / 128) * batch;
-  if (lds_ok && *bm == 64 && t64 < 384 && K >= 256 && N > 64) *bn = 64;
-}
-
-static inline bool gemm_lds_ok(bool ta, bool tb, const float* A, const float* B, int M, int N, int K, long lda, long ldb, long sA,
-                               long sB) {
-  // the LDS-staged kernel needs 16-byte pieces along each operand's contiguous dimension
-  const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool a_ok = al16(A) && lda % 4 == 0 && sA % 4 == 0 && (ta ? M % 4 == 0 : K % 4 == 0);
-  const bool b_ok = al16(B) && ldb % 4 == 0 && sB % 4 == 0 && (tb ? K % 4 == 0 : N % 4 == 0);
-  return a_ok && b_ok && K >= 4 && M >= 4 && N >= 4;
+// The launch decision (kernel, tile, k-splits, reduce groups) lives in gemm_plan.hpp, HIP-free and tested on the host
+static inline GemmGeom gemm_geom(bool ta, bool tb, const float* A, const float* B, int M, int N, int K, long lda, long ldb, long sA,
+                                 long sB, int batch) {
+  return GemmGeom{ta, tb, M, N, K, lda, ldb, sA, sB, batch, (int)(reinterpret_cast<uintptr_t>(A) & 15),
+                  (int)(reinterpret_cast<uintptr_t>(B) & 15)};
 }
 
 int gemm_ksplits(bool ta, bool tb, const float* A, const float* B, int M, int N, int K, long lda, long ldb, long sA, long sB,
                  int batch) {
-  // few output tiles and a long contraction (weight gradients: K = every row of the batch): split K so that the launch has
-  // ~768 workgroups, each split at least 64 deep, the partial tiles at most ~48 MB (written and read once by k_gemm_reduce)
-  int bm, bn;
-  gemm_tile(M, N, K, batch, gemm_lds_ok(ta, tb, A, B, M, N, K, lda, ldb, sA, sB), &bm, &bn);
-  const long tiles = (long)((M + bm - 1) / bm) * ((N + bn - 1) / bn) * batch;
-  if (tiles >= 384 || K < 256) return 1;
-  long s = std::min<long>((768 + tiles - 1) / tiles, K / 64);
-  const long out_bytes = (long)M * N * batch * 4;
-  s = std::min<long>(s, std::max<long>(1, (48L << 20) / out_bytes));
-  return (int)std::max<long>(1, std::min<long>(s, 128));
+  return gemm_ksplits_wanted(gemm_geom(ta, tb, A, B, M, N, K, lda, ldb, sA, sB, batch));
 }
 
 hipError_t launch_gemm_f32(bool ta, bool tb, const float* A, const float* B, float* C, const float* bias, const float* R, int M, int N,
                            int K, long lda, long ldb, long ldc, long sA, long sB, long sC, int batch, float alpha, float* part,
                            int ksplits, int relu, hipStream_t s) {
-  if (!part) ksplits = 1;
-  int kchunk = (K + ksplits - 1) / ksplits;
-  kchunk = (kchunk + 15) / 16 * 16;
-  ksplits = (K + kchunk - 1) / kchunk;
-  const bool lds_ok = gemm_lds_ok(ta, tb, A, B, M, N, K, lda, ldb, sA, sB);    // anything else takes the register-direct kernel
-  int bm, bn;
-  gemm_tile(M, N, K, batch, lds_ok, &bm, &bn);
+  const GemmPlan plan = gemm_plan(gemm_geom(ta, tb, A, B, M, N, K, lda, ldb, sA, sB, batch), part ? ksplits : 1);
+  ksplits = plan.ksplits;
+  const int kchunk = plan.kchunk, bm = plan.bm, bn = plan.bn;
+  const bool lds_ok = plan.lds;
   const dim3 grid((N + bn - 1) / bn, (M + bm - 1) / bm, batch * ksplits);
 #define GMF_GEMM_ARGS grid, dim3(256), 0, s, A, B, C, bias, R, M, N, K, lda, ldb, ldc, sA, sB, sC, ksplits, kchunk, alpha, part, relu
 #define GMF_GEMM_LDS(TA, TB)                                                                         \
@@ -869,7 +849,7 @@ hipError_t launch_gemm_f32(bool ta, bool tb, const float* A, const float* B, flo
 #undef GMF_GEMM_ARGS
   if (ksplits > 1) {
     const long total = (long)batch * M * N;
-    const int groups = ksplits > 64 ? 16 : ksplits > 32 ? 8 : ksplits > 16 ? 4 : ksplits > 8 ? 2 : 1;
+    const int groups = plan.reduce_groups;
     hipLaunchKernelGGL(k_gemm_reduce, dim3((unsigned)((total + 63) / 64)), dim3(64 * groups), 0, s, part, C, bias, R, M, N, ldc, sC, ksplits, alpha, total, relu);
   }
   return hipGetLastError();

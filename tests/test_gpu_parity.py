@@ -2786,12 +2786,13 @@ def test_training_primitives_against_torch():
     gen = torch.Generator().manual_seed(11)
     rn = lambda *s: _gpu(torch.randn(*s, generator=gen))
     A, Bm = rn(70, 45), rn(45, 133)
-    assert _maxerr(T_.gemm(A, Bm).cpu(), (A @ Bm).cpu()) < 1e-4
-    assert _maxerr(T_.gemm(A.t().contiguous(), Bm, ta=True).cpu(), (A @ Bm).cpu()) < 1e-4
-    assert _maxerr(T_.gemm(A, Bm.t().contiguous(), tb=True).cpu(), (A @ Bm).cpu()) < 1e-4
-    assert _maxerr(T_.gemm(A.t().contiguous(), Bm.t().contiguous(), ta=True, tb=True).cpu(), (A @ Bm).cpu()) < 1e-4
+    AB = A.double() @ Bm.double()                              # the float64 product: the same bounds against the true value
+    assert _maxerr(T_.gemm(A, Bm).cpu().double(), AB.cpu()) < 1e-4
+    assert _maxerr(T_.gemm(A.t().contiguous(), Bm, ta=True).cpu().double(), AB.cpu()) < 1e-4
+    assert _maxerr(T_.gemm(A, Bm.t().contiguous(), tb=True).cpu().double(), AB.cpu()) < 1e-4
+    assert _maxerr(T_.gemm(A.t().contiguous(), Bm.t().contiguous(), ta=True, tb=True).cpu().double(), AB.cpu()) < 1e-4
     bias, R = rn(133), rn(70, 133)
-    assert _maxerr(T_.gemm(A, Bm, bias=bias, residual=R, alpha=0.5).cpu(), (0.5 * (A @ Bm) + bias + R).cpu()) < 1e-4
+    assert _maxerr(T_.gemm(A, Bm, bias=bias, residual=R, alpha=0.5).cpu().double(), (0.5 * AB + bias + R).cpu()) < 1e-4
     X, Y = rn(20000, 96), rn(20000, 160)                       # K = 20000 rows: split-K
     ref = (X.double().t() @ Y.double()).float()
     assert _maxerr(T_.gemm(X, Y, ta=True).cpu(), ref.cpu()) < 2e-5 * float(ref.abs().max())
@@ -2809,7 +2810,7 @@ def test_training_primitives_against_torch():
     A3, B3 = rn(5, 300, 64), rn(5, 264, 64)                    # batched Q K^T shape
     out3 = torch.empty(5, 300, 264, device=DEV)
     T_.gemm(A3, B3, tb=True, out=out3, m=300, n=264, k=64, lda=64, ldb=64, ldc=264, batch=5, sa=300 * 64, sb=264 * 64, sc=300 * 264)
-    assert _maxerr(out3.cpu(), torch.matmul(A3, B3.transpose(1, 2)).cpu()) < 1e-4
+    assert _maxerr(out3.cpu().double(), torch.matmul(A3.double(), B3.double().transpose(1, 2)).cpu()) < 1e-4
     P3 = rn(3, 1000, 1000)                                     # long contraction with few tiles: split-K through the LDS kernel
     V3 = rn(3, 1000, 128)
     out4 = torch.empty(3, 1000, 128, device=DEV)
