@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "sparse_conv_plan.hpp"
+
 namespace gmf {
 
 constexpr int kSparseMaxD = 6;          // spatial dimensions (the batch index is column 0 on top)
@@ -56,16 +58,14 @@ struct SparseConvArgs {
   int nsplit; float* partial;
   float* y;
 };
-// output-row groups of one convolution (a function of its shape and cap_out; it does not change any result)
-int sparse_conv_row_groups(int K, int cin, int cout, int nsplit, long long cap_out);
+// grid: (nsplit, 64-channel blocks, sparse_conv_row_groups(..)) - sparse_conv_plan.hpp
 hipError_t launch_sparse_conv(const SparseConvArgs& a, hipStream_t s);
 
 // Narrow-input convolution (FCGF's conv1: Cin = 1, k = 7): y[o] = epilogue(one fma chain over the CSR pairs (d, i) of row o,
 // d ascending, input channels in order within a pair, of x[i][k] W[d][k][c]).  Each output row is computed whole by one group
-// of lanes; W sits in LDS when it fits (kSparseNarrowLdsBytes), else it is read from global memory.
+// of lanes; W sits in LDS when it fits (sparse_narrow_lds, sparse_conv_plan.hpp), else it is read from global memory.
 constexpr int kSparseNarrowMaxCin = 8;
 constexpr int kSparseNarrowMaxCout = 64;
-constexpr long long kSparseNarrowLdsBytes = 64 << 10;
 struct SparseNarrowArgs {
   const int* row_ptr; const int2* pairs; int K;
   const int* n_out; long long cap_out;

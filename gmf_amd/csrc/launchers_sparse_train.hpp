@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "sparse_conv_plan.hpp"
+
 namespace gmf {
 
 // Weight gradient of one sparse convolution: dW[d] = sum over the pairs (d, i -> o) of map (row_ptr, pairs, by_off, off_start)
@@ -13,9 +15,8 @@ namespace gmf {
 // ceil(nnz / (nslots - K))) with nnz the map's pair count, so the chunks fit the nslots slots; chunk_info[d] (d = 0..K) is the
 // first slot of offset d.  k_sparse_wgrad gives each slot its own workgroups (64 x 64 tiles of dW[d]) and writes the chunk's
 // sum into partial[slot]; k_wgrad_reduce adds an offset's chunks in chunk order (zero for an offset without pairs).  Every
-// element's order depends only on the map and nslots (a function of K): bitwise repeatable, no float atomics.
-constexpr int kWgradMinChunk = 64;
-inline int sparse_wgrad_slots(int K) { return K + (K > 256 ? K : 256); }
+// element's order depends only on the map and nslots (a function of K): bitwise repeatable, no float atomics.  kWgradMinChunk,
+// sparse_wgrad_slots, sparse_wgrad_narrow_slots and the chunk length sparse_wgrad_chunk: sparse_conv_plan.hpp.
 struct SparseWgradArgs {
   const int* row_ptr; const int2* pairs; const int* by_off; const int* off_start; int K;
   const int* n_out;
@@ -36,7 +37,6 @@ hipError_t launch_sparse_wgrad(const SparseWgradArgs& a, hipStream_t s);
 // offset's chunks in chunk order.  No float atomics.
 constexpr int kWgradNarrowMaxCin = 8;
 constexpr int kWgradNarrowMaxCout = 64;
-inline int sparse_wgrad_narrow_slots(int K) { return K + 2048; }
 hipError_t launch_sparse_wgrad_narrow(const SparseWgradArgs& a, hipStream_t s);
 
 // FCGF's row normalisation y = x / (||x||_2 + 1e-8) on x [rows, C] (resunet.py:647-648) and its backward, one wave per row.
@@ -81,9 +81,8 @@ hipError_t launch_rows_sum_by_dest(const float* rows, long long E, const long lo
 
 // BatchNorm1d in training mode over the first *n rows of x [cap, C] (the valid rows of a sparse level).  Forward: y =
 // relu?(gamma (x - mean) rstd + beta + residual?) for rows < *n, 0 beyond; running statistics updated as torch does; *n < 2 ORs
-// `status_bit` into *status and leaves the running statistics alone.  Column sums run over kBnmChunks(cap) fixed row chunks, the
-// chunks added in order.  `part` holds bnm_part_floats(cap, C) floats.
-int bnm_chunks(long long cap);
+// `status_bit` into *status and leaves the running statistics alone.  Column sums run over bnm_chunks(cap) fixed row chunks
+// (sparse_conv_plan.hpp), the chunks added in order.  `part` holds bnm_part_floats(cap, C) floats.
 inline size_t bnm_part_floats(long long cap, int C) { return (size_t)bnm_chunks(cap) * C * 2; }
 hipError_t launch_bnm_forward(const float* x, const float* residual, const float* gamma, const float* beta, const int* n,
                               long long cap, int C, float eps, float momentum, int relu, float* y, float* mean, float* rstd,

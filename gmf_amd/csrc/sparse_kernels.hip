@@ -36,7 +36,7 @@ namespace gmf {
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kSparseWgThreads;
 constexpr int kKI = kSparseKeyInts;
 
 int blocks(long long n, int per) { return (int)((n + per - 1) / per); }
@@ -199,18 +199,21 @@ __global__ __launch_bounds__(kThreads) void k_map(const int* __restrict__ out_co
   if (!kFill && lane == 0) cnt[o] = w;
 }
 
-constexpr int kTM = 64, kTN = 64, kTK = 16;
+constexpr int kTM = kSparseConvTile, kTN = kSparseConvTile, kTK = 16;
+
+// The fused ReLU of every epilogue here keeps a NaN, as torch.relu and the training GEMM's relu_nan (mfma_core.hpp) do:
+// fmaxf(NaN, 0) is 0 and would hand a non-finite row on as a clean zero row.  `<=`, not relu_nan's `<`, so that every other
+// value keeps the bits fmaxf gave it: v_max_f32 returns +0 for (-0, +0).
+GMF_DEVINL float relu_keep_nan(float v) { return v <= 0.f ? 0.f : v; }
 
 GMF_DEVINL float epilogue(float v, int o, int oc, const SparseConvArgs& a) {
   if (a.scale || a.shift) v = fmaf(v, a.scale ? a.scale[oc] : 1.f, a.shift ? a.shift[oc] : 0.f);
   if (a.residual) v += a.residual[(size_t)o * a.cout + oc];
-  if (a.relu) v = fmaxf(v, 0.f);
+  if (a.relu) v = relu_keep_nan(v);
   return v;
 }
 
-// offset slices: slice(d) = d nsplit / K, so slice s holds d in [ceil(K s / nsplit), ceil(K (s + 1) / nsplit))
-GMF_DEVINL int slice_of(int d, int nsplit, int K) { return (int)((long long)d * nsplit / K); }
-GMF_DEVINL int slice_begin(int s, int nsplit, int K) { return (int)(((long long)K * s + nsplit - 1) / nsplit); }
+// offset slices (slice_of, slice_begin) and output-row groups: sparse_conv_plan.hpp
 
 // first index j in [lo, hi) with v[j] >= key (v ascending there)
 GMF_DEVINL int lower_bound(const int* __restrict__ v, int lo, int hi, int key) {
@@ -234,7 +237,7 @@ __global__ __launch_bounds__(kThreads) void k_sparse_conv(const SparseConvArgs a
   __shared__ int s_o[kTM], s_i[kTM], s_first[kTM];
   const int n_out = *a.n_out;
   const int split = blockIdx.x, col0 = blockIdx.y * kTN, grp = blockIdx.z;
-  const int rlo = (int)((long long)n_out * grp / gridDim.z), rhi = (int)((long long)n_out * (grp + 1) / gridDim.z);
+  const int rlo = sparse_conv_group_begin(n_out, grp, gridDim.z), rhi = sparse_conv_group_begin(n_out, grp + 1, gridDim.z);
   if (rlo >= rhi) return;
   const bool ident = a.row_ptr == nullptr;
   const int d0 = ident ? 0 : slice_begin(split, a.nsplit, a.K), d1 = ident ? 1 : slice_begin(split + 1, a.nsplit, a.K);
@@ -354,7 +357,7 @@ __global__ __launch_bounds__(kThreads) void k_split_reduce(const SparseConvArgs 
 GMF_DEVINL float narrow_epilogue(float v, int o, int oc, const SparseNarrowArgs& a) {
   if (a.scale || a.shift) v = fmaf(v, a.scale ? a.scale[oc] : 1.f, a.shift ? a.shift[oc] : 0.f);
   if (a.residual) v += a.residual[(size_t)o * a.cout + oc];
-  if (a.relu) v = fmaxf(v, 0.f);
+  if (a.relu) v = relu_keep_nan(v);
   return v;
 }
 
@@ -374,7 +377,7 @@ __global__ __launch_bounds__(kThreads) void k_sparse_conv_narrow(const SparseNar
     __syncthreads();
     W = narrow_ws;
   }
-  const int L = a.cout <= 16 ? 16 : (a.cout <= 32 ? 32 : 64);
+  const int L = sparse_narrow_lanes(a.cout);
   const int G = 64 / L;
   const int lane = threadIdx.x & 63, c = lane % L, gbase = lane - c;
   const int cc = c < a.cout ? c : a.cout - 1;        // lanes past cout compute a copy of the last channel and store nothing
@@ -437,7 +440,7 @@ __global__ __launch_bounds__(kThreads) void k_sparse_head_l2(const SparseHeadArg
     float h = 0.f;
     for (int k = 0; k < a.ca; ++k) h = fmaf(__shfl(xa, k), W1s[k * a.hid + ch], h);
     for (int k = 0; k < a.cb; ++k) h = fmaf(__shfl(xb, k), W1s[(a.ca + k) * a.hid + ch], h);
-    h = fmaxf(h, 0.f);
+    h = relu_keep_nan(h);
     float y = 0.f;
     for (int k = 0; k < a.hid; ++k) y = fmaf(__shfl(h, k), W2s[k * a.cout + cy], y);
     y += b;
@@ -594,17 +597,6 @@ hipError_t launch_sparse_build_plan(const int* coords, const SparsePlanLayout& l
   return hipGetLastError();
 }
 
-int sparse_conv_row_groups(int K, int cin, int cout, int nsplit, long long cap_out) {
-  // A kernel of more than 16 MiB is read once (one row group); a smaller one may be re-read per group, from the caches, to fill
-  // the device.  The grouping decides only which workgroup computes a row, never a result.
-  if ((long long)K * cin * cout * 4 > (16LL << 20)) return 1;
-  const long long wgs = (long long)nsplit * ((cout + kTN - 1) / kTN);
-  long long g = (512 + wgs - 1) / wgs;
-  const long long rows = (cap_out + 127) / 128;
-  if (g > rows) g = rows;
-  return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g));
-}
-
 hipError_t launch_sparse_conv(const SparseConvArgs& a, hipStream_t s) {
   dim3 grid(a.nsplit, blocks(a.cout, kTN), sparse_conv_row_groups(a.K, a.ca + a.cb, a.cout, a.nsplit, a.cap_out));
   k_sparse_conv<<<grid, kThreads, 0, s>>>(a);
@@ -613,26 +605,18 @@ hipError_t launch_sparse_conv(const SparseConvArgs& a, hipStream_t s) {
 }
 
 hipError_t launch_sparse_conv_narrow(const SparseNarrowArgs& a, hipStream_t s) {
-  // Workgroups walk the rows in strides; with W in LDS each one stages it once, so the grid stays near 3 per CU (3 x 43 KiB for
-  // FCGF's conv1 fit the 160 KiB of a CU).  The grid never changes a result.
-  const size_t wbytes = (size_t)a.K * a.cin * a.cout * sizeof(float);
-  const int rows_per_wg = (kThreads / 64) * (64 / (a.cout <= 16 ? 16 : (a.cout <= 32 ? 32 : 64)));
-  long long g = (a.cap_out + rows_per_wg - 1) / rows_per_wg;
-  if ((long long)wbytes <= kSparseNarrowLdsBytes) {
-    if (g > 768) g = 768;
-    k_sparse_conv_narrow<true><<<(int)g, kThreads, wbytes, s>>>(a);
-  } else {
-    if (g > 4096) g = 4096;
-    k_sparse_conv_narrow<false><<<(int)g, kThreads, 0, s>>>(a);
-  }
+  // the grid (sparse_narrow_grid) never changes a result: a row belongs to one lane group whatever the grid
+  const int g = sparse_narrow_grid(a.cap_out, a.K, a.cin, a.cout);
+  if (sparse_narrow_lds(a.K, a.cin, a.cout))
+    k_sparse_conv_narrow<true><<<g, kThreads, (size_t)a.K * a.cin * a.cout * sizeof(float), s>>>(a);
+  else
+    k_sparse_conv_narrow<false><<<g, kThreads, 0, s>>>(a);
   return hipGetLastError();
 }
 
 hipError_t launch_sparse_head_l2(const SparseHeadArgs& a, hipStream_t s) {
   const size_t lds = (size_t)((a.ca + a.cb) * a.hid + a.hid * a.cout) * sizeof(float);
-  long long g = (a.cap_out + kThreads / 64 - 1) / (kThreads / 64);
-  if (g > 1024) g = 1024;
-  k_sparse_head_l2<<<(int)g, kThreads, lds, s>>>(a);
+  k_sparse_head_l2<<<sparse_head_grid(a.cap_out), kThreads, lds, s>>>(a);
   return hipGetLastError();
 }
 

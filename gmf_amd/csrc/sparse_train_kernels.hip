@@ -26,7 +26,7 @@ namespace gmf {
 
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kSparseWgThreads;
 constexpr int kWP = 64;              // pairs per LDS tile
 constexpr int kWT = 64;              // dW tile: 64 input x 64 output channels
 constexpr int kChain = 16;           // pairs per fma chain
@@ -41,9 +41,7 @@ __global__ __launch_bounds__(1024) void k_wgrad_plan(const SparseWgradArgs a) {
   const bool ident = a.row_ptr == nullptr;
   if (threadIdx.x == 0) {
     const long long nnz = ident ? n : a.row_ptr[n];
-    const long long extra = a.nslots - a.K;
-    long long P = (nnz + extra - 1) / extra;       // sum over d of ceil(n_d / P) <= nnz / P + K <= nslots
-    s_P = (int)(P < kWgradMinChunk ? kWgradMinChunk : P);
+    s_P = sparse_wgrad_chunk(nnz, a.K, a.nslots);  // sparse_conv_plan.hpp: the chunks fit the nslots slots
   }
   __syncthreads();
   const int P = s_P;
@@ -187,7 +185,7 @@ __global__ __launch_bounds__(64) void k_sparse_wgrad_narrow(const SparseWgradArg
   const int end = a.off_start[d + 1];
   const int hi = lo + P < end ? lo + P : end;
   const int cin = a.ca, cout = a.cout;
-  const int L = cout <= 16 ? 16 : (cout <= 32 ? 32 : 64);
+  const int L = sparse_narrow_lanes(cout);
   const int G = 64 / L;
   const int lane = threadIdx.x, c = lane % L, g = lane / L;
   const int cc = c < cout ? c : cout - 1;          // lanes past cout compute a copy of the last channel and store nothing
@@ -445,8 +443,8 @@ __global__ __launch_bounds__(kThreads) void k_bnm_colsum(const float* __restrict
   const int c = blockIdx.x * 64 + lane, ch = blockIdx.y;
   long long n = *n_ptr;
   if (n > cap) n = cap;
-  const long long r0 = cap * ch / nch;
-  long long r1 = cap * (ch + 1) / nch;
+  const long long r0 = bnm_chunk_begin(cap, ch, nch);
+  long long r1 = bnm_chunk_begin(cap, ch + 1, nch);
   if (r1 > n) r1 = n;
   float a0 = 0.f, a1 = 0.f;
   if (c < C) {
@@ -522,7 +520,7 @@ __global__ __launch_bounds__(kThreads) void k_bnm_apply(const float* __restrict_
   if (r < *n_ptr) {
     v = fmaf((x[e] - mean[c]) * rstd[c], gamma[c], beta[c]);
     if (residual) v += residual[e];
-    if (relu) v = fmaxf(v, 0.f);
+    if (relu) v = v <= 0.f ? 0.f : v;              // keeps a NaN, as torch.relu does; fmaxf(v, 0) returns 0 for it (sparse_kernels.hip)
   }
   y[e] = v;
 }
@@ -596,11 +594,6 @@ hipError_t launch_rows_sum_by_dest(const float* rows, long long E, const long lo
                                    int C, float* out, hipStream_t s) {
   k_rows_sum_by_dest<<<blocks(N, kThreads / 64), kThreads, 0, s>>>(rows, E, order, row_start, N, C, out);
   return hipGetLastError();
-}
-
-int bnm_chunks(long long cap) {
-  const long long c = (cap + 255) / 256;
-  return (int)(c > 64 ? 64 : c);
 }
 
 hipError_t launch_bnm_forward(const float* x, const float* residual, const float* gamma, const float* beta, const int* n,

@@ -224,7 +224,7 @@ def sparse_conv(plan: SparsePlan, map_index, out_level: int, xa, W, xb=None, sca
 
     xa [M, ca] (and xb [M, cb]: the input is [xa | xb]) hold the input level's rows; W is MinkowskiEngine's `kernel`,
     [K, ca + cb, cout] (or [ca + cb, cout] when K = 1).  y = v * scale + shift (one fma; absent: 1 / 0), + residual [M, cout],
-    then ReLU if `relu`.  Returns out [M, cout]; only the first counts[out_level] rows are written.  `out` must not overlap any
+    then ReLU if `relu` (a NaN stays a NaN, as in torch.relu).  Returns out [M, cout]; only the first counts[out_level] rows are written.  `out` must not overlap any
     input (other workgroups would read rows it has already overwritten).  nsplit (1..K; 1 for the identity map) cuts the
     offsets into fixed slices that run on separate workgroups: it changes how the sum is grouped, so keep it fixed per layer
     for bitwise-equal results."""
@@ -477,7 +477,7 @@ def layer_nsplit(K: int, cin: int, cout: int) -> int:
     """Offset slices of one convolution of the network, a function of its shape alone (so every call groups its sums the same
     way).  A kernel of more than 16 MiB is read once per 64 pairs of an offset by one output-row group, and the slices give the
     parallelism: about 256 workgroups (slices x 64-channel blocks).  A smaller kernel runs in 9 slices and the device is filled
-    by output-row groups (csrc: sparse_conv_row_groups).  The workspace holds nsplit x M x cout floats."""
+    by output-row groups (csrc/sparse_conv_plan.hpp: sparse_conv_row_groups).  The workspace holds nsplit x M x cout floats."""
     if K == 1:
         return 1
     if K * cin * cout * 4 > (16 << 20):

@@ -12,6 +12,7 @@ from gmf_amd import sparse as SP
 from gmf_amd import synthetic
 
 import sparse_reference as R
+from test_sparse_forms_host import random_coords as _random_coords      # shared with tests/test_gpu_sparse_forms.py
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -22,17 +23,6 @@ EPS32 = float(np.finfo(np.float32).eps)
 
 def _g(x):
     return torch.as_tensor(x).to(DEV)
-
-
-def _random_coords(M, D, span, batches, seed):
-    """M unique rows (batch, c_1 .. c_D), coordinates in [-span, span), ragged batch sizes, shuffled."""
-    rng = np.random.default_rng(seed)
-    rows = set()
-    while len(rows) < M:
-        b = int(rng.choice(batches, p=np.linspace(1, 2, len(batches)) / np.linspace(1, 2, len(batches)).sum()))
-        rows.add((b,) + tuple(int(v) for v in rng.integers(-span, span, D)))
-    out = np.array(sorted(rows), dtype=np.int64)
-    return out[rng.permutation(M)]
 
 
 _SETS = {}

@@ -56,7 +56,7 @@ CONVS = [(i, m, lvl, conv) for i, (conv, _, m, lvl) in enumerate(SP.TRUNK)]
 
 
 def row_groups(K, cin, cout, nsplit, cap):
-    """csrc/sparse_kernels.hip: sparse_conv_row_groups (the output-row groups of one convolution)."""
+    """csrc/sparse_conv_plan.hpp: sparse_conv_row_groups (the output-row groups of one convolution)."""
     if K * cin * cout * 4 > (16 << 20):
         return 1
     wgs = nsplit * -(-cout // 64)
