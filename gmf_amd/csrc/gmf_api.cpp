@@ -1037,38 +1037,46 @@ int gmf_tsdf_allocate(gmf_handle* h, const void* depth, int depth_is_u16, const 
   return GMF_OK;
 }
 
-int gmf_tsdf_integrate(gmf_handle* h, const void* depth, int depth_is_u16, const double* poses_inv, const int* frame_offsets, int G,
-                       int F, int H, int W, double fx, double fy, double cx, double cy, double voxel_length, double sdf_trunc,
-                       double depth_scale, double depth_trunc, const int* unit_keys, const int* unit_offsets, const int* birth,
-                       int num_units, float* tsdf_out, float* weight_out, gmf_stream_t stream) {
+namespace {
+
+// gmf_tsdf_integrate (color, color_out null) and gmf_tsdf_integrate_color
+int tsdf_integrate(gmf_handle* h, const char* what, bool colored, const void* depth, int depth_is_u16, const unsigned char* color,
+                   const double* poses_inv, const int* frame_offsets, int G, int F, int H, int W, double fx, double fy, double cx,
+                   double cy, double voxel_length, double sdf_trunc, double depth_scale, double depth_trunc, const int* unit_keys,
+                   const int* unit_offsets, const int* birth, int num_units, float* tsdf_out, float* weight_out, float* color_out,
+                   gmf_stream_t stream) {
+  const std::string w(what);
   gmf::TsdfParams p;
-  if (int rc = check_tsdf_args(h, "tsdf_integrate", depth, poses_inv, frame_offsets, G, F, H, W, fx, fy, cx, cy, voxel_length,
-                               sdf_trunc, depth_scale, depth_trunc, p))
+  if (int rc = check_tsdf_args(h, what, depth, poses_inv, frame_offsets, G, F, H, W, fx, fy, cx, cy, voxel_length, sdf_trunc,
+                               depth_scale, depth_trunc, p))
     return rc;
-  GMF_REQUIRE(num_units >= 0 && num_units <= (1 << 22), GMF_ERR_BAD_ARG, "tsdf_integrate: num_units must be in 0..2^22");
+  GMF_REQUIRE(num_units >= 0 && num_units <= (1 << 22), GMF_ERR_BAD_ARG, w + ": num_units must be in 0..2^22");
   if (num_units == 0) return GMF_OK;
-  GMF_REQUIRE(F >= 1 && unit_keys && unit_offsets && birth && tsdf_out && weight_out, GMF_ERR_BAD_ARG,
-              "tsdf_integrate: null pointer, or units without frames");
+  GMF_REQUIRE(F >= 1 && unit_keys && unit_offsets && birth && tsdf_out && weight_out && (!colored || (color && color_out)),
+              GMF_ERR_BAD_ARG, w + ": null pointer, or units without frames");
   SetDevice sd(h, stream);
   gmf::TsdfIntegrateScratch ws;
   ArenaList bufs;
-  gmf::tsdf_integrate_scratch_list(p, ws, bufs);
+  gmf::tsdf_integrate_scratch_list(p, colored, ws, bufs);
   if (int rc = arena_carve(h, bufs)) return rc;
-  GMF_HIP(gmf::launch_tsdf_integrate(depth, depth_is_u16 != 0, poses_inv, frame_offsets, p, unit_keys, unit_offsets, birth, num_units,
-                                     ws, tsdf_out, weight_out, S(stream)));
+  GMF_HIP(gmf::launch_tsdf_integrate(depth, depth_is_u16 != 0, color, poses_inv, frame_offsets, p, unit_keys, unit_offsets, birth,
+                                     num_units, ws, tsdf_out, weight_out, color_out, S(stream)));
   return GMF_OK;
 }
 
-int gmf_tsdf_extract(gmf_handle* h, const int* unit_keys, const int* unit_offsets, int G, int num_units, const float* tsdf,
-                     const float* weight, double voxel_length, float* points_out, long long max_points, int* point_offsets_out,
-                     long long* num_points, gmf_stream_t stream) {
-  GMF_REQUIRE(h && unit_offsets && point_offsets_out, GMF_ERR_BAD_ARG, "tsdf_extract: null pointer");
-  GMF_REQUIRE(points_out || num_points, GMF_ERR_BAD_ARG, "tsdf_extract: without points_out the call counts into num_points");
-  GMF_REQUIRE(G >= 1 && G <= gmf::kTsdfMaxFragments, GMF_ERR_UNSUPPORTED_SHAPE, "tsdf_extract: G must be in 1..65535");
-  GMF_REQUIRE(num_units >= 0 && num_units <= (1 << 22), GMF_ERR_BAD_ARG, "tsdf_extract: num_units must be in 0..2^22");
-  GMF_REQUIRE(num_units == 0 || (unit_keys && tsdf && weight), GMF_ERR_BAD_ARG, "tsdf_extract: null pointer");
-  GMF_REQUIRE(voxel_length > 0 && std::isfinite(voxel_length), GMF_ERR_BAD_ARG, "tsdf_extract: voxel_length must be finite and > 0");
-  GMF_REQUIRE(max_points >= 0, GMF_ERR_BAD_ARG, "tsdf_extract: max_points must be >= 0");
+// gmf_tsdf_extract (color, colors_out null) and gmf_tsdf_extract_color
+int tsdf_extract(gmf_handle* h, const char* what, bool colored, const int* unit_keys, const int* unit_offsets, int G, int num_units,
+                 const float* tsdf, const float* weight, const float* color, double voxel_length, float* points_out, float* colors_out,
+                 long long max_points, int* point_offsets_out, long long* num_points, gmf_stream_t stream) {
+  const std::string w(what);
+  GMF_REQUIRE(h && unit_offsets && point_offsets_out, GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(points_out || num_points, GMF_ERR_BAD_ARG, w + ": without points_out the call counts into num_points");
+  GMF_REQUIRE(!colored || !points_out || colors_out, GMF_ERR_BAD_ARG, w + ": points_out and colors_out are written together");
+  GMF_REQUIRE(G >= 1 && G <= gmf::kTsdfMaxFragments, GMF_ERR_UNSUPPORTED_SHAPE, w + ": G must be in 1..65535");
+  GMF_REQUIRE(num_units >= 0 && num_units <= (1 << 22), GMF_ERR_BAD_ARG, w + ": num_units must be in 0..2^22");
+  GMF_REQUIRE(num_units == 0 || (unit_keys && tsdf && weight && (!colored || color)), GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(voxel_length > 0 && std::isfinite(voxel_length), GMF_ERR_BAD_ARG, w + ": voxel_length must be finite and > 0");
+  GMF_REQUIRE(max_points >= 0, GMF_ERR_BAD_ARG, w + ": max_points must be >= 0");
   SetDevice sd(h, stream);
   if (num_units == 0) {
     GMF_HIP(hipMemsetAsync(point_offsets_out, 0, ((size_t)G + 1) * 4, S(stream)));
@@ -1080,10 +1088,45 @@ int gmf_tsdf_extract(gmf_handle* h, const int* unit_keys, const int* unit_offset
   gmf::tsdf_extract_scratch_list(num_units, ws, bufs);
   if (int rc = arena_carve(h, bufs)) return rc;
   int host_count = 0;
-  GMF_HIP(gmf::launch_tsdf_extract(unit_keys, unit_offsets, G, num_units, tsdf, weight, voxel_length, ws, points_out, max_points,
-                                   point_offsets_out, &host_count, S(stream)));
+  GMF_HIP(gmf::launch_tsdf_extract(unit_keys, unit_offsets, G, num_units, tsdf, weight, color, voxel_length, ws, points_out, colors_out,
+                                   max_points, point_offsets_out, &host_count, S(stream)));
   if (!points_out) *num_points = host_count;
   return GMF_OK;
+}
+
+}  // namespace
+
+int gmf_tsdf_integrate(gmf_handle* h, const void* depth, int depth_is_u16, const double* poses_inv, const int* frame_offsets, int G,
+                       int F, int H, int W, double fx, double fy, double cx, double cy, double voxel_length, double sdf_trunc,
+                       double depth_scale, double depth_trunc, const int* unit_keys, const int* unit_offsets, const int* birth,
+                       int num_units, float* tsdf_out, float* weight_out, gmf_stream_t stream) {
+  return tsdf_integrate(h, "tsdf_integrate", false, depth, depth_is_u16, nullptr, poses_inv, frame_offsets, G, F, H, W, fx, fy, cx, cy,
+                        voxel_length, sdf_trunc, depth_scale, depth_trunc, unit_keys, unit_offsets, birth, num_units, tsdf_out,
+                        weight_out, nullptr, stream);
+}
+
+int gmf_tsdf_integrate_color(gmf_handle* h, const void* depth, int depth_is_u16, const unsigned char* color, const double* poses_inv,
+                             const int* frame_offsets, int G, int F, int H, int W, double fx, double fy, double cx, double cy,
+                             double voxel_length, double sdf_trunc, double depth_scale, double depth_trunc, const int* unit_keys,
+                             const int* unit_offsets, const int* birth, int num_units, float* tsdf_out, float* weight_out,
+                             float* color_out, gmf_stream_t stream) {
+  return tsdf_integrate(h, "tsdf_integrate_color", true, depth, depth_is_u16, color, poses_inv, frame_offsets, G, F, H, W, fx, fy, cx,
+                        cy, voxel_length, sdf_trunc, depth_scale, depth_trunc, unit_keys, unit_offsets, birth, num_units, tsdf_out,
+                        weight_out, color_out, stream);
+}
+
+int gmf_tsdf_extract(gmf_handle* h, const int* unit_keys, const int* unit_offsets, int G, int num_units, const float* tsdf,
+                     const float* weight, double voxel_length, float* points_out, long long max_points, int* point_offsets_out,
+                     long long* num_points, gmf_stream_t stream) {
+  return tsdf_extract(h, "tsdf_extract", false, unit_keys, unit_offsets, G, num_units, tsdf, weight, nullptr, voxel_length, points_out,
+                      nullptr, max_points, point_offsets_out, num_points, stream);
+}
+
+int gmf_tsdf_extract_color(gmf_handle* h, const int* unit_keys, const int* unit_offsets, int G, int num_units, const float* tsdf,
+                           const float* weight, const float* color, double voxel_length, float* points_out, float* colors_out,
+                           long long max_points, int* point_offsets_out, long long* num_points, gmf_stream_t stream) {
+  return tsdf_extract(h, "tsdf_extract_color", true, unit_keys, unit_offsets, G, num_units, tsdf, weight, color, voxel_length,
+                      points_out, colors_out, max_points, point_offsets_out, num_points, stream);
 }
 
 int gmf_rgbd_pyramids(gmf_handle* h, const void* color, int color_kind, const void* depth, int depth_is_u16, int F, int H, int W,

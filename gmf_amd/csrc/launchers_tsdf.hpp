@@ -1,5 +1,6 @@
 // Internal C++ launch entry points of the fragment builder (tsdf_kernels.hip): TSDF fusion of posed depth frames to a cloud.
-// Public C ABI: include/gmf_hip.h (gmf_tsdf_allocate, gmf_tsdf_integrate, gmf_tsdf_extract).
+// Public C ABI: include/gmf_hip.h (gmf_tsdf_allocate, gmf_tsdf_integrate, gmf_tsdf_extract, and the RGB8 forms
+// gmf_tsdf_integrate_color, gmf_tsdf_extract_color).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -51,23 +52,27 @@ hipError_t launch_tsdf_allocate(const void* depth, bool depth_u16, const double*
                                 int stride, int max_units, const TsdfAllocScratch& ws, int* unit_keys, int* birth, int* unit_offsets,
                                 int* host2, hipStream_t s);
 
-// The device buffers of one gmf_tsdf_integrate call.
+// The device buffers of one gmf_tsdf_integrate or gmf_tsdf_integrate_color call.
 struct TsdfIntegrateScratch {
   float* depth_m = nullptr;                   // [F,H,W] the depth value of every pixel (metres, 0: no measurement)
   float* pixel_scale = nullptr;               // [H,W] length of the pixel's ray at z = 1
   float* extrinsic = nullptr;                 // [F,12] the first three rows of each inverse pose as float32
+  unsigned* color_px = nullptr;               // [F,H,W] R | G << 8 | B << 16 of every pixel (the colour call only)
 };
-inline void tsdf_integrate_scratch_list(const TsdfParams& p, TsdfIntegrateScratch& ws, ArenaList& bufs) {
+inline void tsdf_integrate_scratch_list(const TsdfParams& p, bool color, TsdfIntegrateScratch& ws, ArenaList& bufs) {
   bufs.add(ws.depth_m, (size_t)p.F * p.H * p.W);
   bufs.add(ws.pixel_scale, (size_t)p.H * p.W);
   bufs.add(ws.extrinsic, (size_t)p.F * 12);
+  if (color) bufs.add(ws.color_px, (size_t)p.F * p.H * p.W);
 }
 
 // poses_inv [F,16] world-to-camera (fp64); unit_keys [U,3], unit_offsets [G+1], birth [U] as launch_tsdf_allocate wrote them.
-// Out: tsdf, weight [U,16,16,16] float32, every voxel written.  2 launches, no host synchronisation.
-hipError_t launch_tsdf_integrate(const void* depth, bool depth_u16, const double* poses_inv, const int* frame_offsets,
-                                 const TsdfParams& p, const int* unit_keys, const int* unit_offsets, const int* birth, int U,
-                                 const TsdfIntegrateScratch& ws, float* tsdf, float* weight, hipStream_t s);
+// Out: tsdf, weight [U,16,16,16] float32, every voxel written.  color [F,H,W,3] uint8 (null: the colour-free form, color_out is
+// not touched): color_out [U,16,16,16,3] float32 as well, every voxel written.  2 launches, no host synchronisation.
+hipError_t launch_tsdf_integrate(const void* depth, bool depth_u16, const unsigned char* color, const double* poses_inv,
+                                 const int* frame_offsets, const TsdfParams& p, const int* unit_keys, const int* unit_offsets,
+                                 const int* birth, int U, const TsdfIntegrateScratch& ws, float* tsdf, float* weight, float* color_out,
+                                 hipStream_t s);
 
 // The device buffers of one gmf_tsdf_extract call.
 struct TsdfExtractScratch {
@@ -83,9 +88,10 @@ void tsdf_extract_scratch_list(int U, TsdfExtractScratch& ws, ArenaList& bufs);
 
 // points null: counts only - point_offsets [G+1] is written and the vertex count goes to *host_count after synchronising the
 // stream.  Otherwise points [max_points,3] is written as well (a vertex past max_points is dropped) and nothing is read back
-// (host_count is not touched).
+// (host_count is not touched).  color [U,16,16,16,3] (null: no colours): the emitting call writes colors [max_points,3] beside
+// points, under the same guard.
 hipError_t launch_tsdf_extract(const int* unit_keys, const int* unit_offsets, int G, int U, const float* tsdf, const float* weight,
-                               double voxel_length, const TsdfExtractScratch& ws, float* points, long long max_points,
-                               int* point_offsets, int* host_count, hipStream_t s);
+                               const float* color, double voxel_length, const TsdfExtractScratch& ws, float* points, float* colors,
+                               long long max_points, int* point_offsets, int* host_count, hipStream_t s);
 
 }  // namespace gmf

@@ -9,6 +9,8 @@
 //                over the unit's whole frame loop and are written once
 //   extraction   one workgroup per unit: the unit's values and a one-voxel halo of its 26 neighbours in LDS (18^3), a count
 //                pass, a scan, an emit pass
+//   colour       (open3d's RGB8 volume; steps 3c and 4c, tests/tsdf_color_reference.py) compile-time forms of the integration
+//                and of the emit pass: 16 x 3 more accumulators per thread, and a vertex's colour from its edge's two voxels
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <math.h>
@@ -167,13 +169,19 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_units(const unsigned long lon
 
 // ---- integration --------------------------------------------------------------------------------------------------------------
 
-// one pass over the call's inputs: the depth value of every pixel, the ray length of every pixel, the extrinsics as float32
+// one pass over the call's inputs: the depth value of every pixel, the ray length of every pixel, the extrinsics as float32;
+// COLOR: also each pixel's three colour bytes as one word, R | G << 8 | B << 16, so that an update gathers one load and not three
+template <bool COLOR>
 __global__ __launch_bounds__(kThreads) void k_tsdf_prepare(const void* __restrict__ depth, bool u16, const double* __restrict__ poses_inv,
                                                            TsdfParams p, float* __restrict__ depth_m, float* __restrict__ pixel_scale,
-                                                           float* __restrict__ extrinsic) {
+                                                           float* __restrict__ extrinsic, const unsigned char* __restrict__ color,
+                                                           unsigned* __restrict__ color_px) {
   const size_t t = (size_t)blockIdx.x * kThreads + threadIdx.x;
   const size_t hw = (size_t)p.H * p.W;
-  if (t < hw * p.F) depth_m[t] = depth_value(depth, u16, t, p.depth_scale, p.depth_trunc);
+  if (t < hw * p.F) {
+    depth_m[t] = depth_value(depth, u16, t, p.depth_scale, p.depth_trunc);
+    if constexpr (COLOR) color_px[t] = (unsigned)color[3 * t] | ((unsigned)color[3 * t + 1] << 8) | ((unsigned)color[3 * t + 2] << 16);
+  }
   if (t < hw) {
     const double a = ((double)(int)(t % p.W) - p.cx) / p.fx, b = ((double)(int)(t / p.W) - p.cy) / p.fy;
     pixel_scale[t] = (float)sqrt((a * a + b * b) + 1.0);
@@ -189,13 +197,17 @@ struct TsdfFrustum {
   float bottom_z, bottom_len;  // bottom_z q_z - fy q_y >= 0
 };
 
+// COLOR: step 3c beside step 3 - the column's 16 x 3 colour accumulators stay in registers as tsdf and wt do; color_px [F,H,W] is
+// k_tsdf_prepare's packed word per pixel, read only where the voxel is updated; color_out [U,16,16,16,3]
+template <bool COLOR>
 __global__ __launch_bounds__(kThreads) void k_tsdf_integrate(const float* __restrict__ depth_m, const float* __restrict__ pixel_scale,
                                                              const float* __restrict__ extrinsic, const int* __restrict__ frame_off,
                                                              const int* __restrict__ unit_keys, const int* __restrict__ unit_off,
                                                              const int* __restrict__ birth, int G, int H, int W, float fx, float fy,
                                                              float cx, float cy, double voxel_length, float neg_trunc, float inv_trunc,
                                                              float radius, TsdfFrustum fr, float* __restrict__ tsdf_out,
-                                                             float* __restrict__ weight_out) {
+                                                             float* __restrict__ weight_out, const unsigned* __restrict__ color_px,
+                                                             float* __restrict__ color_out) {
   const int u = blockIdx.x;
   const int g = part_of(unit_off, G, u);
   const int k0 = unit_keys[3 * (size_t)u], k1 = unit_keys[3 * (size_t)u + 1], k2 = unit_keys[3 * (size_t)u + 2];
@@ -204,11 +216,13 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_integrate(const float* __rest
   const float wx = (float)(((double)(kTsdfRes * k0 + lx) + 0.5) * voxel_length);
   const float wy = (float)(((double)(kTsdfRes * k1 + ly) + 0.5) * voxel_length);
   float wz[kTsdfRes], tsdf[kTsdfRes], wt[kTsdfRes];
+  float col[COLOR ? 3 * kTsdfRes : 1];      // [z][channel], the order of color_out
 #pragma unroll
   for (int z = 0; z < kTsdfRes; ++z) {
     wz[z] = (float)(((double)(kTsdfRes * k2 + z) + 0.5) * voxel_length);
     tsdf[z] = 0.f;
     wt[z] = 0.f;
+    if constexpr (COLOR) col[3 * z] = col[3 * z + 1] = col[3 * z + 2] = 0.f;
   }
   // the unit's bounding sphere (centre in float32; `radius` has the slack for that and for the per-voxel rounding)
   const float sx = (float)((double)(kTsdfRes * k0 + 8) * voxel_length), sy = (float)((double)(kTsdfRes * k1 + 8) * voxel_length),
@@ -245,6 +259,12 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_integrate(const float* __rest
       if (sdf > neg_trunc) {
         const float t = fminf(1.f, sdf * inv_trunc);
         tsdf[z] = (tsdf[z] * wt[z] + t) / (wt[z] + 1.f);
+        if constexpr (COLOR) {
+          const unsigned c = color_px[hw * (size_t)(first + f) + pix];
+          col[3 * z] = (col[3 * z] * wt[z] + (float)(c & 255u)) / (wt[z] + 1.f);
+          col[3 * z + 1] = (col[3 * z + 1] * wt[z] + (float)((c >> 8) & 255u)) / (wt[z] + 1.f);
+          col[3 * z + 2] = (col[3 * z + 2] * wt[z] + (float)(c >> 16)) / (wt[z] + 1.f);
+        }
         wt[z] = wt[z] + 1.f;
       }
     }
@@ -255,6 +275,11 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_integrate(const float* __rest
   for (int q = 0; q < 4; ++q) {
     to[q] = make_float4(tsdf[4 * q], tsdf[4 * q + 1], tsdf[4 * q + 2], tsdf[4 * q + 3]);
     wo[q] = make_float4(wt[4 * q], wt[4 * q + 1], wt[4 * q + 2], wt[4 * q + 3]);
+  }
+  if constexpr (COLOR) {      // the thread's 48 floats are contiguous
+    float4* co = reinterpret_cast<float4*>(color_out + 3 * ((size_t)u * kTsdfUnitVoxels + threadIdx.x * kTsdfRes));
+#pragma unroll
+    for (int q = 0; q < 12; ++q) co[q] = make_float4(col[4 * q], col[4 * q + 1], col[4 * q + 2], col[4 * q + 3]);
   }
 }
 
@@ -308,13 +333,16 @@ GMF_DEVINL bool edge_vertex(const float* val, int lx, int ly, int z, int axis, f
 }
 
 // EMIT false: count[u] = the unit's vertices.  EMIT true: they are written from start[u] on, in (local index, axis) order.
-template <bool EMIT>
+// COLOR (with EMIT): step 4c - a vertex's colour beside its position, the two ends' colours read from the volume `color`
+// [U,16,16,16,3] in global memory for the crossing edges only (the far end's unit is in nbr[])
+template <bool EMIT, bool COLOR>
 __global__ __launch_bounds__(kThreads) void k_tsdf_extract(const int* __restrict__ unit_keys, const int* __restrict__ unit_off, int G,
                                                            const float* __restrict__ tsdf, const float* __restrict__ weight,
                                                            unsigned long long tmask, const unsigned long long* __restrict__ table,
                                                            const int* __restrict__ unit_of, double voxel_length,
                                                            int* __restrict__ count, const int* __restrict__ start,
-                                                           float* __restrict__ points, long long max_points) {
+                                                           float* __restrict__ points, long long max_points,
+                                                           const float* __restrict__ color, float* __restrict__ colors) {
   __shared__ float val[kHaloVoxels];          // tsdf of an observed voxel, NaN otherwise
   __shared__ int nbr[27];                     // the unit at offset (dx, dy, dz) in -1..1, or -1
   using Scan = hipcub::BlockScan<int, kThreads>;
@@ -368,6 +396,15 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_extract(const int* __restrict
         out[0] = (float)(axis == 0 ? px + move : px);
         out[1] = (float)(axis == 1 ? py + move : py);
         out[2] = (float)(axis == 2 ? pz + move : pz);
+        if constexpr (COLOR) {
+          const int bx = lx + (axis == 0), by = ly + (axis == 1), bz = z + (axis == 2);      // 0..16: 16 is the next unit's 0
+          const int n = nbr[((1 + (bx >> 4)) * 3 + (1 + (by >> 4))) * 3 + (1 + (bz >> 4))];
+          const float* ca = color + 3 * ((size_t)u * kTsdfUnitVoxels + ((lx * kTsdfRes + ly) * kTsdfRes + z));
+          const float* cb = color + 3 * ((size_t)max(n, 0) * kTsdfUnitVoxels + (((bx & 15) * kTsdfRes + (by & 15)) * kTsdfRes + (bz & 15)));
+          float* cout = colors + 3 * (size_t)at;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) cout[c] = (float)((((db * (double)ca[c]) + (da * (double)cb[c])) / (da + db)) / 255.0);
+        }
       }
       ++at;
     }
@@ -429,13 +466,18 @@ hipError_t launch_tsdf_allocate(const void* depth, bool depth_u16, const double*
   return e;
 }
 
-hipError_t launch_tsdf_integrate(const void* depth, bool depth_u16, const double* poses_inv, const int* frame_offsets,
-                                 const TsdfParams& p, const int* unit_keys, const int* unit_offsets, const int* birth, int U,
-                                 const TsdfIntegrateScratch& ws, float* tsdf, float* weight, hipStream_t s) {
+hipError_t launch_tsdf_integrate(const void* depth, bool depth_u16, const unsigned char* color, const double* poses_inv,
+                                 const int* frame_offsets, const TsdfParams& p, const int* unit_keys, const int* unit_offsets,
+                                 const int* birth, int U, const TsdfIntegrateScratch& ws, float* tsdf, float* weight, float* color_out,
+                                 hipStream_t s) {
   const size_t pixels = (size_t)p.F * p.H * p.W;
   const size_t work = std::max(pixels, std::max((size_t)p.H * p.W, (size_t)p.F * 12));      // the three tables share one launch
-  k_tsdf_prepare<<<blocks((long long)work, kThreads), kThreads, 0, s>>>(depth, depth_u16, poses_inv, p, ws.depth_m, ws.pixel_scale,
-                                                                       ws.extrinsic);
+  if (color)
+    k_tsdf_prepare<true><<<blocks((long long)work, kThreads), kThreads, 0, s>>>(depth, depth_u16, poses_inv, p, ws.depth_m,
+                                                                               ws.pixel_scale, ws.extrinsic, color, ws.color_px);
+  else
+    k_tsdf_prepare<false><<<blocks((long long)work, kThreads), kThreads, 0, s>>>(depth, depth_u16, poses_inv, p, ws.depth_m,
+                                                                                ws.pixel_scale, ws.extrinsic, nullptr, nullptr);
   const float fx = (float)p.fx, fy = (float)p.fy, cx = (float)p.cx, cy = (float)p.cy;
   const float trunc = (float)p.sdf_trunc;
   TsdfFrustum fr;
@@ -449,8 +491,14 @@ hipError_t launch_tsdf_integrate(const void* depth, bool depth_u16, const double
   fr.bottom_len = sqrtf(fy * fy + fr.bottom_z * fr.bottom_z);
   // half the unit's diagonal is 0.866 unit lengths; the rest is slack for the rounding of the test itself
   const float radius = (float)(kTsdfRes * p.voxel_length);
-  k_tsdf_integrate<<<U, kThreads, 0, s>>>(ws.depth_m, ws.pixel_scale, ws.extrinsic, frame_offsets, unit_keys, unit_offsets, birth, p.G,
-                                          p.H, p.W, fx, fy, cx, cy, p.voxel_length, -trunc, 1.0f / trunc, radius, fr, tsdf, weight);
+  if (color)
+    k_tsdf_integrate<true><<<U, kThreads, 0, s>>>(ws.depth_m, ws.pixel_scale, ws.extrinsic, frame_offsets, unit_keys, unit_offsets, birth,
+                                                  p.G, p.H, p.W, fx, fy, cx, cy, p.voxel_length, -trunc, 1.0f / trunc, radius, fr, tsdf,
+                                                  weight, ws.color_px, color_out);
+  else
+    k_tsdf_integrate<false><<<U, kThreads, 0, s>>>(ws.depth_m, ws.pixel_scale, ws.extrinsic, frame_offsets, unit_keys, unit_offsets, birth,
+                                                   p.G, p.H, p.W, fx, fy, cx, cy, p.voxel_length, -trunc, 1.0f / trunc, radius, fr, tsdf,
+                                                   weight, nullptr, nullptr);
   return hipGetLastError();
 }
 
@@ -466,22 +514,26 @@ void tsdf_extract_scratch_list(int U, TsdfExtractScratch& ws, ArenaList& bufs) {
 }
 
 hipError_t launch_tsdf_extract(const int* unit_keys, const int* unit_offsets, int G, int U, const float* tsdf, const float* weight,
-                               double voxel_length, const TsdfExtractScratch& ws, float* points, long long max_points,
-                               int* point_offsets, int* host_count, hipStream_t s) {
+                               const float* color, double voxel_length, const TsdfExtractScratch& ws, float* points, float* colors,
+                               long long max_points, int* point_offsets, int* host_count, hipStream_t s) {
   const unsigned long long tmask = (unsigned long long)ws.T - 1;
   hipError_t e = hipMemsetAsync(ws.table, 0xFF, ws.T * 8, s);
   if (e == hipSuccess) e = hipMemsetAsync(ws.count + U, 0, 4, s);
   if (e != hipSuccess) return e;
   k_tsdf_index<<<blocks(U, kThreads), kThreads, 0, s>>>(unit_keys, unit_offsets, G, U, tmask, ws.table, ws.unit_of);
-  k_tsdf_extract<false><<<U, kThreads, 0, s>>>(unit_keys, unit_offsets, G, tsdf, weight, tmask, ws.table, ws.unit_of, voxel_length,
-                                               ws.count, nullptr, nullptr, 0);
+  k_tsdf_extract<false, false><<<U, kThreads, 0, s>>>(unit_keys, unit_offsets, G, tsdf, weight, tmask, ws.table, ws.unit_of,
+                                                      voxel_length, ws.count, nullptr, nullptr, 0, nullptr, nullptr);
   size_t tb = ws.tmp_bytes;
   e = hipcub::DeviceScan::ExclusiveSum(ws.tmp, tb, ws.count, ws.start, U + 1, s);
   if (e != hipSuccess) return e;
   k_tsdf_point_offsets<<<blocks(G + 1, 64), 64, 0, s>>>(unit_offsets, G, ws.start, point_offsets);
   if (points) {
-    k_tsdf_extract<true><<<U, kThreads, 0, s>>>(unit_keys, unit_offsets, G, tsdf, weight, tmask, ws.table, ws.unit_of, voxel_length,
-                                                nullptr, ws.start, points, max_points);
+    if (color)
+      k_tsdf_extract<true, true><<<U, kThreads, 0, s>>>(unit_keys, unit_offsets, G, tsdf, weight, tmask, ws.table, ws.unit_of,
+                                                        voxel_length, nullptr, ws.start, points, max_points, color, colors);
+    else
+      k_tsdf_extract<true, false><<<U, kThreads, 0, s>>>(unit_keys, unit_offsets, G, tsdf, weight, tmask, ws.table, ws.unit_of,
+                                                         voxel_length, nullptr, ws.start, points, max_points, nullptr, nullptr);
     return hipGetLastError();
   }
   e = hipGetLastError();

@@ -1,11 +1,13 @@
 """Fragments on the device: TSDF fusion of posed depth frames to a cloud, as the reference makes them
 (GMF_PointDSC/multiway/make_fragments.py:112-140 and GMF_DeepGlobalRegistration/*/util/integration.py:44-71: open3d's
 ScalableTSDFVolume, integrate() per frame, extract_triangle_mesh(), of which make_fragments.py keeps the vertices).  Kernels:
-csrc/tsdf_kernels.hip; C ABI: gmf_tsdf_allocate, gmf_tsdf_integrate, gmf_tsdf_extract.
+csrc/tsdf_kernels.hip; C ABI: gmf_tsdf_allocate, gmf_tsdf_integrate, gmf_tsdf_extract.  tsdf_fragments_colored is the RGB8 volume
+of the same scripts (color_type = RGB8, pcd.colors = mesh.vertex_colors): the same vertices and a colour for each, through
+gmf_tsdf_integrate_color and gmf_tsdf_extract_color.
 
-The contract is DESIGN.md section 4o, restated in numpy by tests/tsdf_reference.py; where it knowingly differs from open3d is
-listed there.  Colours, triangles, normals, extract_point_cloud and file reading are not here; the RGB-D odometry that gives the
-poses is gmf_amd/rgbd.py."""
+The contract is DESIGN.md section 4o, restated in numpy by tests/tsdf_reference.py and, for the colours (steps 3c and 4c),
+tests/tsdf_color_reference.py; where it knowingly differs from open3d is listed there.  Triangles, vertex normals,
+extract_point_cloud, grey volumes and file reading are not here; the RGB-D odometry that gives the poses is gmf_amd/rgbd.py."""
 from __future__ import annotations
 
 import ctypes as C
@@ -32,15 +34,20 @@ def _positive(what, name, v, allow_inf=False):
     return f
 
 
-def _nothing(points_off, return_volume):
+def _nothing(points_off, return_volume, colored=False):
     """The result of a call whose frames touch no unit."""
     dev = points_off.device
     pts = torch.zeros((0, 3), device=dev, dtype=torch.float32)
-    if not return_volume:
-        return pts, points_off
-    return (pts, points_off, torch.zeros((0, 3), device=dev, dtype=torch.int32), torch.zeros_like(points_off),
-            torch.zeros(0, device=dev, dtype=torch.int32), torch.zeros((0, 16, 16, 16), device=dev),
-            torch.zeros((0, 16, 16, 16), device=dev))
+    out = (pts, points_off)
+    if return_volume:
+        out += (torch.zeros((0, 3), device=dev, dtype=torch.int32), torch.zeros_like(points_off),
+                torch.zeros(0, device=dev, dtype=torch.int32), torch.zeros((0, 16, 16, 16), device=dev),
+                torch.zeros((0, 16, 16, 16), device=dev))
+    if colored:
+        out += (torch.zeros((0, 3), device=dev, dtype=torch.float32),)
+        if return_volume:
+            out += (torch.zeros((0, 16, 16, 16, 3), device=dev),)
+    return out
 
 
 def tsdf_fragments(depth, poses, intrinsic, frame_offsets=None, voxel_length=0.008, sdf_trunc=0.04, depth_scale=1000.0,
@@ -65,7 +72,31 @@ def tsdf_fragments(depth, poses, intrinsic, frame_offsets=None, voxel_length=0.0
     A function of the inputs alone: the same bits on every run, and a fragment has the same bits alone and in any batch.
     Two host synchronisations per call (the unit count, the vertex count).  Raises when the frames touch more than max_units
     units (raise max_units) or a unit index leaves +-32767 (raise voxel_length)."""
-    what = "tsdf_fragments"
+    return _fragments("tsdf_fragments", None, depth, poses, intrinsic, frame_offsets, voxel_length, sdf_trunc, depth_scale, depth_trunc,
+                      depth_sampling_stride, max_units, return_volume)
+
+
+def tsdf_fragments_colored(color, depth, poses, intrinsic, frame_offsets=None, voxel_length=0.008, sdf_trunc=0.04, depth_scale=1000.0,
+                           depth_trunc=4.5, depth_sampling_stride=4, max_units=1 << 18, return_volume=False):
+    """tsdf_fragments with open3d's RGB8 volume: the same vertices, with the same bits, and a colour for each.
+
+    color [F,H,W,3] uint8 on depth's device, channels R, G, B, the frames of `depth`; every other argument as in tsdf_fragments.
+      integration: a voxel's colour starts at (0, 0, 0) and changes exactly when its tsdf does, from the same pixel:
+      c = (c w + color[f,v,u]) / (w + 1) in fp32 with w the weight before the update; a pixel without a depth measurement is never
+      read, and a voxel of weight 0 keeps colour 0;
+      extraction: a vertex on the edge from voxel a to voxel b, ta = |tsdf_a|, tb = |tsdf_b|, has colour
+      ((tb c_a + ta c_b) / (ta + tb)) / 255 in fp64, rounded once.
+    Returns what tsdf_fragments returns, then colors [M,3] float32 in 0..1 (row i is the colour of points[i]); with return_volume
+    also color_volume [U,16,16,16,3] float32 in 0..255 after that.  The same bits on every run, alone and in any batch; two host
+    synchronisations per call."""
+    return _fragments("tsdf_fragments_colored", color, depth, poses, intrinsic, frame_offsets, voxel_length, sdf_trunc, depth_scale,
+                      depth_trunc, depth_sampling_stride, max_units, return_volume, colored=True)
+
+
+def _fragments(what, color, depth, poses, intrinsic, frame_offsets, voxel_length, sdf_trunc, depth_scale, depth_trunc,
+               depth_sampling_stride, max_units, return_volume, colored=False):
+    """tsdf_fragments (colored False: `color` is not looked at) and tsdf_fragments_colored: the argument checks, raised under the
+    name `what`, and the calls."""
     if not isinstance(depth, torch.Tensor):
         _fail(what, "`depth` must be a torch tensor")
     if depth.dtype not in (torch.uint16, torch.float32):
@@ -75,6 +106,15 @@ def tsdf_fragments(depth, poses, intrinsic, frame_offsets=None, voxel_length=0.0
     F, H, W = depth.shape
     if F * H * W >= 2 ** 31:
         _fail(what, f"`depth` must hold fewer than 2^31 pixels (got {F * H * W})")
+    if colored:
+        if not isinstance(color, torch.Tensor):
+            _fail(what, "`color` must be a torch tensor")
+        if color.dtype != torch.uint8:
+            _fail(what, f"`color` must be uint8 (got {color.dtype})")
+        if tuple(color.shape) != (F, H, W, 3):
+            _fail(what, f"`color` must be [F,H,W,3] (R, G, B) with depth's F, H, W = {F}, {H}, {W} (got {tuple(color.shape)})")
+        if color.device != depth.device:
+            _fail(what, f"`color` must live on depth's device (got {color.device} and {depth.device})")
     if not isinstance(poses, torch.Tensor):
         _fail(what, "`poses` must be a torch tensor")
     if poses.dtype != torch.float64:
@@ -129,7 +169,7 @@ def tsdf_fragments(depth, poses, intrinsic, frame_offsets=None, voxel_length=0.0
 
     points_off = torch.zeros(G + 1, device=dev, dtype=torch.int32)
     if F == 0:
-        return _nothing(points_off, return_volume)
+        return _nothing(points_off, return_volume, colored)
 
     D = depth.contiguous()
     u16 = 1 if depth.dtype == torch.uint16 else 0
@@ -148,15 +188,27 @@ def tsdf_fragments(depth, poses, intrinsic, frame_offsets=None, voxel_length=0.0
     U = int(n.value)
     keys, birth = keys[:U].clone(), birth[:U].clone()
     if U == 0:
-        return _nothing(points_off, return_volume)
+        return _nothing(points_off, return_volume, colored)
     tsdf = torch.empty((U, 16, 16, 16), device=dev, dtype=torch.float32)
     weight = torch.empty((U, 16, 16, 16), device=dev, dtype=torch.float32)
-    h.call("gmf_tsdf_integrate", *shared, both[1].data_ptr(), dev_off.data_ptr(), *camera, keys.data_ptr(), unit_off.data_ptr(),
-           birth.data_ptr(), U, tsdf.data_ptr(), weight.data_ptr(), st)
-    volume = (keys.data_ptr(), unit_off.data_ptr(), G, U, tsdf.data_ptr(), weight.data_ptr(), vl)
-    h.call("gmf_tsdf_extract", *volume, None, 0, points_off.data_ptr(), C.byref(n), st)
+    units = (keys.data_ptr(), unit_off.data_ptr(), birth.data_ptr(), U, tsdf.data_ptr(), weight.data_ptr())
+    volume = (keys.data_ptr(), unit_off.data_ptr(), G, U, tsdf.data_ptr(), weight.data_ptr())
+    if not colored:
+        h.call("gmf_tsdf_integrate", *shared, both[1].data_ptr(), dev_off.data_ptr(), *camera, *units, st)
+        h.call("gmf_tsdf_extract", *volume, vl, None, 0, points_off.data_ptr(), C.byref(n), st)
+        M = int(n.value)
+        pts = torch.empty((M, 3), device=dev, dtype=torch.float32)
+        if M:
+            h.call("gmf_tsdf_extract", *volume, vl, pts.data_ptr(), M, points_off.data_ptr(), None, st)
+        return (pts, points_off) + ((keys, unit_off, birth, tsdf, weight) if return_volume else ())
+    Cf = color.contiguous()
+    cvol = torch.empty((U, 16, 16, 16, 3), device=dev, dtype=torch.float32)
+    h.call("gmf_tsdf_integrate_color", *shared, Cf.data_ptr(), both[1].data_ptr(), dev_off.data_ptr(), *camera, *units, cvol.data_ptr(), st)
+    h.call("gmf_tsdf_extract_color", *volume, cvol.data_ptr(), vl, None, None, 0, points_off.data_ptr(), C.byref(n), st)
     M = int(n.value)
     pts = torch.empty((M, 3), device=dev, dtype=torch.float32)
+    cols = torch.empty((M, 3), device=dev, dtype=torch.float32)
     if M:
-        h.call("gmf_tsdf_extract", *volume, pts.data_ptr(), M, points_off.data_ptr(), None, st)
-    return (pts, points_off) + ((keys, unit_off, birth, tsdf, weight) if return_volume else ())
+        h.call("gmf_tsdf_extract_color", *volume, cvol.data_ptr(), vl, pts.data_ptr(), cols.data_ptr(), M, points_off.data_ptr(), None, st)
+    return (pts, points_off) + ((keys, unit_off, birth, tsdf, weight) if return_volume else ()) + (cols,) + (
+        (cvol,) if return_volume else ())

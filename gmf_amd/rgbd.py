@@ -5,7 +5,8 @@ csrc/rgbd_kernels.hip; C ABI: gmf_rgbd_pyramids, gmf_rgbd_correspondences, gmf_r
 
 The contract is DESIGN.md section 4p, restated in numpy by tests/rgbd_reference.py; it follows open3d 0.9 as remembered, and where
 it knowingly differs is listed there.  The colour-term Jacobian, the 5-point initialisation of non-adjacent key frames (`odo_init`
-is the hook for it), file reading and colours in the TSDF are not here."""
+is the hook for it) and file reading are not here; rgbd_fragments(colors=True) fuses the colour frames as well
+(fragments.py: tsdf_fragments_colored)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,7 +15,7 @@ import numpy as np
 import torch
 
 from ._util import handle_and_stream
-from .fragments import _positive, tsdf_fragments
+from .fragments import _positive, tsdf_fragments, tsdf_fragments_colored
 from .multiway import global_optimization, odometry_poses
 from .spectral import _fail
 
@@ -259,16 +260,24 @@ def rgbd_fragments(color, depth, intrinsic, frame_offsets=None, max_depth_diff=0
     fragment (rgbd_odometry with max_depth_diff, min_depth, max_depth), the odometry chain per fragment (odometry_poses), the
     pose-graph optimisation (global_optimization with reference_node 0, edge_prune_threshold 0.25, the consecutive edges certain;
     optimize=False skips it) and the TSDF fusion with the resulting camera-to-world poses (tsdf_fragments; tsdf_args are its
-    keywords, depth_scale and depth_trunc also go to the pyramids).
+    keywords, depth_scale and depth_trunc also go to the pyramids; colors=True fuses the colour frames as well, through
+    tsdf_fragments_colored, and needs [F,H,W,3] uint8 colour: a grey frame has no R, G, B to fuse).
 
     color, depth, intrinsic: as in rgbd_pyramids / tsdf_fragments; frame_offsets: G + 1 ints (None: one fragment).
-    Returns what tsdf_fragments returns, then poses [F,4,4] float64 (camera to the fragment's first camera) and success [F - G']
-    bool over the consecutive pairs in order (G' fragments that hold a frame), on the device.  A fragment with a failed pair
+    Returns what tsdf_fragments (colors=True: tsdf_fragments_colored) returns, then poses [F,4,4] float64 (camera to the
+    fragment's first camera) and success [F - G'] bool over the consecutive pairs in order (G' fragments that hold a frame), on the device.  A fragment with a failed pair
     raises and names the pair (one host synchronisation, besides tsdf_fragments' own)."""
     what = "rgbd_fragments"
-    unknown = set(tsdf_args) - {"voxel_length", "sdf_trunc", "depth_scale", "depth_trunc", "depth_sampling_stride", "max_units", "return_volume"}
+    unknown = set(tsdf_args) - {"voxel_length", "sdf_trunc", "depth_scale", "depth_trunc", "depth_sampling_stride", "max_units", "return_volume", "colors"}
     if unknown:
         _fail(what, f"unknown argument {sorted(unknown)[0]!r}")
+    tsdf_args = dict(tsdf_args)
+    colors = tsdf_args.pop("colors", False)
+    if not isinstance(colors, (bool, np.bool_)):
+        _fail(what, f"colors must be True or False (got {colors!r})")
+    if colors and not (isinstance(color, torch.Tensor) and color.dtype == torch.uint8 and color.dim() == 4 and color.shape[-1] == 3):
+        got = f"{tuple(color.shape)} {color.dtype}" if isinstance(color, torch.Tensor) else type(color).__name__
+        _fail(what, f"colors=True needs `color` as [F,H,W,3] uint8: a grey frame has no R, G, B to fuse (got {got})")
     if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
         _fail(what, "`depth` must be a [F,H,W] torch tensor")
     F = depth.shape[0]
@@ -295,7 +304,6 @@ def rgbd_fragments(color, depth, intrinsic, frame_offsets=None, max_depth_diff=0
     tgt = [i + 1 for i in src]
     pyramid_args = {k: tsdf_args[k] for k in ("depth_scale",) if k in tsdf_args}
     pyramid_args["depth_trunc"] = tsdf_args.get("depth_trunc", 3.0)
-    tsdf_args = dict(tsdf_args)
     tsdf_args.setdefault("depth_trunc", 3.0)
     try:
         if F == 0:
@@ -332,10 +340,13 @@ def rgbd_fragments(color, depth, intrinsic, frame_offsets=None, max_depth_diff=0
                                              edge_prune_threshold=0.25, preference_loop_closure=p, reference_node=0)[0]
                 poses = poses.clone()
                 poses[rows] = better
-        out = tsdf_fragments(depth, poses, K, frame_offsets=off, **tsdf_args)
+        if colors:
+            out = tsdf_fragments_colored(color, depth, poses, K, frame_offsets=off, **tsdf_args)
+        else:
+            out = tsdf_fragments(depth, poses, K, frame_offsets=off, **tsdf_args)
     except RuntimeError as err:
         msg = str(err)
-        for inner in ("rgbd_odometry", "rgbd_pyramids", "tsdf_fragments", "global_optimization"):
+        for inner in ("rgbd_odometry", "rgbd_pyramids", "tsdf_fragments_colored", "tsdf_fragments", "global_optimization"):
             msg = msg.replace(f"gmf_amd.{inner}", f"gmf_amd.{what}", 1)
         raise RuntimeError(msg) from None
     return tuple(out) + (poses, success)

@@ -45,7 +45,7 @@ enum {
 #define GMF_ABI_VERSION 5   /* 5: gmf_encoder_weights gained `pv_guard` (a caller that fills the struct itself must be rebuilt; one that uses
                              * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  gmf_icp_point_to_point_ex and
                              * gmf_ransac_feature_matching, then gmf_spectral_matching, then gmf_max_clique and gmf_pmc_graph, then gmf_tsdf_allocate, gmf_tsdf_integrate and gmf_tsdf_extract, then gmf_rgbd_pyramids, gmf_rgbd_correspondences and
-                             * gmf_rgbd_odometry joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
+                             * gmf_rgbd_odometry, then gmf_tsdf_integrate_color and gmf_tsdf_extract_color joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
                              * pose head / pick_seeds take any N */
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
@@ -751,6 +751,28 @@ int gmf_tsdf_integrate(gmf_handle* h, const void* depth, int depth_is_u16, const
 int gmf_tsdf_extract(gmf_handle* h, const int* unit_keys, const int* unit_offsets, int G, int num_units, const float* tsdf,
                      const float* weight, double voxel_length, float* points_out, long long max_points, int* point_offsets_out,
                      long long* num_points, gmf_stream_t stream);
+
+/* The RGB8 forms (open3d's color_type = RGB8; tests/tsdf_color_reference.py restates them)
+ * [joined under ABI 5: added entry points].  They compute what the two entries above compute, with the same bits, and colours
+ * beside it.
+ *
+ * gmf_tsdf_integrate_color: color [F,H,W,3] uint8 on the device, channels R, G, B, the frames of `depth`.  A voxel's colour starts
+ * at (0, 0, 0) and changes exactly when its tsdf does, from the same pixel: c_k = (c_k w + float(color_k)) / (w + 1) in fp32 with w
+ * the weight before the update; the colour of a pixel without a depth measurement is never read.  color_out [num_units,16,16,16,3]
+ * float32 in 0..255, every voxel written (exactly 0 where the weight is 0).  Workspace: 4 (2 F + 1) H W bytes. */
+int gmf_tsdf_integrate_color(gmf_handle* h, const void* depth, int depth_is_u16, const unsigned char* color, const double* poses_inv,
+                             const int* frame_offsets, int G, int F, int H, int W, double fx, double fy, double cx, double cy,
+                             double voxel_length, double sdf_trunc, double depth_scale, double depth_trunc, const int* unit_keys,
+                             const int* unit_offsets, const int* birth, int num_units, float* tsdf_out, float* weight_out,
+                             float* color_out, gmf_stream_t stream);
+
+/* gmf_tsdf_extract_color: color [num_units,16,16,16,3] as gmf_tsdf_integrate_color wrote it.  points_out NULL: the counting call
+ * of gmf_tsdf_extract; neither output is touched.  Otherwise points_out and colors_out [max_points,3] float32 are both written,
+ * under the same max_points guard: row i of colors_out is the colour of vertex i, in 0..1 - with ta = |tsdf_a|, tb = |tsdf_b|,
+ * ((tb c_a + ta c_b) / (ta + tb)) / 255 in fp64, rounded once (the vertex lies ta / (ta + tb) of the way from a to b). */
+int gmf_tsdf_extract_color(gmf_handle* h, const int* unit_keys, const int* unit_offsets, int G, int num_units, const float* tsdf,
+                           const float* weight, const float* color, double voxel_length, float* points_out, float* colors_out,
+                           long long max_points, int* point_offsets_out, long long* num_points, gmf_stream_t stream);
 
 /* ---- RGB-D odometry (open3d 0.9's compute_rgbd_odometry with the hybrid Jacobian, as make_fragments.py calls it) -------------- */
 

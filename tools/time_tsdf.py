@@ -1,17 +1,20 @@
-"""Times the fragment builder (gmf_amd/fragments.py: tsdf_fragments), stage by stage.
+"""Times the fragment builder (gmf_amd/fragments.py: tsdf_fragments, and with --color tsdf_fragments_colored), stage by stage.
 
   scene    synthetic: the inside of a 6 x 3 x 7 m room with a sphere in it, ray-cast analytically to 50 frames of 480 x 640 uint16
            millimetres (fx = fy = 525, cx = 319.5, cy = 239.5) from a camera that turns 0.02 rad and moves 1 cm per frame
   shapes   one fragment per call, then 8 (the same frames under 8 fragment numbers), voxel_length 0.008, sdf_trunc 0.04, stride 4
   stages   gmf_tsdf_allocate, gmf_tsdf_integrate, gmf_tsdf_extract (the counting call and the emitting call), as
            tsdf_fragments issues them; and the whole tsdf_fragments call
+  --color  also gmf_tsdf_integrate_color, the emitting gmf_tsdf_extract_color and the whole tsdf_fragments_colored call, each
+           beside the colour-free time of the same run; the colour frames are a pattern of the pixel and the frame (the time does
+           not depend on the values); the colour form moves 12 B per voxel and 3 + 4 B per pixel on top
   figures  units, vertices, voxel updates (the sum of the weights) and unit-frame visits; for the integration call the updates per
            second, and bytes per second over what it must move: the volume written once (8 B per voxel) and every depth frame
            converted once (2 B read, 4 B written) - the gathered reads of depth it does on top are served by the caches
 
 Device events around each call after warm-up; median, min and max over repeats, in us.  There is no open3d to compare the times
 with: they are recorded, not gated.
-Usage: python tools/time_tsdf.py [--repeats 5] [--warmup 1] [--fragments 1,8] [--frames 50] [--out FILE]"""
+Usage: python tools/time_tsdf.py [--repeats 5] [--warmup 1] [--fragments 1,8] [--frames 50] [--color] [--out FILE]"""
 import argparse
 import ctypes as C
 import math
@@ -78,6 +81,7 @@ def main():
     ap.add_argument("--fragments", default="1,8")
     ap.add_argument("--frames", type=int, default=50)
     ap.add_argument("--max-units", type=int, default=1 << 18)
+    ap.add_argument("--color", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -95,6 +99,9 @@ def main():
     F1 = args.frames
     poses1 = np.stack([pose(k) for k in range(F1)])
     depth1 = torch.stack([raycast(P, dev) for P in poses1])
+    if args.color:
+        i, j, k = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), torch.arange(F1, device=dev), indexing="ij")
+        color1 = torch.stack([(3 * j + k) % 256, (5 * i + 2 * k) % 256, (i + j + 7 * k) % 256], -1).permute(2, 0, 1, 3).to(torch.uint8)
     for G in (int(x) for x in args.fragments.split(",")):
         depth = depth1.view(torch.int16).repeat(G, 1, 1).view(torch.uint16)
         poses = np.tile(poses1, (G, 1, 1))
@@ -150,6 +157,33 @@ def main():
         say(f"  extract (count) {fmt(t_count)}")
         say(f"  extract (emit)  {fmt(t_emit)}")
         say(f"  tsdf_fragments  {fmt(t_all)}")
+        if args.color:
+            color = color1.repeat(G, 1, 1, 1).contiguous()
+            cvol = torch.empty((U, 16, 16, 16, 3), device=dev)
+            tsdf_c, weight_c = torch.empty_like(tsdf), torch.empty_like(weight)
+
+            def integrate_color():
+                h.call("gmf_tsdf_integrate_color", depth.data_ptr(), 1, color.data_ptr(), both[1].data_ptr(), off.data_ptr(), *camera,
+                       keys.data_ptr(), uoff.data_ptr(), birth.data_ptr(), U, tsdf_c.data_ptr(), weight_c.data_ptr(), cvol.data_ptr(), st)
+
+            t_int_c, _ = timed(integrate_color, args.warmup, args.repeats)
+            assert torch.equal(tsdf_c, tsdf) and torch.equal(weight_c, weight)
+            pts_c, cols = torch.empty_like(pts), torch.empty_like(pts)
+            t_emit_c, _ = timed(lambda: h.call("gmf_tsdf_extract_color", keys.data_ptr(), uoff.data_ptr(), G, U, tsdf.data_ptr(),
+                                               weight.data_ptr(), cvol.data_ptr(), VOXEL, pts_c.data_ptr(), cols.data_ptr(), M,
+                                               poff.data_ptr(), None, st), args.warmup, args.repeats)
+            assert torch.equal(pts_c, pts)
+            t_all_c, out_c = timed(lambda: gmf_amd.tsdf_fragments_colored(color, depth, torch.from_numpy(poses), K, frame_offsets=off_h,
+                                                                          voxel_length=VOXEL, sdf_trunc=TRUNC,
+                                                                          depth_sampling_stride=STRIDE, max_units=cap),
+                                   args.warmup, args.repeats)
+            assert torch.equal(out_c[0], pts) and torch.equal(out_c[2], cols)
+            moved_c = moved + U * 4096 * 12 + F * H * W * 7
+            tc = statistics.median(t_int_c) * 1e-6
+            say(f"  integrate_color        {fmt(t_int_c)} against {fmt(t_int)} | {updates / tc / 1e9:.2f} G updates/s, "
+                f"{moved_c / tc / 1e9:.1f} GB/s over {moved_c / 1e6:.1f} MB")
+            say(f"  extract_color (emit)   {fmt(t_emit_c)} against {fmt(t_emit)}")
+            say(f"  tsdf_fragments_colored {fmt(t_all_c)} against {fmt(t_all)}")
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
