@@ -8,12 +8,11 @@ share one chain of launches, nothing is read back and the call can be captured i
 INTEGRATION.md, "Maximum-clique baseline"."""
 from __future__ import annotations
 
-import numpy as np
 import torch
 
+from ._args import (check_offsets, check_rows, device_offsets, fail, int_in_range, positive_finite, require_device, same_device,
+                    uniform_offsets)
 from ._util import handle_and_stream
-from .registration import _device_offsets
-from .spectral import _check_offsets, _check_rows, _fail
 
 MAX_ROWS = 8192                     # rows of one pair, at most (kPmcMaxN)
 STEP_SLACK = 256                    # `steps` can pass `max_steps` by this much: one search wave per count (kPmcWaves)
@@ -22,11 +21,9 @@ _METRICS = {"squared": 0, "length": 1}
 
 
 def _check_common(what, inlier_threshold, metric):
-    tau = float(inlier_threshold)
-    if not (tau > 0 and np.isfinite(tau)):
-        _fail(what, f"inlier_threshold must be finite and > 0 (got {inlier_threshold})")
+    tau = positive_finite(what, "inlier_threshold", inlier_threshold)
     if metric not in _METRICS:
-        _fail(what, f"metric must be 'squared' or 'length' (got {metric!r})")
+        fail(what, f"metric must be 'squared' or 'length' (got {metric!r})")
     return tau, _METRICS[metric]
 
 
@@ -53,38 +50,29 @@ def max_clique_batched(corr, src_keypts, tgt_keypts, inlier_threshold, metric="s
     No host synchronisation; the call can be captured into a graph."""
     what = "max_clique_batched"
     dims = 3 if offsets is None else 2
-    _check_rows(corr, "corr", what, dims, 6)
-    _check_rows(src_keypts, "src_keypts", what, dims, 3)
-    _check_rows(tgt_keypts, "tgt_keypts", what, dims, 3)
+    check_rows(what, "corr", corr, dims, 6)
+    check_rows(what, "src_keypts", src_keypts, dims, 3)
+    check_rows(what, "tgt_keypts", tgt_keypts, dims, 3)
     if not corr.shape[:-1] == src_keypts.shape[:-1] == tgt_keypts.shape[:-1]:
-        _fail(what, f"corr, src_keypts and tgt_keypts must have equal row counts (got {tuple(corr.shape)} / "
-                    f"{tuple(src_keypts.shape)} / {tuple(tgt_keypts.shape)})")
+        fail(what, f"corr, src_keypts and tgt_keypts must have equal row counts (got {tuple(corr.shape)} / "
+                   f"{tuple(src_keypts.shape)} / {tuple(tgt_keypts.shape)})")
     if dims == 3 and corr.shape[0] == 0:
-        _fail(what, "the batch must hold at least one pair")
+        fail(what, "the batch must hold at least one pair")
     tau, met = _check_common(what, inlier_threshold, metric)
-    budget = DEFAULT_MAX_STEPS
-    if max_steps is not None:
-        budget = int(max_steps)
-        if budget != max_steps or not 1 <= budget < 2 ** 62:
-            _fail(what, f"max_steps must be an integer >= 1 (got {max_steps})")
+    budget = DEFAULT_MAX_STEPS if max_steps is None else int_in_range(what, "max_steps", max_steps, 1, 2 ** 62 - 1, rule=">= 1")
     n_rows = corr.shape[0] * corr.shape[1] if dims == 3 else corr.shape[0]
-    if dims == 3:
-        off = list(range(0, n_rows + 1, corr.shape[1])) if corr.shape[1] else [0] * (corr.shape[0] + 1)
-    else:
-        off = _check_offsets(offsets, n_rows, what)
+    off = uniform_offsets(*corr.shape[:2]) if dims == 3 else check_offsets(what, "offsets", offsets, n_rows, allow_empty=True)
     for x, name in ((corr, "corr"), (src_keypts, "src_keypts"), (tgt_keypts, "tgt_keypts")):
-        if not x.is_cuda:
-            _fail(what, f"`{name}` must live on a HIP device (got {x.device}); the HIP path is mandatory, there is no CPU fallback")
+        require_device(x, name, what)
     dev = corr.device
-    if src_keypts.device != dev or tgt_keypts.device != dev:
-        _fail(what, "corr, src_keypts and tgt_keypts must live on the same device")
+    same_device(what, corr=corr, src_keypts=src_keypts, tgt_keypts=tgt_keypts)
     if isinstance(off, list):
         if max(b - a for a, b in zip(off, off[1:])) > MAX_ROWS:
             raise NotImplementedError(f"gmf_amd.{what}: a pair holds at most {MAX_ROWS} rows "
                                       f"(got {max(b - a for a, b in zip(off, off[1:]))})")
-        dev_off, max_n = _device_offsets(off, n_rows, dev, what, allow_empty=True)
+        dev_off, max_n = device_offsets(off, n_rows, dev, what, allow_empty=True, checked=True)
     else:
-        dev_off, _ = _device_offsets(off, n_rows, dev, what)
+        dev_off, _ = device_offsets(off, n_rows, dev, what)
         max_n = min(n_rows, MAX_ROWS)                       # the largest pair is not known without a read-back
     B = dev_off.numel() - 1
     Cc = corr.reshape(-1, 6).contiguous()
@@ -106,7 +94,7 @@ def PMC(corr, src_keypts, tgt_keypts, args):
     tgt_keypts [1,N,3], `args.inlier_threshold` read -> (pred_trans [1,4,4], pred_labels [1,N]).  The reference's rule on squared
     lengths; one pair per call; the inputs are not written.  Ties and the empty graph: see max_clique_batched."""
     if not isinstance(corr, torch.Tensor) or corr.dim() != 3 or corr.shape[0] != 1:
-        _fail("PMC", f"corr must be [1,N,6]: one pair per call, as in the reference (got {tuple(getattr(corr, 'shape', ()))})")
+        fail("PMC", f"corr must be [1,N,6]: one pair per call, as in the reference (got {tuple(getattr(corr, 'shape', ()))})")
     return max_clique_batched(corr, src_keypts, tgt_keypts, args.inlier_threshold)
 
 
@@ -114,10 +102,9 @@ def compatibility_graph(corr, inlier_threshold, metric="squared"):
     """The graph max_clique_batched searches, for one pair: corr [N,6] float32 on the device -> [N, ceil(N / 64)] int64 bit rows,
     bit j % 64 of word j / 64 of row i = edge (i, j).  No diagonal; the bits past column N - 1 are zero."""
     what = "compatibility_graph"
-    _check_rows(corr, "corr", what, 2, 6)
+    check_rows(what, "corr", corr, 2, 6)
     tau, met = _check_common(what, inlier_threshold, metric)
-    if not corr.is_cuda:
-        _fail(what, f"`corr` must live on a HIP device (got {corr.device}); the HIP path is mandatory, there is no CPU fallback")
+    require_device(corr, "corr", what)
     N = corr.shape[0]
     if N > MAX_ROWS:
         raise NotImplementedError(f"gmf_amd.{what}: a pair holds at most {MAX_ROWS} rows (got {N})")
@@ -125,7 +112,7 @@ def compatibility_graph(corr, inlier_threshold, metric="squared"):
     if N == 0:
         return bits
     Cc = corr.contiguous()
-    dev_off, _ = _device_offsets([0, N], N, corr.device, what)
+    dev_off, _ = device_offsets([0, N], N, corr.device, what, checked=True)
     degree = torch.empty(N, device=corr.device, dtype=torch.int32)
     h, st = handle_and_stream(Cc)
     h.call("gmf_pmc_graph", Cc.data_ptr(), dev_off.data_ptr(), 1, N, N, tau, met, bits.data_ptr(), degree.data_ptr(), st)

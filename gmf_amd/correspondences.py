@@ -7,10 +7,9 @@ reference's loaders, for B ragged pairs in one chain of five launches.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
+from ._args import c_ints, fail
 from ._util import handle_and_stream, require_cuda_f32
 from .matching import _batch_offsets
 
@@ -19,22 +18,18 @@ def _check_desc(src_desc, tgt_desc, len_batch, what):
     """Shapes and len_batch, before any device call -> (off0, off1)."""
     for name, F in (("src_desc", src_desc), ("tgt_desc", tgt_desc)):
         if not isinstance(F, torch.Tensor) or F.dim() != 2:
-            raise RuntimeError(f"gmf_amd.{what}: `{name}` must be a [rows, d] tensor")
+            fail(what, f"`{name}` must be a [rows, d] tensor")
     if src_desc.shape[1] != tgt_desc.shape[1]:
-        raise RuntimeError(f"gmf_amd.{what}: src_desc and tgt_desc differ in width ({src_desc.shape[1]} / {tgt_desc.shape[1]})")
+        fail(what, f"src_desc and tgt_desc differ in width ({src_desc.shape[1]} / {tgt_desc.shape[1]})")
     if src_desc.shape[1] > 128:
-        raise NotImplementedError(f"gmf_amd.{what}: descriptor width above 128 has no HIP kernel")
+        fail(what, "descriptor width above 128 has no HIP kernel", NotImplementedError)
     if len_batch is None:
         len_batch = [(src_desc.shape[0], tgt_desc.shape[0])]
     off0, off1 = _batch_offsets(len_batch, src_desc.shape[0], tgt_desc.shape[0], what)
     for b in range(len(off0) - 1):
         if off0[b + 1] > off0[b] and off1[b + 1] == off1[b]:
-            raise RuntimeError(f"gmf_amd.{what}: pair {b} has source rows and no target rows")
+            fail(what, f"pair {b} has source rows and no target rows")
     return off0, off1
-
-
-def _c_offsets(off):
-    return (ctypes.c_int * len(off))(*off)
 
 
 def nn_match_mutual(src_desc, tgt_desc, len_batch=None):
@@ -52,7 +47,7 @@ def nn_match_mutual(src_desc, tgt_desc, len_batch=None):
     dist = torch.empty(n, device=F0.device, dtype=torch.float32)
     mutual = torch.empty(n, device=F0.device, dtype=torch.uint8)
     h, st = handle_and_stream(F0)
-    h.call("gmf_nn_match_mutual_batched", F0.data_ptr(), F1.data_ptr(), _c_offsets(off0), _c_offsets(off1), len(off0) - 1, F0.shape[1],
+    h.call("gmf_nn_match_mutual_batched", F0.data_ptr(), F1.data_ptr(), c_ints(off0), c_ints(off1), len(off0) - 1, F0.shape[1],
            idx.data_ptr(), dist.data_ptr(), mutual.data_ptr(), st)
     return idx.long(), dist, mutual.bool()
 
@@ -79,17 +74,17 @@ def build_correspondences(src_keypts, tgt_keypts, src_desc, tgt_desc, len_batch=
     B = len(off0) - 1
     for name, P, n in (("src_keypts", src_keypts, off0[-1]), ("tgt_keypts", tgt_keypts, off1[-1])):
         if not isinstance(P, torch.Tensor) or P.dim() != 2 or tuple(P.shape) != (n, 3):
-            raise RuntimeError(f"gmf_amd.{what}: `{name}` must be [{n}, 3], one row per descriptor row")
+            fail(what, f"`{name}` must be [{n}, 3], one row per descriptor row")
     if in_dim not in (3, 6):
         raise NotImplementedError(f"gmf_amd.{what}: in_dim {in_dim} is not built (3 and 6 are; the 9, 12 and 70 forms are not what "
                                   "GMF instantiates)")
     if gt_trans is not None:
         if inlier_threshold is None:
-            raise RuntimeError(f"gmf_amd.{what}: gt_trans needs an inlier_threshold")
+            fail(what, "gt_trans needs an inlier_threshold")
         if not (float(inlier_threshold) > 0):
-            raise RuntimeError(f"gmf_amd.{what}: inlier_threshold must be > 0")
+            fail(what, "inlier_threshold must be > 0")
         if not isinstance(gt_trans, torch.Tensor) or tuple(gt_trans.shape) not in ((B, 4, 4),) + (((4, 4),) if B == 1 else ()):
-            raise RuntimeError(f"gmf_amd.{what}: gt_trans must be [{B}, 4, 4]")
+            fail(what, f"gt_trans must be [{B}, 4, 4]")
     F0 = require_cuda_f32(src_desc, "src_desc").contiguous()
     F1 = require_cuda_f32(tgt_desc, "tgt_desc").contiguous()
     P0 = require_cuda_f32(src_keypts, "src_keypts").contiguous()
@@ -105,7 +100,7 @@ def build_correspondences(src_keypts, tgt_keypts, src_desc, tgt_desc, len_batch=
     tdesc = torch.empty((cap, d), device=dev) if gather_desc else None
     labels = torch.empty(cap, device=dev) if T is not None else None
     h, st = handle_and_stream(F0)
-    h.call("gmf_build_correspondences", F0.data_ptr(), F1.data_ptr(), P0.data_ptr(), P1.data_ptr(), _c_offsets(off0), _c_offsets(off1),
+    h.call("gmf_build_correspondences", F0.data_ptr(), F1.data_ptr(), P0.data_ptr(), P1.data_ptr(), c_ints(off0), c_ints(off1),
            B, d, 1 if use_mutual else 0, in_dim, T.data_ptr() if T is not None else None,
            float(inlier_threshold) if T is not None else 0.0, offsets.data_ptr(), corr.data_ptr(), src.data_ptr(), tgt.data_ptr(),
            pos.data_ptr(), sdesc.data_ptr() if gather_desc else None, tdesc.data_ptr() if gather_desc else None,

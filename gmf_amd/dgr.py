@@ -16,7 +16,8 @@ from collections.abc import Mapping
 import numpy as np
 import torch
 
-from . import fcgf
+from . import _lib, fcgf
+from ._args import check_offsets, device_offsets, fail, positive_finite, require_device, same_device
 from .features import voxel_select
 from ._util import handle_and_stream
 from .matching import _batch_offsets, _match_batched, find_knn_gpu
@@ -281,26 +282,6 @@ def inlier_training_loss(logits, xyz0s, xyz1s, pred_pairs, is_correct, T_gt, *, 
 INLIER_FEATURE_TYPES = ("ones", "feats", "coords")      # gmf_inlier_input's feat_type 0, 1, 2
 
 
-def _offsets_list(offsets, n_rows, name, what):
-    """A host offset sequence checked (B + 1 entries ascending from 0 to n_rows; empty clouds allowed) -> list, or a device int32
-    tensor as it is (the caller vouches for it)."""
-    if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
-        if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2 or not offsets.is_contiguous():
-            raise RuntimeError(f"gmf_amd.{what}: device `{name}` must be a contiguous int32 vector of B + 1 entries")
-        return offsets
-    try:
-        off = [int(o) for o in (offsets.tolist() if isinstance(offsets, (torch.Tensor, np.ndarray)) else offsets)]
-    except (TypeError, ValueError):
-        raise RuntimeError(f"gmf_amd.{what}: `{name}` must be B + 1 integers") from None
-    if len(off) < 2 or off[0] != 0 or off[-1] != n_rows or any(b < a for a, b in zip(off, off[1:])):
-        raise RuntimeError(f"gmf_amd.{what}: `{name}` must ascend from 0 to the row count {n_rows} (got {off})")
-    return off
-
-
-def _dev_i32(off, device):
-    return off if isinstance(off, torch.Tensor) else torch.tensor(off, dtype=torch.int32, device=device)
-
-
 def matching_indices_batched(xyz0, off0, xyz1, off1, T, radius):
     """The ground-truth pairs of B registration problems on the device: get_matching_indices(source, target, trans,
     search_voxel_size, K=None) (util/pointcloud.py:83-96) for every pair of a batch, by brute force.
@@ -319,23 +300,22 @@ def matching_indices_batched(xyz0, off0, xyz1, off1, T, radius):
     what = "matching_indices_batched"
     for name, x in (("xyz0", xyz0), ("xyz1", xyz1)):
         if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != 3 or x.shape[0] == 0:
-            raise RuntimeError(f"gmf_amd.{what}: `{name}` must be a non-empty float32 [rows, 3] tensor")
-    o0 = _offsets_list(off0, xyz0.shape[0], "off0", what)
-    o1 = _offsets_list(off1, xyz1.shape[0], "off1", what)
+            fail(what, f"`{name}` must be a non-empty float32 [rows, 3] tensor")
+    o0 = check_offsets(what, "off0", off0, xyz0.shape[0], allow_empty=True)
+    o1 = check_offsets(what, "off1", off1, xyz1.shape[0], allow_empty=True)
     B = (o0.numel() if isinstance(o0, torch.Tensor) else len(o0)) - 1
     if (o1.numel() if isinstance(o1, torch.Tensor) else len(o1)) - 1 != B:
-        raise RuntimeError(f"gmf_amd.{what}: off0 and off1 describe different numbers of pairs")
+        fail(what, "off0 and off1 describe different numbers of pairs")
     T = torch.as_tensor(T)
     if tuple(T.shape) != (B, 4, 4):
-        raise RuntimeError(f"gmf_amd.{what}: T must be [{B}, 4, 4] (got {tuple(T.shape)})")
-    r = float(radius)
-    if not (r > 0 and np.isfinite(r)):
-        raise RuntimeError(f"gmf_amd.{what}: radius must be > 0 and finite (got {radius})")
-    if not xyz0.is_cuda or xyz1.device != xyz0.device:
-        raise RuntimeError(f"gmf_amd.{what}: xyz0 and xyz1 must live on one HIP device; there is no CPU fallback")
+        fail(what, f"T must be [{B}, 4, 4] (got {tuple(T.shape)})")
+    r = positive_finite(what, "radius", radius, rule="> 0 and finite")
+    require_device(xyz0, "xyz0", what)
+    same_device(what, xyz0=xyz0, xyz1=xyz1)
     dev = xyz0.device
     xyz0, xyz1 = xyz0.contiguous(), xyz1.contiguous()
-    d0, d1 = _dev_i32(o0, dev), _dev_i32(o1, dev)
+    d0 = device_offsets(o0, xyz0.shape[0], dev, what, allow_empty=True, checked=True)[0]
+    d1 = device_offsets(o1, xyz1.shape[0], dev, what, allow_empty=True, checked=True)[0]
     Td = T.to(dev, torch.float64).contiguous()
     n0, n1 = xyz0.shape[0], xyz1.shape[0]
     row_start = torch.empty(n0 + 1, device=dev, dtype=torch.int64)
@@ -364,7 +344,7 @@ def _label_seeds(n_pairs, hash_seed, len_batch, what):
     """The asserts of core/correspondence.py:30-32 as RuntimeError, and each pair's hash seed."""
     if hash_seed is None:
         if len_batch is None or len(len_batch) != n_pairs:
-            raise RuntimeError(f"gmf_amd.{what}: without hash_seed, len_batch must have one (N0, N1) per pair")
+            fail(what, "without hash_seed, len_batch must have one (N0, N1) per pair")
         return [max(int(a), int(b)) for a, b in len_batch]
     return [int(hash_seed)] * n_pairs
 
@@ -382,14 +362,14 @@ def _positive_keys(pos_pairs, seeds, dev, what):
         for p in pos_pairs:
             p = torch.as_tensor(p)
             if p.dtype.is_floating_point or p.dtype == torch.bool or (p.numel() and (p.dim() != 2 or p.shape[1] != 2)):
-                raise RuntimeError(f"gmf_amd.{what}: every pos_pairs entry must be an integer [K, 2] tensor")
+                fail(what, "every pos_pairs entry must be an integer [K, 2] tensor")
             parts.append(p.reshape(-1, 2).to(dev, torch.int64))
         counts = [int(p.shape[0]) for p in parts]
         pos = torch.cat(parts) if parts else torch.empty((0, 2), dtype=torch.int64, device=dev)
         pos_off = torch.tensor(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), device=dev)
         seg = torch.repeat_interleave(torch.arange(B, device=dev), torch.tensor(counts, device=dev), output_size=pos.shape[0])
     if pos.dim() != 2 or pos.shape[1] != 2:
-        raise RuntimeError(f"gmf_amd.{what}: the packed pos_pairs must be [K, 2]")
+        fail(what, "the packed pos_pairs must be [K, 2]")
     keys = pos[:, 0] + pos[:, 1] * seeds_d[seg.clamp(max=B - 1)]          # core/correspondence.py:14-26, int64
     # sorted inside each pair's range: by key, then stably by pair (the ranges are contiguous already, so they keep their place)
     keys, order = torch.sort(keys, stable=True)
@@ -409,15 +389,14 @@ def find_correct_correspondence(pos_pairs, pred_pairs, hash_seed=None, len_batch
     what = "find_correct_correspondence"
     B = len(pred_pairs)
     if _num_pos(pos_pairs) != B:
-        raise RuntimeError(f"gmf_amd.{what}: {_num_pos(pos_pairs)} pos_pairs entries for {B} pred_pairs entries")
+        fail(what, f"{_num_pos(pos_pairs)} pos_pairs entries for {B} pred_pairs entries")
     seeds = _label_seeds(B, hash_seed, len_batch, what)
     if B == 0:
-        raise RuntimeError(f"gmf_amd.{what}: empty batch")
+        fail(what, "empty batch")
     for p in pred_pairs:
         if not isinstance(p, torch.Tensor) or p.dim() != 2 or p.shape[1] != 2 or p.dtype.is_floating_point:
-            raise RuntimeError(f"gmf_amd.{what}: every pred_pairs entry must be an integer [n, 2] tensor")
-        if not p.is_cuda:
-            raise RuntimeError(f"gmf_amd.{what}: pred_pairs must live on a HIP device; there is no CPU fallback")
+            fail(what, "every pred_pairs entry must be an integer [n, 2] tensor")
+        require_device(p, "pred_pairs", what)
     dev = pred_pairs[0].device
     pred = torch.cat([p.to(torch.int64) for p in pred_pairs]).contiguous()
     M = pred.shape[0]
@@ -437,7 +416,7 @@ def _packed_points(xyz, n_rows, name, what):
     if isinstance(xyz, (list, tuple)):
         xyz = torch.cat([torch.as_tensor(x) for x in xyz], 0)
     if not isinstance(xyz, torch.Tensor) or xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] != n_rows:
-        raise RuntimeError(f"gmf_amd.{what}: `{name}` must hold {n_rows} points [*, 3] (a tensor, or a list with one tensor per pair)")
+        fail(what, f"`{name}` must hold {n_rows} points [*, 3] (a tensor, or a list with one tensor per pair)")
     return xyz
 
 
@@ -459,23 +438,22 @@ def generate_inlier_input(feat_model, xyz0, xyz1, iC0, iC1, iF0, iF1, len_batch,
     if inlier_feature_type not in INLIER_FEATURE_TYPES:
         raise ValueError("Inlier feature type not defined")
     if knn != 1:
-        raise NotImplementedError(f"gmf_amd.{what}: GMF-DGR only uses knn = 1 (deep_global_registration.py:300)")
+        fail(what, "GMF-DGR only uses knn = 1 (deep_global_registration.py:300)", NotImplementedError)
     for name, c in (("iC0", iC0), ("iC1", iC1)):
         if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != 4 or c.dtype.is_floating_point:
-            raise RuntimeError(f"gmf_amd.{what}: `{name}` must be an integer [N, 4] tensor (batch, x, y, z)")
+            fail(what, f"`{name}` must be an integer [N, 4] tensor (batch, x, y, z)")
     off0, off1 = _batch_offsets(len_batch, iC0.shape[0], iC1.shape[0], what)
     B = len(off0) - 1
     if pos_pairs is not None:
         if _num_pos(pos_pairs) != B:
-            raise RuntimeError(f"gmf_amd.{what}: {_num_pos(pos_pairs)} pos_pairs entries for {B} pairs")
+            fail(what, f"{_num_pos(pos_pairs)} pos_pairs entries for {B} pairs")
         seeds = _label_seeds(B, None, len_batch, what)
     ftype = INLIER_FEATURE_TYPES.index(inlier_feature_type)
     if ftype == 2:
         xyz0 = _packed_points(xyz0, iC0.shape[0], "xyz0", what)
         xyz1 = _packed_points(xyz1, iC1.shape[0], "xyz1", what)
     dev = next(feat_model.parameters()).device
-    if dev.type != "cuda":
-        raise RuntimeError(f"gmf_amd.{what}: feat_model must live on a HIP device; there is no CPU fallback")
+    require_device(dev, "feat_model", what)
     iC0 = iC0.to(dev, torch.int32).contiguous()
     iC1 = iC1.to(dev, torch.int32).contiguous()
     with torch.no_grad():
@@ -488,7 +466,7 @@ def generate_inlier_input(feat_model, xyz0, xyz1, iC0, iC1, iF0, iF1, len_batch,
     if ftype == 1:
         a0, a1, width = oF0.contiguous(), oF1.contiguous(), 2 * oF0.shape[1]
         if oF0.shape[1] > 64:
-            raise NotImplementedError(f"gmf_amd.{what}: 'feats' takes descriptors up to 64 wide (got {oF0.shape[1]})")
+            fail(what, f"'feats' takes descriptors up to 64 wide (got {oF0.shape[1]})", NotImplementedError)
     elif ftype == 2:
         a0, a1, width = xyz0.to(dev, torch.float32).contiguous(), xyz1.to(dev, torch.float32).contiguous(), 6
     reg_coords = torch.empty((M, 7), device=dev, dtype=torch.int32)
@@ -499,8 +477,9 @@ def generate_inlier_input(feat_model, xyz0, xyz1, iC0, iC1, iF0, iF1, len_batch,
         labels = torch.empty(M, device=dev, dtype=torch.uint8)
         keys, pos_off, seeds_d = _positive_keys(pos_pairs, seeds, dev, what)
     if M:
-        p = lambda t: None if t is None else t.data_ptr()      # noqa: E731
-        d0, d1 = _dev_i32(off0, dev), _dev_i32(off1, dev)
+        p = _lib.ptr
+        d0 = device_offsets(off0, off0[-1], dev, what, allow_empty=True, checked=True)[0]
+        d1 = device_offsets(off1, off1[-1], dev, what, allow_empty=True, checked=True)[0]
         h, st = handle_and_stream(idx32)
         h.call("gmf_inlier_input", idx32.data_ptr(), None, d0.data_ptr(), d1.data_ptr(), B, M, pred.data_ptr(), iC0.data_ptr(),
                iC1.data_ptr(), reg_coords.data_ptr(), ftype, p(a0), p(a1), oF0.shape[1] if ftype == 1 else 0, reg_feats.data_ptr(),

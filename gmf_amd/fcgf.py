@@ -13,8 +13,9 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._args import fail
 from ._util import handle_and_stream
-from .sparse import CONV1_TR, FINAL, _ResUNet, _fail, _folded_conv, resunet_trunk, sparse_conv_narrow, sparse_head_l2
+from .sparse import CONV1_TR, FINAL, _ResUNet, _folded_conv, resunet_trunk, sparse_conv_narrow, sparse_head_l2
 
 NARROW_MAX_CIN = 8
 HEAD_MAX_C = 64
@@ -33,7 +34,7 @@ class ResUNetBN2C(_ResUNet):
     def __init__(self, in_channels=3, out_channels=32, bn_momentum=0.1, conv1_kernel_size=3, normalize_feature=False, D=3):
         super().__init__(in_channels, out_channels, conv1_kernel_size, normalize_feature, D)
         if not (1 <= int(out_channels) <= HEAD_MAX_C):
-            _fail(self._what, f"the fused head takes out_channels in 1..{HEAD_MAX_C} (got {out_channels})", NotImplementedError)
+            fail(self._what, f"the fused head takes out_channels in 1..{HEAD_MAX_C} (got {out_channels})", NotImplementedError)
         self.narrow_conv1 = True
         self._build_trunk(bn_momentum)
 
@@ -71,9 +72,9 @@ LOSS_MAX_C = 64
 
 def _index_arg(t, name, what, shape_tail=()):
     if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
-        _fail(what, f"`{name}` must be an int64 tensor (got {getattr(t, 'dtype', type(t).__name__)})")
+        fail(what, f"`{name}` must be an int64 tensor (got {getattr(t, 'dtype', type(t).__name__)})")
     if t.dim() != 1 + len(shape_tail) or tuple(t.shape[1:]) != tuple(shape_tail):
-        _fail(what, f"`{name}` must be [n{''.join(', ' + str(s) for s in shape_tail)}] (got {tuple(t.shape)})")
+        fail(what, f"`{name}` must be [n{''.join(', ' + str(s) for s in shape_tail)}] (got {tuple(t.shape)})")
     return t
 
 
@@ -81,23 +82,23 @@ def _loss_args(F0, F1, positive_pairs, sel0, sel1, pos_sel, what):
     """Dtype and shape checks of the loss's arguments (no device needed), then the device checks."""
     for name, F in (("F0", F0), ("F1", F1)):
         if not isinstance(F, torch.Tensor) or F.dtype != torch.float32:
-            _fail(what, f"`{name}` must be a float32 tensor (got {getattr(F, 'dtype', type(F).__name__)})")
+            fail(what, f"`{name}` must be a float32 tensor (got {getattr(F, 'dtype', type(F).__name__)})")
         if F.dim() != 2 or F.shape[0] == 0:
-            _fail(what, f"`{name}` must be a non-empty [N, C] tensor (got {tuple(F.shape)})")
+            fail(what, f"`{name}` must be a non-empty [N, C] tensor (got {tuple(F.shape)})")
     if F0.shape[1] != F1.shape[1]:
-        _fail(what, f"`F0` and `F1` must have the same width (got {F0.shape[1]} and {F1.shape[1]})")
+        fail(what, f"`F0` and `F1` must have the same width (got {F0.shape[1]} and {F1.shape[1]})")
     if not (1 <= F0.shape[1] <= LOSS_MAX_C):
-        _fail(what, f"the feature width must be in 1..{LOSS_MAX_C} (got {F0.shape[1]})", NotImplementedError)
+        fail(what, f"the feature width must be in 1..{LOSS_MAX_C} (got {F0.shape[1]})", NotImplementedError)
     _index_arg(positive_pairs, "positive_pairs", what, (2,))
     _index_arg(sel0, "sel0", what)
     _index_arg(sel1, "sel1", what)
     if pos_sel is not None:
         _index_arg(pos_sel, "pos_sel", what)
     if sel0.shape[0] == 0 or sel1.shape[0] == 0:
-        _fail(what, "`sel0` and `sel1` must hold at least one candidate row each")
+        fail(what, "`sel0` and `sel1` must hold at least one candidate row each")
     for name, t in (("F0", F0), ("F1", F1), ("positive_pairs", positive_pairs), ("sel0", sel0), ("sel1", sel1), ("pos_sel", pos_sel)):
         if t is not None and not t.is_cuda:
-            _fail(what, f"`{name}` must live on a HIP device (got {t.device}); the HIP path is mandatory, there is no CPU fallback")
+            fail(what, f"`{name}` must live on a HIP device (got {t.device}); the HIP path is mandatory, there is no CPU fallback")
 
 
 def _sum_by_dest(rows, dest, N):

@@ -10,52 +10,28 @@ from __future__ import annotations
 
 import ctypes
 
-import numpy as np
 import torch
 
+from ._args import check_offsets, check_rows, device_offsets, fail, int_in_range, positive_finite, require_device, same_device
 from ._util import handle_and_stream
-from .registration import _device_offsets
-from .solvers import _check_offsets, _fail, _require_device
 
 MAX_NN = 256      # the search keeps at most this many neighbours per row
 
 
-def _check_cloud(points, offsets, what, name="points"):
-    if not isinstance(points, torch.Tensor):
-        _fail(what, f"`{name}` must be a torch tensor")
-    if points.dtype != torch.float32:
-        _fail(what, f"`{name}` must be float32 (got {points.dtype})")
-    if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] == 0:
-        _fail(what, f"`{name}` must be a non-empty [sum N,3] tensor (got {tuple(points.shape)})")
+def _check_cloud(points, offsets, what):
+    check_rows(what, "points", points, 2, 3, non_empty=True)
     n = points.shape[0]
-    off = [0, n] if offsets is None else _check_offsets(offsets, n, what)
-    return n, off
+    return n, [0, n] if offsets is None else check_offsets(what, "offsets", offsets, n)
 
 
-def _positive(x, name, what):
-    try:
-        v = float(x)
-    except (TypeError, ValueError):
-        v = float("nan")
-    if not (v > 0 and np.isfinite(v)):
-        _fail(what, f"{name} must be > 0 and finite (got {x})")
-    return v
-
-
-def _check_max_nn(max_nn, what):
-    try:
-        m = int(max_nn)
-    except (TypeError, ValueError):
-        m = 0
-    if m != max_nn or not 1 <= m <= MAX_NN:
-        _fail(what, f"max_nn must be an integer in 1..{MAX_NN} (got {max_nn})")
-    return m
+def _radius_and_nn(what, radius, max_nn):
+    return positive_finite(what, "radius", radius, rule="> 0 and finite"), int_in_range(what, "max_nn", max_nn, 1, MAX_NN)
 
 
 def _prepare(points, offsets, what):
     n, off = _check_cloud(points, offsets, what)
-    _require_device(points, "points", what)
-    dev_off, _ = _device_offsets(off, n, points.device, what)
+    require_device(points, "points", what)
+    dev_off, _ = device_offsets(off, n, points.device, what, checked=True)
     return points.contiguous(), dev_off, dev_off.numel() - 1, n
 
 
@@ -68,8 +44,7 @@ def radius_knn_batched(points, offsets, radius, max_nn):
     Returns idx [sum N, max_nn] int32 (row within the cloud, -1 padding), d2 [sum N, max_nn] float64 (0 padding) and
     count [sum N] int32, each row sorted by key."""
     what = "radius_knn_batched"
-    r = _positive(radius, "radius", what)
-    m = _check_max_nn(max_nn, what)
+    r, m = _radius_and_nn(what, radius, max_nn)
     P, off, B, n = _prepare(points, offsets, what)
     dev = P.device
     idx = torch.empty((n, m), device=dev, dtype=torch.int32)
@@ -85,8 +60,7 @@ def estimate_normals_batched(points, offsets, radius, max_nn=30):
     neighbour set of radius_knn_batched, with >= 3 neighbours the eigenvector of the smallest eigenvalue of the fp64 covariance
     (open3d's FastEigen3x3, whose sign is kept: open3d does not orient these normals), else (0, 0, 1).  -> [sum N,3] float32."""
     what = "estimate_normals_batched"
-    r = _positive(radius, "radius", what)
-    m = _check_max_nn(max_nn, what)
+    r, m = _radius_and_nn(what, radius, max_nn)
     P, off, B, n = _prepare(points, offsets, what)
     normals = torch.empty((n, 3), device=P.device, dtype=torch.float32)
     h, st = handle_and_stream(P)
@@ -100,15 +74,13 @@ def compute_fpfh_batched(points, normals, offsets, radius, max_nn=100):
     neighbours' SPFH weighted by 1 / d^2 (rows at d^2 = 0 skipped), each 11-bin block renormalised to 100, plus the row's own
     SPFH.  -> [sum N,33] float32, row-major (open3d's Feature.data is [33,N]).  Bitwise repeatable."""
     what = "compute_fpfh_batched"
-    r = _positive(radius, "radius", what)
-    m = _check_max_nn(max_nn, what)
+    r, m = _radius_and_nn(what, radius, max_nn)
     n0, _ = _check_cloud(points, offsets, what)
     if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or tuple(normals.shape) != (n0, 3):
-        _fail(what, f"normals must be a float32 [{n0},3] tensor, one row per point")
+        fail(what, f"normals must be a float32 [{n0},3] tensor, one row per point")
     P, off, B, n = _prepare(points, offsets, what)
-    _require_device(normals, "normals", what)
-    if normals.device != P.device:
-        _fail(what, "points and normals must live on the same device")
+    require_device(normals, "normals", what)
+    same_device(what, points=P, normals=normals)
     Nn = normals.contiguous()
     feats = torch.empty((n, 33), device=P.device, dtype=torch.float32)
     h, st = handle_and_stream(P)
@@ -117,7 +89,7 @@ def compute_fpfh_batched(points, normals, offsets, radius, max_nn=100):
 
 
 def _voxel(points, offsets, voxel_size, what, mean):
-    v = _positive(voxel_size, "voxel_size", what)
+    v = positive_finite(what, "voxel_size", voxel_size, rule="> 0 and finite")
     P, off, B, n = _prepare(points, offsets, what)
     dev = P.device
     out = torch.empty((n, 3) if mean else (n,), device=dev, dtype=torch.float32 if mean else torch.int32)
@@ -176,10 +148,10 @@ def fpfh_descriptors(points, voxel_size, offsets=None, voxelize="mean"):
     (xyz_down, features, offsets_down).  The features feed nn_match / find_knn_gpu directly."""
     what = "fpfh_descriptors"
     if voxelize not in ("mean", "select"):
-        _fail(what, f"voxelize must be 'mean' or 'select' (got {voxelize!r})")
-    v = _positive(voxel_size, "voxel_size", what)
+        fail(what, f"voxelize must be 'mean' or 'select' (got {voxelize!r})")
+    v = positive_finite(what, "voxel_size", voxel_size, rule="> 0 and finite")
     n, off = _check_cloud(points, offsets, what)
-    _require_device(points, "points", what)
+    require_device(points, "points", what)
     if voxelize == "mean":
         xyz, off_d = voxel_down_sample_batched(points, off, v)
     else:

@@ -15,23 +15,12 @@ import ctypes as C
 import numpy as np
 import torch
 
+from ._args import device_offsets, fail, positive_finite, require_device
 from ._util import handle_and_stream
-from .registration import _device_offsets
-from .spectral import _fail
 
 MAX_FRAMES = 65535            # frames of one fragment, at most
 MAX_FRAGMENTS = 65535         # fragments of one call, at most (kTsdfMaxFragments)
 MAX_UNITS = 1 << 22           # the largest max_units the library takes
-
-
-def _positive(what, name, v, allow_inf=False):
-    try:
-        f = float(v)
-    except (TypeError, ValueError):
-        _fail(what, f"{name} must be a number (got {v!r})")
-    if not f > 0 or (not allow_inf and not np.isfinite(f)):
-        _fail(what, f"{name} must be {'' if allow_inf else 'finite and '}> 0 (got {v})")
-    return f
 
 
 def _nothing(points_off, return_volume, colored=False):
@@ -98,73 +87,72 @@ def _fragments(what, color, depth, poses, intrinsic, frame_offsets, voxel_length
     """tsdf_fragments (colored False: `color` is not looked at) and tsdf_fragments_colored: the argument checks, raised under the
     name `what`, and the calls."""
     if not isinstance(depth, torch.Tensor):
-        _fail(what, "`depth` must be a torch tensor")
+        fail(what, "`depth` must be a torch tensor")
     if depth.dtype not in (torch.uint16, torch.float32):
-        _fail(what, f"`depth` must be uint16 (sensor values) or float32 (metres) (got {depth.dtype})")
+        fail(what, f"`depth` must be uint16 (sensor values) or float32 (metres) (got {depth.dtype})")
     if depth.dim() != 3 or depth.shape[1] < 1 or depth.shape[2] < 1:
-        _fail(what, f"`depth` must be a [F,H,W] tensor (got {tuple(depth.shape)})")
+        fail(what, f"`depth` must be a [F,H,W] tensor (got {tuple(depth.shape)})")
     F, H, W = depth.shape
     if F * H * W >= 2 ** 31:
-        _fail(what, f"`depth` must hold fewer than 2^31 pixels (got {F * H * W})")
+        fail(what, f"`depth` must hold fewer than 2^31 pixels (got {F * H * W})")
     if colored:
         if not isinstance(color, torch.Tensor):
-            _fail(what, "`color` must be a torch tensor")
+            fail(what, "`color` must be a torch tensor")
         if color.dtype != torch.uint8:
-            _fail(what, f"`color` must be uint8 (got {color.dtype})")
+            fail(what, f"`color` must be uint8 (got {color.dtype})")
         if tuple(color.shape) != (F, H, W, 3):
-            _fail(what, f"`color` must be [F,H,W,3] (R, G, B) with depth's F, H, W = {F}, {H}, {W} (got {tuple(color.shape)})")
+            fail(what, f"`color` must be [F,H,W,3] (R, G, B) with depth's F, H, W = {F}, {H}, {W} (got {tuple(color.shape)})")
         if color.device != depth.device:
-            _fail(what, f"`color` must live on depth's device (got {color.device} and {depth.device})")
+            fail(what, f"`color` must live on depth's device (got {color.device} and {depth.device})")
     if not isinstance(poses, torch.Tensor):
-        _fail(what, "`poses` must be a torch tensor")
+        fail(what, "`poses` must be a torch tensor")
     if poses.dtype != torch.float64:
-        _fail(what, f"`poses` must be float64 (got {poses.dtype})")
+        fail(what, f"`poses` must be float64 (got {poses.dtype})")
     if poses.dim() != 3 or tuple(poses.shape) != (F, 4, 4):
-        _fail(what, f"`poses` must be [F,4,4] with depth's F = {F} (got {tuple(poses.shape)})")
+        fail(what, f"`poses` must be [F,4,4] with depth's F = {F} (got {tuple(poses.shape)})")
     try:
         fx, fy, cx, cy = (float(v) for v in intrinsic)
     except (TypeError, ValueError):
-        _fail(what, f"intrinsic must be four numbers (fx, fy, cx, cy) (got {intrinsic!r})")
+        fail(what, f"intrinsic must be four numbers (fx, fy, cx, cy) (got {intrinsic!r})")
     if not (np.isfinite([fx, fy, cx, cy]).all() and fx > 0 and fy > 0):
-        _fail(what, f"intrinsic must be finite with fx, fy > 0 (got {intrinsic!r})")
+        fail(what, f"intrinsic must be finite with fx, fy > 0 (got {intrinsic!r})")
     if frame_offsets is None:
         off = [0, F]
     else:
         if isinstance(frame_offsets, torch.Tensor) and frame_offsets.is_cuda:
-            _fail(what, "frame_offsets must be G + 1 host integers (they size the call)")
+            fail(what, "frame_offsets must be G + 1 host integers (they size the call)")
         try:
             seq = frame_offsets.tolist() if isinstance(frame_offsets, (torch.Tensor, np.ndarray)) else list(frame_offsets)
             off = [int(o) for o in seq]
             if any(o != s for o, s in zip(off, seq)):
                 raise ValueError
         except (TypeError, ValueError):
-            _fail(what, "frame_offsets must be G + 1 integers")
+            fail(what, "frame_offsets must be G + 1 integers")
         if len(off) < 2 or off[0] != 0 or off[-1] != F or any(b < a for a, b in zip(off, off[1:])):
-            _fail(what, "frame_offsets must not decrease, start at 0 and end at F")
+            fail(what, "frame_offsets must not decrease, start at 0 and end at F")
     G = len(off) - 1
     if G > MAX_FRAGMENTS:
-        _fail(what, f"a call holds at most {MAX_FRAGMENTS} fragments (got {G})")
+        fail(what, f"a call holds at most {MAX_FRAGMENTS} fragments (got {G})")
     if max(b - a for a, b in zip(off, off[1:])) > MAX_FRAMES:
-        _fail(what, f"a fragment holds at most {MAX_FRAMES} frames (got {max(b - a for a, b in zip(off, off[1:]))})")
-    vl = _positive(what, "voxel_length", voxel_length)
-    trunc = _positive(what, "sdf_trunc", sdf_trunc)
-    scale = _positive(what, "depth_scale", depth_scale)
-    far = _positive(what, "depth_trunc", depth_trunc, allow_inf=True)
+        fail(what, f"a fragment holds at most {MAX_FRAMES} frames (got {max(b - a for a, b in zip(off, off[1:]))})")
+    vl = positive_finite(what, "voxel_length", voxel_length, numeric=True)
+    trunc = positive_finite(what, "sdf_trunc", sdf_trunc, numeric=True)
+    scale = positive_finite(what, "depth_scale", depth_scale, numeric=True)
+    far = positive_finite(what, "depth_trunc", depth_trunc, allow_inf=True, numeric=True)
     stride = int(depth_sampling_stride) if isinstance(depth_sampling_stride, (int, np.integer)) else 0
     if stride < 1:
-        _fail(what, f"depth_sampling_stride must be an integer >= 1 (got {depth_sampling_stride!r})")
+        fail(what, f"depth_sampling_stride must be an integer >= 1 (got {depth_sampling_stride!r})")
     units_cap = int(max_units) if isinstance(max_units, (int, np.integer)) else 0
     if not 1 <= units_cap <= MAX_UNITS:
-        _fail(what, f"max_units must be an integer in 1..{MAX_UNITS} (got {max_units!r})")
+        fail(what, f"max_units must be an integer in 1..{MAX_UNITS} (got {max_units!r})")
     P = np.ascontiguousarray(poses.detach().cpu().numpy())
     if not np.isfinite(P).all():
-        _fail(what, "`poses` must be finite")
+        fail(what, "`poses` must be finite")
     try:
         Pinv = np.linalg.inv(P)
     except np.linalg.LinAlgError:
-        _fail(what, "`poses` must be invertible")
-    if not depth.is_cuda:
-        _fail(what, f"`depth` must live on a HIP device (got {depth.device}); the HIP path is mandatory, there is no CPU fallback")
+        fail(what, "`poses` must be invertible")
+    require_device(depth, "depth", what)
     dev = depth.device
 
     points_off = torch.zeros(G + 1, device=dev, dtype=torch.int32)
@@ -174,7 +162,7 @@ def _fragments(what, color, depth, poses, intrinsic, frame_offsets, voxel_length
     D = depth.contiguous()
     u16 = 1 if depth.dtype == torch.uint16 else 0
     both = torch.from_numpy(np.stack([P, Pinv])).pin_memory().to(dev, non_blocking=True)      # [2,F,4,4] fp64, no synchronisation
-    dev_off, _ = _device_offsets(off, F, dev, what, allow_empty=True)
+    dev_off, _ = device_offsets(off, F, dev, what, allow_empty=True, checked=True)
     h, st = handle_and_stream(D)
     shared = (D.data_ptr(), u16)
     camera = (G, F, H, W, fx, fy, cx, cy, vl, trunc, scale, far)

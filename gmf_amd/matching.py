@@ -8,10 +8,9 @@ correspondences on both plugin surfaces.
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
+from ._args import c_ints, fail
 from ._util import handle_and_stream, require_cuda_f32
 
 
@@ -19,9 +18,9 @@ def _match(F0, F1, mode):
     F0 = require_cuda_f32(F0, "F0").contiguous()
     F1 = require_cuda_f32(F1, "F1").contiguous()
     if F0.dim() != 2 or F1.dim() != 2 or F0.shape[1] != F1.shape[1]:
-        raise RuntimeError(f"gmf_amd.matching: expected [N0,d] and [N1,d], got {tuple(F0.shape)} / {tuple(F1.shape)}")
+        fail("matching", f"expected [N0,d] and [N1,d], got {tuple(F0.shape)} / {tuple(F1.shape)}")
     if F0.shape[1] > 128:
-        raise NotImplementedError("gmf_amd.matching: descriptor width above 128 has no HIP kernel")
+        fail("matching", "descriptor width above 128 has no HIP kernel", NotImplementedError)
     idx = torch.empty(F0.shape[0], device=F0.device, dtype=torch.int32)
     dist = torch.empty(F0.shape[0], device=F0.device, dtype=torch.float32)
     h, st = handle_and_stream(F0)
@@ -40,7 +39,7 @@ def find_knn_gpu(F0, F1, nn_max_n=-1, knn=1, return_distance=False):
     """DGR find_knn_gpu.  `nn_max_n` only selects the reference's distance convention (L2 when chunked, squared L2
     otherwise); no chunking is needed here because the N0 x N1 matrix is never materialised."""
     if knn != 1:
-        raise NotImplementedError("gmf_amd.find_knn_gpu: GMF-DGR only uses knn = 1 (deep_global_registration.py:300)")
+        fail("find_knn_gpu", "GMF-DGR only uses knn = 1 (deep_global_registration.py:300)", NotImplementedError)
     idx, dist = _match(F0, F1, 1 if nn_max_n > 1 else 2)
     if nn_max_n > 1:
         idx = idx[:, None]          # the reference concatenates [rows, knn] blocks (knn.py:40-41,62-63)
@@ -52,17 +51,17 @@ def _batch_offsets(len_batch, n0, n1, what):
     try:
         lens = [(int(a), int(b)) for a, b in len_batch]
     except (TypeError, ValueError):
-        raise RuntimeError(f"gmf_amd.{what}: len_batch must be a sequence of (N0, N1) pairs") from None
+        fail(what, "len_batch must be a sequence of (N0, N1) pairs")
     if not lens:
-        raise RuntimeError(f"gmf_amd.{what}: len_batch is empty")
+        fail(what, "len_batch is empty")
     if any(a < 0 or b < 0 for a, b in lens):
-        raise RuntimeError(f"gmf_amd.{what}: len_batch holds a negative size")
+        fail(what, "len_batch holds a negative size")
     off0, off1 = [0], [0]
     for a, b in lens:
         off0.append(off0[-1] + a)
         off1.append(off1[-1] + b)
     if off0[-1] != n0 or off1[-1] != n1:
-        raise RuntimeError(f"gmf_amd.{what}: len_batch sums to ({off0[-1]}, {off1[-1]}) rows, F0 / F1 have ({n0}, {n1})")
+        fail(what, f"len_batch sums to ({off0[-1]}, {off1[-1]}) rows, F0 / F1 have ({n0}, {n1})")
     return off0, off1
 
 
@@ -70,11 +69,11 @@ def _match_batched(F0, F1, len_batch, mode, global_index, what):
     """-> (idx [sum N0] int64, dist [sum N0] float32, off0, off1) of gmf_nn_match_batched."""
     for name, F in (("F0", F0), ("F1", F1)):
         if not isinstance(F, torch.Tensor) or F.dim() != 2:
-            raise RuntimeError(f"gmf_amd.{what}: `{name}` must be a [rows, d] tensor")
+            fail(what, f"`{name}` must be a [rows, d] tensor")
     if F0.shape[1] != F1.shape[1]:
-        raise RuntimeError(f"gmf_amd.{what}: F0 and F1 differ in width ({F0.shape[1]} / {F1.shape[1]})")
+        fail(what, f"F0 and F1 differ in width ({F0.shape[1]} / {F1.shape[1]})")
     if F0.shape[1] > 128:
-        raise NotImplementedError(f"gmf_amd.{what}: descriptor width above 128 has no HIP kernel")
+        fail(what, "descriptor width above 128 has no HIP kernel", NotImplementedError)
     off0, off1 = _batch_offsets(len_batch, F0.shape[0], F1.shape[0], what)
     F0 = require_cuda_f32(F0, "F0").contiguous()
     F1 = require_cuda_f32(F1, "F1").contiguous()
@@ -82,7 +81,7 @@ def _match_batched(F0, F1, len_batch, mode, global_index, what):
     idx = torch.empty(F0.shape[0], device=F0.device, dtype=torch.int32)
     dist = torch.empty(F0.shape[0], device=F0.device, dtype=torch.float32)
     h, st = handle_and_stream(F0)
-    h.call("gmf_nn_match_batched", F0.data_ptr(), F1.data_ptr(), (ctypes.c_int * (B + 1))(*off0), (ctypes.c_int * (B + 1))(*off1),
+    h.call("gmf_nn_match_batched", F0.data_ptr(), F1.data_ptr(), c_ints(off0), c_ints(off1),
            B, F0.shape[1], mode, 1 if global_index else 0, idx.data_ptr(), dist.data_ptr(), st)
     return idx, dist, off0, off1
 
@@ -95,7 +94,7 @@ def find_knn_gpu_batch(F0, F1, len_batch, nn_max_n=-1, knn=1, return_distance=Fa
     bit.  A pair without source rows gives an empty entry; one with source rows and no target rows raises RuntimeError."""
     what = "find_knn_gpu_batch"
     if knn != 1:
-        raise NotImplementedError(f"gmf_amd.{what}: GMF-DGR only uses knn = 1 (deep_global_registration.py:300)")
+        fail(what, "GMF-DGR only uses knn = 1 (deep_global_registration.py:300)", NotImplementedError)
     chunked = nn_max_n > 1
     idx32, dist, off0, _ = _match_batched(F0, F1, len_batch, 1 if chunked else 2, concat_results, what)
     idx = idx32.long()
@@ -117,7 +116,7 @@ def find_knn_batch(F0, F1, len_batch, return_distance=False, nn_max_n=-1, knn=1,
         return find_knn_gpu_batch(F0, F1, len_batch, nn_max_n=nn_max_n, knn=knn, return_distance=return_distance,
                                   concat_results=concat_results)
     if search_method == "cpu":
-        raise NotImplementedError("gmf_amd.find_knn_batch: the 'cpu' search method is not built; there is no CPU fallback")
+        fail("find_knn_batch", "the 'cpu' search method is not built; there is no CPU fallback", NotImplementedError)
     raise ValueError(f"Search method {search_method} not defined")
 
 
@@ -126,7 +125,7 @@ def find_pairs(F0, F1, len_batch, nn_max_n=-1, knn=1):
     nearest target row), both local to the pair.  (The reference returns them on the CPU.)"""
     what = "find_pairs"
     if knn != 1:
-        raise NotImplementedError(f"gmf_amd.{what}: GMF-DGR only uses knn = 1 (deep_global_registration.py:300)")
+        fail(what, "GMF-DGR only uses knn = 1 (deep_global_registration.py:300)", NotImplementedError)
     idx32, _, off0, _ = _match_batched(F0, F1, len_batch, 1 if nn_max_n > 1 else 2, False, what)
     rows = torch.arange(idx32.shape[0], device=idx32.device)
     starts = torch.repeat_interleave(torch.tensor(off0[:-1], device=idx32.device),

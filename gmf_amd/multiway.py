@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import c_ints, check_offsets, fail, positive_finite, require_device, same_device
 from ._util import handle_and_stream
 from .common import rigid_transform_3d
 from .features import voxel_down_sample_batched
@@ -35,59 +36,41 @@ DEFAULT_CRITERIA = dict(max_iteration=100, max_iteration_lm=20, min_relative_inc
                         min_right_term=1e-6, min_residual=1e-6)
 
 
-def _fail(what, msg):
-    raise RuntimeError(f"gmf_amd.{what}: {msg}")
-
-
 def _host_ints(x, name, what):
     """A host list of ints from a list, a NumPy array or a CPU tensor."""
     if isinstance(x, torch.Tensor):
         if x.is_cuda:
-            _fail(what, f"`{name}` is host data (a list, a NumPy array or a CPU tensor): the call plans its work from it")
+            fail(what, f"`{name}` is host data (a list, a NumPy array or a CPU tensor): the call plans its work from it")
         x = x.tolist()
     elif isinstance(x, np.ndarray):
         x = x.tolist()
     try:
         out = [int(v) for v in x]
     except (TypeError, ValueError):
-        _fail(what, f"`{name}` must be a sequence of integers")
+        fail(what, f"`{name}` must be a sequence of integers")
     return out
-
-
-def _c_ints(v):
-    return (ctypes.c_int * max(1, len(v)))(*v)
-
-
-def _require_device(x, name, what):
-    if not isinstance(x, torch.Tensor):
-        _fail(what, f"`{name}` must be a torch tensor")
-    if not x.is_cuda:
-        _fail(what, f"`{name}` must live on a HIP device (got {x.device}); the HIP path is mandatory, there is no CPU fallback")
 
 
 def _check_clouds(points, cloud_offsets, what):
     if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3 or points.shape[0] == 0:
-        _fail(what, "`points` must be a non-empty [sum N, 3] tensor")
+        fail(what, "`points` must be a non-empty [sum N, 3] tensor")
     if points.dtype != torch.float32:
-        _fail(what, f"`points` must be float32 (got {points.dtype})")
-    off = _host_ints(cloud_offsets, "cloud_offsets", what)
-    if len(off) < 2 or off[0] != 0 or off[-1] != points.shape[0] or any(b <= a for a, b in zip(off, off[1:])):
-        _fail(what, "cloud_offsets must increase strictly from 0 to the number of rows (no empty cloud)")
-    return off
+        fail(what, f"`points` must be float32 (got {points.dtype})")
+    return check_offsets(what, "cloud_offsets", _host_ints(cloud_offsets, "cloud_offsets", what), points.shape[0])
 
 
 def _check_edges(edge_source, edge_target, n, what, which="cloud"):
     src, tgt = _host_ints(edge_source, "edge_source", what), _host_ints(edge_target, "edge_target", what)
     if len(src) != len(tgt):
-        _fail(what, "edge_source and edge_target must have the same length")
+        fail(what, "edge_source and edge_target must have the same length")
     if any(not 0 <= v < n for v in src + tgt):
-        _fail(what, f"an edge names a {which} outside 0..{n - 1}")
+        fail(what, f"an edge names a {which} outside 0..{n - 1}")
     return src, tgt
 
 
 def _check_transformations(T, E, name, what):
     if not isinstance(T, torch.Tensor) or T.dtype not in (torch.float32, torch.float64) or tuple(T.shape) != (E, 4, 4):
-        _fail(what, f"`{name}` must be a float32 or float64 [{E}, 4, 4] tensor")
+        fail(what, f"`{name}` must be a float32 or float64 [{E}, 4, 4] tensor")
 
 
 def information_matrix_batched(points, cloud_offsets, edge_source, edge_target, transformation, max_correspondence_distance,
@@ -111,13 +94,10 @@ def information_matrix_batched(points, cloud_offsets, edge_source, edge_target, 
     src, tgt = _check_edges(edge_source, edge_target, F, what)
     E = len(src)
     _check_transformations(transformation, E, "transformation", what)
-    tau = float(max_correspondence_distance)
-    if not (tau > 0 and np.isfinite(tau)):
-        _fail(what, f"max_correspondence_distance must be > 0 (got {max_correspondence_distance})")
-    _require_device(points, "points", what)
-    _require_device(transformation, "transformation", what)
-    if transformation.device != points.device:
-        _fail(what, "points and transformation must live on the same device")
+    tau = positive_finite(what, "max_correspondence_distance", max_correspondence_distance, rule="> 0")
+    require_device(points, "points", what)
+    require_device(transformation, "transformation", what)
+    same_device(what, points=points, transformation=transformation)
     dev = points.device
     P = points.contiguous()
     T = transformation.to(torch.float64).contiguous()
@@ -127,7 +107,7 @@ def information_matrix_batched(points, cloud_offsets, edge_source, edge_target, 
     nn = torch.empty(rows, device=dev, dtype=torch.int64) if return_nn else None
     if E:
         h, st = handle_and_stream(P)
-        h.call("gmf_information_matrix", P.data_ptr(), _c_ints(off), F, _c_ints(src), _c_ints(tgt), E, T.data_ptr(), tau,
+        h.call("gmf_information_matrix", P.data_ptr(), c_ints(off), F, c_ints(src), c_ints(tgt), E, T.data_ptr(), tau,
                info.data_ptr(), count.data_ptr(), nn.data_ptr() if return_nn and rows else None, st)
     return (info, count, nn) if return_nn else (info, count)
 
@@ -153,20 +133,20 @@ def global_optimization(poses, edge_source, edge_target, edge_transformation, ed
     what = "global_optimization"
     if not isinstance(poses, torch.Tensor) or poses.dim() != 3 or poses.shape[1:] != (4, 4) or poses.shape[0] == 0 \
             or poses.dtype not in (torch.float32, torch.float64):
-        _fail(what, "`poses` must be a non-empty float64 or float32 [n, 4, 4] tensor")
+        fail(what, "`poses` must be a non-empty float64 or float32 [n, 4, 4] tensor")
     n = poses.shape[0]
     src, tgt = _host_ints(edge_source, "edge_source", what), _host_ints(edge_target, "edge_target", what)
     m = len(src)
     if len(tgt) != m:
-        _fail(what, "edge_source and edge_target must have the same length")
+        fail(what, "edge_source and edge_target must have the same length")
     if (node_offsets is None) != (edge_offsets is None):
-        _fail(what, "give both node_offsets and edge_offsets, or neither")
+        fail(what, "give both node_offsets and edge_offsets, or neither")
     noff = [0, n] if node_offsets is None else _host_ints(node_offsets, "node_offsets", what)
     eoff = [0, m] if edge_offsets is None else _host_ints(edge_offsets, "edge_offsets", what)
     G = len(noff) - 1
     if G < 1 or len(eoff) != G + 1 or noff[0] != 0 or eoff[0] != 0 or noff[-1] != n or eoff[-1] != m \
             or any(b <= a for a, b in zip(noff, noff[1:])) or any(b < a for a, b in zip(eoff, eoff[1:])):
-        _fail(what, "node_offsets must increase strictly from 0 to n and edge_offsets must not decrease from 0 to m, G + 1 entries each")
+        fail(what, "node_offsets must increase strictly from 0 to n and edge_offsets must not decrease from 0 to m, G + 1 entries each")
     for g in range(G):
         ng, mg = noff[g + 1] - noff[g], eoff[g + 1] - eoff[g]
         if ng > MAX_NODES or mg > MAX_EDGES:
@@ -174,32 +154,32 @@ def global_optimization(poses, edge_source, edge_target, edge_transformation, ed
                                       f"{MAX_NODES} nodes and {MAX_EDGES} edges per graph")
         for k in range(eoff[g], eoff[g + 1]):
             if not (0 <= src[k] < ng and 0 <= tgt[k] < ng):
-                _fail(what, f"edge {k} names a node outside its graph (0..{ng - 1})")
+                fail(what, f"edge {k} names a node outside its graph (0..{ng - 1})")
             if src[k] == tgt[k]:
-                _fail(what, f"edge {k} joins node {src[k]} to itself")
+                fail(what, f"edge {k} joins node {src[k]} to itself")
     _check_transformations(edge_transformation, m, "edge_transformation", what)
     if not isinstance(edge_information, torch.Tensor) or tuple(edge_information.shape) != (m, 6, 6) \
             or edge_information.dtype not in (torch.float32, torch.float64):
-        _fail(what, f"`edge_information` must be a float64 or float32 [{m}, 6, 6] tensor")
+        fail(what, f"`edge_information` must be a float64 or float32 [{m}, 6, 6] tensor")
     for name, x in (("edge_uncertain", edge_uncertain),) + ((("edge_mask", edge_mask),) if edge_mask is not None else ()):
         if not isinstance(x, torch.Tensor) or x.dtype != torch.bool or tuple(x.shape) != (m,):
-            _fail(what, f"`{name}` must be a bool [{m}] tensor")
+            fail(what, f"`{name}` must be a bool [{m}] tensor")
     crit = dict(DEFAULT_CRITERIA)
     for k, v in (criteria or {}).items():
         if k not in crit:
-            _fail(what, f"unknown criterion {k!r} (known: {sorted(crit)})")
+            fail(what, f"unknown criterion {k!r} (known: {sorted(crit)})")
         crit[k] = v
     if not (0 <= int(crit["max_iteration"]) <= 100000 and 0 <= int(crit["max_iteration_lm"]) <= 100000):
-        _fail(what, "max_iteration and max_iteration_lm must be in 0..100000")
+        fail(what, "max_iteration and max_iteration_lm must be in 0..100000")
     p = float(preference_loop_closure)
     if not (p > 0 and np.isfinite(p)):
-        _fail(what, "preference_loop_closure must be > 0")
+        fail(what, "preference_loop_closure must be > 0")
     tensors = [("poses", poses), ("edge_transformation", edge_transformation), ("edge_information", edge_information),
                ("edge_uncertain", edge_uncertain)] + ([("edge_mask", edge_mask)] if edge_mask is not None else [])
     for name, x in tensors:
-        _require_device(x, name, what)
+        require_device(x, name, what)
         if x.device != poses.device:
-            _fail(what, "every tensor must live on the same device")
+            fail(what, "every tensor must live on the same device")
     dev = poses.device
     P = poses.to(torch.float64).contiguous().clone()
     X = edge_transformation.to(torch.float64).contiguous()
@@ -215,7 +195,7 @@ def global_optimization(poses, edge_source, edge_target, edge_transformation, ed
                                 float(crit["min_relative_increment"]), float(crit["min_relative_residual_increment"]),
                                 float(crit["min_right_term"]), float(crit["min_residual"]), float(edge_prune_threshold), p)
     h, st = handle_and_stream(P)
-    h.call("gmf_posegraph_optimize", P.data_ptr(), _c_ints(noff), _c_ints(eoff), G, _c_ints(src), _c_ints(tgt),
+    h.call("gmf_posegraph_optimize", P.data_ptr(), c_ints(noff), c_ints(eoff), G, c_ints(src), c_ints(tgt),
            X.data_ptr() if m else None, L.data_ptr() if m else None, unc.data_ptr() if m else None,
            mask.data_ptr() if (mask is not None and m) else None, ctypes.byref(opt), lp.data_ptr() if m else None,
            kept.data_ptr() if m else None, st_i.data_ptr(), resid.data_ptr(), tr.data_ptr() if trace else None, st)
@@ -293,9 +273,9 @@ def local_refinement_batched(points, cloud_offsets, edge_source, edge_target, in
     E = len(src)
     _check_transformations(init, E, "init", what)
     if len(voxel_size) != len(max_iter) or not len(max_iter):
-        _fail(what, "voxel_size and max_iter must have the same, non-zero length")
-    _require_device(points, "points", what)
-    _require_device(init, "init", what)
+        fail(what, "voxel_size and max_iter must have the same, non-zero length")
+    require_device(points, "points", what)
+    require_device(init, "init", what)
     dev = points.device
     T = init.to(torch.float32).contiguous()
     info = torch.zeros((E, 6, 6), device=dev, dtype=torch.float64)
@@ -353,11 +333,11 @@ def multiway_registration(points, cloud_offsets, pair_source, pair_target, pair_
                                   f"{MAX_EDGES} edges")
     odo = {s: e for e, (s, t) in enumerate(zip(src, tgt)) if t == s + 1}
     if any(i not in odo for i in range(F - 1)):
-        _fail(what, "every consecutive pair (i, i + 1) must be among the pairs: they are the odometry edges")
+        fail(what, "every consecutive pair (i, i + 1) must be among the pairs: they are the odometry edges")
     if any(s == t for s, t in zip(src, tgt)):
-        _fail(what, "a pair joins a fragment to itself")
-    _require_device(points, "points", what)
-    _require_device(pair_transformation, "pair_transformation", what)
+        fail(what, "a pair joins a fragment to itself")
+    require_device(points, "points", what)
+    require_device(pair_transformation, "pair_transformation", what)
     dev = points.device
     odo_e = [odo[i] for i in range(F - 1)]
     odo_idx = torch.tensor(odo_e, device=dev, dtype=torch.long)

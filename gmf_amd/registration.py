@@ -6,70 +6,8 @@ from typing import Sequence
 
 import torch
 
+from ._args import device_offsets, fail
 from ._util import handle_and_stream, require_cuda_f32
-
-
-import collections
-import os
-import threading
-
-# (device, ints) -> [int32 device tensor, largest problem (offset lists), pinned source, event]: an LRU of the 64 most recent offset lists behind a lock (callers on
-# several threads share it).  Evaluation loops that repeat a handful of shapes hit it; a loop whose offsets change on every
-# call pays the upload each time - through a pinned staging buffer and an asynchronous copy, not a pageable synchronous one.
-_OFFSETS_CACHE: "collections.OrderedDict" = collections.OrderedDict()
-_OFFSETS_LOCK = threading.Lock()
-_OFFSETS_CAP = 64
-
-
-def _cached_upload(values: tuple, device):
-    """The cache entry [int32 device tensor, slot for the caller's derived figure, pinned source, event] of a tuple of ints:
-    uploaded once per (device, tuple) through a pinned buffer, asynchronously on the current stream, and kept."""
-    key = (device, values)
-    with _OFFSETS_LOCK:
-        hit = _OFFSETS_CACHE.get(key)
-        if hit is not None:
-            _OFFSETS_CACHE.move_to_end(key)
-            if hit[3] is not None:                   # the upload may still be in flight on ANOTHER stream: order this one behind it
-                # (an event may not be queried while a stream captures a graph; waiting on it there is legal)
-                if not torch.cuda.is_current_stream_capturing() and hit[3].query():
-                    hit[3] = None
-                else:
-                    torch.cuda.current_stream(device).wait_event(hit[3])
-            return hit
-    # not cached: a pinned host copy and an asynchronous upload on the current stream (ordered before the solve that follows)
-    host = torch.tensor(values, dtype=torch.int32).pin_memory()
-    dev = host.to(device, non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record(torch.cuda.current_stream(device))
-    entry = [dev, None, host, ev]                    # (the pinned source lives as long as the entry)
-    with _OFFSETS_LOCK:
-        _OFFSETS_CACHE[key] = entry
-        while len(_OFFSETS_CACHE) > _OFFSETS_CAP:
-            _OFFSETS_CACHE.popitem(last=False)
-    return entry
-
-
-def _device_offsets(offsets, n_rows: int, device, what: str, allow_empty: bool = False):
-    """The row offsets of a ragged batch as an int32 device tensor, and the largest problem.  A Python sequence is checked
-    here (increasing, from 0 to n_rows; allow_empty: not decreasing) without a device round trip and its device copy is kept for
-    the next call with the same offsets (a list met for the first time travels through a pinned buffer, asynchronously); an int32
-    tensor already on the device is taken as it is (the caller vouches for it: only its end is not read back)."""
-    if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
-        if offsets.dtype != torch.int32 or offsets.dim() != 1 or offsets.numel() < 2 or not offsets.is_contiguous() \
-                or offsets.device != device:
-            raise RuntimeError(f"gmf_amd.{what}: device offsets must be a contiguous int32 vector of B + 1 entries on the points' device")
-        if os.environ.get("GMF_DEBUG_OFFSETS"):          # (debugging aid: one device read-back of the whole vector)
-            off_h = offsets.cpu().tolist()
-            if off_h[0] != 0 or off_h[-1] != n_rows or any(b < a or (b == a and not allow_empty) for a, b in zip(off_h, off_h[1:])):
-                raise RuntimeError(f"gmf_amd.{what}: device offsets must be increasing, start at 0 and end at N")
-        return offsets, n_rows
-    off = tuple(int(o) for o in offsets)
-    if len(off) < 2 or off[0] != 0 or off[-1] != n_rows or any(b < a or (b == a and not allow_empty) for a, b in zip(off, off[1:])):
-        raise RuntimeError(f"gmf_amd.{what}: offsets must be increasing, start at 0 and end at N")
-    entry = _cached_upload(off, device)
-    if entry[1] is None:
-        entry[1] = max(b - a for a, b in zip(off, off[1:]))
-    return entry[0], entry[1]
 
 
 class _WeightedProcrustes(torch.autograd.Function):
@@ -110,10 +48,10 @@ def weighted_procrustes_batched(X, Y, w, offsets: Sequence[int], eps):
     Y = require_cuda_f32(Y, "Y").contiguous()
     w = require_cuda_f32(w, "w").contiguous().reshape(-1)
     if X.shape != Y.shape or X.dim() != 2 or X.shape[1] != 3 or w.numel() != X.shape[0]:
-        raise RuntimeError("gmf_amd.weighted_procrustes: expected X,Y [N,3] and w [N]")
+        fail("weighted_procrustes", "expected X,Y [N,3] and w [N]")
     if torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad):
-        raise RuntimeError("gmf_amd.weighted_procrustes: gradients with respect to X / Y are not implemented (only w)")
-    off, _ = _device_offsets(offsets, X.shape[0], X.device, "weighted_procrustes")
+        fail("weighted_procrustes", "gradients with respect to X / Y are not implemented (only w)")
+    off, _ = device_offsets(offsets, X.shape[0], X.device, "weighted_procrustes")
     if not (torch.is_grad_enabled() and w.requires_grad):
         return _WeightedProcrustes.forward(None, w, X, Y, off, eps)
     return _WeightedProcrustes.apply(w, X.detach(), Y.detach(), off, eps)
@@ -139,13 +77,13 @@ def global_registration_batched(points, trans_points, weights, offsets: Sequence
     X = require_cuda_f32(points, "points").contiguous()
     Y = require_cuda_f32(trans_points, "trans_points").contiguous()
     if X.shape != Y.shape or X.dim() != 2 or X.shape[1] != 3:
-        raise RuntimeError("gmf_amd.GlobalRegistration: expected points, trans_points [N,3]")
+        fail("GlobalRegistration", "expected points, trans_points [N,3]")
     w = None
     if weights is not None:
         w = require_cuda_f32(weights, "weights").contiguous().reshape(-1)
         if w.numel() != X.shape[0]:
-            raise RuntimeError("gmf_amd.GlobalRegistration: weights must hold one value per point")
-    off, max_points = _device_offsets(offsets, X.shape[0], X.device, "GlobalRegistration")
+            fail("GlobalRegistration", "weights must hold one value per point")
+    off, max_points = device_offsets(offsets, X.shape[0], X.device, "GlobalRegistration")
     B = off.numel() - 1
     R = torch.empty((B, 3, 3), device=X.device, dtype=torch.float32)
     t = torch.empty((B, 3), device=X.device, dtype=torch.float32)
@@ -166,7 +104,7 @@ def GlobalRegistration(points, trans_points, weights=None, max_iter=1000, verbos
     callers never pass one) and raises."""
     import numpy as np
     if loss_fn is not None:
-        raise NotImplementedError("gmf_amd.GlobalRegistration: only the default HighDimSmoothL1Loss is implemented")
+        fail("GlobalRegistration", "only the default HighDimSmoothL1Loss is implemented", NotImplementedError)
     dev = None
     for v in (points, trans_points, weights):
         if isinstance(v, torch.Tensor) and v.is_cuda:

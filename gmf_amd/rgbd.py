@@ -14,10 +14,10 @@ import ctypes as C
 import numpy as np
 import torch
 
+from ._args import cached_upload, fail, positive_finite, require_device
 from ._util import handle_and_stream
-from .fragments import _positive, tsdf_fragments, tsdf_fragments_colored
+from .fragments import tsdf_fragments, tsdf_fragments_colored
 from .multiway import global_optimization, odometry_poses
-from .spectral import _fail
 
 MAX_LEVELS = 8
 PLANES = ("I", "D", "Idx", "Idy", "Ddx", "Ddy")
@@ -28,14 +28,10 @@ def _intrinsic(what, intrinsic):
     try:
         fx, fy, cx, cy = (float(v) for v in intrinsic)
     except (TypeError, ValueError):
-        _fail(what, f"intrinsic must be four numbers (fx, fy, cx, cy) (got {intrinsic!r})")
+        fail(what, f"intrinsic must be four numbers (fx, fy, cx, cy) (got {intrinsic!r})")
     if not (np.isfinite([fx, fy, cx, cy]).all() and fx > 0 and fy > 0):
-        _fail(what, f"intrinsic must be finite with fx, fy > 0 (got {intrinsic!r})")
+        fail(what, f"intrinsic must be finite with fx, fy > 0 (got {intrinsic!r})")
     return fx, fy, cx, cy
-
-
-def _upload_ints(values, dev):
-    return torch.tensor(values, dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
 
 
 class RGBDPyramids:
@@ -57,7 +53,7 @@ class RGBDPyramids:
 
     def planes(self, level):
         if not isinstance(level, (int, np.integer)) or not 0 <= level < self.levels:
-            _fail("rgbd_pyramids", f"level must be an integer in 0..{self.levels - 1} (got {level!r})")
+            fail("rgbd_pyramids", f"level must be an integer in 0..{self.levels - 1} (got {level!r})")
         return self._views[level]
 
 
@@ -73,36 +69,35 @@ def rgbd_pyramids(color, depth, depth_scale=1000.0, depth_trunc=3.0, min_depth=0
     what = "rgbd_pyramids"
     for name, x in (("color", color), ("depth", depth)):
         if not isinstance(x, torch.Tensor):
-            _fail(what, f"`{name}` must be a torch tensor")
+            fail(what, f"`{name}` must be a torch tensor")
     if depth.dtype not in (torch.uint16, torch.float32):
-        _fail(what, f"`depth` must be uint16 (sensor values) or float32 (metres) (got {depth.dtype})")
+        fail(what, f"`depth` must be uint16 (sensor values) or float32 (metres) (got {depth.dtype})")
     if depth.dim() != 3 or min(depth.shape) < 1:
-        _fail(what, f"`depth` must be a non-empty [F,H,W] tensor (got {tuple(depth.shape)})")
+        fail(what, f"`depth` must be a non-empty [F,H,W] tensor (got {tuple(depth.shape)})")
     F, H, W = depth.shape
     if color.dtype == torch.uint8 and color.dim() == 4 and tuple(color.shape) == (F, H, W, 3):
         kind = 1
     elif color.dtype in (torch.uint8, torch.float32) and tuple(color.shape) == (F, H, W):
         kind = 0 if color.dtype == torch.uint8 else 2
     else:
-        _fail(what, f"`color` must be [F,H,W] uint8, [F,H,W,3] uint8 or [F,H,W] float32 with depth's F, H, W = {F}, {H}, {W} "
-                    f"(got {tuple(color.shape)} {color.dtype})")
+        fail(what, f"`color` must be [F,H,W] uint8, [F,H,W,3] uint8 or [F,H,W] float32 with depth's F, H, W = {F}, {H}, {W} "
+                   f"(got {tuple(color.shape)} {color.dtype})")
     if 6 * F * H * W >= 2 ** 31:
-        _fail(what, f"the frames must hold fewer than 2^31 / 6 pixels (got {F * H * W})")
-    scale = _positive(what, "depth_scale", depth_scale)
-    far = _positive(what, "depth_trunc", depth_trunc, allow_inf=True)
+        fail(what, f"the frames must hold fewer than 2^31 / 6 pixels (got {F * H * W})")
+    scale = positive_finite(what, "depth_scale", depth_scale, numeric=True)
+    far = positive_finite(what, "depth_trunc", depth_trunc, allow_inf=True, numeric=True)
     try:
         lo, hi = float(min_depth), float(max_depth)
     except (TypeError, ValueError):
-        _fail(what, f"min_depth and max_depth must be numbers (got {min_depth!r}, {max_depth!r})")
+        fail(what, f"min_depth and max_depth must be numbers (got {min_depth!r}, {max_depth!r})")
     if not (np.isfinite(lo) and lo >= 0 and hi > lo):
-        _fail(what, f"min_depth must be finite and >= 0 and max_depth above it (got {min_depth}, {max_depth})")
+        fail(what, f"min_depth must be finite and >= 0 and max_depth above it (got {min_depth}, {max_depth})")
     if not isinstance(levels, (int, np.integer)) or not 1 <= levels <= MAX_LEVELS or (H >> (levels - 1)) < 1 or (W >> (levels - 1)) < 1:
-        _fail(what, f"levels must be an integer in 1..{MAX_LEVELS} that leaves the coarsest level a pixel (got {levels!r})")
-    if not depth.is_cuda or not color.is_cuda:
-        _fail(what, f"`color` and `depth` must live on a HIP device (got {color.device}, {depth.device}); the HIP path is "
-                    "mandatory, there is no CPU fallback")
+        fail(what, f"levels must be an integer in 1..{MAX_LEVELS} that leaves the coarsest level a pixel (got {levels!r})")
+    require_device(color, "color", what)
+    require_device(depth, "depth", what)
     if color.device != depth.device:
-        _fail(what, "`color` and `depth` must live on the same device")
+        fail(what, "`color` and `depth` must live on the same device")
     levels = int(levels)
     col, dep = color.contiguous(), depth.contiguous()
     total = sum(F * 6 * (H >> l) * (W >> l) for l in range(levels))
@@ -115,43 +110,41 @@ def rgbd_pyramids(color, depth, depth_scale=1000.0, depth_trunc=3.0, min_depth=0
 
 def _pairs(what, pyr, pair_source, pair_target):
     if not isinstance(pyr, RGBDPyramids):
-        _fail(what, "`pyr` must be what rgbd_pyramids returned")
+        fail(what, "`pyr` must be what rgbd_pyramids returned")
     lists = []
     for name, x in (("pair_source", pair_source), ("pair_target", pair_target)):
         if isinstance(x, torch.Tensor) and x.is_cuda:
-            _fail(what, f"`{name}` is host data (a list, a NumPy array or a CPU tensor): the call plans its work from it")
+            fail(what, f"`{name}` is host data (a list, a NumPy array or a CPU tensor): the call plans its work from it")
         try:
             seq = x.tolist() if isinstance(x, (torch.Tensor, np.ndarray)) else list(x)
             v = [int(o) for o in seq]
             if any(a != b for a, b in zip(v, seq)):
                 raise ValueError
         except (TypeError, ValueError):
-            _fail(what, f"`{name}` must be a sequence of integers")
+            fail(what, f"`{name}` must be a sequence of integers")
         lists.append(v)
     src, tgt = lists
     if len(src) != len(tgt):
-        _fail(what, "pair_source and pair_target must have the same length")
+        fail(what, "pair_source and pair_target must have the same length")
     for e, (s, t) in enumerate(zip(src, tgt)):
         if not (0 <= s < pyr.frames and 0 <= t < pyr.frames):
-            _fail(what, f"pair {e} names a frame outside 0..{pyr.frames - 1}")
+            fail(what, f"pair {e} names a frame outside 0..{pyr.frames - 1}")
     if len(src) >= 1 << 24:
-        _fail(what, f"a call holds fewer than 2^24 pairs (got {len(src)})")
+        fail(what, f"a call holds fewer than 2^24 pairs (got {len(src)})")
     return src, tgt
 
 
 def _poses(what, name, T, E, dev):
     if not isinstance(T, torch.Tensor) or T.dtype != torch.float64 or tuple(T.shape) != (E, 4, 4):
-        _fail(what, f"`{name}` must be a float64 [{E}, 4, 4] tensor")
-    if not T.is_cuda:
-        _fail(what, f"`{name}` must live on a HIP device (got {T.device}); the HIP path is mandatory, there is no CPU fallback")
+        fail(what, f"`{name}` must be a float64 [{E}, 4, 4] tensor")
+    require_device(T, name, what)
     if T.device != dev:
-        _fail(what, f"`{name}` must live on the device of the pyramids")
+        fail(what, f"`{name}` must live on the device of the pyramids")
     return T.contiguous()
 
 
 def _on_device(what, pyr):
-    if not pyr.device.type == "cuda":
-        _fail(what, f"the pyramids must live on a HIP device (got {pyr.device}); the HIP path is mandatory, there is no CPU fallback")
+    require_device(pyr.device, "the pyramids", what)
     return pyr.device
 
 
@@ -159,9 +152,9 @@ def _depth_diff(what, v):
     try:
         f = float(v)
     except (TypeError, ValueError):
-        _fail(what, f"max_depth_diff must be a number (got {v!r})")
+        fail(what, f"max_depth_diff must be a number (got {v!r})")
     if not (np.isfinite(f) and f >= 0):
-        _fail(what, f"max_depth_diff must be finite and >= 0 (got {v})")
+        fail(what, f"max_depth_diff must be finite and >= 0 (got {v})")
     return f
 
 
@@ -174,7 +167,7 @@ def rgbd_correspondence_map(pyr, pair_source, pair_target, transformation, intri
     E = len(src)
     K = _intrinsic(what, intrinsic)
     if not isinstance(level, (int, np.integer)) or not 0 <= level < pyr.levels:
-        _fail(what, f"level must be an integer in 0..{pyr.levels - 1} (got {level!r})")
+        fail(what, f"level must be an integer in 0..{pyr.levels - 1} (got {level!r})")
     mdd = _depth_diff(what, max_depth_diff)
     T = _poses(what, "transformation", transformation, E, pyr.device)
     dev = _on_device(what, pyr)
@@ -182,7 +175,7 @@ def rgbd_correspondence_map(pyr, pair_source, pair_target, transformation, intri
     if E == 0:
         return out
     h, st = handle_and_stream(pyr._buffer)
-    pairs = _upload_ints([src, tgt], dev)
+    pairs = cached_upload((tuple(src), tuple(tgt)), dev)[0]
     h.call("gmf_rgbd_correspondences", pyr._buffer.data_ptr(), pyr.frames, pyr.height, pyr.width, pyr.levels, int(level),
            pairs[0].data_ptr(), pairs[1].data_ptr(), E, T.data_ptr(), *K, mdd, out.data_ptr(), st)
     return out
@@ -209,26 +202,26 @@ def rgbd_odometry(pyr_or_color, depth=None, pair_source=(), pair_target=(), intr
         if any(a != b for a, b in zip(its, iterations)) or not its or min(its) < 0 or max(its) > 10000:
             raise ValueError
     except (TypeError, ValueError):
-        _fail(what, f"iterations must be a sequence of integers in 0..10000, one per level (got {iterations!r})")
+        fail(what, f"iterations must be a sequence of integers in 0..10000, one per level (got {iterations!r})")
     K = _intrinsic(what, intrinsic)
     mdd = _depth_diff(what, max_depth_diff)
     if isinstance(pyr_or_color, RGBDPyramids):
         if depth is not None or pyramid_args:
-            _fail(what, "with pyramids, `depth` and the pyramid arguments are not taken: they went into rgbd_pyramids")
+            fail(what, "with pyramids, `depth` and the pyramid arguments are not taken: they went into rgbd_pyramids")
         pyr = pyr_or_color
     else:
         if depth is None:
-            _fail(what, "give what rgbd_pyramids returned, or colour frames and `depth`")
+            fail(what, "give what rgbd_pyramids returned, or colour frames and `depth`")
         unknown = set(pyramid_args) - {"depth_scale", "depth_trunc", "min_depth", "max_depth", "levels"}
         if unknown:
-            _fail(what, f"unknown argument {sorted(unknown)[0]!r}")
+            fail(what, f"unknown argument {sorted(unknown)[0]!r}")
         pyramid_args.setdefault("levels", len(its))
         try:
             pyr = rgbd_pyramids(pyr_or_color, depth, **pyramid_args)
         except RuntimeError as err:
             raise RuntimeError(str(err).replace("gmf_amd.rgbd_pyramids", f"gmf_amd.{what}", 1)) from None
     if len(its) != pyr.levels:
-        _fail(what, f"iterations must have one entry per level: {pyr.levels} (got {len(its)})")
+        fail(what, f"iterations must have one entry per level: {pyr.levels} (got {len(its)})")
     src, tgt = _pairs(what, pyr, pair_source, pair_target)
     E, N = len(src), sum(its)
     init = None if odo_init is None else _poses(what, "odo_init", odo_init, E, pyr.device)
@@ -242,7 +235,7 @@ def rgbd_odometry(pyr_or_color, depth=None, pair_source=(), pair_target=(), intr
         td = torch.full((E, N, _TRACE), float("nan"), device=dev, dtype=torch.float64)
     if E:
         h, st = handle_and_stream(pyr._buffer)
-        pairs = _upload_ints([src, tgt], dev)
+        pairs = cached_upload((tuple(src), tuple(tgt)), dev)[0]
         h.call("gmf_rgbd_odometry", pyr._buffer.data_ptr(), pyr.frames, pyr.height, pyr.width, pyr.levels,
                pairs[0].data_ptr(), pairs[1].data_ptr(), E, init.data_ptr() if init is not None else None,
                *K, mdd, (C.c_int * len(its))(*its), success.data_ptr(), T.data_ptr(), info.data_ptr(),
@@ -270,34 +263,34 @@ def rgbd_fragments(color, depth, intrinsic, frame_offsets=None, max_depth_diff=0
     what = "rgbd_fragments"
     unknown = set(tsdf_args) - {"voxel_length", "sdf_trunc", "depth_scale", "depth_trunc", "depth_sampling_stride", "max_units", "return_volume", "colors"}
     if unknown:
-        _fail(what, f"unknown argument {sorted(unknown)[0]!r}")
+        fail(what, f"unknown argument {sorted(unknown)[0]!r}")
     tsdf_args = dict(tsdf_args)
     colors = tsdf_args.pop("colors", False)
     if not isinstance(colors, (bool, np.bool_)):
-        _fail(what, f"colors must be True or False (got {colors!r})")
+        fail(what, f"colors must be True or False (got {colors!r})")
     if colors and not (isinstance(color, torch.Tensor) and color.dtype == torch.uint8 and color.dim() == 4 and color.shape[-1] == 3):
         got = f"{tuple(color.shape)} {color.dtype}" if isinstance(color, torch.Tensor) else type(color).__name__
-        _fail(what, f"colors=True needs `color` as [F,H,W,3] uint8: a grey frame has no R, G, B to fuse (got {got})")
+        fail(what, f"colors=True needs `color` as [F,H,W,3] uint8: a grey frame has no R, G, B to fuse (got {got})")
     if not isinstance(depth, torch.Tensor) or depth.dim() != 3:
-        _fail(what, "`depth` must be a [F,H,W] torch tensor")
+        fail(what, "`depth` must be a [F,H,W] torch tensor")
     F = depth.shape[0]
     if frame_offsets is None:
         off = [0, F]
     else:
         if isinstance(frame_offsets, torch.Tensor) and frame_offsets.is_cuda:
-            _fail(what, "frame_offsets must be G + 1 host integers (they size the call)")
+            fail(what, "frame_offsets must be G + 1 host integers (they size the call)")
         try:
             seq = frame_offsets.tolist() if isinstance(frame_offsets, (torch.Tensor, np.ndarray)) else list(frame_offsets)
             off = [int(o) for o in seq]
             if any(o != s for o, s in zip(off, seq)):
                 raise ValueError
         except (TypeError, ValueError):
-            _fail(what, "frame_offsets must be G + 1 integers")
+            fail(what, "frame_offsets must be G + 1 integers")
         if len(off) < 2 or off[0] != 0 or off[-1] != F or any(b < a for a, b in zip(off, off[1:])):
-            _fail(what, "frame_offsets must not decrease, start at 0 and end at F")
+            fail(what, "frame_offsets must not decrease, start at 0 and end at F")
     p = float(preference_loop_closure) if isinstance(preference_loop_closure, (int, float, np.number)) else float("nan")
     if not (p > 0 and np.isfinite(p)):
-        _fail(what, f"preference_loop_closure must be finite and > 0 (got {preference_loop_closure!r})")
+        fail(what, f"preference_loop_closure must be finite and > 0 (got {preference_loop_closure!r})")
     K = _intrinsic(what, intrinsic)
     _depth_diff(what, max_depth_diff)
     src = [i for a, b in zip(off, off[1:]) for i in range(a, b - 1)]
@@ -307,8 +300,10 @@ def rgbd_fragments(color, depth, intrinsic, frame_offsets=None, max_depth_diff=0
     tsdf_args.setdefault("depth_trunc", 3.0)
     try:
         if F == 0:
-            if not isinstance(color, torch.Tensor) or not color.is_cuda or not depth.is_cuda:
-                _fail(what, "`color` and `depth` must live on a HIP device; the HIP path is mandatory, there is no CPU fallback")
+            if not isinstance(color, torch.Tensor):
+                fail(what, "`color` must be a torch tensor")
+            require_device(color, "color", what)
+            require_device(depth, "depth", what)
             dev = depth.device
             success = torch.zeros(0, device=dev, dtype=torch.bool)
             poses = torch.zeros((0, 4, 4), device=dev, dtype=torch.float64)
@@ -320,7 +315,7 @@ def rgbd_fragments(color, depth, intrinsic, frame_offsets=None, max_depth_diff=0
             if bad:
                 e = bad[0]
                 g = max(g for g in range(len(off) - 1) if off[g] <= src[e])
-                _fail(what, f"the odometry of frames {src[e]} -> {tgt[e]} (fragment {g}) failed: {len(bad)} of {len(src)} pairs did")
+                fail(what, f"the odometry of frames {src[e]} -> {tgt[e]} (fragment {g}) failed: {len(bad)} of {len(src)} pairs did")
             parts, e0 = [], 0
             for a, b in zip(off, off[1:]):
                 if b > a:

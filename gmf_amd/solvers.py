@@ -12,50 +12,16 @@ import collections
 import numpy as np
 import torch
 
+from . import _lib
+from ._args import (check_offsets, check_rows, device_offsets, fail, int_in_range, positive_finite, require_device, same_device,
+                    uniform_offsets)
 from ._util import handle_and_stream
-from .registration import _device_offsets
 
 RegistrationResult = collections.namedtuple("RegistrationResult", "transformation correspondence_set fitness inlier_rmse")
 
 _MAX_HYPOTHESES = 1 << 24
 _MAX_VALIDATION = 1 << 16
 _ICP_SEARCH = {"brute": 0, "grid": 1}
-
-
-def _fail(what, msg):
-    raise RuntimeError(f"gmf_amd.{what}: {msg}")
-
-
-def _check_points(x, name, what, dims):
-    if not isinstance(x, torch.Tensor):
-        _fail(what, f"`{name}` must be a torch tensor")
-    if x.dtype != torch.float32:
-        _fail(what, f"`{name}` must be float32 (got {x.dtype})")
-    if x.dim() != dims or x.shape[-1] != 3 or any(s == 0 for s in x.shape):
-        _fail(what, f"`{name}` must be a non-empty [{'B,N' if dims == 3 else 'sum N'},3] tensor (got {tuple(x.shape)})")
-
-
-def _check_offsets(offsets, n_rows, what):
-    """Host-side checks of an offset list (a device int32 tensor is checked by _device_offsets, as in registration.py)."""
-    if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
-        return offsets
-    off = offsets.tolist() if isinstance(offsets, (torch.Tensor, np.ndarray)) else list(offsets)
-    try:
-        off = [int(o) for o in off]
-    except (TypeError, ValueError):
-        _fail(what, "offsets must be B + 1 integers")
-    if len(off) < 2 or off[0] != 0 or off[-1] != n_rows or any(b <= a for a, b in zip(off, off[1:])):
-        _fail(what, "offsets must be increasing, start at 0 and end at N")
-    return off
-
-
-def _require_device(x, name, what):
-    if not x.is_cuda:
-        _fail(what, f"`{name}` must live on a HIP device (got {x.device}); the HIP path is mandatory, there is no CPU fallback")
-
-
-def _max_rows(off, n_rows):
-    return max(b - a for a, b in zip(off, off[1:])) if isinstance(off, list) else n_rows
 
 
 def ransac_correspondence_batched(src, tgt, max_correspondence_distance, offsets=None, mask=None, ransac_n=3,
@@ -74,34 +40,24 @@ def ransac_correspondence_batched(src, tgt, max_correspondence_distance, offsets
     rows, numbered within the pair)."""
     what = "ransac_correspondence_batched"
     dims = 3 if offsets is None else 2
-    _check_points(src, "src", what, dims)
-    _check_points(tgt, "tgt", what, dims)
+    check_rows(what, "src", src, dims, 3, non_empty=True)
+    check_rows(what, "tgt", tgt, dims, 3, non_empty=True)
     if src.shape != tgt.shape:
-        _fail(what, f"src and tgt must have the same shape (got {tuple(src.shape)} / {tuple(tgt.shape)})")
+        fail(what, f"src and tgt must have the same shape (got {tuple(src.shape)} / {tuple(tgt.shape)})")
     if mask is not None:
         if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.shape != src.shape[:-1]:
-            _fail(what, f"mask must be a bool tensor of shape {tuple(src.shape[:-1])}")
-    n = int(ransac_n)
-    if n != ransac_n or not 3 <= n <= 8:
-        _fail(what, f"ransac_n must be an integer in 3..8 (got {ransac_n})")
-    H = int(num_hypotheses)
-    if H != num_hypotheses or not 1 <= H <= _MAX_HYPOTHESES:
-        _fail(what, f"num_hypotheses must be an integer in 1..2**24 (got {num_hypotheses})")
-    tau = float(max_correspondence_distance)
-    if not (tau > 0 and np.isfinite(tau)):
-        _fail(what, f"max_correspondence_distance must be > 0 (got {max_correspondence_distance})")
+            fail(what, f"mask must be a bool tensor of shape {tuple(src.shape[:-1])}")
+    n = int_in_range(what, "ransac_n", ransac_n, 3, 8)
+    H = int_in_range(what, "num_hypotheses", num_hypotheses, 1, _MAX_HYPOTHESES, rule="in 1..2**24")
+    tau = positive_finite(what, "max_correspondence_distance", max_correspondence_distance, rule="> 0")
     if int(first_pair) < 0:
-        _fail(what, "first_pair must be >= 0")
+        fail(what, "first_pair must be >= 0")
     n_rows = src.shape[0] * src.shape[1] if dims == 3 else src.shape[0]
-    if dims == 3:
-        off = list(range(0, n_rows + 1, src.shape[1]))
-    else:
-        off = _check_offsets(offsets, n_rows, what)
-    _require_device(src, "src", what)
-    _require_device(tgt, "tgt", what)
-    if tgt.device != src.device or (mask is not None and mask.device != src.device):
-        _fail(what, "src, tgt and mask must live on the same device")
-    dev_off, _ = _device_offsets(off, n_rows, src.device, what)
+    off = uniform_offsets(*src.shape[:2]) if dims == 3 else check_offsets(what, "offsets", offsets, n_rows)
+    require_device(src, "src", what)
+    require_device(tgt, "tgt", what)
+    same_device(what, src=src, tgt=tgt, mask=mask)
+    dev_off, max_rows = device_offsets(off, n_rows, src.device, what, checked=True)
     B = dev_off.numel() - 1
     S = src.reshape(-1, 3).contiguous()
     Q = tgt.reshape(-1, 3).contiguous()
@@ -113,7 +69,7 @@ def ransac_correspondence_batched(src, tgt, max_correspondence_distance, offsets
     ids = torch.empty((B, 1 + n), device=dev, dtype=torch.int64)
     h, st = handle_and_stream(S)
     h.call("gmf_ransac_correspondence", S.data_ptr(), Q.data_ptr(), dev_off.data_ptr(), None if m is None else m.data_ptr(), B,
-           n_rows, _max_rows(off, n_rows), n, H, tau, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_pair), T.data_ptr(),
+           n_rows, max_rows, n, H, tau, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_pair), T.data_ptr(),
            inliers.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), ids.data_ptr(), ids.data_ptr() + 8 * B, st)
     # ids holds hypothesis [B] followed by sample [B, n] (one allocation)
     flat = ids.view(-1)
@@ -135,47 +91,41 @@ def icp_point_to_point_batched(source, target, init, max_correspondence_distance
     source's leading shape: the matched target row within the pair, -1 outside C)."""
     what = "icp_point_to_point_batched"
     if not isinstance(search, str) or search not in _ICP_SEARCH:
-        _fail(what, f'search must be "brute" or "grid" (got {search!r})')
+        fail(what, f'search must be "brute" or "grid" (got {search!r})')
     if (source_offsets is None) != (target_offsets is None):
-        _fail(what, "give both source_offsets and target_offsets, or neither")
+        fail(what, "give both source_offsets and target_offsets, or neither")
     dims = 3 if source_offsets is None else 2
-    _check_points(source, "source", what, dims)
-    _check_points(target, "target", what, dims)
+    check_rows(what, "source", source, dims, 3, non_empty=True)
+    check_rows(what, "target", target, dims, 3, non_empty=True)
     if dims == 3 and source.shape[0] != target.shape[0]:
-        _fail(what, f"source and target must hold the same number of pairs (got {source.shape[0]} / {target.shape[0]})")
+        fail(what, f"source and target must hold the same number of pairs (got {source.shape[0]} / {target.shape[0]})")
     if not isinstance(init, torch.Tensor) or init.dtype != torch.float32 or init.dim() != 3 or init.shape[1:] != (4, 4):
-        _fail(what, "init must be a float32 [B,4,4] tensor")
-    tau = float(max_correspondence_distance)
-    if not (tau > 0 and np.isfinite(tau)):
-        _fail(what, f"max_correspondence_distance must be > 0 (got {max_correspondence_distance})")
-    it = int(max_iteration)
-    if it != max_iteration or not 0 <= it <= 100000:
-        _fail(what, f"max_iteration must be an integer in 0..100000 (got {max_iteration})")
+        fail(what, "init must be a float32 [B,4,4] tensor")
+    tau = positive_finite(what, "max_correspondence_distance", max_correspondence_distance, rule="> 0")
+    it = int_in_range(what, "max_iteration", max_iteration, 0, 100000)
     rf, rr = float(relative_fitness), float(relative_rmse)
     if not (rf >= 0 and rr >= 0):
-        _fail(what, "relative_fitness and relative_rmse must be >= 0")
+        fail(what, "relative_fitness and relative_rmse must be >= 0")
     ns_rows = source.shape[0] * source.shape[1] if dims == 3 else source.shape[0]
     nt_rows = target.shape[0] * target.shape[1] if dims == 3 else target.shape[0]
     if dims == 3:
-        soff = list(range(0, ns_rows + 1, source.shape[1]))
-        toff = list(range(0, nt_rows + 1, target.shape[1]))
+        soff, toff = uniform_offsets(*source.shape[:2]), uniform_offsets(*target.shape[:2])
     else:
-        soff = _check_offsets(source_offsets, ns_rows, what)
-        toff = _check_offsets(target_offsets, nt_rows, what)
+        soff = check_offsets(what, "source_offsets", source_offsets, ns_rows)
+        toff = check_offsets(what, "target_offsets", target_offsets, nt_rows)
         if isinstance(soff, list) and isinstance(toff, list) and len(soff) != len(toff):
-            _fail(what, "source_offsets and target_offsets must describe the same number of pairs")
+            fail(what, "source_offsets and target_offsets must describe the same number of pairs")
     for x, name in ((source, "source"), (target, "target"), (init, "init")):
-        _require_device(x, name, what)
-    if target.device != source.device or init.device != source.device:
-        _fail(what, "source, target and init must live on the same device")
+        require_device(x, name, what)
+    same_device(what, source=source, target=target, init=init)
     dev = source.device
-    dso, _ = _device_offsets(soff, ns_rows, dev, what)
-    dto, _ = _device_offsets(toff, nt_rows, dev, what)
+    dso, max_s = device_offsets(soff, ns_rows, dev, what, checked=True)
+    dto, max_t = device_offsets(toff, nt_rows, dev, what, checked=True)
     B = dso.numel() - 1
     if dto.numel() != B + 1:
-        _fail(what, "source_offsets and target_offsets must describe the same number of pairs")
+        fail(what, "source_offsets and target_offsets must describe the same number of pairs")
     if init.shape[0] != B:
-        _fail(what, f"init must hold one [4,4] transformation per pair ({B}; got {init.shape[0]})")
+        fail(what, f"init must hold one [4,4] transformation per pair ({B}; got {init.shape[0]})")
     S = source.reshape(-1, 3).contiguous()
     Q = target.reshape(-1, 3).contiguous()
     T0 = init.contiguous()
@@ -184,34 +134,13 @@ def icp_point_to_point_batched(source, target, init, max_correspondence_distance
     iters = torch.empty(B, device=dev, dtype=torch.int32)
     nn = torch.empty(source.shape[:-1], device=dev, dtype=torch.int64)
     h, st = handle_and_stream(S)
-    args = (S.data_ptr(), dso.data_ptr(), Q.data_ptr(), dto.data_ptr(), B, ns_rows, _max_rows(soff, ns_rows),
-            _max_rows(toff, nt_rows), T0.data_ptr(), tau, it, rf, rr, T.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
-            iters.data_ptr(), nn.data_ptr())
+    args = (S.data_ptr(), dso.data_ptr(), Q.data_ptr(), dto.data_ptr(), B, ns_rows, max_s, max_t, T0.data_ptr(), tau, it, rf, rr,
+            T.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), iters.data_ptr(), nn.data_ptr())
     if search == "brute":
         h.call("gmf_icp_point_to_point", *args, st)
     else:
         h.call("gmf_icp_point_to_point_ex", *args, nt_rows, _ICP_SEARCH[search], st)
     return T, stats[0], stats[1], iters, nn
-
-
-def _check_target_offsets(offsets, n_rows, what):
-    """`_check_offsets` for the targets of the feature-matching RANSAC, where a pair may have no targets."""
-    if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
-        return offsets
-    off = offsets.tolist() if isinstance(offsets, (torch.Tensor, np.ndarray)) else list(offsets)
-    try:
-        off = [int(o) for o in off]
-    except (TypeError, ValueError):
-        _fail(what, "target_offsets must be B + 1 integers")
-    if len(off) < 2 or off[0] != 0 or off[-1] != n_rows or any(b < a for a, b in zip(off, off[1:])):
-        _fail(what, "target_offsets must not decrease, start at 0 and end at the number of target rows")
-    return off
-
-
-def _device_target_offsets(off, n_rows, device, what):
-    if isinstance(off, list) and any(b == a for a, b in zip(off, off[1:])):
-        return torch.tensor(off, dtype=torch.int32, device=device)      # (an empty pair: _device_offsets would refuse it)
-    return _device_offsets(off, n_rows, device, what)[0]
 
 
 def ransac_feature_matching_batched(source, target, nn, max_correspondence_distance, source_offsets=None, target_offsets=None,
@@ -242,60 +171,50 @@ def ransac_feature_matching_batched(source, target, nn, max_correspondence_dista
     No host synchronisation; the call can be captured into a graph."""
     what = "ransac_feature_matching_batched"
     if not isinstance(search, str) or search not in _ICP_SEARCH:
-        _fail(what, f'search must be "brute" or "grid" (got {search!r})')
+        fail(what, f'search must be "brute" or "grid" (got {search!r})')
     if (source_offsets is None) != (target_offsets is None):
-        _fail(what, "give both source_offsets and target_offsets, or neither")
+        fail(what, "give both source_offsets and target_offsets, or neither")
     dims = 3 if source_offsets is None else 2
-    _check_points(source, "source", what, dims)
-    _check_points(target, "target", what, dims)
+    check_rows(what, "source", source, dims, 3, non_empty=True)
+    check_rows(what, "target", target, dims, 3, non_empty=True)
     if dims == 3 and source.shape[0] != target.shape[0]:
-        _fail(what, f"source and target must hold the same number of pairs (got {source.shape[0]} / {target.shape[0]})")
+        fail(what, f"source and target must hold the same number of pairs (got {source.shape[0]} / {target.shape[0]})")
     if not isinstance(nn, torch.Tensor) or nn.dtype not in (torch.int64, torch.int32) or nn.shape != source.shape[:-1]:
-        _fail(what, f"nn must be an int64 or int32 tensor of shape {tuple(source.shape[:-1])}")
-    n = int(ransac_n)
-    if n != ransac_n or not 3 <= n <= 8:
-        _fail(what, f"ransac_n must be an integer in 3..8 (got {ransac_n})")
-    H = int(max_iteration)
-    if H != max_iteration or not 1 <= H <= _MAX_HYPOTHESES:
-        _fail(what, f"max_iteration must be an integer in 1..2**24 (got {max_iteration})")
-    V = int(max_validation)
-    if V != max_validation or not 1 <= V <= _MAX_VALIDATION:
-        _fail(what, f"max_validation must be an integer in 1..65536 (got {max_validation})")
-    tau = float(max_correspondence_distance)
-    if not (tau > 0 and np.isfinite(tau)):
-        _fail(what, f"max_correspondence_distance must be > 0 (got {max_correspondence_distance})")
+        fail(what, f"nn must be an int64 or int32 tensor of shape {tuple(source.shape[:-1])}")
+    n = int_in_range(what, "ransac_n", ransac_n, 3, 8)
+    H = int_in_range(what, "max_iteration", max_iteration, 1, _MAX_HYPOTHESES, rule="in 1..2**24")
+    V = int_in_range(what, "max_validation", max_validation, 1, _MAX_VALIDATION)
+    tau = positive_finite(what, "max_correspondence_distance", max_correspondence_distance, rule="> 0")
     cd = -1.0
     if checker_distance is not None:
         cd = float(checker_distance)
         if not (cd >= 0 and np.isfinite(cd)):
-            _fail(what, f"checker_distance must be >= 0 or None (got {checker_distance})")
+            fail(what, f"checker_distance must be >= 0 or None (got {checker_distance})")
     el = 0.0
     if edge_length_threshold is not None:
         el = float(edge_length_threshold)
         if not 0 < el <= 1:
-            _fail(what, f"edge_length_threshold must be in (0, 1] or None (got {edge_length_threshold})")
+            fail(what, f"edge_length_threshold must be in (0, 1] or None (got {edge_length_threshold})")
     if int(first_pair) < 0:
-        _fail(what, "first_pair must be >= 0")
+        fail(what, "first_pair must be >= 0")
     ns_rows = source.shape[0] * source.shape[1] if dims == 3 else source.shape[0]
     nt_rows = target.shape[0] * target.shape[1] if dims == 3 else target.shape[0]
     if dims == 3:
-        soff = list(range(0, ns_rows + 1, source.shape[1]))
-        toff = list(range(0, nt_rows + 1, target.shape[1]))
+        soff, toff = uniform_offsets(*source.shape[:2]), uniform_offsets(*target.shape[:2])
     else:
-        soff = _check_offsets(source_offsets, ns_rows, what)
-        toff = _check_target_offsets(target_offsets, nt_rows, what)
+        soff = check_offsets(what, "source_offsets", source_offsets, ns_rows)
+        toff = check_offsets(what, "target_offsets", target_offsets, nt_rows, allow_empty=True)
         if isinstance(soff, list) and isinstance(toff, list) and len(soff) != len(toff):
-            _fail(what, "source_offsets and target_offsets must describe the same number of pairs")
+            fail(what, "source_offsets and target_offsets must describe the same number of pairs")
     for x, name in ((source, "source"), (target, "target"), (nn, "nn")):
-        _require_device(x, name, what)
-    if target.device != source.device or nn.device != source.device:
-        _fail(what, "source, target and nn must live on the same device")
+        require_device(x, name, what)
+    same_device(what, source=source, target=target, nn=nn)
     dev = source.device
-    dso, _ = _device_offsets(soff, ns_rows, dev, what)
-    dto = _device_target_offsets(toff, nt_rows, dev, what)
+    dso, max_s = device_offsets(soff, ns_rows, dev, what, checked=True)
+    dto, _ = device_offsets(toff, nt_rows, dev, what, allow_empty=True, checked=True)
     B = dso.numel() - 1
     if dto.numel() != B + 1:
-        _fail(what, "source_offsets and target_offsets must describe the same number of pairs")
+        fail(what, "source_offsets and target_offsets must describe the same number of pairs")
     S = source.reshape(-1, 3).contiguous()
     Q = target.reshape(-1, 3).contiguous()
     J = nn.reshape(-1).to(torch.int64).contiguous()
@@ -309,12 +228,11 @@ def ransac_feature_matching_batched(source, target, nn, max_correspondence_dista
         hyp = torch.empty((B, V), device=dev, dtype=torch.int32)
         count = torch.empty((B, V), device=dev, dtype=torch.int32)
         total = torch.empty((B, V), device=dev, dtype=torch.int64)
-    ptr = lambda t: None if t is None else t.data_ptr()      # noqa: E731
     h, st = handle_and_stream(S)
     h.call("gmf_ransac_feature_matching", S.data_ptr(), dso.data_ptr(), Q.data_ptr(), dto.data_ptr(), J.data_ptr(), B, ns_rows,
-           nt_rows, _max_rows(soff, ns_rows), n, H, V, tau, cd, el, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_pair),
+           nt_rows, max_s, n, H, V, tau, cd, el, int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_pair),
            _ICP_SEARCH[search], T.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), ids.data_ptr(), ids.data_ptr() + 8 * B,
-           nn_out.data_ptr(), validated.data_ptr(), ptr(hyp), ptr(count), ptr(total), st)
+           nn_out.data_ptr(), validated.data_ptr(), _lib.ptr(hyp), _lib.ptr(count), _lib.ptr(total), st)
     flat = ids.view(-1)                                      # hypothesis [B] followed by sample [B, n] (one allocation)
     out = (T, stats[0], stats[1], flat[:B], flat[B:].view(B, n), nn_out, validated)
     return out + (hyp, count, total) if return_hypotheses else out
@@ -341,21 +259,20 @@ def registration_ransac_based_on_correspondence(source, target, corres, max_corr
     correspondence_set [K,2] int64 on the device (the winner's inlier rows of corres), fitness, inlier_rmse)."""
     what = "registration_ransac_based_on_correspondence"
     dev = _device_of(source, target, corres)
-    if dev.type != "cuda":
-        _fail(what, f"the points must live on a HIP device (got {dev}); the HIP path is mandatory, there is no CPU fallback")
+    require_device(dev, "the points", what)
     src_pts = _on_device(source, dev, torch.float32)
     tgt_pts = _on_device(target, dev, torch.float32)
     c = _on_device(corres, dev, torch.int64)
     if c.dim() != 2 or c.shape[1] != 2:
-        _fail(what, f"corres must be [M,2] (got {tuple(c.shape)})")
+        fail(what, f"corres must be [M,2] (got {tuple(c.shape)})")
     H = min(int(max_iteration), int(max_validation))
     if H < 1:
-        _fail(what, "max_iteration and max_validation must be >= 1")
+        fail(what, "max_iteration and max_validation must be >= 1")
     if c.shape[0] == 0:
         return RegistrationResult(torch.eye(4, device=dev), c.clone(), 0.0, 0.0)
     lo, hi0, hi1 = torch.stack([c.min(), c[:, 0].max(), c[:, 1].max()]).tolist()      # (a host read: indices are checked)
     if lo < 0 or hi0 >= src_pts.shape[0] or hi1 >= tgt_pts.shape[0]:
-        _fail(what, "corres holds a row outside source / target")
+        fail(what, "corres holds a row outside source / target")
     T, inl, fit, rmse, _, _ = ransac_correspondence_batched(src_pts[c[:, 0]][None], tgt_pts[c[:, 1]][None],
                                                             max_correspondence_distance, ransac_n=ransac_n, num_hypotheses=H,
                                                             seed=seed)
@@ -380,14 +297,13 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     for x, f, name in ((source, source_feature, "source"), (target, target_feature, "target")):
         xs, fs = tuple(np.shape(x)), tuple(np.shape(f))
         if len(xs) != 2 or xs[1] != 3 or len(fs) != 2 or fs[0] != xs[0]:
-            _fail(what, f"{name} must be [N,3] and {name}_feature [N,d], one row per point (got {xs} / {fs}; open3d's [d,N] "
-                        "Feature layout is not accepted)")
+            fail(what, f"{name} must be [N,3] and {name}_feature [N,d], one row per point (got {xs} / {fs}; open3d's [d,N] "
+                       "Feature layout is not accepted)")
     if np.shape(source_feature)[1] != np.shape(target_feature)[1]:
-        _fail(what, f"source_feature and target_feature differ in width ({np.shape(source_feature)[1]} / "
-                    f"{np.shape(target_feature)[1]})")
+        fail(what, f"source_feature and target_feature differ in width ({np.shape(source_feature)[1]} / "
+                   f"{np.shape(target_feature)[1]})")
     dev = _device_of(source, target, source_feature, target_feature)
-    if dev.type != "cuda":
-        _fail(what, f"the points must live on a HIP device (got {dev}); the HIP path is mandatory, there is no CPU fallback")
+    require_device(dev, "the points", what)
     S = _on_device(source, dev, torch.float32)
     Q = _on_device(target, dev, torch.float32)
     F0 = _on_device(source_feature, dev, torch.float32)
@@ -411,15 +327,14 @@ def registration_icp(source, target, max_correspondence_distance, init=None, max
     nearest target row) of the final C, fitness, inlier_rmse)."""
     what = "registration_icp"
     if not isinstance(search, str) or search not in _ICP_SEARCH:
-        _fail(what, f'search must be "brute" or "grid" (got {search!r})')
+        fail(what, f'search must be "brute" or "grid" (got {search!r})')
     dev = _device_of(source, target, init)
-    if dev.type != "cuda":
-        _fail(what, f"the points must live on a HIP device (got {dev}); the HIP path is mandatory, there is no CPU fallback")
+    require_device(dev, "the points", what)
     S = _on_device(source, dev, torch.float32)
     Q = _on_device(target, dev, torch.float32)
     T0 = torch.eye(4, device=dev) if init is None else _on_device(init, dev, torch.float32)
     if T0.shape != (4, 4):
-        _fail(what, f"init must be [4,4] (got {tuple(T0.shape)})")
+        fail(what, f"init must be [4,4] (got {tuple(T0.shape)})")
     T, fit, rmse, _, nn = icp_point_to_point_batched(S[None], Q[None], T0[None], max_correspondence_distance,
                                                      max_iteration=max_iteration, relative_fitness=relative_fitness,
                                                      relative_rmse=relative_rmse, search=search)

@@ -25,6 +25,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._args import fail
 from ._util import WeightWatcher, handle_and_stream
 from .perceiver_io import PerceiverIO
 from .pointdsc import ImageEncoder
@@ -33,10 +34,6 @@ MAX_D = 6
 MAX_KERNEL_VOLUME = 1024
 MAX_LEVELS = 8
 MAX_MAPS = 16
-
-
-def _fail(what, msg, exc=RuntimeError):
-    raise exc(f"gmf_amd.{what}: {msg}")
 
 
 def kernel_volume(kernel_size: int, D: int) -> int:
@@ -64,27 +61,27 @@ def _check_map_desc(maps, D, levels, what):
     for m in maps:
         k, o, i = (int(v) for v in m)
         if k < 1 or k % 2 == 0:
-            _fail(what, f"kernel size {k} must be odd and >= 1")
+            fail(what, f"kernel size {k} must be odd and >= 1")
         if k ** D > MAX_KERNEL_VOLUME:
-            _fail(what, f"kernel volume {k}^{D} = {k ** D} exceeds {MAX_KERNEL_VOLUME}", NotImplementedError)
+            fail(what, f"kernel volume {k}^{D} = {k ** D} exceeds {MAX_KERNEL_VOLUME}", NotImplementedError)
         if not (0 <= o < levels and 0 <= i < levels and abs(o - i) <= 1):
-            _fail(what, f"map ({k}, {o}, {i}): levels must exist and differ by at most one")
+            fail(what, f"map ({k}, {o}, {i}): levels must exist and differ by at most one")
         out.append((k, o, i))
     if len(out) > MAX_MAPS:
-        _fail(what, f"at most {MAX_MAPS} kernel maps")
+        fail(what, f"at most {MAX_MAPS} kernel maps")
     return out
 
 
 def check_coords(coords, what="SparsePlan"):
     """Shape / dtype / device checks of MinkowskiEngine batched coordinates [M, 1 + D] int32; returns (M, D)."""
     if not isinstance(coords, torch.Tensor):
-        _fail(what, "`coords` must be a torch tensor")
+        fail(what, "`coords` must be a torch tensor")
     if coords.dtype != torch.int32:
-        _fail(what, f"`coords` must be int32 (got {coords.dtype})")
+        fail(what, f"`coords` must be int32 (got {coords.dtype})")
     if coords.dim() != 2 or coords.shape[0] == 0 or not (2 <= coords.shape[1] <= 1 + MAX_D):
-        _fail(what, f"`coords` must be a non-empty [M, 1 + D] tensor with D in 1..{MAX_D} (got {tuple(coords.shape)})")
+        fail(what, f"`coords` must be a non-empty [M, 1 + D] tensor with D in 1..{MAX_D} (got {tuple(coords.shape)})")
     if not coords.is_cuda:
-        _fail(what, f"`coords` must live on a HIP device (got {coords.device}); the HIP path is mandatory, there is no CPU fallback")
+        fail(what, f"`coords` must live on a HIP device (got {coords.device}); the HIP path is mandatory, there is no CPU fallback")
     return coords.shape[0], coords.shape[1] - 1
 
 
@@ -99,7 +96,7 @@ class SparsePlan:
     def __init__(self, coords, levels: int, maps=()):
         self.M, self.D = check_coords(coords)
         if not (1 <= levels <= MAX_LEVELS):
-            _fail("SparsePlan", f"levels must be in 1..{MAX_LEVELS}")
+            fail("SparsePlan", f"levels must be in 1..{MAX_LEVELS}")
         self.levels = int(levels)
         self.maps = _check_map_desc(maps, self.D, self.levels, "SparsePlan")
         self.K = [kernel_volume(k, self.D) for k, _, _ in self.maps]
@@ -164,23 +161,23 @@ class SparsePlan:
 
 def _f32_dev(t, name, what):
     if not isinstance(t, torch.Tensor):
-        _fail(what, f"`{name}` must be a torch tensor")
+        fail(what, f"`{name}` must be a torch tensor")
     if not t.is_cuda:
-        _fail(what, f"`{name}` must live on a HIP device (got {t.device}); the HIP path is mandatory, there is no CPU fallback")
+        fail(what, f"`{name}` must live on a HIP device (got {t.device}); the HIP path is mandatory, there is no CPU fallback")
     if t.dtype != torch.float32:
-        _fail(what, f"`{name}` must be float32 (got {t.dtype})")
+        fail(what, f"`{name}` must be float32 (got {t.dtype})")
     return t.contiguous()
 
 
 def _check_sources(xa, xb, M, what):
     """The two-source input [xa | xb] of a convolution, xa already through `_f32_dev`: (xb or None, ca, cb)."""
     if xa.dim() != 2 or xa.shape[0] != M:
-        _fail(what, f"`xa` must be [M = {M}, ca] (got {tuple(xa.shape)})")
+        fail(what, f"`xa` must be [M = {M}, ca] (got {tuple(xa.shape)})")
     if xb is None:
         return None, xa.shape[1], 0
     xb = _f32_dev(xb, "xb", what)
     if xb.dim() != 2 or xb.shape[0] != M:
-        _fail(what, f"`xb` must be [M = {M}, cb] (got {tuple(xb.shape)})")
+        fail(what, f"`xb` must be [M = {M}, cb] (got {tuple(xb.shape)})")
     return xb, xa.shape[1], xb.shape[1]
 
 
@@ -192,7 +189,7 @@ def _check_epilogue(scale, shift, residual, M, cout, what):
         if v is not None:
             v = _f32_dev(v, name, what)
             if tuple(v.shape) != shape and not (name != "residual" and v.numel() == cout):
-                _fail(what, f"`{name}` must be {list(shape)} (got {tuple(v.shape)})")
+                fail(what, f"`{name}` must be {list(shape)} (got {tuple(v.shape)})")
         vecs.append(v)
     return vecs
 
@@ -201,10 +198,10 @@ def _check_out(out, M, cout, inputs, what, device):
     if out is None:
         return torch.empty((M, cout), dtype=torch.float32, device=device)
     if out.shape != (M, cout) or out.dtype != torch.float32 or not out.is_contiguous():
-        _fail(what, f"`out` must be a contiguous float32 [{M}, {cout}] tensor")
+        fail(what, f"`out` must be a contiguous float32 [{M}, {cout}] tensor")
     for name, t in inputs:
         if t is not None and _overlap(out, t):
-            _fail(what, f"`out` overlaps `{name}`: the convolution cannot run in place")
+            fail(what, f"`out` overlaps `{name}`: the convolution cannot run in place")
     return out
 
 
@@ -212,7 +209,7 @@ def _map_arrays(plan, map_index, out_level, what):
     if map_index is None:
         return 1, None, None, None, None
     if plan.maps[map_index][1] != out_level:
-        _fail(what, f"map {map_index} writes level {plan.maps[map_index][1]}, not {out_level}")
+        fail(what, f"map {map_index} writes level {plan.maps[map_index][1]}, not {out_level}")
     rp, pairs = plan.kernel_map(map_index)
     by_off, off_start = plan.offset_lists(map_index)
     return plan.K[map_index], rp, pairs, by_off, off_start
@@ -237,11 +234,11 @@ def sparse_conv(plan: SparsePlan, map_index, out_level: int, xa, W, xb=None, sca
     if W.dim() == 2 and K == 1:
         W = W.unsqueeze(0)
     if W.dim() != 3 or W.shape[0] != K or W.shape[1] != ca + cb:
-        _fail(what, f"`W` must be [K = {K}, Cin = {ca + cb}, Cout] (got {tuple(W.shape)})")
+        fail(what, f"`W` must be [K = {K}, Cin = {ca + cb}, Cout] (got {tuple(W.shape)})")
     cout = W.shape[2]
     vecs = _check_epilogue(scale, shift, residual, M, cout, what)
     if not (1 <= int(nsplit) <= K):
-        _fail(what, f"nsplit must be in 1..K = {K}")
+        fail(what, f"nsplit must be in 1..K = {K}")
     out = _check_out(out, M, cout, (("xa", xa), ("xb", xb), ("W", W), ("scale", vecs[0]), ("shift", vecs[1]),
                                     ("residual", vecs[2])), what, xa.device)
     h, st = handle_and_stream(xa)
@@ -260,7 +257,7 @@ def sparse_conv_wgrad(plan: SparsePlan, map_index, out_level: int, xa, dy, xb=No
     dy = _f32_dev(dy, "dy", what)
     M = plan.M
     if xa.dim() != 2 or xa.shape[0] != M or dy.dim() != 2 or dy.shape[0] != M:
-        _fail(what, f"`xa` and `dy` must be [M = {M}, C] (got {tuple(xa.shape)}, {tuple(dy.shape)})")
+        fail(what, f"`xa` and `dy` must be [M = {M}, C] (got {tuple(xa.shape)}, {tuple(dy.shape)})")
     xb, ca, cb = _check_sources(xa, xb, M, what)
     K, rp, pairs, by_off, off_start = _map_arrays(plan, map_index, out_level, what)
     cout = dy.shape[1]
@@ -282,7 +279,7 @@ def transposed_map(plan: SparsePlan, map_index):
     if o == i:
         return map_index, True
     if (k, i, o) not in plan.maps:
-        _fail("sparse_conv_dgrad", f"the plan has no map ({k}, {i}, {o}), the transpose of map {map_index}")
+        fail("sparse_conv_dgrad", f"the plan has no map ({k}, {i}, {o}), the transpose of map {map_index}")
     return plan.maps.index((k, i, o)), False
 
 
@@ -343,7 +340,7 @@ def sparse_conv_train(plan: SparsePlan, map_index, out_level: int, xa, W, xb=Non
     `kernel` ([K, Cin, Cout], or [Cin, Cout] when K = 1); a bias [1, Cout] only into level 0, where every row is valid (its
     gradient sums all M rows)."""
     if bias is not None and out_level != 0:
-        _fail("sparse_conv_train", "a bias is supported into level 0 only")
+        fail("sparse_conv_train", "a bias is supported into level 0 only")
     return _SparseConvFn.apply(plan, map_index, out_level, xa, xb, W, bias, bool(relu))
 
 
@@ -358,20 +355,20 @@ def sparse_conv_narrow(plan: SparsePlan, map_index: int, out_level: int, x, W, s
     W = _f32_dev(W, "W", what)
     M = plan.M
     if x.dim() != 2 or x.shape[0] != M:
-        _fail(what, f"`x` must be [M = {M}, cin] (got {tuple(x.shape)})")
+        fail(what, f"`x` must be [M = {M}, cin] (got {tuple(x.shape)})")
     if map_index is None or not (0 <= int(map_index) < len(plan.maps)):
-        _fail(what, "`map_index` must name a kernel map of the plan")
+        fail(what, "`map_index` must name a kernel map of the plan")
     K = plan.K[map_index]
     if plan.maps[map_index][1] != out_level:
-        _fail(what, f"map {map_index} writes level {plan.maps[map_index][1]}, not {out_level}")
+        fail(what, f"map {map_index} writes level {plan.maps[map_index][1]}, not {out_level}")
     if W.dim() == 2 and K == 1:
         W = W.unsqueeze(0)
     cin = x.shape[1]
     if W.dim() != 3 or W.shape[0] != K or W.shape[1] != cin:
-        _fail(what, f"`W` must be [K = {K}, Cin = {cin}, Cout] (got {tuple(W.shape)})")
+        fail(what, f"`W` must be [K = {K}, Cin = {cin}, Cout] (got {tuple(W.shape)})")
     cout = W.shape[2]
     if not (1 <= cin <= 8 and 1 <= cout <= 64):
-        _fail(what, f"Cin must be in 1..8 and Cout in 1..64 (got {cin}, {cout})", NotImplementedError)
+        fail(what, f"Cin must be in 1..8 and Cout in 1..64 (got {cin}, {cout})", NotImplementedError)
     vecs = _check_epilogue(scale, shift, residual, M, cout, what)
     out = _check_out(out, M, cout, (("x", x), ("W", W), ("scale", vecs[0]), ("shift", vecs[1]), ("residual", vecs[2])), what,
                      x.device)
@@ -392,12 +389,12 @@ def sparse_conv_narrow_wgrad(plan: SparsePlan, map_index: int, out_level: int, x
     dy = _f32_dev(dy, "dy", what)
     M = plan.M
     if x.dim() != 2 or x.shape[0] != M or dy.dim() != 2 or dy.shape[0] != M:
-        _fail(what, f"`x` and `dy` must be [M = {M}, C] (got {tuple(x.shape)}, {tuple(dy.shape)})")
+        fail(what, f"`x` and `dy` must be [M = {M}, C] (got {tuple(x.shape)}, {tuple(dy.shape)})")
     if map_index is None or not (0 <= int(map_index) < len(plan.maps)):
-        _fail(what, "`map_index` must name a kernel map of the plan")
+        fail(what, "`map_index` must name a kernel map of the plan")
     cin, cout = x.shape[1], dy.shape[1]
     if not (1 <= cin <= 8 and 1 <= cout <= 64):
-        _fail(what, f"Cin must be in 1..8 and Cout in 1..64 (got {cin}, {cout})", NotImplementedError)
+        fail(what, f"Cin must be in 1..8 and Cout in 1..64 (got {cin}, {cout})", NotImplementedError)
     K, rp, pairs, by_off, off_start = _map_arrays(plan, map_index, out_level, what)
     dW = torch.empty((K, cin, cout), dtype=torch.float32, device=x.device)
     h, st = handle_and_stream(x)
@@ -430,8 +427,8 @@ class _SparseConvNarrowFn(torch.autograd.Function):
 def sparse_conv_narrow_train(plan: SparsePlan, map_index: int, out_level: int, x, W):
     """`sparse_conv_narrow` with its weight gradient (`sparse_conv_narrow_wgrad`); x gets no gradient and must not need one."""
     if isinstance(x, torch.Tensor) and x.requires_grad:
-        _fail("sparse_conv_narrow_train", "`x` requires a gradient: the narrow convolution has no data gradient "
-              "(use sparse_conv_train)", NotImplementedError)
+        fail("sparse_conv_narrow_train", "`x` requires a gradient: the narrow convolution has no data gradient "
+             "(use sparse_conv_train)", NotImplementedError)
     return _SparseConvNarrowFn.apply(plan, map_index, out_level, x, W)
 
 
@@ -448,17 +445,17 @@ def sparse_head_l2(plan: SparsePlan, level: int, xa, W1, W2, xb=None, bias=None,
     W1 = W1[0] if W1.dim() == 3 and W1.shape[0] == 1 else W1
     W2 = W2[0] if W2.dim() == 3 and W2.shape[0] == 1 else W2
     if W1.dim() != 2 or W1.shape[0] != ca + cb:
-        _fail(what, f"`W1` must be [ca + cb = {ca + cb}, hid] (got {tuple(W1.shape)})")
+        fail(what, f"`W1` must be [ca + cb = {ca + cb}, hid] (got {tuple(W1.shape)})")
     hid = W1.shape[1]
     if W2.dim() != 2 or W2.shape[0] != hid:
-        _fail(what, f"`W2` must be [hid = {hid}, cout] (got {tuple(W2.shape)})")
+        fail(what, f"`W2` must be [hid = {hid}, cout] (got {tuple(W2.shape)})")
     cout = W2.shape[1]
     if max(ca, cb, hid, cout) > 64:
-        _fail(what, f"every width must be at most 64 (ca {ca}, cb {cb}, hid {hid}, cout {cout})", NotImplementedError)
+        fail(what, f"every width must be at most 64 (ca {ca}, cb {cb}, hid {hid}, cout {cout})", NotImplementedError)
     if bias is not None:
         bias = _f32_dev(bias, "bias", what)
         if bias.numel() != cout:
-            _fail(what, f"`bias` must hold {cout} values (got {tuple(bias.shape)})")
+            fail(what, f"`bias` must hold {cout} values (got {tuple(bias.shape)})")
     W1, W2 = W1.contiguous(), W2.contiguous()
     out = _check_out(out, M, cout, (("xa", xa), ("xb", xb), ("W1", W1), ("W2", W2), ("bias", bias)), what, xa.device)
     h, st = handle_and_stream(xa)
@@ -598,14 +595,14 @@ class _ResUNet(nn.Module):
         super().__init__()
         what = self._what = self._MODULE + type(self).__name__
         if self.REGION_TYPE != "HYPER_CUBE":
-            _fail(what, f"only the hypercube kernel region is built (got {self.REGION_TYPE})", NotImplementedError)
+            fail(what, f"only the hypercube kernel region is built (got {self.REGION_TYPE})", NotImplementedError)
         if not (1 <= int(D) <= MAX_D):
-            _fail(what, f"D must be in 1..{MAX_D} (got {D})", ValueError)
+            fail(what, f"D must be in 1..{MAX_D} (got {D})", ValueError)
         for k in (conv1_kernel_size, 3):
             if k % 2 == 0 or k < 1:
-                _fail(what, f"kernel size {k} must be odd", ValueError)
+                fail(what, f"kernel size {k} must be odd", ValueError)
             if kernel_volume(k, D) > MAX_KERNEL_VOLUME:
-                _fail(what, f"kernel volume {k}^{D} exceeds {MAX_KERNEL_VOLUME}", NotImplementedError)
+                fail(what, f"kernel volume {k}^{D} exceeds {MAX_KERNEL_VOLUME}", NotImplementedError)
         self.D, self.conv1_kernel_size = int(D), int(conv1_kernel_size)
         self.in_channels, self.out_channels = int(in_channels), int(out_channels)
         self.normalize_feature = bool(normalize_feature)
@@ -661,10 +658,10 @@ class _ResUNet(nn.Module):
         what = self._what
         M, D = check_coords(coords, what)
         if D != self.D:
-            _fail(what, f"coords have D = {D}, the network was built for D = {self.D}")
+            fail(what, f"coords have D = {D}, the network was built for D = {self.D}")
         feats = _f32_dev(feats, "feats", what)
         if feats.dim() != 2 or feats.shape != (M, self.in_channels):
-            _fail(what, f"`feats` must be [{M}, {self.in_channels}] (got {tuple(feats.shape)})")
+            fail(what, f"`feats` must be [{M}, {self.in_channels}] (got {tuple(feats.shape)})")
         return feats
 
     def _plan(self, coords, conv1_needs_pairs=False):
@@ -704,7 +701,7 @@ class ResUNetBN2C(_ResUNet):
                  pe=False):
         super().__init__(in_channels, out_channels, conv1_kernel_size, normalize_feature, D)
         if normalize_feature:
-            _fail(self._what, "normalize_feature=True is not built (DGR's inlier network uses False)", NotImplementedError)
+            fail(self._what, "normalize_feature=True is not built (DGR's inlier network uses False)", NotImplementedError)
         self.pe = bool(pe)
         CH = self.CHANNELS
 
@@ -787,7 +784,7 @@ def inlier_coordinates(coords0, coords1, idx0, idx1):
     voxel of its correspondence) = cat(coords0[idx0], coords1[idx1, 1:]).  coords0 / coords1 [N, 4] int (batch, x, y, z)."""
     for name, c in (("coords0", coords0), ("coords1", coords1)):
         if not isinstance(c, torch.Tensor) or c.dim() != 2 or c.shape[1] != 4 or c.dtype.is_floating_point:
-            _fail("inlier_coordinates", f"`{name}` must be an integer [N, 4] tensor (batch, x, y, z)")
+            fail("inlier_coordinates", f"`{name}` must be an integer [N, 4] tensor (batch, x, y, z)")
     if idx0.shape != idx1.shape or idx0.dim() != 1:
-        _fail("inlier_coordinates", "`idx0` and `idx1` must be 1-D and of equal length")
+        fail("inlier_coordinates", "`idx0` and `idx1` must be 1-D and of equal length")
     return torch.cat((coords0[idx0.long()], coords1[idx1.long(), 1:]), dim=1).to(torch.int32).contiguous()

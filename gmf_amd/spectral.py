@@ -9,40 +9,13 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
 import torch
 
+from ._args import (cached_upload, check_offsets, check_rows, device_offsets, fail, int_in_range, positive_finite, require_device,
+                    same_device, uniform_offsets)
 from ._util import handle_and_stream
-from .registration import _cached_upload, _device_offsets
 
 _MAX_SPLITS = 32
-
-
-def _fail(what, msg):
-    raise RuntimeError(f"gmf_amd.{what}: {msg}")
-
-
-def _check_rows(x, name, what, dims, width):
-    if not isinstance(x, torch.Tensor):
-        _fail(what, f"`{name}` must be a torch tensor")
-    if x.dtype != torch.float32:
-        _fail(what, f"`{name}` must be float32 (got {x.dtype})")
-    if x.dim() != dims or x.shape[-1] != width:
-        _fail(what, f"`{name}` must be a [{'B,N' if dims == 3 else 'sum N'},{width}] tensor (got {tuple(x.shape)})")
-
-
-def _check_offsets(offsets, n_rows, what):
-    """Host-side checks of an offset list; a pair may be empty.  A device int32 tensor is checked by _device_offsets."""
-    if isinstance(offsets, torch.Tensor) and offsets.is_cuda:
-        return offsets
-    off = offsets.tolist() if isinstance(offsets, (torch.Tensor, np.ndarray)) else list(offsets)
-    try:
-        off = [int(o) for o in off]
-    except (TypeError, ValueError):
-        _fail(what, "offsets must be B + 1 integers")
-    if len(off) < 2 or off[0] != 0 or off[-1] != n_rows or any(b < a for a, b in zip(off, off[1:])):
-        _fail(what, "offsets must not decrease, start at 0 and end at sum N")
-    return off
 
 
 def spectral_matching_batched(corr, src_keypts, tgt_keypts, inlier_threshold, top_ratio=0.1, num_iterations=10, offsets=None,
@@ -64,45 +37,32 @@ def spectral_matching_batched(corr, src_keypts, tgt_keypts, inlier_threshold, to
     No host synchronisation; the call can be captured into a graph."""
     what = "spectral_matching_batched"
     dims = 3 if offsets is None else 2
-    _check_rows(corr, "corr", what, dims, 6)
-    _check_rows(src_keypts, "src_keypts", what, dims, 3)
-    _check_rows(tgt_keypts, "tgt_keypts", what, dims, 3)
+    check_rows(what, "corr", corr, dims, 6)
+    check_rows(what, "src_keypts", src_keypts, dims, 3)
+    check_rows(what, "tgt_keypts", tgt_keypts, dims, 3)
     if not corr.shape[:-1] == src_keypts.shape[:-1] == tgt_keypts.shape[:-1]:
-        _fail(what, f"corr, src_keypts and tgt_keypts must have equal row counts (got {tuple(corr.shape)} / "
-                    f"{tuple(src_keypts.shape)} / {tuple(tgt_keypts.shape)})")
+        fail(what, f"corr, src_keypts and tgt_keypts must have equal row counts (got {tuple(corr.shape)} / "
+                   f"{tuple(src_keypts.shape)} / {tuple(tgt_keypts.shape)})")
     if dims == 3 and corr.shape[0] == 0:
-        _fail(what, "the batch must hold at least one pair")
-    tau = float(inlier_threshold)
-    if not (tau > 0 and np.isfinite(tau)):
-        _fail(what, f"inlier_threshold must be finite and > 0 (got {inlier_threshold})")
+        fail(what, "the batch must hold at least one pair")
+    tau = positive_finite(what, "inlier_threshold", inlier_threshold)
     ratio = float(top_ratio)
     if not 0 <= ratio <= 1:
-        _fail(what, f"top_ratio must be in [0, 1] (got {top_ratio})")
-    its = int(num_iterations)
-    if its != num_iterations or not 1 <= its <= 1000:
-        _fail(what, f"num_iterations must be an integer in 1..1000 (got {num_iterations})")
-    forced = 0
-    if _col_splits is not None:
-        forced = int(_col_splits)
-        if forced != _col_splits or not 1 <= forced <= _MAX_SPLITS:
-            _fail(what, f"_col_splits must be an integer in 1..{_MAX_SPLITS} (got {_col_splits})")
+        fail(what, f"top_ratio must be in [0, 1] (got {top_ratio})")
+    its = int_in_range(what, "num_iterations", num_iterations, 1, 1000)
+    forced = 0 if _col_splits is None else int_in_range(what, "_col_splits", _col_splits, 1, _MAX_SPLITS)
     n_rows = corr.shape[0] * corr.shape[1] if dims == 3 else corr.shape[0]
-    if dims == 3:
-        off = list(range(0, n_rows + 1, corr.shape[1])) if corr.shape[1] else [0] * (corr.shape[0] + 1)
-    else:
-        off = _check_offsets(offsets, n_rows, what)
+    off = uniform_offsets(*corr.shape[:2]) if dims == 3 else check_offsets(what, "offsets", offsets, n_rows, allow_empty=True)
     for x, name in ((corr, "corr"), (src_keypts, "src_keypts"), (tgt_keypts, "tgt_keypts")):
-        if not x.is_cuda:
-            _fail(what, f"`{name}` must live on a HIP device (got {x.device}); the HIP path is mandatory, there is no CPU fallback")
+        require_device(x, name, what)
     dev = corr.device
-    if src_keypts.device != dev or tgt_keypts.device != dev:
-        _fail(what, "corr, src_keypts and tgt_keypts must live on the same device")
+    same_device(what, corr=corr, src_keypts=src_keypts, tgt_keypts=tgt_keypts)
     if isinstance(off, list):
-        dev_off, max_n = _device_offsets(off, n_rows, dev, what, allow_empty=True)
+        dev_off, max_n = device_offsets(off, n_rows, dev, what, allow_empty=True, checked=True)
         # k = int(N * top_ratio) per pair, uploaded once per list of sizes and ratio like the offsets themselves
-        topk = _cached_upload(tuple(int((b - a) * ratio) for a, b in zip(off, off[1:])), dev)[0]
+        topk = cached_upload(tuple(int((b - a) * ratio) for a, b in zip(off, off[1:])), dev)[0]
     else:
-        dev_off, _ = _device_offsets(off, n_rows, dev, what)
+        dev_off, _ = device_offsets(off, n_rows, dev, what)
         max_n = n_rows                                      # the largest pair is not known without a read-back
         topk = ((dev_off[1:] - dev_off[:-1]).double() * ratio).floor().to(torch.int32)      # int(N * top_ratio), Python's arithmetic
     B = dev_off.numel() - 1
@@ -135,5 +95,5 @@ def SM(corr, src_keypts, tgt_keypts, args, top_ratio=0.1):
     tgt_keypts [1,N,3], `args.inlier_threshold` read -> (pred_trans [1,4,4], pred_labels [1,N]).  One pair per call, as the
     reference's label assignment implies; the inputs are not written.  Ties: see spectral_matching_batched."""
     if not isinstance(corr, torch.Tensor) or corr.dim() != 3 or corr.shape[0] != 1:
-        _fail("SM", f"corr must be [1,N,6]: one pair per call, as in the reference (got {tuple(getattr(corr, 'shape', ()))})")
+        fail("SM", f"corr must be [1,N,6]: one pair per call, as in the reference (got {tuple(getattr(corr, 'shape', ()))})")
     return spectral_matching_batched(corr, src_keypts, tgt_keypts, args.inlier_threshold, top_ratio=top_ratio)

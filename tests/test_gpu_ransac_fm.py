@@ -285,6 +285,29 @@ def test_pair_without_targets_and_bad_nn():
     assert (hyp[hyp >= 0] == np.flatnonzero(ok)).all() and int(out[6][0]) == ok.sum() > 0
 
 
+def test_host_target_offsets_with_an_empty_pair_in_the_middle():
+    """A host list of target offsets with an empty pair is uploaded like every other table (pinned, cached): the pair without
+    targets reports no winner, its neighbours return what they return alone, and the second call, which finds the list in the
+    cache, returns the same bits."""
+    r = np.random.default_rng(41)
+    tgt = r.uniform(-1, 1, (32, 3)).astype(np.float32)
+    nn = np.tile(np.arange(24) % 16, 3)
+    src = np.concatenate([tgt[:16][nn[:24]], tgt[:16][nn[:24]], tgt[16:][nn[:24]]]) + r.normal(0, 1e-3, (72, 3)).astype(np.float32)
+    S, Q, J = _g(src.astype(np.float32)), _g(tgt), _g(nn)
+    soff, toff = [0, 24, 48, 72], [0, 16, 16, 32]
+    kw = dict(max_iteration=64, max_validation=8, ransac_n=3, seed=3)
+    out = gmf_amd.ransac_feature_matching_batched(S, Q, J, TAU, source_offsets=soff, target_offsets=toff, **kw)
+    assert torch.equal(out[0][1], torch.eye(4, device=DEV)) and out[3][1] == -1 and out[1][1] == 0 and out[2][1] == 0
+    for b in (0, 2):
+        one = gmf_amd.ransac_feature_matching_batched(S[soff[b]:soff[b + 1]][None], Q[toff[b]:toff[b + 1]][None],
+                                                      J[soff[b]:soff[b + 1]][None], TAU, first_pair=b, **kw)
+        got = [out[k][b:b + 1] for k in range(5)] + [out[5][soff[b]:soff[b + 1]][None], out[6][b:b + 1]]
+        _assert_equal(got, one, f"pair {b}")
+        assert out[3][b] >= 0                                # (exact correspondences up to 1e-3: a triple fits and has inliers)
+    again = gmf_amd.ransac_feature_matching_batched(S, Q, J, TAU, source_offsets=soff, target_offsets=toff, **kw)
+    _assert_equal(out, again, "second call")
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # 5. determinism, the seed, graph capture, a clean scene
 # ---------------------------------------------------------------------------------------------------------------------------
