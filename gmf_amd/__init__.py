@@ -14,7 +14,7 @@ from .matching import nn_match, find_knn_gpu, find_knn_gpu_batch, find_knn_batch
 from .correspondences import nn_match_mutual, build_correspondences    # noqa: F401
 from . import se3 as SE3                         # noqa: F401
 from ._lib import check_status, set_handle_per_stream   # noqa: F401
-from .solvers import (ransac_correspondence_batched, icp_point_to_point_batched, RegistrationResult,  # noqa: F401
+from .solvers import (ransac_correspondence_batched, icp_point_to_point_batched, icp_point_to_plane_batched, RegistrationResult,  # noqa: F401
                       registration_ransac_based_on_correspondence, registration_icp, icp_refine,
                       ransac_feature_matching_batched, registration_ransac_based_on_feature_matching)
 from .spectral import spectral_matching_batched, SM   # noqa: F401
@@ -36,7 +36,7 @@ __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointD
            "rigid_transform_3d", "knn", "weighted_procrustes", "weighted_procrustes_batched", "GlobalRegistration", "global_registration_batched", "argmin_se3_squared_dist", "Transformation", "ortho2rotation", "nn_match", "nn_match_mutual", "build_correspondences",
            "find_knn_gpu", "SE3", "ClassificationLoss", "SpectralMatchingLoss", "TransformationLoss",
            "similarity_matrix", "check_status", "set_handle_per_stream", "ransac_correspondence_batched",
-           "icp_point_to_point_batched", "RegistrationResult", "registration_ransac_based_on_correspondence", "registration_icp",
+           "icp_point_to_point_batched", "icp_point_to_plane_batched", "RegistrationResult", "registration_ransac_based_on_correspondence", "registration_icp",
            "icp_refine", "radius_knn_batched", "estimate_normals_batched", "compute_fpfh_batched", "voxel_down_sample_batched",
            "voxel_select_batched", "voxel_down_sample", "voxel_select", "estimate_normals", "compute_fpfh_feature",
            "fpfh_descriptors", "SparsePlan", "sparse_conv", "sparse_conv_narrow", "sparse_conv_narrow_wgrad", "sparse_head_l2",

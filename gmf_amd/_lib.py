@@ -216,6 +216,8 @@ SIGNATURES = {
                                          C.c_double, C.c_double] + [_vp] * 6),
     "gmf_icp_point_to_point_ex": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _ll, C.c_int, C.c_int, _vp, C.c_float, C.c_int,
                                             C.c_double, C.c_double] + [_vp] * 5 + [_ll, C.c_int, _vp]),
+    "gmf_icp_point_to_plane": (C.c_int, [_vp] * 6 + [C.c_int, _ll, C.c_int, C.c_int, _vp, C.c_float, C.c_int, C.c_double,
+                                         C.c_double] + [_vp] * 5 + [_ll, C.c_int, _vp]),
     "gmf_information_matrix": (C.c_int, [_vp, _vp, _i32p, C.c_int, _i32p, _i32p, C.c_int, _vp, C.c_float, _vp, _vp, _vp, _vp]),
     "gmf_posegraph_optimize": (C.c_int, [_vp, _vp, _i32p, _i32p, C.c_int, _i32p, _i32p] + [_vp] * 4 + [C.POINTER(PoseGraphOptions)]
                                + [_vp] * 6),

@@ -814,6 +814,43 @@ int gmf_icp_point_to_point_ex(gmf_handle* h, const float* src, const int* src_of
   return GMF_OK;
 }
 
+int gmf_icp_point_to_plane(gmf_handle* h, const float* src, const int* src_offsets, const float* tgt, const float* tgt_normals,
+                           const int* tgt_offsets, int B, long long total_src, int max_src, int max_tgt, const float* init,
+                           float tau, int max_iter, double rel_fitness, double rel_rmse, float* T_out, float* fitness,
+                           float* inlier_rmse, int* iterations, long long* nn, long long total_tgt, int search,
+                           gmf_stream_t stream) {
+  GMF_REQUIRE(h && src && src_offsets && tgt && tgt_normals && tgt_offsets && init && T_out && fitness && inlier_rmse &&
+                  iterations && nn,
+              GMF_ERR_BAD_ARG, "icp_point_to_plane: null pointer");
+  GMF_REQUIRE(B > 0 && total_src > 0 && total_src < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "icp_point_to_plane: empty batch or more than 2^31 source rows");
+  GMF_REQUIRE(total_tgt > 0 && total_tgt < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "icp_point_to_plane: total_tgt must be in 1..2^31 - 1");
+  GMF_REQUIRE(search == 0 || search == 1, GMF_ERR_BAD_ARG, "icp_point_to_plane: search must be 0 (brute force) or 1 (grid)");
+  GMF_REQUIRE(tau > 0.f && std::isfinite(tau), GMF_ERR_BAD_ARG, "icp_point_to_plane: max_correspondence_distance must be > 0");
+  GMF_REQUIRE(max_iter >= 0 && max_iter <= 100000, GMF_ERR_BAD_ARG, "icp_point_to_plane: max_iteration must be in 0..100000");
+  GMF_REQUIRE(search == 0 || total_tgt < (1LL << 29), GMF_ERR_UNSUPPORTED_SHAPE,
+              "icp_point_to_plane: the grid search takes fewer than 2^29 target rows");
+  GMF_REQUIRE(max_src <= total_src, GMF_ERR_BAD_ARG, "icp_point_to_plane: max_src exceeds total_src");
+  const int bound_src = max_src > 0 ? max_src : (int)total_src;
+  gmf::IcpPlaneScratch ps;
+  ps.normals = tgt_normals;
+  GMF_REQUIRE(gmf::icp_plane_plan(B, bound_src, ps.plan), GMF_ERR_UNSUPPORTED_SHAPE,
+              "icp_point_to_plane: the step's B * ceil(max_src / kIcpPlaneRows) workgroups do not fit one launch");
+  SetDevice sd(h, stream);
+  gmf::IcpScratch ws;
+  gmf::KnnScratch gs;
+  ArenaList bufs;
+  gmf::icp_scratch_list(total_src, B, ws, bufs);
+  gmf::icp_plane_scratch_list(ps, bufs);
+  if (search == 1) gmf::knn_scratch_list(total_tgt, gs, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  GMF_HIP(gmf::launch_icp(src, src_offsets, tgt, tgt_offsets, B, total_src, bound_src, max_tgt > 0 ? max_tgt : (int)total_tgt, init,
+                          tau, max_iter, rel_fitness, rel_rmse, ws, T_out, fitness, inlier_rmse, iterations, nn, S(stream),
+                          search == 1 ? &gs : nullptr, total_tgt, &ps));
+  return GMF_OK;
+}
+
 // The host plan (chunk table, the edges' cloud indices, the cloud offsets) goes up in ONE ring slot and ONE upload.
 int gmf_information_matrix(gmf_handle* h, const float* points, const int* cloud_offsets, int F, const int* edge_source,
                            const int* edge_target, int E, const double* transformation, float tau, double* info, int* count,

@@ -20,6 +20,10 @@
 //                      target lies within tau gets k_icp_nn's key and the whole result is bit-identical.
 //   k_icp_step         one workgroup per pair: C, fitness, rmse, the convergence test, then Umeyama over C and T <- dT T.
 //   A finished pair's workgroups return at once.
+// Point-to-plane ICP: the same launches with k_icp_step replaced by two, 2 + 3 (max_iteration + 1) in all:
+//   k_icp_plane_partials  one workgroup per 512 source rows of ONE pair: C, nn and a partial of 29 fp64 sums in a fixed tree.
+//   k_icp_plane_solve     one wave per pair: the partials in ascending order, fitness, rmse, the convergence test, then the
+//                         6 x 6 LDL^T of the linearised step and T <- dT T.
 // Feature-matching RANSAC (open3d's registration_ransac_based_on_feature_matching), three memsets, the grid build and seven
 // launches, none of which the host waits for:
 //   k_fm_propose       one lane per hypothesis: draw, pair each row with its feature-space match, edge-length test, fp64 Kabsch,
@@ -559,6 +563,191 @@ k_icp_step(const float* __restrict__ src, const int* __restrict__ soff, const fl
   }
 }
 
+// Point-to-plane (open3d 0.9 TransformationEstimationPointToPlane): k_icp_step's work split in two launches.
+//
+// k_icp_plane_partials, grid (B * parts): workgroup x is part x % parts of pair x / parts and owns the pair's source rows
+// [part R, (part + 1) R), R = kIcpPlaneRows (icp_plane_plan.hpp); a part behind the pair's rows returns.  It reads and resets
+// the keys and writes nn as k_icp_step does, and leaves one partial of kIcpPlaneSums doubles: |C|, sum d^2, and over the rows of
+// C with a finite normal the 21 upper entries of sum J J^T and the 6 of sum J r, J = [p x n ; n], r = (p - q) . n in fp64.
+// Thread t takes the rows t, t + 256 of the part in that order; the 64 lanes of a wave fold with an xor butterfly (both
+// operands of every add are the same two numbers in both lanes, so all lanes hold one sum), the four waves as (0 + 1) + (2 + 3).
+// A fixed tree over rows counted from the pair's first row: the partial depends on the pair's rows alone.
+__global__ void __launch_bounds__(kThreads)
+k_icp_plane_partials(const float* __restrict__ src, const int* __restrict__ soff, const float* __restrict__ tgt,
+                     const float* __restrict__ nrm, const int* __restrict__ toff, int parts, float tau2,
+                     const double* __restrict__ Tst, const int* __restrict__ done, unsigned long long* __restrict__ key,
+                     long long* __restrict__ nn, double* __restrict__ part) {
+  constexpr int kWaves = kThreads / 64;
+  static_assert(kWaves == 4 && kIcpPlaneRows % kThreads == 0, "the fold below is written for four waves and whole sweeps");
+  __shared__ double wsum[kWaves][kIcpPlaneSums];
+  const int b = blockIdx.x / parts, pt = blockIdx.x % parts, tid = threadIdx.x;
+  if (done[b]) return;
+  const int s0 = soff[b], ns = soff[b + 1] - s0, q0 = toff[b];
+  if ((long long)pt * kIcpPlaneRows >= ns) return;
+  const int r0 = pt * kIcpPlaneRows, left = ns - r0;     // rows of the pair from this part on (>= 1)
+  double T[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[e] = Tst[12 * (size_t)b + e];
+  double v[kIcpPlaneSums];
+#pragma unroll
+  for (int e = 0; e < kIcpPlaneSums; ++e) v[e] = 0.0;
+#pragma unroll
+  for (int u = 0; u < kIcpPlaneRows / kThreads; ++u) {
+    const int l = u * kThreads + tid;
+    if (l >= left) continue;
+    const size_t i = (size_t)s0 + r0 + l;
+    const unsigned long long kv = key[i];
+    key[i] = ~0ull;
+    const float d2 = __uint_as_float((unsigned)(kv >> 32));
+    const int j = (int)(kv & 0xffffffffull);
+    const bool in = kv != ~0ull && d2 < tau2;
+    nn[i] = in ? j : -1;
+    if (!in) continue;
+    v[0] += 1.0;
+    v[1] += (double)d2;
+    const float* n = nrm + 3 * (size_t)(q0 + j);
+    const float n0 = n[0], n1 = n[1], n2 = n[2];
+    if (!(isfinite(n0) && isfinite(n1) && isfinite(n2))) continue;
+    float p[3];
+    transform_row(T, src + 3 * i, p);
+    const float* q = tgt + 3 * (size_t)(q0 + j);
+    const double px = p[0], py = p[1], pz = p[2], nx = n0, ny = n1, nz = n2;
+    // (the products of two fp32 are exact in fp64: each entry of p x n is rounded once)
+    const double J[6] = {fma(py, nz, -(pz * ny)), fma(pz, nx, -(px * nz)), fma(px, ny, -(py * nx)), nx, ny, nz};
+    const double r = fma(px - (double)q[0], nx, fma(py - (double)q[1], ny, (pz - (double)q[2]) * nz));
+    int e = 2;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int c = a; c < 6; ++c) { v[e] = fma(J[a], J[c], v[e]); ++e; }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) v[23 + a] = fma(J[a], r, v[23 + a]);
+  }
+#pragma unroll
+  for (int e = 0; e < kIcpPlaneSums; ++e) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[e] += __shfl_xor(v[e], o, 64);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int e = 0; e < kIcpPlaneSums; ++e) wsum[tid >> 6][e] = v[e];
+  }
+  __syncthreads();
+  if (tid < kIcpPlaneSums)
+    part[((size_t)b * parts + pt) * kIcpPlaneSums + tid] = (wsum[0][tid] + wsum[1][tid]) + (wsum[2][tid] + wsum[3][tid]);
+}
+
+// One wave per pair.  Lane e < 29 adds entry e of the pair's partials in ascending part; lane 0 then does what k_icp_step does
+// with its sums (fitness, rmse, the convergence test, the outputs and `done` on stop) and otherwise solves A x = -b by LDL^T
+// without pivoting in a fixed order.  Pivot d_k is accepted when it is finite and d_k > 2^-40 A_kk (A_kk: the original diagonal
+// entry); a rejected pivot or an empty C leaves T as it is for this pass.  dT = [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)], T <- dT T.
+__global__ void __launch_bounds__(64)
+k_icp_plane_solve(const int* __restrict__ soff, int parts, const double* __restrict__ part, int k, int max_iter, double rel_f,
+                  double rel_r, double* __restrict__ Tst, double* __restrict__ prev, int* __restrict__ done,
+                  float* __restrict__ T_out, float* __restrict__ fit_out, float* __restrict__ rmse_out, int* __restrict__ it_out) {
+  __shared__ double acc[kIcpPlaneSums];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (done[b]) return;
+  const int ns = soff[b + 1] - soff[b], np = icp_plane_pair_parts(ns);
+  if (np > parts) {                                      // the caller's max_src was no bound for this pair: say so, loudly
+    if (tid < 12) T_out[16 * (size_t)b + tid] = NAN;
+    if (tid == 0) { fit_out[b] = 0.f; rmse_out[b] = 0.f; it_out[b] = -1; done[b] = 1; }
+    return;
+  }
+  if (tid < kIcpPlaneSums) {
+    // ascending p; sixteen loads are in flight before their adds, which keep that order (one load per add waits for each)
+    const double* mine = part + (size_t)b * parts * kIcpPlaneSums + tid;
+    double s = 0.0;
+    int p = 0;
+    for (; p + 16 <= np; p += 16) {
+      double x[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) x[u] = mine[(size_t)(p + u) * kIcpPlaneSums];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) s += x[u];
+    }
+    for (; p < np; ++p) s += mine[(size_t)p * kIcpPlaneSums];
+    acc[tid] = s;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  double T[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[e] = Tst[12 * (size_t)b + e];
+  const double nc = acc[0];
+  const double fit = nc / ns, rm = nc > 0 ? sqrt(acc[1] / nc) : 0.0;
+  bool stop = k >= max_iter;
+  if (k >= 1 && fabs(prev[2 * b] - fit) < rel_f && fabs(prev[2 * b + 1] - rm) < rel_r) stop = true;
+  prev[2 * b] = fit;
+  prev[2 * b + 1] = rm;
+  if (stop) {
+    float* To = T_out + 16 * (size_t)b;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) To[e] = (float)T[e];
+    To[12] = 0.f; To[13] = 0.f; To[14] = 0.f; To[15] = 1.f;
+    fit_out[b] = (float)fit;
+    rmse_out[b] = (float)rm;
+    it_out[b] = k;
+    done[b] = 1;
+    return;
+  }
+  if (nc == 0.0) return;                                 // empty C: dT = identity, T stays
+  double A[6][6], L[6][6], D[6], x[6];
+  {
+    int e = 2;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int c = a; c < 6; ++c) { A[a][c] = acc[e]; A[c][a] = acc[e]; ++e; }
+  }
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    double d = A[c][c];
+#pragma unroll
+    for (int m = 0; m < c; ++m) d -= (L[c][m] * L[c][m]) * D[m];
+    ok = ok && isfinite(d) && d > 0x1p-40 * A[c][c];
+    D[c] = d;
+#pragma unroll
+    for (int i = c + 1; i < 6; ++i) {
+      double l = A[i][c];
+#pragma unroll
+      for (int m = 0; m < c; ++m) l -= (L[i][m] * L[c][m]) * D[m];
+      L[i][c] = l / d;
+    }
+  }
+  if (!ok) return;                                       // a rejected pivot: dT = identity
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {                          // L y = -b
+    double y = -acc[23 + i];
+#pragma unroll
+    for (int m = 0; m < i; ++m) y -= L[i][m] * x[m];
+    x[i] = y;
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) x[i] /= D[i];
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {                         // L^T x = z
+#pragma unroll
+    for (int m = i + 1; m < 6; ++m) x[i] -= L[m][i] * x[m];
+  }
+  const double sx = sin(x[0]), cx = cos(x[0]), sy = sin(x[1]), cy = cos(x[1]), sz = sin(x[2]), cz = cos(x[2]);
+  const double R[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx,
+                       sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx,
+                       -sy,     cy * sx,                cy * cx};
+  double Tn[12];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      Tn[4 * r + c] = R[3 * r] * T[c] + R[3 * r + 1] * T[4 + c] + R[3 * r + 2] * T[8 + c] + (c == 3 ? x[3 + r] : 0.0);
+  }
+#pragma unroll
+  for (int e = 0; e < 12; ++e) Tst[12 * (size_t)b + e] = Tn[e];
+}
+
+void icp_plane_scratch_list(IcpPlaneScratch& s, ArenaList& bufs) { bufs.add(s.part, s.plan.partial_doubles); }
+
 void icp_scratch_list(long long total_src, int B, IcpScratch& s, ArenaList& bufs) {
   bufs.add(s.key, (size_t)total_src);
   bufs.add(s.T, (size_t)B * 12);
@@ -569,7 +758,7 @@ void icp_scratch_list(long long total_src, int B, IcpScratch& s, ArenaList& bufs
 hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, const int* tgt_off, int B, long long total_src,
                       int max_src, int max_tgt, const float* init, float tau, int max_iter, double rel_fitness, double rel_rmse,
                       const IcpScratch& ws, float* T_out, float* fitness, float* rmse, int* iterations, long long* nn,
-                      hipStream_t s, const KnnScratch* grid, long long total_tgt) {
+                      hipStream_t s, const KnnScratch* grid, long long total_tgt, const IcpPlaneScratch* plane) {
   hipError_t e = hipMemsetAsync(ws.key, 0xff, (size_t)total_src * 8, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_icp_init, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, s, init, B, ws.T, ws.prev, ws.done);
@@ -594,8 +783,15 @@ hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, co
     else
       hipLaunchKernelGGL(k_icp_nn, dim3((unsigned)wg, Y), dim3(kThreads), 0, s, src, src_off, tgt, tgt_off, stiles, ws.T, ws.done,
                          ws.key);
-    hipLaunchKernelGGL(k_icp_step, dim3(B), dim3(kThreads), 0, s, src, src_off, tgt, tgt_off, k, max_iter, tau2, rel_fitness,
-                       rel_rmse, ws.T, ws.prev, ws.done, ws.key, T_out, fitness, rmse, iterations, nn);
+    if (plane) {
+      hipLaunchKernelGGL(k_icp_plane_partials, dim3((unsigned)plane->plan.blocks), dim3(kThreads), 0, s, src, src_off, tgt,
+                         plane->normals, tgt_off, plane->plan.parts, tau2, ws.T, ws.done, ws.key, nn, plane->part);
+      hipLaunchKernelGGL(k_icp_plane_solve, dim3(B), dim3(64), 0, s, src_off, plane->plan.parts, plane->part, k, max_iter,
+                         rel_fitness, rel_rmse, ws.T, ws.prev, ws.done, T_out, fitness, rmse, iterations);
+    } else {
+      hipLaunchKernelGGL(k_icp_step, dim3(B), dim3(kThreads), 0, s, src, src_off, tgt, tgt_off, k, max_iter, tau2, rel_fitness,
+                         rel_rmse, ws.T, ws.prev, ws.done, ws.key, T_out, fitness, rmse, iterations, nn);
+    }
   }
   return hipGetLastError();
 }

@@ -25,8 +25,8 @@ from . import _lib
 from ._args import c_ints, check_offsets, fail, positive_finite, require_device, same_device
 from ._util import handle_and_stream
 from .common import rigid_transform_3d
-from .features import voxel_down_sample_batched
-from .solvers import icp_point_to_point_batched
+from .features import estimate_normals_batched, voxel_down_sample_batched
+from .solvers import check_estimation, icp_point_to_plane_batched, icp_point_to_point_batched
 
 STOP_REASONS = ("max_iteration", "min_right_term", "min_relative_increment", "min_relative_residual_increment", "min_residual",
                 "max_iteration_lm", "pivot")
@@ -255,7 +255,8 @@ def _gather_index(off, clouds, dev):
 
 
 def local_refinement_batched(points, cloud_offsets, edge_source, edge_target, init, voxel_size=(0.05, 0.025, 0.0125),
-                             max_iter=(50, 30, 14), max_correspondence_distance=0.05 * 1.4, memory_budget=1 << 30):
+                             max_iter=(50, 30, 14), max_correspondence_distance=0.05 * 1.4, memory_budget=1 << 30,
+                             estimation="point_to_point"):
     """The reference's `local_refinement` / `multi_scale_icp` (test_multi_ate.py:54-83) for E edges over F shared clouds.
 
     At each scale the F clouds are voxel-down-sampled ONCE (`voxel_down_sample_batched`), then every edge runs
@@ -263,6 +264,10 @@ def local_refinement_batched(points, cloud_offsets, edge_source, edge_target, in
     open3d's default relative criteria.  The information matrix is taken at the last scale with 1.4 x that voxel size
     (`information_matrix_batched`, over the shared clouds).  ICP takes one cloud pair per entry, so the edges are gathered in
     chunks whose packed source and target rows stay under `memory_budget` bytes.
+    estimation="point_to_plane" is open3d's multi-scale recipe instead: each scale estimates the normals of the F down-sampled
+    clouds ONCE (`estimate_normals_batched`, radius 2 x the voxel size, 30 neighbours), gathers them with each chunk's targets
+    (12 more bytes per target row in the budget) and runs `icp_point_to_plane_batched(search="grid")`.  The information matrix
+    is the same either way.
 
     init [E, 4, 4].  Returns transformation [E, 4, 4] float32 and info [E, 6, 6] float64.  Host traffic: the F + 1 offsets of the
     down-sampled clouds once per scale (the voxel call synchronises for its row count anyway); nothing per edge."""
@@ -274,6 +279,7 @@ def local_refinement_batched(points, cloud_offsets, edge_source, edge_target, in
     _check_transformations(init, E, "init", what)
     if len(voxel_size) != len(max_iter) or not len(max_iter):
         fail(what, "voxel_size and max_iter must have the same, non-zero length")
+    plane = check_estimation(what, "estimation", estimation)
     require_device(points, "points", what)
     require_device(init, "init", what)
     dev = points.device
@@ -284,20 +290,27 @@ def local_refinement_batched(points, cloud_offsets, edge_source, edge_target, in
     for scale, (vs, it) in enumerate(zip(voxel_size, max_iter)):
         down, doff_dev = voxel_down_sample_batched(points, off, float(vs))
         doff = doff_dev.tolist()
+        normals = estimate_normals_batched(down, doff, 2.0 * float(vs), 30) if plane else None
         per_row = 3 * 4 + 8                                           # a packed fp32 row and its nn
+        per_tgt = 3 * 4 if plane else 0                               # and a target row's normal
         k = 0
         while k < E:
-            rows, k1 = 0, k
+            used, k1 = 0, k                                           # (used: the chunk's bytes so far)
             while k1 < E:
-                need = (doff[src[k1] + 1] - doff[src[k1]]) + (doff[tgt[k1] + 1] - doff[tgt[k1]])
-                if k1 > k and (rows + need) * per_row > memory_budget:
+                n_tgt = doff[tgt[k1] + 1] - doff[tgt[k1]]
+                need = (doff[src[k1] + 1] - doff[src[k1]] + n_tgt) * per_row + n_tgt * per_tgt
+                if k1 > k and used + need > memory_budget:
                     break
-                rows += need
+                used += need
                 k1 += 1
             si, soff = _gather_index(doff, src[k:k1], dev)
             ti, toff = _gather_index(doff, tgt[k:k1], dev)
-            Tk = icp_point_to_point_batched(down[si], down[ti], T[k:k1].contiguous(), max_correspondence_distance, soff, toff,
-                                            max_iteration=int(it), search="grid")[0]
+            if plane:
+                Tk = icp_point_to_plane_batched(down[si], down[ti], normals[ti], T[k:k1].contiguous(), max_correspondence_distance,
+                                                soff, toff, max_iteration=int(it), search="grid")[0]
+            else:
+                Tk = icp_point_to_point_batched(down[si], down[ti], T[k:k1].contiguous(), max_correspondence_distance, soff, toff,
+                                                max_iteration=int(it), search="grid")[0]
             T = torch.cat([T[:k], Tk, T[k1:]])
             k = k1
         if scale == len(max_iter) - 1:
@@ -308,7 +321,7 @@ def local_refinement_batched(points, cloud_offsets, edge_source, edge_target, in
 def multiway_registration(points, cloud_offsets, pair_source, pair_target, pair_transformation, use_icp=True,
                           refine_odometry=True, max_correspondence_distance=0.05 * 1.4, min_overlap=0.30, edge_prune_threshold=0.25,
                           preference_loop_closure=20.0, reference_node=0, criteria=None, voxel_size=(0.05, 0.025, 0.0125),
-                          max_iter=(50, 30, 14), memory_budget=1 << 30):
+                          max_iter=(50, 30, 14), memory_budget=1 << 30, icp_estimation="point_to_point"):
     """`eval_redwood_scene` (test_multi_ate.py:86-227) from the pair poses on, for F fragments packed in `points` /
     `cloud_offsets` and E pairs (pair_source[e], pair_target[e]) with pair_transformation [E, 4, 4] (PointDSC's `final_trans` of
     `forward_ragged`, or any initial pose for the consecutive pairs).  Every consecutive pair (i, i + 1) must be among the pairs:
@@ -317,7 +330,7 @@ def multiway_registration(points, cloud_offsets, pair_source, pair_target, pair_
     (uncertain), with its information matrix at max_correspondence_distance and the overlap filter.  The poses start from the
     odometry chain; `global_optimization` prunes the false closures.  With use_icp every pair is refined and the graph is
     optimised a second time over the edges that survived the first (the refinement runs for the others too and is masked out:
-    which edges survived is not read back).
+    which edges survived is not read back).  icp_estimation: the `estimation` of every `local_refinement_batched` call.
 
     Returns a dict: "poses" [F, 4, 4] float64, "kept" [E] bool, "line_process" [E], "mask" [E] bool (the overlap filter),
     "transformation" [E, 4, 4] float64 and "information" [E, 6, 6] of the edges as optimised last, "stats" (of the last
@@ -328,6 +341,7 @@ def multiway_registration(points, cloud_offsets, pair_source, pair_target, pair_
     src, tgt = _check_edges(pair_source, pair_target, F, what)
     E = len(src)
     _check_transformations(pair_transformation, E, "pair_transformation", what)
+    check_estimation(what, "icp_estimation", icp_estimation)
     if F > MAX_NODES or E > MAX_EDGES:
         raise NotImplementedError(f"gmf_amd.{what}: {F} fragments and {E} pairs; the optimiser is built for at most {MAX_NODES} nodes and "
                                   f"{MAX_EDGES} edges")
@@ -348,7 +362,7 @@ def multiway_registration(points, cloud_offsets, pair_source, pair_target, pair_
     opt = dict(edge_prune_threshold=edge_prune_threshold, preference_loop_closure=preference_loop_closure,
                reference_node=reference_node, criteria=criteria)
     refine = dict(voxel_size=voxel_size, max_iter=max_iter, max_correspondence_distance=max_correspondence_distance,
-                  memory_budget=memory_budget)
+                  memory_budget=memory_budget, estimation=icp_estimation)
 
     # first graph: refined odometry edges, loop closures as PointDSC gave them
     X = pair_transformation.to(torch.float64).clone()

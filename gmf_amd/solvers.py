@@ -1,4 +1,4 @@
-"""Correspondence RANSAC, feature-matching RANSAC and point-to-point ICP on the device: the solvers the reference's evaluation scripts run after the network
+"""Correspondence RANSAC, feature-matching RANSAC and point-to-point and point-to-plane ICP on the device: the solvers the reference's evaluation scripts run after the network
 through open3d 0.9 / 0.10 on the CPU (GMF_PointDSC/evaluation/test_3DMatch.py:76-96, benchmark_utils.py:40-56;
 GMF_DeepGlobalRegistration/*/core/deep_global_registration.py:26-85, 256-276, 385-405).  Kernels: csrc/solver_kernels.hip.
 
@@ -22,6 +22,8 @@ RegistrationResult = collections.namedtuple("RegistrationResult", "transformatio
 _MAX_HYPOTHESES = 1 << 24
 _MAX_VALIDATION = 1 << 16
 _ICP_SEARCH = {"brute": 0, "grid": 1}
+_ICP_ESTIMATION = ("point_to_point", "point_to_plane")
+ICP_PLANE_ROWS = 512          # csrc/icp_plane_plan.hpp kIcpPlaneRows: the source rows of one partial sum of the point-to-plane step
 
 
 def ransac_correspondence_batched(src, tgt, max_correspondence_distance, offsets=None, mask=None, ransac_n=3,
@@ -89,7 +91,32 @@ def icp_point_to_point_batched(source, target, init, max_correspondence_distance
 
     Returns T [B,4,4] f32, fitness [B] (|C| / Ns), inlier_rmse [B], iterations [B] int32 (loop passes run) and nn (int64,
     source's leading shape: the matched target row within the pair, -1 outside C)."""
-    what = "icp_point_to_point_batched"
+    return _icp_batched("icp_point_to_point_batched", source, target, None, init, max_correspondence_distance, source_offsets,
+                        target_offsets, max_iteration, relative_fitness, relative_rmse, search)
+
+
+def icp_point_to_plane_batched(source, target, target_normals, init, max_correspondence_distance, source_offsets=None,
+                               target_offsets=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, search="brute"):
+    """Point-to-plane ICP over B pairs (open3d 0.9's registration_icp with TransformationEstimationPointToPlane).
+
+    The arguments of `icp_point_to_point_batched` and target_normals: float32 of target's shape, one normal per target row, used
+    as given (not renormalised; negating any of them changes no output bit).  C, nn, fitness, inlier_rmse (Euclidean), the loop
+    and the stopping rule are the point-to-point form's; only the update differs.  Over the rows of C whose normal is finite,
+    with p the transformed source row, q its target and n the normal: r = (p - q) . n, J = [p x n ; n], A = sum J J^T,
+    b = sum J r in fp64; A x = -b by LDL^T without pivoting, where a pivot d_k is accepted when it is finite and
+    d_k > 2^-40 A_kk; T <- [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)] T (fp64).  A rejected pivot or an empty C leaves T alone for
+    that pass.  The sums are taken per ICP_PLANE_ROWS source rows of a pair in a fixed tree: a pair's bits do not depend on
+    the batch or on the search.  tests/icp_plane_reference.py restates all of it in float64.
+
+    Returns T [B,4,4] f32, fitness [B], inlier_rmse [B], iterations [B] int32 and nn (int64, source's leading shape), as the
+    point-to-point form does.  No host synchronisation; the call can be captured into a graph."""
+    return _icp_batched("icp_point_to_plane_batched", source, target, target_normals, init, max_correspondence_distance,
+                        source_offsets, target_offsets, max_iteration, relative_fitness, relative_rmse, search, plane=True)
+
+
+def _icp_batched(what, source, target, normals, init, max_correspondence_distance, source_offsets, target_offsets, max_iteration,
+                 relative_fitness, relative_rmse, search, plane=False):
+    """The argument checks, the outputs and the call of both ICP forms (plane: target normals and gmf_icp_point_to_plane)."""
     if not isinstance(search, str) or search not in _ICP_SEARCH:
         fail(what, f'search must be "brute" or "grid" (got {search!r})')
     if (source_offsets is None) != (target_offsets is None):
@@ -99,6 +126,11 @@ def icp_point_to_point_batched(source, target, init, max_correspondence_distance
     check_rows(what, "target", target, dims, 3, non_empty=True)
     if dims == 3 and source.shape[0] != target.shape[0]:
         fail(what, f"source and target must hold the same number of pairs (got {source.shape[0]} / {target.shape[0]})")
+    if plane:
+        if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or normals.shape != target.shape:
+            fail(what, f"target_normals must be a float32 tensor of target's shape {tuple(target.shape)}, one normal per target row")
+        if normals.device != target.device:
+            fail(what, f"target_normals must live on target's device ({target.device}; got {normals.device})")
     if not isinstance(init, torch.Tensor) or init.dtype != torch.float32 or init.dim() != 3 or init.shape[1:] != (4, 4):
         fail(what, "init must be a float32 [B,4,4] tensor")
     tau = positive_finite(what, "max_correspondence_distance", max_correspondence_distance, rule="> 0")
@@ -136,7 +168,10 @@ def icp_point_to_point_batched(source, target, init, max_correspondence_distance
     h, st = handle_and_stream(S)
     args = (S.data_ptr(), dso.data_ptr(), Q.data_ptr(), dto.data_ptr(), B, ns_rows, max_s, max_t, T0.data_ptr(), tau, it, rf, rr,
             T.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), iters.data_ptr(), nn.data_ptr())
-    if search == "brute":
+    if plane:
+        Nn = normals.reshape(-1, 3).contiguous()
+        h.call("gmf_icp_point_to_plane", *args[:3], Nn.data_ptr(), *args[3:], nt_rows, _ICP_SEARCH[search], st)
+    elif search == "brute":
         h.call("gmf_icp_point_to_point", *args, st)
     else:
         h.call("gmf_icp_point_to_point_ex", *args, nt_rows, _ICP_SEARCH[search], st)
@@ -319,15 +354,28 @@ def registration_ransac_based_on_feature_matching(source, target, source_feature
     return RegistrationResult(T[0], torch.stack([rows, nn_out[rows]], 1), info[0], info[1])
 
 
+def check_estimation(what, name, estimation):
+    if not isinstance(estimation, str) or estimation not in _ICP_ESTIMATION:
+        fail(what, f'{name} must be "point_to_point" or "point_to_plane" (got {estimation!r})')
+    return estimation == "point_to_plane"
+
+
 def registration_icp(source, target, max_correspondence_distance, init=None, max_iteration=30, relative_fitness=1e-6,
-                     relative_rmse=1e-6, search="brute"):
+                     relative_rmse=1e-6, search="brute", estimation="point_to_point", target_normals=None):
     """open3d.registration.registration_icp with TransformationEstimationPointToPoint(): source [Ns,3], target [Nt,3] (tensors
     or numpy), init [4,4] (default identity); search: "brute" or "grid", as in icp_point_to_point_batched.
+    estimation="point_to_plane" is TransformationEstimationPointToPlane() and takes target_normals [Nt,3] (open3d reads them
+    from the target cloud), as in icp_point_to_plane_batched.
     -> RegistrationResult(transformation [4,4] f32 on the device, correspondence_set [K,2] int64 on the device (source row,
     nearest target row) of the final C, fitness, inlier_rmse)."""
     what = "registration_icp"
     if not isinstance(search, str) or search not in _ICP_SEARCH:
         fail(what, f'search must be "brute" or "grid" (got {search!r})')
+    plane = check_estimation(what, "estimation", estimation)
+    if plane and target_normals is None:
+        fail(what, 'estimation="point_to_plane" needs target_normals')
+    if plane and not isinstance(target_normals, (torch.Tensor, np.ndarray)):
+        fail(what, "target_normals must be a tensor or a NumPy array")
     dev = _device_of(source, target, init)
     require_device(dev, "the points", what)
     S = _on_device(source, dev, torch.float32)
@@ -335,9 +383,14 @@ def registration_icp(source, target, max_correspondence_distance, init=None, max
     T0 = torch.eye(4, device=dev) if init is None else _on_device(init, dev, torch.float32)
     if T0.shape != (4, 4):
         fail(what, f"init must be [4,4] (got {tuple(T0.shape)})")
-    T, fit, rmse, _, nn = icp_point_to_point_batched(S[None], Q[None], T0[None], max_correspondence_distance,
-                                                     max_iteration=max_iteration, relative_fitness=relative_fitness,
-                                                     relative_rmse=relative_rmse, search=search)
+    crit = dict(max_iteration=max_iteration, relative_fitness=relative_fitness, relative_rmse=relative_rmse, search=search)
+    if plane:
+        Nn = _on_device(target_normals, dev, torch.float32)
+        if Nn.shape != Q.shape:
+            fail(what, f"target_normals must be [Nt,3], one normal per target row (got {tuple(Nn.shape)} for {tuple(Q.shape)})")
+        T, fit, rmse, _, nn = icp_point_to_plane_batched(S[None], Q[None], Nn[None], T0[None], max_correspondence_distance, **crit)
+    else:
+        T, fit, rmse, _, nn = icp_point_to_point_batched(S[None], Q[None], T0[None], max_correspondence_distance, **crit)
     nn = nn[0]
     info = torch.stack([fit[0], rmse[0], (nn >= 0).sum().float()]).cpu().tolist()   # the one synchronisation
     rows = torch.nonzero_static(nn >= 0, size=int(info[2])).view(-1)

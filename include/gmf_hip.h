@@ -45,7 +45,7 @@ enum {
 #define GMF_ABI_VERSION 5   /* 5: gmf_encoder_weights gained `pv_guard` (a caller that fills the struct itself must be rebuilt; one that uses
                              * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  gmf_icp_point_to_point_ex and
                              * gmf_ransac_feature_matching, then gmf_spectral_matching, then gmf_max_clique and gmf_pmc_graph, then gmf_tsdf_allocate, gmf_tsdf_integrate and gmf_tsdf_extract, then gmf_rgbd_pyramids, gmf_rgbd_correspondences and
-                             * gmf_rgbd_odometry, then gmf_tsdf_integrate_color and gmf_tsdf_extract_color joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
+                             * gmf_rgbd_odometry, then gmf_tsdf_integrate_color and gmf_tsdf_extract_color, then gmf_icp_point_to_plane joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
                              * pose head / pick_seeds take any N */
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
@@ -595,6 +595,24 @@ int gmf_icp_point_to_point_ex(gmf_handle* h, const float* src, const int* src_of
                               int B, long long total_src, int max_src, int max_tgt, const float* init, float tau, int max_iter,
                               double rel_fitness, double rel_rmse, float* T_out, float* fitness, float* inlier_rmse,
                               int* iterations, long long* nn, long long total_tgt, int search, gmf_stream_t stream);
+
+/* registration_icp with TransformationEstimationPointToPlane (open3d 0.9) over B ragged pairs [joined under ABI 5: an added
+ * entry point].  The arguments, the correspondence set C, nn, fitness, inlier_rmse (Euclidean), the loop and its stopping rule
+ * are gmf_icp_point_to_point_ex's; tgt_normals [total_tgt,3] fp32 holds one normal per target row, used as given (not
+ * renormalised, any sign: negating normals changes no output bit).  Only the update differs: over the rows of C whose normal is
+ * finite, with p the transformed source row, q its target and n the target's normal, r = (p - q) . n and J = [p x n ; n] in
+ * fp64, A = sum J J^T, b = sum J r; A x = -b is solved by LDL^T without pivoting, a pivot d_k being accepted when it is finite
+ * and d_k > 2^-40 A_kk (the original diagonal entry); T <- [Rz(x2) Ry(x1) Rx(x0) | (x3, x4, x5)] T in fp64.  A rejected pivot
+ * or an empty C leaves T as it is for that pass (the loop then normally stops at the next comparison).  max_src: an upper bound
+ * of every pair's source rows (<= 0: total_src is taken); here it sizes the grid of the split step, and a pair with more rows
+ * than it comes back with NaN in T_out and iterations -1.  The sums are taken per 512 source rows of a pair in a fixed tree, then
+ * in ascending order: no float atomics, and a pair's bits do not depend on the batch, on max_src or on the search.
+ * 3 max_iter + 5 launches (search 1: four more); no host synchronisation; graph-capturable. */
+int gmf_icp_point_to_plane(gmf_handle* h, const float* src, const int* src_offsets, const float* tgt, const float* tgt_normals,
+                           const int* tgt_offsets, int B, long long total_src, int max_src, int max_tgt, const float* init,
+                           float tau, int max_iter, double rel_fitness, double rel_rmse, float* T_out, float* fitness,
+                           float* inlier_rmse, int* iterations, long long* nn, long long total_tgt, int search,
+                           gmf_stream_t stream);
 
 /* registration_ransac_based_on_feature_matching (GMF_DeepGlobalRegistration/.../core/deep_global_registration.py:26-54) over B
  * ragged pairs: src [total_src,3] with src_offsets [B+1], tgt [total_tgt,3] with tgt_offsets [B+1] (device int32; a pair may have

@@ -4,6 +4,8 @@ The per-kernel averages of the stats file mix working launches with those of a f
 the trace (*_kernel_trace.csv), splits it into calls at k_icp_init, keeps the calls of 11 passes (both criteria at 0,
 max_iteration = 10: every pass runs) and prints medians over passes 0..9: the search kernel, k_icp_step, the last step (pass
 10 stops before the Umeyama update) and, for the grid, the sum of launch_grid_build's four kernels.
+A trace of `tools/time_solvers.py --plane-shape SHAPE` also holds point-to-plane calls (k_icp_plane_partials, k_icp_plane_solve
+in place of k_icp_step); they get a line of their own.
 Usage: python tools/icp_trace_passes.py TRACE.csv [TRACE.csv ...]"""
 import csv
 import statistics as st
@@ -16,7 +18,7 @@ def passes(path):
     for r in rows:
         n, dur = r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
         if "k_icp_init" in n:
-            cur = {"nn": [], "step": [], "build": [], "grid": False}
+            cur = {"nn": [], "step": [], "build": [], "grid": False, "partials": [], "solve": []}
             calls.append(cur)
         elif cur is None:
             continue
@@ -27,10 +29,16 @@ def passes(path):
             cur["nn"].append(dur)
         elif "k_icp_step" in n:
             cur["step"].append(dur)
+        elif "k_icp_plane_partials" in n:
+            cur["partials"].append(dur)
+        elif "k_icp_plane_solve" in n:
+            cur["solve"].append(dur)
         elif "k_grid_count" in n or "k_grid_scatter" in n or "rocprim" in n:
             cur["build"].append(dur)
     for grid in (False, True):
-        c11 = [c for c in calls if len(c["nn"]) == 11 and c["grid"] == grid]
+        c11 = [c for c in calls if len(c["nn"]) == 11 and c["grid"] == grid and len(c["step"]) == 11]
+        if not c11:
+            continue
         nn = [x for c in c11 for x in c["nn"][:10]]
         step = [x for c in c11 for x in c["step"][:10]]
         last = [c["step"][10] for c in c11]
@@ -40,6 +48,13 @@ def passes(path):
         if build:
             line += f", build kernels {st.median(build):.1f} us (median of {len(build)} calls)"
         print(line)
+    p11 = [c for c in calls if len(c["nn"]) == 11 and len(c["partials"]) == 11]
+    if p11:
+        def med(k):
+            x = [v for c in p11 for v in c[k][:10]]
+            return f"{st.median(x):.1f} [{min(x):.1f}, {max(x):.1f}] us"
+        print(f"{path}: point-to-plane {len(p11)} calls; search {med('nn')}, k_icp_plane_partials {med('partials')}, "
+              f"k_icp_plane_solve {med('solve')}")
 
 
 if __name__ == "__main__":

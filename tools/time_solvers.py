@@ -16,6 +16,12 @@
                     process, so that the per-kernel averages belong to one size; shapes: keypoints, 10k, 50k).
                     tools/icp_trace_passes.py picks the working passes out of such a trace.
   ICP crossover     whole calls, brute against grid, at keypoint pairs of 125 ... 2000 rows.
+  ICP point-to-plane   icp_point_to_point_batched against icp_point_to_plane_batched on the "ICP search" shapes, both with
+                    search="grid", alternated call by call in this one process; the targets' normals come from
+                    estimate_normals_batched (radius 2 tau, 30 neighbours) outside the timed region.  Whole calls at the default
+                    criteria (the two estimators run different numbers of passes), then t0 and t10 as above: one pass is the
+                    same search and k_icp_step in one column, k_icp_plane_partials + k_icp_plane_solve in the other, so the
+                    difference of the columns is the difference of the steps (--plane-shape runs this block alone).
   feature-matching RANSAC   DGR's call: ransac_n = 4, the distance checker and tau at 2 voxels (0.10), 80 000 proposals, 1000
                     validations; clouds of 10k / 10k and 50k / 50k points (40 % of the feature matches right, the others random)
                     and keypoints 5000 / 5000.  The whole call with search="grid", and search="brute" beside it where the
@@ -111,6 +117,30 @@ def icp_search_rows(report, repeats, dev, keys=ICP_SHAPES):
         report(f"    grid build                  | {(g0 - b0) + (pb - pg):9.1f}   ((t0 grid - t0 brute) + (pass brute - pass grid))")
 
 
+def icp_plane_rows(report, repeats, dev, keys=ICP_SHAPES):
+    """Point-to-point against point-to-plane (the module docstring's "ICP point-to-plane")."""
+    report("ICP point-to-plane: point-to-point | point-to-plane, search=\"grid\", alternated; us, median")
+    for name, s, q, T0, tau in (icp_shape(k) for k in keys):
+        s, q, T0 = s.to(dev), q.to(dev), T0.to(dev)
+        n = gmf_amd.estimate_normals_batched(q[0], [0, q.shape[1]], 2 * tau, 30)[None]
+
+        def call(plane, **kw):
+            if plane:
+                return lambda: gmf_amd.icp_point_to_plane_batched(s, q, n, T0, tau, search="grid", **kw)
+            return lambda: gmf_amd.icp_point_to_point_batched(s, q, T0, tau, search="grid", **kw)
+
+        its = [int(call(k)()[3][0]) for k in (False, True)]
+        every = dict(relative_fitness=0.0, relative_rmse=0.0)
+        fns = [call(k, **kw) for kw in ({}, dict(max_iteration=0, **every), dict(max_iteration=10, **every)) for k in (False, True)]
+        (wa, wb, a0, b0, a10, b10) = timed_alternating(fns, repeats)
+        pa, pb = (a10 - a0) / 10, (b10 - b0) / 10
+        report(f"  {name}: {its[0]} | {its[1]} passes at the default criteria")
+        report(f"    whole call        {wa:9.1f} | {wb:9.1f}")
+        report(f"    max_iteration=0   {a0:9.1f} | {b0:9.1f}   (init, the grid build, one search, one evaluation)")
+        report(f"    one pass          {pa:9.1f} | {pb:9.1f}   (search + k_icp_step | search + k_icp_plane_partials + "
+               f"k_icp_plane_solve; the steps differ by {pb - pa:.1f})")
+
+
 def icp_crossover_rows(report, repeats, dev):
     """Whole calls at small keypoint pairs (tau = 0.10, default criteria, gt pose as init), to find the size below which the
     grid's four extra launches cost more than its search saves."""
@@ -185,6 +215,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--icp-shape", choices=ICP_SHAPES, default=None, help="only the ICP search rows of one shape (for a kernel trace)")
+    ap.add_argument("--plane-shape", choices=ICP_SHAPES + ("all",), default=None,
+                    help="only the point-to-plane rows of one shape, or of all three")
     ap.add_argument("--fm-shape", choices=FM_SHAPES, default=None,
                     help="only the feature-matching RANSAC rows of one shape (for a kernel trace)")
     a = ap.parse_args()
@@ -199,6 +231,9 @@ def main():
     report(f"device: {torch.cuda.get_device_name(0)}; median [min, max] over {a.repeats} repeats, device events")
     if a.icp_shape:
         icp_search_rows(report, a.repeats, dev, (a.icp_shape,))
+        return
+    if a.plane_shape:
+        icp_plane_rows(report, a.repeats, dev, ICP_SHAPES if a.plane_shape == "all" else (a.plane_shape,))
         return
     if a.fm_shape:
         fm_rows(report, a.repeats, dev, (a.fm_shape,))
@@ -243,6 +278,7 @@ def main():
                f"nearest-neighbour pass, {N * N / per * 1e-3:.0f} G distance tests/s)")
     icp_search_rows(report, a.repeats, dev)
     icp_crossover_rows(report, a.repeats, dev)
+    icp_plane_rows(report, a.repeats, dev)
     fm_rows(report, a.repeats, dev)
     if a.out:
         with open(a.out, "w") as f:
