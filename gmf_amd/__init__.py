@@ -28,7 +28,8 @@ from . import fcgf, dgr                          # noqa: F401  (gmf_amd.fcgf.Res
 from .dgr import matching_indices_batched, find_correct_correspondence, generate_inlier_input   # noqa: F401
 from .multiway import (information_matrix_batched, global_optimization, local_refinement_batched, loop_closure_mask,  # noqa: F401
                        odometry_poses, absolute_trajectory_error, multiway_registration)
-from .fragments import tsdf_fragments, tsdf_fragments_colored            # noqa: F401
+from .fragments import (TsdfMeshes, tsdf_extract_mesh, tsdf_fragment_meshes, tsdf_fragments,      # noqa: F401
+                        tsdf_fragments_colored)
 from .rgbd import rgbd_pyramids, rgbd_correspondence_map, rgbd_odometry, rgbd_fragments, RGBDPyramids   # noqa: F401
 from .losses import ClassificationLoss, SpectralMatchingLoss, TransformationLoss, similarity_matrix   # noqa: F401
 
@@ -46,5 +47,6 @@ __all__ = ["FusionLayer", "PerceiverIO", "NonLocalBlock", "NonLocalNet", "PointD
            "registration_ransac_based_on_feature_matching", "spectral_matching_batched", "SM", "max_clique_batched", "PMC",
            "compatibility_graph", "information_matrix_batched",
            "global_optimization", "local_refinement_batched", "loop_closure_mask", "odometry_poses", "absolute_trajectory_error",
-           "multiway_registration", "tsdf_fragments", "tsdf_fragments_colored", "rgbd_pyramids", "rgbd_correspondence_map",
+           "multiway_registration", "tsdf_fragments", "tsdf_fragments_colored", "tsdf_fragment_meshes", "tsdf_extract_mesh",
+           "TsdfMeshes", "rgbd_pyramids", "rgbd_correspondence_map",
            "rgbd_odometry", "rgbd_fragments", "RGBDPyramids"]

@@ -235,6 +235,8 @@ SIGNATURES = {
                                            _vp, _vp, _vp, _vp]),
     "gmf_tsdf_extract_color": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, _vp, _vp, _ll, _vp, C.POINTER(_ll),
                                          _vp]),
+    "gmf_tsdf_extract_mesh": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp,
+                                        C.POINTER(_ll), C.POINTER(_ll), _vp]),
     "gmf_rgbd_pyramids": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_double] * 4 + [C.c_int, _vp, _vp]),
     "gmf_rgbd_correspondences": (C.c_int, [_vp, _vp] + [C.c_int] * 5 + [_vp, _vp, C.c_int, _vp] + [C.c_double] * 5 + [_vp, _vp]),
     "gmf_rgbd_odometry": (C.c_int, [_vp, _vp] + [C.c_int] * 4 + [_vp, _vp, C.c_int, _vp] + [C.c_double] * 5 + [_vp] * 8),

@@ -1166,6 +1166,44 @@ int gmf_tsdf_extract_color(gmf_handle* h, const int* unit_keys, const int* unit_
                       points_out, colors_out, max_points, point_offsets_out, num_points, stream);
 }
 
+int gmf_tsdf_extract_mesh(gmf_handle* h, const int* unit_keys, const int* unit_offsets, int G, int num_units, const float* tsdf,
+                          const float* weight, const float* color, double voxel_length, float* points_out, float* normals_out,
+                          float* colors_out, long long max_points, int* triangles_out, long long max_triangles, int* point_offsets_out,
+                          int* triangle_offsets_out, long long* num_points, long long* num_triangles, gmf_stream_t stream) {
+  const std::string w("tsdf_extract_mesh");
+  const bool emit = points_out || normals_out || colors_out || triangles_out;
+  GMF_REQUIRE(h && unit_offsets && point_offsets_out && triangle_offsets_out, GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(emit || (num_points && num_triangles), GMF_ERR_BAD_ARG,
+              w + ": without outputs the call counts into num_points and num_triangles");
+  GMF_REQUIRE(!emit || (points_out && normals_out && triangles_out && (!color == !colors_out)), GMF_ERR_BAD_ARG,
+              w + ": points_out, normals_out and triangles_out are written together, and colors_out exactly with color");
+  GMF_REQUIRE(G >= 1 && G <= gmf::kTsdfMaxFragments, GMF_ERR_UNSUPPORTED_SHAPE, w + ": G must be in 1..65535");
+  GMF_REQUIRE(num_units >= 0 && num_units <= (1 << 22), GMF_ERR_BAD_ARG, w + ": num_units must be in 0..2^22");
+  GMF_REQUIRE(num_units == 0 || (unit_keys && tsdf && weight), GMF_ERR_BAD_ARG, w + ": null pointer");
+  GMF_REQUIRE(voxel_length > 0 && std::isfinite(voxel_length), GMF_ERR_BAD_ARG, w + ": voxel_length must be finite and > 0");
+  GMF_REQUIRE(max_points >= 0 && max_triangles >= 0, GMF_ERR_BAD_ARG, w + ": max_points and max_triangles must be >= 0");
+  SetDevice sd(h, stream);
+  if (num_units == 0) {
+    GMF_HIP(hipMemsetAsync(point_offsets_out, 0, ((size_t)G + 1) * 4, S(stream)));
+    GMF_HIP(hipMemsetAsync(triangle_offsets_out, 0, ((size_t)G + 1) * 4, S(stream)));
+    if (!emit) *num_points = *num_triangles = 0;
+    return GMF_OK;
+  }
+  gmf::TsdfMeshScratch ws;
+  ArenaList bufs;
+  gmf::tsdf_mesh_scratch_list(num_units, ws, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  int host_counts[2] = {0, 0};
+  GMF_HIP(gmf::launch_tsdf_extract_mesh(unit_keys, unit_offsets, G, num_units, tsdf, weight, color, voxel_length, ws, points_out,
+                                        normals_out, colors_out, max_points, triangles_out, max_triangles, point_offsets_out,
+                                        triangle_offsets_out, host_counts, S(stream)));
+  if (!emit) {
+    *num_points = host_counts[0];
+    *num_triangles = host_counts[1];
+  }
+  return GMF_OK;
+}
+
 int gmf_rgbd_pyramids(gmf_handle* h, const void* color, int color_kind, const void* depth, int depth_is_u16, int F, int H, int W,
                       double depth_scale, double depth_trunc, double min_depth, double max_depth, int levels, float* planes_out,
                       gmf_stream_t stream) {

@@ -1,6 +1,6 @@
 // Internal C++ launch entry points of the fragment builder (tsdf_kernels.hip): TSDF fusion of posed depth frames to a cloud.
 // Public C ABI: include/gmf_hip.h (gmf_tsdf_allocate, gmf_tsdf_integrate, gmf_tsdf_extract, and the RGB8 forms
-// gmf_tsdf_integrate_color, gmf_tsdf_extract_color).
+// gmf_tsdf_integrate_color, gmf_tsdf_extract_color; the mesh: gmf_tsdf_extract_mesh).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -93,5 +93,31 @@ void tsdf_extract_scratch_list(int U, TsdfExtractScratch& ws, ArenaList& bufs);
 hipError_t launch_tsdf_extract(const int* unit_keys, const int* unit_offsets, int G, int U, const float* tsdf, const float* weight,
                                const float* color, double voxel_length, const TsdfExtractScratch& ws, float* points, float* colors,
                                long long max_points, int* point_offsets, int* host_count, hipStream_t s);
+
+// The device buffers of one gmf_tsdf_extract_mesh call.
+struct TsdfMeshScratch {
+  long long T = 0;
+  size_t tmp_bytes = 0;
+  unsigned long long* table = nullptr;        // [T] packed key -> slot
+  int* unit_of = nullptr;                     // [T] the slot's unit
+  int* count = nullptr;                       // [U + 1] vertices of each unit (0 at [U])
+  int* start = nullptr;                       // [U + 1] exclusive scan of count
+  int* tri_count = nullptr;                   // [U + 1] triangles of each unit (0 at [U])
+  int* tri_start = nullptr;                   // [U + 1] exclusive scan of tri_count
+  unsigned char* flags = nullptr;             // [U,4096] bit `axis`: the voxel's edge along that axis yields a vertex
+  int* col_before = nullptr;                  // [U,256] the unit's vertices before column (x, y)
+  int* totals = nullptr;                      // [2] the call's vertices and triangles, read back together
+  char* tmp = nullptr;
+};
+void tsdf_mesh_scratch_list(int U, TsdfMeshScratch& ws, ArenaList& bufs);
+
+// The mesh of the volume.  points null: counts only - point_offsets and triangle_offsets
+// [G+1] are written and the vertex and triangle counts go to host_counts[0..1] after synchronising the stream.  Otherwise points
+// and normals [max_points,3], colors [max_points,3] (with `color`) and triangles [max_triangles,3] are written as well, a row past
+// its cap dropped, and nothing is read back.  Triangle entries count from the fragment's first vertex.
+hipError_t launch_tsdf_extract_mesh(const int* unit_keys, const int* unit_offsets, int G, int U, const float* tsdf, const float* weight,
+                                    const float* color, double voxel_length, const TsdfMeshScratch& ws, float* points, float* normals,
+                                    float* colors, long long max_points, int* triangles, long long max_triangles, int* point_offsets,
+                                    int* triangle_offsets, int* host_counts, hipStream_t s);
 
 }  // namespace gmf

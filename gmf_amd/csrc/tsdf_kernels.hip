@@ -415,6 +415,321 @@ __global__ void k_tsdf_point_offsets(const int* __restrict__ unit_off, int G, co
   if (g <= G) point_off[g] = start[unit_off[g]];
 }
 
+// ---- the mesh: triangles and vertex normals (steps 5 and 6) ------------------------------------------------------------------
+//
+// k_tsdf_extract above stays as it is; these are new forms beside it, one workgroup per unit over the same 18^3 halo.
+//   k_tsdf_mesh_count      vertices and triangles of every unit, and what turns (voxel, axis) into a vertex index without a hash
+//                          of edges: a byte per voxel with the three "this axis yields a vertex" bits, and the unit's vertex count
+//                          before each (x, y) column
+//   k_tsdf_mesh_vertices   step 4's positions (and 4c's colours) with the same statements, and each vertex's normal by gather:
+//                          the triangles of the up to four cubes around its edge, recomputed from the halo in ascending triangle
+//                          order - no triangle list, no float atomics
+//   k_tsdf_mesh_triangles  thread (x, y) emits the triangles of its 16 cube origins, consecutive in output order
+
+// The case table (tools/gen_mc_table.py writes the rows from gmf_amd/_mc_table.py).  In constant address space: a row is one
+// 16-byte load, per cube and not per entry, and the table's 4 KB stay in cache; the workgroup's LDS keeps to the halo.
+__constant__ __attribute__((aligned(16))) signed char kTriTable[256][16] = {
+#include "tsdf_mc_table.inc"
+};
+
+struct TriRow { unsigned long long lo, hi; };      // the 16 entries of a row; -1 (0xff) ends it
+GMF_DEVINL TriRow tri_row(int cube_case) {
+  const ulonglong2 r = *reinterpret_cast<const ulonglong2*>(kTriTable[cube_case]);
+  return {r.x, r.y};
+}
+GMF_DEVINL int row_entry(const TriRow& r, int i) {      // 0..11, or -1
+  return (int)(signed char)((i < 8 ? r.lo >> (8 * i) : r.hi >> (8 * (i - 8))) & 0xff);
+}
+GMF_DEVINL int row_triangles(const TriRow& r) {
+  const unsigned long long ends = 0x8080808080808080ull;
+  return (16 - __popcll(r.lo & ends) - __popcll(r.hi & ends)) / 3;
+}
+
+// cube edge e starts at the cube's origin + (code & 1, (code >> 1) & 1, (code >> 2) & 1) and runs along axis code >> 3
+constexpr int kEdgeCode[12] = {0, 9, 2, 8, 4, 13, 6, 12, 16, 17, 19, 18};
+constexpr unsigned long long pack_edge_codes() {
+  unsigned long long v = 0;
+  for (int e = 0; e < 12; ++e) v |= (unsigned long long)kEdgeCode[e] << (5 * e);
+  return v;
+}
+constexpr unsigned long long kEdgeCodes = pack_edge_codes();
+GMF_DEVINL int edge_code(int e) { return (int)((kEdgeCodes >> (5 * e)) & 31); }
+
+// nbr[] and the halo, as k_tsdf_extract fills them
+GMF_DEVINL void load_halo(const int* __restrict__ unit_keys, int u, int g, const float* __restrict__ tsdf,
+                          const float* __restrict__ weight, unsigned long long tmask, const unsigned long long* __restrict__ table,
+                          const int* __restrict__ unit_of, int* k, float* val, int* nbr) {
+  k[0] = unit_keys[3 * (size_t)u];
+  k[1] = unit_keys[3 * (size_t)u + 1];
+  k[2] = unit_keys[3 * (size_t)u + 2];
+  if (threadIdx.x < 27) {
+    const int x = k[0] + (int)threadIdx.x / 9 - 1, y = k[1] + ((int)threadIdx.x / 3) % 3 - 1, z = k[2] + (int)threadIdx.x % 3 - 1;
+    int n = -1;
+    if (threadIdx.x == 13) {
+      n = u;
+    } else if (abs(x) <= kTsdfMaxIndex && abs(y) <= kTsdfMaxIndex && abs(z) <= kTsdfMaxIndex) {
+      const long long h = table_find(table, tmask, pack_key(g, x, y, z), cell_hash(g, x, y, z) & tmask);
+      if (h >= 0) n = unit_of[h];
+    }
+    nbr[threadIdx.x] = n;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kHaloVoxels; i += kThreads) {
+    const int hx = i / (kHalo * kHalo) - 1, hy = (i / kHalo) % kHalo - 1, hz = i % kHalo - 1;      // -1..16
+    const int n = nbr[((hx < 0 ? 0 : hx > 15 ? 2 : 1) * 3 + (hy < 0 ? 0 : hy > 15 ? 2 : 1)) * 3 + (hz < 0 ? 0 : hz > 15 ? 2 : 1)];
+    float v = __builtin_nanf("");
+    if (n >= 0) {
+      const size_t at = (size_t)n * kTsdfUnitVoxels + (((hx & 15) * kTsdfRes + (hy & 15)) * kTsdfRes + (hz & 15));
+      if (weight[at] > 0.f) v = tsdf[at];
+    }
+    val[i] = v;
+  }
+  __syncthreads();
+}
+
+// step 5's case of the cube with origin (x, y, z) (halo coordinates, 0..16), or -1 unless all eight corners are observed
+GMF_DEVINL int cube_case(const float* val, int x, int y, int z) {
+  int c = 0;
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {      // corner i at shift[i] = (0,0,0) (1,0,0) (1,1,0) (0,1,0) (0,0,1) (1,0,1) (1,1,1) (0,1,1)
+    const float v = val[halo_at(x + (((i + 1) >> 1) & 1), y + ((i >> 1) & 1), z + (i >> 2))];
+    ok = ok && v == v;
+    c |= (v < 0.f ? 1 : 0) << i;
+  }
+  return ok ? c : -1;
+}
+
+// step 4's position of the vertex on the edge from halo voxel (hx, hy, hz) along `axis`, as the float32 that is returned
+GMF_DEVINL void edge_point(const float* val, const int* k, int hx, int hy, int hz, int axis, double voxel_length, double* p) {
+  const int a = halo_at(hx, hy, hz);
+  const double da = fabs((double)val[a]), db = fabs((double)val[a + (axis == 0 ? kHalo * kHalo : axis == 1 ? kHalo : 1)]);
+  const double move = (da * voxel_length) / (da + db);
+  const double px = ((double)(kTsdfRes * k[0] + hx - 1) + 0.5) * voxel_length, py = ((double)(kTsdfRes * k[1] + hy - 1) + 0.5) * voxel_length,
+               pz = ((double)(kTsdfRes * k[2] + hz - 1) + 0.5) * voxel_length;
+  p[0] = (double)(float)(axis == 0 ? px + move : px);
+  p[1] = (double)(float)(axis == 1 ? py + move : py);
+  p[2] = (double)(float)(axis == 2 ? pz + move : pz);
+}
+
+// step 6 for the vertex on the edge from local voxel (lx, ly, z) along AXIS: the cubes around the edge in (unit, local index)
+// order - the units of one workgroup's halo are listed in the order of their nbr[] slot - and of each the triangles that use the
+// edge, in row order: ascending triangle index
+template <int AXIS>
+GMF_DEVINL void vertex_normal(const float* val, const int* k, int lx, int ly, int z, double voxel_length, float* out) {
+  constexpr int P = AXIS == 0 ? 1 : 0, Q = AXIS == 2 ? 1 : 2;
+  const int a[3] = {lx + 1, ly + 1, z + 1};
+  int key[4], cs[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    int o[3] = {a[0], a[1], a[2]};
+    o[P] -= c >> 1;
+    o[Q] -= c & 1;
+    cs[c] = cube_case(val, o[0], o[1], o[2]);
+    const int slot = ((o[0] == 0 ? 0 : 1) * 3 + (o[1] == 0 ? 0 : 1)) * 3 + (o[2] == 0 ? 0 : 1);
+    const int local = (((o[0] - 1) & 15) * kTsdfRes + ((o[1] - 1) & 15)) * kTsdfRes + ((o[2] - 1) & 15);
+    key[c] = cs[c] >= 0 ? slot * kTsdfUnitVoxels + local : 0x7fffffff;
+  }
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  int done = 0;
+  for (int round = 0; round < 4; ++round) {
+    int best = -1, best_key = 0x7fffffff, best_case = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (!((done >> c) & 1) && key[c] < best_key) {
+        best = c;
+        best_key = key[c];
+        best_case = cs[c];
+      }
+    if (best < 0) break;
+    done |= 1 << best;
+    const int dp = best >> 1, dq = best & 1;
+    int o[3] = {a[0], a[1], a[2]};
+    o[P] -= dp;
+    o[Q] -= dq;
+    const int e = AXIS == 0 ? 2 * dp + 4 * dq : AXIS == 1 ? 3 - 2 * dp + 4 * dq : 8 + (dq ? 3 - dp : dp);      // this edge, in that cube
+    const TriRow row = tri_row(best_case);
+    for (int t = 0; t < 5; ++t) {
+      const int e0 = row_entry(row, 3 * t), e1 = row_entry(row, 3 * t + 1), e2 = row_entry(row, 3 * t + 2);
+      if (e0 < 0) break;
+      if (e0 != e && e1 != e && e2 != e) continue;
+      double pi[3], pj[3], pl[3];      // the triangle (v(e0), v(e2), v(e1))
+      const int c0 = edge_code(e0), c1 = edge_code(e2), c2 = edge_code(e1);
+      edge_point(val, k, o[0] + (c0 & 1), o[1] + ((c0 >> 1) & 1), o[2] + ((c0 >> 2) & 1), c0 >> 3, voxel_length, pi);
+      edge_point(val, k, o[0] + (c1 & 1), o[1] + ((c1 >> 1) & 1), o[2] + ((c1 >> 2) & 1), c1 >> 3, voxel_length, pj);
+      edge_point(val, k, o[0] + (c2 & 1), o[1] + ((c2 >> 1) & 1), o[2] + ((c2 >> 2) & 1), c2 >> 3, voxel_length, pl);
+      const double ax = pj[0] - pi[0], ay = pj[1] - pi[1], az = pj[2] - pi[2];
+      const double bx = pl[0] - pi[0], by = pl[1] - pi[1], bz = pl[2] - pi[2];
+      sx = sx + (ay * bz - az * by);
+      sy = sy + (az * bx - ax * bz);
+      sz = sz + (ax * by - ay * bx);
+    }
+  }
+  const double len = sqrt((sx * sx + sy * sy) + sz * sz);
+  const bool good = len > 0.0 && !isinf(len);      // (a NaN fails the comparison)
+  out[0] = good ? (float)(sx / len) : 0.f;
+  out[1] = good ? (float)(sy / len) : 0.f;
+  out[2] = good ? (float)(sz / len) : 1.f;
+}
+
+// count[u], tri_count[u]: the unit's vertices and triangles.  flags [U,4096]: bit `axis` of a voxel's byte is set when its edge
+// along that axis yields a vertex.  col_before [U,256]: the unit's vertices before column (x, y).
+__global__ __launch_bounds__(kThreads) void k_tsdf_mesh_count(const int* __restrict__ unit_keys, const int* __restrict__ unit_off, int G,
+                                                              const float* __restrict__ tsdf, const float* __restrict__ weight,
+                                                              unsigned long long tmask, const unsigned long long* __restrict__ table,
+                                                              const int* __restrict__ unit_of, int* __restrict__ count,
+                                                              int* __restrict__ tri_count, unsigned char* __restrict__ flags,
+                                                              int* __restrict__ col_before) {
+  __shared__ float val[kHaloVoxels];
+  __shared__ int nbr[27];
+  using Scan = hipcub::BlockScan<int, kThreads>;
+  __shared__ typename Scan::TempStorage scan_tmp;
+  const int u = blockIdx.x;
+  int k[3];
+  load_halo(unit_keys, u, part_of(unit_off, G, u), tsdf, weight, tmask, table, unit_of, k, val, nbr);
+  const int lx = threadIdx.x >> 4, ly = threadIdx.x & 15;
+  float ta, tb;
+  int mine = 0, tris = 0, before, total, tri_total;
+  unsigned long long lo = 0, hi = 0;
+  for (int z = 0; z < kTsdfRes; ++z) {
+    unsigned long long bits = 0;
+    for (int axis = 0; axis < 3; ++axis) bits |= (unsigned long long)edge_vertex(val, lx, ly, z, axis, ta, tb) << axis;
+    mine += __popcll(bits);
+    if (z < 8) lo |= bits << (8 * z); else hi |= bits << (8 * (z - 8));
+    const int c = cube_case(val, lx + 1, ly + 1, z + 1);
+    if (c > 0 && c < 255) tris += row_triangles(tri_row(c));
+  }
+  *reinterpret_cast<ulonglong2*>(flags + (size_t)u * kTsdfUnitVoxels + threadIdx.x * kTsdfRes) = make_ulonglong2(lo, hi);
+  Scan(scan_tmp).ExclusiveSum(mine, before, total);
+  col_before[(size_t)u * kThreads + threadIdx.x] = before;
+  __syncthreads();
+  Scan(scan_tmp).ExclusiveSum(tris, before, tri_total);
+  if (threadIdx.x == 0) {
+    count[u] = total;
+    tri_count[u] = tri_total;
+  }
+}
+
+// totals[0], totals[1]: the call's vertices and triangles, side by side for one read-back
+__global__ void k_tsdf_mesh_offsets(const int* __restrict__ unit_off, int G, int U, const int* __restrict__ start,
+                                    const int* __restrict__ tri_start, int* __restrict__ point_off, int* __restrict__ tri_off,
+                                    int* __restrict__ totals) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g <= G) {
+    point_off[g] = start[unit_off[g]];
+    tri_off[g] = tri_start[unit_off[g]];
+  }
+  if (g == 0) {
+    totals[0] = start[U];
+    totals[1] = tri_start[U];
+  }
+}
+
+// k_tsdf_extract<true, COLOR>'s vertices, by its statements, and normals [max_points,3] beside them
+template <bool COLOR>
+__global__ __launch_bounds__(kThreads) void k_tsdf_mesh_vertices(const int* __restrict__ unit_keys, const int* __restrict__ unit_off, int G,
+                                                                 const float* __restrict__ tsdf, const float* __restrict__ weight,
+                                                                 unsigned long long tmask, const unsigned long long* __restrict__ table,
+                                                                 const int* __restrict__ unit_of, double voxel_length,
+                                                                 const int* __restrict__ start, const int* __restrict__ col_before,
+                                                                 float* __restrict__ points, float* __restrict__ normals,
+                                                                 long long max_points, const float* __restrict__ color,
+                                                                 float* __restrict__ colors) {
+  __shared__ float val[kHaloVoxels];
+  __shared__ int nbr[27];
+  const int u = blockIdx.x;
+  int k[3];
+  load_halo(unit_keys, u, part_of(unit_off, G, u), tsdf, weight, tmask, table, unit_of, k, val, nbr);
+  const int lx = threadIdx.x >> 4, ly = threadIdx.x & 15;
+  float ta, tb;
+  long long at = (long long)start[u] + col_before[(size_t)u * kThreads + threadIdx.x];
+  for (int z = 0; z < kTsdfRes; ++z)
+#pragma unroll
+    for (int axis = 0; axis < 3; ++axis) {
+      if (!edge_vertex(val, lx, ly, z, axis, ta, tb)) continue;
+      const double px = ((double)(kTsdfRes * k[0] + lx) + 0.5) * voxel_length, py = ((double)(kTsdfRes * k[1] + ly) + 0.5) * voxel_length,
+                   pz = ((double)(kTsdfRes * k[2] + z) + 0.5) * voxel_length;
+      const double da = fabs((double)ta), db = fabs((double)tb);
+      const double move = (da * voxel_length) / (da + db);
+      if (at < max_points) {
+        float* out = points + 3 * (size_t)at;
+        out[0] = (float)(axis == 0 ? px + move : px);
+        out[1] = (float)(axis == 1 ? py + move : py);
+        out[2] = (float)(axis == 2 ? pz + move : pz);
+        float* nout = normals + 3 * (size_t)at;
+        if (axis == 0) vertex_normal<0>(val, k, lx, ly, z, voxel_length, nout);
+        else if (axis == 1) vertex_normal<1>(val, k, lx, ly, z, voxel_length, nout);
+        else vertex_normal<2>(val, k, lx, ly, z, voxel_length, nout);
+        if constexpr (COLOR) {
+          const int bx = lx + (axis == 0), by = ly + (axis == 1), bz = z + (axis == 2);      // 0..16: 16 is the next unit's 0
+          const int n = nbr[((1 + (bx >> 4)) * 3 + (1 + (by >> 4))) * 3 + (1 + (bz >> 4))];
+          const float* ca = color + 3 * ((size_t)u * kTsdfUnitVoxels + ((lx * kTsdfRes + ly) * kTsdfRes + z));
+          const float* cb = color + 3 * ((size_t)max(n, 0) * kTsdfUnitVoxels + (((bx & 15) * kTsdfRes + (by & 15)) * kTsdfRes + (bz & 15)));
+          float* cout = colors + 3 * (size_t)at;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) cout[c] = (float)((((db * (double)ca[c]) + (da * (double)cb[c])) / (da + db)) / 255.0);
+        }
+      }
+      ++at;
+    }
+}
+
+// The index, counted from the fragment's first vertex (`first`: start[] of the fragment's first unit), of the vertex on the edge
+// from voxel (bx, by, bz) along `axis`; the coordinates are local to the workgroup's unit, 0..16, 16 being the next unit's 0.
+GMF_DEVINL int vertex_index(const int* nbr, const unsigned char* __restrict__ flags, const int* __restrict__ col_before,
+                            const int* __restrict__ start, int first, int bx, int by, int bz, int axis) {
+  const int n = max(nbr[((1 + (bx >> 4)) * 3 + (1 + (by >> 4))) * 3 + (1 + (bz >> 4))], 0);      // (the voxel is observed: its unit exists)
+  const int col = (bx & 15) * kTsdfRes + (by & 15), z = bz & 15;
+  const ulonglong2 f = *reinterpret_cast<const ulonglong2*>(flags + (size_t)n * kTsdfUnitVoxels + col * kTsdfRes);
+  const int below = z < 8 ? __popcll(f.x & ((1ull << (8 * z)) - 1)) : __popcll(f.x) + __popcll(f.y & ((1ull << (8 * (z - 8))) - 1));
+  const unsigned own = (unsigned)((z < 8 ? f.x >> (8 * z) : f.y >> (8 * (z - 8))) & 7);
+  return (start[n] - first) + col_before[(size_t)n * kThreads + col] + below + __popc(own & ((1u << axis) - 1));
+}
+
+// step 5: triangles [max_triangles,3], from tri_start[u] on, in (local index of the cube's origin, row) order
+__global__ __launch_bounds__(kThreads) void k_tsdf_mesh_triangles(const int* __restrict__ unit_keys, const int* __restrict__ unit_off, int G,
+                                                                  const float* __restrict__ tsdf, const float* __restrict__ weight,
+                                                                  unsigned long long tmask, const unsigned long long* __restrict__ table,
+                                                                  const int* __restrict__ unit_of, const unsigned char* __restrict__ flags,
+                                                                  const int* __restrict__ col_before, const int* __restrict__ start,
+                                                                  const int* __restrict__ tri_start, int* __restrict__ triangles,
+                                                                  long long max_triangles) {
+  __shared__ float val[kHaloVoxels];
+  __shared__ int nbr[27];
+  using Scan = hipcub::BlockScan<int, kThreads>;
+  __shared__ typename Scan::TempStorage scan_tmp;
+  const int u = blockIdx.x;
+  const int g = part_of(unit_off, G, u);
+  int k[3];
+  load_halo(unit_keys, u, g, tsdf, weight, tmask, table, unit_of, k, val, nbr);
+  const int lx = threadIdx.x >> 4, ly = threadIdx.x & 15;
+  int mine = 0, before;
+  for (int z = 0; z < kTsdfRes; ++z) {
+    const int c = cube_case(val, lx + 1, ly + 1, z + 1);
+    if (c > 0 && c < 255) mine += row_triangles(tri_row(c));
+  }
+  Scan(scan_tmp).ExclusiveSum(mine, before);
+  const int first = start[unit_off[g]];
+  long long at = (long long)tri_start[u] + before;
+  for (int z = 0; z < kTsdfRes; ++z) {
+    const int c = cube_case(val, lx + 1, ly + 1, z + 1);
+    if (!(c > 0 && c < 255)) continue;
+    const TriRow row = tri_row(c);
+    for (int t = 0; t < 5; ++t) {
+      const int e0 = row_entry(row, 3 * t);
+      if (e0 < 0) break;
+      if (at < max_triangles) {
+        const int c0 = edge_code(e0), c1 = edge_code(row_entry(row, 3 * t + 2)), c2 = edge_code(row_entry(row, 3 * t + 1));
+        int* out = triangles + 3 * (size_t)at;      // (v(e0), v(e2), v(e1))
+        out[0] = vertex_index(nbr, flags, col_before, start, first, lx + (c0 & 1), ly + ((c0 >> 1) & 1), z + ((c0 >> 2) & 1), c0 >> 3);
+        out[1] = vertex_index(nbr, flags, col_before, start, first, lx + (c1 & 1), ly + ((c1 >> 1) & 1), z + ((c1 >> 2) & 1), c1 >> 3);
+        out[2] = vertex_index(nbr, flags, col_before, start, first, lx + (c2 & 1), ly + ((c2 >> 1) & 1), z + ((c2 >> 2) & 1), c2 >> 3);
+      }
+      ++at;
+    }
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -538,6 +853,57 @@ hipError_t launch_tsdf_extract(const int* unit_keys, const int* unit_offsets, in
   }
   e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(host_count, ws.start + U, 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return e;
+}
+
+void tsdf_mesh_scratch_list(int U, TsdfMeshScratch& ws, ArenaList& bufs) {
+  ws.T = tsdf_table_slots(U);
+  ws.tmp_bytes = 0;
+  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, ws.tmp_bytes, (int*)nullptr, (int*)nullptr, U + 1);
+  bufs.add(ws.table, (size_t)ws.T);
+  bufs.add(ws.unit_of, (size_t)ws.T);
+  bufs.add(ws.count, (size_t)U + 1);
+  bufs.add(ws.start, (size_t)U + 1);
+  bufs.add(ws.tri_count, (size_t)U + 1);
+  bufs.add(ws.tri_start, (size_t)U + 1);
+  bufs.add(ws.flags, (size_t)U * kTsdfUnitVoxels);
+  bufs.add(ws.col_before, (size_t)U * kThreads);
+  bufs.add(ws.totals, 2);
+  bufs.add(ws.tmp, ws.tmp_bytes);
+}
+
+hipError_t launch_tsdf_extract_mesh(const int* unit_keys, const int* unit_offsets, int G, int U, const float* tsdf, const float* weight,
+                                    const float* color, double voxel_length, const TsdfMeshScratch& ws, float* points, float* normals,
+                                    float* colors, long long max_points, int* triangles, long long max_triangles, int* point_offsets,
+                                    int* triangle_offsets, int* host_counts, hipStream_t s) {
+  const unsigned long long tmask = (unsigned long long)ws.T - 1;
+  hipError_t e = hipMemsetAsync(ws.table, 0xFF, ws.T * 8, s);
+  if (e == hipSuccess) e = hipMemsetAsync(ws.count + U, 0, 4, s);
+  if (e == hipSuccess) e = hipMemsetAsync(ws.tri_count + U, 0, 4, s);
+  if (e != hipSuccess) return e;
+  k_tsdf_index<<<blocks(U, kThreads), kThreads, 0, s>>>(unit_keys, unit_offsets, G, U, tmask, ws.table, ws.unit_of);
+  k_tsdf_mesh_count<<<U, kThreads, 0, s>>>(unit_keys, unit_offsets, G, tsdf, weight, tmask, ws.table, ws.unit_of, ws.count, ws.tri_count,
+                                           ws.flags, ws.col_before);
+  size_t tb = ws.tmp_bytes;
+  e = hipcub::DeviceScan::ExclusiveSum(ws.tmp, tb, ws.count, ws.start, U + 1, s);
+  tb = ws.tmp_bytes;
+  if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(ws.tmp, tb, ws.tri_count, ws.tri_start, U + 1, s);
+  if (e != hipSuccess) return e;
+  k_tsdf_mesh_offsets<<<blocks(G + 1, 64), 64, 0, s>>>(unit_offsets, G, U, ws.start, ws.tri_start, point_offsets, triangle_offsets, ws.totals);
+  if (points) {
+    if (color)
+      k_tsdf_mesh_vertices<true><<<U, kThreads, 0, s>>>(unit_keys, unit_offsets, G, tsdf, weight, tmask, ws.table, ws.unit_of, voxel_length,
+                                                        ws.start, ws.col_before, points, normals, max_points, color, colors);
+    else
+      k_tsdf_mesh_vertices<false><<<U, kThreads, 0, s>>>(unit_keys, unit_offsets, G, tsdf, weight, tmask, ws.table, ws.unit_of, voxel_length,
+                                                         ws.start, ws.col_before, points, normals, max_points, nullptr, nullptr);
+    k_tsdf_mesh_triangles<<<U, kThreads, 0, s>>>(unit_keys, unit_offsets, G, tsdf, weight, tmask, ws.table, ws.unit_of, ws.flags,
+                                                 ws.col_before, ws.start, ws.tri_start, triangles, max_triangles);
+    return hipGetLastError();
+  }
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(host_counts, ws.totals, 8, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   return e;
 }

@@ -6,16 +6,19 @@ of the same scripts (color_type = RGB8, pcd.colors = mesh.vertex_colors): the sa
 gmf_tsdf_integrate_color and gmf_tsdf_extract_color.
 
 The contract is DESIGN.md section 4o, restated in numpy by tests/tsdf_reference.py and, for the colours (steps 3c and 4c),
-tests/tsdf_color_reference.py; where it knowingly differs from open3d is listed there.  Triangles, vertex normals,
-extract_point_cloud, grey volumes and file reading are not here; the RGB-D odometry that gives the poses is gmf_amd/rgbd.py."""
+tests/tsdf_color_reference.py; where it knowingly differs from open3d is listed there.  tsdf_fragment_meshes and
+tsdf_extract_mesh give the mesh itself (steps 5 and 6, tests/tsdf_mesh_reference.py; gmf_tsdf_extract_mesh): the same vertices, the
+triangles and, as mesh.compute_vertex_normals() does, a normal per vertex.  extract_point_cloud, grey volumes and file reading are
+not here; the RGB-D odometry that gives the poses is gmf_amd/rgbd.py."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
 import torch
 
-from ._args import device_offsets, fail, positive_finite, require_device
+from ._args import check_offsets, device_offsets, fail, positive_finite, require_device, same_device
 from ._util import handle_and_stream
 
 MAX_FRAMES = 65535            # frames of one fragment, at most
@@ -23,9 +26,14 @@ MAX_FRAGMENTS = 65535         # fragments of one call, at most (kTsdfMaxFragment
 MAX_UNITS = 1 << 22           # the largest max_units the library takes
 
 
-def _nothing(points_off, return_volume, colored=False):
+def _nothing(points_off, return_volume, colored=False, mesh=False):
     """The result of a call whose frames touch no unit."""
     dev = points_off.device
+    if mesh:
+        parts = _nothing(points_off, True, colored)
+        meshes = TsdfMeshes(parts[0], points_off, torch.zeros((0, 3), device=dev, dtype=torch.int32), torch.zeros_like(points_off),
+                            torch.zeros((0, 3), device=dev, dtype=torch.float32), parts[7] if colored else None)
+        return (meshes, parts[2:7] + parts[8:]) if return_volume else meshes
     pts = torch.zeros((0, 3), device=dev, dtype=torch.float32)
     out = (pts, points_off)
     if return_volume:
@@ -82,10 +90,105 @@ def tsdf_fragments_colored(color, depth, poses, intrinsic, frame_offsets=None, v
                       depth_trunc, depth_sampling_stride, max_units, return_volume, colored=True)
 
 
+TsdfMeshes = collections.namedtuple("TsdfMeshes", ("points", "point_offsets", "triangles", "triangle_offsets", "normals", "colors"))
+TsdfMeshes.__doc__ = """The meshes of G fragments, on the device: points [M,3] float32, point_offsets [G+1] int32, triangles [K,3] int32
+(each entry counts from its fragment's first vertex: fragment g's triangles index points[point_offsets[g]:point_offsets[g+1]]),
+triangle_offsets [G+1] int32, normals [M,3] float32 (row i belongs to points[i]) and colors [M,3] float32 in 0..1, or None."""
+
+
+def tsdf_fragment_meshes(depth, poses, intrinsic, frame_offsets=None, voxel_length=0.008, sdf_trunc=0.04, depth_scale=1000.0,
+                         depth_trunc=4.5, depth_sampling_stride=4, max_units=1 << 18, color=None, return_volume=False):
+    """tsdf_fragments, with the fragments as meshes: what the reference's make_fragments.py gets from
+    volume.extract_triangle_mesh() and mesh.compute_vertex_normals().
+
+    Every argument as in tsdf_fragments; with color [F,H,W,3] uint8 the volume is tsdf_fragments_colored's.  The vertices are those
+    of tsdf_fragments (of tsdf_fragments_colored, with their colours), with the same bits and in the same order.
+      triangles: every 2x2x2 cube of observed voxels whose corners do not all lie on one side of the surface yields the triangles
+      of the classic marching-cubes table, between the vertices on its edges; ordered by fragment, unit, voxel of the cube's
+      origin, table row; every vertex lies in at least one triangle;
+      normals: per vertex the normalised sum, in fp64 and in ascending triangle order, of the cross products
+      (p_j - p_i) x (p_l - p_i) of its triangles (i, j, l) over the returned float32 positions - area-weighted, pointing from
+      negative to positive tsdf, which is towards the cameras; (0, 0, 1) where the sum has no finite positive length.
+    Returns a TsdfMeshes; with return_volume the pair (TsdfMeshes, (unit_keys, unit_offsets, birth, tsdf, weight)), the volume
+    followed by color_volume when there is `color`.  The same bits on every run, alone and in any batch; two host
+    synchronisations per call (the unit count; the vertex and triangle counts, read back together).  `normals` is what
+    icp_point_to_plane_batched takes as target normals."""
+    what = "tsdf_fragment_meshes"
+    return _fragments(what, color, depth, poses, intrinsic, frame_offsets, voxel_length, sdf_trunc, depth_scale, depth_trunc,
+                      depth_sampling_stride, max_units, return_volume, colored=color is not None, mesh=True)
+
+
+def tsdf_extract_mesh(unit_keys, unit_offsets, tsdf, weight, voxel_length, color_volume=None):
+    """The meshes of a volume, as tsdf_fragments(..., return_volume=True) returns one - or any other: steps 4 to 6 of the contract.
+
+    unit_keys [U,3] int32, tsdf and weight [U,16,16,16] float32 and, optionally, color_volume [U,16,16,16,3] float32 in 0..255, on
+    one device; unit_offsets: G + 1 ints that ascend from 0 to U (fragment g owns units unit_offsets[g] .. unit_offsets[g+1] - 1),
+    or an int32 tensor on that device, which is taken as it is.  voxel_length as the volume was built with.
+    The volume is looked at only through weight > 0: a voxel with weight <= 0 (or NaN) is unobserved, whatever its tsdf, and no
+    other property of the weights matters.  Within each fragment the keys must be ascending in (x, y, z) and distinct, each within
+    +-32767, as tsdf_fragments lists them: the order of the output is defined by that listing, and it is not checked (the keys
+    are on the device).
+    Returns a TsdfMeshes (tsdf_fragment_meshes describes it); colors is None without a color_volume.  One host synchronisation
+    (the vertex and triangle counts, read back together)."""
+    what = "tsdf_extract_mesh"
+    for name, x, dtype in (("unit_keys", unit_keys, torch.int32), ("tsdf", tsdf, torch.float32), ("weight", weight, torch.float32),
+                           ("color_volume", color_volume, torch.float32)):
+        if x is None and name == "color_volume":
+            continue
+        if not isinstance(x, torch.Tensor):
+            fail(what, f"`{name}` must be a torch tensor")
+        if x.dtype != dtype:
+            fail(what, f"`{name}` must be {str(dtype).replace('torch.', '')} (got {x.dtype})")
+    if unit_keys.dim() != 2 or unit_keys.shape[1] != 3:
+        fail(what, f"`unit_keys` must be a [U,3] tensor (got {tuple(unit_keys.shape)})")
+    U = unit_keys.shape[0]
+    if U > MAX_UNITS:
+        fail(what, f"a call holds at most {MAX_UNITS} units (got {U})")
+    for name, x in (("tsdf", tsdf), ("weight", weight)):
+        if tuple(x.shape) != (U, 16, 16, 16):
+            fail(what, f"`{name}` must be [U,16,16,16] with unit_keys' U = {U} (got {tuple(x.shape)})")
+    if color_volume is not None and tuple(color_volume.shape) != (U, 16, 16, 16, 3):
+        fail(what, f"`color_volume` must be [U,16,16,16,3] with unit_keys' U = {U} (got {tuple(color_volume.shape)})")
+    vl = positive_finite(what, "voxel_length", voxel_length, numeric=True)
+    same_device(what, unit_keys=unit_keys, tsdf=tsdf, weight=weight, color_volume=color_volume)
+    off = check_offsets(what, "unit_offsets", unit_offsets, U, allow_empty=True)
+    G = (off.numel() if isinstance(off, torch.Tensor) else len(off)) - 1
+    if G > MAX_FRAGMENTS:
+        fail(what, f"a call holds at most {MAX_FRAGMENTS} fragments (got {G})")
+    require_device(unit_keys, "unit_keys", what)
+    dev = unit_keys.device
+    dev_off, _ = device_offsets(off, U, dev, what, allow_empty=True, checked=True)
+    h, st = handle_and_stream(tsdf)
+    return _extract_mesh(h, st, unit_keys.contiguous(), dev_off, G, tsdf.contiguous(), weight.contiguous(),
+                         None if color_volume is None else color_volume.contiguous(), vl)
+
+
+def _extract_mesh(h, st, keys, unit_off, G, tsdf, weight, cvol, vl):
+    """The counting and the emitting call of gmf_tsdf_extract_mesh on a checked, contiguous volume -> TsdfMeshes."""
+    dev = tsdf.device
+    U = keys.shape[0]
+    point_off = torch.zeros(G + 1, device=dev, dtype=torch.int32)
+    tri_off = torch.zeros(G + 1, device=dev, dtype=torch.int32)
+    n, m = C.c_longlong(0), C.c_longlong(0)
+    volume = (keys.data_ptr(), unit_off.data_ptr(), G, U, tsdf.data_ptr(), weight.data_ptr(), None if cvol is None else cvol.data_ptr(), vl)
+    offsets = (point_off.data_ptr(), tri_off.data_ptr())
+    if U:
+        h.call("gmf_tsdf_extract_mesh", *volume, None, None, None, 0, None, 0, *offsets, C.byref(n), C.byref(m), st)
+    M, K = int(n.value), int(m.value)
+    pts = torch.empty((M, 3), device=dev, dtype=torch.float32)
+    nrm = torch.empty((M, 3), device=dev, dtype=torch.float32)
+    cols = None if cvol is None else torch.empty((M, 3), device=dev, dtype=torch.float32)
+    tris = torch.empty((K, 3), device=dev, dtype=torch.int32)
+    if M:
+        h.call("gmf_tsdf_extract_mesh", *volume, pts.data_ptr(), nrm.data_ptr(), None if cols is None else cols.data_ptr(), M,
+               tris.data_ptr(), K, *offsets, None, None, st)
+    return TsdfMeshes(pts, point_off, tris, tri_off, nrm, cols)
+
+
 def _fragments(what, color, depth, poses, intrinsic, frame_offsets, voxel_length, sdf_trunc, depth_scale, depth_trunc,
-               depth_sampling_stride, max_units, return_volume, colored=False):
-    """tsdf_fragments (colored False: `color` is not looked at) and tsdf_fragments_colored: the argument checks, raised under the
-    name `what`, and the calls."""
+               depth_sampling_stride, max_units, return_volume, colored=False, mesh=False):
+    """tsdf_fragments (colored False: `color` is not looked at), tsdf_fragments_colored and (mesh) tsdf_fragment_meshes: the
+    argument checks, raised under the name `what`, and the calls."""
     if not isinstance(depth, torch.Tensor):
         fail(what, "`depth` must be a torch tensor")
     if depth.dtype not in (torch.uint16, torch.float32):
@@ -157,7 +260,7 @@ def _fragments(what, color, depth, poses, intrinsic, frame_offsets, voxel_length
 
     points_off = torch.zeros(G + 1, device=dev, dtype=torch.int32)
     if F == 0:
-        return _nothing(points_off, return_volume, colored)
+        return _nothing(points_off, return_volume, colored, mesh)
 
     D = depth.contiguous()
     u16 = 1 if depth.dtype == torch.uint16 else 0
@@ -176,13 +279,16 @@ def _fragments(what, color, depth, poses, intrinsic, frame_offsets, voxel_length
     U = int(n.value)
     keys, birth = keys[:U].clone(), birth[:U].clone()
     if U == 0:
-        return _nothing(points_off, return_volume, colored)
+        return _nothing(points_off, return_volume, colored, mesh)
     tsdf = torch.empty((U, 16, 16, 16), device=dev, dtype=torch.float32)
     weight = torch.empty((U, 16, 16, 16), device=dev, dtype=torch.float32)
     units = (keys.data_ptr(), unit_off.data_ptr(), birth.data_ptr(), U, tsdf.data_ptr(), weight.data_ptr())
     volume = (keys.data_ptr(), unit_off.data_ptr(), G, U, tsdf.data_ptr(), weight.data_ptr())
     if not colored:
         h.call("gmf_tsdf_integrate", *shared, both[1].data_ptr(), dev_off.data_ptr(), *camera, *units, st)
+        if mesh:
+            meshes = _extract_mesh(h, st, keys, unit_off, G, tsdf, weight, None, vl)
+            return (meshes, (keys, unit_off, birth, tsdf, weight)) if return_volume else meshes
         h.call("gmf_tsdf_extract", *volume, vl, None, 0, points_off.data_ptr(), C.byref(n), st)
         M = int(n.value)
         pts = torch.empty((M, 3), device=dev, dtype=torch.float32)
@@ -192,6 +298,9 @@ def _fragments(what, color, depth, poses, intrinsic, frame_offsets, voxel_length
     Cf = color.contiguous()
     cvol = torch.empty((U, 16, 16, 16, 3), device=dev, dtype=torch.float32)
     h.call("gmf_tsdf_integrate_color", *shared, Cf.data_ptr(), both[1].data_ptr(), dev_off.data_ptr(), *camera, *units, cvol.data_ptr(), st)
+    if mesh:
+        meshes = _extract_mesh(h, st, keys, unit_off, G, tsdf, weight, cvol, vl)
+        return (meshes, (keys, unit_off, birth, tsdf, weight, cvol)) if return_volume else meshes
     h.call("gmf_tsdf_extract_color", *volume, cvol.data_ptr(), vl, None, None, 0, points_off.data_ptr(), C.byref(n), st)
     M = int(n.value)
     pts = torch.empty((M, 3), device=dev, dtype=torch.float32)

@@ -45,7 +45,7 @@ enum {
 #define GMF_ABI_VERSION 5   /* 5: gmf_encoder_weights gained `pv_guard` (a caller that fills the struct itself must be rebuilt; one that uses
                              * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  gmf_icp_point_to_point_ex and
                              * gmf_ransac_feature_matching, then gmf_spectral_matching, then gmf_max_clique and gmf_pmc_graph, then gmf_tsdf_allocate, gmf_tsdf_integrate and gmf_tsdf_extract, then gmf_rgbd_pyramids, gmf_rgbd_correspondences and
-                             * gmf_rgbd_odometry, then gmf_tsdf_integrate_color and gmf_tsdf_extract_color, then gmf_icp_point_to_plane joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
+                             * gmf_rgbd_odometry, then gmf_tsdf_integrate_color and gmf_tsdf_extract_color, then gmf_icp_point_to_plane, then gmf_tsdf_extract_mesh joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
                              * pose head / pick_seeds take any N */
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
@@ -791,6 +791,25 @@ int gmf_tsdf_integrate_color(gmf_handle* h, const void* depth, int depth_is_u16,
 int gmf_tsdf_extract_color(gmf_handle* h, const int* unit_keys, const int* unit_offsets, int G, int num_units, const float* tsdf,
                            const float* weight, const float* color, double voxel_length, float* points_out, float* colors_out,
                            long long max_points, int* point_offsets_out, long long* num_points, gmf_stream_t stream);
+
+/* gmf_tsdf_extract_mesh [joined under ABI 5: an added entry point]: the marching-cubes mesh of the volume, DESIGN.md section 4o
+ * steps 4 to 6 (tests/tsdf_mesh_reference.py restates 5 and 6).  The vertices, their order and their bits are gmf_tsdf_extract's
+ * (with `color` [num_units,16,16,16,3], or NULL: gmf_tsdf_extract_color's colours as well).  A cube of 2x2x2 voxels that all have
+ * weight > 0 and do not all lie on one side yields the triangles of the classic case table (corner i of the cube sets bit i of
+ * the case when its tsdf < 0); a triangle is three vertex indices counted from its fragment's first vertex, wound so that the
+ * normals point from negative to positive tsdf.  Order: fragment, unit, voxel index of the cube's origin, table row.  A vertex
+ * normal is the normalised sum, in fp64 and in ascending triangle order, of (p_j - p_i) x (p_l - p_i) over its triangles (i, j, l),
+ * p the float32 positions that are returned; (0, 0, 1) where the sum has no finite positive length.
+ * The volume is looked at only through weight > 0; unit_keys must be ascending in (x, y, z) and distinct within each fragment.
+ * Every output NULL: counts - point_offsets_out and triangle_offsets_out [G+1] (device int32) are written, and *num_points and
+ * *num_triangles (host) after synchronising the stream once.  Otherwise points_out, normals_out [max_points,3] float32,
+ * colors_out [max_points,3] (exactly when color is given) and triangles_out [max_triangles,3] int32 are written as well (a row
+ * past its cap is dropped: give what the counting call reported), nothing is read back and the two counts are not touched.
+ * Workspace: about 5.2 KB per unit.  Fewer than 2^31 vertices and triangles per call. */
+int gmf_tsdf_extract_mesh(gmf_handle* h, const int* unit_keys, const int* unit_offsets, int G, int num_units, const float* tsdf,
+                          const float* weight, const float* color, double voxel_length, float* points_out, float* normals_out,
+                          float* colors_out, long long max_points, int* triangles_out, long long max_triangles, int* point_offsets_out,
+                          int* triangle_offsets_out, long long* num_points, long long* num_triangles, gmf_stream_t stream);
 
 /* ---- RGB-D odometry (open3d 0.9's compute_rgbd_odometry with the hybrid Jacobian, as make_fragments.py calls it) -------------- */
 

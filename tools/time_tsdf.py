@@ -8,13 +8,16 @@
   --color  also gmf_tsdf_integrate_color, the emitting gmf_tsdf_extract_color and the whole tsdf_fragments_colored call, each
            beside the colour-free time of the same run; the colour frames are a pattern of the pixel and the frame (the time does
            not depend on the values); the colour form moves 12 B per voxel and 3 + 4 B per pixel on top
+  --mesh   also gmf_tsdf_extract_mesh (the counting and the emitting call: vertices, normals, triangles), each beside
+           gmf_tsdf_extract's time of the same run, and estimate_normals_batched (radius three voxels, max_nn 30) on the same
+           vertices: the normals the mesh normals replace
   figures  units, vertices, voxel updates (the sum of the weights) and unit-frame visits; for the integration call the updates per
            second, and bytes per second over what it must move: the volume written once (8 B per voxel) and every depth frame
            converted once (2 B read, 4 B written) - the gathered reads of depth it does on top are served by the caches
 
 Device events around each call after warm-up; median, min and max over repeats, in us.  There is no open3d to compare the times
 with: they are recorded, not gated.
-Usage: python tools/time_tsdf.py [--repeats 5] [--warmup 1] [--fragments 1,8] [--frames 50] [--color] [--out FILE]"""
+Usage: python tools/time_tsdf.py [--repeats 5] [--warmup 1] [--fragments 1,8] [--frames 50] [--color] [--mesh] [--out FILE]"""
 import argparse
 import ctypes as C
 import math
@@ -82,6 +85,8 @@ def main():
     ap.add_argument("--frames", type=int, default=50)
     ap.add_argument("--max-units", type=int, default=1 << 18)
     ap.add_argument("--color", action="store_true")
+    ap.add_argument("--mesh", action="store_true")
+    ap.add_argument("--normal-radius", type=float, default=0.024)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -184,6 +189,28 @@ def main():
                 f"{moved_c / tc / 1e9:.1f} GB/s over {moved_c / 1e6:.1f} MB")
             say(f"  extract_color (emit)   {fmt(t_emit_c)} against {fmt(t_emit)}")
             say(f"  tsdf_fragments_colored {fmt(t_all_c)} against {fmt(t_all)}")
+        if args.mesh:
+            toff = torch.empty(G + 1, dtype=torch.int32, device=dev)
+            m = C.c_longlong(0)
+            mesh_volume = volume[:6] + (None, VOXEL)
+
+            def mesh_count():
+                h.call("gmf_tsdf_extract_mesh", *mesh_volume, None, None, None, 0, None, 0, poff.data_ptr(), toff.data_ptr(), C.byref(n),
+                       C.byref(m), st)
+                return int(n.value), int(m.value)
+
+            t_mcount, (Mm, Km) = timed(mesh_count, args.warmup, args.repeats)
+            assert Mm == M
+            pts_m, nrm = torch.empty_like(pts), torch.empty_like(pts)
+            tri = torch.empty((Km, 3), dtype=torch.int32, device=dev)
+            t_memit, _ = timed(lambda: h.call("gmf_tsdf_extract_mesh", *mesh_volume, pts_m.data_ptr(), nrm.data_ptr(), None, M,
+                                              tri.data_ptr(), Km, poff.data_ptr(), toff.data_ptr(), None, None, st), args.warmup, args.repeats)
+            assert torch.equal(pts_m, pts)
+            t_knn, _ = timed(lambda: gmf_amd.estimate_normals_batched(pts, poff, args.normal_radius, 30), args.warmup, args.repeats)
+            say(f"  mesh: {Km} triangles")
+            say(f"  extract_mesh (count)     {fmt(t_mcount)} against {fmt(t_count)}")
+            say(f"  extract_mesh (emit)      {fmt(t_memit)} against {fmt(t_emit)}")
+            say(f"  estimate_normals_batched {fmt(t_knn)} (radius {args.normal_radius}, max_nn 30, the same {M} vertices)")
     if args.out:
         with open(args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
