@@ -62,6 +62,17 @@ def positive_finite(what, name, v, allow_inf=False, rule=None, numeric=False):
     return f
 
 
+def unit_interval(what, name, v):
+    """float(v), finite and in [0, 1]; something that is no number fails the rule like a NaN."""
+    try:
+        f = float(v)
+    except (TypeError, ValueError):
+        f = float("nan")
+    if not 0.0 <= f <= 1.0:
+        fail(what, f"{name} must be finite and in [0, 1] (got {v})")
+    return f
+
+
 def int_in_range(what, name, v, lo, hi, rule=None):
     """int(v) when v is integral and lo <= v <= hi.  rule: how the message states the range (default "lo..hi")."""
     try:

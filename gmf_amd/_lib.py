@@ -218,6 +218,8 @@ SIGNATURES = {
                                             C.c_double, C.c_double] + [_vp] * 5 + [_ll, C.c_int, _vp]),
     "gmf_icp_point_to_plane": (C.c_int, [_vp] * 6 + [C.c_int, _ll, C.c_int, C.c_int, _vp, C.c_float, C.c_int, C.c_double,
                                          C.c_double] + [_vp] * 5 + [_ll, C.c_int, _vp]),
+    "gmf_icp_colored": (C.c_int, [_vp] * 6 + [C.c_int, _ll, C.c_int, C.c_int, _vp, C.c_float, C.c_int, C.c_double,
+                                  C.c_double] + [_vp] * 5 + [_ll, C.c_int, _vp, _vp, _vp, C.c_double, _vp]),
     "gmf_information_matrix": (C.c_int, [_vp, _vp, _i32p, C.c_int, _i32p, _i32p, C.c_int, _vp, C.c_float, _vp, _vp, _vp, _vp]),
     "gmf_posegraph_optimize": (C.c_int, [_vp, _vp, _i32p, _i32p, C.c_int, _i32p, _i32p] + [_vp] * 4 + [C.POINTER(PoseGraphOptions)]
                                + [_vp] * 6),
@@ -244,6 +246,8 @@ SIGNATURES = {
     "gmf_estimate_normals": (C.c_int, [_vp, _vp, _vp, C.c_int, _ll, C.c_double, C.c_int, _vp, _vp]),
     "gmf_compute_fpfh": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _ll, C.c_double, C.c_int, _vp, _vp]),
     "gmf_voxel_down_sample": (C.c_int, [_vp, _vp, _vp, C.c_int, _ll, C.c_double, _vp, _vp, C.POINTER(_ll), _vp]),
+    "gmf_voxel_down_sample_color": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _ll, C.c_double, _vp, _vp, _vp, C.POINTER(_ll), _vp]),
+    "gmf_color_gradients": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _ll, C.c_double, C.c_int, _vp, _vp]),
     "gmf_voxel_select": (C.c_int, [_vp, _vp, _vp, C.c_int, _ll, C.c_double, _vp, _vp, C.POINTER(_ll), _vp]),
     "gmf_sparse_plan_bytes": (C.c_int, [_vp, _ll, C.c_int, C.c_int, C.c_int, _i32p, C.POINTER(_ll)]),
     "gmf_sparse_build_plan": (C.c_int, [_vp, _vp, _ll, C.c_int, C.c_int, C.c_int, _i32p, _vp, _ll, C.POINTER(_ll), _vp]),

@@ -122,7 +122,8 @@ int take_knn(gmf_handle* h, long long N, int max_nn, bool spfh, KnnLists& k) {
 }
 
 int voxel_call(gmf_handle* h, const char* what, const float* pts, const int* offsets, int B, long long total_rows, double voxel,
-               float* out_pts, int* out_idx, int* out_offsets, long long* num_out, gmf_stream_t stream) {
+               float* out_pts, int* out_idx, int* out_offsets, long long* num_out, gmf_stream_t stream,
+               const float* colors = nullptr, float* out_colors = nullptr) {
   if (int rc = check_cloud_args(h, what, pts, offsets, B, total_rows, voxel, 1)) return rc;
   GMF_REQUIRE((out_pts || out_idx) && out_offsets && num_out, GMF_ERR_BAD_ARG, std::string(what) + ": null pointer");
   SetDevice sd(h, stream);
@@ -132,7 +133,7 @@ int voxel_call(gmf_handle* h, const char* what, const float* pts, const int* off
   if (int rc = arena_carve(h, bufs)) return rc;
   int host2[2] = {0, 0};
   GMF_HIP(gmf::launch_voxel(pts, offsets, B, total_rows, voxel, out_pts != nullptr, ws, out_pts, out_idx, out_offsets, host2,
-                            S(stream)));
+                            S(stream), colors, out_colors));
   GMF_REQUIRE(host2[1] == 0, GMF_ERR_UNSUPPORTED_SHAPE,
               std::string(what) + ": a voxel index does not fit in int32 (voxel size too small for the extent) or a coordinate is "
                                   "not finite");
@@ -851,6 +852,46 @@ int gmf_icp_point_to_plane(gmf_handle* h, const float* src, const int* src_offse
   return GMF_OK;
 }
 
+int gmf_icp_colored(gmf_handle* h, const float* src, const int* src_offsets, const float* tgt, const float* tgt_normals,
+                    const int* tgt_offsets, int B, long long total_src, int max_src, int max_tgt, const float* init, float tau,
+                    int max_iter, double rel_fitness, double rel_rmse, float* T_out, float* fitness, float* inlier_rmse,
+                    int* iterations, long long* nn, long long total_tgt, int search, const float* src_intensity,
+                    const float* tgt_intensity, const float* tgt_gradients, double lambda_geometric, gmf_stream_t stream) {
+  GMF_REQUIRE(h && src && src_offsets && tgt && tgt_normals && tgt_offsets && init && T_out && fitness && inlier_rmse &&
+                  iterations && nn && src_intensity && tgt_intensity && tgt_gradients,
+              GMF_ERR_BAD_ARG, "icp_colored: null pointer");
+  GMF_REQUIRE(B > 0 && total_src > 0 && total_src < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE,
+              "icp_colored: empty batch or more than 2^31 source rows");
+  GMF_REQUIRE(total_tgt > 0 && total_tgt < (1LL << 31), GMF_ERR_UNSUPPORTED_SHAPE, "icp_colored: total_tgt must be in 1..2^31 - 1");
+  GMF_REQUIRE(search == 0 || search == 1, GMF_ERR_BAD_ARG, "icp_colored: search must be 0 (brute force) or 1 (grid)");
+  GMF_REQUIRE(tau > 0.f && std::isfinite(tau), GMF_ERR_BAD_ARG, "icp_colored: max_correspondence_distance must be > 0");
+  GMF_REQUIRE(max_iter >= 0 && max_iter <= 100000, GMF_ERR_BAD_ARG, "icp_colored: max_iteration must be in 0..100000");
+  GMF_REQUIRE(lambda_geometric >= 0.0 && lambda_geometric <= 1.0, GMF_ERR_BAD_ARG,
+              "icp_colored: lambda_geometric must be in 0..1");
+  GMF_REQUIRE(search == 0 || total_tgt < (1LL << 29), GMF_ERR_UNSUPPORTED_SHAPE,
+              "icp_colored: the grid search takes fewer than 2^29 target rows");
+  GMF_REQUIRE(max_src <= total_src, GMF_ERR_BAD_ARG, "icp_colored: max_src exceeds total_src");
+  const int bound_src = max_src > 0 ? max_src : (int)total_src;
+  gmf::IcpPlaneScratch ps;
+  ps.normals = tgt_normals;
+  GMF_REQUIRE(gmf::icp_plane_plan(B, bound_src, ps.plan), GMF_ERR_UNSUPPORTED_SHAPE,
+              "icp_colored: the step's B * ceil(max_src / kIcpPlaneRows) workgroups do not fit one launch");
+  const gmf::IcpColorTerms ct{src_intensity, tgt_intensity, tgt_gradients, std::sqrt(lambda_geometric),
+                              std::sqrt(1.0 - lambda_geometric)};
+  SetDevice sd(h, stream);
+  gmf::IcpScratch ws;
+  gmf::KnnScratch gs;
+  ArenaList bufs;
+  gmf::icp_scratch_list(total_src, B, ws, bufs);
+  gmf::icp_plane_scratch_list(ps, bufs);
+  if (search == 1) gmf::knn_scratch_list(total_tgt, gs, bufs);
+  if (int rc = arena_carve(h, bufs)) return rc;
+  GMF_HIP(gmf::launch_icp(src, src_offsets, tgt, tgt_offsets, B, total_src, bound_src, max_tgt > 0 ? max_tgt : (int)total_tgt, init,
+                          tau, max_iter, rel_fitness, rel_rmse, ws, T_out, fitness, inlier_rmse, iterations, nn, S(stream),
+                          search == 1 ? &gs : nullptr, total_tgt, &ps, &ct));
+  return GMF_OK;
+}
+
 // The host plan (chunk table, the edges' cloud indices, the cloud offsets) goes up in ONE ring slot and ONE upload.
 int gmf_information_matrix(gmf_handle* h, const float* points, const int* cloud_offsets, int F, const int* edge_source,
                            const int* edge_target, int E, const double* transformation, float tau, double* info, int* count,
@@ -1291,6 +1332,19 @@ int gmf_estimate_normals(gmf_handle* h, const float* pts, const int* offsets, in
   return GMF_OK;
 }
 
+int gmf_color_gradients(gmf_handle* h, const float* pts, const float* normals, const float* intensity, const int* offsets, int B,
+                        long long total_rows, double radius, int max_nn, float* gradients, gmf_stream_t stream) {
+  if (int rc = check_cloud_args(h, "color_gradients", pts, offsets, B, total_rows, radius, max_nn)) return rc;
+  GMF_REQUIRE(normals && intensity && gradients, GMF_ERR_BAD_ARG, "color_gradients: null pointer");
+  SetDevice sd(h, stream);
+  KnnLists k;
+  if (int rc = take_knn(h, total_rows, max_nn, false, k)) return rc;
+  GMF_HIP(gmf::launch_radius_knn(pts, offsets, B, total_rows, radius, max_nn, k.ws, k.idx, nullptr, k.count, S(stream)));
+  GMF_HIP(gmf::launch_color_gradient(pts, normals, intensity, offsets, B, total_rows, k.idx, k.count, max_nn, gradients,
+                                     S(stream)));
+  return GMF_OK;
+}
+
 int gmf_compute_fpfh(gmf_handle* h, const float* pts, const float* normals, const int* offsets, int B, long long total_rows,
                      double radius, int max_nn, float* features, gmf_stream_t stream) {
   if (int rc = check_cloud_args(h, "compute_fpfh", pts, offsets, B, total_rows, radius, max_nn)) return rc;
@@ -1307,6 +1361,14 @@ int gmf_voxel_down_sample(gmf_handle* h, const float* pts, const int* offsets, i
                           float* out_pts, int* out_offsets, long long* num_out, gmf_stream_t stream) {
   GMF_REQUIRE(out_pts, GMF_ERR_BAD_ARG, "voxel_down_sample: null pointer");
   return voxel_call(h, "voxel_down_sample", pts, offsets, B, total_rows, voxel, out_pts, nullptr, out_offsets, num_out, stream);
+}
+
+int gmf_voxel_down_sample_color(gmf_handle* h, const float* pts, const float* colors, const int* offsets, int B,
+                                long long total_rows, double voxel, float* out_pts, float* out_colors, int* out_offsets,
+                                long long* num_out, gmf_stream_t stream) {
+  GMF_REQUIRE(out_pts && colors && out_colors, GMF_ERR_BAD_ARG, "voxel_down_sample_color: null pointer");
+  return voxel_call(h, "voxel_down_sample_color", pts, offsets, B, total_rows, voxel, out_pts, nullptr, out_offsets, num_out, stream,
+                    colors, out_colors);
 }
 
 int gmf_voxel_select(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double voxel,

@@ -1,7 +1,7 @@
 // Internal C++ launch entry points of the point-cloud descriptor kernels (pointcloud_kernels.hip): radius-bounded kNN on a
-// hashed grid, normals, FPFH and the two voxel grids.
-// Public C ABI: include/gmf_hip.h (gmf_radius_knn, gmf_estimate_normals, gmf_compute_fpfh, gmf_voxel_down_sample,
-// gmf_voxel_select).
+// hashed grid, normals, colour gradients, FPFH and the two voxel grids.
+// Public C ABI: include/gmf_hip.h (gmf_radius_knn, gmf_estimate_normals, gmf_color_gradients, gmf_compute_fpfh,
+// gmf_voxel_down_sample, gmf_voxel_down_sample_color, gmf_voxel_select).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -37,6 +37,9 @@ hipError_t launch_radius_knn(const float* pts, const int* offsets, int B, long l
                              const KnnScratch& ws, int* idx, double* d2, int* count, hipStream_t s);
 hipError_t launch_normals(const float* pts, const int* offsets, int B, long long N, const int* idx, const int* count,
                           int max_nn, float* normals, hipStream_t s);
+// open3d's InitializePointCloudForColoredICP over the lists of launch_radius_knn: intensity [N], gradients [N, 3].
+hipError_t launch_color_gradient(const float* pts, const float* normals, const float* intensity, const int* offsets, int B,
+                                 long long N, const int* idx, const int* count, int max_nn, float* gradients, hipStream_t s);
 // spfh: [N, 33] fp64 scratch
 hipError_t launch_fpfh(const float* pts, const float* normals, const int* offsets, int B, long long N, const int* idx,
                        const double* d2, const int* count, int max_nn, double* spfh, float* features, hipStream_t s);
@@ -62,8 +65,10 @@ struct VoxelScratch {
 void voxel_scratch_list(long long N, int B, VoxelScratch& s, ArenaList& bufs);
 // mean = true: voxel_down_sample (origin min - v/2, out_pts [nv, 3] the fp64 means stored as fp32); false: voxel_select
 // (origin 0, out_idx [nv] the smallest row of each voxel, within its cloud).  out_offsets [B + 1].  Writes the voxel count and
-// the range flag to `host2` after synchronising the stream.
+// the range flag to `host2` after synchronising the stream.  colors [N, 3] (mean only, may be null): out_colors [nv, 3] is the
+// fp64 mean of each voxel's colours over the same rows in the same order, stored as fp32 (open3d's AccumulatedPoint).
 hipError_t launch_voxel(const float* pts, const int* offsets, int B, long long N, double voxel, bool mean,
-                        const VoxelScratch& ws, float* out_pts, int* out_idx, int* out_offsets, int* host2, hipStream_t s);
+                        const VoxelScratch& ws, float* out_pts, int* out_idx, int* out_offsets, int* host2, hipStream_t s,
+                        const float* colors = nullptr, float* out_colors = nullptr);
 
 }  // namespace gmf

@@ -1,7 +1,7 @@
 // Internal C++ launch entry points of the correspondence RANSAC, point-to-point ICP and feature-matching RANSAC solvers
 // (solver_kernels.hip).
 // Public C ABI: include/gmf_hip.h (gmf_ransac_correspondence, gmf_icp_point_to_point, gmf_icp_point_to_point_ex,
-// gmf_icp_point_to_plane, gmf_ransac_feature_matching).
+// gmf_icp_point_to_plane, gmf_icp_colored, gmf_ransac_feature_matching).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -44,17 +44,28 @@ struct IcpPlaneScratch {
   double* part;               // [plan.partial_doubles]
 };
 
+// What coloured ICP adds to a point-to-plane call: one intensity per source and per target row, the targets' colour gradients
+// (launch_color_gradient), and the square roots of the two weights, taken on the host in double.
+struct IcpColorTerms {
+  const float* src_intensity;   // [total_src]
+  const float* tgt_intensity;   // [total_tgt]
+  const float* tgt_gradients;   // [total_tgt, 3]
+  double sqrt_geometric;        // sqrt(lambda_geometric)
+  double sqrt_photometric;      // sqrt(1 - lambda_geometric)
+};
+
 void icp_scratch_list(long long total_src, int B, IcpScratch& s, ArenaList& bufs);
 void icp_plane_scratch_list(IcpPlaneScratch& s, ArenaList& bufs);    // s.plan filled by icp_plane_plan
 // grid: null = the brute-force search (k_icp_nn).  Otherwise a KnnScratch listed for total_tgt rows (all targets of the batch):
 // the call builds the hashed grid over the targets first (launch_grid_build) and searches it (k_icp_nn_grid), bit-identically.
 // plane: null = point-to-point (k_icp_step).  Otherwise each pass ends with k_icp_plane_partials and k_icp_plane_solve instead,
 // and max_src must bound every pair's source rows (a pair that exceeds it comes back with NaN in T_out and iterations -1).
+// color (with plane): coloured ICP, k_icp_color_partials in the place of k_icp_plane_partials.
 hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, const int* tgt_off, int B, long long total_src,
                       int max_src, int max_tgt, const float* init, float tau, int max_iter, double rel_fitness, double rel_rmse,
                       const IcpScratch& ws, float* T_out, float* fitness, float* rmse, int* iterations, long long* nn,
                       hipStream_t s, const KnnScratch* grid = nullptr, long long total_tgt = 0,
-                      const IcpPlaneScratch* plane = nullptr);
+                      const IcpPlaneScratch* plane = nullptr, const IcpColorTerms* color = nullptr);
 
 // Device scratch of one feature-matching RANSAC call.  H = max_iteration, V = max_validation.
 struct FmScratch {

@@ -427,6 +427,72 @@ __global__ __launch_bounds__(kThreads) void k_normals(const float* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// colour gradients: open3d's InitializePointCloudForColoredICP
+// ---------------------------------------------------------------------------------------------------------------------------
+
+// One lane per row, over the row's neighbour list (key (d^2, row), self included).  count < 4: g = 0.  Otherwise the first list
+// entry is skipped as open3d skips it (the query row, unless an earlier row coincides with it), and over the others in list
+// order, in fp64 from the fp32 inputs: e = v_a - v, d = e - (e . n) n, A = sum d d^T + (count - 1)^2 n n^T,
+// b = sum d (I_a - I).  A g = b by 3 x 3 LDL^T without pivoting; pivot d_k is accepted when it is finite and d_k > 2^-40 A_kk.
+// A rejected pivot or a non-finite component gives g = 0 (open3d applies whatever ldlt() returns).  Every use of n is an even
+// product: negating a normal changes no bit.
+__global__ __launch_bounds__(kThreads) void k_color_gradient(const float* __restrict__ pts, const float* __restrict__ nrm,
+                                                             const float* __restrict__ inten, const int* __restrict__ off, int B,
+                                                             int N, const int* __restrict__ idx, const int* __restrict__ count,
+                                                             int max_nn, float* __restrict__ grad) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= N) return;
+  const int c = count[i];
+  double g[3] = {0, 0, 0};
+  if (c >= 4) {
+    const int lo = off[cloud_of(off, B, i)];
+    const double vx = pts[3 * i], vy = pts[3 * i + 1], vz = pts[3 * i + 2];
+    const double nx = nrm[3 * i], ny = nrm[3 * i + 1], nz = nrm[3 * i + 2], I = inten[i];
+    double A[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};          // A: xx xy xz yy yz zz
+    const int* row = idx + (size_t)i * max_nn;
+    for (int t = 1; t < c; ++t) {
+      const int j = lo + row[t];
+      const double ex = (double)pts[3 * j] - vx, ey = (double)pts[3 * j + 1] - vy, ez = (double)pts[3 * j + 2] - vz;
+      const double en = fma(ex, nx, fma(ey, ny, ez * nz));
+      const double dx = fma(-en, nx, ex), dy = fma(-en, ny, ey), dz = fma(-en, nz, ez);
+      const double di = (double)inten[j] - I;
+      A[0] = fma(dx, dx, A[0]);
+      A[1] = fma(dx, dy, A[1]);
+      A[2] = fma(dx, dz, A[2]);
+      A[3] = fma(dy, dy, A[3]);
+      A[4] = fma(dy, dz, A[4]);
+      A[5] = fma(dz, dz, A[5]);
+      b[0] = fma(dx, di, b[0]);
+      b[1] = fma(dy, di, b[1]);
+      b[2] = fma(dz, di, b[2]);
+    }
+    const double w = (double)(c - 1) * (double)(c - 1);           // (the products of two fp32 normals are exact in fp64)
+    A[0] = fma(w, nx * nx, A[0]);
+    A[1] = fma(w, nx * ny, A[1]);
+    A[2] = fma(w, nx * nz, A[2]);
+    A[3] = fma(w, ny * ny, A[3]);
+    A[4] = fma(w, ny * nz, A[4]);
+    A[5] = fma(w, nz * nz, A[5]);
+    const double d0 = A[0];
+    bool ok = isfinite(d0) && d0 > 0x1p-40 * A[0];
+    const double l10 = A[1] / d0, l20 = A[2] / d0;
+    const double d1 = A[3] - (l10 * l10) * d0;
+    ok = ok && isfinite(d1) && d1 > 0x1p-40 * A[3];
+    const double l21 = (A[4] - (l20 * l10) * d0) / d1;
+    const double d2 = (A[5] - (l20 * l20) * d0) - (l21 * l21) * d1;
+    ok = ok && isfinite(d2) && d2 > 0x1p-40 * A[5];
+    if (ok) {
+      const double y0 = b[0], y1 = b[1] - l10 * y0, y2 = (b[2] - l20 * y0) - l21 * y1;      // L y = b
+      const double x2 = y2 / d2, x1 = y1 / d1 - l21 * x2, x0 = (y0 / d0 - l10 * x1) - l20 * x2;   // D z = y, L^T g = z
+      if (isfinite(x0) && isfinite(x1) && isfinite(x2)) { g[0] = x0; g[1] = x1; g[2] = x2; }
+    }
+  }
+  grad[3 * i] = (float)g[0];
+  grad[3 * i + 1] = (float)g[1];
+  grad[3 * i + 2] = (float)g[2];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // FPFH: open3d's ComputePairFeatures, SPFH and FPFH
 // ---------------------------------------------------------------------------------------------------------------------------
 
@@ -679,6 +745,13 @@ hipError_t launch_normals(const float* pts, const int* offsets, int B, long long
   return hipGetLastError();
 }
 
+hipError_t launch_color_gradient(const float* pts, const float* normals, const float* intensity, const int* offsets, int B,
+                                 long long N, const int* idx, const int* count, int max_nn, float* gradients, hipStream_t s) {
+  k_color_gradient<<<blocks(N, kThreads), kThreads, 0, s>>>(pts, normals, intensity, offsets, B, (int)N, idx, count, max_nn,
+                                                            gradients);
+  return hipGetLastError();
+}
+
 hipError_t launch_fpfh(const float* pts, const float* normals, const int* offsets, int B, long long N, const int* idx,
                        const double* d2, const int* count, int max_nn, double* spfh, float* features, hipStream_t s) {
   k_spfh<<<blocks(N, kWaves), kThreads, 0, s>>>(pts, normals, offsets, B, (int)N, idx, count, max_nn, spfh);
@@ -706,7 +779,8 @@ void voxel_scratch_list(long long N, int B, VoxelScratch& s, ArenaList& bufs) {
 }
 
 hipError_t launch_voxel(const float* pts, const int* offsets, int B, long long N, double voxel, bool mean,
-                        const VoxelScratch& ws, float* out_pts, int* out_idx, int* out_offsets, int* host2, hipStream_t s) {
+                        const VoxelScratch& ws, float* out_pts, int* out_idx, int* out_offsets, int* host2, hipStream_t s,
+                        const float* colors, float* out_colors) {
   const unsigned long long tmask = (unsigned long long)ws.T - 1;
   const int n = (int)N;
   hipError_t e = hipMemsetAsync(ws.table, 0xFF, ws.T * 4, s);
@@ -729,6 +803,8 @@ hipError_t launch_voxel(const float* pts, const int* offsets, int B, long long N
     if (e != hipSuccess) return e;
     k_voxel_starts<<<blocks(N, kThreads), kThreads, 0, s>>>(n, ws.key_sorted, ws.vstart);
     k_voxel_mean<<<blocks(N, kThreads), kThreads, 0, s>>>(pts, n, ws.key_sorted, ws.vstart, ws.vid + N, out_pts);
+    if (colors)                                        // the same mean over the same rows in the same order, of the colours
+      k_voxel_mean<<<blocks(N, kThreads), kThreads, 0, s>>>(colors, n, ws.key_sorted, ws.vstart, ws.vid + N, out_colors);
   } else {
     k_voxel_select<<<blocks(N, kThreads), kThreads, 0, s>>>(offsets, B, n, ws.head, ws.vid, out_idx);
   }

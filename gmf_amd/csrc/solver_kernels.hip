@@ -24,6 +24,9 @@
 //   k_icp_plane_partials  one workgroup per 512 source rows of ONE pair: C, nn and a partial of 29 fp64 sums in a fixed tree.
 //   k_icp_plane_solve     one wave per pair: the partials in ascending order, fitness, rmse, the convergence test, then the
 //                         6 x 6 LDL^T of the linearised step and T <- dT T.
+// Coloured ICP: point-to-plane ICP's launches with k_icp_color_partials in the place of k_icp_plane_partials:
+//   k_icp_color_partials  the same 29 sums, A and b holding lambda times the geometric and (1 - lambda) times the photometric
+//                         term of every row (the target's colour gradients: pointcloud_kernels.hip, k_color_gradient).
 // Feature-matching RANSAC (open3d's registration_ransac_based_on_feature_matching), three memsets, the grid build and seven
 // launches, none of which the host waits for:
 //   k_fm_propose       one lane per hypothesis: draw, pair each row with its feature-space match, edge-length test, fp64 Kabsch,
@@ -637,6 +640,94 @@ k_icp_plane_partials(const float* __restrict__ src, const int* __restrict__ soff
     part[((size_t)b * parts + pt) * kIcpPlaneSums + tid] = (wsum[0][tid] + wsum[1][tid]) + (wsum[2][tid] + wsum[3][tid]);
 }
 
+// Coloured ICP (open3d 0.9 TransformationEstimationForColoredICP; Park, Zhou, Koltun, ICCV 2017): k_icp_plane_partials with a
+// photometric term beside the geometric one.  The same grid, rows, keys, nn, |C|, sum d^2 and fold; the 27 sums of A and b hold
+// the two terms of every row of C whose normal, gradient and two intensities are finite: with p, q, n as above, g the target's
+// colour gradient and I_s, I_t the intensities of the source row and of its target,
+//   r_G = (p - q) . n,  J_G = [p x n ; n]  (the plane form's expressions),
+//   u = (p - q) - r_G n,  r_I = I_s - (g . u + I_t),  m = -(g - (g . n) n),  J_I = [p x m ; m],
+// each term scaled by sg = sqrt(lambda) or si = sqrt(1 - lambda) (host doubles) before its products, so that
+// A = sum lambda J_G J_G^T + (1 - lambda) J_I J_I^T and b = sum lambda J_G r_G + (1 - lambda) J_I r_I.  Every use of n is an
+// even product, written so that negating n negates both operands of a multiplication or none: no output bit changes.
+__global__ void __launch_bounds__(kThreads)
+k_icp_color_partials(const float* __restrict__ src, const int* __restrict__ soff, const float* __restrict__ tgt,
+                     const float* __restrict__ nrm, const int* __restrict__ toff, const float* __restrict__ sint,
+                     const float* __restrict__ tint, const float* __restrict__ grd, double sg, double si, int parts, float tau2,
+                     const double* __restrict__ Tst, const int* __restrict__ done, unsigned long long* __restrict__ key,
+                     long long* __restrict__ nn, double* __restrict__ part) {
+  constexpr int kWaves = kThreads / 64;
+  static_assert(kWaves == 4 && kIcpPlaneRows % kThreads == 0, "the fold below is written for four waves and whole sweeps");
+  __shared__ double wsum[kWaves][kIcpPlaneSums];
+  const int b = blockIdx.x / parts, pt = blockIdx.x % parts, tid = threadIdx.x;
+  if (done[b]) return;
+  const int s0 = soff[b], ns = soff[b + 1] - s0, q0 = toff[b];
+  if ((long long)pt * kIcpPlaneRows >= ns) return;
+  const int r0 = pt * kIcpPlaneRows, left = ns - r0;     // rows of the pair from this part on (>= 1)
+  double T[12];
+#pragma unroll
+  for (int e = 0; e < 12; ++e) T[e] = Tst[12 * (size_t)b + e];
+  double v[kIcpPlaneSums];
+#pragma unroll
+  for (int e = 0; e < kIcpPlaneSums; ++e) v[e] = 0.0;
+#pragma unroll
+  for (int u = 0; u < kIcpPlaneRows / kThreads; ++u) {
+    const int l = u * kThreads + tid;
+    if (l >= left) continue;
+    const size_t i = (size_t)s0 + r0 + l;
+    const unsigned long long kv = key[i];
+    key[i] = ~0ull;
+    const float d2 = __uint_as_float((unsigned)(kv >> 32));
+    const int j = (int)(kv & 0xffffffffull);
+    const bool in = kv != ~0ull && d2 < tau2;
+    nn[i] = in ? j : -1;
+    if (!in) continue;
+    v[0] += 1.0;
+    v[1] += (double)d2;
+    const size_t jt = (size_t)(q0 + j);
+    const float* n = nrm + 3 * jt;
+    const float* g = grd + 3 * jt;
+    const float n0 = n[0], n1 = n[1], n2 = n[2], g0 = g[0], g1 = g[1], g2 = g[2], is = sint[i], it = tint[jt];
+    if (!(isfinite(n0) && isfinite(n1) && isfinite(n2) && isfinite(g0) && isfinite(g1) && isfinite(g2) && isfinite(is) &&
+          isfinite(it)))
+      continue;
+    float p[3];
+    transform_row(T, src + 3 * i, p);
+    const float* q = tgt + 3 * jt;
+    const double px = p[0], py = p[1], pz = p[2], nx = n0, ny = n1, nz = n2, gx = g0, gy = g1, gz = g2;
+    const double ex = px - (double)q[0], ey = py - (double)q[1], ez = pz - (double)q[2];
+    // (the products of two fp32 are exact in fp64: each entry of p x n is rounded once)
+    double JG[6] = {fma(py, nz, -(pz * ny)), fma(pz, nx, -(px * nz)), fma(px, ny, -(py * nx)), nx, ny, nz};
+    const double rG = fma(ex, nx, fma(ey, ny, ez * nz));
+    const double ux = fma(-rG, nx, ex), uy = fma(-rG, ny, ey), uz = fma(-rG, nz, ez);
+    const double gn = fma(gx, nx, fma(gy, ny, gz * nz));
+    const double mx = fma(gn, nx, -gx), my = fma(gn, ny, -gy), mz = fma(gn, nz, -gz);
+    const double rI = ((double)is - (fma(gx, ux, fma(gy, uy, gz * uz)) + (double)it)) * si;
+    double JI[6] = {fma(py, mz, -(pz * my)), fma(pz, mx, -(px * mz)), fma(px, my, -(py * mx)), mx, my, mz};
+    const double rGs = rG * sg;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) { JG[a] *= sg; JI[a] *= si; }
+    int e = 2;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int c = a; c < 6; ++c) { v[e] = fma(JI[a], JI[c], fma(JG[a], JG[c], v[e])); ++e; }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) v[23 + a] = fma(JI[a], rI, fma(JG[a], rGs, v[23 + a]));
+  }
+#pragma unroll
+  for (int e = 0; e < kIcpPlaneSums; ++e) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[e] += __shfl_xor(v[e], o, 64);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int e = 0; e < kIcpPlaneSums; ++e) wsum[tid >> 6][e] = v[e];
+  }
+  __syncthreads();
+  if (tid < kIcpPlaneSums)
+    part[((size_t)b * parts + pt) * kIcpPlaneSums + tid] = (wsum[0][tid] + wsum[1][tid]) + (wsum[2][tid] + wsum[3][tid]);
+}
+
 // One wave per pair.  Lane e < 29 adds entry e of the pair's partials in ascending part; lane 0 then does what k_icp_step does
 // with its sums (fitness, rmse, the convergence test, the outputs and `done` on stop) and otherwise solves A x = -b by LDL^T
 // without pivoting in a fixed order.  Pivot d_k is accepted when it is finite and d_k > 2^-40 A_kk (A_kk: the original diagonal
@@ -758,7 +849,8 @@ void icp_scratch_list(long long total_src, int B, IcpScratch& s, ArenaList& bufs
 hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, const int* tgt_off, int B, long long total_src,
                       int max_src, int max_tgt, const float* init, float tau, int max_iter, double rel_fitness, double rel_rmse,
                       const IcpScratch& ws, float* T_out, float* fitness, float* rmse, int* iterations, long long* nn,
-                      hipStream_t s, const KnnScratch* grid, long long total_tgt, const IcpPlaneScratch* plane) {
+                      hipStream_t s, const KnnScratch* grid, long long total_tgt, const IcpPlaneScratch* plane,
+                      const IcpColorTerms* color) {
   hipError_t e = hipMemsetAsync(ws.key, 0xff, (size_t)total_src * 8, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_icp_init, dim3((B + kThreads - 1) / kThreads), dim3(kThreads), 0, s, init, B, ws.T, ws.prev, ws.done);
@@ -783,7 +875,14 @@ hipError_t launch_icp(const float* src, const int* src_off, const float* tgt, co
     else
       hipLaunchKernelGGL(k_icp_nn, dim3((unsigned)wg, Y), dim3(kThreads), 0, s, src, src_off, tgt, tgt_off, stiles, ws.T, ws.done,
                          ws.key);
-    if (plane) {
+    if (plane && color) {
+      hipLaunchKernelGGL(k_icp_color_partials, dim3((unsigned)plane->plan.blocks), dim3(kThreads), 0, s, src, src_off, tgt,
+                         plane->normals, tgt_off, color->src_intensity, color->tgt_intensity, color->tgt_gradients,
+                         color->sqrt_geometric, color->sqrt_photometric, plane->plan.parts, tau2, ws.T, ws.done, ws.key, nn,
+                         plane->part);
+      hipLaunchKernelGGL(k_icp_plane_solve, dim3(B), dim3(64), 0, s, src_off, plane->plan.parts, plane->part, k, max_iter,
+                         rel_fitness, rel_rmse, ws.T, ws.prev, ws.done, T_out, fitness, rmse, iterations);
+    } else if (plane) {
       hipLaunchKernelGGL(k_icp_plane_partials, dim3((unsigned)plane->plan.blocks), dim3(kThreads), 0, s, src, src_off, tgt,
                          plane->normals, tgt_off, plane->plan.parts, tau2, ws.T, ws.done, ws.key, nn, plane->part);
       hipLaunchKernelGGL(k_icp_plane_solve, dim3(B), dim3(64), 0, s, src_off, plane->plan.parts, plane->part, k, max_iter,

@@ -4,7 +4,7 @@ GMF_PointDSC/misc/cal_fpfh.py:202-215, datasets/ThreeDMatch.py:104-117).  Kernel
 
 Every stage is batched over ragged clouds given by `offsets` (B + 1 row offsets, a list or an int32 device tensor); a neighbour
 never crosses a cloud boundary.  The search, normals and FPFH make no host synchronisation and can be captured into a graph for
-a fixed row count.  The voxel grids read back one count per call (their output size).  Differences from open3d: INTEGRATION.md,
+a fixed row count; so do the colour gradients of coloured ICP (solvers.py).  The voxel grids read back one count per call (their output size).  Differences from open3d: INTEGRATION.md,
 "Descriptors"."""
 from __future__ import annotations
 
@@ -68,6 +68,45 @@ def estimate_normals_batched(points, offsets, radius, max_nn=30):
     return normals
 
 
+def color_intensity(what, name, colors, rows_shape):
+    """One float32 intensity per row from `colors`: float32 of shape rows_shape + (3,) (colours in 0..1, as
+    `tsdf_fragments_colored` returns them) reduced elementwise to fp32(((r + g) + b) / 3) evaluated in fp64, or of shape
+    rows_shape, taken as the intensity itself.  -> a flat contiguous tensor."""
+    shape = tuple(rows_shape)
+    if not isinstance(colors, torch.Tensor) or colors.dtype != torch.float32 or tuple(colors.shape) not in (shape + (3,), shape):
+        fail(what, f"{name} must be a float32 tensor of shape {shape + (3,)} (colours) or {shape} (intensities), one per row")
+    if tuple(colors.shape) == shape:
+        return colors.reshape(-1).contiguous()
+    c = colors.reshape(-1, 3).double()
+    return (((c[:, 0] + c[:, 1]) + c[:, 2]) / 3.0).float()
+
+
+def color_gradients_batched(points, normals, colors, offsets, radius, max_nn=30):
+    """open3d 0.9's InitializePointCloudForColoredICP(KDTreeSearchParamHybrid(radius, max_nn)) over ragged clouds: the colour
+    gradient of every row in its tangent plane, over the neighbour list of radius_knn_batched.
+
+    points [sum N,3], normals [sum N,3] (used as given: negating any of them changes no output bit), colors [sum N,3] in 0..1
+    (reduced to the intensity fp32(((r + g) + b) / 3), evaluated in fp64) or [sum N] (the intensity itself), all float32.
+    A row whose list holds fewer than 4 entries gets 0.  Otherwise the first entry is skipped, as open3d skips it (the row
+    itself, unless an earlier row coincides with it), and over the others in list order, in fp64: e = v_a - v,
+    d = e - (e . n) n, A = sum d d^T + (count - 1)^2 n n^T, b = sum d (I_a - I); A g = b by 3 x 3 LDL^T without pivoting, where
+    a pivot d_k is accepted when it is finite and d_k > 2^-40 A_kk.  A rejected pivot or a non-finite component gives g = 0
+    (open3d applies whatever ldlt() returns).  -> [sum N,3] float32.  No host synchronisation."""
+    what = "color_gradients_batched"
+    r, m = _radius_and_nn(what, radius, max_nn)
+    n0, _ = _check_cloud(points, offsets, what)
+    if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or tuple(normals.shape) != (n0, 3):
+        fail(what, f"normals must be a float32 [{n0},3] tensor, one row per point")
+    inten = color_intensity(what, "colors", colors, (n0,))
+    P, off, B, n = _prepare(points, offsets, what)
+    same_device(what, points=P, normals=normals, colors=inten)
+    Nn = normals.contiguous()
+    grad = torch.empty((n, 3), device=P.device, dtype=torch.float32)
+    h, st = handle_and_stream(P)
+    h.call("gmf_color_gradients", P.data_ptr(), Nn.data_ptr(), inten.data_ptr(), off.data_ptr(), B, n, r, m, grad.data_ptr(), st)
+    return grad
+
+
 def compute_fpfh_batched(points, normals, offsets, radius, max_nn=100):
     """open3d compute_fpfh_feature(KDTreeSearchParamHybrid(radius, max_nn)) over ragged clouds: the neighbour set of
     radius_knn_batched without the query row; SPFH from the fp64 pair features (phi, alpha, theta), 11 bins each; FPFH = the
@@ -108,6 +147,29 @@ def voxel_down_sample_batched(points, offsets, voxel_size):
     -> (points_down [M,3] float32, offsets_down [B+1] int32 device tensor).  One host synchronisation (M)."""
     pts, off, _ = _voxel(points, offsets, voxel_size, "voxel_down_sample_batched", True)
     return pts, off
+
+
+def voxel_down_sample_colored_batched(points, colors, offsets, voxel_size):
+    """`voxel_down_sample_batched` for clouds with colours: colors [sum N,3] float32.  The points, their order and the offsets
+    are `voxel_down_sample_batched`'s, bit for bit; a voxel's colour is the fp64 mean of its rows' colours in ascending row
+    order, stored as float32 (open3d's AccumulatedPoint).
+    -> (points_down [M,3], colors_down [M,3], offsets_down [B+1] int32 device tensor).  One host synchronisation (M)."""
+    what = "voxel_down_sample_colored_batched"
+    v = positive_finite(what, "voxel_size", voxel_size, rule="> 0 and finite")
+    n0, _ = _check_cloud(points, offsets, what)
+    if not isinstance(colors, torch.Tensor) or colors.dtype != torch.float32 or tuple(colors.shape) != (n0, 3):
+        fail(what, f"colors must be a float32 [{n0},3] tensor, one row per point")
+    same_device(what, points=points, colors=colors)
+    P, off, B, n = _prepare(points, offsets, what)
+    Cc = colors.contiguous()
+    dev = P.device
+    out = torch.empty((2, n, 3), device=dev, dtype=torch.float32)
+    out_off = torch.empty(B + 1, device=dev, dtype=torch.int32)
+    num = ctypes.c_longlong(0)
+    h, st = handle_and_stream(P)
+    h.call("gmf_voxel_down_sample_color", P.data_ptr(), Cc.data_ptr(), off.data_ptr(), B, n, v, out[0].data_ptr(),
+           out[1].data_ptr(), out_off.data_ptr(), ctypes.byref(num), st)
+    return out[0, :num.value], out[1, :num.value], out_off
 
 
 def voxel_select_batched(points, offsets, voxel_size):

@@ -22,11 +22,12 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._args import c_ints, check_offsets, fail, positive_finite, require_device, same_device
+from ._args import c_ints, check_offsets, fail, positive_finite, require_device, same_device, unit_interval
 from ._util import handle_and_stream
 from .common import rigid_transform_3d
-from .features import estimate_normals_batched, voxel_down_sample_batched
-from .solvers import check_estimation, icp_point_to_plane_batched, icp_point_to_point_batched
+from .features import (color_gradients_batched, color_intensity, estimate_normals_batched, voxel_down_sample_batched,
+                       voxel_down_sample_colored_batched)
+from .solvers import check_estimation, icp_colored_batched, icp_point_to_plane_batched, icp_point_to_point_batched
 
 STOP_REASONS = ("max_iteration", "min_right_term", "min_relative_increment", "min_relative_residual_increment", "min_residual",
                 "max_iteration_lm", "pivot")
@@ -315,6 +316,70 @@ def local_refinement_batched(points, cloud_offsets, edge_source, edge_target, in
             k = k1
         if scale == len(max_iter) - 1:
             info = information_matrix_batched(down, doff, src, tgt, T, 1.4 * float(vs))[0]
+    return T, info
+
+
+def colored_refinement_batched(points, colors, cloud_offsets, edge_source, edge_target, init, voxel_size=(0.05, 0.025, 0.0125),
+                               max_iter=(50, 30, 14), lambda_geometric=0.968, memory_budget=1 << 30):
+    """open3d's reconstruction-system refinement of fragment pairs (multi-scale `registration_colored_icp`) for E edges over F
+    shared clouds with a colour per row, laid out like `local_refinement_batched`.
+
+    points [sum N,3] and colors [sum N,3] (float32, colours in 0..1, as `tsdf_fragments_colored` returns them).  At each scale
+    the F clouds are prepared ONCE: `voxel_down_sample_colored_batched`, `estimate_normals_batched` (radius 2 x the voxel size,
+    30 neighbours) and `color_gradients_batched` (radius 2 x 1.4 x the voxel size, 30 neighbours).  Then every edge runs
+    `icp_colored_batched(search="grid")` from the previous scale's pose with max_correspondence_distance 1.4 x the voxel size
+    and open3d's default relative criteria, in chunks whose packed rows stay under `memory_budget` bytes: a packed fp32 row and
+    its nn, a source row's intensity, and a target row's intensity, normal and gradient.  The information matrix is taken at the
+    last scale with 1.4 x that voxel size (`information_matrix_batched`).
+
+    init [E, 4, 4].  Returns transformation [E, 4, 4] float32 and info [E, 6, 6] float64.  Host traffic: the F + 1 offsets of the
+    down-sampled clouds once per scale; nothing per edge."""
+    what = "colored_refinement_batched"
+    off = _check_clouds(points, cloud_offsets, what)
+    F = len(off) - 1
+    src, tgt = _check_edges(edge_source, edge_target, F, what)
+    E = len(src)
+    _check_transformations(init, E, "init", what)
+    if len(voxel_size) != len(max_iter) or not len(max_iter):
+        fail(what, "voxel_size and max_iter must have the same, non-zero length")
+    if not isinstance(colors, torch.Tensor) or colors.dtype != torch.float32 or colors.shape != points.shape:
+        fail(what, f"colors must be a float32 tensor of points' shape {tuple(points.shape)}, one colour per row")
+    lam = unit_interval(what, "lambda_geometric", lambda_geometric)
+    require_device(points, "points", what)
+    require_device(init, "init", what)
+    same_device(what, points=points, colors=colors)
+    dev = points.device
+    T = init.to(torch.float32).contiguous()
+    info = torch.zeros((E, 6, 6), device=dev, dtype=torch.float64)
+    if E == 0:
+        return T, info
+    for scale, (vs, it) in enumerate(zip(voxel_size, max_iter)):
+        tau = 1.4 * float(vs)
+        down, cdown, doff_dev = voxel_down_sample_colored_batched(points, colors, off, float(vs))
+        doff = doff_dev.tolist()
+        normals = estimate_normals_batched(down, doff, 2.0 * float(vs), 30)
+        inten = color_intensity(what, "colors", cdown, cdown.shape[:1])
+        grads = color_gradients_batched(down, normals, inten, doff, 2.0 * tau, 30)
+        per_row = 3 * 4 + 8                                           # a packed fp32 row and its nn
+        per_src, per_tgt = 4, 4 + 3 * 4 + 3 * 4                       # an intensity; an intensity, a normal and a gradient
+        k = 0
+        while k < E:
+            used, k1 = 0, k                                           # (used: the chunk's bytes so far)
+            while k1 < E:
+                n_src, n_tgt = doff[src[k1] + 1] - doff[src[k1]], doff[tgt[k1] + 1] - doff[tgt[k1]]
+                need = (n_src + n_tgt) * per_row + n_src * per_src + n_tgt * per_tgt
+                if k1 > k and used + need > memory_budget:
+                    break
+                used += need
+                k1 += 1
+            si, soff = _gather_index(doff, src[k:k1], dev)
+            ti, toff = _gather_index(doff, tgt[k:k1], dev)
+            Tk = icp_colored_batched(down[si], down[ti], inten[si], inten[ti], normals[ti], T[k:k1].contiguous(), tau, soff, toff,
+                                     max_iteration=int(it), search="grid", lambda_geometric=lam, target_gradients=grads[ti])[0]
+            T = torch.cat([T[:k], Tk, T[k1:]])
+            k = k1
+        if scale == len(max_iter) - 1:
+            info = information_matrix_batched(down, doff, src, tgt, T, tau)[0]
     return T, info
 
 

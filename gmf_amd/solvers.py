@@ -1,4 +1,4 @@
-"""Correspondence RANSAC, feature-matching RANSAC and point-to-point and point-to-plane ICP on the device: the solvers the reference's evaluation scripts run after the network
+"""Correspondence RANSAC, feature-matching RANSAC and point-to-point, point-to-plane and coloured ICP on the device: the solvers the reference's evaluation scripts run after the network
 through open3d 0.9 / 0.10 on the CPU (GMF_PointDSC/evaluation/test_3DMatch.py:76-96, benchmark_utils.py:40-56;
 GMF_DeepGlobalRegistration/*/core/deep_global_registration.py:26-85, 256-276, 385-405).  Kernels: csrc/solver_kernels.hip.
 
@@ -14,8 +14,9 @@ import torch
 
 from . import _lib
 from ._args import (check_offsets, check_rows, device_offsets, fail, int_in_range, positive_finite, require_device, same_device,
-                    uniform_offsets)
+                    uniform_offsets, unit_interval)
 from ._util import handle_and_stream
+from .features import color_gradients_batched, color_intensity
 
 RegistrationResult = collections.namedtuple("RegistrationResult", "transformation correspondence_set fitness inlier_rmse")
 
@@ -114,9 +115,34 @@ def icp_point_to_plane_batched(source, target, target_normals, init, max_corresp
                         source_offsets, target_offsets, max_iteration, relative_fitness, relative_rmse, search, plane=True)
 
 
+def icp_colored_batched(source, target, source_colors, target_colors, target_normals, init, max_correspondence_distance,
+                        source_offsets=None, target_offsets=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
+                        search="brute", lambda_geometric=0.968, target_gradients=None):
+    """Coloured ICP over B pairs (open3d 0.9's registration_colored_icp; Park, Zhou, Koltun, ICCV 2017).
+
+    The arguments of `icp_point_to_plane_batched`, and: source_colors and target_colors, float32 of the points' shape (colours in
+    0..1, reduced to the intensity fp32(((r + g) + b) / 3) evaluated in fp64) or of their leading shape (the intensity itself);
+    lambda_geometric in [0, 1]; target_gradients, float32 of target's shape: the targets' colour gradients, by default
+    `color_gradients_batched` of every pair's target with radius 2 x max_correspondence_distance and 30 neighbours (open3d's
+    choice).  C, nn, fitness, inlier_rmse (Euclidean), the loop, the stopping rule, the solve and the sum tree are the
+    point-to-plane form's; the sums run over the rows of C whose normal, gradient and two intensities are finite.  With p the
+    transformed source row, q its target, n and g the target's normal and gradient, I_s and I_t the intensities, in fp64:
+    r_G = (p - q) . n, J_G = [p x n ; n], u = (p - q) - r_G n, r_I = I_s - (g . u + I_t), m = -(g - (g . n) n),
+    J_I = [p x m ; m]; A = sum lambda J_G J_G^T + (1 - lambda) J_I J_I^T, b = sum lambda J_G r_G + (1 - lambda) J_I r_I.
+    Negating normals changes no output bit; a pair's bits do not depend on the batch or on the search.
+    tests/colored_icp_reference.py restates all of it in float64.
+
+    Returns T [B,4,4] f32, fitness [B], inlier_rmse [B], iterations [B] int32 and nn (int64, source's leading shape), as the
+    other two forms do.  No host synchronisation; the call can be captured into a graph."""
+    return _icp_batched("icp_colored_batched", source, target, target_normals, init, max_correspondence_distance, source_offsets,
+                        target_offsets, max_iteration, relative_fitness, relative_rmse, search, plane=True,
+                        color=(source_colors, target_colors, lambda_geometric, target_gradients))
+
+
 def _icp_batched(what, source, target, normals, init, max_correspondence_distance, source_offsets, target_offsets, max_iteration,
-                 relative_fitness, relative_rmse, search, plane=False):
-    """The argument checks, the outputs and the call of both ICP forms (plane: target normals and gmf_icp_point_to_plane)."""
+                 relative_fitness, relative_rmse, search, plane=False, color=None):
+    """The argument checks, the outputs and the call of the three ICP forms (plane: target normals and gmf_icp_point_to_plane;
+    color, with plane: (source_colors, target_colors, lambda_geometric, target_gradients) and gmf_icp_colored)."""
     if not isinstance(search, str) or search not in _ICP_SEARCH:
         fail(what, f'search must be "brute" or "grid" (got {search!r})')
     if (source_offsets is None) != (target_offsets is None):
@@ -147,9 +173,19 @@ def _icp_batched(what, source, target, normals, init, max_correspondence_distanc
         toff = check_offsets(what, "target_offsets", target_offsets, nt_rows)
         if isinstance(soff, list) and isinstance(toff, list) and len(soff) != len(toff):
             fail(what, "source_offsets and target_offsets must describe the same number of pairs")
+    if color is not None:
+        Is = color_intensity(what, "source_colors", color[0], source.shape[:-1])
+        It = color_intensity(what, "target_colors", color[1], target.shape[:-1])
+        lam = unit_interval(what, "lambda_geometric", color[2])
+        G = color[3]
+        if G is not None and (not isinstance(G, torch.Tensor) or G.dtype != torch.float32 or G.shape != target.shape):
+            fail(what, f"target_gradients must be None or a float32 tensor of target's shape {tuple(target.shape)}, one gradient "
+                       "per target row")
     for x, name in ((source, "source"), (target, "target"), (init, "init")):
         require_device(x, name, what)
     same_device(what, source=source, target=target, init=init)
+    if color is not None:
+        same_device(what, source=source, source_colors=Is, target_colors=It, target_gradients=G)
     dev = source.device
     dso, max_s = device_offsets(soff, ns_rows, dev, what, checked=True)
     dto, max_t = device_offsets(toff, nt_rows, dev, what, checked=True)
@@ -168,7 +204,13 @@ def _icp_batched(what, source, target, normals, init, max_correspondence_distanc
     h, st = handle_and_stream(S)
     args = (S.data_ptr(), dso.data_ptr(), Q.data_ptr(), dto.data_ptr(), B, ns_rows, max_s, max_t, T0.data_ptr(), tau, it, rf, rr,
             T.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(), iters.data_ptr(), nn.data_ptr())
-    if plane:
+    if color is not None:
+        Nn = normals.reshape(-1, 3).contiguous()
+        if G is None:
+            G = color_gradients_batched(Q, Nn, It, dto, 2.0 * tau, 30)
+        h.call("gmf_icp_colored", *args[:3], Nn.data_ptr(), *args[3:], nt_rows, _ICP_SEARCH[search], Is.data_ptr(), It.data_ptr(),
+               G.reshape(-1, 3).contiguous().data_ptr(), lam, st)
+    elif plane:
         Nn = normals.reshape(-1, 3).contiguous()
         h.call("gmf_icp_point_to_plane", *args[:3], Nn.data_ptr(), *args[3:], nt_rows, _ICP_SEARCH[search], st)
     elif search == "brute":
@@ -391,6 +433,42 @@ def registration_icp(source, target, max_correspondence_distance, init=None, max
         T, fit, rmse, _, nn = icp_point_to_plane_batched(S[None], Q[None], Nn[None], T0[None], max_correspondence_distance, **crit)
     else:
         T, fit, rmse, _, nn = icp_point_to_point_batched(S[None], Q[None], T0[None], max_correspondence_distance, **crit)
+    nn = nn[0]
+    info = torch.stack([fit[0], rmse[0], (nn >= 0).sum().float()]).cpu().tolist()   # the one synchronisation
+    rows = torch.nonzero_static(nn >= 0, size=int(info[2])).view(-1)
+    return RegistrationResult(T[0], torch.stack([rows, nn[rows]], 1), info[0], info[1])
+
+
+def registration_colored_icp(source, target, source_colors, target_colors, target_normals, max_correspondence_distance, init=None,
+                             lambda_geometric=0.968, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, search="brute"):
+    """open3d.registration.registration_colored_icp (0.9): source [Ns,3], target [Nt,3], source_colors [Ns,3] or [Ns],
+    target_colors [Nt,3] or [Nt], target_normals [Nt,3] (tensors or numpy; open3d reads the colours and the normals from the
+    clouds), init [4,4] (default identity); the rest as in icp_colored_batched, which computes the targets' colour gradients.
+    -> RegistrationResult(transformation [4,4] f32 on the device, correspondence_set [K,2] int64 on the device (source row,
+    nearest target row) of the final C, fitness, inlier_rmse (Euclidean))."""
+    what = "registration_colored_icp"
+    if not isinstance(search, str) or search not in _ICP_SEARCH:
+        fail(what, f'search must be "brute" or "grid" (got {search!r})')
+    for x, name in ((source_colors, "source_colors"), (target_colors, "target_colors"), (target_normals, "target_normals")):
+        if not isinstance(x, (torch.Tensor, np.ndarray)):
+            fail(what, f"{name} must be a tensor or a NumPy array")
+    unit_interval(what, "lambda_geometric", lambda_geometric)
+    dev = _device_of(source, target, init)
+    require_device(dev, "the points", what)
+    S = _on_device(source, dev, torch.float32)
+    Q = _on_device(target, dev, torch.float32)
+    Cs, Ct, Nn = (_on_device(x, dev, torch.float32) for x in (source_colors, target_colors, target_normals))
+    T0 = torch.eye(4, device=dev) if init is None else _on_device(init, dev, torch.float32)
+    if T0.shape != (4, 4):
+        fail(what, f"init must be [4,4] (got {tuple(T0.shape)})")
+    if Nn.shape != Q.shape:
+        fail(what, f"target_normals must be [Nt,3], one normal per target row (got {tuple(Nn.shape)} for {tuple(Q.shape)})")
+    for c, x, name in ((Cs, S, "source"), (Ct, Q, "target")):
+        if c.shape != x.shape and c.shape != x.shape[:1]:
+            fail(what, f"{name}_colors must be [N,3] or [N], one per {name} row (got {tuple(c.shape)} for {tuple(x.shape)})")
+    T, fit, rmse, _, nn = icp_colored_batched(S[None], Q[None], Cs[None], Ct[None], Nn[None], T0[None], max_correspondence_distance,
+                                              max_iteration=max_iteration, relative_fitness=relative_fitness,
+                                              relative_rmse=relative_rmse, search=search, lambda_geometric=lambda_geometric)
     nn = nn[0]
     info = torch.stack([fit[0], rmse[0], (nn >= 0).sum().float()]).cpu().tolist()   # the one synchronisation
     rows = torch.nonzero_static(nn >= 0, size=int(info[2])).view(-1)

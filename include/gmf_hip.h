@@ -45,7 +45,8 @@ enum {
 #define GMF_ABI_VERSION 5   /* 5: gmf_encoder_weights gained `pv_guard` (a caller that fills the struct itself must be rebuilt; one that uses
                              * gmf_encoder_pack_weights keeps working); "pv_fp8" takes 0 / 1 / 2.  gmf_icp_point_to_point_ex and
                              * gmf_ransac_feature_matching, then gmf_spectral_matching, then gmf_max_clique and gmf_pmc_graph, then gmf_tsdf_allocate, gmf_tsdf_integrate and gmf_tsdf_extract, then gmf_rgbd_pyramids, gmf_rgbd_correspondences and
-                             * gmf_rgbd_odometry, then gmf_tsdf_integrate_color and gmf_tsdf_extract_color, then gmf_icp_point_to_plane, then gmf_tsdf_extract_mesh joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
+                             * gmf_rgbd_odometry, then gmf_tsdf_integrate_color and gmf_tsdf_extract_color, then gmf_icp_point_to_plane, then gmf_tsdf_extract_mesh, then gmf_color_gradients,
+                             * gmf_icp_colored and gmf_voxel_down_sample_color joined under 5: added entry points, no existing signature or struct changed.  4: + gmf_get_tuning; the
                              * pose head / pick_seeds take any N */
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
@@ -614,6 +615,23 @@ int gmf_icp_point_to_plane(gmf_handle* h, const float* src, const int* src_offse
                            float* inlier_rmse, int* iterations, long long* nn, long long total_tgt, int search,
                            gmf_stream_t stream);
 
+/* registration_colored_icp (open3d 0.9; Park, Zhou, Koltun, ICCV 2017) over B ragged pairs [joined under ABI 5: an added entry
+ * point].  gmf_icp_point_to_plane's arguments, then src_intensity [total_src] and tgt_intensity [total_tgt] (float32, one per
+ * row), tgt_gradients [total_tgt,3] (float32: gmf_color_gradients of the targets) and lambda_geometric in [0, 1].  C, nn,
+ * fitness, inlier_rmse (Euclidean), the loop, its stopping rule, the solve and the sum tree are gmf_icp_point_to_plane's.  The
+ * sums of A and b run over the rows of C whose normal, gradient and two intensities are finite: with p the transformed source
+ * row, q its target, n and g the target's normal and gradient, r_G = (p - q) . n, J_G = [p x n ; n], u = (p - q) - r_G n,
+ * r_I = I_s - (g . u + I_t), m = -(g - (g . n) n), J_I = [p x m ; m] in fp64,
+ * A = sum lambda J_G J_G^T + (1 - lambda) J_I J_I^T, b = sum lambda J_G r_G + (1 - lambda) J_I r_I (each term scaled by the
+ * square root of its weight, taken on the host in double).  Negating normals changes no output bit; a pair's bits do not
+ * depend on the batch, on max_src or on the search.  3 max_iter + 5 launches (search 1: four more); no host synchronisation;
+ * graph-capturable. */
+int gmf_icp_colored(gmf_handle* h, const float* src, const int* src_offsets, const float* tgt, const float* tgt_normals,
+                    const int* tgt_offsets, int B, long long total_src, int max_src, int max_tgt, const float* init, float tau,
+                    int max_iter, double rel_fitness, double rel_rmse, float* T_out, float* fitness, float* inlier_rmse,
+                    int* iterations, long long* nn, long long total_tgt, int search, const float* src_intensity,
+                    const float* tgt_intensity, const float* tgt_gradients, double lambda_geometric, gmf_stream_t stream);
+
 /* registration_ransac_based_on_feature_matching (GMF_DeepGlobalRegistration/.../core/deep_global_registration.py:26-54) over B
  * ragged pairs: src [total_src,3] with src_offsets [B+1], tgt [total_tgt,3] with tgt_offsets [B+1] (device int32; a pair may have
  * no targets), nn [total_src] int64: the feature-space nearest target row of every source row, numbered within the pair.
@@ -867,6 +885,17 @@ int gmf_radius_knn(gmf_handle* h, const float* pts, const int* offsets, int B, l
 int gmf_estimate_normals(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double radius,
                          int max_nn, float* normals, gmf_stream_t stream);
 
+/* open3d 0.9's InitializePointCloudForColoredICP(KDTreeSearchParamHybrid(radius, max_nn)) [joined under ABI 5: an added entry
+ * point]: the colour gradient of every row over the neighbour list of gmf_radius_knn.  normals [total_rows,3] float32, used as
+ * given (negating any of them changes no output bit); intensity [total_rows] float32, one per row.  A row with fewer than 4
+ * list entries gets 0.  Otherwise the first entry is skipped (the query row, unless an earlier row coincides with it) and over
+ * the others in list order, in fp64 from the fp32 inputs: e = v_a - v, d = e - (e . n) n, A = sum d d^T + (count - 1)^2 n n^T,
+ * b = sum d (I_a - I); A g = b by 3 x 3 LDL^T without pivoting, a pivot d_k being accepted when it is finite and
+ * d_k > 2^-40 A_kk.  A rejected pivot or a non-finite component of g gives g = 0 (open3d applies whatever ldlt() returns).
+ * gradients [total_rows,3] float32.  Fixed summation order; no host synchronisation. */
+int gmf_color_gradients(gmf_handle* h, const float* pts, const float* normals, const float* intensity, const int* offsets, int B,
+                        long long total_rows, double radius, int max_nn, float* gradients, gmf_stream_t stream);
+
 /* open3d compute_fpfh_feature(KDTreeSearchParamHybrid(radius, max_nn)): the neighbour set of gmf_radius_knn, the query excluded
  * by index; SPFH from the fp64 pair features (11 bins per angle), FPFH = the SPFH of the neighbours weighted by 1 / d^2, each
  * 11-bin block renormalised to 100, plus the row's own SPFH.  features [total_rows,33] float32 (row-major; open3d's is
@@ -881,6 +910,14 @@ int gmf_compute_fpfh(gmf_handle* h, const float* pts, const float* normals, cons
  * a coordinate is not finite. */
 int gmf_voxel_down_sample(gmf_handle* h, const float* pts, const int* offsets, int B, long long total_rows, double voxel,
                           float* out_pts, int* out_offsets, long long* num_out, gmf_stream_t stream);
+
+/* gmf_voxel_down_sample for a cloud with colours [joined under ABI 5: an added entry point]: colors [total_rows,3] float32.
+ * out_pts, their order, out_offsets, *num_out and the errors are gmf_voxel_down_sample's, bit for bit; out_colors
+ * [<= total_rows,3] is the fp64 mean of each voxel's colours over the same rows in ascending row order, stored as float32
+ * (open3d's AccumulatedPoint). */
+int gmf_voxel_down_sample_color(gmf_handle* h, const float* pts, const float* colors, const int* offsets, int B,
+                                long long total_rows, double voxel, float* out_pts, float* out_colors, int* out_offsets,
+                                long long* num_out, gmf_stream_t stream);
 
 /* MinkowskiEngine sparse_quantize(pts / voxel, return_index=True) as DGR's preprocess calls it: the voxel floor(p / voxel),
  * out_idx [<= total_rows] int32 the smallest row (within its cloud) of each voxel, ascending per cloud.  out_offsets, num_out

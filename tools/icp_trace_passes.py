@@ -5,7 +5,8 @@ the trace (*_kernel_trace.csv), splits it into calls at k_icp_init, keeps the ca
 max_iteration = 10: every pass runs) and prints medians over passes 0..9: the search kernel, k_icp_step, the last step (pass
 10 stops before the Umeyama update) and, for the grid, the sum of launch_grid_build's four kernels.
 A trace of `tools/time_solvers.py --plane-shape SHAPE` also holds point-to-plane calls (k_icp_plane_partials, k_icp_plane_solve
-in place of k_icp_step); they get a line of their own.
+in place of k_icp_step); they get a line of their own.  So do the coloured calls of `--colored-shape SHAPE` (k_icp_color_partials
+in the place of k_icp_plane_partials), with the medians of k_knn_search and k_color_gradient over the whole trace beside them.
 Usage: python tools/icp_trace_passes.py TRACE.csv [TRACE.csv ...]"""
 import csv
 import statistics as st
@@ -18,7 +19,7 @@ def passes(path):
     for r in rows:
         n, dur = r["Kernel_Name"], (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
         if "k_icp_init" in n:
-            cur = {"nn": [], "step": [], "build": [], "grid": False, "partials": [], "solve": []}
+            cur = {"nn": [], "step": [], "build": [], "grid": False, "partials": [], "solve": [], "color": []}
             calls.append(cur)
         elif cur is None:
             continue
@@ -31,6 +32,8 @@ def passes(path):
             cur["step"].append(dur)
         elif "k_icp_plane_partials" in n:
             cur["partials"].append(dur)
+        elif "k_icp_color_partials" in n:
+            cur["color"].append(dur)
         elif "k_icp_plane_solve" in n:
             cur["solve"].append(dur)
         elif "k_grid_count" in n or "k_grid_scatter" in n or "rocprim" in n:
@@ -48,13 +51,18 @@ def passes(path):
         if build:
             line += f", build kernels {st.median(build):.1f} us (median of {len(build)} calls)"
         print(line)
-    p11 = [c for c in calls if len(c["nn"]) == 11 and len(c["partials"]) == 11]
-    if p11:
-        def med(k):
-            x = [v for c in p11 for v in c[k][:10]]
-            return f"{st.median(x):.1f} [{min(x):.1f}, {max(x):.1f}] us"
-        print(f"{path}: point-to-plane {len(p11)} calls; search {med('nn')}, k_icp_plane_partials {med('partials')}, "
-              f"k_icp_plane_solve {med('solve')}")
+    for key, what in (("partials", "point-to-plane"), ("color", "coloured")):
+        p11 = [c for c in calls if len(c["nn"]) == 11 and len(c[key]) == 11]
+        if p11:
+            def med(k):
+                x = [v for c in p11 for v in c[k][:10]]
+                return f"{st.median(x):.1f} [{min(x):.1f}, {max(x):.1f}] us"
+            print(f"{path}: {what} {len(p11)} calls; search {med('nn')}, k_icp_{'plane' if key == 'partials' else 'color'}_partials "
+                  f"{med(key)}, k_icp_plane_solve {med('solve')}")
+    for name in ("k_knn_search", "k_color_gradient"):
+        x = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if name in r["Kernel_Name"]]
+        if x:
+            print(f"{path}: {name} {len(x)} launches; {st.median(x):.1f} [{min(x):.1f}, {max(x):.1f}] us")
 
 
 if __name__ == "__main__":

@@ -22,6 +22,13 @@
                     criteria (the two estimators run different numbers of passes), then t0 and t10 as above: one pass is the
                     same search and k_icp_step in one column, k_icp_plane_partials + k_icp_plane_solve in the other, so the
                     difference of the columns is the difference of the steps (--plane-shape runs this block alone).
+  ICP coloured      icp_point_to_plane_batched against icp_colored_batched on the "ICP search" shapes, both with search="grid",
+                    alternated call by call; normals as above, intensities from a smooth field, the targets' colour gradients
+                    computed outside the timed region and passed.  Whole calls, then t0 and t10 as above: one pass differs by
+                    k_icp_color_partials against k_icp_plane_partials alone.  Beside them radius_knn_batched and
+                    color_gradients_batched (the same search and k_color_gradient) at radius 2 tau, 30 neighbours, and the
+                    10-pass call that computes its gradients itself (--colored-shape runs this block alone; under
+                    rocprofv3 --kernel-trace --stats it gives the kernel times).
   feature-matching RANSAC   DGR's call: ransac_n = 4, the distance checker and tau at 2 voxels (0.10), 80 000 proposals, 1000
                     validations; clouds of 10k / 10k and 50k / 50k points (40 % of the feature matches right, the others random)
                     and keypoints 5000 / 5000.  The whole call with search="grid", and search="brute" beside it where the
@@ -141,6 +148,46 @@ def icp_plane_rows(report, repeats, dev, keys=ICP_SHAPES):
                f"k_icp_plane_solve; the steps differ by {pb - pa:.1f})")
 
 
+def smooth_intensity(x):
+    """A smooth intensity in 0.15 .. 0.85 at the rows of x [N,3] (a tensor)."""
+    return (0.5 + 0.2 * torch.sin(3 * x[:, 0] + 0.5) * torch.cos(2 * x[:, 1]) + 0.15 * torch.sin(2.5 * x[:, 2] + 1.7 * x[:, 0] - 1.1 * x[:, 1])).float()
+
+
+def icp_colored_rows(report, repeats, dev, keys=ICP_SHAPES):
+    """Point-to-plane against coloured ICP, and the colour gradients beside their search (the module docstring's "ICP coloured")."""
+    report("ICP coloured: point-to-plane | coloured (gradients passed), search=\"grid\", alternated; us, median")
+    for name, s, q, T0, tau in (icp_shape(k) for k in keys):
+        s, q, T0 = s.to(dev), q.to(dev), T0.to(dev)
+        off = [0, q.shape[1]]
+        n = gmf_amd.estimate_normals_batched(q[0], off, 2 * tau, 30)
+        it_ = smooth_intensity(q[0])
+        is_ = smooth_intensity(s[0] @ T0[0, :3, :3].T + T0[0, :3, 3])
+        g = gmf_amd.color_gradients_batched(q[0], n, it_, off, 2 * tau, 30)
+
+        def call(colored, **kw):
+            if colored:
+                return lambda: gmf_amd.icp_colored_batched(s, q, is_[None], it_[None], n[None], T0, tau, search="grid",
+                                                           target_gradients=g[None], **kw)
+            return lambda: gmf_amd.icp_point_to_plane_batched(s, q, n[None], T0, tau, search="grid", **kw)
+
+        its = [int(call(k)()[3][0]) for k in (False, True)]
+        every = dict(relative_fitness=0.0, relative_rmse=0.0)
+        fns = [call(k, **kw) for kw in ({}, dict(max_iteration=0, **every), dict(max_iteration=10, **every)) for k in (False, True)]
+        fns += [lambda: gmf_amd.radius_knn_batched(q[0], off, 2 * tau, 30),
+                lambda: gmf_amd.color_gradients_batched(q[0], n, it_, off, 2 * tau, 30),
+                lambda: gmf_amd.icp_colored_batched(s, q, is_[None], it_[None], n[None], T0, tau, search="grid",
+                                                    max_iteration=10, **every)]
+        (wa, wb, a0, b0, a10, b10, knn, grad, c10) = timed_alternating(fns, repeats)
+        pa, pb = (a10 - a0) / 10, (b10 - b0) / 10
+        report(f"  {name}: {its[0]} | {its[1]} passes at the default criteria")
+        report(f"    whole call        {wa:9.1f} | {wb:9.1f}")
+        report(f"    max_iteration=0   {a0:9.1f} | {b0:9.1f}   (init, the grid build, one search, one evaluation)")
+        report(f"    max_iteration=10  {a10:9.1f} | {b10:9.1f}   (equal pass counts; gradients computed inside: {c10:.1f})")
+        report(f"    one pass          {pa:9.1f} | {pb:9.1f}   (search + k_icp_plane_partials | k_icp_color_partials + "
+               f"k_icp_plane_solve; the steps differ by {pb - pa:.1f})")
+        report(f"    radius search (2 tau, 30) {knn:9.1f}; color_gradients_batched (the search and k_color_gradient) {grad:9.1f}")
+
+
 def icp_crossover_rows(report, repeats, dev):
     """Whole calls at small keypoint pairs (tau = 0.10, default criteria, gt pose as init), to find the size below which the
     grid's four extra launches cost more than its search saves."""
@@ -217,6 +264,8 @@ def main():
     ap.add_argument("--icp-shape", choices=ICP_SHAPES, default=None, help="only the ICP search rows of one shape (for a kernel trace)")
     ap.add_argument("--plane-shape", choices=ICP_SHAPES + ("all",), default=None,
                     help="only the point-to-plane rows of one shape, or of all three")
+    ap.add_argument("--colored-shape", choices=ICP_SHAPES + ("all",), default=None,
+                    help="only the coloured ICP rows of one shape, or of all three")
     ap.add_argument("--fm-shape", choices=FM_SHAPES, default=None,
                     help="only the feature-matching RANSAC rows of one shape (for a kernel trace)")
     a = ap.parse_args()
@@ -234,6 +283,12 @@ def main():
         return
     if a.plane_shape:
         icp_plane_rows(report, a.repeats, dev, ICP_SHAPES if a.plane_shape == "all" else (a.plane_shape,))
+        return
+    if a.colored_shape:
+        icp_colored_rows(report, a.repeats, dev, ICP_SHAPES if a.colored_shape == "all" else (a.colored_shape,))
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
         return
     if a.fm_shape:
         fm_rows(report, a.repeats, dev, (a.fm_shape,))
@@ -279,6 +334,7 @@ def main():
     icp_search_rows(report, a.repeats, dev)
     icp_crossover_rows(report, a.repeats, dev)
     icp_plane_rows(report, a.repeats, dev)
+    icp_colored_rows(report, a.repeats, dev)
     fm_rows(report, a.repeats, dev)
     if a.out:
         with open(a.out, "w") as f:
